@@ -1,13 +1,15 @@
 """The two launchers as a user starts them from a bare shell -- `python bench.py --gpus N` and `python main.py --gpus=N` start
 their own ranks as child processes -- staged on ONE GPU (ELIMREC_SAME_GPU=1: gloo group, collectives through the host). They
 are subprocess runs, kept in a file of their own that sorts last so that a failure here hides no other test; the launcher the
-driver's scaling run depends on (bench.py) goes first. Needs a GPU: `-m gpu`."""
+driver's scaling run depends on (bench.py) goes first, then bench.py's one-GPU run with --dump-outputs and --full. Needs a
+GPU: `-m gpu`."""
 import json
 import os
 import re
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from helpers import ROOT
@@ -57,6 +59,52 @@ def test_bench_launch_survives_a_hang():
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode != 0 and time.time() - t0 < 2 * 25 + 120
     assert "attempt 1" in out.stderr and not any(l.startswith("{") for l in out.stdout.splitlines())
+
+
+def _bench_one_gpu(args, dump_dir=None):
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "ELIMREC_SAME_GPU"):
+        env.pop(k, None)
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2"] + list(args)
+    if dump_dir is not None:
+        cmd += ["--dump-outputs", str(dump_dir)]
+    out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    return json.loads(out.stdout.strip().splitlines()[-1])
+
+
+def _load_dump(d):
+    return {f[:-len(".npy")]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+
+
+def test_bench_plain_run_dump_outputs_and_full(tmp_path):
+    """`bench.py --dump-outputs DIR`: the last timed step's loss and every parameter after its Adam update, float32, within 64 MB,
+    bit-identical from run to run and between a plain run and a --full run (the dump is taken before the --full lines, which
+    train on). A plain run prints the headline without the secondary lines; --full adds them, and they give the same results
+    with and without the dump in front of them."""
+    a = _bench_one_gpu([], tmp_path / "a")
+    b = _bench_one_gpu([], tmp_path / "b")
+    for line in (a, b):
+        assert line["steps"] == 6 and line["warmup"] == 2 and line["unit"] == "triplets/s" and line["higher_is_better"] is True
+        assert line["dtype"] == "f32" and line["ms_per_step"] > 0
+        assert abs(line["value"] - line["config"]["global_batch"] * 1e3 / line["ms_per_step"]) < 1e-6 * line["value"]
+        assert not {"roofline", "plugin_api_loop", "reduced_precision", "cpu_baseline", "eval", "batch_sweep"} & set(line)
+    da, db = _load_dump(tmp_path / "a"), _load_dump(tmp_path / "b")
+    assert da.keys() == db.keys() and len(da) == 19                      # loss + the 18 parameters
+    assert da["embedding_user.weight"].shape == (36656, 64) and da["embedding_item.weight"].shape == (76085, 64)
+    assert all(v.dtype == np.float32 for v in da.values()) and sum(v.nbytes for v in da.values()) <= 64 << 20
+    assert float(da["loss"][0]) == a["config"]["final_loss"]
+    assert all(np.array_equal(da[k], db[k]) for k in da)
+    short = ["--full", "--no-eval", "--no-cpu-baseline", "--no-reference-work", "--no-b-sweep", "--no-projection"]
+    c = _bench_one_gpu(short, tmp_path / "c")
+    d = _bench_one_gpu(short)
+    dc = _load_dump(tmp_path / "c")
+    assert dc.keys() == da.keys() and all(np.array_equal(da[k], dc[k]) for k in da)
+    for line in (c, d):
+        assert line["roofline"]["avg_launch_us"] > 0
+        assert "error" not in line["plugin_api_loop"] and "error" not in line["reduced_precision"], line
+    assert c["plugin_api_loop"]["final_loss"] == d["plugin_api_loop"]["final_loss"]
+    assert c["reduced_precision"]["loss_delta_vs_f32"] == d["reduced_precision"]["loss_delta_vs_f32"]
 
 
 # a "[TIE]\tR\tP\tNDCG" line of a TEST pass (main.py:141-143's format), whatever else shares the pipe's line with it

@@ -1,4 +1,4 @@
-"""Summarise rocprofv3 --pmc passes of `bench.py --steps K --warmup W --no-cpu-baseline` into the JSON bench.py reads
+"""Summarise rocprofv3 --pmc passes of `bench.py --full --steps K --warmup W --no-cpu-baseline` into the JSON bench.py reads
 (profiles/<round>_pmc_traffic.json). Usage:
     python tools/pmc_summary.py --fetch DIR --write DIR --mfma DIR --steps 10 --out profiles/r01_g_pmc_traffic.json
 FETCH_SIZE / WRITE_SIZE are KiB; FETCH_SIZE is doubled as MI355X_MICROARCH.md prescribes for gfx950 (its calibration:
