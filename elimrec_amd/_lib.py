@@ -268,6 +268,9 @@ SIGNATURES = {
     "elimrec_comm_all_to_all": (c_i32, [c_ptr, c_ptr, c_ptr, c_i64, c_ptr]),
     "elimrec_comm_all_to_all_v": (c_i32, [c_ptr, c_ptr, c_ptr, ctypes.POINTER(c_i64), c_ptr]),
     "elimrec_sample_triplets": (c_i32, [c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_u64, c_u64, c_ptr, c_ptr, c_ptr, c_ptr]),
+    "elimrec_sample_negatives": (c_i32, [c_ptr, c_ptr, c_i64, c_i64, c_i32, c_u64, c_ptr, c_ptr]),
+    "elimrec_score_candidates": (c_i32, [c_ptr, c_i64, c_i64, c_i64, c_ptr, c_i32, c_i32, c_i32, c_u32, c_i32, c_i32,
+                                         c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_i64, c_ptr]),
 }
 
 _lib = None

@@ -17,8 +17,20 @@ class BasicModel(nn.Module):
         train = dataset.get_user_train_dict()
         common = dict(metric=config["metric"], group_view=config["group_view"], top_k=config["topks"],
                       batch_size=config["test_batch_size"], num_thread=config["num_thread"])
-        self.valid_evaluator = ProxyEvaluator(dataset, train, dataset.get_user_valid_dict(), None, **common)
-        self.test_evaluator = ProxyEvaluator(dataset, train, dataset.get_user_test_dict(), None, **common)
+        # --eval_candidates=full|sampled (CLI-only, default full): "sampled" ranks each user's test items among the data set's
+        # rec.evaluate.neg sampled negatives (cpp/uni_evaluator.py:132-140); "full" ranks the whole catalogue even when
+        # rec.evaluate.neg > 0, as the reference's driver does (models/BasicModel.py:14-31 passes None)
+        mode = str(config["eval_candidates"]) if "eval_candidates" in config else "full"
+        if mode not in ("full", "sampled"):
+            raise ValueError("eval_candidates must be full or sampled")
+        valid_neg = test_neg = None
+        if mode == "sampled":
+            n_neg = int(config["rec.evaluate.neg"]) if "rec.evaluate.neg" in config else 0
+            if n_neg <= 0:
+                raise ValueError("--eval_candidates=sampled needs rec.evaluate.neg > 0 (negatives per user)")
+            valid_neg, test_neg = dataset.get_user_valid_neg_dict(n_neg), dataset.get_user_test_neg_dict(n_neg)
+        self.valid_evaluator = ProxyEvaluator(dataset, train, dataset.get_user_valid_dict(), valid_neg, **common)
+        self.test_evaluator = ProxyEvaluator(dataset, train, dataset.get_user_test_dict(), test_neg, **common)
         if "tie_order" in config:        # --tie_order=reference (CLI-only): the reference's lists among equal scores too (evaluator.py)
             if str(config["tie_order"]) not in ("id", "reference"):
                 raise ValueError("tie_order must be id or reference")

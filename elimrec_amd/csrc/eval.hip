@@ -1443,6 +1443,169 @@ __global__ __launch_bounds__(256) void rank_metrics_kernel(const int32_t *__rest
     }
 }
 
+// ---- Candidate scoring: given (user, item) lists instead of the whole catalogue (sampled-negative evaluation,
+// cpp/uni_evaluator.py:132-140; re-ranking a retrieval stage's short list). Score of candidate (u, i) = the value the
+// full-catalogue scorer gives at (u, i): the same expressions (fuse_t / fuse2_t / rubi_fast_ / sig_out_ in both math
+// modes), inverse norms from the same squared-norm table, the TIE mean row_sum / I_total as on the item-shard path.
+// Memory-bound row gathers: an item row of Y is (1 + S) d floats (1 KiB at recdim 64 with three heads), scattered over
+// a cache-resident table. A DPP row of 16 lanes owns one candidate at a time: lane l holds float4 columns l, l + 16, ...
+// of every head block, so a block's dot is one row16_sum and every lane of the row ends with all (1 + S) dots. Each row
+// keeps CAND_UNR candidates in flight (4 x (1 + S) x DT dwordx4 loads per lane), the four rows of a wave cover
+// CAND_STEP consecutive columns of one user, and lane u < CAND_UNR of a row runs the epilogue of its row's u-th
+// candidate -- one epilogue pass per 16 candidates. Work items (user, column chunk) are flattened over the grid:
+// a user with a long list does not set the launch's length. Output row b = its candidates' scores in list order, then
+// -inf up to `width` (pad_sequences, post); an id outside [0, I) scores NaN and is not read.
+constexpr int CAND_UNR = 4;
+constexpr int CAND_STEP = 4 * CAND_UNR;
+
+struct CandArgs {
+    const float *Y; int64_t ldy; int64_t U; int64_t I; const int64_t *users; int d; int S;
+    uint32_t head_mask; int fusion_mode; int predict_type;
+    const float *sqn;                        // [N x (1 + S)]
+    const int64_t *ptr; const int32_t *items;  // candidate CSR over the B users
+    const float *row_sum; int64_t I_total;   // TIE: sum_i sigmoid(u . i) over the catalogue
+    float *out; int64_t lds; int64_t width;
+    int64_t chunks;                          // column chunks per user: ceil(width / CAND_STEP)
+    int64_t n_work;                          // B * chunks
+};
+
+// the score of one (user, item) pair from its block dots: dot[0] = u . i, dot[1 + h] = head h's; un / in = the user's /
+// item's block norms (FAST: their reciprocals), as the t16 scorers' epilogue takes them
+template <bool FAST>
+__device__ __forceinline__ float cand_score_(int ptype, int fmode, int S, uint32_t mask, const float *dot, const float *un,
+                                             const float *in, float m) {
+    const float ui = sig_abs_<FAST>(dot[0]);
+    if (ptype == 0) return sig_small_<FAST>(ui);
+    if (FAST && fmode == 0) {
+        float zs[kMaxS];
+#pragma unroll
+        for (int h = 0; h < kMaxS; ++h) zs[h] = h < S ? dot[1 + h] * (un[h] * (in[h] * -1.44269502162933349609375f)) : 0.f;
+        return rubi_fast_(dot[0], zs, S, mask, ptype == 2, m);
+    }
+    float z[kMaxS];
+#pragma unroll
+    for (int h = 0; h < kMaxS; ++h) {
+        const float nn = un[h] * in[h];
+        z[h] = h < S ? (FAST ? dot[1 + h] * nn : dot[1 + h] / nn) : 0.f;
+    }
+    if (ptype == 1) return sig_out_<FAST>(fmode, fuse_t<FAST>(fmode, ui, z, S, mask));
+    float te, nde;
+    fuse2_t<FAST>(fmode, ui, m, z, S, mask, te, nde);
+    return sig_out_<FAST>(fmode, te - nde);
+}
+
+__device__ __forceinline__ float dot4_(const float4 &x, const float4 &y, float acc) {
+    return fmaf(x.w, y.w, fmaf(x.z, y.z, fmaf(x.y, y.y, fmaf(x.x, y.x, acc))));
+}
+
+// NB = 1 + S head blocks; DT = float4 columns per lane and block held in registers (1: recdim <= 64, 2: <= 128), 0: any
+// recdim, the user's row re-read (from cache) per candidate
+template <int NB, int DT, bool FAST>
+__global__ __launch_bounds__(256) void score_cand_kernel(CandArgs a) {
+    const int lane = threadIdx.x & 63, row = lane >> 4, li = lane & 15;
+    const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (w >= a.n_work) return;                                  // wave-uniform
+    const int64_t b = w / a.chunks;
+    const int64_t col0 = (w - b * a.chunks) * CAND_STEP + row * CAND_UNR;
+    const int64_t beg = a.ptr[b], len = a.ptr[b + 1] - beg;
+    const int d = a.d, d4 = d >> 2;
+    const int64_t unode = a.users[b];
+    const float *urow = a.Y + unode * a.ldy;
+    // this row's candidates: item id, -1 = padding (column >= the list's length), -2 = an id outside [0, I)
+    int32_t item[CAND_UNR];
+#pragma unroll
+    for (int u = 0; u < CAND_UNR; ++u) {
+        const int64_t col = col0 + u;
+        const int32_t it = col < len ? a.items[beg + col] : -1;
+        item[u] = col < len ? ((it >= 0 && it < a.I) ? it : -2) : -1;
+    }
+    float acc[CAND_UNR][NB];
+    if (DT > 0) {
+        constexpr int T = DT > 0 ? DT : 1;
+        float4 ur[NB][T];
+#pragma unroll
+        for (int h = 0; h < NB; ++h)
+#pragma unroll
+            for (int t = 0; t < T; ++t) {
+                const int j = li + 16 * t;
+                ur[h][t] = j < d4 ? *reinterpret_cast<const float4 *>(urow + h * d + 4 * j) : make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+        float4 iv[CAND_UNR][NB][T];
+#pragma unroll
+        for (int u = 0; u < CAND_UNR; ++u) {
+            const float *irow = a.Y + (a.U + (item[u] >= 0 ? item[u] : 0)) * a.ldy;
+#pragma unroll
+            for (int h = 0; h < NB; ++h)
+#pragma unroll
+                for (int t = 0; t < T; ++t) {
+                    const int j = li + 16 * t;
+                    iv[u][h][t] = (item[u] >= 0 && j < d4) ? *reinterpret_cast<const float4 *>(irow + h * d + 4 * j)
+                                                            : make_float4(0.f, 0.f, 0.f, 0.f);
+                }
+        }
+#pragma unroll
+        for (int u = 0; u < CAND_UNR; ++u)
+#pragma unroll
+            for (int h = 0; h < NB; ++h) {
+                float s = 0.f;
+#pragma unroll
+                for (int t = 0; t < T; ++t) s = dot4_(ur[h][t], iv[u][h][t], s);
+                acc[u][h] = s;
+            }
+    } else {
+#pragma unroll
+        for (int u = 0; u < CAND_UNR; ++u) {
+            const float *irow = a.Y + (a.U + (item[u] >= 0 ? item[u] : 0)) * a.ldy;
+#pragma unroll
+            for (int h = 0; h < NB; ++h) {
+                float s = 0.f;
+                if (item[u] >= 0)
+                    for (int j = li; j < d4; j += 16)
+                        s = dot4_(*reinterpret_cast<const float4 *>(urow + h * d + 4 * j),
+                                  *reinterpret_cast<const float4 *>(irow + h * d + 4 * j), s);
+                acc[u][h] = s;
+            }
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < CAND_UNR; ++u)
+#pragma unroll
+        for (int h = 0; h < NB; ++h) acc[u][h] = row16_sum(acc[u][h]);      // every lane of the row: all dots of all CAND_UNR
+    // lane u < CAND_UNR of the row: candidate u's epilogue
+    float dot[NB];
+    int32_t it = item[0];
+#pragma unroll
+    for (int h = 0; h < NB; ++h) dot[h] = acc[0][h];
+#pragma unroll
+    for (int u = 1; u < CAND_UNR; ++u)
+        if (li == u) {
+            it = item[u];
+#pragma unroll
+            for (int h = 0; h < NB; ++h) dot[h] = acc[u][h];
+        }
+    const int64_t col = col0 + li;
+    if (li >= CAND_UNR || col >= a.width) return;
+    float out = it == -1 ? -INFINITY : __builtin_nanf("");
+    if (it >= 0) {
+        const int ptype = a.predict_type;
+        const float eps = 1e-12f;
+        float un[kMaxS], in[kMaxS];
+#pragma unroll
+        for (int h = 0; h < kMaxS; ++h) {
+            float nu = 1.f, ni = 1.f;
+            if (h + 1 < NB && ptype != 0) {
+                nu = fmaxf(sqrtf(a.sqn[unode * NB + 1 + h]), eps);
+                ni = fmaxf(sqrtf(a.sqn[(a.U + it) * NB + 1 + h]), eps);
+                if (FAST) { nu = rcp_nr(nu); ni = rcp_nr(ni); }
+            }
+            un[h] = nu; in[h] = ni;
+        }
+        const float m = ptype == 2 ? a.row_sum[b] / (float)a.I_total : 0.f;
+        out = cand_score_<FAST>(ptype, a.fusion_mode, NB - 1, a.head_mask, dot, un, in, m);
+    }
+    a.out[b * a.lds + col] = out;
+}
+
 }  // namespace elimrec
 
 using namespace elimrec;
@@ -2073,5 +2236,53 @@ extern "C" int elimrec_topk_reference_order(const float *h_scores, int64_t n_row
         int32_t *out = h_topk + r * K;
         std::partial_sort_copy(index.begin(), index.end(), out, out + K, [ratings](int x1, int x2) -> bool { return ratings[x1] > ratings[x2]; });
     }
+    return 0;
+}
+
+// Candidate lists instead of the whole catalogue (score_cand_kernel): d_scores [B x width] (leading dimension lds) = row b's
+// candidates' scores in list order, then -inf; TIE needs d_row_sum (elimrec_score_topk_shard phase 1 over the whole catalogue).
+extern "C" int elimrec_score_candidates(const float *d_Y, int64_t ldy, int64_t U, int64_t I, const int64_t *d_users, int B,
+                                        int d, int S, uint32_t head_mask, int fusion_mode, int predict_type,
+                                        const float *d_sqnorm, const int64_t *d_cand_ptr, const int32_t *d_cand_items,
+                                        const float *d_row_sum, int64_t I_total, float *d_scores, int64_t lds, int64_t width,
+                                        void *stream) {
+    ELIMREC_REQUIRE(d_Y && d_users && d_cand_ptr && d_scores, "score_candidates: null pointer");
+    ELIMREC_REQUIRE(d > 0 && d % 4 == 0 && ldy % 4 == 0 && ldy >= (int64_t)(1 + S) * d, "score_candidates: recdim/ldy must be multiples of 4");
+    ELIMREC_REQUIRE(S >= 0 && S < kMaxS, "score_candidates: at most %d single-modal heads", kMaxS - 1);
+    ELIMREC_REQUIRE(fusion_mode >= 0 && fusion_mode <= 2 && predict_type >= 0 && predict_type <= 2,
+                    "score_candidates: bad fusion_mode/predict_type");
+    ELIMREC_REQUIRE(width >= 0 && lds >= width, "score_candidates: need 0 <= width <= lds");
+    ELIMREC_REQUIRE(predict_type == 0 || d_sqnorm, "score_candidates: predict types TE / TIE need the squared-norm table");
+    ELIMREC_REQUIRE(predict_type != 2 || (d_row_sum && I_total > 0), "score_candidates: TIE needs d_row_sum and I_total > 0");
+    if (B <= 0 || width <= 0) return 0;
+    ELIMREC_REQUIRE(d_cand_items, "score_candidates: null candidate items");
+    CandArgs a;
+    a.Y = d_Y; a.ldy = ldy; a.U = U; a.I = I; a.users = d_users; a.d = d; a.S = S; a.head_mask = head_mask;
+    a.fusion_mode = fusion_mode; a.predict_type = predict_type; a.sqn = d_sqnorm; a.ptr = d_cand_ptr; a.items = d_cand_items;
+    a.row_sum = d_row_sum; a.I_total = I_total; a.out = d_scores; a.lds = lds; a.width = width;
+    a.chunks = (width + CAND_STEP - 1) / CAND_STEP;
+    a.n_work = (int64_t)B * a.chunks;
+    const dim3 grid((unsigned)((a.n_work + 3) / 4));
+    hipStream_t s = (hipStream_t)stream;
+    const bool fast = score_math() == 1;
+    const int dt = d <= 64 ? 1 : (d <= 128 ? 2 : 0);
+#define ELIMREC_CAND_LAUNCH(NB, DT)                                                                          \
+    do {                                                                                                   \
+        if (fast) hipLaunchKernelGGL((score_cand_kernel<NB, DT, true>), grid, dim3(256), 0, s, a);         \
+        else hipLaunchKernelGGL((score_cand_kernel<NB, DT, false>), grid, dim3(256), 0, s, a);             \
+    } while (0)
+#define ELIMREC_CAND_NB(NB)                                                                                  \
+    do {                                                                                                   \
+        if (dt == 1) ELIMREC_CAND_LAUNCH(NB, 1);                                                           \
+        else if (dt == 2) ELIMREC_CAND_LAUNCH(NB, 2);                                                      \
+        else ELIMREC_CAND_LAUNCH(NB, 0);                                                                   \
+    } while (0)
+    if (S == 0) ELIMREC_CAND_NB(1);
+    else if (S == 1) ELIMREC_CAND_NB(2);
+    else if (S == 2) ELIMREC_CAND_NB(3);
+    else ELIMREC_CAND_NB(4);
+#undef ELIMREC_CAND_NB
+#undef ELIMREC_CAND_LAUNCH
+    ELIMREC_LAUNCH_CHECK("score_candidates");
     return 0;
 }

@@ -76,6 +76,69 @@ __global__ void sample_triplets_kernel(const int32_t *__restrict__ user_ids, con
     neg[i] = cand;
 }
 
+
+// Distinct negatives per user for sampled-negative evaluation (data/dataset.py:270-288; random_choice.pyx:20-62 with
+// replace=False): n_neg distinct ids uniform over [0, I) minus the user's sorted exclusion list. One wave per user draws
+// RANKS in [0, M), M = I - |exclusion|, 64 at a time (Philox keyed by (seed, user), counter = draw round), keeps those not
+// drawn before -- the accepted ranks in LDS, duplicates within a round resolved in lane order -- and maps rank r to the
+// r-th id not excluded (binary search over e_j - j, non-decreasing for a sorted unique list). Each kept rank is uniform
+// over the ranks not yet kept: the draws are a uniform random n_neg-subset, in draw order.
+constexpr int NEG_MAX = 16000;
+constexpr uint32_t NEG_ROUNDS = 1u << 16;
+
+__global__ __launch_bounds__(64) void sample_negatives_kernel(const int64_t *__restrict__ ptr, const int32_t *__restrict__ excl,
+                                                              int64_t I, int n_neg, uint64_t seed, int32_t *__restrict__ out) {
+    extern __shared__ int32_t drawn[];                 // [n_neg] accepted ranks
+    __shared__ int32_t round_c[64];
+    const int64_t u = blockIdx.x;
+    const int lane = threadIdx.x;
+    const int64_t beg = ptr[u], ne = ptr[u + 1] - beg;
+    const int64_t M = I - ne;
+    int32_t *o = out + u * (int64_t)n_neg;
+    if (M <= n_neg) {                                  // (the host rejects this: "There is not enough integers to be sampled.")
+        for (int k = lane; k < n_neg; k += 64) o[k] = -1;
+        return;
+    }
+    Philox ph;
+    ph.k[0] = (uint32_t)seed; ph.k[1] = (uint32_t)(seed >> 32);
+    ph.c[0] = (uint32_t)u; ph.c[1] = (uint32_t)((uint64_t)u >> 32);
+    int n_acc = 0;
+    for (uint32_t rnd = 0; rnd < NEG_ROUNDS && n_acc < n_neg; ++rnd) {
+        ph.c[2] = rnd; ph.c[3] = (uint32_t)lane;
+        uint32_t r[4];
+        ph.generate(r);
+        const int32_t c = (int32_t)((((uint64_t)r[0] << 32) | r[1]) % (uint64_t)M);
+        round_c[lane] = c;
+        __syncthreads();
+        bool bad = false;
+        for (int k = 0; k < n_acc; ++k) bad |= drawn[k] == c;          // (wave-uniform address: broadcast reads)
+        for (int j = 0; j < lane; ++j) bad |= round_c[j] == c;
+        const uint64_t ok = __ballot(!bad);
+        const int pos = n_acc + __popcll(ok & ((1ull << lane) - 1ull));
+        if (!bad && pos < n_neg) drawn[pos] = c;
+        n_acc = min(n_neg, n_acc + __popcll(ok));
+        __syncthreads();
+    }
+    if (n_acc < n_neg) {        // 2^16 rounds without completing (M barely above n_neg and large): the smallest ranks left
+        if (lane == 0)
+            for (int32_t c = 0; n_acc < n_neg; ++c) {
+                bool in = false;
+                for (int k = 0; k < n_acc; ++k) in |= drawn[k] == c;
+                if (!in) drawn[n_acc++] = c;
+            }
+        __syncthreads();
+    }
+    for (int k = lane; k < n_neg; k += 64) {
+        const int64_t rk = drawn[k];
+        int64_t lo = 0, hi = ne;                       // lo = #{j : excl[j] - j <= rk}
+        while (lo < hi) {
+            const int64_t mid = (lo + hi) >> 1;
+            if ((int64_t)excl[beg + mid] - mid <= rk) lo = mid + 1; else hi = mid;
+        }
+        o[k] = (int32_t)(rk + lo);
+    }
+}
+
 }  // namespace elimrec
 
 using namespace elimrec;
@@ -89,5 +152,17 @@ extern "C" int elimrec_sample_triplets(const int32_t *d_user_ids, const int64_t 
     hipLaunchKernelGGL(sample_triplets_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        d_user_ids, d_ptr, d_items, n_train_users, I, n, seed, epoch, d_users, d_pos, d_neg);
     ELIMREC_LAUNCH_CHECK("sample_triplets");
+    return 0;
+}
+
+extern "C" int elimrec_sample_negatives(const int64_t *d_excl_ptr, const int32_t *d_excl_items, int64_t n_users, int64_t I,
+                                        int n_neg, uint64_t seed, int32_t *d_out, void *stream) {
+    ELIMREC_REQUIRE(d_excl_ptr && d_out, "sample_negatives: null pointer");
+    ELIMREC_REQUIRE(I > 0 && I < (int64_t)INT32_MAX, "sample_negatives: 0 < I < 2^31");
+    ELIMREC_REQUIRE(n_neg > 0 && n_neg <= NEG_MAX, "sample_negatives: 0 < n_neg <= %d", NEG_MAX);
+    if (n_users <= 0) return 0;
+    hipLaunchKernelGGL(sample_negatives_kernel, dim3((unsigned)n_users), dim3(64), (size_t)n_neg * sizeof(int32_t), (hipStream_t)stream,
+                       d_excl_ptr, d_excl_items, I, n_neg, seed, d_out);
+    ELIMREC_LAUNCH_CHECK("sample_negatives");
     return 0;
 }

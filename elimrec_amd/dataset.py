@@ -39,6 +39,57 @@ class _DatasetBase(object):
     def get_user_test_dict(self):
         return csr_to_user_dict(self.test_matrix)
 
+    neg_seed = 2022             # Philox key of the evaluation negatives (the reference's libc rand() stream is not reproducible)
+
+    def get_user_test_neg_dict(self, n_neg=None):
+        """{user: ascending list of n_neg sampled negatives} (data/dataset.py:270-300, 335-345): distinct ids outside the
+        user's train + valid + test items, drawn once, on the first call (csrc/sampler.hip sample_negatives_kernel). None
+        when n_neg (default: the data set's rec.evaluate.neg) is 0."""
+        return self._neg_dict(n_neg)
+
+    def get_user_valid_neg_dict(self, n_neg=None):
+        """The same negatives as get_user_test_neg_dict (the reference's valid and test dicts are one matrix)."""
+        return self._neg_dict(n_neg)
+
+    def _default_neg(self):
+        return 0
+
+    def _neg_dict(self, n_neg):
+        n_neg = self._default_neg() if n_neg is None else int(n_neg)
+        if n_neg <= 0:
+            return None
+        cache = self.__dict__.setdefault("_neg_cache", {})
+        if n_neg not in cache:
+            users, rows = self._load_negatives(n_neg)
+            cache[n_neg] = {int(u): sorted(int(i) for i in r) for u, r in zip(users, rows)}
+        return cache[n_neg]
+
+    def _load_negatives(self, n_neg):
+        return self._draw_negatives(n_neg)
+
+    def exclusion_csr(self):
+        """(indptr int64, indices int32) of every user's train + valid + test items, sorted and unique per row."""
+        m = (self.train_matrix + self.valid_matrix + self.test_matrix).tocsr()
+        m.sum_duplicates()
+        m.sort_indices()
+        return m.indptr.astype(np.int64), m.indices.astype(np.int32)
+
+    def _draw_negatives(self, n_neg):
+        """(users, [users x n_neg] int32) for every user with an interaction, drawn on the GPU (a host check first:
+        "There is not enough integers to be sampled.", util/cython/random_choice.pyx:35-37)."""
+        from . import ops
+        ptr, items = self.exclusion_csr()
+        users = np.nonzero(np.diff(ptr) > 0)[0]
+        ops.check_negative_room(ptr, self.num_items, n_neg)
+        if not torch.cuda.is_available():
+            raise RuntimeError("sampling evaluation negatives runs on the GPU (csrc/sampler.hip); no device is available")
+        dev = torch.device("cuda", torch.cuda.current_device())
+        out = torch.empty(len(ptr) - 1, n_neg, dtype=torch.int32, device=dev)
+        ops.sample_negatives(torch.from_numpy(ptr).to(dev), torch.from_numpy(items).to(dev), self.num_items, n_neg,
+                             self.neg_seed, out)
+        rows = out.cpu().numpy()
+        return users, rows[users]
+
     def get_train_interactions(self):
         """(users, items) of the de-duplicated training interactions (data/dataset.py:347-354)."""
         coo = self.train_matrix.tocoo()
@@ -100,6 +151,8 @@ class SyntheticDataset(_DatasetBase):
     def __init__(self, num_users, num_items, num_interactions, feat_dims=(128, 128, 128), seed=0,
                  name="synthetic", zipf=0.8):
         rs = np.random.RandomState(seed)
+        self.neg_seed = 2022 + int(seed)       # the evaluation negatives, drawn in memory on first use (get_user_test_neg_dict)
+        self.evaluate_neg = 0                  # their default count (the driver sets rec.evaluate.neg)
         U, I = int(num_users), int(num_items)
         p = 1.0 / np.arange(1, I + 1, dtype=np.float64) ** zipf
         p /= p.sum()
@@ -121,6 +174,9 @@ class SyntheticDataset(_DatasetBase):
         g = torch.Generator().manual_seed(seed + 1)
         for name_, dm in zip(names, feat_dims):
             setattr(self, name_, torch.randn(I, int(dm), generator=g, dtype=torch.float32))
+
+    def _default_neg(self):
+        return int(self.evaluate_neg)
 
     def feature_blocks(self, m):
         """The same table as `<m>_feat`, served block by block (a stand-in for a file: the rows are sliced out of the seeded tensor)."""
@@ -162,6 +218,31 @@ class Dataset(_DatasetBase):
         self.train_matrix, self.test_matrix, self.valid_matrix = mats
         if conf["with_item_vat"] if "with_item_vat" in conf else True:
             self._load_features(path, list(self.itemids.keys()))
+
+    def _default_neg(self):
+        return int(self.conf["rec.evaluate.neg"]) if "rec.evaluate.neg" in self.conf else 0
+
+    def neg_file(self, n_neg):
+        """<data.input.path>/_tmp_<name>/<name>_<splitter>_u<user_min>_i<item_min>.neg<N> (data/dataset.py:66-73, 270-275)."""
+        c = self.conf
+        name = self.dataset_name
+        prefix = "%s_%s_u%d_i%d" % (name, c["splitter"], int(c["user_min"]) if "user_min" in c else 0,
+                                    int(c["item_min"]) if "item_min" in c else 0)
+        return os.path.join(c["data.input.path"], "_tmp_" + name, "%s.neg%d" % (prefix, n_neg))
+
+    def _load_negatives(self, n_neg):
+        """The file of the reference's format when it exists (no header; user id then n_neg item ids, remapped ids, separator
+        data.convert.separator), else drawn on the GPU and written in that format (data/dataset.py:270-288)."""
+        import pandas as pd
+        sep = self.conf["data.convert.separator"]
+        fn = self.neg_file(n_neg)
+        if os.path.isfile(fn):
+            table = pd.read_csv(fn, sep=sep, header=None).to_numpy(dtype=np.int64)
+            return table[:, 0], table[:, 1:]
+        users, rows = self._draw_negatives(n_neg)
+        os.makedirs(os.path.dirname(fn), exist_ok=True)
+        np.savetxt(fn, np.concatenate([users[:, None].astype(np.int64), rows.astype(np.int64)], axis=1), fmt="%d", delimiter=sep)
+        return users, rows
 
     def feature_blocks(self, m):
         """`<m>_feat` block by block, without reading the file whole: the .npy files of the generic loader are memory-mapped and

@@ -23,6 +23,11 @@ metric_dict = {"Precision": 1, "Recall": 2, "MAP": 3, "NDCG": 4, "MRR": 5}
 re_metric_dict = {v: k for k, v in metric_dict.items()}
 
 
+class CandidateScoringError(ValueError):
+    """A candidate-list (sampled-negative) evaluation or scoring call this package does not run: item-sharded / lean tables,
+    or a top-K beyond the shortest candidate list."""
+
+
 class UniEvaluator(object):
     def __init__(self, dataset, user_train_dict, user_test_dict, user_neg_test=None, metric=None, top_k=50,
                  batch_size=1024, num_thread=8):
@@ -39,8 +44,8 @@ class UniEvaluator(object):
         for m in metric:
             if m not in metric_dict:
                 raise ValueError("There is not the metric named '%s'!" % metric)
-        if user_neg_test is not None:
-            raise NotImplementedError("sampled-negative evaluation (rec.evaluate.neg > 0) is not on the EliMRec path")
+        if user_neg_test is not None and not isinstance(user_neg_test, dict):
+            raise TypeError("user_neg_test must be a dict or None")
         self.dataset = dataset
         self.user_pos_train = user_train_dict
         self.user_pos_test = user_test_dict
@@ -75,6 +80,14 @@ class UniEvaluator(object):
         self._evaluations = 0
         self.scorer_checked_rows = self.scorer_mismatch_rows = 0
         self.range_violations = 0          # scorer waves that saw a score outside their launch's range invariant, over all passes
+        if user_neg_test is not None:
+            # sampled negatives: every user's list holds its test items and at least n_neg negatives, so K <= n_neg + 1 keeps K real
+            # candidates in every row with a test item; beyond it the reference's zero-filled topk_rank tail (evaluate.h counts
+            # position 0 again) would be reproduced. Decided over the whole dict: the same for any grouping of the users into blocks
+            n_neg = min((len(v) for v in user_neg_test.values()), default=0)
+            if self.max_top > n_neg + 1:
+                raise CandidateScoringError("sampled-negative evaluation ranks 1 test item + %d negatives: top-K %d exceeds "
+                                            "rec.evaluate.neg + 1 = %d" % (n_neg, self.max_top, n_neg + 1))
 
     def _cross_check_scorer(self, model, users, cache_key=None):
         """Top-K of the first `scorer_check_users` users by the default (bf16 x 3) scorer and by the fp32-MFMA scorer, compared ON THE
@@ -187,6 +200,8 @@ class UniEvaluator(object):
         import torch.distributed as dist
         if shard is None and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             shard = (dist.get_rank(), dist.get_world_size())
+        if self.user_neg_test is not None:
+            return self._sampled_metric_rows(model, test_users, shard, cached, reduce)
         n = len(test_users)
         sharded = shard is not None and shard[1] > 1
         if hasattr(model, "_ensure_tables") and getattr(model, "_cache", None) is not None and not sharded:
@@ -220,6 +235,67 @@ class UniEvaluator(object):
             out_of_range = self._range_verdict(model, first=attempt == 0, act=not sharded and getattr(model, "_eval_shard", None) is None)
             if attempt == 1 or not (self._cross_check_verdict(pending) or out_of_range):
                 break
+        if sharded and reduce:
+            dist.all_reduce(all_dev, op=dist.ReduceOp.SUM)
+        return all_dev
+
+    def _sampled_metric_rows(self, model, test_users, shard, cached, reduce):
+        """The reference's candidate branch (cpp/uni_evaluator.py:132-140) on the device: per user block the candidate lists
+        list(user_pos_test[u]) + user_neg_test[u] as CSR, their scores (-inf padded rows, csrc/eval.hip score_cand_kernel), the
+        top-K positions -- tie_order "reference": evaluate.h's partial_sort_copy replayed on the device over the padded rows;
+        "id": (score desc, position asc) -- and the metric curves with truth = positions 0 .. npos - 1. No train-item masking."""
+        import torch.distributed as dist
+        n = len(test_users)
+        sharded = shard is not None and shard[1] > 1
+        if hasattr(model, "_ensure_tables"):
+            model._ensure_tables()
+        if getattr(model, "_eval_shard", None) is not None:
+            raise CandidateScoringError("sampled-negative evaluation needs the whole cached item table on every rank; the tables are "
+                                        "item-sharded (lean / multi-rank evaluation): evaluate with --eval_candidates=full")
+        device = model._require_gpu()
+        lo, hi = (n * shard[0] // shard[1], n * (shard[0] + 1) // shard[1]) if sharded else (0, n)
+        alloc = torch.zeros if sharded else torch.empty
+        all_dev = alloc(n, self.metrics_num * self.max_top, dtype=torch.float32, device=device)
+        K = self.max_top
+        at = lo
+        for k, batch_users in enumerate(DataIterator(test_users[lo:hi], batch_size=self.block_users, shuffle=False, drop_last=False)):
+            key = (str(device), "sampled", k, lo, hi, self.block_users) if cached else None
+            hit = self._dev_cache.get(key) if key is not None else None
+            if hit is None:
+                lists = [list(self.user_pos_test[u]) + list(self.user_neg_test[u]) for u in batch_users]
+                npos = [len(self.user_pos_test[u]) for u in batch_users]
+                lens = np.fromiter((len(x) for x in lists), dtype=np.int64, count=len(lists))
+                ptr = np.zeros(len(lists) + 1, dtype=np.int64)
+                np.cumsum(lens, out=ptr[1:])
+                flat = np.fromiter((i for x in lists for i in x), dtype=np.int32, count=int(ptr[-1]))
+                tptr = np.zeros(len(lists) + 1, dtype=np.int64)
+                np.cumsum(npos, out=tptr[1:])
+                titems = np.concatenate([np.arange(p, dtype=np.int32) for p in npos]) if tptr[-1] else np.zeros(1, dtype=np.int32)
+                width = int(lens.max())
+                users_t = torch.as_tensor(np.asarray(batch_users, dtype=np.int64)).to(device)
+                pos_t = torch.arange(width, dtype=torch.int32, device=device).expand(len(lists), width).contiguous() \
+                    if self.tie_order != "reference" else None
+                hit = (users_t, torch.from_numpy(ptr).to(device), torch.from_numpy(flat).to(device), torch.from_numpy(tptr).to(device),
+                       torch.from_numpy(titems).to(device), width, pos_t)
+                if key is not None:
+                    self._dev_cache[key] = hit
+            users_t, cand_ptr, cand_items, truth_ptr, truth_items, width, pos_t = hit
+            B = users_t.numel()
+            scores = torch.empty(B, width, dtype=torch.float32, device=device)
+            model.predict_candidates_device(users_t, cand_ptr, cand_items, scores)
+            idx = torch.empty(B, K, dtype=torch.int32, device=device)
+            val = torch.empty(B, K, dtype=torch.float32, device=device)
+            if self.tie_order == "reference":
+                ops.topk_reference_order(scores, K, idx, val)
+            else:
+                if pos_t is None:
+                    pos_t = torch.arange(width, dtype=torch.int32, device=device).expand(B, width).contiguous()
+                ops.topk_merge(scores, pos_t, K, idx, val)
+            ops.score_range_check(val, idx, model.predict_type, model.fusion_mode)
+            ops.rank_metrics(idx, truth_ptr, truth_items, self.metrics, all_dev[at:at + B])
+            at += B
+        self._evaluations += 1
+        self._range_verdict(model, first=False, act=not sharded)
         if sharded and reduce:
             dist.all_reduce(all_dev, op=dist.ReduceOp.SUM)
         return all_dev

@@ -31,6 +31,7 @@ from torch.nn import functional as F
 
 from . import _lib, ops
 from .basic_model import BasicModel
+from .evaluator import CandidateScoringError
 from .logger import Logger
 from .plugin import EmbeddingParameter, LazyGradParameter, StepController
 
@@ -1155,17 +1156,68 @@ class EliMRec(BasicModel):
         if top_k:
             idx = torch.empty(B, top_k, dtype=torch.int32, device=dev)
             val = torch.empty(B, top_k, dtype=torch.float32, device=dev)
-        # block norms of the cached tables: computed once per table version, reused by every user block
-        if self._ws.get("sqn_version") != self._table_version:
-            if self._ws.get("sqn") is None:
-                self._ws["sqn"] = torch.empty(self.num_users + I, 1 + self.S, dtype=torch.float32, device=dev)
-            ops.row_sqnorms(self._ws["Y"], self.latent_dim, 1 + self.S, self._ws["sqn"])
-            self._ws["sqn_version"] = self._table_version
+        self._block_sqnorms(dev)
         ops.score_topk(self._ws["Y"], self.num_users, I, users, self.latent_dim, self.S, self._head_mask(),
                        self.fusion_mode, self.predict_type, self._ws["score_ws"], scores=scores, K=top_k,
                        topk_idx=idx, topk_val=val, train_ptr=train_ptr, train_items=train_items, sqnorm=self._ws["sqn"],
                        tie_order=tie_order)
         return idx, val
+
+    def _block_sqnorms(self, dev):
+        """Block norms of the cached tables: computed once per table version, reused by every user block."""
+        if self._ws.get("sqn_version") != self._table_version:
+            if self._ws.get("sqn") is None:
+                self._ws["sqn"] = torch.empty(self.num_users + self.num_items, 1 + self.S, dtype=torch.float32, device=dev)
+            ops.row_sqnorms(self._ws["Y"], self.latent_dim, 1 + self.S, self._ws["sqn"])
+            self._ws["sqn_version"] = self._table_version
+        return self._ws["sqn"]
+
+    @torch.no_grad()
+    def predict_candidates_device(self, user_ids, cand_ptr, cand_items, out):
+        """Device form of predict_candidates: the lists as CSR (cand_ptr int64 [B + 1], cand_items int32, device tensors) ->
+        out [B x width] (float32, rows contiguous) = each user's candidate scores in list order, then -inf (csrc/eval.hip
+        score_cand_kernel). Score of candidate (u, i) = predict([u])[0, i]; TIE's catalogue mean comes from the scorer's pass 1
+        over the whole catalogue (one launch per call)."""
+        dev = self._require_gpu()
+        self._plugin.realise_forward()
+        if self._ws is None or self._cache is None:
+            raise RuntimeError("predict_candidates() needs the tables cached by a training forward (call bpr_loss or compute first)")
+        self._ensure_tables()
+        if self.__dict__.get("_eval_shard") is not None:
+            raise CandidateScoringError("candidate scoring needs the whole cached item table on this rank; the tables are item-sharded "
+                                        "(lean / multi-rank evaluation): score the full catalogue instead")
+        users = torch.as_tensor(user_ids, device=dev).long().contiguous()
+        B, I = users.numel(), self.num_items
+        sqn = self._block_sqnorms(dev)
+        row_sum = None
+        if ops.PREDICT_TYPES.get(self.predict_type, 0) == 2 and B:
+            # pass 1 only, the whole catalogue as the one shard: sum_i sigmoid(u . i) per user
+            need = ops.score_workspace(B, self.num_users, I, self.S, 1, topk_only=True, d=self.latent_dim)
+            if self._ws.get("score_ws") is None or self._ws["score_ws"].numel() < need:
+                self._ws["score_ws"] = torch.empty(need, dtype=torch.uint8, device=dev)
+            row_sum = torch.empty(B, dtype=torch.float32, device=dev)
+            ops.score_topk_shard(self._ws["Y"], self.num_users, I, users, self.latent_dim, self.S, self._head_mask(), self.fusion_mode,
+                                 self.predict_type, self._ws["score_ws"], 1, row_sum, I, 0, sqnorm=sqn)
+        ops.score_candidates(self._ws["Y"], self.num_users, I, users, self.latent_dim, self.S, self._head_mask(), self.fusion_mode,
+                             self.predict_type, cand_ptr, cand_items, out, sqnorm=sqn, row_sum=row_sum, I_total=I)
+        return out
+
+    def predict_candidates(self, user_ids, candidate_items):
+        """Scores of given candidate lists: CPU fp32 [len(user_ids) x longest list], row b = predict([u_b])[0, candidate_items[b]]
+        in list order, padded with -inf (the layout cpp/uni_evaluator.py:136-137 ranks: util/tool.py pad_sequences, post)."""
+        dev = self._require_gpu()
+        if len(candidate_items) != len(user_ids):
+            raise ValueError("one candidate list per user: %d lists for %d users" % (len(candidate_items), len(user_ids)))
+        lens = np.fromiter((len(c) for c in candidate_items), dtype=np.int64, count=len(candidate_items))
+        ptr = np.zeros(len(lens) + 1, dtype=np.int64)
+        np.cumsum(lens, out=ptr[1:])
+        flat = np.fromiter((int(i) for c in candidate_items for i in c), dtype=np.int64, count=int(ptr[-1]))
+        if flat.size and (flat.min() < 0 or flat.max() >= self.num_items):
+            raise IndexError("candidate item ids must lie in [0, %d)" % self.num_items)
+        width = int(lens.max()) if lens.size else 0
+        out = torch.empty(len(user_ids), width, dtype=torch.float32, device=dev)
+        self.predict_candidates_device(user_ids, torch.from_numpy(ptr).to(dev), torch.from_numpy(flat.astype(np.int32)).to(dev), out)
+        return out.cpu()
 
     def predict(self, user_ids, candidate_items=None):
         """:96-113. CPU fp32 tensor [len(user_ids) x I]; `candidate_items` is ignored as in the reference."""

@@ -6,6 +6,8 @@ else raises (no CPU path).
 """
 import ctypes
 
+import numpy as np
+
 import torch
 
 from . import _lib
@@ -742,6 +744,50 @@ def sample_triplets(user_ids, ptr, items, num_items, n, seed, epoch, users, pos,
                                                    int(seed), int(epoch), _dev(users, "users", torch.int64),
                                                    _dev(pos, "pos", torch.int64), _dev(neg, "neg", torch.int64),
                                                    _stream()), "sample_triplets")
+
+
+def score_candidates(Y, U, I, users, d, S, head_mask, fusion_mode, predict_type, cand_ptr, cand_items, out, sqnorm=None,
+                     row_sum=None, I_total=0):
+    """elimrec_score_candidates: out [B x width] (rows contiguous) = each user's candidate scores in list order, then -inf.
+    cand_ptr int64 [B + 1] / cand_items int32: the lists as CSR. TIE: row_sum [B] (score_topk_shard phase 1) and I_total."""
+    y, ldy = _rowmajor(Y, "Y")
+    op, lds = _rowmajor(out, "out")
+    B = users.numel()
+    if out.shape[0] != B or cand_ptr.numel() != B + 1:
+        raise ValueError("elimrec_amd.ops.score_candidates: out needs one row and cand_ptr B + 1 entries for each of the %d users" % B)
+    items = cand_items if cand_items.numel() else None
+    _lib.check(_lib.load().elimrec_score_candidates(y, ldy, U, I, _dev(users, "users", torch.int64), B, d, S, int(head_mask),
+                                                    FUSION_MODES[fusion_mode], PREDICT_TYPES.get(predict_type, 0),
+                                                    _dev(sqnorm, "sqnorm"), _dev(cand_ptr, "cand_ptr", torch.int64),
+                                                    _dev(items, "cand_items", torch.int32), _dev(row_sum, "row_sum"),
+                                                    int(I_total), op, lds, out.shape[1], _stream()), "score_candidates")
+    return out
+
+
+def check_negative_room(excl_ptr, num_items, n_neg):
+    """The reference's condition (random_choice.pyx:35-37) on the host, before any launch: every row must leave more than
+    n_neg ids outside its exclusion list."""
+    counts = np.diff(np.asarray(excl_ptr, dtype=np.int64))
+    if n_neg <= 0:
+        raise ValueError("'size' must be a positive integer.")
+    if counts.size and (num_items <= counts).any():
+        raise ValueError("The number of 'exclusion' is greater than 'high'.")
+    if counts.size and (num_items - counts <= n_neg).any():
+        raise ValueError("There is not enough integers to be sampled.")
+
+
+def sample_negatives(excl_ptr, excl_items, num_items, n_neg, seed, out):
+    """elimrec_sample_negatives: out int32 [n_users x n_neg] = per row n_neg distinct ids of [0, num_items) outside the row's
+    sorted exclusion list (excl_ptr int64 [n_users + 1] / excl_items int32, device tensors)."""
+    n_users = excl_ptr.numel() - 1
+    if tuple(out.shape) != (n_users, n_neg) or not out.is_contiguous():
+        raise ValueError("elimrec_amd.ops.sample_negatives: out must be a contiguous [%d x %d] tensor" % (n_users, n_neg))
+    check_negative_room(excl_ptr.cpu().numpy(), num_items, n_neg)
+    items = excl_items if excl_items.numel() else None
+    _lib.check(_lib.load().elimrec_sample_negatives(_dev(excl_ptr, "excl_ptr", torch.int64), _dev(items, "excl_items", torch.int32),
+                                                    n_users, int(num_items), int(n_neg), int(seed), _dev(out, "out", torch.int32),
+                                                    _stream()), "sample_negatives")
+    return out
 
 
 def head_pack_floats(dims):

@@ -515,6 +515,20 @@ int elimrec_topk_reference_order_device(const float *d_scores, int64_t n_rows, i
                                         int32_t *d_topk_idx, float *d_topk_val, void *stream);
 int elimrec_topk_reference_order(const float *h_scores, int64_t n_rows, int64_t I, int64_t ld, int K, int32_t *h_topk);
 
+/* Candidate lists instead of the whole catalogue (sampled-negative evaluation: the reference's evaluator/backend/cpp/
+ * uni_evaluator.py:132-140 scores list(user_pos_test[u]) + user_neg_test[u] per user and pads the rows with -inf,
+ * util/tool.py:168 pad_sequences, post). The score of candidate (u, i) is the value the full-catalogue scorer gives at
+ * (u, i) (models/EliMRec.py:96-113: same expressions, both elimrec_score_set_math modes). d_cand_ptr int64[B+1] /
+ * d_cand_items int32: the ragged lists as CSR. d_scores [B x width] (leading dimension lds >= width): row b = its
+ * candidates' scores in list order, then -inf up to width (a list longer than width is cut; an id outside [0, I) scores
+ * NaN and is not read). d_sqnorm: elimrec_row_sqnorms' table (predict types TE / TIE). TIE: d_row_sum[B] = the users'
+ * sums of sigmoid(u.i) over the catalogue (elimrec_score_topk_shard phase 1 with the whole catalogue as the shard), the
+ * mean is d_row_sum[b] / I_total. Any recdim % 4 == 0, S 0..3. */
+int elimrec_score_candidates(const float *d_Y, int64_t ldy, int64_t U, int64_t I, const int64_t *d_users, int B, int d,
+                             int S, uint32_t head_mask, int fusion_mode, int predict_type, const float *d_sqnorm,
+                             const int64_t *d_cand_ptr, const int32_t *d_cand_items, const float *d_row_sum,
+                             int64_t I_total, float *d_scores, int64_t lds, int64_t width, void *stream);
+
 /* Precision/Recall/MAP/NDCG/MRR prefix curves @1..K from ranked lists (metric.h:17-106).
  * d_truth_ptr int64[B+1], d_truth_items int32 (unique per row). metric_ids host int[n_metrics]
  * (1..5 as in cpp/uni_evaluator.py:14). d_out [B x n_metrics x K]. */
@@ -533,6 +547,15 @@ int elimrec_sample_triplets(const int32_t *d_user_ids, const int64_t *d_ptr, con
                             int64_t n_train_users, int64_t I, int64_t n, uint64_t seed,
                             uint64_t epoch, int64_t *d_users, int64_t *d_pos, int64_t *d_neg,
                             void *stream);
+
+/* Negatives of sampled-negative evaluation (the reference's data/dataset.py:270-288; util/cython/random_choice.pyx:20-62,
+ * replace=False): per user row u, n_neg DISTINCT ids uniform over [0, I) minus the row's exclusion list d_excl_items
+ * [d_excl_ptr[u], d_excl_ptr[u+1]) (sorted ascending, unique, inside [0, I): the user's train + valid + test items).
+ * d_out int32 [n_users x n_neg], in draw order. Philox4x32-10 keyed by (seed, u): the contract is distributional, as for
+ * elimrec_sample_triplets. The caller rejects I - |exclusion| <= n_neg ("There is not enough integers to be sampled.",
+ * random_choice.pyx:35-37); such a row comes back as -1. 0 < n_neg <= 16000. */
+int elimrec_sample_negatives(const int64_t *d_excl_ptr, const int32_t *d_excl_items, int64_t n_users, int64_t I,
+                             int n_neg, uint64_t seed, int32_t *d_out, void *stream);
 
 /* ================================================================ slab-major propagation (column shards)
  * The d-column table [E_u ; E_i] and every layer table X^k = A X^(k-1) of the folded propagation

@@ -71,7 +71,9 @@ def open_dataset(cfg):
         return Dataset(cfg)
     users, items, interactions = cfg["synthetic_shape"] if "synthetic_shape" in cfg else (36656, 76085, 720829)
     dims = tuple(cfg["synthetic_dims"]) if "synthetic_dims" in cfg else (128, 128, 128)
-    return SyntheticDataset(users, items, interactions, feat_dims=dims, seed=0)
+    data = SyntheticDataset(users, items, interactions, feat_dims=dims, seed=0)
+    data.evaluate_neg = int(cfg["rec.evaluate.neg"]) if "rec.evaluate.neg" in cfg else 0
+    return data
 
 
 class Net(object):
