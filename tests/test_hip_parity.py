@@ -1046,7 +1046,8 @@ def test_tile_guided_topk_at_recdim_64(with_scores, d, I):
     against a stable sort of the full masked score matrix: continuous scores and massive ties; rows with nothing, a few,
     hundreds (K + masked > 256 group maxima -> fall-back) and all-but-4 items masked; 200 users (two user groups per
     launch); with the caller's score matrix and with the private one (top-K only). I > 16384 without a score matrix: the
-    catalogue is scored in chunks (no [B x I] block in the workspace), per-chunk top-K lists merged -- the same lists."""
+    catalogue is scored in chunks (no [B x I] block in the workspace), per-chunk top-K lists merged -- the same lists.
+    Absolute accuracy: see test_score_fp64_gpu.py."""
     from elimrec_amd import ops
     U, S = 260, 3
     Cy = (1 + S) * d
@@ -1099,7 +1100,8 @@ def test_tile_guided_topk_at_recdim_64(with_scores, d, I):
 def test_fast_evaluation_math_is_close_and_ranks_alike():
     """elimrec_score_set_math(1), the default: sigmoids through v_exp_f32 (two-float argument product) and v_rcp_f32 + one
     Newton step, reciprocal norms. Scores within 4e-7 of the EXACT mode (IEEE division, libm expf) in all three fusion
-    modes; top-K lists differ only where two EXACT scores are closer than that."""
+    modes; top-K lists differ only where two EXACT scores are closer than that.
+    Absolute accuracy: see test_score_fp64_gpu.py."""
     from elimrec_amd import _lib, ops
     lib = _lib.load()
     U, I, d, S, K = 130, 4000, 64, 3, 20
@@ -1169,7 +1171,8 @@ def test_topk_only_workspace_fits_any_recdim_and_k(d, K):
     """top-K only at I > 16384 with a recdim outside the 16-user-per-wave scorer's set (48, 256) or
     K > 256 takes the whole-catalogue form; ops.score_workspace(..., topk_only=True, d=d) asks the library's own predicate
     and returns a workspace that fits (the reference accepts any recdim and any K, models/EliMRec.py:96-113). The lists
-    equal a stable sort of the full masked score matrix."""
+    equal a stable sort of the full masked score matrix.
+    Absolute accuracy: see test_score_fp64_gpu.py."""
     from elimrec_amd import ops
     U, I, S = 40, 20000, 3
     g = torch.Generator().manual_seed(d + K)
@@ -1227,7 +1230,8 @@ def test_bf16x3_scorer_matches_exact_math(d, mode):
     EXACT mode (fp32 MFMA, IEEE division, libm expf) over a 40 000-item catalogue, normal / TE / TIE: every returned score
     within 2.4e-7 of the EXACT score of the same (user, item) -- FAST's own 1.2e-7 + the split form's round-off --, the top-20
     lists identical except where two EXACT scores are closer than 4.8e-7, masked items never returned; with the switch off the
-    fp32-MFMA FAST scorer gives its own (equally close) lists."""
+    fp32-MFMA FAST scorer gives its own (equally close) lists.
+    Absolute accuracy: see test_score_fp64_gpu.py."""
     from elimrec_amd import _lib, ops
     lib = _lib.load()
     U, I, S, K, B = 300, 40000, 3, 20, 200
@@ -1277,7 +1281,8 @@ def test_bf16x3_scorer_is_stable_over_repeated_launches(mode, ptype, d, reps):
     """The same top-20 call, `reps` times on fresh workspaces: every launch returns the bits of the first, and the first
     is within 2.4e-7 of the EXACT scores. (Built with the SLP vectoriser's packed-fp32 forms, score_t16b_kernel<2,4,2,1,64>
     -- TIE, hm -- returned 1.0 for the 16 items of one tile on lanes 48-63 of one accumulator row about once in 150
-    launches, more often early in a process; csrc/Makefile builds eval.hip without them.)"""
+    launches, more often early in a process; csrc/Makefile builds eval.hip without them.)
+    Absolute accuracy: see test_score_fp64_gpu.py."""
     from elimrec_amd import _lib, ops
     lib = _lib.load()
     U, I, S, K, B = 300, 40000, 3, 20, 200
@@ -1321,7 +1326,8 @@ def test_item_sharded_scoring_equals_whole_catalogue(d, ptype, W, eval_math):
     """elimrec_score_topk_shard on W emulated item shards (uneven blocks): phase 1 row sums added in rank order (the
     all_reduce), phase 2 scores / top-K per shard, elimrec_topk_merge of the W lists. The concatenated shard scores equal
     the whole-catalogue call's to 2e-7 (the NDE mean is the same sum split into W fixed-order partial sums), masks land on
-    the same items, and the merged top-K IS the stable (score desc, id asc) ranking of those scores."""
+    the same items, and the merged top-K IS the stable (score desc, id asc) ranking of those scores.
+    Absolute accuracy: see test_score_fp64_gpu.py."""
     from elimrec_amd import ops
     U, I, S, K, B = 90, 7000, 3, 20, 70
     g = torch.Generator().manual_seed(d + W)
