@@ -95,6 +95,7 @@ int elimrec_gather_rows(const float *d_src, int64_t lds, const int32_t *d_rows, 
  * deterministic two-stage reduction: fixed row chunks -> partial slabs in workspace -> summed in
  * chunk order. Rows r run over [range[0], range[1]) if d_range != NULL (device int32[2]) else
  * [0, R). d_colsum (nullable, [n1]) additionally receives sum_r A[r, i] (the bias gradient).
+ * accumulate != 0 adds to what d_out AND d_colsum held; an empty range leaves exact zeros (or what they held).
  * workspace: elimrec_linear_bwd_w_workspace(R, n1, n2) bytes. */
 size_t elimrec_linear_bwd_w_workspace(int64_t R, int n1, int n2);
 int elimrec_linear_bwd_w(const float *d_A, int64_t lda, const float *d_B, int64_t ldb,

@@ -20,15 +20,26 @@ def _t(a, dtype=None):
     return t if dtype is None else t.to(dtype)
 
 
-def _random_graph(n, seed, hot=6, hot_deg=400):
-    """Ragged rows: empty rows, rows of a few entries and `hot` rows far above the split threshold."""
+def _random_graph(n, seed, hot=6, hot_deg=400, row_len=None):
+    """Ragged rows: empty rows, rows of a few entries and `hot` rows far above the split threshold. row_len = {row: length}:
+    these rows get exactly that many neighbours (distinct columns, drawn from a generator of their own: the other rows are
+    what they are without it)."""
     rng = np.random.RandomState(seed)
     deg = rng.poisson(6, n)
     deg[rng.rand(n) < 0.05] = 0
     deg[rng.choice(n, hot, replace=False)] = hot_deg + rng.randint(0, 70, hot)
+    if row_len:
+        deg[list(row_len)] = 0
     rows = np.repeat(np.arange(n), deg)
     cols = rng.randint(0, n, len(rows))
-    m = sp.csr_matrix((rng.rand(len(rows)).astype(np.float32) + 0.1, (rows, cols)), shape=(n, n))
+    vals = rng.rand(len(rows)).astype(np.float32) + 0.1
+    if row_len:
+        rng2 = np.random.RandomState(seed + 7919)
+        for r, k in sorted(row_len.items()):
+            rows = np.concatenate([rows, np.full(k, r)])
+            cols = np.concatenate([cols, rng2.choice(n, k, replace=False)])
+            vals = np.concatenate([vals, ((rng2.rand(k) + 0.1) * rng2.choice([-1.0, 1.0], k) / max(k, 1) ** 0.5).astype(np.float32)])
+    m = sp.csr_matrix((vals, (rows, cols)), shape=(n, n))
     m.sum_duplicates()
     m.sort_indices()
     return m
