@@ -3,6 +3,7 @@
 // evaluate.h:23-42; metric.h:17-106). Removes the [B_t x I] device->host copy of the reference.
 #include "common.h"
 #include <cstdlib>
+#include <type_traits>
 
 namespace elimrec {
 
@@ -1700,31 +1701,39 @@ extern "C" size_t elimrec_score_workspace_topk(int B, int64_t U, int64_t I, int 
     return score_layout(B, U, I, S, K, true).total;
 }
 
-// The ONE predicate for the chunked (top-K only, no [B x I] score block) form, shared by the sizing function below and by
-// elimrec_score_topk: the 16-user-per-wave scorer (recdim 32 / 64 / 128, 1..3 heads, MFMA + T16 forms enabled), K <= 256
-// (the tile-guided selection with its running list) and more than one chunk -- any catalogue size.
 constexpr size_t TOPK_MERGE_LDS_MAX = 160 * 1024;
-// (the plain-VALU scorer, the one-user-tile-per-workgroup MFMA scorer without tile maxima and the unchunked top-K were run-time
-// switches until round 6 -- ELIMREC_SCORE_VALU / _T16 / _CHUNKED / _RESIDENT; each lost to the form below at every shape measured,
-// docs/REJECTED.md -- and are now fixed: the forms are chosen by recdim and call shape alone)
-static bool score_uses_mfma() { return true; }
-static bool score_uses_t16() { return true; }
-static bool score_uses_chunks() { return true; }
-static bool score_t16_path(int d, int S) {
-    return score_uses_mfma() && score_uses_t16() && (d == 32 || d == 64 || d == 128) && S >= 1 && S <= 3;
-}
-static bool score_chunked_form(int d, int S, int K, int64_t I, bool want_scores, bool want_topk) {
-    return score_t16_path(d, S) && score_uses_chunks() && !want_scores && want_topk && K <= RM_KMAX && I > SCORE_CHUNK;
-}
-static bool score_matrix_chunks(int d, int S, int64_t I) {
-    return score_t16_path(d, S) && score_uses_chunks() && I > SCORE_CHUNK;
+
+// The forms of elimrec_score_topk, chosen by recdim and call shape alone (the plain-VALU scorer, the one-user-tile-per-workgroup
+// MFMA scorer without tile maxima and the unchunked top-K each lost to these at every shape measured: docs/REJECTED.md).
+// ONE plan per call shape, filled by score_plan for the sizing function and for the call: they cannot disagree.
+struct ScorePlan {
+    bool t16;              // 16 users per wave (score_t16_kernel / _t16b_): recdim 32 / 64 / 128, 1..3 heads; score_mfma_kernel otherwise
+    bool chunked;          // only top-K wanted, K <= RM_KMAX, more than one chunk: no [B x I] score block, a running list per user
+    bool matrix_chunks;    // a [B x I] block (the caller's, or a private one: K > RM_KMAX) beyond one chunk: the same launches, every tile stored
+    bool bf16x3;           // FAST math, recdim 32 / 64: the chunks on the bf16 matrix cores from exact three-piece splits
+    ScoreLayout L;         // L.planes bytes are what the call needs; L.total has room for one chunk's pieces behind them
+};
+// phase 1 (row sums only) touches no score block: the smaller of the full and the chunked layout is enough. bf16x3 is taken only
+// where the workspace has room for the pieces (one sized by elimrec_score_workspace_for has it).
+static ScorePlan score_plan(int B, int64_t U, int64_t I, int S, int K, int d, bool want_scores, bool want_topk, int phase,
+                            size_t workspace_bytes) {
+    ScorePlan p;
+    p.t16 = (d == 32 || d == 64 || d == 128) && S >= 1 && S <= 3;
+    const bool chunks = p.t16 && I > SCORE_CHUNK;
+    p.chunked = chunks && !want_scores && want_topk && K <= RM_KMAX;
+    p.matrix_chunks = chunks && !p.chunked;
+    p.L = score_layout(B, U, I, S, K, p.chunked, d);
+    const ScoreLayout Lc = score_layout(B, U, I, S, K, true, d);
+    if (phase == 1 && Lc.planes < p.L.planes) p.L = Lc;
+    p.bf16x3 = chunks && d != 128 && phase != 1 && workspace_bytes >= p.L.total && score_bf16x3() && score_math() == 1;
+    return p;
 }
 
 // Bytes elimrec_score_topk needs for THIS call shape: recdim d, K, and whether the caller passes a score matrix
 // (want_scores) -- the chunked layout exactly when the call will take the chunked form, the full [B x I] layout otherwise
 // (any recdim, any K: the reference accepts both, models/EliMRec.py:96-113, evaluator/backend/cpp/uni_evaluator.py:131).
 extern "C" size_t elimrec_score_workspace_for(int B, int64_t U, int64_t I, int S, int K, int d, int want_scores) {
-    return score_layout(B, U, I, S, K, score_chunked_form(d, S, K, I, want_scores != 0, K > 0), d).total;
+    return score_plan(B, U, I, S, K, d, want_scores != 0, K > 0, 0, 0).L.total;
 }
 
 extern "C" int elimrec_row_sqnorms(const float *d_Y, int64_t ldy, int64_t n_rows, int d, int n_blocks, float *d_out,
@@ -1737,6 +1746,312 @@ extern "C" int elimrec_row_sqnorms(const float *d_Y, int64_t ldy, int64_t n_rows
     return 0;
 }
 
+// ---- run-time value -> template argument: f is a generic lambda called with std::integral_constants (the sets ARE the code object's)
+template <int V> using int_c = std::integral_constant<int, V>;
+template <bool HEADLESS, class F> static void with_nb(int S, F f) {       // NB = 1 + S head blocks (NB = 1: the candidate scorer only)
+    if constexpr (HEADLESS) { if (S == 0) return f(int_c<1>{}); }
+    if (S == 1) f(int_c<2>{}); else if (S == 2) f(int_c<3>{}); else f(int_c<4>{});
+}
+template <bool WIDE, class F> static void with_d(int d, F f) {            // recdim 32 / 64 (/ 128 -- WIDE: the fp32 form only)
+    if constexpr (WIDE) { if (d == 128) return f(int_c<128>{}); }
+    if (d == 64) f(int_c<64>{}); else f(int_c<32>{});
+}
+template <class F> static void with_pt_fm(int pt, int fm, F f) {          // (predict type, fusion mode); type normal has no fusion
+    if (pt == 0) f(int_c<0>{}, int_c<0>{});
+    else if (pt == 1 && fm == 0) f(int_c<1>{}, int_c<0>{});
+    else if (pt == 1 && fm == 1) f(int_c<1>{}, int_c<1>{});
+    else if (pt == 1) f(int_c<1>{}, int_c<2>{});
+    else if (fm == 0) f(int_c<2>{}, int_c<0>{});
+    else if (fm == 1) f(int_c<2>{}, int_c<1>{});
+    else f(int_c<2>{}, int_c<2>{});
+}
+template <class F> static void with_fast(bool fast, F f) { if (fast) f(std::true_type{}); else f(std::false_type{}); }
+
+// score_t16_kernel: 16 users per wave, 128 per workgroup, a persistent grid over 16-item tiles (two workgroups per CU)
+constexpr size_t t16_lds(int pass, int nb, int d) {
+    return ((size_t)2 * TI * ((pass == 1 ? 1 : nb) * d + 4) + (size_t)TW * TU * (nb > 1 ? nb - 1 : 1) + TW * TU) * sizeof(float);
+}
+static dim3 t16_grid(int tiles, int B) {                   // tiles dealt evenly to at most 512 workgroups
+    const int per = (tiles + 511) / 512;
+    return dim3((unsigned)((tiles + per - 1) / per), (B + TW * TU - 1) / (TW * TU));
+}
+template <auto KERNEL> static void allow_lds(size_t lds) {      // beyond 64 KiB of dynamic LDS: once per kernel instantiation
+    static bool done = false;
+    if (!done) { (void)hipFuncSetAttribute((const void *)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); done = true; }
+}
+template <int PASS, int NB, int PT, int FM, bool FAST, int D>
+static void launch_t16(dim3 grid, const ScoreArgs &a, int tiles, hipStream_t s) {
+    constexpr size_t lds = t16_lds(PASS, NB, D);
+    if constexpr (lds > 64 * 1024) allow_lds<score_t16_kernel<PASS, NB, PT, FM, FAST, D>>(lds);
+    hipLaunchKernelGGL((score_t16_kernel<PASS, NB, PT, FM, FAST, D>), grid, dim3(512), lds, s, a, tiles);
+}
+// score_t16b_kernel (recdim 32 / 64, FAST math)
+constexpr size_t t16b_lds(int pass, int nb, int d) {
+    return (size_t)2 * t16b_win(pass, nb, d) * TI * t16b_row4(pass, nb, d) * 16 + ((size_t)TWB * TU * (nb > 1 ? nb - 1 : 1) + TWB * TU) * sizeof(float);
+}
+template <int PASS, int NB, int PT, int FM, int D>
+static void launch_t16b(dim3 grid, const ScoreArgs &a, int tiles, hipStream_t s) {
+    constexpr size_t lds = t16b_lds(PASS, NB, D);
+    if constexpr (PASS == 2 && lds > 64 * 1024) allow_lds<score_t16b_kernel<PASS, NB, PT, FM, D>>(lds);
+    hipLaunchKernelGGL((score_t16b_kernel<PASS, NB, PT, FM, D>), grid, dim3(NTB), lds, s, a, tiles);
+}
+
+// One scorer launch over items [a.item0, a.item_end) = `tiles` 16-item tiles (pass 1: predict type / fusion mode from the arguments)
+static int t16_pass1(const ScoreArgs &a, int tiles, dim3 grid, hipStream_t s) {
+    with_nb<false>(a.S, [&](auto nb) { with_fast(score_math() == 1, [&](auto f) { with_d<true>(a.d, [&](auto d) {
+        launch_t16<1, decltype(nb)::value, -1, -1, decltype(f)::value, decltype(d)::value>(grid, a, tiles, s);
+    }); }); });
+    ELIMREC_LAUNCH_CHECK("score_t16_pass1");
+    return 0;
+}
+static int t16_pass2(const ScoreArgs &a, int tiles, dim3 grid, hipStream_t s) {
+    with_nb<false>(a.S, [&](auto nb) { with_pt_fm(a.predict_type, a.fusion_mode, [&](auto pt, auto fm) { with_fast(score_math() == 1, [&](auto f) { with_d<true>(a.d, [&](auto d) {
+        launch_t16<2, decltype(nb)::value, decltype(pt)::value, decltype(fm)::value, decltype(f)::value, decltype(d)::value>(grid, a, tiles, s);
+    }); }); }); });
+    ELIMREC_LAUNCH_CHECK("score_t16_pass2");
+    return 0;
+}
+static int t16b_pass1(const ScoreArgs &a, int tiles, dim3 grid, hipStream_t s) {
+    with_nb<false>(a.S, [&](auto nb) { with_d<false>(a.d, [&](auto d) {
+        launch_t16b<1, decltype(nb)::value, -1, -1, decltype(d)::value>(grid, a, tiles, s);
+    }); });
+    ELIMREC_LAUNCH_CHECK("score_t16b_pass1");
+    return 0;
+}
+static int t16b_pass2(const ScoreArgs &a, int tiles, dim3 grid, hipStream_t s) {
+    with_nb<false>(a.S, [&](auto nb) { with_pt_fm(a.predict_type, a.fusion_mode, [&](auto pt, auto fm) { with_d<false>(a.d, [&](auto d) {
+        launch_t16b<2, decltype(nb)::value, decltype(pt)::value, decltype(fm)::value, decltype(d)::value>(grid, a, tiles, s);
+    }); }); });
+    ELIMREC_LAUNCH_CHECK("score_t16b_pass2");
+    return 0;
+}
+
+// What the stages of one elimrec_score_topk call share
+struct ScoreCall {
+    ScorePlan p;
+    ScoreArgs a;                       // the kernels' argument block for the whole catalogue; the chunk loops edit copies of it
+                                       // (a.tile_max set: the scorer leaves tile maxima, the selection reads them and the bitmap)
+    hipStream_t s;
+    float *mean_dst;                   // where pass 1 leaves the TIE row means (phase 1: sums -- divisor 1 -- straight to the caller)
+    int64_t mean_div;
+    const int64_t *train_ptr; const int32_t *train_items;
+    float *d_scores, *topk_val, *run_val, *thr;      // run_val [B x K] / thr [B]: the chunked form's running list and K-th best score
+    int32_t *topk_idx, *fallback;
+    int K, tie_order;
+    int64_t id_offset, bits_ld;
+    uint32_t *bits;                    // the masked items as a bitmap [B x bits_ld] (tile maxima wanted, a train mask given)
+    uint4 *planes;                     // bf16x3: one chunk's item rows as three bf16 planes, the chunk's inverse item norms behind them
+    float *inrm;
+};
+
+// squared norms, the shards' mean, the train bitmap
+static int score_prepare(ScoreCall &c, const float *d_sqnorm, float *wsqn, int phase, const float *d_row_sum, int64_t I_total) {
+    ScoreArgs &a = c.a;
+    if (!d_sqnorm && a.predict_type != 0) {            // not supplied: compute the whole table for this call
+        const int64_t N = a.U + a.I;
+        hipLaunchKernelGGL(row_sqnorm_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, c.s, a.Y, a.ldy, N, a.d, 1 + a.S, wsqn);
+        ELIMREC_LAUNCH_CHECK("row_sqnorm");
+    }
+    a.sqn = d_sqnorm ? d_sqnorm : wsqn;
+    if (phase == 2 && a.predict_type == 2) {           // phase 2: the mean comes from the all-reduced sums
+        hipLaunchKernelGGL(mean_from_sum_kernel, dim3((a.B + 255) / 256), dim3(256), 0, c.s, d_row_sum, a.B, I_total, c.mean_dst);
+        ELIMREC_LAUNCH_CHECK("mean_from_sum");
+    }
+    ELIMREC_REQUIRE(c.p.chunked || a.lds >= a.I, "score_topk: lds < I");
+    if (a.tile_max && c.train_ptr) {
+        ELIMREC_REQUIRE(c.train_items, "score_topk: train_items missing");
+        hipLaunchKernelGGL(train_bits_kernel, dim3(a.B), dim3(256), 0, c.s, c.train_ptr, c.train_items, a.I, c.bits, c.bits_ld);
+        ELIMREC_LAUNCH_CHECK("train_bits");
+    }
+    return 0;
+}
+
+// pass 1 (TIE): row means of sigmoid(u.i) over the WHOLE catalogue, partials per workgroup added in order by row_mean_kernel
+static int score_row_mean(const ScoreCall &c, int n_part) {
+    hipLaunchKernelGGL(row_mean_kernel, dim3(c.a.B), dim3(256), 0, c.s, c.a.partial, n_part, c.a.B, c.mean_div, c.mean_dst);
+    ELIMREC_LAUNCH_CHECK("row_mean");
+    return 0;
+}
+static int score_pass1_whole(const ScoreCall &c) {
+    const int tiles = n_item_tiles(c.a.I);
+    const dim3 grid = c.p.t16 ? t16_grid(tiles, c.a.B) : dim3(tiles, (c.a.B + MU - 1) / MU);
+    if (c.p.t16) {
+        const int rc = t16_pass1(c.a, tiles, grid, c.s);
+        if (rc) return rc;
+    } else {
+        hipLaunchKernelGGL(score_mfma_kernel<1>, grid, dim3(256), 0, c.s, c.a);
+        ELIMREC_LAUNCH_CHECK("score_mfma_pass1");
+    }
+    return score_row_mean(c, (int)grid.x);
+}
+// ... on the bf16 matrix cores: chunk by chunk (the fused block's pieces only), <= 64 workgroups per user group and chunk,
+// partials in (chunk, workgroup) order
+static int score_pass1_bf16x3(const ScoreCall &c) {
+    const ScoreArgs &a = c.a;
+    const int ug = (a.B + TWB * TU - 1) / (TWB * TU);
+    int n_part = 0;
+    for (int64_t at = 0; at < a.I; at += SCORE_CHUNK) {
+        ScoreArgs ac = a;
+        ac.item0 = at;
+        ac.item_end = at + SCORE_CHUNK < a.I ? at + SCORE_CHUNK : a.I;
+        const int64_t cnt = ac.item_end - ac.item0;
+        const int tc = n_item_tiles(cnt);
+        hipLaunchKernelGGL(split3_items_kernel, dim3((unsigned)((cnt * (a.d / 8) + 255) / 256)), dim3(256), 0, c.s, a.Y, a.ldy, a.U,
+                           ac.item0, cnt, a.d, c.planes, (const float *)nullptr, 0, (float *)nullptr);
+        ELIMREC_LAUNCH_CHECK("split3_items(pass 1)");
+        const int gx = tc < 64 ? tc : 64;
+        ac.planes = c.planes;
+        ac.partial = a.partial + (int64_t)n_part * a.B;
+        const int rc = t16b_pass1(ac, tc, dim3((unsigned)gx, ug), c.s);
+        if (rc) return rc;
+        n_part += gx;
+    }
+    return score_row_mean(c, n_part);
+}
+
+// pass 2 + (chunked) selection, SCORE_CHUNK items at a time. chunked: a [B x SCORE_CHUNK] block and a RUNNING top-K per user --
+// every chunk's selection leaves the best K so far and their K-th score; the next chunk's scorer stores a tile's scores of a user
+// only where the tile's maximum reaches that score -- about one tile in seven after the 2 048-item pilot chunk, one in a hundred
+// after the first full chunk -- so the block is hardly written at all (it was 537 MB per launch at 8 192 users). The lists after
+// the last chunk are the result: no merge launch. tie_order 0: topk_tiles_kernel, lists by (score desc, id asc); tie_order 1:
+// ref_order_kernel, the reference's heap carried from chunk to chunk (its top IS the K-th best score so far).
+// matrix_chunks: every tile stored at its place in the [B x I] block; the selection follows over the whole block.
+static int score_pass2_chunks(const ScoreCall &c) {
+    const ScoreArgs &a = c.a;
+    const bool chunked = c.p.chunked, bf16x3 = c.p.bf16x3;
+    const int B = a.B, K = c.K;
+    int64_t at = 0;
+    for (int ch = 0; at < a.I; ++ch) {
+        ScoreArgs ac = a;
+        ac.item0 = at;
+        const int64_t len = (chunked && ch == 0 && a.I > SCORE_PILOT) ? SCORE_PILOT : SCORE_CHUNK;
+        ac.item_end = ac.item0 + len < a.I ? ac.item0 + len : a.I;
+        at = ac.item_end;
+        if (chunked) ac.thr = ch == 0 ? nullptr : c.thr;
+        else {                                                   // this chunk's columns of the [B x I] block
+            ac.scores = a.scores + ac.item0;
+            if (a.tile_max) ac.tile_max = a.tile_max + ac.item0 / TI;
+        }
+        const int64_t cnt = ac.item_end - ac.item0;
+        const int tc = n_item_tiles(cnt);
+        // ~512 workgroups per launch in all: a workgroup walks several tiles with its users' operands resident
+        const int wu = (bf16x3 ? TWB : TW) * TU;               // users per workgroup
+        const int ug = (B + wu - 1) / wu;
+        int gx = 512 / ug > 0 ? 512 / ug : 1;
+        if (gx > tc) gx = tc;
+        const int per = (tc + gx - 1) / gx;
+        const dim3 grid((unsigned)((tc + per - 1) / per), ug);
+        int rc;
+        if (bf16x3) {
+            const int cols = (1 + a.S) * a.d;
+            // (predict type normal has no heads to normalise)
+            hipLaunchKernelGGL(split3_items_kernel, dim3((unsigned)((cnt * (cols / 8) + 255) / 256)), dim3(256), 0, c.s, a.Y, a.ldy, a.U,
+                               ac.item0, cnt, cols, c.planes, a.predict_type != 0 ? a.sqn : (const float *)nullptr, 1 + a.S,
+                               a.predict_type != 0 ? c.inrm : (float *)nullptr);
+            ELIMREC_LAUNCH_CHECK("split3_items");
+            ac.planes = c.planes;
+            ac.inrm = c.inrm;
+            rc = t16b_pass2(ac, tc, grid, c.s);
+        } else {
+            rc = t16_pass2(ac, tc, grid, c.s);
+        }
+        if (rc) return rc;
+        if (!chunked) continue;
+        const uint32_t *bits = c.train_ptr ? (const uint32_t *)c.bits : (const uint32_t *)nullptr;
+        if (c.tie_order == 1) {
+            hipLaunchKernelGGL(ref_order_kernel<true>, dim3((unsigned)((B + 3) / 4)), dim3(256), (size_t)K * 32, c.s,
+                               (const float *)ac.scores, ac.lds, cnt, (const float *)a.tile_max, ac.tmax_ld, B, K, bits, c.bits_ld, ac.item0,
+                               c.topk_idx, c.run_val, (int64_t)K, c.thr, ch == 0 ? 1 : 0, at >= a.I ? 1 : 0);
+            ELIMREC_LAUNCH_CHECK("ref_order(chunk)");
+        } else {
+            hipLaunchKernelGGL(topk_tiles_kernel, dim3(B), dim3(256), 0, c.s, ac.scores, ac.lds, cnt, (const float *)a.tile_max, ac.tmax_ld,
+                               tc, K, c.train_ptr, bits, c.bits_ld, c.topk_idx, c.run_val, c.fallback, ac.item0, (int64_t)K, (int64_t)0,
+                               c.thr, ch == 0 ? 1 : 0);
+            ELIMREC_LAUNCH_CHECK("topk_tiles(chunk)");
+        }
+    }
+    return 0;
+}
+
+// pass 2 over the whole catalogue in one launch
+static int score_pass2_whole(const ScoreCall &c) {
+    const int tiles = n_item_tiles(c.a.I);
+    if (c.p.t16) return t16_pass2(c.a, tiles, t16_grid(tiles, c.a.B), c.s);
+    hipLaunchKernelGGL(score_mfma_kernel<2>, dim3(tiles, (c.a.B + MU - 1) / MU), dim3(256), 0, c.s, c.a);
+    ELIMREC_LAUNCH_CHECK("score_mfma_pass2");
+    return 0;
+}
+
+// the train mask on the score block, then the lists from it (every form but the chunked one, which selects chunk by chunk)
+static int score_select(const ScoreCall &c) {
+    const ScoreArgs &a = c.a;
+    const int B = a.B, K = c.K;
+    const int64_t I = a.I;
+    if (c.train_ptr && (c.d_scores || !a.tile_max)) {       // the caller's score matrix is masked; a private one only if a sweep reads it
+        ELIMREC_REQUIRE(c.train_items, "score_topk: train_items missing");
+        hipLaunchKernelGGL(mask_train_kernel, dim3(B), dim3(128), 0, c.s, a.scores, a.lds, c.train_ptr, c.train_items, B);
+        ELIMREC_LAUNCH_CHECK("mask_train");
+    }
+    if (!c.topk_idx) return 0;
+    const uint32_t *bits = c.train_ptr ? (const uint32_t *)c.bits : (const uint32_t *)nullptr;
+    if (c.tie_order == 1) {
+        // the reference's heap over the whole row: guided by the tile maxima where the scorer left them (the private matrix is
+        // then unmasked: the bitmap), item by item otherwise (the matrix is masked)
+        if (a.tile_max)
+            hipLaunchKernelGGL(ref_order_kernel<true>, dim3((unsigned)((B + 3) / 4)), dim3(256), (size_t)K * 32, c.s, (const float *)a.scores,
+                               a.lds, I, (const float *)a.tile_max, a.tmax_ld, B, K, bits, c.bits_ld, (int64_t)0, c.topk_idx, c.topk_val,
+                               (int64_t)K, (float *)nullptr, 1, 1);
+        else
+            hipLaunchKernelGGL(ref_order_kernel<false>, dim3((unsigned)((B + 3) / 4)), dim3(256), (size_t)K * 32, c.s, (const float *)a.scores,
+                               a.lds, I, (const float *)nullptr, (int64_t)0, B, K, (const uint32_t *)nullptr, (int64_t)0, (int64_t)0,
+                               c.topk_idx, c.topk_val, (int64_t)K, (float *)nullptr, 1, 1);
+        ELIMREC_LAUNCH_CHECK("ref_order");
+    } else if (a.tile_max) {
+        hipLaunchKernelGGL(topk_tiles_kernel, dim3(B), dim3(256), 0, c.s, a.scores, a.lds, I, (const float *)a.tile_max, a.tmax_ld,
+                           (int)a.tmax_ld, K, c.train_ptr, bits, c.bits_ld, c.topk_idx, c.topk_val, c.fallback, (int64_t)0, (int64_t)K,
+                           (int64_t)0, (float *)nullptr, 0);
+        ELIMREC_LAUNCH_CHECK("topk_tiles");
+    } else {
+        const int32_t *picked = nullptr;                       // 2 K <= 1024: topk_select_kernel's candidates first
+        if (2 * K <= 1024) {
+            int G = 32;
+            while (G < 2 * K && G < 1024) G *= 2;
+            hipLaunchKernelGGL(topk_select_kernel, dim3(B), dim3(1024), 0, c.s, a.scores, a.lds, I, K, G, c.topk_idx, c.topk_val, c.fallback);
+            ELIMREC_LAUNCH_CHECK("topk_select");
+            picked = c.fallback;
+        }
+        hipLaunchKernelGGL(topk_kernel, dim3(B), dim3(1024), 0, c.s, a.scores, a.lds, I, K, c.topk_idx, c.topk_val, picked,
+                           (const uint32_t *)nullptr, (int64_t)0, (int64_t)0, (int64_t)K, (int64_t)0);
+        ELIMREC_LAUNCH_CHECK("topk");
+    }
+    return 0;
+}
+
+// this shard's ids -> catalogue ids, and the range invariant on what the call returns. range_check_kernel skips ids < 0 and
+// add_id_offset_kernel rewrites ids >= 0: the chunked form checks its running list first and renumbers after, the other forms
+// renumber first (and only the 16-user scorers' calls are checked).
+static int score_finish(const ScoreCall &c) {
+    const ScoreArgs &a = c.a;
+    const float *mean = a.predict_type == 2 ? (const float *)a.row_mean : (const float *)nullptr;
+    const int64_t n = (int64_t)a.B * c.K;
+    const dim3 check_grid((unsigned)((a.B + 255) / 256)), offset_grid((unsigned)((n + 255) / 256));
+    if (c.p.chunked && a.range_flag) {
+        hipLaunchKernelGGL(range_check_kernel, check_grid, dim3(256), 0, c.s, (const float *)c.run_val, (const int32_t *)c.topk_idx, a.B, c.K,
+                           a.lo, a.hi, mean, a.range_flag);
+        ELIMREC_LAUNCH_CHECK("range_check");
+    }
+    if (c.topk_idx && c.id_offset) {
+        hipLaunchKernelGGL(add_id_offset_kernel, offset_grid, dim3(256), 0, c.s, c.topk_idx, n, (int32_t)c.id_offset);
+        ELIMREC_LAUNCH_CHECK("add_id_offset");
+    }
+    const bool lists = c.topk_idx && c.topk_val;
+    if (!c.p.chunked && a.range_flag && c.p.t16 && (lists || a.predict_type == 2)) {
+        hipLaunchKernelGGL(range_check_kernel, check_grid, dim3(256), 0, c.s, lists ? (const float *)c.topk_val : (const float *)nullptr,
+                           (const int32_t *)c.topk_idx, a.B, c.K, a.lo, a.hi, mean, a.range_flag);
+        ELIMREC_LAUNCH_CHECK("range_check");
+    }
+    return 0;
+}
 
 // phase 0: the whole call. Item-sharded evaluation (this rank holds items [id_offset, id_offset + I) of I_total):
 // phase 1 = pass 1 only, d_row_sum[b] = sum over MY items of sigmoid(u.i) (TIE; a no-op otherwise); the caller adds the
@@ -1760,361 +2075,49 @@ static int score_topk_impl(const float *d_Y, int64_t ldy, int64_t U, int64_t I, 
     ELIMREC_REQUIRE(d_scores || d_topk_idx || phase == 1, "score_topk: nothing to output");
     ELIMREC_REQUIRE(!d_topk_idx || (K > 0 && K <= I), "score_topk: need 0 < K <= I");
     if (B <= 0) return 0;
-    const bool t16_path = score_t16_path(d, S);
-    // only top-K wanted: no [B x I] score block -- the catalogue goes through the scorer in chunks (a workspace sized by
-    // elimrec_score_workspace_for is enough; a larger one is accepted)
-    const bool chunked = score_chunked_form(d, S, K, I, d_scores != nullptr, d_topk_idx != nullptr);
-    // the score MATRIX of a catalogue beyond one chunk goes through the same launches, chunk by chunk, every tile stored: the rows
-    // predict() returns are then the bits the chunked top-K ranks (one score form per call shape, whatever the caller asks for)
-    const bool matrix_chunks = !chunked && score_matrix_chunks(d, S, I);      // (a [B x I] block, the caller's or -- K > 256 -- a private one)
-    ScoreLayout L = score_layout(B, U, I, S, K, chunked);
-    if (phase == 1) {        // row sums only: no score block is touched -- the chunked layout (no [B x I] block) will do as well
-        const ScoreLayout Lc = score_layout(B, U, I, S, K, true);
-        if (Lc.total < L.total) L = Lc;
-    }
-    if (workspace_bytes < L.total) {
-        set_error("score_topk: workspace too small (%zu < %zu)", workspace_bytes, L.total);
+    ScoreCall c;
+    const ScorePlan &p = c.p = score_plan(B, U, I, S, K, d, d_scores != nullptr, d_topk_idx != nullptr, phase, workspace_bytes);
+    const ScoreLayout &L = p.L;
+    if (workspace_bytes < L.planes) {      // (a workspace sized by elimrec_score_workspace_for is enough; a larger one is accepted)
+        set_error("score_topk: workspace too small (%zu < %zu)", workspace_bytes, L.planes);
         return ELIMREC_E_WORKSPACE;
     }
-    // FAST math, chunked top-K, recdim 32 / 64: pass 2 on the bf16 matrix cores from exact three-piece splits (needs room for one
-    // chunk's pieces behind the chunked layout: a workspace sized by elimrec_score_workspace_for has it)
-    const int use_b3 = score_bf16x3();
-    const ScoreLayout Lp = score_layout(B, U, I, S, K, chunked, d);
-    const bool bf16x3 = (chunked || matrix_chunks) && use_b3 && score_math() == 1 && (d == 32 || d == 64) && phase != 1 && workspace_bytes >= Lp.total;
-    hipStream_t s = (hipStream_t)stream;
-    const int tiles = n_item_tiles(I);
     char *ws = (char *)d_workspace;
-    float *partial = (float *)(ws + L.partial);
-    float *mean = (float *)(ws + L.mean);
-    float *wscores = (float *)(ws + L.scores);
-    int32_t *fallback = (int32_t *)(ws + L.flags);
-    float *cand_val = (float *)(ws + L.cand_val);
-    int32_t *cand_idx = (int32_t *)(ws + L.cand_idx);
-    ScoreArgs a;
+    c.s = (hipStream_t)stream;
+    c.mean_dst = phase == 1 ? d_row_sum : (float *)(ws + L.mean);
+    c.mean_div = phase == 1 ? 1 : I;
+    c.train_ptr = d_train_ptr; c.train_items = d_train_items;
+    c.d_scores = d_scores; c.topk_idx = d_topk_idx; c.topk_val = d_topk_val;
+    c.run_val = d_topk_val ? d_topk_val : (float *)(ws + L.cand_val);      // (the caller's list is the running list)
+    c.thr = (float *)(ws + L.cand_idx);
+    c.fallback = (int32_t *)(ws + L.flags);
+    c.K = K; c.tie_order = tie_order; c.id_offset = id_offset;
+    c.bits = (uint32_t *)(ws + L.bits); c.bits_ld = (I + 31) / 32;
+    c.planes = nullptr; c.inrm = nullptr;
+    if (p.bf16x3) {
+        c.planes = (uint4 *)(ws + L.planes);
+        c.inrm = (float *)(ws + L.planes + (size_t)(I > SCORE_CHUNK ? SCORE_CHUNK : I) * 3 * (size_t)((1 + S) * d) * 2);
+    }
+    ScoreArgs &a = c.a;
     a.Y = d_Y; a.ldy = ldy; a.U = U; a.I = I; a.users = d_users; a.B = B; a.d = d; a.S = S; a.head_mask = head_mask;
-    a.fusion_mode = fusion_mode; a.predict_type = predict_type; a.row_mean = mean; a.partial = partial;
-    a.scores = d_scores ? d_scores : wscores; a.lds = d_scores ? lds : (chunked ? SCORE_CHUNK : I);
+    a.fusion_mode = fusion_mode; a.predict_type = predict_type; a.row_mean = (float *)(ws + L.mean); a.partial = (float *)(ws + L.partial);
+    a.scores = d_scores ? d_scores : (float *)(ws + L.scores); a.lds = d_scores ? lds : (p.chunked ? SCORE_CHUNK : I);
     a.item0 = 0; a.item_end = I; a.planes = nullptr; a.inrm = nullptr; a.thr = nullptr;
+    // lists of K <= RM_KMAX from the 16-user scorers: the selection reads the scorer's tile maxima and a bitmap of the masked items
+    a.tile_max = (p.t16 && d_topk_idx && K <= RM_KMAX) ? (float *)(ws + L.tmax) : nullptr;
+    a.tmax_ld = n_item_tiles(p.chunked ? SCORE_CHUNK : I);
     score_range_bounds(predict_type, fusion_mode, &a.lo, &a.hi);      // the range invariant of the (predict type, fusion mode)
     a.range_flag = score_range_flag();
-    float *wsqn = (float *)(ws + L.sqn);
-    if (!d_sqnorm && predict_type != 0) {            // not supplied: compute the whole table for this call
-        const int64_t N = U + I;
-        hipLaunchKernelGGL(row_sqnorm_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, d_Y, ldy, N, d, 1 + S, wsqn);
-        ELIMREC_LAUNCH_CHECK("row_sqnorm");
+    int rc = score_prepare(c, d_sqnorm, (float *)(ws + L.sqn), phase, d_row_sum, I_total);
+    if (rc) return rc;
+    if (predict_type == 2 && phase != 2) {
+        rc = p.bf16x3 ? score_pass1_bf16x3(c) : score_pass1_whole(c);
+        if (rc) return rc;
     }
-    a.sqn = d_sqnorm ? d_sqnorm : wsqn;
-    const bool own_pass1 = predict_type == 2 && phase != 2;      // phase 2: the mean comes from the all-reduced sums
-    float *mean_dst = phase == 1 ? d_row_sum : mean;            // phase 1: sums (divisor 1), straight to the caller
-    const int64_t mean_div = phase == 1 ? 1 : I;
-    if (phase == 2 && predict_type == 2) {
-        hipLaunchKernelGGL(mean_from_sum_kernel, dim3((B + 255) / 256), dim3(256), 0, s, (const float *)d_row_sum, B, I_total, mean);
-        ELIMREC_LAUNCH_CHECK("mean_from_sum");
-    }
-    uint32_t *wbits = (uint32_t *)(ws + L.bits);
-    float *wtmax = (float *)(ws + L.tmax);
-    const int64_t bits_ld = (I + 31) / 32;
-    a.tile_max = nullptr; a.tmax_ld = n_item_tiles(chunked ? SCORE_CHUNK : I);
-    bool tiles_ready = false;
-    ELIMREC_REQUIRE(chunked || a.lds >= I, "score_topk: lds < I");
-    if (t16_path) {
-        // 16 users per wave, 128 per workgroup, a persistent grid over 16-item tiles (two workgroups per CU)
-        const int t16 = (int)((I + TI - 1) / TI);
-        const bool fast = score_math() == 1;
-        if (d_topk_idx && K <= 256) {    // the selection reads the scorer's tile maxima and a bitmap of the masked items
-            a.tile_max = wtmax;
-            tiles_ready = true;
-            if (d_train_ptr) {
-                ELIMREC_REQUIRE(d_train_items, "score_topk: train_items missing");
-                hipLaunchKernelGGL(train_bits_kernel, dim3(B), dim3(256), 0, s, d_train_ptr, d_train_items, I, wbits, bits_ld);
-                ELIMREC_LAUNCH_CHECK("train_bits");
-            }
-        }
-        auto t16_grid = [&](int pass) {      // chunks dealt evenly to at most 512 workgroups
-            const int chunks = (t16 + t16_sub(pass) - 1) / t16_sub(pass);
-            const int per = (chunks + 511) / 512;
-            return dim3((unsigned)((chunks + per - 1) / per), (B + TW * TU - 1) / (TW * TU));
-        };
-        const dim3 grid1 = t16_grid(1), grid = t16_grid(2);
-        auto t16_lds = [d](int pass, int nb) {
-            const int cols = (pass == 1 ? 1 : nb) * d;
-            return ((size_t)2 * t16_sub(pass) * TI * (cols + 4) + (size_t)TW * TU * (nb > 1 ? nb - 1 : 1) + TW * TU) * sizeof(float);
-        };
-#define ELIMREC_T16_LAUNCH_D(PASS, NB, PT, FM, FAST, GRID, DD)                                               \
-    do {                                                                                                   \
-        static bool attr = false;                                                                          \
-        if (!attr && t16_lds(PASS, NB) > 64 * 1024) {                                                      \
-            (void)hipFuncSetAttribute((const void *)score_t16_kernel<PASS, NB, PT, FM, FAST, DD>,          \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)t16_lds(PASS, NB)); \
-            attr = true;                                                                                   \
-        }                                                                                                  \
-        hipLaunchKernelGGL((score_t16_kernel<PASS, NB, PT, FM, FAST, DD>), GRID, dim3(512), t16_lds(PASS, NB), s, a, t16); \
-    } while (0)
-#define ELIMREC_T16_LAUNCH(PASS, NB, PT, FM, FAST, GRID)                                                     \
-    do {                                                                                                   \
-        if (d == 64) ELIMREC_T16_LAUNCH_D(PASS, NB, PT, FM, FAST, GRID, 64);                               \
-        else if (d == 128) ELIMREC_T16_LAUNCH_D(PASS, NB, PT, FM, FAST, GRID, 128);                        \
-        else ELIMREC_T16_LAUNCH_D(PASS, NB, PT, FM, FAST, GRID, 32);                                       \
-    } while (0)
-#define ELIMREC_T16_P2(NB, PT, FM)                                                                           \
-    do {                                                                                                   \
-        if (fast) ELIMREC_T16_LAUNCH(2, NB, PT, FM, true, grid);                                           \
-        else ELIMREC_T16_LAUNCH(2, NB, PT, FM, false, grid);                                               \
-    } while (0)
-#define ELIMREC_T16_PASS1(NB)                                                                               \
-    do {                                                                                                   \
-        if (fast) ELIMREC_T16_LAUNCH(1, NB, -1, -1, true, grid1);                                          \
-        else ELIMREC_T16_LAUNCH(1, NB, -1, -1, false, grid1);                                              \
-    } while (0)
-#define ELIMREC_T16_PASS2(NB)                                                                               \
-    do {                                                                                                   \
-        if (predict_type == 0) ELIMREC_T16_P2(NB, 0, 0);                                                   \
-        else if (predict_type == 1 && fusion_mode == 0) ELIMREC_T16_P2(NB, 1, 0);                          \
-        else if (predict_type == 1 && fusion_mode == 1) ELIMREC_T16_P2(NB, 1, 1);                          \
-        else if (predict_type == 1) ELIMREC_T16_P2(NB, 1, 2);                                              \
-        else if (fusion_mode == 0) ELIMREC_T16_P2(NB, 2, 0);                                               \
-        else if (fusion_mode == 1) ELIMREC_T16_P2(NB, 2, 1);                                               \
-        else ELIMREC_T16_P2(NB, 2, 2);                                                                     \
-    } while (0)
-        // pass 1 (TIE): row means of sigmoid(u.i) over the WHOLE catalogue
-        a.item0 = 0; a.item_end = I;
-        if (own_pass1 && !(bf16x3 && phase == 0)) {
-            if (S == 1) ELIMREC_T16_PASS1(2);
-            else if (S == 2) ELIMREC_T16_PASS1(3);
-            else ELIMREC_T16_PASS1(4);
-            ELIMREC_LAUNCH_CHECK("score_t16_pass1");
-            hipLaunchKernelGGL(row_mean_kernel, dim3(B), dim3(256), 0, s, partial, (int)grid1.x, B, mean_div, mean_dst);
-            ELIMREC_LAUNCH_CHECK("row_mean");
-        }
-        if (phase == 1) return 0;
-        // pass 2 over items [a.item0, a.item_end): the arguments, tile count and grid are the lambda's (they shadow the outer ones)
-        auto pass2 = [&](const ScoreArgs &a, int t16, dim3 grid) -> int {
-            if (S == 1) ELIMREC_T16_PASS2(2);
-            else if (S == 2) ELIMREC_T16_PASS2(3);
-            else ELIMREC_T16_PASS2(4);
-            ELIMREC_LAUNCH_CHECK("score_t16_pass2");
-            return 0;
-        };
-        auto b3_lds = [d](int pass, int nb) {
-            const int nh = pass == 1 ? 1 : nb;
-            return ((size_t)2 * t16b_win(pass, nb, d) * TI * (3 * nh * d / 8 + 1) * 16 + ((size_t)TWB * TU * (nb > 1 ? nb - 1 : 1) + TWB * TU) * sizeof(float));
-        };
-#define ELIMREC_T16B_LAUNCH1(NB, GRID, DD)                                                                   \
-    hipLaunchKernelGGL((score_t16b_kernel<1, NB, -1, -1, DD>), GRID, dim3(NTB), b3_lds(1, NB), s, a, t16)
-#define ELIMREC_T16B_LAUNCH(NB, PT, FM, GRID, DD)                                                            \
-    do {                                                                                                   \
-        static bool attr = false;                                                                          \
-        if (!attr && b3_lds(2, NB) > 64 * 1024) {                                                          \
-            (void)hipFuncSetAttribute((const void *)score_t16b_kernel<2, NB, PT, FM, DD>,                  \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)b3_lds(2, NB));     \
-            attr = true;                                                                                   \
-        }                                                                                                  \
-        hipLaunchKernelGGL((score_t16b_kernel<2, NB, PT, FM, DD>), GRID, dim3(NTB), b3_lds(2, NB), s, a, t16); \
-    } while (0)
-#define ELIMREC_T16B_D(NB, PT, FM, GRID)                                                                     \
-    do {                                                                                                   \
-        if (d == 64) ELIMREC_T16B_LAUNCH(NB, PT, FM, GRID, 64);                                            \
-        else ELIMREC_T16B_LAUNCH(NB, PT, FM, GRID, 32);                                                    \
-    } while (0)
-#define ELIMREC_T16B_PASS2(NB)                                                                              \
-    do {                                                                                                   \
-        if (predict_type == 0) ELIMREC_T16B_D(NB, 0, 0, grid);                                             \
-        else if (predict_type == 1 && fusion_mode == 0) ELIMREC_T16B_D(NB, 1, 0, grid);                    \
-        else if (predict_type == 1 && fusion_mode == 1) ELIMREC_T16B_D(NB, 1, 1, grid);                    \
-        else if (predict_type == 1) ELIMREC_T16B_D(NB, 1, 2, grid);                                        \
-        else if (fusion_mode == 0) ELIMREC_T16B_D(NB, 2, 0, grid);                                         \
-        else if (fusion_mode == 1) ELIMREC_T16B_D(NB, 2, 1, grid);                                         \
-        else ELIMREC_T16B_D(NB, 2, 2, grid);                                                               \
-    } while (0)
-        auto pass1_b3 = [&](const ScoreArgs &a, int t16, dim3 grid) -> int {
-            if (d == 64) { if (S == 1) ELIMREC_T16B_LAUNCH1(2, grid, 64); else if (S == 2) ELIMREC_T16B_LAUNCH1(3, grid, 64); else ELIMREC_T16B_LAUNCH1(4, grid, 64); }
-            else { if (S == 1) ELIMREC_T16B_LAUNCH1(2, grid, 32); else if (S == 2) ELIMREC_T16B_LAUNCH1(3, grid, 32); else ELIMREC_T16B_LAUNCH1(4, grid, 32); }
-            ELIMREC_LAUNCH_CHECK("score_t16b_pass1");
-            return 0;
-        };
-        auto pass2_b3 = [&](const ScoreArgs &a, int t16, dim3 grid) -> int {
-            if (S == 1) ELIMREC_T16B_PASS2(2);
-            else if (S == 2) ELIMREC_T16B_PASS2(3);
-            else ELIMREC_T16B_PASS2(4);
-            ELIMREC_LAUNCH_CHECK("score_t16b_pass2");
-            return 0;
-        };
-        if (chunked || matrix_chunks) {
-            // the catalogue goes through the scorer SCORE_CHUNK items at a time. chunked (only top-K wanted): a [B x SCORE_CHUNK]
-            // block instead of [B x I], a RUNNING top-K per user; matrix_chunks (the caller's [B x I] matrix): the same launches
-            // with every tile stored at its place in the matrix -- the same bits
-            const int nch = (int)((I + SCORE_CHUNK - 1) / SCORE_CHUNK);
-            if (own_pass1 && bf16x3 && phase == 0) {
-                // pass 1 (row means of sigmoid(u.i)) on the bf16 matrix cores too: chunk by chunk (the fused block's pieces only),
-                // <= 64 workgroups per user group and chunk, partials in (chunk, workgroup) order
-                uint4 *planes = (uint4 *)(ws + Lp.planes);
-                const int ug = (B + TWB * TU - 1) / (TWB * TU);
-                int n_part = 0;
-                for (int c = 0; c < nch; ++c) {
-                    ScoreArgs ac = a;
-                    ac.item0 = (int64_t)c * SCORE_CHUNK;
-                    ac.item_end = ac.item0 + SCORE_CHUNK < I ? ac.item0 + SCORE_CHUNK : I;
-                    const int64_t cnt = ac.item_end - ac.item0;
-                    const int tc = (int)((cnt + TI - 1) / TI);
-                    hipLaunchKernelGGL(split3_items_kernel, dim3((unsigned)((cnt * (d / 8) + 255) / 256)), dim3(256), 0, s, d_Y, ldy, U,
-                                       ac.item0, cnt, d, planes, (const float *)nullptr, 0, (float *)nullptr);
-                    ELIMREC_LAUNCH_CHECK("split3_items(pass 1)");
-                    int gx = tc < 64 ? tc : 64;
-                    ac.planes = planes;
-                    ac.partial = partial + (int64_t)n_part * B;
-                    int rc = pass1_b3(ac, tc, dim3((unsigned)gx, ug));
-                    if (rc) return rc;
-                    n_part += gx;
-                }
-                hipLaunchKernelGGL(row_mean_kernel, dim3(B), dim3(256), 0, s, partial, n_part, B, mean_div, mean_dst);
-                ELIMREC_LAUNCH_CHECK("row_mean");
-            }
-            // pass 2 + selection, chunk by chunk, with a RUNNING top-K per user: every chunk's selection leaves the best K so far and
-            // their K-th score; the next chunk's scorer stores a tile's scores of a user only where the tile's maximum reaches that
-            // score -- about one tile in seven after the 2 048-item pilot chunk, one in a hundred after the first full chunk -- so
-            // the [B x 16 384] block is hardly written at all (it was 537 MB per launch at 8 192 users). The lists after the last
-            // chunk are the result: no merge launch. tie_order 0: topk_tiles_kernel, lists by (score desc, id asc); tie_order 1:
-            // ref_order_kernel, the reference's heap carried from chunk to chunk (its top IS the K-th best score so far).
-            float *thrbuf = (float *)cand_idx;                           // [B]
-            float *run_val = d_topk_val ? d_topk_val : cand_val;         // [B x K] (the caller's list is the running list)
-            int64_t at = 0;
-            for (int c = 0; at < I; ++c) {
-                ScoreArgs ac = a;
-                ac.item0 = at;
-                const int64_t len = (chunked && c == 0 && I > SCORE_PILOT) ? SCORE_PILOT : SCORE_CHUNK;
-                ac.item_end = ac.item0 + len < I ? ac.item0 + len : I;
-                at = ac.item_end;
-                if (chunked) ac.thr = c == 0 ? nullptr : thrbuf;
-                else {                                                   // this chunk's columns of the [B x I] block
-                    ac.scores = a.scores + ac.item0;
-                    ac.lds = a.lds;
-                    ac.thr = nullptr;
-                    if (a.tile_max) ac.tile_max = a.tile_max + ac.item0 / TI;
-                }
-                const int64_t cnt = ac.item_end - ac.item0;
-                const int tc = (int)((cnt + TI - 1) / TI);
-                // ~512 workgroups per launch in all: a workgroup walks several tiles with its users' operands resident
-                const int wu = (bf16x3 ? TWB : TW) * TU;               // users per workgroup
-                const int ug = (B + wu - 1) / wu;
-                int gx = 512 / ug > 0 ? 512 / ug : 1;
-                if (gx > tc) gx = tc;
-                const int per = (tc + gx - 1) / gx;
-                int rc = 0;
-                if (bf16x3) {
-                    const int cols = (1 + S) * d;
-                    uint4 *planes = (uint4 *)(ws + Lp.planes);
-                    // (the chunk's inverse item norms behind its planes; predict type normal has no heads to normalise)
-                    float *inrm = (float *)(ws + Lp.planes + (size_t)(I > SCORE_CHUNK ? SCORE_CHUNK : I) * 3 * (size_t)cols * 2);
-                    hipLaunchKernelGGL(split3_items_kernel, dim3((unsigned)((cnt * (cols / 8) + 255) / 256)), dim3(256), 0, s, d_Y, ldy, U,
-                                       ac.item0, cnt, cols, planes, predict_type != 0 ? a.sqn : (const float *)nullptr, 1 + S,
-                                       predict_type != 0 ? inrm : (float *)nullptr);
-                    ELIMREC_LAUNCH_CHECK("split3_items");
-                    ac.planes = planes;
-                    ac.inrm = inrm;
-                    rc = pass2_b3(ac, tc, dim3((unsigned)((tc + per - 1) / per), ug));
-                } else {
-                    rc = pass2(ac, tc, dim3((unsigned)((tc + per - 1) / per), ug));
-                }
-                if (rc) return rc;
-                if (!chunked) continue;
-                if (tie_order == 1) {
-                    hipLaunchKernelGGL(ref_order_kernel<true>, dim3((unsigned)((B + 3) / 4)), dim3(256), (size_t)K * 32, s,
-                                       (const float *)ac.scores, ac.lds, cnt, (const float *)wtmax, ac.tmax_ld, B, K,
-                                       d_train_ptr ? (const uint32_t *)wbits : (const uint32_t *)nullptr, bits_ld, ac.item0, d_topk_idx,
-                                       run_val, (int64_t)K, thrbuf, c == 0 ? 1 : 0, at >= I ? 1 : 0);
-                    ELIMREC_LAUNCH_CHECK("ref_order(chunk)");
-                } else {
-                    hipLaunchKernelGGL(topk_tiles_kernel, dim3(B), dim3(256), 0, s, ac.scores, ac.lds, cnt, (const float *)wtmax, ac.tmax_ld,
-                                       tc, K, d_train_ptr, d_train_ptr ? (const uint32_t *)wbits : (const uint32_t *)nullptr, bits_ld,
-                                       d_topk_idx, run_val, fallback, ac.item0, (int64_t)K, (int64_t)0, thrbuf, c == 0 ? 1 : 0);
-                    ELIMREC_LAUNCH_CHECK("topk_tiles(chunk)");
-                }
-            }
-            if (chunked) {
-                if (a.range_flag) {
-                    hipLaunchKernelGGL(range_check_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, (const float *)run_val,
-                                       (const int32_t *)d_topk_idx, B, K, a.lo, a.hi, predict_type == 2 ? (const float *)mean : (const float *)nullptr,
-                                       a.range_flag);
-                    ELIMREC_LAUNCH_CHECK("range_check");
-                }
-                if (id_offset) {
-                    hipLaunchKernelGGL(add_id_offset_kernel, dim3((unsigned)(((int64_t)B * K + 255) / 256)), dim3(256), 0, s, d_topk_idx,
-                                       (int64_t)B * K, (int32_t)id_offset);
-                    ELIMREC_LAUNCH_CHECK("add_id_offset");
-                }
-                return 0;
-            }
-        } else { int rc = pass2(a, t16, grid); if (rc) return rc; }
-#undef ELIMREC_T16
-#undef ELIMREC_T16_P2
-#undef ELIMREC_T16_LAUNCH
-#undef ELIMREC_T16_LAUNCH_D
-    } else {
-        dim3 grid(tiles, (B + MU - 1) / MU);
-        if (own_pass1) {
-            hipLaunchKernelGGL(score_mfma_kernel<1>, grid, dim3(256), 0, s, a);
-            ELIMREC_LAUNCH_CHECK("score_mfma_pass1");
-            hipLaunchKernelGGL(row_mean_kernel, dim3(B), dim3(256), 0, s, partial, tiles, B, mean_div, mean_dst);
-            ELIMREC_LAUNCH_CHECK("row_mean");
-        }
-        if (phase == 1) return 0;
-        hipLaunchKernelGGL(score_mfma_kernel<2>, grid, dim3(256), 0, s, a);
-        ELIMREC_LAUNCH_CHECK("score_mfma_pass2");
-    }
-    if (d_train_ptr && (d_scores || !tiles_ready)) {       // the caller's score matrix is masked; a private one only if a sweep reads it
-        ELIMREC_REQUIRE(d_train_items, "score_topk: train_items missing");
-        hipLaunchKernelGGL(mask_train_kernel, dim3(B), dim3(128), 0, s, a.scores, a.lds, d_train_ptr, d_train_items, B);
-        ELIMREC_LAUNCH_CHECK("mask_train");
-    }
-    if (d_topk_idx && tie_order == 1) {
-        // the reference's heap over the whole row: guided by the tile maxima where the scorer left them (the private matrix is
-        // then unmasked: the bitmap), item by item otherwise (the matrix is masked)
-        if (tiles_ready)
-            hipLaunchKernelGGL(ref_order_kernel<true>, dim3((unsigned)((B + 3) / 4)), dim3(256), (size_t)K * 32, s, (const float *)a.scores,
-                               a.lds, I, (const float *)wtmax, a.tmax_ld, B, K, d_train_ptr ? (const uint32_t *)wbits : (const uint32_t *)nullptr,
-                               bits_ld, (int64_t)0, d_topk_idx, d_topk_val, (int64_t)K, (float *)nullptr, 1, 1);
-        else
-            hipLaunchKernelGGL(ref_order_kernel<false>, dim3((unsigned)((B + 3) / 4)), dim3(256), (size_t)K * 32, s, (const float *)a.scores,
-                               a.lds, I, (const float *)nullptr, (int64_t)0, B, K, (const uint32_t *)nullptr, (int64_t)0, (int64_t)0,
-                               d_topk_idx, d_topk_val, (int64_t)K, (float *)nullptr, 1, 1);
-        ELIMREC_LAUNCH_CHECK("ref_order");
-        if (id_offset) {
-            hipLaunchKernelGGL(add_id_offset_kernel, dim3((unsigned)(((int64_t)B * K + 255) / 256)), dim3(256), 0, s, d_topk_idx,
-                               (int64_t)B * K, (int32_t)id_offset);
-            ELIMREC_LAUNCH_CHECK("add_id_offset");
-        }
-    } else if (d_topk_idx) {
-        int G = 32;
-        while (G < 2 * K && G < 1024) G *= 2;
-        if (tiles_ready) {
-            hipLaunchKernelGGL(topk_tiles_kernel, dim3(B), dim3(256), 0, s, a.scores, a.lds, I, (const float *)wtmax, a.tmax_ld,
-                               (int)a.tmax_ld, K, d_train_ptr, d_train_ptr ? (const uint32_t *)wbits : (const uint32_t *)nullptr,
-                               bits_ld, d_topk_idx, d_topk_val, fallback, (int64_t)0, (int64_t)K, (int64_t)0, (float *)nullptr, 0);
-            ELIMREC_LAUNCH_CHECK("topk_tiles");
-        } else if (2 * K <= 1024) {
-            hipLaunchKernelGGL(topk_select_kernel, dim3(B), dim3(1024), 0, s, a.scores, a.lds, I, K, G, d_topk_idx,
-                               d_topk_val, fallback);
-            ELIMREC_LAUNCH_CHECK("topk_select");
-            hipLaunchKernelGGL(topk_kernel, dim3(B), dim3(1024), 0, s, a.scores, a.lds, I, K, d_topk_idx, d_topk_val,
-                               (const int32_t *)fallback, (const uint32_t *)nullptr, (int64_t)0, (int64_t)0, (int64_t)K, (int64_t)0);
-        } else {
-            hipLaunchKernelGGL(topk_kernel, dim3(B), dim3(1024), 0, s, a.scores, a.lds, I, K, d_topk_idx, d_topk_val,
-                               (const int32_t *)nullptr, (const uint32_t *)nullptr, (int64_t)0, (int64_t)0, (int64_t)K, (int64_t)0);
-        }
-        ELIMREC_LAUNCH_CHECK("topk");
-        if (id_offset) {
-            hipLaunchKernelGGL(add_id_offset_kernel, dim3((unsigned)(((int64_t)B * K + 255) / 256)), dim3(256), 0, s, d_topk_idx,
-                               (int64_t)B * K, (int32_t)id_offset);
-            ELIMREC_LAUNCH_CHECK("add_id_offset");
-        }
-    }
-    if (a.range_flag && t16_path && ((d_topk_idx && d_topk_val) || predict_type == 2)) {
-        const bool lists = d_topk_idx && d_topk_val;
-        hipLaunchKernelGGL(range_check_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, lists ? (const float *)d_topk_val : (const float *)nullptr,
-                           (const int32_t *)d_topk_idx, B, K, a.lo, a.hi, predict_type == 2 ? (const float *)mean : (const float *)nullptr, a.range_flag);
-        ELIMREC_LAUNCH_CHECK("range_check");
-    }
-    return 0;
+    if (phase == 1) return 0;
+    rc = (p.chunked || p.matrix_chunks) ? score_pass2_chunks(c) : score_pass2_whole(c);
+    if (!rc && !p.chunked) rc = score_select(c);      // (the chunked form selected chunk by chunk)
+    return rc ? rc : score_finish(c);
 }
 
 // The check every scoring call ends with, over lists the caller holds (d_topk_val / d_topk_idx [B x K]; d_row_mean [B] nullable):
@@ -2239,6 +2242,10 @@ extern "C" int elimrec_topk_reference_order(const float *h_scores, int64_t n_row
     return 0;
 }
 
+template <int NB, int DT, bool FAST> static void launch_cand(dim3 grid, const CandArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL((score_cand_kernel<NB, DT, FAST>), grid, dim3(256), 0, s, a);
+}
+
 // Candidate lists instead of the whole catalogue (score_cand_kernel): d_scores [B x width] (leading dimension lds) = row b's
 // candidates' scores in list order, then -inf; TIE needs d_row_sum (elimrec_score_topk_shard phase 1 over the whole catalogue).
 extern "C" int elimrec_score_candidates(const float *d_Y, int64_t ldy, int64_t U, int64_t I, const int64_t *d_users, int B,
@@ -2266,23 +2273,13 @@ extern "C" int elimrec_score_candidates(const float *d_Y, int64_t ldy, int64_t U
     hipStream_t s = (hipStream_t)stream;
     const bool fast = score_math() == 1;
     const int dt = d <= 64 ? 1 : (d <= 128 ? 2 : 0);
-#define ELIMREC_CAND_LAUNCH(NB, DT)                                                                          \
-    do {                                                                                                   \
-        if (fast) hipLaunchKernelGGL((score_cand_kernel<NB, DT, true>), grid, dim3(256), 0, s, a);         \
-        else hipLaunchKernelGGL((score_cand_kernel<NB, DT, false>), grid, dim3(256), 0, s, a);             \
-    } while (0)
-#define ELIMREC_CAND_NB(NB)                                                                                  \
-    do {                                                                                                   \
-        if (dt == 1) ELIMREC_CAND_LAUNCH(NB, 1);                                                           \
-        else if (dt == 2) ELIMREC_CAND_LAUNCH(NB, 2);                                                      \
-        else ELIMREC_CAND_LAUNCH(NB, 0);                                                                   \
-    } while (0)
-    if (S == 0) ELIMREC_CAND_NB(1);
-    else if (S == 1) ELIMREC_CAND_NB(2);
-    else if (S == 2) ELIMREC_CAND_NB(3);
-    else ELIMREC_CAND_NB(4);
-#undef ELIMREC_CAND_NB
-#undef ELIMREC_CAND_LAUNCH
+    with_nb<true>(S, [&](auto nb) { with_fast(fast, [&](auto f) {
+        constexpr int NB = decltype(nb)::value;
+        constexpr bool FAST = decltype(f)::value;
+        if (dt == 1) launch_cand<NB, 1, FAST>(grid, a, s);
+        else if (dt == 2) launch_cand<NB, 2, FAST>(grid, a, s);
+        else launch_cand<NB, 0, FAST>(grid, a, s);
+    }); });
     ELIMREC_LAUNCH_CHECK("score_candidates");
     return 0;
 }

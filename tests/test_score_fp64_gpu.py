@@ -28,6 +28,7 @@ Case -> kernel form (the dispatch conditions of score_topk_impl):
                                   own score matrix
   test_item_shards                elimrec_score_topk_shard phases 1 / 2: mean_from_sum_kernel, id_offset, I_total
   test_candidate_lists            score_cand_kernel<NB 1..4, DT 1|2|0, FAST 0|1>, TIE fed by phase 1
+  test_workspace_for_is_exact     elimrec_score_workspace_for against what the call accepts (one plan for both), generic / t16 / t16b
   test_row_sqnorms_*              row_sqnorm_kernel against float64 sums of squares, (d + 4) 2^-24 relative
 
 Worst err / tol measured on an MI355X (run with -s: every case prints err, tol and E32, the module its worst ratios at the end):
@@ -448,6 +449,47 @@ def test_item_shards(eval_math):
                 outside[:, i1:] = False
                 best_out = ref64.masked_fill(~outside, -np.inf).max(1).values
                 assert bool((best_out <= ref64.gather(1, gi).min(1).values + 2 * tol).all()), what
+
+
+# --------------------------------------------------------------------------- workspace sizing
+PLANES_IN_SIZING = (32, 64)      # recdims whose elimrec_score_workspace_for figure holds room for the bf16 piece planes
+
+
+def test_workspace_for_is_exact():
+    """The sizing function and the call share one plan: a workspace of exactly ops.score_workspace(..., d=d) bytes is accepted and
+    gives the bits of a workspace 1 MiB larger (lists, and the matrix where one is passed); 256 bytes fewer is refused as too small.
+    FAST math only (the bf16x3 gate depends on the size). 18 433 items: the 2 048-item pilot chunk, one full chunk and a 1-item
+    tail; K = 300 is beyond the tile-guided selection: the private [B x I] block, scored in chunks.
+    The refusal is NOT asserted at recdim 64: there the figure includes the piece planes, which the call treats as optional (without
+    them it takes the fp32 form), so a workspace 256 bytes short of it is accepted -- the rule the call has always had."""
+    from elimrec_amd import ops
+    B, U, S = 5, 7, 3
+    g = torch.Generator().manual_seed(7)
+    users = torch.tensor([0, 6, 3, 1, 3], device=DEV)
+    with _Switches(True):
+        for d in (48, 64, 128):
+            for I in (300, 18433):
+                Y = torch.randn((U + I, (1 + S) * d), generator=g).to(DEV)
+                for K in (10, 300):
+                    for want_scores in (False, True):
+                        def call(nbytes):
+                            ws = torch.empty(nbytes, dtype=torch.uint8, device=DEV)
+                            idx = torch.full((B, K), -1, dtype=torch.int32, device=DEV)
+                            val = torch.full((B, K), NAN, device=DEV)
+                            sc = torch.full((B, I), NAN, device=DEV) if want_scores else None
+                            ops.score_topk(Y, U, I, users, d, S, 0b111, "hm", "TIE", ws, scores=sc, K=K, topk_idx=idx, topk_val=val)
+                            return idx, val, sc
+                        what = "d=%d I=%d K=%d scores=%s" % (d, I, K, want_scores)
+                        need = ops.score_workspace(B, U, I, S, K, topk_only=not want_scores, d=d)
+                        idx, val, sc = call(need)
+                        idx2, val2, sc2 = call(need + (1 << 20))
+                        assert torch.equal(idx, idx2) and _bits_equal(val, val2), ("lists differ with a roomier workspace", what)
+                        assert bool((idx >= 0).all()) and not bool(torch.isnan(val).any()), what
+                        if want_scores:
+                            assert _bits_equal(sc, sc2) and not bool(torch.isnan(sc).any()), ("matrix differs with a roomier workspace", what)
+                        if d not in PLANES_IN_SIZING:
+                            with pytest.raises(RuntimeError, match="workspace too small"):
+                                call(need - 256)
 
 
 # --------------------------------------------------------------------------- candidate lists
