@@ -60,6 +60,14 @@ class BasicModel(nn.Module):
     def test(self):
         return self.test_evaluator.evaluate(self)
 
+    # (overall final, overall buf, group final, group buf) from one pass; the overall pair is what evaluate() / test() return
+    # without group_view, the group pair is (None, None) then
+    def evaluate_with_overall(self):
+        return self.valid_evaluator.evaluate_with_overall(self)
+
+    def test_with_overall(self):
+        return self.test_evaluator.evaluate_with_overall(self)
+
     # ---- generic losses on top of getEmbedding (BasicModel.py:59-113). EliMRec overrides bpr_loss; these are the
     # reference's base-class versions, differentiable through EliMRec.compute()'s autograd bridge.
     def bpr_loss(self, users, pos, neg):

@@ -2220,6 +2220,124 @@ extern "C" int elimrec_rank_metrics(const int32_t *d_topk_idx, int B, int K, con
     return 0;
 }
 
+// ---- per-group means of the metric rows (grouped evaluation: evaluator/grouped_evaluator.py:63-112 takes one evaluator pass
+// and one float32 np.mean per user group; here the rows are scored once and reduced on the device)
+// A group is a CSR segment of row indices. Two launches, every sum in a fixed order, float64 throughout:
+//   1. group_partial_kernel: a wave takes (segment, chunk of GM_CHUNK listed rows, tile of 64 columns); a lane owns a column
+//      and adds the chunk's rows in listed order. The wave reads 64 list entries with one load and takes each row's index from
+//      there as a scalar; GM_UNROLL rows' loads are issued before the first of them is added -- the additions stay one chain,
+//      the loads do not wait on it.
+//   2. group_finish_kernel: per (segment, column) the chunk partials in ascending order, divided by the segment length in
+//      float64, rounded to float32 once.
+// The partial of chunk c of segment g lives in slot ptr[g] / GM_CHUNK + g + c: segment g has at most
+// ptr[g + 1] / GM_CHUNK - ptr[g] / GM_CHUNK + 1 chunks, so the slots of different segments never overlap, there are at most
+// n_listed / GM_CHUNK + G of them, and no prefix sum over the segments is needed. A slot's value depends on its segment's rows
+// alone -- not on the grid, the other segments or timing -- and every slot that is read has been written by launch 1 of the same
+// call (the workspace needs no initialisation).
+constexpr int GM_CHUNK = 256, GM_UNROLL = 8, GM_CMAX = 8 * RM_KMAX;
+
+__device__ __forceinline__ int64_t gm_ptr(const int64_t *__restrict__ ptr, int g, int64_t n_listed) {
+    const int64_t p = ptr[g];
+    return p < 0 ? 0 : (p > n_listed ? n_listed : p);         // (a pointer outside the list reads nothing)
+}
+
+__global__ __launch_bounds__(64) void group_partial_kernel(const float *__restrict__ rows, int64_t n_rows, int C, int64_t ld,
+                                                           const int64_t *__restrict__ gptr, const int32_t *__restrict__ grows,
+                                                           int64_t n_listed, int G, int n_tiles, double *__restrict__ partial) {
+    const int lane = threadIdx.x;
+    const int64_t slot = blockIdx.x / n_tiles;
+    const int col = (int)(blockIdx.x % n_tiles) * 64 + lane;
+    // the last segment whose first slot is <= this one (first slots ascend strictly with g)
+    int lo = 0, hi = G - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (gm_ptr(gptr, mid, n_listed) / GM_CHUNK + mid <= slot) lo = mid; else hi = mid - 1;
+    }
+    const int64_t seg_begin = gm_ptr(gptr, lo, n_listed), seg_end = gm_ptr(gptr, lo + 1, n_listed);
+    const int64_t begin = seg_begin + (slot - (seg_begin / GM_CHUNK + lo)) * GM_CHUNK;
+    if (begin < seg_begin || begin >= seg_end) return;          // a slot no chunk owns (wave-uniform)
+    const int n = (int)(seg_end - begin < GM_CHUNK ? seg_end - begin : GM_CHUNK);
+    const int32_t *__restrict__ list = grows + begin;
+    const bool col_ok = col < C;
+    const float *__restrict__ src = rows + (col_ok ? col : 0);
+    double acc = 0.0;
+    for (int j0 = 0; j0 < n; j0 += 64) {
+        // 64 entries of the list as one coalesced load, an index outside the block marked (it is not read and adds nothing);
+        // every row's index then reaches the wave as a scalar
+        const int cnt = n - j0 < 64 ? n - j0 : 64;
+        int idx = lane < cnt ? list[j0 + lane] : -1;
+        if (idx < 0 || idx >= n_rows) idx = -1;
+        auto row_value = [&](int u) -> float {
+            const int r = __builtin_amdgcn_readlane(idx, u);
+            const float x = src[(int64_t)(r < 0 ? 0 : r) * ld];       // (unconditional: the loads of a group stay in flight together)
+            return r < 0 ? 0.f : x;
+        };
+        int u = 0;
+        for (; u + GM_UNROLL <= cnt; u += GM_UNROLL) {
+            float v[GM_UNROLL];
+#pragma unroll
+            for (int k = 0; k < GM_UNROLL; ++k) v[k] = row_value(u + k);
+#pragma unroll
+            for (int k = 0; k < GM_UNROLL; ++k) acc += (double)v[k];
+        }
+        for (; u < cnt; ++u) acc += (double)row_value(u);
+    }
+    if (col_ok) partial[slot * C + col] = acc;
+}
+
+__global__ __launch_bounds__(64) void group_finish_kernel(const double *__restrict__ partial, int C, const int64_t *__restrict__ gptr,
+                                                          int64_t n_listed, int n_tiles, float *__restrict__ means) {
+    const int g = blockIdx.x / n_tiles;
+    const int col = (int)(blockIdx.x % n_tiles) * 64 + threadIdx.x;
+    if (col >= C) return;
+    const int64_t seg_begin = gm_ptr(gptr, g, n_listed), seg_end = gm_ptr(gptr, g + 1, n_listed);
+    const int64_t len = seg_end - seg_begin;
+    float out = 0.f;                                            // an empty segment: zeros
+    if (len > 0) {
+        const int64_t n_chunks = (len + GM_CHUNK - 1) / GM_CHUNK;
+        const double *__restrict__ p = partial + (seg_begin / GM_CHUNK + g) * C + col;
+        double acc = 0.0;
+        for (int64_t c = 0; c < n_chunks; ++c) acc += p[c * C];
+        out = (float)(acc / (double)len);
+    }
+    means[(int64_t)g * C + col] = out;
+}
+
+extern "C" int elimrec_group_metric_means_chunk(void) { return GM_CHUNK; }
+
+extern "C" size_t elimrec_group_metric_means_workspace(int64_t n_listed_rows, int C, int G) {
+    if (n_listed_rows < 0 || C < 1 || G < 1) return 0;
+    return (size_t)(n_listed_rows / GM_CHUNK + G) * (size_t)C * sizeof(double);
+}
+
+extern "C" int elimrec_group_metric_means(const float *d_rows, int64_t n_rows, int C, int64_t ld, const int64_t *d_group_ptr,
+                                          const int32_t *d_group_rows, int64_t n_listed_rows, int G, float *d_means,
+                                          void *d_workspace, size_t workspace_bytes, void *stream) {
+    ELIMREC_REQUIRE(d_group_ptr && d_means && d_workspace, "group_metric_means: null pointer");
+    ELIMREC_REQUIRE(((uintptr_t)d_workspace & 7) == 0, "group_metric_means: the workspace must be 8-byte aligned");
+    ELIMREC_REQUIRE(C >= 1 && C <= GM_CMAX, "group_metric_means: 1 <= C <= %d", GM_CMAX);
+    ELIMREC_REQUIRE(G >= 1 && n_rows >= 0 && n_listed_rows >= 0, "group_metric_means: need G >= 1, n_rows >= 0, n_listed_rows >= 0");
+    ELIMREC_REQUIRE(ld >= C, "group_metric_means: ld < C");
+    ELIMREC_REQUIRE(n_listed_rows == 0 || (d_rows && d_group_rows && n_rows >= 1), "group_metric_means: rows are listed, but there are none");
+    ELIMREC_REQUIRE(workspace_bytes >= elimrec_group_metric_means_workspace(n_listed_rows, C, G),
+                    "group_metric_means: workspace too small (%zu < %zu bytes)", workspace_bytes,
+                    elimrec_group_metric_means_workspace(n_listed_rows, C, G));
+    const int n_tiles = (C + 63) / 64;
+    const int64_t slots = n_listed_rows / GM_CHUNK + G;
+    ELIMREC_REQUIRE(slots * n_tiles < (int64_t)INT32_MAX, "group_metric_means: %lld chunks x %d column tiles exceed one launch",
+                    (long long)slots, n_tiles);
+    hipStream_t s = (hipStream_t)stream;
+    if (n_listed_rows > 0) {
+        hipLaunchKernelGGL(group_partial_kernel, dim3((unsigned)(slots * n_tiles)), dim3(64), 0, s, d_rows, n_rows, C, ld, d_group_ptr,
+                           d_group_rows, n_listed_rows, G, n_tiles, (double *)d_workspace);
+        ELIMREC_LAUNCH_CHECK("group_metric_means (partials)");
+    }
+    hipLaunchKernelGGL(group_finish_kernel, dim3((unsigned)((int64_t)G * n_tiles)), dim3(64), 0, s, (const double *)d_workspace, C,
+                       d_group_ptr, n_listed_rows, n_tiles, d_means);
+    ELIMREC_LAUNCH_CHECK("group_metric_means");
+    return 0;
+}
+
 
 // The reference's OWN order among equal scores, for the rows that have any: evaluate.h:26-33 ranks a user's scores with
 // std::partial_sort_copy over the item ids under comp(x1, x2) = ratings[x1] > ratings[x2], whose result among ties is the heap order

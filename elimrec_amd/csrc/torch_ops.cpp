@@ -14,6 +14,8 @@
 //   score_topk(Y, U, I, users, d, S, head_mask, fusion_mode, predict_type, train_ptr?, train_items?, K, tie_order=0) -> (idx, val)
 //       (tie_order 1: the reference's partial_sort_copy order among equal scores, evaluate.h:26-33, replayed on the device)
 //   rank_metrics(topk_idx, truth_ptr, truth_items, metric_ids) -> f32[B x n_metrics x K]
+//   group_metric_means(rows f32[n x C], group_ptr i64[G+1], group_rows i32) -> f32[G x C]: per CSR segment of row indices the
+//       column means, float64 sums in listed order (the indices are checked on the host first: a synchronisation)
 //   sample_triplets(user_ids, ptr, items, num_items, n, seed, epoch) -> (users, pos, neg)
 //   score_candidates(Y, U, I, users, d, S, head_mask, fusion_mode, predict_type, cand_ptr, cand_items, width) -> f32[B x width]
 //       (each row: its candidates' scores in list order, then -inf)
@@ -165,6 +167,35 @@ at::Tensor rank_metrics(const at::Tensor &topk_idx, const at::Tensor &truth_ptr,
     check(elimrec_rank_metrics(t.data_ptr<int32_t>(), (int)t.size(0), (int)t.size(1), tp.data_ptr<int64_t>(), ti.data_ptr<int32_t>(),
                                ids.data(), (int)ids.size(), out.data_ptr<float>(), cur_stream()),
           "rank_metrics");
+    return out;
+}
+
+at::Tensor group_metric_means(const at::Tensor &rows, const at::Tensor &group_ptr, const at::Tensor &group_rows) {
+    const at::Tensor r = rowmajor(rows, "rows");
+    need(group_ptr, "group_ptr", at::kLong, 1); need(group_rows, "group_rows", at::kInt, 1);
+    const at::Tensor gp = group_ptr.contiguous(), gr = group_rows.contiguous();
+    const int64_t G = gp.numel() - 1, n_listed = gr.numel();
+    TORCH_CHECK(G >= 1, "elimrec::group_metric_means: group_ptr needs G + 1 >= 2 entries");
+    {   // no unchecked index reaches the kernel: the CSR is validated on the host
+        const at::Tensor hp = gp.cpu();
+        const int64_t *p = hp.data_ptr<int64_t>();
+        bool ok = p[0] == 0 && p[G] == n_listed;
+        for (int64_t g = 0; g < G && ok; ++g) ok = p[g] <= p[g + 1];
+        TORCH_CHECK(ok, "elimrec::group_metric_means: group_ptr must ascend from 0 to len(group_rows) = ", n_listed);
+        if (n_listed > 0) {
+            const int64_t lo = gr.min().item<int64_t>(), hi = gr.max().item<int64_t>();
+            TORCH_CHECK(lo >= 0 && hi < r.size(0), "elimrec::group_metric_means: row indices span [", lo, ", ", hi, "], the block has ",
+                        r.size(0), " rows");
+        }
+    }
+    at::Tensor out = at::empty({G, r.size(1)}, r.options());
+    const size_t need_ws = elimrec_group_metric_means_workspace(n_listed, (int)r.size(1), (int)G);
+    at::Tensor ws = at::empty({(int64_t)(need_ws ? need_ws : 1)}, r.options().dtype(at::kByte));
+    at::Tensor none = at::zeros({1}, gr.options());
+    check(elimrec_group_metric_means(r.data_ptr<float>(), r.size(0), (int)r.size(1), r.stride(0), gp.data_ptr<int64_t>(),
+                                     n_listed ? gr.data_ptr<int32_t>() : none.data_ptr<int32_t>(), n_listed, (int)G, out.data_ptr<float>(),
+                                     ws.data_ptr(), (size_t)ws.numel(), cur_stream()),
+          "group_metric_means");
     return out;
 }
 
@@ -386,6 +417,7 @@ TORCH_LIBRARY(elimrec, m) {
     m.def("adam_step_(Tensor(a!) p, Tensor g, Tensor(b!) m, Tensor(c!) v, float lr, float beta1, float beta2, float eps, float weight_decay, int step) -> Tensor(a!)");
     m.def("score_topk(Tensor Y, int U, int I, Tensor users, int d, int S, int head_mask, int fusion_mode, int predict_type, Tensor? train_ptr, Tensor? train_items, int K, int tie_order=0) -> (Tensor, Tensor)");
     m.def("rank_metrics(Tensor topk_idx, Tensor truth_ptr, Tensor truth_items, int[] metric_ids) -> Tensor");
+    m.def("group_metric_means(Tensor rows, Tensor group_ptr, Tensor group_rows) -> Tensor");
     m.def("sample_triplets(Tensor user_ids, Tensor ptr, Tensor items, int num_items, int n, int seed, int epoch) -> (Tensor, Tensor, Tensor)");
     m.def("bpr_head_bwd(Tensor grad_rows, Tensor keys, Tensor grad_out, int n_rows) -> Tensor");
     m.def("score_shard_row_sums(Tensor Y, int U, int I, Tensor users, int d, int S, int head_mask, int fusion_mode, int I_total) -> Tensor");
@@ -407,6 +439,7 @@ TORCH_LIBRARY_IMPL(elimrec, CUDA, m) {
     m.impl("adam_step_", &adam_step_);
     m.impl("score_topk", &score_topk);
     m.impl("rank_metrics", &rank_metrics);
+    m.impl("group_metric_means", &group_metric_means);
     m.impl("sample_triplets", &sample_triplets);
     m.impl("bpr_head_bwd", &bpr_head_bwd);
     m.impl("score_shard_row_sums", &score_shard_row_sums);

@@ -1,6 +1,7 @@
 """Full-catalogue top-K evaluation with the reference's facade (evaluator/proxy_evaluator.py:40-108,
 evaluator/backend/cpp/uni_evaluator.py:37-203): `ProxyEvaluator(...).evaluate(model)` ->
-(float32 ndarray over metrics x top_show, tab-joined "%.8f" string).
+(float32 ndarray over metrics x top_show, tab-joined "%.8f" string); with `group_view` the same per user group
+(GroupedEvaluator below: one scoring pass, the group means reduced on the device).
 
 What changed underneath: for a model that exposes `predict_device`, scoring, train-item masking,
 top-K and the metric curves all run on the GPU (csrc/eval.hip) and only the per-user metric rows
@@ -179,17 +180,27 @@ class UniEvaluator(object):
         the same rows -- and, the final mean being taken over the same matrix, the same bits -- as a single process.
         Default: the ranks of an initialised torch.distributed job (the cached tables are replicated on every rank)."""
         if test_users is None:
-            if getattr(self, "_default_users", None) is None:
-                self._default_users = list(self.user_pos_test.keys())
-            test_users = self._default_users
+            test_users = self.default_users()
+        all_dev = self._rows_of(model, test_users, shard)
+        return self._summary(all_dev.cpu().numpy())                       # [users, metrics*K]
+
+    def _rows_of(self, model, test_users, shard):
+        """evaluate()'s argument checks and its metric_rows call; the default users' index tensors are the cached ones."""
         cached = test_users is self._default_users
         if not isinstance(test_users, (list, tuple, set, np.ndarray)):
             raise TypeError("'test_user' must be a list, tuple, set or numpy array!")
         if not hasattr(model, "predict_device"):
             raise TypeError("model must expose predict_device(); host-side ranking is not part of this package")
-        test_users = list(test_users)
-        all_dev = self.metric_rows(model, test_users, shard=shard, cached=cached)
-        all_rows = all_dev.cpu().numpy()                                  # [users, metrics*K]
+        return self.metric_rows(model, list(test_users), shard=shard, cached=cached)
+
+    def default_users(self):
+        """The test users in evaluate()'s default order (the list whose index tensors stay cached on the device)."""
+        if getattr(self, "_default_users", None) is None:
+            self._default_users = list(self.user_pos_test.keys())
+        return self._default_users
+
+    def _summary(self, all_rows):
+        """Host rows [users, metrics*K] -> (float32 means at the shown K, their tab-joined "%.8f" string)."""
         final = np.mean(all_rows, axis=0).reshape(self.metrics_num, self.max_top)[:, self.top_show - 1].reshape(-1)
         buf = "\t".join(("%.8f" % x).ljust(12) for x in final)
         return final, buf
@@ -378,17 +389,126 @@ class UniEvaluator(object):
         return (out, idx, val) if return_topk else out
 
 
+def assign_user_groups(test_users, user_train_dict, group_view):
+    """The reference's user groups (evaluator/grouped_evaluator.py:63-80) without pandas: bounds [0] + group_view, a test user's
+    group is np.searchsorted(group_view, n_train) -- n_train in (lo, hi], so a user without training items lands in the first
+    group -- users beyond the last bound are discarded, groups without users are omitted; groups in ascending order of their
+    bounds, a group's users in the order of `test_users`.
+    -> (labels ["(lo,hi]:".ljust(12)], positions [int64 arrays of indices into test_users], number of discarded users)."""
+    if not isinstance(group_view, list):
+        raise TypeError("The type of 'group_view' must be `list`!")
+    for b in group_view:
+        if isinstance(b, bool) or not isinstance(b, (int, np.integer)) or b <= 0:
+            raise ValueError("group_view must hold strictly ascending positive integers, got %r" % (group_view,))
+    if any(hi <= lo for lo, hi in zip(group_view[:-1], group_view[1:])):
+        raise ValueError("group_view must hold strictly ascending positive integers, got %r" % (group_view,))
+    bounds = [0] + [int(b) for b in group_view]
+    n_train = np.fromiter((len(user_train_dict.get(u, [])) for u in test_users), dtype=np.int64, count=len(test_users))
+    group = np.searchsorted(np.asarray(bounds[1:], dtype=np.int64), n_train)
+    labels, positions = [], []
+    for g in range(len(group_view)):
+        at = np.flatnonzero(group == g)
+        if at.size:
+            labels.append(("(%d,%d]:" % (bounds[g], bounds[g + 1])).ljust(12))
+            positions.append(at.astype(np.int64))
+    if not labels:
+        raise ValueError("The splitting of user groups is not suitable!")
+    return labels, positions, int((group >= len(group_view)).sum())
+
+
+class GroupedEvaluator(object):
+    """Ranking quality per user group, the users bucketed by their number of TRAINING interactions (the reference's
+    evaluator/grouped_evaluator.py:12-112; group_view = [10, 30, 50, 100] -> (0,10], (10,30], (30,50], (50,100], heavier users
+    discarded). The reference runs one evaluator pass per group; here every test user is scored ONCE -- the inner UniEvaluator's
+    metric_rows over its default user order, so the full-catalogue, the sampled-negative, the user-sliced and the item-sharded
+    forms all apply -- and one launch pair (ops.group_metric_means, csrc/eval.hip) turns the [users x metrics*K] block into
+    [groups x metrics*K] float64-accumulated means on the device; only those cross to the host."""
+
+    def __init__(self, dataset, user_train_dict, user_test_dict, user_neg_test=None, metric=None, group_view=None, top_k=50,
+                 batch_size=1024, num_thread=8):
+        if not isinstance(group_view, list):
+            raise TypeError("The type of 'group_view' must be `list`!")
+        self.evaluator = UniEvaluator(dataset, user_train_dict, user_test_dict, user_neg_test, metric=metric, top_k=top_k,
+                                      batch_size=batch_size, num_thread=num_thread)
+        self.user_pos_train = user_train_dict
+        self.user_pos_test = user_test_dict
+        self.group_view = list(group_view)
+        users = self.evaluator.default_users()
+        self.group_labels, self._positions, self.num_discarded = assign_user_groups(users, user_train_dict, group_view)
+        self.group_sizes = [int(p.size) for p in self._positions]
+        self.grouped_user = {label: [users[i] for i in at] for label, at in zip(self.group_labels, self._positions)}
+        self._index = {}                   # device -> ops.GroupIndex: the groups as CSR over the rows of the default user order
+
+    # (BasicModel's --tie_order plumbing sets `.evaluator.tie_order` of the facade: it reaches the evaluator that ranks)
+    @property
+    def tie_order(self):
+        return self.evaluator.tie_order
+
+    @tie_order.setter
+    def tie_order(self, value):
+        self.evaluator.tie_order = value
+
+    def metrics_info(self):
+        return self.evaluator.metrics_info()
+
+    def _group_index(self, device):
+        hit = self._index.get(str(device))
+        if hit is None:
+            ptr = np.zeros(len(self._positions) + 1, dtype=np.int64)
+            np.cumsum(self.group_sizes, out=ptr[1:])
+            hit = ops.GroupIndex(ptr, np.concatenate(self._positions).astype(np.int32), len(self.evaluator.default_users()), device)
+            self._index[str(device)] = hit
+        return hit
+
+    def group_means(self, rows):
+        """Device rows [default users x metrics*K] (UniEvaluator.metric_rows) -> host float32 [groups x metrics*K]."""
+        out = torch.empty(len(self.group_labels), rows.shape[1], dtype=torch.float32, device=rows.device)
+        return ops.group_metric_means(rows, self._group_index(rows.device), None, out).cpu().numpy()
+
+    def format_groups(self, final):
+        """[groups x shown columns] -> the reference's multi-line string (grouped_evaluator.py:107-112)."""
+        return "".join("\n%s\t%s" % (label, "\t".join(("%.8f" % x).ljust(12) for x in row))
+                       for label, row in zip(self.group_labels, final))
+
+    def evaluate_rows(self, rows):
+        """(final [groups x metrics*len(top_show)] float32, buf) from the metric rows of the default users."""
+        ev = self.evaluator
+        means = self.group_means(rows)
+        final = means.reshape(len(self.group_labels), ev.metrics_num, ev.max_top)[:, :, ev.top_show - 1].reshape(len(self.group_labels), -1)
+        return final, self.format_groups(final)
+
+    def evaluate(self, model, shard=None):
+        ev = self.evaluator
+        return self.evaluate_rows(ev._rows_of(model, ev.default_users(), shard))
+
+    def evaluate_with_overall(self, model, shard=None):
+        """(overall final, overall buf, group final, group buf) from ONE scoring pass: the overall pair is UniEvaluator.evaluate's
+        own expression over the same rows -- the bits an evaluation without group_view has."""
+        ev = self.evaluator
+        rows = ev._rows_of(model, ev.default_users(), shard)
+        group_final, group_buf = self.evaluate_rows(rows)
+        final, buf = ev._summary(rows.cpu().numpy())
+        return final, buf, group_final, group_buf
+
+
 class ProxyEvaluator(object):
     def __init__(self, dataset, user_train_dict, user_test_dict, user_neg_test=None, metric=None, group_view=None,
                  top_k=50, batch_size=1024, num_thread=8):
         if group_view is not None:
-            raise NotImplementedError("group_view evaluation is out of scope (NeuRec.properties:27 sets None; the "
-                                      "reference's GroupedEvaluator cannot be constructed as shipped)")
-        self.evaluator = UniEvaluator(dataset, user_train_dict, user_test_dict, user_neg_test, metric=metric,
-                                      top_k=top_k, batch_size=batch_size, num_thread=num_thread)
+            self.evaluator = GroupedEvaluator(dataset, user_train_dict, user_test_dict, user_neg_test, metric=metric,
+                                              group_view=group_view, top_k=top_k, batch_size=batch_size, num_thread=num_thread)
+        else:
+            self.evaluator = UniEvaluator(dataset, user_train_dict, user_test_dict, user_neg_test, metric=metric,
+                                          top_k=top_k, batch_size=batch_size, num_thread=num_thread)
 
     def metrics_info(self):
         return self.evaluator.metrics_info()
 
     def evaluate(self, model):
         return self.evaluator.evaluate(model)
+
+    def evaluate_with_overall(self, model):
+        """(overall final, overall buf, group final, group buf); without group_view the group pair is (None, None)."""
+        if isinstance(self.evaluator, GroupedEvaluator):
+            return self.evaluator.evaluate_with_overall(model)
+        return self.evaluator.evaluate(model) + (None, None)

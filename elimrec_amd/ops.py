@@ -738,6 +738,71 @@ def rank_metrics(topk_idx, truth_ptr, truth_items, metric_ids, out):
     return out
 
 
+class GroupIndex(object):
+    """Groups of rows as CSR (group_ptr [G + 1], group_rows: row indices into a block of n_rows rows), CHECKED ON THE HOST --
+    ptr[0] = 0, ascending, ptr[G] = len(group_rows), every index in [0, n_rows) -- and then resident on `device`:
+    group_metric_means takes it as is, call after call, and no unchecked index ever reaches a kernel."""
+
+    def __init__(self, group_ptr, group_rows, n_rows, device):
+        ptr = np.ascontiguousarray(_host(group_ptr), dtype=np.int64).reshape(-1)
+        rows = _host(group_rows).reshape(-1)
+        if ptr.size < 2:
+            raise ValueError("elimrec_amd.ops.GroupIndex: group_ptr needs G + 1 >= 2 entries")
+        if rows.size and not np.issubdtype(rows.dtype, np.integer):
+            raise TypeError("elimrec_amd.ops.GroupIndex: group_rows must hold integers, got %s" % rows.dtype)
+        if ptr[0] != 0 or ptr[-1] != rows.size or (np.diff(ptr) < 0).any():
+            raise ValueError("elimrec_amd.ops.GroupIndex: group_ptr must ascend from 0 to len(group_rows) = %d" % rows.size)
+        if rows.size and (int(rows.min()) < 0 or int(rows.max()) >= int(n_rows)):
+            raise IndexError("elimrec_amd.ops.GroupIndex: row indices span [%d, %d], the block has %d rows"
+                             % (int(rows.min()), int(rows.max()), int(n_rows)))
+        self.n_rows, self.n_groups, self.n_listed = int(n_rows), int(ptr.size - 1), int(rows.size)
+        self.sizes = np.diff(ptr)
+        self.ptr = torch.from_numpy(ptr).to(device)
+        # (never empty: the kernels read nothing of it when n_listed = 0, the binding still wants a device tensor)
+        self.rows = torch.from_numpy(np.ascontiguousarray(rows if rows.size else np.zeros(1), dtype=np.int32)).to(device)
+
+
+def _host(x):
+    return x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+
+
+def group_metric_means(rows, group_ptr, group_rows, out, workspace=None):
+    """out [G x C] (float32, contiguous) = per group the column means of rows [n x C] (a column slice of a wider block is
+    fine): float64 sums in listed order, divided in float64, rounded once (elimrec_group_metric_means). group_ptr / group_rows:
+    the groups as CSR, host arrays or tensors -- checked on the host at every call (device tensors are copied back for it: a
+    synchronisation) -- or group_ptr = a GroupIndex (group_rows = None), checked once when it was built. workspace: uint8 device
+    tensor of at least elimrec_group_metric_means_workspace bytes (default: allocated here)."""
+    lib = _lib.load()
+    rp, ld = _rowmajor(rows, "rows")
+    n, C = rows.shape
+    if isinstance(group_ptr, GroupIndex):
+        index = group_ptr
+        if group_rows is not None and group_rows is not index.rows:
+            raise ValueError("elimrec_amd.ops.group_metric_means: a GroupIndex carries its own rows (pass group_rows=None)")
+        if index.n_rows > n or index.ptr.device != rows.device:
+            raise IndexError("elimrec_amd.ops.group_metric_means: the GroupIndex was checked for %d rows on %s, the block has %d on %s"
+                             % (index.n_rows, index.ptr.device, n, rows.device))
+    else:
+        index = GroupIndex(group_ptr, group_rows, n, rows.device)
+    G = index.n_groups
+    if not (isinstance(out, torch.Tensor) and out.is_contiguous() and tuple(out.shape) == (G, C)):
+        raise ValueError("elimrec_amd.ops.group_metric_means: out must be a contiguous [%d x %d] tensor" % (G, C))
+    if workspace is None:
+        workspace = torch.empty(max(1, int(lib.elimrec_group_metric_means_workspace(index.n_listed, C, G))), dtype=torch.uint8,
+                                device=rows.device)
+    _lib.check(lib.elimrec_group_metric_means(rp, n, C, ld, _dev(index.ptr, "group_ptr", torch.int64),
+                                              _dev(index.rows, "group_rows", torch.int32), index.n_listed, G, _dev(out, "out"),
+                                              _dev(workspace, "workspace", torch.uint8), workspace.numel(), _stream()),
+               "group_metric_means")
+    return out
+
+
+def __getattr__(name):
+    if name == "GROUP_MEAN_CHUNK":       # listed rows per partial sum of group_metric_means (a compile-time constant of the library)
+        return int(_lib.load().elimrec_group_metric_means_chunk())
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))
+
+
 def sample_triplets(user_ids, ptr, items, num_items, n, seed, epoch, users, pos, neg):
     _lib.check(_lib.load().elimrec_sample_triplets(_dev(user_ids, "user_ids", torch.int32), _dev(ptr, "ptr", torch.int64),
                                                    _dev(items, "items", torch.int32), user_ids.numel(), num_items, n,

@@ -29,5 +29,5 @@ def load():
     return torch.ops.elimrec
 
 
-OPS = ("propagate", "linear_fwd", "linear_bwd_w", "bpr_head_fwd", "adam_step_", "score_topk", "rank_metrics", "sample_triplets",
+OPS = ("propagate", "linear_fwd", "linear_bwd_w", "bpr_head_fwd", "adam_step_", "score_topk", "rank_metrics", "group_metric_means", "sample_triplets",
        "score_candidates", "sample_negatives")

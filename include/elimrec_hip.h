@@ -537,6 +537,23 @@ int elimrec_rank_metrics(const int32_t *d_topk_idx, int B, int K, const int64_t 
                          const int32_t *d_truth_items, const int *metric_ids, int n_metrics,
                          float *d_out, void *stream);
 
+/* Per-group column means of a row block (grouped evaluation, evaluator/grouped_evaluator.py:63-112: the metric rows of
+ * elimrec_rank_metrics averaged per user group). d_rows [n_rows x C] float32 with leading dimension ld >= C (a column slice
+ * of a wider block is fine), 1 <= C <= 2048. A group is a CSR segment of row indices: d_group_ptr int64[G + 1] (ascending,
+ * d_group_ptr[0] = 0, d_group_ptr[G] = n_listed_rows), d_group_rows int32[n_listed_rows], every index in [0, n_rows) -- the
+ * CALLER guarantees that (the Python wrapper checks it on the host; an index outside the block is not read and adds nothing).
+ * A row may be listed by no segment or by several. d_means [G x C]: for every column the float64 sum of the segment's rows,
+ * divided by the segment length in float64, rounded to float32 once; an empty segment gives zeros.
+ * Fixed order, no atomics: rows are added in listed order within chunks of elimrec_group_metric_means_chunk() listed rows,
+ * the chunks in ascending order by a second launch; the bits of a group's means depend on that group's rows alone -- not on
+ * the other groups of the call, the grid or timing. The workspace (8-byte aligned, elimrec_group_metric_means_workspace
+ * bytes) needs no initialisation. Two launches on `stream`, no host synchronisation. */
+int elimrec_group_metric_means(const float *d_rows, int64_t n_rows, int C, int64_t ld, const int64_t *d_group_ptr,
+                               const int32_t *d_group_rows, int64_t n_listed_rows, int G, float *d_means,
+                               void *d_workspace, size_t workspace_bytes, void *stream);
+size_t elimrec_group_metric_means_workspace(int64_t n_listed_rows, int C, int G);
+int elimrec_group_metric_means_chunk(void);
+
 /* ---------------------------------------------------------------- pairwise sampler (K20)
  * n triplets: user uniform over the `n_train_users` users with >= 1 training item (with
  * replacement), positive uniform over that user's training items, negative uniform over [0,I)

@@ -5,7 +5,8 @@
 
 Behaviour kept from the reference's `Net.run`: one pass of the pairwise sampler per epoch, validation every
 `test_step` epochs with predict_type TIE, a checkpoint + TE/TIE test pass whenever validation recall improves
-(not on epoch 0), early stop after `stop_cnt` epochs without improvement, the same log lines. The per-batch work,
+(not on epoch 0), early stop after `stop_cnt` epochs without improvement, the same log lines (`--group_view=[10,30,50,100]` adds
+the per-user-group table under each test line; validation and model selection stay on the overall metrics). The per-batch work,
 the sampler and the evaluator run on the GPU (elimrec_amd). `--data.input.dataset=synthetic` uses the seeded
 Tiktok-shape generator instead of reading files.
 
@@ -88,6 +89,9 @@ class Net(object):
             raise ValueError("unknown recommender '%s'" % cfg.recommender)
         self.recommender = EliMRec(cfg, self.dataset).to(cfg.device)
         self.cf_mode = cfg["cf_mode"] if "cf_mode" in cfg else True
+        # --group_view=[10,30,50,100]: metrics per user group (users bucketed by their number of training items) beside the overall
+        # ones, from the same scoring pass. Validation and model selection keep the overall metrics -- the bits of a run without it
+        self.grouped = cfg["group_view"] is not None
         Logger.info(count_parameters(self.recommender))
         self.opt = FusedAdam(self.recommender.parameters(), lr=cfg.lr, weight_decay=cfg.weight_decay)
         self.loss_name = str(cfg.loss)
@@ -203,7 +207,7 @@ class Net(object):
         for m in meters.values():
             m.reset_time()
         rec.predict_type = "TIE"
-        result, _ = rec.evaluate()
+        result = rec.evaluate_with_overall()[0] if self.grouped else rec.evaluate()[0]
         if result is not None:
             for key, value in zip(("precision", "recall", "ndcg"), result):
                 meters[key].update(val=value, epoch=epoch)
@@ -213,12 +217,16 @@ class Net(object):
     def test_all_effects(self):
         """TE and TIE metrics on the test split, formatted as the reference prints them."""
         rec, lines = self.recommender, {}
+        if self.grouped:
+            Logger.info(rec.test_evaluator.metrics_info())
         for effect in EFFECTS:
             rec.predict_type = effect
-            result, _ = rec.test()
+            result, _, _, group_table = rec.test_with_overall() if self.grouped else rec.test() + (None, None)
             assert result is not None
             lines[effect] = "  [{}]\t{}\t{}\t{}".format(effect, result[1], result[0], result[2])
             Logger.info(lines[effect])
+            if self.grouped:               # one line per user group: "(lo,hi]:" and the metrics in the header's order
+                Logger.info("  [{}] by training interactions:{}".format(effect, group_table))
         return lines
 
     # ------------------------------------------------------------------ the run
