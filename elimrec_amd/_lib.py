@@ -274,6 +274,8 @@ SIGNATURES = {
     "elimrec_sample_negatives": (c_i32, [c_ptr, c_ptr, c_i64, c_i64, c_i32, c_u64, c_ptr, c_ptr]),
     "elimrec_score_candidates": (c_i32, [c_ptr, c_i64, c_i64, c_i64, c_ptr, c_i32, c_i32, c_i32, c_u32, c_i32, c_i32,
                                          c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_i64, c_ptr]),
+    "elimrec_score_effects": (c_i32, [c_ptr, c_i64, c_i64, c_i64, c_ptr, c_i32, c_i32, c_i32, c_u32, c_i32,
+                                      c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_ptr]),
 }
 
 _lib = None

@@ -6,7 +6,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from .evaluator import ProxyEvaluator
+from .evaluator import EffectReport, ProxyEvaluator
 
 
 class BasicModel(nn.Module):
@@ -36,6 +36,13 @@ class BasicModel(nn.Module):
                 raise ValueError("tie_order must be id or reference")
             for ev in (self.valid_evaluator, self.test_evaluator):
                 ev.evaluator.tie_order = str(config["tie_order"])
+        # --effect_report=K (CLI-only, default 0 = off): the effect breakdown of the test users' top-K lists, its column means
+        # overall and per user group (evaluator.EffectReport)
+        k_report = int(config["effect_report"]) if "effect_report" in config else 0
+        if k_report < 0:
+            raise ValueError("effect_report must be 0 (off) or the K of the lists to break down")
+        self.effect_reporter = EffectReport(dataset, train, dataset.get_user_test_dict(), k_report,
+                                            group_view=config["group_view"]) if k_report else None
         self.infonce_criterion = nn.CrossEntropyLoss()          # BasicModel.py:32
 
     def getFileName(self):
@@ -67,6 +74,10 @@ class BasicModel(nn.Module):
 
     def test_with_overall(self):
         return self.test_evaluator.evaluate_with_overall(self)
+
+    def effect_report(self):
+        """(final, buf) of evaluator.EffectReport over the test users under the current predict type; None when --effect_report is off."""
+        return self.effect_reporter.evaluate(self) if self.effect_reporter is not None else None
 
     # ---- generic losses on top of getEmbedding (BasicModel.py:59-113). EliMRec overrides bpr_loss; these are the
     # reference's base-class versions, differentiable through EliMRec.compute()'s autograd bridge.

@@ -1456,6 +1456,10 @@ __global__ __launch_bounds__(256) void rank_metrics_kernel(const int32_t *__rest
 // candidate -- one epilogue pass per 16 candidates. Work items (user, column chunk) are flattened over the grid:
 // a user with a long list does not set the launch's length. Output row b = its candidates' scores in list order, then
 // -inf up to `width` (pad_sequences, post); an id outside [0, I) scores NaN and is not read.
+// FX = the effect breakdown (elimrec_score_effects): the same body -- gather, block dots, reduction -- with an epilogue that
+// stores the terms the score is made of, FX_BASE + S floats per pair (include/elimrec_hip.h), instead of one score. Its two
+// score columns are cand_score_ under TE and TIE, so they are the bits the FX = false instantiation stores; ui, the
+// cosines and te / nde (fuse2_t) are the same expressions on the same dots and norms. Padding and bad ids: NaN throughout.
 constexpr int CAND_UNR = 4;
 constexpr int CAND_STEP = 4 * CAND_UNR;
 
@@ -1465,7 +1469,7 @@ struct CandArgs {
     const float *sqn;                        // [N x (1 + S)]
     const int64_t *ptr; const int32_t *items;  // candidate CSR over the B users
     const float *row_sum; int64_t I_total;   // TIE: sum_i sigmoid(u . i) over the catalogue
-    float *out; int64_t lds; int64_t width;
+    float *out; int64_t lds; int64_t width;      // FX: out [B x width x (FX_BASE + S)], lds unused
     int64_t chunks;                          // column chunks per user: ceil(width / CAND_STEP)
     int64_t n_work;                          // B * chunks
 };
@@ -1499,9 +1503,11 @@ __device__ __forceinline__ float dot4_(const float4 &x, const float4 &y, float a
     return fmaf(x.w, y.w, fmaf(x.z, y.z, fmaf(x.y, y.y, fmaf(x.x, y.x, acc))));
 }
 
+constexpr int FX_BASE = 6;      // FX: ui, mean_ui, te, nde, score_te, score_tie; then one cosine per head
+
 // NB = 1 + S head blocks; DT = float4 columns per lane and block held in registers (1: recdim <= 64, 2: <= 128), 0: any
-// recdim, the user's row re-read (from cache) per candidate
-template <int NB, int DT, bool FAST>
+// recdim, the user's row re-read (from cache) per candidate; FX: the effect breakdown's epilogue instead of the score's
+template <int NB, int DT, bool FAST, bool FX = false>
 __global__ __launch_bounds__(256) void score_cand_kernel(CandArgs a) {
     const int lane = threadIdx.x & 63, row = lane >> 4, li = lane & 15;
     const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -1586,6 +1592,39 @@ __global__ __launch_bounds__(256) void score_cand_kernel(CandArgs a) {
         }
     const int64_t col = col0 + li;
     if (li >= CAND_UNR || col >= a.width) return;
+    if constexpr (FX) {
+        constexpr int S = NB - 1, C = FX_BASE + S;
+        float *o = a.out + (b * a.width + col) * C;
+        if (it < 0) {
+#pragma unroll
+            for (int c = 0; c < C; ++c) o[c] = __builtin_nanf("");
+            return;
+        }
+        const float eps = 1e-12f;
+        float un[kMaxS], in[kMaxS], z[kMaxS];
+#pragma unroll
+        for (int h = 0; h < kMaxS; ++h) {
+            float nu = 1.f, ni = 1.f;
+            if (h < S) {
+                nu = fmaxf(sqrtf(a.sqn[unode * NB + 1 + h]), eps);
+                ni = fmaxf(sqrtf(a.sqn[(a.U + it) * NB + 1 + h]), eps);
+                if (FAST) { nu = rcp_nr(nu); ni = rcp_nr(ni); }
+            }
+            un[h] = nu; in[h] = ni;
+            const float nn = nu * ni;                      // z as cand_score_ forms it
+            z[h] = h < S ? (FAST ? dot[1 + h] * nn : dot[1 + h] / nn) : 0.f;
+        }
+        const float m = a.row_sum[b] / (float)a.I_total;
+        const float ui = sig_abs_<FAST>(dot[0]);
+        float te, nde;
+        fuse2_t<FAST>(a.fusion_mode, ui, m, z, S, a.head_mask, te, nde);
+        o[0] = ui; o[1] = m; o[2] = te; o[3] = nde;
+        o[4] = cand_score_<FAST>(1, a.fusion_mode, S, a.head_mask, dot, un, in, m);
+        o[5] = cand_score_<FAST>(2, a.fusion_mode, S, a.head_mask, dot, un, in, m);
+#pragma unroll
+        for (int h = 0; h < S; ++h) o[FX_BASE + h] = z[h];
+        return;
+    }
     float out = it == -1 ? -INFINITY : __builtin_nanf("");
     if (it >= 0) {
         const int ptype = a.predict_type;
@@ -2360,8 +2399,8 @@ extern "C" int elimrec_topk_reference_order(const float *h_scores, int64_t n_row
     return 0;
 }
 
-template <int NB, int DT, bool FAST> static void launch_cand(dim3 grid, const CandArgs &a, hipStream_t s) {
-    hipLaunchKernelGGL((score_cand_kernel<NB, DT, FAST>), grid, dim3(256), 0, s, a);
+template <int NB, int DT, bool FAST, bool FX = false> static void launch_cand(dim3 grid, const CandArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL((score_cand_kernel<NB, DT, FAST, FX>), grid, dim3(256), 0, s, a);
 }
 
 // Candidate lists instead of the whole catalogue (score_cand_kernel): d_scores [B x width] (leading dimension lds) = row b's
@@ -2399,5 +2438,41 @@ extern "C" int elimrec_score_candidates(const float *d_Y, int64_t ldy, int64_t U
         else launch_cand<NB, 0, FAST>(grid, a, s);
     }); });
     ELIMREC_LAUNCH_CHECK("score_candidates");
+    return 0;
+}
+
+// The effect breakdown of the same lists (score_cand_kernel<.., FX = true>): d_out [B x width x (6 + S)], contiguous; the
+// catalogue mean row_sum / I_total is always needed (NDE is evaluated at it).
+extern "C" int elimrec_score_effects(const float *d_Y, int64_t ldy, int64_t U, int64_t I, const int64_t *d_users, int B, int d, int S,
+                                     uint32_t head_mask, int fusion_mode, const float *d_sqnorm, const int64_t *d_cand_ptr,
+                                     const int32_t *d_cand_items, const float *d_row_sum, int64_t I_total, float *d_out,
+                                     int64_t width, void *stream) {
+    ELIMREC_REQUIRE(d_Y && d_users && d_cand_ptr && d_out, "score_effects: null pointer");
+    ELIMREC_REQUIRE(d > 0 && d % 4 == 0 && ldy % 4 == 0 && ldy >= (int64_t)(1 + S) * d, "score_effects: recdim/ldy must be multiples of 4");
+    ELIMREC_REQUIRE(S >= 0 && S < kMaxS, "score_effects: at most %d single-modal heads", kMaxS - 1);
+    ELIMREC_REQUIRE(fusion_mode >= 0 && fusion_mode <= 2, "score_effects: bad fusion_mode");
+    ELIMREC_REQUIRE(width >= 0, "score_effects: need width >= 0");
+    ELIMREC_REQUIRE(S == 0 || d_sqnorm, "score_effects: single-modal heads need the squared-norm table");
+    ELIMREC_REQUIRE(d_row_sum && I_total > 0, "score_effects: needs d_row_sum and I_total > 0");
+    if (B <= 0 || width <= 0) return 0;
+    ELIMREC_REQUIRE(d_cand_items, "score_effects: null candidate items");
+    CandArgs a;
+    a.Y = d_Y; a.ldy = ldy; a.U = U; a.I = I; a.users = d_users; a.d = d; a.S = S; a.head_mask = head_mask;
+    a.fusion_mode = fusion_mode; a.predict_type = 0; a.sqn = d_sqnorm; a.ptr = d_cand_ptr; a.items = d_cand_items;
+    a.row_sum = d_row_sum; a.I_total = I_total; a.out = d_out; a.lds = 0; a.width = width;
+    a.chunks = (width + CAND_STEP - 1) / CAND_STEP;
+    a.n_work = (int64_t)B * a.chunks;
+    const dim3 grid((unsigned)((a.n_work + 3) / 4));
+    hipStream_t s = (hipStream_t)stream;
+    const bool fast = score_math() == 1;
+    const int dt = d <= 64 ? 1 : (d <= 128 ? 2 : 0);
+    with_nb<true>(S, [&](auto nb) { with_fast(fast, [&](auto f) {
+        constexpr int NB = decltype(nb)::value;
+        constexpr bool FAST = decltype(f)::value;
+        if (dt == 1) launch_cand<NB, 1, FAST, true>(grid, a, s);
+        else if (dt == 2) launch_cand<NB, 2, FAST, true>(grid, a, s);
+        else launch_cand<NB, 0, FAST, true>(grid, a, s);
+    }); });
+    ELIMREC_LAUNCH_CHECK("score_effects");
     return 0;
 }

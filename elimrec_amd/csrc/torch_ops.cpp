@@ -20,6 +20,8 @@
 //   score_candidates(Y, U, I, users, d, S, head_mask, fusion_mode, predict_type, cand_ptr, cand_items, width) -> f32[B x width]
 //       (each row: its candidates' scores in list order, then -inf)
 //   sample_negatives(excl_ptr, excl_items, num_items, n_neg, seed) -> i32[n_users x n_neg]
+//   score_effects(Y, U, I, users, d, S, head_mask, fusion_mode, cand_ptr, cand_items, width) -> f32[B x width x (6 + S)]
+//       (per listed pair: ui, mean_ui, te, nde, score_te, score_tie, one cosine per head; NaN beyond a list and at bad ids)
 #include <ATen/ATen.h>
 #include <ATen/hip/HIPContext.h>
 #include <torch/library.h>
@@ -307,6 +309,34 @@ at::Tensor score_candidates(const at::Tensor &Y, int64_t U, int64_t I, const at:
     return out;
 }
 
+// ---- effect breakdown of candidate lists: block norms and the catalogue row sums are computed here
+at::Tensor score_effects(const at::Tensor &Y, int64_t U, int64_t I, const at::Tensor &users, int64_t d, int64_t S, int64_t head_mask,
+                         int64_t fusion_mode, const at::Tensor &cand_ptr, const at::Tensor &cand_items, int64_t width) {
+    const at::Tensor y = rowmajor(Y, "Y");
+    need(users, "users", at::kLong, 1); need(cand_ptr, "cand_ptr", at::kLong, 1); need(cand_items, "cand_items", at::kInt, 1);
+    const at::Tensor u = users.contiguous(), cp = cand_ptr.contiguous(), ci = cand_items.contiguous();
+    const int64_t B = u.numel();
+    TORCH_CHECK(cp.numel() == B + 1 && width >= 0 && S >= 0, "elimrec::score_effects: cand_ptr needs B + 1 entries, width >= 0, S >= 0");
+    at::Tensor out = at::empty({B, width, 6 + S}, y.options());
+    if (B == 0 || width == 0) return out;
+    at::Tensor sqn = at::empty({U + I, S + 1}, y.options());
+    check(elimrec_row_sqnorms(y.data_ptr<float>(), y.stride(0), U + I, (int)d, (int)S + 1, sqn.data_ptr<float>(), cur_stream()),
+          "score_effects(row_sqnorms)");
+    at::Tensor row_sum = at::zeros({B}, y.options());
+    const size_t need_ws = elimrec_score_workspace_for((int)B, U, I, (int)S, 1, (int)d, 0);
+    at::Tensor ws = at::empty({(int64_t)(need_ws ? need_ws : 1)}, y.options().dtype(at::kByte));
+    check(elimrec_score_topk_shard(y.data_ptr<float>(), y.stride(0), U, I, u.data_ptr<int64_t>(), (int)B, (int)d, (int)S,
+                                   (uint32_t)head_mask, (int)fusion_mode, 2, sqn.data_ptr<float>(), nullptr, nullptr, nullptr, 0, 0,
+                                   nullptr, nullptr, ws.data_ptr(), (size_t)ws.numel(), 1, row_sum.data_ptr<float>(), I, 0, cur_stream()),
+          "score_effects(row sums)");
+    check(elimrec_score_effects(y.data_ptr<float>(), y.stride(0), U, I, u.data_ptr<int64_t>(), (int)B, (int)d, (int)S, (uint32_t)head_mask,
+                                (int)fusion_mode, sqn.data_ptr<float>(), cp.data_ptr<int64_t>(),
+                                ci.numel() ? ci.data_ptr<int32_t>() : nullptr, row_sum.data_ptr<float>(), I, out.data_ptr<float>(), width,
+                                cur_stream()),
+          "score_effects");
+    return out;
+}
+
 at::Tensor sample_negatives(const at::Tensor &excl_ptr, const at::Tensor &excl_items, int64_t num_items, int64_t n_neg, int64_t seed) {
     need(excl_ptr, "excl_ptr", at::kLong, 1); need(excl_items, "excl_items", at::kInt, 1);
     const at::Tensor p = excl_ptr.contiguous(), it = excl_items.contiguous();
@@ -424,6 +454,7 @@ TORCH_LIBRARY(elimrec, m) {
     m.def("score_topk_shard(Tensor Y, int U, int I, Tensor users, int d, int S, int head_mask, int fusion_mode, int predict_type, Tensor? train_ptr, Tensor? train_items, int K, Tensor row_sum, int I_total, int id_offset) -> (Tensor, Tensor)");
     m.def("topk_merge(Tensor cand_val, Tensor cand_idx, int K) -> (Tensor, Tensor)");
     m.def("score_candidates(Tensor Y, int U, int I, Tensor users, int d, int S, int head_mask, int fusion_mode, int predict_type, Tensor cand_ptr, Tensor cand_items, int width) -> Tensor");
+    m.def("score_effects(Tensor Y, int U, int I, Tensor users, int d, int S, int head_mask, int fusion_mode, Tensor cand_ptr, Tensor cand_items, int width) -> Tensor");
     m.def("sample_negatives(Tensor excl_ptr, Tensor excl_items, int num_items, int n_neg, int seed) -> Tensor");
     m.def("lookup_counts(Tensor acts, int U, int I, int[] user_bounds, int[] item_bounds) -> Tensor");
     m.def("lookup_pack(Tensor acts, int U, int I, int[] user_bounds, int[] item_bounds, int me, Tensor shard, int row_bytes) -> (Tensor, Tensor)");
@@ -446,6 +477,7 @@ TORCH_LIBRARY_IMPL(elimrec, CUDA, m) {
     m.impl("score_topk_shard", &score_topk_shard);
     m.impl("topk_merge", &topk_merge);
     m.impl("score_candidates", &score_candidates);
+    m.impl("score_effects", &score_effects);
     m.impl("sample_negatives", &sample_negatives);
     m.impl("lookup_counts", &lookup_counts);
     m.impl("lookup_pack", &lookup_pack);

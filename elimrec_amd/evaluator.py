@@ -491,6 +491,87 @@ class GroupedEvaluator(object):
         return final, buf, group_final, group_buf
 
 
+class EffectReport(object):
+    """What the test users' top-K lists are made of (--effect_report=K): per (user, rank <= K) pair the effect breakdown of
+    EliMRec.effects_device -- ui, its catalogue mean, te, nde, the TE / TIE scores, the heads' cosines -- and its column means
+    over all pairs and, with group_view, per user group (assign_user_groups). The lists are the model's top-K under its current
+    predict type with train items masked, in user blocks as metric_rows takes them; the means are ops.group_metric_means over
+    the [users*K x C] block (float64 sums, the segments = rows of that block): only [1 + groups x C] floats reach the host."""
+
+    def __init__(self, dataset, user_train_dict, user_test_dict, top_k, group_view=None):
+        if not isinstance(user_train_dict, dict) or not isinstance(user_test_dict, dict):
+            raise TypeError("user_train_dict and user_test_dict must be dicts")
+        if isinstance(top_k, bool) or not isinstance(top_k, (int, np.integer)) or top_k < 1:
+            raise ValueError("top_k must be a positive integer, got %r" % (top_k,))
+        self.dataset = dataset
+        self.user_pos_train = user_train_dict
+        self.user_pos_test = user_test_dict
+        self.top_k = int(top_k)
+        self.users = list(user_test_dict.keys())
+        self.block_users = 8192
+        self.tie_order = "id"
+        self.group_labels, self._positions = ["all:".ljust(12)], [np.arange(len(self.users), dtype=np.int64)]
+        if group_view is not None:
+            labels, positions, self.num_discarded = assign_user_groups(self.users, user_train_dict, group_view)
+            self.group_labels += labels
+            self._positions += positions
+        self._index = {}                   # device -> ops.GroupIndex over the rows of the [users*K x C] block
+
+    def _group_index(self, device):
+        hit = self._index.get(str(device))
+        if hit is None:
+            K = self.top_k
+            rows = [(p[:, None] * K + np.arange(K, dtype=np.int64)[None, :]).reshape(-1) for p in self._positions]
+            ptr = np.zeros(len(rows) + 1, dtype=np.int64)
+            np.cumsum([r.size for r in rows], out=ptr[1:])
+            hit = ops.GroupIndex(ptr, np.concatenate(rows).astype(np.int32), len(self.users) * K, device)
+            self._index[str(device)] = hit
+        return hit
+
+    def effect_rows(self, model):
+        """The breakdown of every test user's top-K list on the device: ([users*K x C] float32, column names)."""
+        if not hasattr(model, "effects_device"):
+            raise TypeError("model must expose effects_device()")
+        if hasattr(model, "_ensure_tables") and getattr(model, "_cache", None) is not None:
+            model._ensure_tables()
+        if getattr(model, "_eval_shard", None) is not None:
+            raise CandidateScoringError("the effect report needs the whole cached item table on this rank; the tables are "
+                                        "item-sharded (lean / multi-rank evaluation): run without --effect_report")
+        if self.top_k > model.num_items:
+            raise CandidateScoringError("effect report of the top-%d lists: the catalogue has %d items" % (self.top_k, model.num_items))
+        device = model._require_gpu()
+        columns = ops.effect_columns(model._mods)
+        K, C = self.top_k, len(columns)
+        rows = torch.empty(len(self.users) * K, C, dtype=torch.float32, device=device)
+        at = 0
+        for batch_users in DataIterator(self.users, batch_size=self.block_users, shuffle=False, drop_last=False):
+            B = len(batch_users)
+            lists = [self.user_pos_train.get(u, []) for u in batch_users]
+            ptr = np.zeros(B + 1, dtype=np.int64)
+            np.cumsum([len(x) for x in lists], out=ptr[1:])
+            flat = np.fromiter((i for x in lists for i in x), dtype=np.int32, count=int(ptr[-1]))
+            users_t = torch.as_tensor(np.asarray(batch_users, dtype=np.int64)).to(device)
+            idx, _ = model.predict_device(users_t, top_k=K, train_ptr=torch.from_numpy(ptr).to(device),
+                                          train_items=torch.from_numpy(flat).to(device), tie_order=self.tie_order)
+            cand_ptr = torch.arange(B + 1, dtype=torch.int64, device=device) * K
+            model.effects_device(users_t, cand_ptr, idx.reshape(-1), rows[at * K:(at + B) * K].view(B, K, C))
+            at += B
+        return rows, columns
+
+    def columns_info(self, columns):
+        return "columns:\t%s" % "\t".join(str(c).ljust(12) for c in columns)
+
+    def evaluate(self, model):
+        """(final [1 + groups x C] float32: row 0 = all pairs, then one row per user group; buf: a header of column names and
+        one line per row in the grouped evaluator's format)."""
+        rows, columns = self.effect_rows(model)
+        out = torch.empty(len(self.group_labels), rows.shape[1], dtype=torch.float32, device=rows.device)
+        final = ops.group_metric_means(rows, self._group_index(rows.device), None, out).cpu().numpy()
+        buf = self.columns_info(columns) + "".join("\n%s\t%s" % (label, "\t".join(("%.8f" % x).ljust(12) for x in row))
+                                                    for label, row in zip(self.group_labels, final))
+        return final, buf
+
+
 class ProxyEvaluator(object):
     def __init__(self, dataset, user_train_dict, user_test_dict, user_neg_test=None, metric=None, group_view=None,
                  top_k=50, batch_size=1024, num_thread=8):

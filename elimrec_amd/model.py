@@ -21,6 +21,7 @@ What the reference does with 12+12 torch.sparse.mm calls, 8 addmm and autograd p
       BasicModel losses differentiate through, and bench.py's "reference-equivalent work" line.
 Propagation is linear, so nothing of the forward pass is kept for backward except Out (or its active rows) and Y.
 """
+import collections
 import os
 
 import numpy as np
@@ -34,6 +35,10 @@ from .basic_model import BasicModel
 from .evaluator import CandidateScoringError
 from .logger import Logger
 from .plugin import EmbeddingParameter, LazyGradParameter, StepController
+
+
+# EliMRec.explain's result: column names, item ids CPU int32 [B x W] (-1 = padding), values CPU fp32 [B x W x C]
+Effects = collections.namedtuple("Effects", ("columns", "items", "values"))
 
 
 def create_adj_mat(train_users, train_items, num_users, num_items, adj_type):
@@ -1218,6 +1223,85 @@ class EliMRec(BasicModel):
         out = torch.empty(len(user_ids), width, dtype=torch.float32, device=dev)
         self.predict_candidates_device(user_ids, torch.from_numpy(ptr).to(dev), torch.from_numpy(flat.astype(np.int32)).to(dev), out)
         return out.cpu()
+
+    @torch.no_grad()
+    def effects_device(self, user_ids, cand_ptr, cand_items, out):
+        """The effect breakdown of candidate lists (CSR as predict_candidates_device takes them) -> out [B x width x (6 + S)]
+        (float32, contiguous): per listed pair the columns of ops.effect_columns(self._mods) -- ui, the user's catalogue mean of it,
+        te, nde, the TE and TIE scores (the bits predict_candidates gives under either type) and every head's cosine; NaN beyond a
+        list's length (csrc/eval.hip score_cand_kernel, FX form). The catalogue mean comes from the scorer's pass 1 over the whole
+        catalogue whatever self.predict_type is (one launch per call)."""
+        dev = self._require_gpu()
+        self._plugin.realise_forward()
+        if self._ws is None or self._cache is None:
+            raise RuntimeError("explain() needs the tables cached by a training forward (call bpr_loss or compute first)")
+        self._ensure_tables()
+        if self.__dict__.get("_eval_shard") is not None:
+            raise CandidateScoringError("the effect breakdown needs the whole cached item table on this rank; the tables are "
+                                        "item-sharded (lean / multi-rank evaluation)")
+        users = torch.as_tensor(user_ids, device=dev).long().contiguous()
+        B, I = users.numel(), self.num_items
+        if not B:
+            return out
+        sqn = self._block_sqnorms(dev)
+        need = ops.score_workspace(B, self.num_users, I, self.S, 1, topk_only=True, d=self.latent_dim)
+        if self._ws.get("score_ws") is None or self._ws["score_ws"].numel() < need:
+            self._ws["score_ws"] = torch.empty(need, dtype=torch.uint8, device=dev)
+        row_sum = torch.empty(B, dtype=torch.float32, device=dev)
+        ops.score_topk_shard(self._ws["Y"], self.num_users, I, users, self.latent_dim, self.S, self._head_mask(), self.fusion_mode,
+                             "TIE", self._ws["score_ws"], 1, row_sum, I, 0, sqnorm=sqn)
+        ops.score_effects(self._ws["Y"], self.num_users, I, users, self.latent_dim, self.S, self._head_mask(), self.fusion_mode,
+                          cand_ptr, cand_items, out, sqn, row_sum, I)
+        return out
+
+    def explain(self, user_ids, candidate_items=None, top_k=None, exclude=None, tie_order="id"):
+        """Why items rank where they do: Effects(columns, items int32 [B x W] (-1 padded), values fp32 [B x W x C]) on the CPU,
+        columns = ops.effect_columns(self._mods). candidate_items: one list of item ids per user -- the breakdown of those pairs.
+        top_k: the breakdown of each user's top-K list under the model's current predict type and fusion mode (predict_device),
+        `exclude` = dict user -> item ids left out of the ranking (the train items, masked as the evaluator masks them)."""
+        if (candidate_items is None) == (top_k is None):
+            raise ValueError("explain() takes exactly one of candidate_items and top_k")
+        n = len(user_ids)
+        columns = ops.effect_columns(self._mods)
+        if candidate_items is not None:
+            if exclude is not None:
+                raise ValueError("exclude applies to top_k lists; candidate_items are taken as given")
+            if len(candidate_items) != n:
+                raise ValueError("one candidate list per user: %d lists for %d users" % (len(candidate_items), n))
+            lens = np.fromiter((len(c) for c in candidate_items), dtype=np.int64, count=n)
+            ptr = np.zeros(n + 1, dtype=np.int64)
+            np.cumsum(lens, out=ptr[1:])
+            flat = np.fromiter((int(i) for c in candidate_items for i in c), dtype=np.int64, count=int(ptr[-1]))
+            if flat.size and (flat.min() < 0 or flat.max() >= self.num_items):
+                raise IndexError("candidate item ids must lie in [0, %d)" % self.num_items)
+            width = int(lens.max()) if n else 0
+            items = np.full((n, width), -1, dtype=np.int32)
+            items[np.arange(width)[None, :] < lens[:, None]] = flat
+            dev = self._require_gpu()
+            cand_ptr, cand_items = torch.from_numpy(ptr).to(dev), torch.from_numpy(flat.astype(np.int32)).to(dev)
+        else:
+            top_k = int(top_k)
+            if top_k < 1 or top_k > self.num_items:
+                raise ValueError("top_k must lie in [1, %d]" % self.num_items)
+            lists = [(exclude or {}).get(int(u), []) for u in user_ids]
+            tptr = np.zeros(n + 1, dtype=np.int64)
+            np.cumsum([len(x) for x in lists], out=tptr[1:])
+            tflat = np.fromiter((int(i) for x in lists for i in x), dtype=np.int64, count=int(tptr[-1]))
+            if tflat.size and (tflat.min() < 0 or tflat.max() >= self.num_items):
+                raise IndexError("excluded item ids must lie in [0, %d)" % self.num_items)
+            dev = self._require_gpu()
+            width = top_k
+            if n:
+                idx, _ = self.predict_device(user_ids, top_k=top_k, train_ptr=torch.from_numpy(tptr).to(dev),
+                                             train_items=torch.from_numpy(tflat.astype(np.int32)).to(dev), tie_order=tie_order)
+            else:
+                idx = torch.empty(0, top_k, dtype=torch.int32, device=dev)
+            items = idx.cpu().numpy()
+            cand_ptr = torch.arange(n + 1, dtype=torch.int64, device=dev) * top_k
+            cand_items = idx.reshape(-1)
+        out = torch.empty(n, width, len(columns), dtype=torch.float32, device=dev)
+        self.effects_device(user_ids, cand_ptr, cand_items, out)
+        return Effects(columns, torch.from_numpy(np.ascontiguousarray(items)), out.cpu())
 
     def predict(self, user_ids, candidate_items=None):
         """:96-113. CPU fp32 tensor [len(user_ids) x I]; `candidate_items` is ignored as in the reference."""

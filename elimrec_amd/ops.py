@@ -829,6 +829,39 @@ def score_candidates(Y, U, I, users, d, S, head_mask, fusion_mode, predict_type,
     return out
 
 
+EFFECT_COLUMNS = ("ui", "mean_ui", "te", "nde", "score_te", "score_tie")
+
+
+def effect_columns(mods):
+    """Column names of score_effects' output: the six terms, then one cosine per single-modal head (mods: the heads' modality
+    letters in head order, e.g. ("v", "a", "t"))."""
+    return EFFECT_COLUMNS + tuple("cos_" + str(m) for m in mods)
+
+
+def score_effects(Y, U, I, users, d, S, head_mask, fusion_mode, cand_ptr, cand_items, out, sqnorm, row_sum, I_total):
+    """elimrec_score_effects: out [B x width x (6 + S)] (float32, contiguous) = per listed (user, item) pair the columns of
+    effect_columns(); NaN beyond a list's length and at ids outside [0, I). cand_ptr int64 [B + 1] / cand_items int32: the lists
+    as CSR. row_sum [B] (score_topk_shard phase 1 over the whole catalogue) and I_total always; sqnorm whenever S > 0."""
+    y, ldy = _rowmajor(Y, "Y")
+    B = users.numel()
+    C = len(EFFECT_COLUMNS) + S
+    if not (isinstance(out, torch.Tensor) and out.dim() == 3 and out.is_contiguous() and out.shape[0] == B and out.shape[2] == C):
+        raise ValueError("elimrec_amd.ops.score_effects: out must be a contiguous [%d x width x %d] tensor" % (B, C))
+    if cand_ptr.numel() != B + 1:
+        raise ValueError("elimrec_amd.ops.score_effects: cand_ptr needs B + 1 entries for the %d users" % B)
+    if row_sum is None or row_sum.numel() != B or int(I_total) <= 0:
+        raise ValueError("elimrec_amd.ops.score_effects: row_sum needs one catalogue sum for each of the %d users, and I_total > 0" % B)
+    if S > 0 and sqnorm is None:
+        raise ValueError("elimrec_amd.ops.score_effects: %d single-modal heads need the squared-norm table" % S)
+    items = cand_items if cand_items.numel() else None
+    _lib.check(_lib.load().elimrec_score_effects(y, ldy, U, I, _dev(users, "users", torch.int64), B, d, S, int(head_mask),
+                                                 FUSION_MODES[fusion_mode], _dev(sqnorm, "sqnorm"),
+                                                 _dev(cand_ptr, "cand_ptr", torch.int64), _dev(items, "cand_items", torch.int32),
+                                                 _dev(row_sum, "row_sum"), int(I_total), _dev(out, "out"), out.shape[1], _stream()),
+               "score_effects")
+    return out
+
+
 def check_negative_room(excl_ptr, num_items, n_neg):
     """The reference's condition (random_choice.pyx:35-37) on the host, before any launch: every row must leave more than
     n_neg ids outside its exclusion list."""

@@ -530,6 +530,24 @@ int elimrec_score_candidates(const float *d_Y, int64_t ldy, int64_t U, int64_t I
                              const int64_t *d_cand_ptr, const int32_t *d_cand_items, const float *d_row_sum,
                              int64_t I_total, float *d_scores, int64_t lds, int64_t width, void *stream);
 
+/* The effect breakdown of the same lists: what a pair's score is made of (models/EliMRec.py:96-113, 155-212). Same tables,
+ * lists, math modes and kernel body as elimrec_score_candidates (score_cand_kernel, second instantiation: the same block
+ * dots), no predict type. d_out [B x width x C] float32, contiguous, C = 6 + S; columns of pair (u, i):
+ *   0 ui        sigmoid(u0 . i0), the fused-embedding score both fusions start from
+ *   1 mean_ui   d_row_sum[b] / (float)I_total, the user's catalogue mean that NDE is evaluated at
+ *   2 te        general_cm_fusion(ui, ...), before the outer sigmoid
+ *   3 nde       general_cm_fusion(mean_ui, ...)
+ *   4 score_te  predict() under predict type TE  -- the bits elimrec_score_candidates stores under TE
+ *   5 score_tie predict() under predict type TIE -- likewise under TIE
+ *   6 + h       cos(u_h, i_h) of head h (norm floors 1e-12), every head whether or not head_mask has it
+ * head_mask acts as in the scorers (rubi: only masked heads multiply into te / nde; hm and sum take every head). A list
+ * position beyond the list's length and an id outside [0, I) (not read) get NaN in all C columns -- a component is not a
+ * rank key. d_row_sum / I_total are always required, d_sqnorm whenever S > 0. */
+int elimrec_score_effects(const float *d_Y, int64_t ldy, int64_t U, int64_t I, const int64_t *d_users, int B, int d, int S,
+                          uint32_t head_mask, int fusion_mode, const float *d_sqnorm, const int64_t *d_cand_ptr,
+                          const int32_t *d_cand_items, const float *d_row_sum, int64_t I_total, float *d_out, int64_t width,
+                          void *stream);
+
 /* Precision/Recall/MAP/NDCG/MRR prefix curves @1..K from ranked lists (metric.h:17-106).
  * d_truth_ptr int64[B+1], d_truth_items int32 (unique per row). metric_ids host int[n_metrics]
  * (1..5 as in cpp/uni_evaluator.py:14). d_out [B x n_metrics x K]. */

@@ -6,7 +6,7 @@
 Behaviour kept from the reference's `Net.run`: one pass of the pairwise sampler per epoch, validation every
 `test_step` epochs with predict_type TIE, a checkpoint + TE/TIE test pass whenever validation recall improves
 (not on epoch 0), early stop after `stop_cnt` epochs without improvement, the same log lines (`--group_view=[10,30,50,100]` adds
-the per-user-group table under each test line; validation and model selection stay on the overall metrics). The per-batch work,
+the per-user-group table under each test line, `--effect_report=K` the effect breakdown of the top-K lists; validation and model selection stay on the overall metrics). The per-batch work,
 the sampler and the evaluator run on the GPU (elimrec_amd). `--data.input.dataset=synthetic` uses the seeded
 Tiktok-shape generator instead of reading files.
 
@@ -92,6 +92,10 @@ class Net(object):
         # --group_view=[10,30,50,100]: metrics per user group (users bucketed by their number of training items) beside the overall
         # ones, from the same scoring pass. Validation and model selection keep the overall metrics -- the bits of a run without it
         self.grouped = cfg["group_view"] is not None
+        # --effect_report=K (default 0: off): under each [TEST] line the effect breakdown of the test users' top-K lists
+        self.effect_report = int(cfg["effect_report"]) if "effect_report" in cfg else 0
+        if self.effect_report and self.world > 1:
+            raise ValueError("--effect_report needs the whole cached item table on one rank: it is single-GPU")
         Logger.info(count_parameters(self.recommender))
         self.opt = FusedAdam(self.recommender.parameters(), lr=cfg.lr, weight_decay=cfg.weight_decay)
         self.loss_name = str(cfg.loss)
@@ -227,6 +231,8 @@ class Net(object):
             Logger.info(lines[effect])
             if self.grouped:               # one line per user group: "(lo,hi]:" and the metrics in the header's order
                 Logger.info("  [{}] by training interactions:{}".format(effect, group_table))
+            if self.effect_report:         # what the top-K lists under this effect are made of: column means, overall and per group
+                Logger.info("  [{}] effect breakdown of the top-{} lists:\n{}".format(effect, self.effect_report, rec.effect_report()[1]))
         return lines
 
     # ------------------------------------------------------------------ the run
