@@ -185,6 +185,11 @@ SIGNATURES = {
     "elimrec_group_metric_means": (c_i32, [c_ptr, c_i64, c_i32, c_i64, c_ptr, c_ptr, c_i64, c_i32, c_ptr, c_ptr, c_size, c_ptr]),
     "elimrec_group_metric_means_workspace": (c_size, [c_i64, c_i32, c_i32]),
     "elimrec_group_metric_means_chunk": (c_i32, []),
+    "elimrec_rank_targets": (c_i32, [c_ptr, c_i64, c_i64, c_i64, c_ptr, c_ptr, c_i64, c_ptr, c_ptr]),
+    "elimrec_rank_segment": (c_i32, []),
+    "elimrec_rank_targets_per_pass": (c_i32, []),
+    "elimrec_rank_pair_rows": (c_i32, [c_ptr, c_ptr, c_i64, ctypes.POINTER(ctypes.c_int), c_i32, c_ptr, c_ptr]),
+    "elimrec_rank_user_rows": (c_i32, [c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr]),
     "elimrec_slab_partials_bytes": (c_size, [c_sell, c_i32, c_i32]),
     "elimrec_slab_hop": (c_i32, [c_sell, c_i32, c_i32, c_i32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_f32, c_ptr, c_size, c_i32,
                                  c_ptr]),
@@ -326,6 +331,7 @@ class _Recording(object):
             fn = getattr(lib, name)
             plain = name in ("elimrec_abi_version", "elimrec_program_fn_count", "elimrec_program_fn_args", "elimrec_comm_unique_id",
                              "elimrec_score_get_math", "elimrec_score_get_bf16x3", "elimrec_group_metric_means_chunk",
+                             "elimrec_rank_segment", "elimrec_rank_targets_per_pass",
                              "elimrec_comm_create", "elimrec_comm_destroy", "elimrec_comm_nranks") or name.startswith("elimrec_program_")
             setattr(self, name, self._wrap(fn, name) if res is c_i32 and not plain else fn)
 

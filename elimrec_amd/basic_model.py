@@ -6,7 +6,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from .evaluator import EffectReport, ProxyEvaluator
+from .evaluator import EffectReport, ProxyEvaluator, RankReport
 
 
 class BasicModel(nn.Module):
@@ -43,6 +43,13 @@ class BasicModel(nn.Module):
             raise ValueError("effect_report must be 0 (off) or the K of the lists to break down")
         self.effect_reporter = EffectReport(dataset, train, dataset.get_user_test_dict(), k_report,
                                             group_view=config["group_view"]) if k_report else None
+        # --rank_report=1 (CLI-only, default 0 = off): the exact catalogue rank of every (test user, test item) pair and its means
+        # overall, per user group and -- with --item_group_view=[...] -- per item popularity group (evaluator.RankReport)
+        item_view = config["item_group_view"] if "item_group_view" in config else None
+        if "rank_report" in config and int(config["rank_report"]) not in (0, 1):
+            raise ValueError("rank_report must be 0 (off) or 1")
+        self.rank_reporter = RankReport(dataset, train, dataset.get_user_test_dict(), config["topks"], group_view=config["group_view"],
+                                        item_group_view=item_view) if "rank_report" in config and int(config["rank_report"]) else None
         self.infonce_criterion = nn.CrossEntropyLoss()          # BasicModel.py:32
 
     def getFileName(self):

@@ -16,6 +16,8 @@
 //   rank_metrics(topk_idx, truth_ptr, truth_items, metric_ids) -> f32[B x n_metrics x K]
 //   group_metric_means(rows f32[n x C], group_ptr i64[G+1], group_rows i32) -> f32[G x C]: per CSR segment of row indices the
 //       column means, float64 sums in listed order (the indices are checked on the host first: a synchronisation)
+//   rank_targets(scores f32[B x I], tgt_ptr i64[B+1], tgt_items i32) -> i32[n_targets]: the 0-based position of every listed item in
+//       its row's full ranking by (score desc, id asc), -1 at -inf (the lists are checked on the host first: a synchronisation)
 //   sample_triplets(user_ids, ptr, items, num_items, n, seed, epoch) -> (users, pos, neg)
 //   score_candidates(Y, U, I, users, d, S, head_mask, fusion_mode, predict_type, cand_ptr, cand_items, width) -> f32[B x width]
 //       (each row: its candidates' scores in list order, then -inf)
@@ -337,6 +339,33 @@ at::Tensor score_effects(const at::Tensor &Y, int64_t U, int64_t I, const at::Te
     return out;
 }
 
+// ---- exact catalogue rank of listed items in rows of (masked) scores
+at::Tensor rank_targets(const at::Tensor &scores, const at::Tensor &tgt_ptr, const at::Tensor &tgt_items) {
+    need(scores, "scores", at::kFloat, 2);
+    const at::Tensor sc = scores.stride(1) == 1 ? scores : scores.contiguous();
+    need(tgt_ptr, "tgt_ptr", at::kLong, 1); need(tgt_items, "tgt_items", at::kInt, 1);
+    const at::Tensor tp = tgt_ptr.contiguous(), ti = tgt_items.contiguous();
+    const int64_t B = sc.size(0), I = sc.size(1), n = ti.numel();
+    TORCH_CHECK(tp.numel() == B + 1, "elimrec::rank_targets: tgt_ptr needs B + 1 = ", B + 1, " entries, got ", tp.numel());
+    {   // no unchecked id reaches the kernel: the CSR is validated on the host
+        const at::Tensor hp = tp.cpu();
+        const int64_t *p = hp.data_ptr<int64_t>();
+        bool ok = p[0] == 0 && p[B] == n;
+        for (int64_t b = 0; b < B && ok; ++b) ok = p[b + 1] >= p[b];
+        TORCH_CHECK(ok, "elimrec::rank_targets: tgt_ptr must ascend from 0 to len(tgt_items) = ", n);
+        if (n > 0) {
+            const int64_t lo = ti.min().item<int64_t>(), hi = ti.max().item<int64_t>();
+            TORCH_CHECK(lo >= 0 && hi < I, "elimrec::rank_targets: item ids span [", lo, ", ", hi, "], the catalogue has ", I, " items");
+        }
+    }
+    at::Tensor out = at::empty({n}, ti.options());
+    if (n == 0 || B == 0) return out;
+    check(elimrec_rank_targets(sc.data_ptr<float>(), B, I, sc.stride(0), tp.data_ptr<int64_t>(), ti.data_ptr<int32_t>(), n,
+                               out.data_ptr<int32_t>(), cur_stream()),
+          "rank_targets");
+    return out;
+}
+
 at::Tensor sample_negatives(const at::Tensor &excl_ptr, const at::Tensor &excl_items, int64_t num_items, int64_t n_neg, int64_t seed) {
     need(excl_ptr, "excl_ptr", at::kLong, 1); need(excl_items, "excl_items", at::kInt, 1);
     const at::Tensor p = excl_ptr.contiguous(), it = excl_items.contiguous();
@@ -455,6 +484,7 @@ TORCH_LIBRARY(elimrec, m) {
     m.def("topk_merge(Tensor cand_val, Tensor cand_idx, int K) -> (Tensor, Tensor)");
     m.def("score_candidates(Tensor Y, int U, int I, Tensor users, int d, int S, int head_mask, int fusion_mode, int predict_type, Tensor cand_ptr, Tensor cand_items, int width) -> Tensor");
     m.def("score_effects(Tensor Y, int U, int I, Tensor users, int d, int S, int head_mask, int fusion_mode, Tensor cand_ptr, Tensor cand_items, int width) -> Tensor");
+    m.def("rank_targets(Tensor scores, Tensor tgt_ptr, Tensor tgt_items) -> Tensor");
     m.def("sample_negatives(Tensor excl_ptr, Tensor excl_items, int num_items, int n_neg, int seed) -> Tensor");
     m.def("lookup_counts(Tensor acts, int U, int I, int[] user_bounds, int[] item_bounds) -> Tensor");
     m.def("lookup_pack(Tensor acts, int U, int I, int[] user_bounds, int[] item_bounds, int me, Tensor shard, int row_bytes) -> (Tensor, Tensor)");
@@ -478,6 +508,7 @@ TORCH_LIBRARY_IMPL(elimrec, CUDA, m) {
     m.impl("topk_merge", &topk_merge);
     m.impl("score_candidates", &score_candidates);
     m.impl("score_effects", &score_effects);
+    m.impl("rank_targets", &rank_targets);
     m.impl("sample_negatives", &sample_negatives);
     m.impl("lookup_counts", &lookup_counts);
     m.impl("lookup_pack", &lookup_pack);

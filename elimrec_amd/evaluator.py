@@ -14,6 +14,8 @@ algorithm is replayed on the device, one wave per user, inside the scoring call 
 ref_order_kernel) -- same cost as tie_order = "id", the device's own rule (score descending, item
 id ascending). The two agree on every row without tied scores at or across the K boundary.
 """
+import collections
+
 import numpy as np
 import torch
 
@@ -570,6 +572,205 @@ class EffectReport(object):
         buf = self.columns_info(columns) + "".join("\n%s\t%s" % (label, "\t".join(("%.8f" % x).ljust(12) for x in row))
                                                     for label, row in zip(self.group_labels, final))
         return final, buf
+
+
+def assign_item_groups(item_ids, train_item_counts, item_group_view):
+    """Items bucketed by popularity, the counterpart of assign_user_groups: item_group_view = [b1..bn] (strictly ascending
+    positive integers) gives `cold` (0 training interactions), (0,b1], ..., (b(n-1),bn] and the open (bn,inf); an entry of
+    item_ids lands in the bucket of train_item_counts[its id]. Groups without entries are omitted; groups in that order, a
+    group's entries in the order of item_ids.
+    -> (labels ["cold:" / "(lo,hi]:" / "(bn,inf):", each .ljust(12)], positions [int64 arrays of indices into item_ids])."""
+    if not isinstance(item_group_view, list) or not item_group_view:
+        raise TypeError("The type of 'item_group_view' must be a non-empty `list`!")
+    for b in item_group_view:
+        if isinstance(b, bool) or not isinstance(b, (int, np.integer)) or b <= 0:
+            raise ValueError("item_group_view must hold strictly ascending positive integers, got %r" % (item_group_view,))
+    if any(hi <= lo for lo, hi in zip(item_group_view[:-1], item_group_view[1:])):
+        raise ValueError("item_group_view must hold strictly ascending positive integers, got %r" % (item_group_view,))
+    bounds = [int(b) for b in item_group_view]
+    ids = np.asarray(item_ids, dtype=np.int64).reshape(-1)
+    counts = np.asarray(train_item_counts, dtype=np.int64).reshape(-1)
+    if ids.size and (ids.min() < 0 or ids.max() >= counts.size):
+        raise IndexError("item ids must lie in [0, %d)" % counts.size)
+    n = counts[ids]
+    # 0 = cold, 1 + g = (bounds[g - 1], bounds[g]] (count in (lo, hi], as the user groups), 1 + len(bounds) = beyond the last bound
+    group = np.where(n == 0, 0, 1 + np.searchsorted(np.asarray(bounds, dtype=np.int64), n))
+    names = ["cold:"] + ["(%d,%d]:" % (lo, hi) for lo, hi in zip([0] + bounds[:-1], bounds)] + ["(%d,inf):" % bounds[-1]]
+    labels, positions = [], []
+    for g, name in enumerate(names):
+        at = np.flatnonzero(group == g)
+        if at.size:
+            labels.append(name.ljust(12))
+            positions.append(at.astype(np.int64))
+    return labels, positions
+
+
+RankTables = collections.namedtuple("RankTables", ("pair_columns", "pair_labels", "pairs", "user_columns", "user_labels", "users"))
+
+
+class RankReport(object):
+    """Where the held-out items stand in the FULL ranking (--rank_report=1): every (test user, test item) pair's exact catalogue
+    rank under the model's current predict type with the train items masked (EliMRec.rank_items_device: the evaluator's scoring
+    call into a score block, then csrc/rank.hip's count over it), and from the ranks
+      per pair: rank, rr = 1 / (rank + 1), pct = rank / (candidates - 1), hit@K for every K of top_k;
+      per user: auc, mrr_full = 1 / (first_rank + 1), first_rank = the best rank among the user's test items
+    as means over all pairs / users, per user group (group_view, assign_user_groups) and -- pair columns -- per item popularity
+    group (item_group_view, assign_item_groups over the items' training interactions). The pair means are MICRO-averages: every
+    pair weighs the same, so a user with many test items weighs more, and hit@K here is NOT the evaluator's per-user recall
+    (a mean of per-user ratios). Ranks order equal scores by item id whatever the evaluator's tie_order is.
+    Pairs are all (user, item) of user_test_dict in dict order; a pair whose item is also in the user's train list is dropped
+    (num_dropped), then a user without a pair or without a candidate besides its test items (num_skipped_users). Users go in
+    blocks whose [users x items] score block stays within block_bytes; the row and mean kernels leave only the tables to the host."""
+
+    def __init__(self, dataset, user_train_dict, user_test_dict, top_k, group_view=None, item_group_view=None):
+        if not isinstance(user_train_dict, dict) or not isinstance(user_test_dict, dict):
+            raise TypeError("user_train_dict and user_test_dict must be dicts")
+        ks = [top_k] if isinstance(top_k, (int, np.integer)) and not isinstance(top_k, bool) else list(top_k)
+        if not ks or any(isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1 for k in ks):
+            raise ValueError("top_k must be a positive integer or a list of them, got %r" % (top_k,))
+        self.dataset = dataset
+        self.num_items = I = int(dataset.num_items)
+        self.user_pos_train = user_train_dict
+        self.user_pos_test = user_test_dict
+        self.ks = [int(k) for k in ks]
+        self.block_bytes = 2 << 30
+        self.num_dropped = self.num_skipped_users = 0
+        self.users, pair_items, lens, n_cand = [], [], [], []
+        for u, test_items in user_test_dict.items():
+            seen = set(int(i) for i in user_train_dict.get(u, []))
+            kept = [int(i) for i in test_items if int(i) not in seen]
+            self.num_dropped += len(test_items) - len(kept)
+            if not kept or I - len(seen) - len(kept) <= 0:
+                self.num_skipped_users += 1
+                continue
+            self.users.append(u)
+            pair_items.append(kept)
+            lens.append(len(kept))
+            n_cand.append(I - len(seen))
+        if not self.users:
+            raise ValueError("the rank report has no (test user, test item) pair left to rank")
+        self.pair_ptr = np.zeros(len(self.users) + 1, dtype=np.int64)
+        np.cumsum(lens, out=self.pair_ptr[1:])
+        self.pair_items = np.fromiter((i for x in pair_items for i in x), dtype=np.int32, count=int(self.pair_ptr[-1]))
+        if self.pair_items.min() < 0 or self.pair_items.max() >= I:
+            raise IndexError("test item ids must lie in [0, %d)" % I)
+        self.pair_user = np.repeat(np.arange(len(self.users), dtype=np.int64), lens)       # position in self.users
+        self.user_n_cand = np.asarray(n_cand, dtype=np.int32)
+        self.pair_n_cand = self.user_n_cand[self.pair_user]
+        self.num_pairs = int(self.pair_items.size)
+        # groups: rows of the user block / of the pair block
+        self.user_labels, user_pos = ["all:".ljust(12)], [np.arange(len(self.users), dtype=np.int64)]
+        self.pair_labels, pair_pos = ["all:".ljust(12)], [np.arange(self.num_pairs, dtype=np.int64)]
+        if group_view is not None:
+            labels, positions, self.num_discarded = assign_user_groups(self.users, user_train_dict, group_view)
+            self.user_labels += labels
+            user_pos += positions
+            self.pair_labels += labels
+            pair_pos += [np.flatnonzero(np.isin(self.pair_user, p)) for p in positions]
+        if item_group_view is not None:
+            counts = np.zeros(I, dtype=np.int64)
+            for items in user_train_dict.values():
+                np.add.at(counts, np.asarray(list(items), dtype=np.int64), 1)
+            labels, positions = assign_item_groups(self.pair_items, counts, item_group_view)
+            self.pair_labels += [("item " + x.strip()).ljust(12) for x in labels]
+            pair_pos += positions
+        self._user_pos, self._pair_pos = user_pos, pair_pos
+        self._device = {}                  # device -> the CSRs, candidate counts and group indices resident there
+
+    @property
+    def block_users(self):
+        """Users per scoring call: as many as keep the [users x items] float32 block (rows padded to 16 bytes) within block_bytes."""
+        return max(1, int(self.block_bytes) // ((self.num_items + 3) // 4 * 16))
+
+    def _resident(self, device):
+        hit = self._device.get(str(device))
+        if hit is None:
+            def index(positions, n_rows):
+                ptr = np.zeros(len(positions) + 1, dtype=np.int64)
+                np.cumsum([p.size for p in positions], out=ptr[1:])
+                return ops.GroupIndex(ptr, np.concatenate(positions).astype(np.int32), n_rows, device)
+            hit = dict(pair_ptr=torch.from_numpy(self.pair_ptr).to(device), user_n_cand=torch.from_numpy(self.user_n_cand).to(device),
+                       pair_n_cand=torch.from_numpy(np.ascontiguousarray(self.pair_n_cand)).to(device),
+                       user_groups=index(self._user_pos, len(self.users)), pair_groups=index(self._pair_pos, self.num_pairs), blocks={})
+            self._device[str(device)] = hit
+        return hit
+
+    def _block(self, res, a, b, device):
+        """Users [a, b) of self.users as one scoring call's inputs, kept on the device: (users, TargetIndex, train_ptr, train_items)."""
+        hit = res["blocks"].get((a, b))
+        if hit is None:
+            ptr = self.pair_ptr[a:b + 1] - self.pair_ptr[a]
+            target = ops.TargetIndex(ptr, self.pair_items[self.pair_ptr[a]:self.pair_ptr[b]], b - a, self.num_items, device)
+            lists = [self.user_pos_train.get(u, []) for u in self.users[a:b]]
+            tptr = np.zeros(b - a + 1, dtype=np.int64)
+            np.cumsum([len(x) for x in lists], out=tptr[1:])
+            flat = np.fromiter((int(i) for x in lists for i in x), dtype=np.int32, count=int(tptr[-1]))
+            train = (torch.from_numpy(tptr).to(device), torch.from_numpy(flat).to(device)) if flat.size else (None, None)
+            hit = (torch.as_tensor(np.asarray(self.users[a:b], dtype=np.int64)).to(device), target) + train
+            res["blocks"][(a, b)] = hit
+        return hit
+
+    def pair_ranks(self, model):
+        """The exact catalogue rank of every pair under the model's current predict type: int32 [num_pairs] on the device."""
+        if not hasattr(model, "rank_items_device"):
+            raise TypeError("model must expose rank_items_device()")
+        if hasattr(model, "_ensure_tables") and getattr(model, "_cache", None) is not None:
+            model._ensure_tables()
+        if getattr(model, "_eval_shard", None) is not None:
+            raise CandidateScoringError("the rank report needs the whole cached item table on this rank; the tables are "
+                                        "item-sharded (lean / multi-rank evaluation): run without --rank_report")
+        if model.num_items != self.num_items:
+            raise ValueError("the report was built for %d items, the model has %d" % (self.num_items, model.num_items))
+        device = model._require_gpu()
+        res = self._resident(device)
+        ranks = torch.empty(self.num_pairs, dtype=torch.int32, device=device)
+        step = self.block_users
+        for a in range(0, len(self.users), step):
+            b = min(a + step, len(self.users))
+            users, target, tptr, titems = self._block(res, a, b, device)
+            ranks[self.pair_ptr[a]:self.pair_ptr[b]] = model.rank_items_device(users, target, tptr, titems)[0]
+        return ranks
+
+    def _tables(self, pair_rows, pair_columns, user_rows, user_columns, res):
+        pairs = torch.empty(len(self.pair_labels), pair_rows.shape[1], dtype=torch.float32, device=pair_rows.device)
+        ops.group_metric_means(pair_rows, res["pair_groups"], None, pairs)
+        users = None
+        if user_rows is not None:
+            users = torch.empty(len(self.user_labels), user_rows.shape[1], dtype=torch.float32, device=user_rows.device)
+            users = ops.group_metric_means(user_rows, res["user_groups"], None, users).cpu().numpy()
+        final = RankTables(tuple(pair_columns), list(self.pair_labels), pairs.cpu().numpy(), tuple(user_columns),
+                           list(self.user_labels) if users is not None else [], users)
+        buf = self._format(final.pair_columns, final.pair_labels, final.pairs)
+        if users is not None:
+            buf += "\n" + self._format(final.user_columns, final.user_labels, final.users)
+        return final, buf
+
+    @staticmethod
+    def _format(columns, labels, table):
+        return "columns:\t%s" % "\t".join(str(c).ljust(12) for c in columns) + "".join(
+            "\n%s\t%s" % (label, "\t".join(("%.8f" % x).ljust(12) for x in row)) for label, row in zip(labels, table))
+
+    def evaluate(self, model, ranks=None):
+        """(final, buf). final = RankTables: pairs [1 + user groups + item groups x (3 + len(ks))] float32 -- row 0 = all pairs --
+        the means of rank, rr, pct, hit@K; users [1 + user groups x 3] the means of auc, mrr_full, first_rank. The pair means are
+        micro-averages (see the class). buf: per table a header of column names and one "%.8f" line per row, in the grouped
+        evaluator's format. ranks: pair_ranks(model) if the caller already holds it."""
+        if ranks is None:
+            ranks = self.pair_ranks(model)
+        res = self._resident(ranks.device)
+        pair_rows = torch.empty(self.num_pairs, 3 + len(self.ks), dtype=torch.float32, device=ranks.device)
+        ops.rank_pair_rows(ranks, res["pair_n_cand"], self.ks, pair_rows)
+        user_rows = torch.empty(len(self.users), 3, dtype=torch.float32, device=ranks.device)
+        ops.rank_user_rows(ranks, res["pair_ptr"], res["user_n_cand"], user_rows)
+        return self._tables(pair_rows, ops.rank_pair_columns(self.ks), user_rows, ops.RANK_USER_COLUMNS, res)
+
+    def shift(self, ranks_a, ranks_b):
+        """How far the pairs move from ranking a to ranking b (e.g. TE -> TIE): (final, buf) in evaluate()'s pair grouping over
+        delta = a - b (positive: b ranks the test item higher), improved = (b < a), worsened = (b > a)."""
+        if ranks_a.shape != (self.num_pairs,) or ranks_b.shape != (self.num_pairs,) or ranks_a.device != ranks_b.device:
+            raise ValueError("shift() takes two pair_ranks() results of this report on one device")
+        rows = torch.stack(((ranks_a - ranks_b).float(), (ranks_b < ranks_a).float(), (ranks_b > ranks_a).float()), dim=1)
+        return self._tables(rows, ("delta", "improved", "worsened"), None, (), self._resident(ranks_a.device))
 
 
 class ProxyEvaluator(object):

@@ -1303,6 +1303,70 @@ class EliMRec(BasicModel):
         self.effects_device(user_ids, cand_ptr, cand_items, out)
         return Effects(columns, torch.from_numpy(np.ascontiguousarray(items)), out.cpu())
 
+    @torch.no_grad()
+    def rank_items_device(self, user_ids, tgt_index, train_ptr=None, train_items=None, top_k=0):
+        """Where given items stand in each user's FULL ranking under the current predict type and fusion mode: (rank int32 [P], idx,
+        val). tgt_index: ops.TargetIndex over (len(user_ids), num_items) -- one list of item ids per user, checked on the host when
+        it was built; rank[p] = the 0-based position of target p by (score descending, id ascending) among the whole catalogue
+        with the train items (train_ptr / train_items, CSR on the device) masked, -1 for a target that is itself masked. One
+        predict_device call into a [B x I] block -- scored and masked as the evaluator's lists are -- then ops.rank_targets over
+        that block (csrc/rank.hip). top_k > 0: idx / val [B x top_k] are the top-K lists selected from the same block by the same
+        call (tie order "id"), so rank < top_k exactly for the listed targets; None otherwise."""
+        dev = self._require_gpu()
+        if not isinstance(tgt_index, ops.TargetIndex):
+            raise TypeError("rank_items_device takes the targets as an ops.TargetIndex (checked on the host once)")
+        self._plugin.realise_forward()
+        if self._ws is None or self._cache is None:
+            raise RuntimeError("rank_items() needs the tables cached by a training forward (call bpr_loss or compute first)")
+        self._ensure_tables()
+        if self.__dict__.get("_eval_shard") is not None:
+            raise CandidateScoringError("exact ranks need the whole cached item table on this rank; the tables are item-sharded "
+                                        "(lean / multi-rank evaluation)")
+        users = torch.as_tensor(user_ids, device=dev).long().contiguous()
+        B, I = users.numel(), self.num_items
+        if tgt_index.n_rows != B or tgt_index.n_items != I:
+            raise ValueError("the TargetIndex was built for %d users of %d items, the call has %d users of %d items"
+                             % (tgt_index.n_rows, tgt_index.n_items, B, I))
+        rank = torch.empty(tgt_index.n_targets, dtype=torch.int32, device=dev)
+        if not B:
+            return rank, None, None
+        lds = (I + 3) // 4 * 4                    # rows 16-byte aligned: the count takes its 16-byte loads
+        block = torch.empty(B, lds, dtype=torch.float32, device=dev)[:, :I]
+        idx, val = self.predict_device(users, scores=block, top_k=int(top_k), train_ptr=train_ptr, train_items=train_items,
+                                       tie_order="id")
+        ops.rank_targets(block, tgt_index, None, rank)
+        return rank, idx, val
+
+    def rank_items(self, user_ids, items, exclude=None):
+        """The exact catalogue rank of given items: CPU int32 [len(user_ids) x longest list], row b = the 0-based positions of
+        items[b] (one list of item ids per user) in user b's full ranking under the current predict type, padded with -1.
+        `exclude` = dict user -> item ids masked out of the ranking (the train items, as explain() takes it); an item that is
+        itself excluded gets -1."""
+        n = len(user_ids)
+        if len(items) != n:
+            raise ValueError("one item list per user: %d lists for %d users" % (len(items), n))
+        lens = np.fromiter((len(c) for c in items), dtype=np.int64, count=n)
+        ptr = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum(lens, out=ptr[1:])
+        flat = np.fromiter((int(i) for c in items for i in c), dtype=np.int64, count=int(ptr[-1]))
+        if flat.size and (flat.min() < 0 or flat.max() >= self.num_items):
+            raise IndexError("item ids must lie in [0, %d)" % self.num_items)
+        lists = [(exclude or {}).get(int(u), []) for u in user_ids]
+        tptr = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum([len(x) for x in lists], out=tptr[1:])
+        tflat = np.fromiter((int(i) for x in lists for i in x), dtype=np.int64, count=int(tptr[-1]))
+        if tflat.size and (tflat.min() < 0 or tflat.max() >= self.num_items):
+            raise IndexError("excluded item ids must lie in [0, %d)" % self.num_items)
+        dev = self._require_gpu()
+        width = int(lens.max()) if n else 0
+        out = np.full((n, width), -1, dtype=np.int32)
+        if flat.size:
+            index = ops.TargetIndex(ptr, flat.astype(np.int32), n, self.num_items, dev)
+            masked = (torch.from_numpy(tptr).to(dev), torch.from_numpy(tflat.astype(np.int32)).to(dev)) if tflat.size else (None, None)
+            rank, _, _ = self.rank_items_device(user_ids, index, *masked)
+            out[np.arange(width)[None, :] < lens[:, None]] = rank.cpu().numpy()
+        return torch.from_numpy(out)
+
     def predict(self, user_ids, candidate_items=None):
         """:96-113. CPU fp32 tensor [len(user_ids) x I]; `candidate_items` is ignored as in the reference."""
         dev = self._require_gpu()

@@ -797,9 +797,104 @@ def group_metric_means(rows, group_ptr, group_rows, out, workspace=None):
     return out
 
 
+class TargetIndex(object):
+    """Target items per score row as CSR (ptr [B + 1], items: item ids of an I-item catalogue), CHECKED ON THE HOST -- B + 1
+    entries, ptr[0] = 0, ascending, ptr[B] = len(items), every id in [0, I) -- and then resident on `device`: rank_targets takes
+    it as is, call after call, and no unchecked id ever reaches a kernel (the counterpart of GroupIndex)."""
+
+    def __init__(self, ptr, items, B, I, device):
+        p = np.ascontiguousarray(_host(ptr), dtype=np.int64).reshape(-1)
+        it = _host(items).reshape(-1)
+        if p.size != int(B) + 1:
+            raise ValueError("elimrec_amd.ops.TargetIndex: ptr needs B + 1 = %d entries, got %d" % (int(B) + 1, p.size))
+        if it.size and not np.issubdtype(it.dtype, np.integer):
+            raise TypeError("elimrec_amd.ops.TargetIndex: items must hold integers, got %s" % it.dtype)
+        if p[0] != 0 or p[-1] != it.size or (np.diff(p) < 0).any():
+            raise ValueError("elimrec_amd.ops.TargetIndex: ptr must ascend from 0 to len(items) = %d" % it.size)
+        if it.size and (int(it.min()) < 0 or int(it.max()) >= int(I)):
+            raise IndexError("elimrec_amd.ops.TargetIndex: item ids span [%d, %d], the catalogue has %d items"
+                             % (int(it.min()), int(it.max()), int(I)))
+        self.n_rows, self.n_items, self.n_targets = int(B), int(I), int(it.size)
+        self.sizes = np.diff(p)
+        self.ptr = torch.from_numpy(p).to(device)
+        # (never empty: the kernels read nothing of it when n_targets = 0, the binding still wants a device tensor)
+        self.items = torch.from_numpy(np.ascontiguousarray(it if it.size else np.zeros(1), dtype=np.int32)).to(device)
+
+
+def rank_targets(scores, tgt_ptr, tgt_items, out):
+    """elimrec_rank_targets: out int32 [>= n_targets] <- the 0-based position of every listed target in its row's full ranking by
+    (score descending, id ascending): #{j: scores[b, j] > s or (scores[b, j] == s and j < t)}; -1 for a target at -inf (masked).
+    scores [B x I] float32, unit column stride (a padded block's columns beyond I are not read). tgt_ptr / tgt_items: the lists as
+    CSR, host arrays or tensors -- checked on the host at every call (a synchronisation for device tensors) -- or tgt_ptr = a
+    TargetIndex (tgt_items = None), checked once. Entries of out beyond n_targets are left alone."""
+    sp, lds = _rowmajor(scores, "scores")
+    B, I = scores.shape
+    if isinstance(tgt_ptr, TargetIndex):
+        index = tgt_ptr
+        if tgt_items is not None and tgt_items is not index.items:
+            raise ValueError("elimrec_amd.ops.rank_targets: a TargetIndex carries its own items (pass tgt_items=None)")
+        if index.n_rows != B or index.n_items > I or index.ptr.device != scores.device:
+            raise IndexError("elimrec_amd.ops.rank_targets: the TargetIndex was checked for %d rows of %d items on %s, the block is "
+                             "[%d x %d] on %s" % (index.n_rows, index.n_items, index.ptr.device, B, I, scores.device))
+    else:
+        index = TargetIndex(tgt_ptr, tgt_items, B, I, scores.device)
+    if not (isinstance(out, torch.Tensor) and out.dim() == 1 and out.is_contiguous() and out.numel() >= index.n_targets):
+        raise ValueError("elimrec_amd.ops.rank_targets: out must be a contiguous 1-D tensor of at least %d entries" % index.n_targets)
+    _lib.check(_lib.load().elimrec_rank_targets(sp, B, I, lds, _dev(index.ptr, "tgt_ptr", torch.int64),
+                                                _dev(index.items, "tgt_items", torch.int32), index.n_targets,
+                                                _dev(out, "out", torch.int32), _stream()), "rank_targets")
+    return out
+
+
+RANK_PAIR_COLUMNS = ("rank", "rr", "pct")
+RANK_USER_COLUMNS = ("auc", "mrr_full", "first_rank")
+
+
+def rank_pair_columns(ks):
+    """Column names of rank_pair_rows' output: rank, rr, pct, then hit@K for every K of ks."""
+    return RANK_PAIR_COLUMNS + tuple("hit@%d" % int(k) for k in ks)
+
+
+def rank_pair_rows(rank, n_cand, ks, out):
+    """elimrec_rank_pair_rows: out [P x (3 + len(ks))] (float32, contiguous) = per pair rank, rr = 1 / (rank + 1),
+    pct = rank / (n_cand - 1) (0 when n_cand <= 1), hit@K = (rank < K) for each K of ks (at most 16); a NaN row where rank < 0.
+    rank, n_cand: int32 [P]."""
+    P = rank.numel()
+    ks = [int(k) for k in ks]
+    if n_cand.numel() != P or not rank.is_contiguous() or not n_cand.is_contiguous():
+        raise ValueError("elimrec_amd.ops.rank_pair_rows: rank and n_cand must be contiguous with one entry per pair")
+    if not (isinstance(out, torch.Tensor) and out.is_contiguous() and tuple(out.shape) == (P, 3 + len(ks))):
+        raise ValueError("elimrec_amd.ops.rank_pair_rows: out must be a contiguous [%d x %d] tensor" % (P, 3 + len(ks)))
+    _lib.check(_lib.load().elimrec_rank_pair_rows(_dev(rank, "rank", torch.int32), _dev(n_cand, "n_cand", torch.int32), P,
+                                                  (ctypes.c_int * max(1, len(ks)))(*ks), len(ks), _dev(out, "out"), _stream()),
+               "rank_pair_rows")
+    return out
+
+
+def rank_user_rows(rank, tgt_ptr, n_cand, out):
+    """elimrec_rank_user_rows: out [B x 3] (float32, contiguous) = per user auc, mrr_full, first_rank over its targets with
+    rank >= 0 (NaN when it has none, or no candidate besides them). rank int32 [n_targets]; tgt_ptr: int64 [B + 1] device tensor
+    or a TargetIndex; n_cand int32 [B]: the user's candidates (the catalogue without its masked items)."""
+    if isinstance(tgt_ptr, TargetIndex):
+        tgt_ptr = tgt_ptr.ptr
+    B = n_cand.numel()
+    if tgt_ptr.numel() != B + 1 or not rank.is_contiguous() or not n_cand.is_contiguous() or not tgt_ptr.is_contiguous():
+        raise ValueError("elimrec_amd.ops.rank_user_rows: tgt_ptr needs B + 1 entries for the %d users of n_cand" % B)
+    if not (isinstance(out, torch.Tensor) and out.is_contiguous() and tuple(out.shape) == (B, 3)):
+        raise ValueError("elimrec_amd.ops.rank_user_rows: out must be a contiguous [%d x 3] tensor" % B)
+    _lib.check(_lib.load().elimrec_rank_user_rows(_dev(rank, "rank", torch.int32), _dev(tgt_ptr, "tgt_ptr", torch.int64),
+                                                  rank.numel(), _dev(n_cand, "n_cand", torch.int32), B, _dev(out, "out"),
+                                                  _stream()), "rank_user_rows")
+    return out
+
+
 def __getattr__(name):
     if name == "GROUP_MEAN_CHUNK":       # listed rows per partial sum of group_metric_means (a compile-time constant of the library)
         return int(_lib.load().elimrec_group_metric_means_chunk())
+    if name == "RANK_SEGMENT":           # columns of a score row one workgroup of rank_targets counts
+        return int(_lib.load().elimrec_rank_segment())
+    if name == "RANK_TARGETS_PER_PASS":  # targets rank_targets stages per pass over a segment
+        return int(_lib.load().elimrec_rank_targets_per_pass())
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 

@@ -572,6 +572,39 @@ int elimrec_group_metric_means(const float *d_rows, int64_t n_rows, int C, int64
 size_t elimrec_group_metric_means_workspace(int64_t n_listed_rows, int C, int G);
 int elimrec_group_metric_means_chunk(void);
 
+/* Exact catalogue rank of given items in a user's full ranking (csrc/rank.hip): the position the reference's evaluator would
+ * give the item if its list had no K (evaluate.h:26-33 ranks the masked score row, metric.h:17-106 reads positions < K only).
+ * d_scores [B x I] float32 with row stride lds >= I, masked items = -inf -- the block elimrec_score_topk(_ordered) leaves when
+ * the caller passes d_scores: the same values its top-K list is selected from. Targets as CSR: d_tgt_ptr int64[B + 1]
+ * (ascending, [0] = 0, [B] = n_targets), d_tgt_items int32[n_targets]. d_rank int32[n_targets]: for target t of row b with
+ * s = scores[b, t]
+ *     rank = #{ j in [0, I) : scores[b, j] > s  or  (scores[b, j] == s and j < t) }
+ * the (score descending, id ascending) order, 0-based -- also under tie_order 1, whose lists order equal scores differently;
+ * -1 where s == -inf (a masked item) and where t lies outside [0, I) (not read; the Python wrappers reject such ids on the
+ * host). Columns >= I of a padded row are never read. Duplicated targets each get their rank; -0.0 == 0.0 as IEEE compares
+ * them. NaN scores are outside the contract: every scoring call ends with the range check (elimrec_score_range_violations).
+ * One streaming pass over the rows that list a target, integer atomic adds into the zeroed d_rank (one memset + one launch
+ * on `stream`): the counts do not depend on the grid or on arrival order. Exactly n_targets entries of d_rank are written.
+ * elimrec_rank_segment(): columns one workgroup counts; elimrec_rank_targets_per_pass(): targets staged per pass over them. */
+int elimrec_rank_targets(const float *d_scores, int64_t B, int64_t I, int64_t lds, const int64_t *d_tgt_ptr,
+                         const int32_t *d_tgt_items, int64_t n_targets, int32_t *d_rank, void *stream);
+int elimrec_rank_segment(void);
+int elimrec_rank_targets_per_pass(void);
+/* Rows of the rank report from those ranks. Per pair (no counterpart in the reference, whose metrics stop at K:
+ * metric.h:17-106): d_out [P x (3 + n_k)] float32 contiguous = rank, rr = 1 / (rank + 1), pct = rank / (n_cand - 1) (0 when
+ * n_cand <= 1), then hit@ks[c] = (rank < ks[c]); ks host int[n_k], n_k <= 16; computed in double, rounded once (the rank column
+ * is exact up to 2^24); a pair with rank < 0 gives a NaN row. */
+int elimrec_rank_pair_rows(const int32_t *d_rank, const int32_t *d_n_cand, int64_t P, const int *ks, int n_k, float *d_out,
+                           void *stream);
+/* Per user (one wave each; any list length): over the user's T targets with rank >= 0 and N_neg = d_n_cand[b] - T
+ * (d_n_cand[b] = the user's candidates: the catalogue without its masked items), d_out [B x 3] float32 =
+ *   auc        1 - sum_t (rank_t - #the user's valid targets ranked above t) / (T N_neg)
+ *   mrr_full   1 / (min_t rank_t + 1)        (metric.h:86-106's MRR without the K cut)
+ *   first_rank min_t rank_t
+ * exact integer sums, double arithmetic, rounded once; NaN when T == 0 or N_neg <= 0. */
+int elimrec_rank_user_rows(const int32_t *d_rank, const int64_t *d_tgt_ptr, int64_t n_targets, const int32_t *d_n_cand,
+                           int64_t B, float *d_out, void *stream);
+
 /* ---------------------------------------------------------------- pairwise sampler (K20)
  * n triplets: user uniform over the `n_train_users` users with >= 1 training item (with
  * replacement), positive uniform over that user's training items, negative uniform over [0,I)

@@ -6,7 +6,7 @@
 Behaviour kept from the reference's `Net.run`: one pass of the pairwise sampler per epoch, validation every
 `test_step` epochs with predict_type TIE, a checkpoint + TE/TIE test pass whenever validation recall improves
 (not on epoch 0), early stop after `stop_cnt` epochs without improvement, the same log lines (`--group_view=[10,30,50,100]` adds
-the per-user-group table under each test line, `--effect_report=K` the effect breakdown of the top-K lists; validation and model selection stay on the overall metrics). The per-batch work,
+the per-user-group table under each test line, `--effect_report=K` the effect breakdown of the top-K lists, `--rank_report=1` the test items' exact catalogue ranks; validation and model selection stay on the overall metrics). The per-batch work,
 the sampler and the evaluator run on the GPU (elimrec_amd). `--data.input.dataset=synthetic` uses the seeded
 Tiktok-shape generator instead of reading files.
 
@@ -96,6 +96,11 @@ class Net(object):
         self.effect_report = int(cfg["effect_report"]) if "effect_report" in cfg else 0
         if self.effect_report and self.world > 1:
             raise ValueError("--effect_report needs the whole cached item table on one rank: it is single-GPU")
+        # --rank_report=1 (default 0: off): under each [TEST] line where the test items stand in the FULL ranking (rank, rr, pct,
+        # hit@K per pair; auc, mrr_full, first_rank per user), after both effects how far TIE moves them relative to TE
+        self.rank_report = int(cfg["rank_report"]) if "rank_report" in cfg else 0
+        if self.rank_report and self.world > 1:
+            raise ValueError("--rank_report needs the whole cached item table on one rank: it is single-GPU")
         Logger.info(count_parameters(self.recommender))
         self.opt = FusedAdam(self.recommender.parameters(), lr=cfg.lr, weight_decay=cfg.weight_decay)
         self.loss_name = str(cfg.loss)
@@ -220,7 +225,7 @@ class Net(object):
 
     def test_all_effects(self):
         """TE and TIE metrics on the test split, formatted as the reference prints them."""
-        rec, lines = self.recommender, {}
+        rec, lines, ranks = self.recommender, {}, {}
         if self.grouped:
             Logger.info(rec.test_evaluator.metrics_info())
         for effect in EFFECTS:
@@ -233,6 +238,11 @@ class Net(object):
                 Logger.info("  [{}] by training interactions:{}".format(effect, group_table))
             if self.effect_report:         # what the top-K lists under this effect are made of: column means, overall and per group
                 Logger.info("  [{}] effect breakdown of the top-{} lists:\n{}".format(effect, self.effect_report, rec.effect_report()[1]))
+            if self.rank_report:           # where the test items stand in the full ranking under this effect
+                ranks[effect] = rec.rank_reporter.pair_ranks(rec)
+                Logger.info("  [{}] catalogue rank of the test items:\n{}".format(effect, rec.rank_reporter.evaluate(rec, ranks[effect])[1]))
+        if self.rank_report:               # positive delta: TIE ranks the test item higher than TE does
+            Logger.info("  [TE->TIE] rank shift of the test items:\n{}".format(rec.rank_reporter.shift(ranks["TE"], ranks["TIE"])[1]))
         return lines
 
     # ------------------------------------------------------------------ the run
