@@ -190,6 +190,12 @@ SIGNATURES = {
     "elimrec_rank_targets_per_pass": (c_i32, []),
     "elimrec_rank_pair_rows": (c_i32, [c_ptr, c_ptr, c_i64, ctypes.POINTER(ctypes.c_int), c_i32, c_ptr, c_ptr]),
     "elimrec_rank_user_rows": (c_i32, [c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr]),
+    "elimrec_cosine_topk": (c_i32, [c_ptr, c_i64, c_i64, c_i32, c_ptr, c_i64, c_ptr, c_i64, c_i32, c_ptr, c_ptr, c_i32, c_ptr, c_ptr,
+                                    c_ptr, c_size, c_ptr]),
+    "elimrec_cosine_topk_workspace": (c_size, [c_i64, c_i64, c_i32]),
+    "elimrec_cosine_topk_chunk": (c_i32, []),
+    "elimrec_cosine_topk_tile": (c_i32, []),
+    "elimrec_list_overlap": (c_i32, [c_ptr, c_ptr, c_i64, c_i32, c_ptr, c_ptr]),
     "elimrec_slab_partials_bytes": (c_size, [c_sell, c_i32, c_i32]),
     "elimrec_slab_hop": (c_i32, [c_sell, c_i32, c_i32, c_i32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_f32, c_ptr, c_size, c_i32,
                                  c_ptr]),
@@ -332,6 +338,7 @@ class _Recording(object):
             plain = name in ("elimrec_abi_version", "elimrec_program_fn_count", "elimrec_program_fn_args", "elimrec_comm_unique_id",
                              "elimrec_score_get_math", "elimrec_score_get_bf16x3", "elimrec_group_metric_means_chunk",
                              "elimrec_rank_segment", "elimrec_rank_targets_per_pass",
+                             "elimrec_cosine_topk_chunk", "elimrec_cosine_topk_tile",
                              "elimrec_comm_create", "elimrec_comm_destroy", "elimrec_comm_nranks") or name.startswith("elimrec_program_")
             setattr(self, name, self._wrap(fn, name) if res is c_i32 and not plain else fn)
 

@@ -6,7 +6,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from .evaluator import EffectReport, ProxyEvaluator, RankReport
+from .evaluator import EffectReport, NeighbourReport, ProxyEvaluator, RankReport
 
 
 class BasicModel(nn.Module):
@@ -50,6 +50,13 @@ class BasicModel(nn.Module):
             raise ValueError("rank_report must be 0 (off) or 1")
         self.rank_reporter = RankReport(dataset, train, dataset.get_user_test_dict(), config["topks"], group_view=config["group_view"],
                                         item_group_view=item_view) if "rank_report" in config and int(config["rank_report"]) else None
+        # --neighbour_report=K (CLI-only, default 0 = off): every item's top-K cosine neighbours in the fused space and in each head's
+        # space -- how much of the fused list a head's list repeats, the lists' mean cosine and popularity -- as means overall and,
+        # with --item_group_view=[...], per item popularity group (evaluator.NeighbourReport)
+        k_near = int(config["neighbour_report"]) if "neighbour_report" in config else 0
+        if k_near < 0:
+            raise ValueError("neighbour_report must be 0 (off) or the K of the neighbour lists")
+        self.neighbour_reporter = NeighbourReport(dataset, train, k_near, item_group_view=item_view) if k_near else None
         self.infonce_criterion = nn.CrossEntropyLoss()          # BasicModel.py:32
 
     def getFileName(self):

@@ -1,0 +1,378 @@
+// Cosine top-K of table rows against the rows of the same table (similar items / similar users), and the overlap of two id lists.
+//
+// knn_chunk_kernel: the grid is (query tiles x candidate chunks). A workgroup of W waves holds 16 W query rows -- a wave owns 16
+// of them as the A operands of v_mfma_f32_16x16x4_f32 (registers for d = 32 / 64 / 128, a lane-private LDS column otherwise) --
+// and streams the KNN_CHUNK candidate rows of its chunk through ONE LDS stage of SR rows (row stride d + 4 floats: 16-byte
+// aligned b128 stores, B-operand reads two-way at worst); the next stage's rows and squared norms travel in registers while the
+// current one is multiplied (two barriers per stage). Every wave multiplies every 16-row candidate tile of the stage against its
+// own queries: lane (li, kq) ends with the dot products of candidate li against query rows 4 kq .. 4 kq + 3.
+//     score = (dot * (1 / max(sqrt(sq_q), 1e-12))) * (1 / max(sqrt(sq_c), 1e-12))
+// in this order, IEEE division: a pair's bits depend on the two rows' values and d alone (the k-loop runs 0, 4, 8, ... for every
+// pair; rows outside the table are zero operands and never read), not on its tile, stage, chunk or grid.
+// Selection (per chunk): a query row's list lives in LDS, CAP = K + 32 (score, id) slots, touched by its own wave only. A lane
+// whose score is > the row's threshold (-inf until K are kept, then the K-th best kept score; candidates arrive in ascending id
+// order, so an equal score later in the chunk loses the tie and is rightly dropped) checks the exclusions -- the query row itself,
+// then a linear scan of the query's CSR list: only scores that beat the threshold get there -- and appends with an LDS integer
+// add (a tile appends at most 16 entries per row). When a row holds more than CAP - 16 entries its wave ranks them by (score
+// descending, id ascending) by counting, keeps the K best in rank order and raises the threshold; the order of arrival in the
+// list never reaches the result. After warm-up the epilogue is two multiplies and one compare per score.
+// A chunk leaves K (score, id) pairs per query (id -1 / -inf where it has fewer) in the workspace, laid out [Q][chunks x K];
+// elimrec_topk_merge ranks them by the same order into the result.
+// Query tile and LDS: K <= 64 -> 4 waves, 64 query rows, lists 64 x 96 x 8 B = 48 KiB, stage <= 17 KiB (64 rows at d <= 64, 32
+// at d = 128, 16 otherwise), lane-private A columns d x 256 B for the general d (64 KiB at d = 256: one workgroup per CU there,
+// two or more for every other shape). K > 64 -> the tile is cut to ONE wave, 16 query rows: lists 16 x 288 x 8 B = 36 KiB,
+// stage 16 rows <= 16.3 KiB, A columns <= 16 KiB: at most 69 KiB, two workgroups per CU at K = 256 and any d.
+// list_overlap_kernel: one wave per row, list b in LDS, every lane counts its entries of a; integer, exact.
+#include "common.h"
+
+namespace elimrec {
+
+constexpr int KNN_CHUNK = 4096, KNN_TILE = 64, KNN_MAXK = 256, KNN_MAXD = 256, KNN_SLACK = 32, KNN_SMALLK = 64;
+constexpr int KNN_OVERLAP_MAXK = 1024;
+typedef float knn_v4f __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ void knn_wave_sync() {          // LDS written by other lanes of this wave is read next
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+__device__ __forceinline__ bool knn_before(float va, int ia, float vb, int ib) {   // a ranks before b (elimrec_topk_merge's order)
+    return va > vb || (va == vb && ia < ib);
+}
+__device__ __forceinline__ float knn_inv_norm(float sq) { return 1.f / fmaxf(sqrtf(sq), 1e-12f); }
+
+struct KnnArgs {
+    const float *T; int64_t ld, n_rows; int d;
+    const float *sq; int64_t ld_sq;
+    const int32_t *qrows; int64_t Q; int exclude_self;
+    const int64_t *excl_ptr; const int32_t *excl_rows;
+    int K, n_chunks, vec;              // vec: T is 16-byte aligned and ld % 4 == 0 -> a row's float4s are single loads
+    float *ws_val; int32_t *ws_idx;    // [Q][n_chunks x K]
+};
+
+constexpr int knn_stage_rows(int D, int W) { return (D == 0 || W == 1) ? 16 : (D <= 64 ? 64 : 32); }
+// dynamic LDS of one workgroup, in bytes (host and device agree through this one function)
+static inline size_t knn_lds_bytes(int D, int W, int d, int K) {
+    const size_t sr = (size_t)knn_stage_rows(D, W), cap = (size_t)K + KNN_SLACK, rows = 16 * (size_t)W;
+    return sr * (d + 4) * 4 + sr * 4 + rows * cap * 8 + rows * 8 + (D == 0 ? (size_t)W * (d / 4) * 64 * 4 : 0);
+}
+
+// the whole wave ranks the n entries of one list, leaves the K best in rank order, the new length and threshold
+template <int E>
+__device__ __forceinline__ void knn_compact(float *lv, int *li_, int *cnt, float *thr, int K, int lane) {
+    const int n = *cnt;
+    float v[E];
+    int id[E], rk[E];
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        const int c = lane + 64 * e;
+        v[e] = c < n ? lv[c] : 0.f;
+        id[e] = c < n ? li_[c] : 0;
+        rk[e] = 0;
+    }
+    for (int j = 0; j < n; ++j) {
+        const float vj = lv[j];
+        const int ij = li_[j];
+#pragma unroll
+        for (int e = 0; e < E; ++e) rk[e] += knn_before(vj, ij, v[e], id[e]) ? 1 : 0;
+    }
+    knn_wave_sync();                                        // every lane has read the list
+#pragma unroll
+    for (int e = 0; e < E; ++e)
+        if (lane + 64 * e < n && rk[e] < K) {
+            lv[rk[e]] = v[e];
+            li_[rk[e]] = id[e];
+            if (rk[e] == K - 1) *thr = v[e];
+        }
+    if (lane == 0) *cnt = n < K ? n : K;
+    knn_wave_sync();
+}
+
+// D: 32 / 64 / 128 = the dimension at compile time, query operands in registers; 0 = any d % 4 == 0 up to KNN_MAXD.
+// W: waves per workgroup (4: K <= KNN_SMALLK; 1: larger K)
+template <int D, int W>
+__global__ __launch_bounds__(64 * W) void knn_chunk_kernel(KnnArgs a) {
+    constexpr int SR = knn_stage_rows(D, W), NT = 64 * W, ROWS = 16 * W;
+    constexpr int E = W == 4 ? (KNN_SMALLK + KNN_SLACK + 63) / 64 : (KNN_MAXK + KNN_SLACK + 63) / 64;
+    constexpr int PFN = (SR * (D ? D : KNN_MAXD) / 4 + NT - 1) / NT;
+    const int d = D ? D : a.d, LD = d + 4, K = a.K, CAP = K + KNN_SLACK;
+    extern __shared__ float smem[];
+    float *s_b = smem;                                       // [SR][LD] the stage's candidate rows
+    float *s_invc = s_b + SR * LD;                           // [SR]     their reciprocal norms
+    float *s_lv = s_invc + SR;                               // [ROWS][CAP] list scores
+    int *s_li = (int *)(s_lv + ROWS * CAP);                  // [ROWS][CAP] list ids
+    int *s_cnt = s_li + ROWS * CAP;                          // [ROWS]
+    float *s_thr = (float *)(s_cnt + ROWS);                  // [ROWS]
+    float *s_a = s_thr + ROWS;                               // D == 0: [W][d / 4][64] lane-private query operands
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int li = lane & 15, kq = lane >> 4;
+    const int64_t q0 = (int64_t)blockIdx.x * ROWS + wave * 16;   // this wave's first query
+    const int chunk = blockIdx.y;
+    const int64_t c_begin = (int64_t)chunk * KNN_CHUNK;
+    const int64_t c_end = c_begin + KNN_CHUNK < a.n_rows ? c_begin + KNN_CHUNK : a.n_rows;
+    const float NEG = -__builtin_huge_valf(), POS = __builtin_huge_valf();
+
+    // A operands: query (q0 + li), element k = 4 ks + kq; a query outside [0, Q) or with an id outside the table is all zeros
+    float qa[D ? D / 4 : 1];
+    {
+        const int64_t q = q0 + li;
+        int64_t qr = q < a.Q ? (int64_t)a.qrows[q] : -1;
+        if (qr >= a.n_rows) qr = -1;
+        const float *row = qr >= 0 ? a.T + qr * a.ld + kq : nullptr;
+        if (D) {
+#pragma unroll
+            for (int ks = 0; ks < (D ? D / 4 : 1); ++ks) qa[ks] = row ? row[4 * ks] : 0.f;
+        } else {
+            for (int ks = 0; ks < d / 4; ++ks) s_a[(wave * (d / 4) + ks) * 64 + lane] = row ? row[4 * ks] : 0.f;
+        }
+    }
+    // the four query rows this lane's accumulators belong to: ids, reciprocal norms, thresholds (+inf: nothing is kept)
+    int qid[4];
+    float invq[4], thr[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int64_t q = q0 + 4 * kq + r;
+        int64_t qr = q < a.Q ? (int64_t)a.qrows[q] : -1;
+        if (qr >= a.n_rows) qr = -1;
+        qid[r] = (int)qr;
+        invq[r] = qr >= 0 ? knn_inv_norm(a.sq[qr * a.ld_sq]) : 0.f;
+        thr[r] = qr >= 0 ? NEG : POS;
+    }
+    if (lane < 16) {
+        const int64_t q = q0 + lane;
+        int64_t qr = q < a.Q ? (int64_t)a.qrows[q] : -1;
+        if (qr >= a.n_rows) qr = -1;
+        s_cnt[wave * 16 + lane] = 0;
+        s_thr[wave * 16 + lane] = qr >= 0 ? NEG : POS;
+    }
+
+    // a stage's rows as float4 over the workgroup, its squared norms on the first SR threads
+    float4 pf[PFN];
+    float sq_pf = 0.f;
+    auto load_stage = [&](int64_t s0) {
+#pragma unroll
+        for (int p = 0; p < PFN; ++p) {
+            const int e = (tid + NT * p) * 4;
+            if (e < SR * d) {
+                const int r = e / d, c = e - r * d;
+                const int64_t cand = s0 + r;
+                float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (cand < c_end) {
+                    const float *src = a.T + cand * a.ld + c;
+                    if (a.vec) x = *reinterpret_cast<const float4 *>(src);
+                    else x = make_float4(src[0], src[1], src[2], src[3]);
+                }
+                pf[p] = x;
+            }
+        }
+        if (tid < SR) sq_pf = s0 + tid < c_end ? a.sq[(s0 + tid) * a.ld_sq] : 1.f;
+    };
+    auto store_stage = [&]() {
+#pragma unroll
+        for (int p = 0; p < PFN; ++p) {
+            const int e = (tid + NT * p) * 4;
+            if (e < SR * d) {
+                const int r = e / d, c = e - r * d;
+                *reinterpret_cast<float4 *>(s_b + r * LD + c) = pf[p];
+            }
+        }
+        if (tid < SR) s_invc[tid] = knn_inv_norm(sq_pf);
+    };
+
+    float *my_lv = s_lv + wave * 16 * CAP;
+    int *my_li = s_li + wave * 16 * CAP;
+    int *my_cnt = s_cnt + wave * 16;
+    float *my_thr = s_thr + wave * 16;
+
+    load_stage(c_begin);
+    store_stage();
+    __syncthreads();
+    for (int64_t s0 = c_begin; s0 < c_end; s0 += SR) {
+        const bool more = s0 + SR < c_end;                   // workgroup-uniform
+        if (more) load_stage(s0 + SR);
+#pragma unroll 1
+        for (int t = 0; t < SR / 16; ++t) {
+            const int64_t t0 = s0 + 16 * t;
+            if (t0 >= c_end) break;                          // workgroup-uniform
+            knn_v4f acc = (knn_v4f){0.f, 0.f, 0.f, 0.f};
+            const float *bp = s_b + (16 * t + li) * LD + kq;
+            if (D) {
+#pragma unroll
+                for (int ks = 0; ks < (D ? D / 4 : 1); ++ks) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(qa[ks], bp[4 * ks], acc, 0, 0, 0);
+            } else {
+                const float *ap = s_a + wave * (d / 4) * 64 + lane;
+                for (int ks = 0; ks < d / 4; ++ks) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(ap[ks * 64], bp[4 * ks], acc, 0, 0, 0);
+            }
+            // lane: candidate t0 + li against query rows 4 kq + r of this wave
+            const int64_t cand = t0 + li;
+            const bool cand_ok = cand < c_end;
+            const float invc = s_invc[16 * t + li];
+            float s[4];
+            bool pass[4], any = false;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                s[r] = (acc[r] * invq[r]) * invc;
+                pass[r] = cand_ok && s[r] > thr[r];
+                any = any || pass[r];
+            }
+            if (__ballot(any) == 0ull) continue;             // wave-uniform: the steady state
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                if (!pass[r]) continue;
+                bool keep = !(a.exclude_self && (int)cand == qid[r]);
+                if (keep && a.excl_ptr) {
+                    const int64_t q = q0 + 4 * kq + r;
+                    const int64_t e1 = a.excl_ptr[q + 1];
+                    for (int64_t e = a.excl_ptr[q]; e < e1 && keep; ++e) keep = a.excl_rows[e] != (int)cand;
+                }
+                if (keep) {
+                    const int row = 4 * kq + r;
+                    const int pos = atomicAdd(&my_cnt[row], 1);  // <= CAP - 16 before the tile, at most 16 adds per row and tile
+                    my_lv[row * CAP + pos] = s[r];
+                    my_li[row * CAP + pos] = (int)cand;
+                }
+            }
+            knn_wave_sync();
+            unsigned long long full = __ballot(lane < 16 && my_cnt[lane & 15] > CAP - 16) & 0xffffull;
+            if (full) {                                      // wave-uniform
+                while (full) {
+                    const int row = __builtin_ctzll(full);
+                    full &= full - 1;
+                    knn_compact<E>(my_lv + row * CAP, my_li + row * CAP, &my_cnt[row], &my_thr[row], K, lane);
+                }
+#pragma unroll
+                for (int r = 0; r < 4; ++r) thr[r] = my_thr[4 * kq + r];
+            }
+        }
+        __syncthreads();                                     // every wave is done with the stage
+        if (more) store_stage();
+        __syncthreads();
+    }
+
+    // the chunk's K best of every query row of this wave, in rank order, fillers behind them
+    for (int row = 0; row < 16; ++row) {
+        const int64_t q = q0 + row;
+        if (q >= a.Q) break;                                 // wave-uniform
+        knn_compact<E>(my_lv + row * CAP, my_li + row * CAP, &my_cnt[row], &my_thr[row], K, lane);
+        const int n = my_cnt[row];
+        const int64_t o = (q * a.n_chunks + chunk) * K;
+        for (int k = lane; k < K; k += 64) {
+            a.ws_val[o + k] = k < n ? my_lv[row * CAP + k] : NEG;
+            a.ws_idx[o + k] = k < n ? my_li[row * CAP + k] : -1;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void list_overlap_kernel(const int32_t *__restrict__ la, const int32_t *__restrict__ lb, int64_t n_rows,
+                                                           int K, int32_t *__restrict__ count) {
+    extern __shared__ int s_list[];                          // [4][K]
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t r = (int64_t)blockIdx.x * 4 + wave;
+    if (r >= n_rows) return;                                 // (wave-uniform; no workgroup barrier below)
+    int *b = s_list + wave * K;
+    for (int k = lane; k < K; k += 64) b[k] = lb[r * K + k];
+    knn_wave_sync();
+    int n = 0;
+    for (int k = lane; k < K; k += 64) {
+        const int x = la[r * K + k];
+        if (x < 0) continue;
+        bool hit = false;
+        for (int j = 0; j < K; ++j) hit = hit || b[j] == x;
+        n += hit ? 1 : 0;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off, 64);
+    if (lane == 0) count[r] = n;
+}
+
+template <int D, int W>
+static int knn_launch(const KnnArgs &a, int64_t n_tiles, hipStream_t s) {
+    const size_t lds = knn_lds_bytes(D, W, a.d, a.K);
+    if (lds > 64 * 1024) {
+        int rc = check_hip(hipFuncSetAttribute((const void *)knn_chunk_kernel<D, W>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
+                           "cosine_topk (LDS)");
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL((knn_chunk_kernel<D, W>), dim3((unsigned)n_tiles, (unsigned)a.n_chunks), dim3(64 * W), lds, s, a);
+    ELIMREC_LAUNCH_CHECK("cosine_topk");
+    return 0;
+}
+
+template <int W>
+static int knn_dispatch(const KnnArgs &a, int64_t n_tiles, hipStream_t s) {
+    switch (a.d) {
+    case 32: return knn_launch<32, W>(a, n_tiles, s);
+    case 64: return knn_launch<64, W>(a, n_tiles, s);
+    case 128: return knn_launch<128, W>(a, n_tiles, s);
+    default: return knn_launch<0, W>(a, n_tiles, s);
+    }
+}
+
+static inline int64_t knn_chunks(int64_t n_rows) { return (n_rows + KNN_CHUNK - 1) / KNN_CHUNK; }
+
+}  // namespace elimrec
+
+using namespace elimrec;
+
+extern "C" int elimrec_cosine_topk_chunk(void) { return KNN_CHUNK; }
+extern "C" int elimrec_cosine_topk_tile(void) { return KNN_TILE; }
+
+extern "C" size_t elimrec_cosine_topk_workspace(int64_t Q, int64_t n_rows, int K) {
+    if (Q <= 0 || n_rows <= 0 || K <= 0) return 16;
+    const size_t pairs = (size_t)Q * (size_t)knn_chunks(n_rows) * (size_t)K;
+    return align_up(pairs * 4, 16) + align_up(pairs * 4, 16);
+}
+
+extern "C" int elimrec_cosine_topk(const float *d_T, int64_t ld, int64_t n_rows, int d, const float *d_sqnorm, int64_t ld_sq,
+                                   const int32_t *d_query_rows, int64_t Q, int exclude_self, const int64_t *d_excl_ptr,
+                                   const int32_t *d_excl_rows, int K, int32_t *d_idx, float *d_val, void *d_workspace,
+                                   size_t workspace_bytes, void *stream) {
+    ELIMREC_REQUIRE(K >= 1 && K <= KNN_MAXK, "cosine_topk: 1 <= K <= %d, got %d", KNN_MAXK, K);
+    ELIMREC_REQUIRE(d >= 4 && d <= KNN_MAXD && d % 4 == 0, "cosine_topk: d %% 4 == 0 and 4 <= d <= %d, got %d", KNN_MAXD, d);
+    ELIMREC_REQUIRE(Q >= 0 && n_rows >= 0 && n_rows < (int64_t)INT32_MAX - KNN_CHUNK, "cosine_topk: need Q >= 0 and 0 <= n_rows < 2^31 - %d",
+                    KNN_CHUNK + 1);
+    ELIMREC_REQUIRE(ld >= d && ld_sq >= 1, "cosine_topk: ld < d or ld_sq < 1");
+    if (Q == 0) return 0;
+    ELIMREC_REQUIRE(d_query_rows && d_idx && d_workspace, "cosine_topk: null pointer");
+    ELIMREC_REQUIRE(n_rows == 0 || (d_T && d_sqnorm), "cosine_topk: null pointer");
+    ELIMREC_REQUIRE((d_excl_ptr == nullptr) == (d_excl_rows == nullptr), "cosine_topk: the exclusion CSR needs both arrays or neither");
+    ELIMREC_REQUIRE(((uintptr_t)d_workspace & 15) == 0, "cosine_topk: the workspace must be 16-byte aligned");
+    const size_t need = elimrec_cosine_topk_workspace(Q, n_rows, K);
+    ELIMREC_REQUIRE(workspace_bytes >= need, "cosine_topk: workspace too small (%zu < %zu bytes)", workspace_bytes, need);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t n_chunks = knn_chunks(n_rows);
+    if (n_chunks == 0) {                                     // an empty table: every list is fillers
+        int rc = check_hip(hipMemsetAsync(d_idx, 0xff, (size_t)Q * K * sizeof(int32_t), s), "cosine_topk (fill)");
+        if (rc == 0 && d_val) rc = check_hip(hipMemsetD32Async((hipDeviceptr_t)d_val, (int)0xff800000u, (size_t)Q * K, s), "cosine_topk (fill)");
+        return rc;
+    }
+    ELIMREC_REQUIRE(n_chunks <= 65535, "cosine_topk: %lld chunks exceed one launch", (long long)n_chunks);
+    ELIMREC_REQUIRE(Q < (int64_t)INT32_MAX && n_chunks * K < (int64_t)INT32_MAX, "cosine_topk: too many queries or chunks for the merge");
+    const size_t pairs = (size_t)Q * (size_t)n_chunks * (size_t)K;
+    KnnArgs a;
+    a.T = d_T; a.ld = ld; a.n_rows = n_rows; a.d = d;
+    a.sq = d_sqnorm; a.ld_sq = ld_sq;
+    a.qrows = d_query_rows; a.Q = Q; a.exclude_self = exclude_self ? 1 : 0;
+    a.excl_ptr = d_excl_ptr; a.excl_rows = d_excl_rows;
+    a.K = K; a.n_chunks = (int)n_chunks;
+    a.vec = (((uintptr_t)d_T & 15) == 0 && ld % 4 == 0) ? 1 : 0;
+    a.ws_val = (float *)d_workspace;
+    a.ws_idx = (int32_t *)((char *)d_workspace + align_up(pairs * 4, 16));
+    const int rows = K <= KNN_SMALLK ? KNN_TILE : 16;
+    const int64_t n_tiles = (Q + rows - 1) / rows;
+    ELIMREC_REQUIRE(n_tiles < (int64_t)INT32_MAX, "cosine_topk: too many query tiles for one launch");
+    int rc = K <= KNN_SMALLK ? knn_dispatch<4>(a, n_tiles, s) : knn_dispatch<1>(a, n_tiles, s);
+    if (rc) return rc;
+    return elimrec_topk_merge(a.ws_val, a.ws_idx, (int)Q, (int)(n_chunks * K), K, d_idx, d_val, stream);
+}
+
+extern "C" int elimrec_list_overlap(const int32_t *d_a, const int32_t *d_b, int64_t n_rows, int K, int32_t *d_count, void *stream) {
+    ELIMREC_REQUIRE(n_rows >= 0 && K >= 1 && K <= KNN_OVERLAP_MAXK, "list_overlap: need n_rows >= 0 and 1 <= K <= %d", KNN_OVERLAP_MAXK);
+    if (n_rows == 0) return 0;
+    ELIMREC_REQUIRE(d_a && d_b && d_count, "list_overlap: null pointer");
+    ELIMREC_REQUIRE((n_rows + 3) / 4 < (int64_t)INT32_MAX, "list_overlap: too many rows for one launch");
+    hipLaunchKernelGGL(list_overlap_kernel, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), (size_t)4 * K * sizeof(int), (hipStream_t)stream,
+                       d_a, d_b, n_rows, K, d_count);
+    ELIMREC_LAUNCH_CHECK("list_overlap");
+    return 0;
+}

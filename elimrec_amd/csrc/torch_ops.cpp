@@ -366,6 +366,41 @@ at::Tensor rank_targets(const at::Tensor &scores, const at::Tensor &tgt_ptr, con
     return out;
 }
 
+// ---- cosine top-K of table rows against the rows of the same table; overlap of two id lists
+std::tuple<at::Tensor, at::Tensor> cosine_topk(const at::Tensor &table, const at::Tensor &sqnorm, const at::Tensor &query_rows, int64_t K,
+                                               bool exclude_self) {
+    const at::Tensor t = rowmajor(table, "table");
+    need(sqnorm, "sqnorm", at::kFloat, 1); need(query_rows, "query_rows", at::kInt, 1);
+    const at::Tensor q = query_rows.contiguous();
+    const int64_t n = t.size(0), d = t.size(1), Q = q.numel();
+    TORCH_CHECK(K >= 1 && K <= 256, "elimrec::cosine_topk: 1 <= K <= 256, got ", K);
+    TORCH_CHECK(d % 4 == 0 && d >= 4 && d <= 256, "elimrec::cosine_topk: the table needs d % 4 == 0 and 4 <= d <= 256 columns, got ", d);
+    TORCH_CHECK(sqnorm.numel() == n, "elimrec::cosine_topk: sqnorm needs one entry per table row (", n, "), got ", sqnorm.numel());
+    if (Q > 0) {    // no unchecked id reaches the kernel
+        const int64_t lo = q.min().item<int64_t>(), hi = q.max().item<int64_t>();
+        TORCH_CHECK_INDEX(lo >= 0 && hi < n, "elimrec::cosine_topk: query rows span [", lo, ", ", hi, "], the table has ", n, " rows");
+    }
+    at::Tensor idx = at::empty({Q, K}, q.options()), val = at::empty({Q, K}, t.options());
+    if (Q == 0) return {idx, val};
+    const size_t need_ws = elimrec_cosine_topk_workspace(Q, n, (int)K);
+    at::Tensor ws = at::empty({(int64_t)need_ws}, t.options().dtype(at::kByte));
+    check(elimrec_cosine_topk(t.data_ptr<float>(), t.stride(0), n, (int)d, sqnorm.data_ptr<float>(), n > 1 ? sqnorm.stride(0) : 1,
+                              q.data_ptr<int32_t>(), Q, exclude_self ? 1 : 0, nullptr, nullptr, (int)K, idx.data_ptr<int32_t>(),
+                              val.data_ptr<float>(), ws.data_ptr(), (size_t)ws.numel(), cur_stream()),
+          "cosine_topk");
+    return {idx, val};
+}
+
+at::Tensor list_overlap(const at::Tensor &a, const at::Tensor &b) {
+    need(a, "a", at::kInt, 2); need(b, "b", at::kInt, 2);
+    const at::Tensor x = a.contiguous(), y = b.contiguous();
+    TORCH_CHECK(x.sizes() == y.sizes() && x.size(1) >= 1 && x.size(1) <= 1024, "elimrec::list_overlap: two [n x K] lists of one shape, 1 <= K <= 1024");
+    at::Tensor out = at::empty({x.size(0)}, x.options());
+    check(elimrec_list_overlap(x.data_ptr<int32_t>(), y.data_ptr<int32_t>(), x.size(0), (int)x.size(1), out.data_ptr<int32_t>(), cur_stream()),
+          "list_overlap");
+    return out;
+}
+
 at::Tensor sample_negatives(const at::Tensor &excl_ptr, const at::Tensor &excl_items, int64_t num_items, int64_t n_neg, int64_t seed) {
     need(excl_ptr, "excl_ptr", at::kLong, 1); need(excl_items, "excl_items", at::kInt, 1);
     const at::Tensor p = excl_ptr.contiguous(), it = excl_items.contiguous();
@@ -485,6 +520,8 @@ TORCH_LIBRARY(elimrec, m) {
     m.def("score_candidates(Tensor Y, int U, int I, Tensor users, int d, int S, int head_mask, int fusion_mode, int predict_type, Tensor cand_ptr, Tensor cand_items, int width) -> Tensor");
     m.def("score_effects(Tensor Y, int U, int I, Tensor users, int d, int S, int head_mask, int fusion_mode, Tensor cand_ptr, Tensor cand_items, int width) -> Tensor");
     m.def("rank_targets(Tensor scores, Tensor tgt_ptr, Tensor tgt_items) -> Tensor");
+    m.def("cosine_topk(Tensor table, Tensor sqnorm, Tensor query_rows, int K, bool exclude_self) -> (Tensor, Tensor)");
+    m.def("list_overlap(Tensor a, Tensor b) -> Tensor");
     m.def("sample_negatives(Tensor excl_ptr, Tensor excl_items, int num_items, int n_neg, int seed) -> Tensor");
     m.def("lookup_counts(Tensor acts, int U, int I, int[] user_bounds, int[] item_bounds) -> Tensor");
     m.def("lookup_pack(Tensor acts, int U, int I, int[] user_bounds, int[] item_bounds, int me, Tensor shard, int row_bytes) -> (Tensor, Tensor)");
@@ -509,6 +546,8 @@ TORCH_LIBRARY_IMPL(elimrec, CUDA, m) {
     m.impl("score_candidates", &score_candidates);
     m.impl("score_effects", &score_effects);
     m.impl("rank_targets", &rank_targets);
+    m.impl("cosine_topk", &cosine_topk);
+    m.impl("list_overlap", &list_overlap);
     m.impl("sample_negatives", &sample_negatives);
     m.impl("lookup_counts", &lookup_counts);
     m.impl("lookup_pack", &lookup_pack);

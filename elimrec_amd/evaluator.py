@@ -773,6 +773,96 @@ class RankReport(object):
         return self._tables(rows, ("delta", "improved", "worsened"), None, (), self._resident(ranks_a.device))
 
 
+class NeighbourReport(object):
+    """Whose neighbourhood the fused space copies (--neighbour_report=K): for EVERY item its top-k neighbour lists by cosine in the
+    fused space and in each single-modal head's space (EliMRec.neighbours_device, csrc/knn.hip), items in blocks of block_items,
+    and per item the columns of ops.neighbour_columns(mods):
+      overlap_<m> = |fused list & head m's list| / k (ops.list_overlap); cos_fused, cos_<m> = the mean score of the list;
+      pop_fused, pop_<m> = the mean training-interaction count of the listed neighbours
+    (fillers skipped; a column of a row without neighbours is NaN). Their means over all items and -- item_group_view -- per item
+    popularity group (assign_item_groups over the items' training interactions) are ops.group_metric_means over the
+    [items x C] block: only the [1 + groups x C] table reaches the host. The lists do not depend on the predict type."""
+
+    def __init__(self, dataset, user_train_dict, k, item_group_view=None):
+        if not isinstance(user_train_dict, dict):
+            raise TypeError("user_train_dict must be a dict")
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1 or k > ops.KNN_MAX_K:
+            raise ValueError("k must be an integer in [1, %d], got %r" % (ops.KNN_MAX_K, k))
+        self.dataset = dataset
+        self.num_items = I = int(dataset.num_items)
+        self.k = int(k)
+        self.block_items = 8192
+        self.item_counts = np.zeros(I, dtype=np.int64)
+        for items in user_train_dict.values():
+            np.add.at(self.item_counts, np.asarray(list(items), dtype=np.int64), 1)
+        self.group_labels, self._positions = ["all:".ljust(12)], [np.arange(I, dtype=np.int64)]
+        if item_group_view is not None:
+            labels, positions = assign_item_groups(np.arange(I, dtype=np.int64), self.item_counts, item_group_view)
+            self.group_labels += labels
+            self._positions += positions
+        self._device = {}                  # device -> the group index, the counts and the blocks' checked queries resident there
+
+    def _resident(self, device):
+        hit = self._device.get(str(device))
+        if hit is None:
+            ptr = np.zeros(len(self._positions) + 1, dtype=np.int64)
+            np.cumsum([p.size for p in self._positions], out=ptr[1:])
+            hit = dict(groups=ops.GroupIndex(ptr, np.concatenate(self._positions).astype(np.int32), self.num_items, device),
+                       counts=torch.from_numpy(self.item_counts.astype(np.float64)).to(device), queries={})
+            self._device[str(device)] = hit
+        return hit
+
+    def neighbour_rows(self, model):
+        """Every item's row of the report on the device: ([items x C] float32, column names)."""
+        if not hasattr(model, "neighbours_device"):
+            raise TypeError("model must expose neighbours_device()")
+        if hasattr(model, "_ensure_tables") and getattr(model, "_cache", None) is not None:
+            model._ensure_tables()
+        if getattr(model, "_eval_shard", None) is not None:
+            raise CandidateScoringError("the neighbour report needs the whole cached item table on this rank; the tables are "
+                                        "item-sharded (lean / multi-rank evaluation): run without --neighbour_report")
+        if model.num_items != self.num_items:
+            raise ValueError("the report was built for %d items, the model has %d" % (self.num_items, model.num_items))
+        device = model._require_gpu()
+        res = self._resident(device)
+        mods = tuple(model._mods)
+        columns = ops.neighbour_columns(mods)
+        S, k, I = len(mods), self.k, self.num_items
+        rows = torch.empty(I, len(columns), dtype=torch.float32, device=device)
+        step = max(1, int(self.block_items))
+        idx = torch.empty(1 + S, min(step, I), k, dtype=torch.int32, device=device)
+        val = torch.empty(1 + S, min(step, I), k, dtype=torch.float32, device=device)
+        cnt = torch.empty(min(step, I), dtype=torch.int32, device=device)
+        nan = torch.full((), float("nan"), dtype=torch.float64, device=device)
+        for a in range(0, I, step):
+            b = min(a + step, I)
+            query = res["queries"].get((a, b))
+            if query is None:
+                query = res["queries"][(a, b)] = ops.NeighbourQuery(np.arange(a, b, dtype=np.int32), I, device)
+            for h, space in enumerate(("fused",) + mods):
+                model.neighbours_device("item", None, k, space, idx[h, :b - a], val[h, :b - a], query=query)
+            listed = idx[:, :b - a] >= 0                                           # [1 + S x B x k]
+            n = listed.sum(dim=2).double()
+            out = rows[a:b]
+            for h in range(S):
+                ops.list_overlap(idx[0, :b - a], idx[1 + h, :b - a], cnt)
+                out[:, h] = torch.where(n[0] > 0, cnt[:b - a].double() / k, nan).float()
+            out[:, S:2 * S + 1] = (torch.where(listed, val[:, :b - a].double(), 0.0).sum(dim=2) / n).t().float()
+            pop = res["counts"][idx[:, :b - a].clamp(min=0).long()]
+            out[:, 2 * S + 1:] = (torch.where(listed, pop, 0.0).sum(dim=2) / n).t().float()
+        return rows, columns
+
+    def evaluate(self, model):
+        """(final [1 + item groups x C] float32: row 0 = all items, then one row per item popularity group; buf: a header of column
+        names and one "%.8f" line per row, in the effect report's format)."""
+        rows, columns = self.neighbour_rows(model)
+        out = torch.empty(len(self.group_labels), rows.shape[1], dtype=torch.float32, device=rows.device)
+        final = ops.group_metric_means(rows, self._resident(rows.device)["groups"], None, out).cpu().numpy()
+        buf = "columns:\t%s" % "\t".join(str(c).ljust(12) for c in columns) + "".join(
+            "\n%s\t%s" % (label, "\t".join(("%.8f" % x).ljust(12) for x in row)) for label, row in zip(self.group_labels, final))
+        return final, buf
+
+
 class ProxyEvaluator(object):
     def __init__(self, dataset, user_train_dict, user_test_dict, user_neg_test=None, metric=None, group_view=None,
                  top_k=50, batch_size=1024, num_thread=8):

@@ -39,6 +39,7 @@ from .plugin import EmbeddingParameter, LazyGradParameter, StepController
 
 # EliMRec.explain's result: column names, item ids CPU int32 [B x W] (-1 = padding), values CPU fp32 [B x W x C]
 Effects = collections.namedtuple("Effects", ("columns", "items", "values"))
+Neighbours = collections.namedtuple("Neighbours", ("ids", "scores"))
 
 
 def create_adj_mat(train_users, train_items, num_users, num_items, adj_type):
@@ -1366,6 +1367,81 @@ class EliMRec(BasicModel):
             rank, _, _ = self.rank_items_device(user_ids, index, *masked)
             out[np.arange(width)[None, :] < lens[:, None]] = rank.cpu().numpy()
         return torch.from_numpy(out)
+
+    def _neighbour_space(self, space):
+        """Head block of the cached Y a neighbour space names: 0 = the fused rows predict() scores with, 1 + h = head h."""
+        if space == "fused":
+            return 0
+        if isinstance(space, str) and space in self._mods:
+            return 1 + list(self._mods).index(space)
+        raise ValueError("space must be 'fused' or one of this model's heads %s, got %r" % ("/".join(self._mods) or "(none)", space))
+
+    @torch.no_grad()
+    def neighbours_device(self, side, rows, k, space, out_idx, out_val, query=None):
+        """The k rows closest by cosine to each given row, among the item rows (side "item") or the user rows ("user") of one block
+        of the cached tables: space "fused" (block 0, the rows predict() scores with) or a head letter of self._mods. out_idx int32 /
+        out_val float32 (optional) [B x k] on the device, (score descending, id ascending), -1 / -inf where fewer than k rows exist
+        (csrc/knn.hip). rows: the query ids (host array or tensor, checked on the host; the row itself is always left out) -- or
+        query = an ops.NeighbourQuery over the side's rows, checked once, which may carry per-query exclusion lists. Tables as
+        predict_device: those of the last training forward."""
+        dev = self._require_gpu()
+        if side not in ("item", "user"):
+            raise ValueError("side must be 'item' or 'user', got %r" % (side,))
+        h = self._neighbour_space(space)
+        self._plugin.realise_forward()
+        if self._ws is None or self._cache is None:
+            raise RuntimeError("similar_items() / similar_users() need the tables cached by a training forward (call bpr_loss or "
+                               "compute first)")
+        self._ensure_tables()
+        if self.__dict__.get("_eval_shard") is not None:
+            raise CandidateScoringError("neighbour lists need the whole cached tables on this rank; the tables are item-sharded "
+                                        "(lean / multi-rank evaluation)")
+        U, d = self.num_users, self.latent_dim
+        lo, n = (U, self.num_items) if side == "item" else (0, U)
+        sqn = self._block_sqnorms(dev)
+        if query is None:
+            query = ops.NeighbourQuery(rows, n, dev)
+        elif not isinstance(query, ops.NeighbourQuery) or query.n_rows != n:
+            raise ValueError("query must be an ops.NeighbourQuery over the %d %s rows" % (n, side))
+        need = ops.cosine_topk_workspace(query.n_queries, n, k)
+        if self._ws.get("knn_ws") is None or self._ws["knn_ws"].numel() < need:
+            self._ws["knn_ws"] = torch.empty(need, dtype=torch.uint8, device=dev)
+        ops.cosine_topk(self._ws["Y"][lo:lo + n, h * d:(h + 1) * d], sqn[lo:lo + n, h], query, k, out_idx, out_val, exclude_self=True,
+                        workspace=self._ws["knn_ws"])
+        return out_idx, out_val
+
+    def _similar(self, side, ids, k, space, exclude):
+        n_rows = self.num_items if side == "item" else self.num_users
+        k = int(k)
+        if not 1 <= k <= ops.KNN_MAX_K:
+            raise ValueError("k must lie in [1, %d]" % ops.KNN_MAX_K)
+        self._neighbour_space(space)
+        ids = np.asarray([int(i) for i in ids], dtype=np.int64)
+        if ids.size and (ids.min() < 0 or ids.max() >= n_rows):
+            raise IndexError("%s ids must lie in [0, %d)" % (side, n_rows))
+        lists = [(exclude or {}).get(int(i), []) for i in ids]
+        ptr = np.zeros(ids.size + 1, dtype=np.int64)
+        np.cumsum([len(x) for x in lists], out=ptr[1:])
+        flat = np.fromiter((int(i) for x in lists for i in x), dtype=np.int64, count=int(ptr[-1]))
+        if flat.size and (flat.min() < 0 or flat.max() >= n_rows):
+            raise IndexError("excluded %s ids must lie in [0, %d)" % (side, n_rows))
+        dev = self._require_gpu()
+        idx = torch.empty(ids.size, k, dtype=torch.int32, device=dev)
+        val = torch.empty(ids.size, k, dtype=torch.float32, device=dev)
+        query = ops.NeighbourQuery(ids, n_rows, dev, ptr if flat.size else None, flat if flat.size else None)
+        self.neighbours_device(side, None, k, space, idx, val, query=query)
+        return Neighbours(idx.cpu(), val.cpu())
+
+    def similar_items(self, item_ids, k, space="fused", exclude=None):
+        """The k items closest to each given item by cosine: Neighbours(ids CPU int32 [B x k] (-1 padded), scores CPU fp32 [B x k]
+        (-inf padded)), by (score descending, id ascending). space: "fused" -- the rows predict() scores with -- or one of the
+        model's single-modal heads (a letter of self._mods: does the fused neighbourhood copy the visual one?). The item itself is
+        always left out; `exclude` = dict item -> item ids to leave out as well. 1 <= k <= 256."""
+        return self._similar("item", item_ids, k, space, exclude)
+
+    def similar_users(self, user_ids, k, space="fused", exclude=None):
+        """similar_items over the user rows: the k users closest to each given user."""
+        return self._similar("user", user_ids, k, space, exclude)
 
     def predict(self, user_ids, candidate_items=None):
         """:96-113. CPU fp32 tensor [len(user_ids) x I]; `candidate_items` is ignored as in the reference."""

@@ -895,6 +895,10 @@ def __getattr__(name):
         return int(_lib.load().elimrec_rank_segment())
     if name == "RANK_TARGETS_PER_PASS":  # targets rank_targets stages per pass over a segment
         return int(_lib.load().elimrec_rank_targets_per_pass())
+    if name == "KNN_CHUNK":              # candidate rows one workgroup of cosine_topk streams
+        return int(_lib.load().elimrec_cosine_topk_chunk())
+    if name == "KNN_TILE":               # query rows one workgroup of cosine_topk holds (16 when K > 64)
+        return int(_lib.load().elimrec_cosine_topk_tile())
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 
@@ -1089,3 +1093,131 @@ def peer_cols_to_rows(recv, out0, out1):
     assert recv.is_contiguous() and out0.stride(1) == 1 and out1.stride(1) == 1 and out0.shape == (R, W * dl) and out1.shape == (R, W * dl)
     _lib.check(_lib.load().elimrec_peer_cols_to_rows(_dev(recv, "recv"), W, R, dl, _dev(out0, "out0"), out0.stride(0), _dev(out1, "out1"),
                                                     out1.stride(0), _stream()), "peer_cols_to_rows")
+
+
+KNN_MAX_K, KNN_MAX_D = 256, 256
+
+
+class NeighbourQuery(object):
+    """Query rows of an n_rows-row table and, optionally, per query a list of rows to leave out as CSR (excl_ptr [Q + 1],
+    excl_rows), CHECKED ON THE HOST -- every query id and every exclusion id in [0, n_rows), ptr[0] = 0, ascending,
+    ptr[Q] = len(excl_rows) -- and then resident on `device`: cosine_topk takes it as is, call after call, and no unchecked id
+    ever reaches a kernel (the counterpart of TargetIndex). Exclusion lists may repeat ids, in any order, and may be empty."""
+
+    def __init__(self, rows, n_rows, device, excl_ptr=None, excl_rows=None):
+        q = _host(rows).reshape(-1)
+        if q.size and not np.issubdtype(q.dtype, np.integer):
+            raise TypeError("elimrec_amd.ops.NeighbourQuery: rows must hold integers, got %s" % q.dtype)
+        if q.size and (int(q.min()) < 0 or int(q.max()) >= int(n_rows)):
+            raise IndexError("elimrec_amd.ops.NeighbourQuery: query rows span [%d, %d], the table has %d rows"
+                             % (int(q.min()), int(q.max()), int(n_rows)))
+        if (excl_ptr is None) != (excl_rows is None):
+            raise ValueError("elimrec_amd.ops.NeighbourQuery: the exclusion CSR needs excl_ptr and excl_rows, or neither")
+        self.n_rows, self.n_queries = int(n_rows), int(q.size)
+        self.rows = torch.from_numpy(np.ascontiguousarray(q if q.size else np.zeros(1), dtype=np.int32)).to(device)
+        self.excl_ptr = self.excl_rows = None
+        if excl_ptr is not None:
+            p = np.ascontiguousarray(_host(excl_ptr), dtype=np.int64).reshape(-1)
+            e = _host(excl_rows).reshape(-1)
+            if p.size != q.size + 1:
+                raise ValueError("elimrec_amd.ops.NeighbourQuery: excl_ptr needs Q + 1 = %d entries, got %d" % (q.size + 1, p.size))
+            if e.size and not np.issubdtype(e.dtype, np.integer):
+                raise TypeError("elimrec_amd.ops.NeighbourQuery: excl_rows must hold integers, got %s" % e.dtype)
+            if p[0] != 0 or p[-1] != e.size or (np.diff(p) < 0).any():
+                raise ValueError("elimrec_amd.ops.NeighbourQuery: excl_ptr must ascend from 0 to len(excl_rows) = %d" % e.size)
+            if e.size and (int(e.min()) < 0 or int(e.max()) >= int(n_rows)):
+                raise IndexError("elimrec_amd.ops.NeighbourQuery: excluded rows span [%d, %d], the table has %d rows"
+                                 % (int(e.min()), int(e.max()), int(n_rows)))
+            self.excl_ptr = torch.from_numpy(p).to(device)
+            self.excl_rows = torch.from_numpy(np.ascontiguousarray(e if e.size else np.zeros(1), dtype=np.int32)).to(device)
+
+
+def cosine_topk_workspace(Q, n_rows, K):
+    """Bytes of workspace cosine_topk needs (host arithmetic only)."""
+    return int(_lib.load().elimrec_cosine_topk_workspace(int(Q), int(n_rows), int(K)))
+
+
+def _knn_out(t, name, dtype, Q, K):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError("elimrec_amd.ops: '%s' must be a HIP device tensor (the hot path has no CPU implementation)" % name)
+    if t.dtype != dtype:
+        raise TypeError("elimrec_amd.ops: '%s' must be %s, got %s" % (name, dtype, t.dtype))
+    ok = t.is_contiguous() and ((t.dim() == 2 and t.shape[1] == K and t.shape[0] >= Q) or (t.dim() == 1 and t.numel() >= Q * K))
+    if not ok:
+        raise ValueError("elimrec_amd.ops.cosine_topk: %s must be contiguous, [>= %d x %d] or 1-D with at least %d entries"
+                         % (name, Q, K, Q * K))
+    return t.data_ptr()
+
+
+def cosine_topk(table, sqnorm, query_rows, K, out_idx, out_val=None, exclude_self=True, excl_ptr=None, excl_rows=None,
+                workspace=None):
+    """elimrec_cosine_topk: per query row the K rows of `table` closest to it by cosine, by (score descending, row id ascending):
+    out_idx int32 / out_val float32 (optional) [Q x K], -1 / -inf where fewer than K candidates exist; entries of the outputs beyond
+    [Q x K] are left alone. table [n x d] float32 with unit column stride (a column block of a wider matrix is fine), d % 4 == 0,
+    4 <= d <= 256; sqnorm: 1-D float32, n entries, any stride (a column of row_sqnorms' table): the rows' squared norms. 1 <= K <= 256.
+    Left out: the query itself (exclude_self), then the query's list of the CSR excl_ptr [Q + 1] / excl_rows. query_rows and the
+    CSR: host arrays or tensors -- checked on the host at every call (a synchronisation for device tensors) -- or query_rows = a
+    NeighbourQuery (excl_ptr = excl_rows = None), checked once. workspace: uint8 device tensor of at least cosine_topk_workspace
+    bytes, 16-byte aligned (default: allocated here)."""
+    if not isinstance(table, torch.Tensor) or not table.is_cuda:
+        _dev(table, "table")
+    tp, ld = _rowmajor(table, "table")
+    n, d = table.shape
+    sp = _dev(sqnorm, "sqnorm")
+    if sqnorm.dim() != 1 or sqnorm.numel() != n or sqnorm.device != table.device:
+        raise ValueError("elimrec_amd.ops.cosine_topk: sqnorm must be 1-D with one entry per table row (%d) on the table's device" % n)
+    ld_sq = max(1, int(sqnorm.stride(0)))
+    K = int(K)
+    if not 1 <= K <= KNN_MAX_K:
+        raise ValueError("elimrec_amd.ops.cosine_topk: 1 <= K <= %d, got %d" % (KNN_MAX_K, K))
+    if d % 4 != 0 or not 4 <= d <= KNN_MAX_D:
+        raise ValueError("elimrec_amd.ops.cosine_topk: the table needs d %% 4 == 0 and 4 <= d <= %d columns, got %d" % (KNN_MAX_D, d))
+    if isinstance(query_rows, NeighbourQuery):
+        query = query_rows
+        if excl_ptr is not None or excl_rows is not None:
+            raise ValueError("elimrec_amd.ops.cosine_topk: a NeighbourQuery carries its own exclusions (pass excl_ptr=excl_rows=None)")
+        if query.n_rows > n or query.rows.device != table.device:
+            raise IndexError("elimrec_amd.ops.cosine_topk: the NeighbourQuery was checked for %d rows on %s, the table has %d on %s"
+                             % (query.n_rows, query.rows.device, n, table.device))
+    else:
+        query = NeighbourQuery(query_rows, n, table.device, excl_ptr, excl_rows)
+    Q = query.n_queries
+    ip = _knn_out(out_idx, "out_idx", torch.int32, Q, K)
+    vp = _knn_out(out_val, "out_val", torch.float32, Q, K) if out_val is not None else None
+    lib = _lib.load()
+    need = int(lib.elimrec_cosine_topk_workspace(Q, n, K))
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=table.device)
+    wp = _dev(workspace, "workspace", torch.uint8)
+    if workspace.numel() < need or not workspace.is_contiguous() or wp % 16:
+        raise ValueError("elimrec_amd.ops.cosine_topk: the workspace needs %d contiguous bytes, 16-byte aligned (got %d)"
+                         % (need, workspace.numel()))
+    if Q == 0:
+        return out_idx
+    _lib.check(lib.elimrec_cosine_topk(tp, ld, n, d, sp, ld_sq, _dev(query.rows, "query_rows", torch.int32), Q, 1 if exclude_self else 0,
+                                       _dev(query.excl_ptr, "excl_ptr", torch.int64), _dev(query.excl_rows, "excl_rows", torch.int32),
+                                       K, ip, vp, wp, workspace.numel(), _stream()), "cosine_topk")
+    return out_idx
+
+
+def list_overlap(a, b, out):
+    """elimrec_list_overlap: out int32 [n] <- per row the number of ids >= 0 of a[r, :] that also occur in b[r, :]; a, b int32
+    [n x K] contiguous, lists of distinct ids and -1 fillers, K <= 1024."""
+    ap, bp = _dev(a, "a", torch.int32), _dev(b, "b", torch.int32)
+    if a.dim() != 2 or a.shape != b.shape or not a.is_contiguous() or not b.is_contiguous() or a.shape[1] < 1:
+        raise ValueError("elimrec_amd.ops.list_overlap: a and b must be contiguous [n x K] tensors of one shape, K >= 1")
+    n, K = a.shape
+    op = _dev(out, "out", torch.int32)
+    if out.dim() != 1 or not out.is_contiguous() or out.numel() < n:
+        raise ValueError("elimrec_amd.ops.list_overlap: out must be a contiguous 1-D tensor of at least %d entries" % n)
+    _lib.check(_lib.load().elimrec_list_overlap(ap, bp, n, K, op, _stream()), "list_overlap")
+    return out
+
+
+def neighbour_columns(mods):
+    """Column names of the neighbour report: overlap_<m> per single-modal head (the share of the fused list that the head's list
+    repeats), then the mean cosine of the fused list and of each head's, then the mean training-interaction count of the listed
+    neighbours (mods: the heads' modality letters in head order)."""
+    mods = tuple(str(m) for m in mods)
+    return (tuple("overlap_" + m for m in mods) + ("cos_fused",) + tuple("cos_" + m for m in mods)
+            + ("pop_fused",) + tuple("pop_" + m for m in mods))

@@ -605,6 +605,42 @@ int elimrec_rank_pair_rows(const int32_t *d_rank, const int32_t *d_n_cand, int64
 int elimrec_rank_user_rows(const int32_t *d_rank, const int64_t *d_tgt_ptr, int64_t n_targets, const int32_t *d_n_cand,
                            int64_t B, float *d_out, void *stream);
 
+/* Cosine top-K of rows of a table against the rows of the same table (csrc/knn.hip): the items closest to an item, the users
+ * closest to a user, in the fused space or in one head's space. No counterpart in the reference, which only ranks items for users
+ * (models/EliMRec.py:96-113); the cosine is the one its losses train (F.normalize's floor, as the cos_<m> columns of
+ * elimrec_score_effects).
+ * Table slice: d_T points at row 0, column 0 of an [n_rows x d] slice of a row-major float32 matrix with row stride ld >= d (the
+ * caller offsets into Y: the item rows of block h start at Y + U*ldy + h*d); row ids are local to the slice. d_sqnorm[r * ld_sq] is
+ * the squared norm of row r of that block (a column of elimrec_row_sqnorms' table, offset the same way). d % 4 == 0, 4 <= d <= 256.
+ *     score(q, c) = (T[q] . T[c]) / (max(sqrt(sq[q]), 1e-12) * max(sqrt(sq[c]), 1e-12))
+ * the dot product on the fp32 matrix cores with fp32 accumulation, then two multiplications by the correctly rounded reciprocal
+ * norms. The value of a pair depends only on the two rows' values and d -- not on where either row falls in the tiling or the
+ * chunking: two bit-identical candidate rows get bit-identical scores against any query, which is what makes the tie order
+ * meaningful. d_query_rows int32[Q]: the query rows (duplicates allowed: identical lists). Per query d_idx / d_val (nullable)
+ * [Q x K] = the K best candidates by (score descending, row id ascending), -1 / -inf behind them when fewer than K candidates
+ * exist; 1 <= K <= 256. Left out: with exclude_self the query row itself, then the query's list of the nullable CSR d_excl_ptr
+ * int64[Q + 1] / d_excl_rows int32 (ids may repeat, in any order; a list may be empty). A query id outside [0, n_rows) is not
+ * dereferenced and gives a row of fillers, an exclusion id outside it is ignored; the CSR pointers themselves are the caller's to
+ * guarantee (the Python wrappers check all three on the host before any launch). NaN rows are outside the contract (a NaN score is
+ * never listed).
+ * No [Q x n_rows] block is written: a workgroup holds one tile of elimrec_cosine_topk_tile() query rows (16 when K > 64), streams
+ * one chunk of elimrec_cosine_topk_chunk() candidates through LDS in 16-row tiles and leaves each query's K best of that chunk;
+ * elimrec_topk_merge turns the per-chunk lists into the result by the same order. The grid is (query tiles x chunks). The
+ * workspace (16-byte aligned, elimrec_cosine_topk_workspace bytes = Q * ceil(n_rows / chunk) * K pairs, no initialisation needed;
+ * the function is host-only and works without a GPU) holds those lists. Deterministic: no float atomics, the bits do not depend on
+ * the grid or on arrival order. Two launches on `stream`, no host synchronisation; exactly Q * K entries of the outputs are
+ * written. */
+int elimrec_cosine_topk(const float *d_T, int64_t ld, int64_t n_rows, int d, const float *d_sqnorm, int64_t ld_sq,
+                        const int32_t *d_query_rows, int64_t Q, int exclude_self, const int64_t *d_excl_ptr,
+                        const int32_t *d_excl_rows, int K, int32_t *d_idx, float *d_val, void *d_workspace, size_t workspace_bytes,
+                        void *stream);
+size_t elimrec_cosine_topk_workspace(int64_t Q, int64_t n_rows, int K);
+int elimrec_cosine_topk_chunk(void);
+int elimrec_cosine_topk_tile(void);
+/* d_count[r] = the number of ids >= 0 of d_a[r, :] that also occur in d_b[r, :]; d_a / d_b int32 [n_rows x K] contiguous, lists of
+ * distinct ids and -1 fillers, 1 <= K <= 1024. One wave per row, the integers are exact. */
+int elimrec_list_overlap(const int32_t *d_a, const int32_t *d_b, int64_t n_rows, int K, int32_t *d_count, void *stream);
+
 /* ---------------------------------------------------------------- pairwise sampler (K20)
  * n triplets: user uniform over the `n_train_users` users with >= 1 training item (with
  * replacement), positive uniform over that user's training items, negative uniform over [0,I)

@@ -6,7 +6,7 @@
 Behaviour kept from the reference's `Net.run`: one pass of the pairwise sampler per epoch, validation every
 `test_step` epochs with predict_type TIE, a checkpoint + TE/TIE test pass whenever validation recall improves
 (not on epoch 0), early stop after `stop_cnt` epochs without improvement, the same log lines (`--group_view=[10,30,50,100]` adds
-the per-user-group table under each test line, `--effect_report=K` the effect breakdown of the top-K lists, `--rank_report=1` the test items' exact catalogue ranks; validation and model selection stay on the overall metrics). The per-batch work,
+the per-user-group table under each test line, `--effect_report=K` the effect breakdown of the top-K lists, `--rank_report=1` the test items' exact catalogue ranks, `--neighbour_report=K` the items' cosine neighbourhoods, fused against single-modal; validation and model selection stay on the overall metrics). The per-batch work,
 the sampler and the evaluator run on the GPU (elimrec_amd). `--data.input.dataset=synthetic` uses the seeded
 Tiktok-shape generator instead of reading files.
 
@@ -101,6 +101,11 @@ class Net(object):
         self.rank_report = int(cfg["rank_report"]) if "rank_report" in cfg else 0
         if self.rank_report and self.world > 1:
             raise ValueError("--rank_report needs the whole cached item table on one rank: it is single-GPU")
+        # --neighbour_report=K (default 0: off): once per [TEST], after both effects' lines, how much of every item's top-K cosine
+        # neighbourhood in the fused space each single-modal head's neighbourhood repeats (the lists do not depend on the predict type)
+        self.neighbour_report = int(cfg["neighbour_report"]) if "neighbour_report" in cfg else 0
+        if self.neighbour_report and self.world > 1:
+            raise ValueError("--neighbour_report needs the whole cached item table on one rank: it is single-GPU")
         Logger.info(count_parameters(self.recommender))
         self.opt = FusedAdam(self.recommender.parameters(), lr=cfg.lr, weight_decay=cfg.weight_decay)
         self.loss_name = str(cfg.loss)
@@ -243,6 +248,9 @@ class Net(object):
                 Logger.info("  [{}] catalogue rank of the test items:\n{}".format(effect, rec.rank_reporter.evaluate(rec, ranks[effect])[1]))
         if self.rank_report:               # positive delta: TIE ranks the test item higher than TE does
             Logger.info("  [TE->TIE] rank shift of the test items:\n{}".format(rec.rank_reporter.shift(ranks["TE"], ranks["TIE"])[1]))
+        if self.neighbour_report:
+            Logger.info("  [neighbours] top-{} cosine neighbours of every item, fused space against the heads:\n{}".format(
+                self.neighbour_report, rec.neighbour_reporter.evaluate(rec)[1]))
         return lines
 
     # ------------------------------------------------------------------ the run

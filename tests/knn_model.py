@@ -1,0 +1,90 @@
+"""Float64 numpy model of the cosine top-K lists (csrc/knn.hip), of list_overlap and of the neighbour report's rows and means."""
+import numpy as np
+
+
+def tol(d):
+    """Bound on |fp32 score - float64 score|: the worst case of an fp32 dot product of length d in any summation order is
+    d u |a||b| (u = 2^-24); the roundings of two norms, their floors and the products add a few u; doubled for an approximate
+    reciprocal square root with a Newton step. Derived, not measured."""
+    return 2.0 * (d + 8) * 2.0 ** -24
+
+
+def cos64(T, rows=None):
+    """Scores of `rows` (default all) against every row of T: dot / (max(|q|, 1e-12) max(|c|, 1e-12)), float64."""
+    T = np.asarray(T, dtype=np.float64)
+    nrm = np.maximum(np.sqrt((T * T).sum(1)), 1e-12)
+    q = np.arange(T.shape[0]) if rows is None else np.asarray(rows, dtype=np.int64)
+    return (T[q] @ T.T) / (nrm[q][:, None] * nrm[None, :])
+
+
+def cos64_loops(T):
+    T = np.asarray(T, dtype=np.float64)
+    n, d = T.shape
+    out = np.zeros((n, n))
+    for a in range(n):
+        for b in range(n):
+            dot = na = nb = 0.0
+            for k in range(d):
+                dot += T[a, k] * T[b, k]
+                na += T[a, k] * T[a, k]
+                nb += T[b, k] * T[b, k]
+            out[a, b] = dot / (max(np.sqrt(na), 1e-12) * max(np.sqrt(nb), 1e-12))
+    return out
+
+
+def masked(scores, rows, exclude_self=True, excl=None):
+    """Scores with the left-out entries at -inf: the query row itself, then the query's list of excl (one list per query)."""
+    s = np.array(scores, dtype=np.float64, copy=True)
+    for b, q in enumerate(rows):
+        if exclude_self:
+            s[b, int(q)] = -np.inf
+        if excl is not None:
+            for e in excl[b]:
+                s[b, int(e)] = -np.inf
+    return s
+
+
+def topk64(scores, K):
+    """Per row the K best by (score descending, id ascending); -inf entries are no candidates: ids -1 / values -inf behind."""
+    scores = np.asarray(scores, dtype=np.float64)
+    B, n = scores.shape
+    ids = np.full((B, K), -1, dtype=np.int64)
+    vals = np.full((B, K), -np.inf)
+    for b in range(B):
+        order = np.lexsort((np.arange(n), -scores[b]))
+        order = order[scores[b, order] > -np.inf][:K]
+        ids[b, :order.size] = order
+        vals[b, :order.size] = scores[b, order]
+    return ids, vals
+
+
+def overlap(a, b):
+    """Per row the number of ids >= 0 of a[r] that occur in b[r]."""
+    return np.asarray([len(set(int(x) for x in ra if x >= 0) & set(int(x) for x in rb if x >= 0)) for ra, rb in zip(a, b)],
+                      dtype=np.int32)
+
+
+def csr(lists):
+    ptr = np.zeros(len(lists) + 1, dtype=np.int64)
+    np.cumsum([len(x) for x in lists], out=ptr[1:])
+    return ptr, np.asarray([int(i) for x in lists for i in x], dtype=np.int32)
+
+
+def report_rows(ids, vals, counts, k):
+    """The neighbour report's rows from the lists: ids / vals [1 + S x I x k] (fused first), counts [I] training interactions.
+    Columns: overlap per head, mean score per space, mean count per space; float64 quotients rounded to float32 (what a row
+    holds), NaN where a list is empty."""
+    ids, vals = np.asarray(ids), np.asarray(vals, dtype=np.float64)
+    S, I = ids.shape[0] - 1, ids.shape[1]
+    listed = ids >= 0
+    n = listed.sum(2).astype(np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        over = np.stack([np.where(n[0] > 0, overlap(ids[0], ids[1 + h]) / float(k), np.nan) for h in range(S)], 1) if S else np.zeros((I, 0))
+        cos = (np.where(listed, vals, 0.0).sum(2) / n).T
+        pop = (np.where(listed, np.asarray(counts, dtype=np.float64)[np.maximum(ids, 0)], 0.0).sum(2) / n).T
+    return np.concatenate([over, cos, pop], 1).astype(np.float32)
+
+
+def report_means(rows, positions):
+    """Float64 means of the float32 rows per group of row positions."""
+    return np.stack([rows[p].astype(np.float64).mean(0) for p in positions])
