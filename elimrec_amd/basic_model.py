@@ -6,7 +6,8 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from .evaluator import EffectReport, NeighbourReport, ProxyEvaluator, RankReport
+from . import ops
+from .evaluator import EffectReport, ListReport, NeighbourReport, ProxyEvaluator, RankReport
 
 
 class BasicModel(nn.Module):
@@ -57,6 +58,15 @@ class BasicModel(nn.Module):
         if k_near < 0:
             raise ValueError("neighbour_report must be 0 (off) or the K of the neighbour lists")
         self.neighbour_reporter = NeighbourReport(dataset, train, k_near, item_group_view=item_view) if k_near else None
+        # --list_report=K (CLI-only, default 0 = off): the test users' top-K lists themselves -- intra-list similarity in the fused
+        # space and in each head's space, popularity of the listed items, catalogue coverage / Gini / entropy of the exposure --
+        # overall, per user group (--group_view) and per item popularity group (--item_group_view) (evaluator.ListReport)
+        k_list = int(config["list_report"]) if "list_report" in config else 0
+        if k_list and not 2 <= k_list <= min(ops.LIST_MAX_K, int(dataset.num_items)):
+            raise ValueError("list_report must be 0 (off) or the K of the lists, 2 <= K <= min(%d, the catalogue's %d items), got %d"
+                             % (ops.LIST_MAX_K, int(dataset.num_items), k_list))
+        self.list_reporter = ListReport(dataset, train, dataset.get_user_test_dict(), k_list, group_view=config["group_view"],
+                                        item_group_view=item_view) if k_list else None
         self.infonce_criterion = nn.CrossEntropyLoss()          # BasicModel.py:32
 
     def getFileName(self):

@@ -18,6 +18,9 @@
 //       column means, float64 sums in listed order (the indices are checked on the host first: a synchronisation)
 //   rank_targets(scores f32[B x I], tgt_ptr i64[B+1], tgt_items i32) -> i32[n_targets]: the 0-based position of every listed item in
 //       its row's full ranking by (score desc, id asc), -1 at -inf (the lists are checked on the host first: a synchronisation)
+//   list_pair_cosine(table f32[n x blocks*d], sqnorm f32[n x blocks], lists i32[B x K], blocks) -> f32[B x blocks]: per list and
+//       column block the mean pairwise cosine of the listed rows (entries outside [0, n) are not listed; NaN below two)
+//   list_exposure(lists i32[B x K], n_rows) -> i32[n_rows]: how often every row is listed
 //   sample_triplets(user_ids, ptr, items, num_items, n, seed, epoch) -> (users, pos, neg)
 //   score_candidates(Y, U, I, users, d, S, head_mask, fusion_mode, predict_type, cand_ptr, cand_items, width) -> f32[B x width]
 //       (each row: its candidates' scores in list order, then -inf)
@@ -401,6 +404,40 @@ at::Tensor list_overlap(const at::Tensor &a, const at::Tensor &b) {
     return out;
 }
 
+// ---- the lists themselves: mean pairwise cosine per list and column block; exposure counts of the catalogue
+at::Tensor list_pair_cosine(const at::Tensor &table, const at::Tensor &sqnorm, const at::Tensor &lists, int64_t blocks) {
+    const at::Tensor t = rowmajor(table, "table");
+    need(sqnorm, "sqnorm", at::kFloat); need(lists, "lists", at::kInt, 2);
+    const at::Tensor l = lists.contiguous();
+    const int64_t n = t.size(0), B = l.size(0), K = l.size(1);
+    TORCH_CHECK(blocks >= 1 && blocks <= 8 && t.size(1) % blocks == 0, "elimrec::list_pair_cosine: 1 <= blocks <= 8 equal column blocks, got ",
+                blocks, " for ", t.size(1), " columns");
+    const int64_t d = t.size(1) / blocks;
+    TORCH_CHECK(K >= 1 && K <= 256, "elimrec::list_pair_cosine: 1 <= K <= 256, got ", K);
+    TORCH_CHECK(d % 4 == 0 && d >= 4 && d <= 256, "elimrec::list_pair_cosine: a block needs d % 4 == 0 and 4 <= d <= 256 columns, got ", d);
+    TORCH_CHECK(sqnorm.numel() == n * blocks && (sqnorm.dim() == 2 ? sqnorm.size(0) == n : (sqnorm.dim() == 1 && blocks == 1)),
+                "elimrec::list_pair_cosine: sqnorm must be [", n, " x ", blocks, "]");
+    const at::Tensor sq = (sqnorm.dim() == 1 || sqnorm.stride(1) == 1 || blocks == 1) ? sqnorm : sqnorm.contiguous();
+    at::Tensor out = at::empty({B, blocks}, t.options());
+    if (B == 0) return out;
+    const int64_t ld_sq = std::max<int64_t>(blocks, n > 1 ? sq.stride(0) : blocks);
+    check(elimrec_list_pair_cosine(t.data_ptr<float>(), t.stride(0), n, (int)blocks, (int)d, sq.data_ptr<float>(), ld_sq,
+                                   l.data_ptr<int32_t>(), B, (int)K, out.data_ptr<float>(), cur_stream()),
+          "list_pair_cosine");
+    return out;
+}
+
+at::Tensor list_exposure(const at::Tensor &lists, int64_t n_rows) {
+    need(lists, "lists", at::kInt, 2);
+    const at::Tensor l = lists.contiguous();
+    TORCH_CHECK(n_rows >= 0 && l.size(1) >= 1, "elimrec::list_exposure: n_rows >= 0 and [B x K] lists with K >= 1");
+    at::Tensor counts = at::zeros({n_rows}, l.options());
+    if (l.size(0) == 0 || n_rows == 0) return counts;
+    check(elimrec_list_exposure(l.data_ptr<int32_t>(), l.size(0), (int)l.size(1), n_rows, counts.data_ptr<int32_t>(), cur_stream()),
+          "list_exposure");
+    return counts;
+}
+
 at::Tensor sample_negatives(const at::Tensor &excl_ptr, const at::Tensor &excl_items, int64_t num_items, int64_t n_neg, int64_t seed) {
     need(excl_ptr, "excl_ptr", at::kLong, 1); need(excl_items, "excl_items", at::kInt, 1);
     const at::Tensor p = excl_ptr.contiguous(), it = excl_items.contiguous();
@@ -522,6 +559,8 @@ TORCH_LIBRARY(elimrec, m) {
     m.def("rank_targets(Tensor scores, Tensor tgt_ptr, Tensor tgt_items) -> Tensor");
     m.def("cosine_topk(Tensor table, Tensor sqnorm, Tensor query_rows, int K, bool exclude_self) -> (Tensor, Tensor)");
     m.def("list_overlap(Tensor a, Tensor b) -> Tensor");
+    m.def("list_pair_cosine(Tensor table, Tensor sqnorm, Tensor lists, int blocks) -> Tensor");
+    m.def("list_exposure(Tensor lists, int n_rows) -> Tensor");
     m.def("sample_negatives(Tensor excl_ptr, Tensor excl_items, int num_items, int n_neg, int seed) -> Tensor");
     m.def("lookup_counts(Tensor acts, int U, int I, int[] user_bounds, int[] item_bounds) -> Tensor");
     m.def("lookup_pack(Tensor acts, int U, int I, int[] user_bounds, int[] item_bounds, int me, Tensor shard, int row_bytes) -> (Tensor, Tensor)");
@@ -548,6 +587,8 @@ TORCH_LIBRARY_IMPL(elimrec, CUDA, m) {
     m.impl("rank_targets", &rank_targets);
     m.impl("cosine_topk", &cosine_topk);
     m.impl("list_overlap", &list_overlap);
+    m.impl("list_pair_cosine", &list_pair_cosine);
+    m.impl("list_exposure", &list_exposure);
     m.impl("sample_negatives", &sample_negatives);
     m.impl("lookup_counts", &lookup_counts);
     m.impl("lookup_pack", &lookup_pack);

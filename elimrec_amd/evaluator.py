@@ -863,6 +863,170 @@ class NeighbourReport(object):
         return final, buf
 
 
+EXPOSURE_COLUMNS = ("items", "coverage", "gini", "entropy", "slot_share")
+
+
+def exposure_summary(counts, positions):
+    """How the list slots spread over the catalogue: float64 [len(positions) x 5], per group of item positions (index arrays into
+    counts) the columns EXPOSURE_COLUMNS:
+      items = the group's size; coverage = the share of its items with count > 0;
+      gini = the Gini coefficient of its counts, sum_i (2 i - n - 1) c_(i) / (n sum c) over the ascending counts c_(1..n)
+             (0 = every item listed equally often, (n - 1) / n = one item takes every slot; 0 for an empty or all-zero group);
+      entropy = -sum p log2 p in bits over p = c / sum c of the group (0 for an empty or all-zero group);
+      slot_share = the group's counts over ALL counts (0 when nothing is listed at all).
+    counts: how often each item is listed (ops.list_exposure). Pure numpy, float64."""
+    c_all = np.asarray(counts, dtype=np.float64).reshape(-1)
+    total = c_all.sum()
+    out = np.zeros((len(positions), len(EXPOSURE_COLUMNS)), dtype=np.float64)
+    for g, at in enumerate(positions):
+        c = np.sort(c_all[np.asarray(at, dtype=np.int64).reshape(-1)])
+        n, s = c.size, c.sum()
+        out[g, 0] = n
+        if n:
+            out[g, 1] = np.count_nonzero(c > 0) / float(n)
+        if n and s > 0:
+            out[g, 2] = ((2.0 * np.arange(1, n + 1) - n - 1.0) * c).sum() / (n * s)
+            p = c[c > 0] / s
+            out[g, 3] = 0.0 - (p * np.log2(p)).sum()
+        if total > 0:
+            out[g, 4] = s / total
+    return out
+
+
+ListTables = collections.namedtuple("ListTables", ("user_columns", "user_labels", "users", "item_columns", "item_labels", "items"))
+
+
+class ListReport(object):
+    """The recommendation lists themselves (--list_report=K): every test user's top-K list under the model's current predict
+    type with the train items masked (predict_device, users in blocks of block_users as EffectReport takes them), and
+      per user the columns of ops.list_columns(mods): ils_fused, ils_<m> = the mean pairwise cosine of the K listed items in the
+        fused space and in each head's space (EliMRec.list_similarity_device, csrc/lists.hip: one launch per block for all
+        spaces), pop = the mean training-interaction count of the listed items (float64 quotient; NaN for an empty list);
+      per item how often it is listed (ops.list_exposure, int32 counters filled block after block).
+    The user table is ops.group_metric_means over the rows: all users, then the group_view groups (assign_user_groups). The
+    item table is exposure_summary of the counters over all items, then the item_group_view groups (assign_item_groups over the
+    items' training interactions); the counters come to the host once per evaluate(): num_items int32 values."""
+
+    def __init__(self, dataset, user_train_dict, user_test_dict, top_k, group_view=None, item_group_view=None):
+        if not isinstance(user_train_dict, dict) or not isinstance(user_test_dict, dict):
+            raise TypeError("user_train_dict and user_test_dict must be dicts")
+        if isinstance(top_k, bool) or not isinstance(top_k, (int, np.integer)) or top_k < 2 or top_k > ops.LIST_MAX_K:
+            raise ValueError("top_k must be an integer in [2, %d], got %r" % (ops.LIST_MAX_K, top_k))
+        self.dataset = dataset
+        self.num_items = I = int(dataset.num_items)
+        self.user_pos_train = user_train_dict
+        self.user_pos_test = user_test_dict
+        self.top_k = int(top_k)
+        self.users = list(user_test_dict.keys())
+        self.block_users = 8192
+        self.tie_order = "id"
+        self.item_counts = np.zeros(I, dtype=np.int64)
+        for items in user_train_dict.values():
+            np.add.at(self.item_counts, np.asarray(list(items), dtype=np.int64), 1)
+        self.group_labels, self._positions = ["all:".ljust(12)], [np.arange(len(self.users), dtype=np.int64)]
+        if group_view is not None:
+            labels, positions, self.num_discarded = assign_user_groups(self.users, user_train_dict, group_view)
+            self.group_labels += labels
+            self._positions += positions
+        self.item_labels, self._item_positions = ["all:".ljust(12)], [np.arange(I, dtype=np.int64)]
+        if item_group_view is not None:
+            labels, positions = assign_item_groups(np.arange(I, dtype=np.int64), self.item_counts, item_group_view)
+            self.item_labels += [("item " + x.strip()).ljust(12) for x in labels]
+            self._item_positions += positions
+        self.columns = self.shift_columns = None   # ops.list_columns of the model list_rows() last saw; ("overlap", "d_<column>"...)
+        self._device = {}                  # device -> the user group index and the items' training counts resident there
+
+    def _resident(self, device):
+        hit = self._device.get(str(device))
+        if hit is None:
+            ptr = np.zeros(len(self._positions) + 1, dtype=np.int64)
+            np.cumsum([p.size for p in self._positions], out=ptr[1:])
+            hit = dict(groups=ops.GroupIndex(ptr, np.concatenate(self._positions).astype(np.int32), len(self.users), device),
+                       counts=torch.from_numpy(self.item_counts.astype(np.float64)).to(device))
+            self._device[str(device)] = hit
+        return hit
+
+    def list_rows(self, model):
+        """Every test user's row, list and the catalogue's exposure on the device: ([users x C] float32, column names,
+        lists int32 [users x K], counts int32 [num_items])."""
+        if not hasattr(model, "list_similarity_device"):
+            raise TypeError("model must expose list_similarity_device()")
+        if hasattr(model, "_ensure_tables") and getattr(model, "_cache", None) is not None:
+            model._ensure_tables()
+        if getattr(model, "_eval_shard", None) is not None:
+            raise CandidateScoringError("the list report needs the whole cached item table on this rank; the tables are "
+                                        "item-sharded (lean / multi-rank evaluation): run without --list_report")
+        if model.num_items != self.num_items:
+            raise ValueError("the report was built for %d items, the model has %d" % (self.num_items, model.num_items))
+        if self.top_k > model.num_items:
+            raise CandidateScoringError("list report of the top-%d lists: the catalogue has %d items" % (self.top_k, model.num_items))
+        device = model._require_gpu()
+        res = self._resident(device)
+        columns = self.columns = ops.list_columns(model._mods)
+        K, nb, n_users = self.top_k, len(columns) - 1, len(self.users)
+        rows = torch.empty(n_users, len(columns), dtype=torch.float32, device=device)
+        ils = torch.empty(n_users, nb, dtype=torch.float32, device=device)
+        lists = torch.empty(n_users, K, dtype=torch.int32, device=device)
+        counts = torch.zeros(self.num_items, dtype=torch.int32, device=device)
+        at = 0
+        for batch_users in DataIterator(self.users, batch_size=self.block_users, shuffle=False, drop_last=False):
+            B = len(batch_users)
+            train = [self.user_pos_train.get(u, []) for u in batch_users]
+            ptr = np.zeros(B + 1, dtype=np.int64)
+            np.cumsum([len(x) for x in train], out=ptr[1:])
+            flat = np.fromiter((i for x in train for i in x), dtype=np.int32, count=int(ptr[-1]))
+            users_t = torch.as_tensor(np.asarray(batch_users, dtype=np.int64)).to(device)
+            idx, _ = model.predict_device(users_t, top_k=K, train_ptr=torch.from_numpy(ptr).to(device),
+                                          train_items=torch.from_numpy(flat).to(device), tie_order=self.tie_order)
+            lists[at:at + B] = idx
+            model.list_similarity_device(lists[at:at + B], ils[at:at + B], side="item")
+            ops.list_exposure(lists[at:at + B], counts)
+            at += B
+        listed = lists >= 0
+        pop = torch.where(listed, res["counts"][lists.clamp(min=0).long()], 0.0).sum(dim=1) / listed.sum(dim=1).double()
+        rows[:, :nb] = ils
+        rows[:, nb] = pop.float()
+        return rows, columns, lists, counts
+
+    def _user_table(self, rows):
+        out = torch.empty(len(self.group_labels), rows.shape[1], dtype=torch.float32, device=rows.device)
+        return ops.group_metric_means(rows, self._resident(rows.device)["groups"], None, out).cpu().numpy()
+
+    @staticmethod
+    def _format(columns, labels, table):
+        return "columns:\t%s" % "\t".join(str(c).ljust(12) for c in columns) + "".join(
+            "\n%s\t%s" % (label, "\t".join(("%.8f" % x).ljust(12) for x in row)) for label, row in zip(labels, table))
+
+    def evaluate(self, model, rows=None):
+        """(final, buf). final = ListTables: users [1 + user groups x C] float32 -- row 0 = all test users -- the means of
+        ops.list_columns; items [1 + item groups x 5] float64 -- row 0 = the whole catalogue -- exposure_summary of the counters,
+        columns EXPOSURE_COLUMNS. buf: per table a header of column names and one "%.8f" line per row, in the grouped evaluator's
+        format. rows: list_rows(model) if the caller already holds it."""
+        rows, columns, _, counts = self.list_rows(model) if rows is None else rows
+        items = exposure_summary(counts.cpu().numpy(), self._item_positions)
+        final = ListTables(tuple(columns), list(self.group_labels), self._user_table(rows), EXPOSURE_COLUMNS, list(self.item_labels), items)
+        buf = self._format(final.user_columns, final.user_labels, final.users) + "\n" + self._format(
+            final.item_columns, final.item_labels, final.items)
+        return final, buf
+
+    def shift(self, rows_a, lists_a, rows_b, lists_b):
+        """How the lists change from a to b (e.g. TE -> TIE): (final [1 + user groups x 1 + C] float32, buf) in evaluate()'s user
+        grouping over the columns self.shift_columns: overlap = |list a & list b| / K (ops.list_overlap) and d_<column> = b - a for
+        every user column."""
+        n, K = len(self.users), self.top_k
+        if (tuple(lists_a.shape) != (n, K) or lists_a.shape != lists_b.shape or rows_a.shape != rows_b.shape or rows_a.shape[0] != n
+                or len({t.device for t in (rows_a, rows_b, lists_a, lists_b)}) != 1):
+            raise ValueError("shift() takes the rows and lists of two list_rows() results of this report on one device")
+        cnt = torch.empty(n, dtype=torch.int32, device=lists_a.device)
+        ops.list_overlap(lists_a, lists_b, cnt)
+        rows = torch.cat(((cnt.double() / K).float()[:, None], rows_b - rows_a), dim=1)
+        if self.columns is None or len(self.columns) != rows_a.shape[1]:
+            raise ValueError("shift() takes rows of this report's list_rows()")
+        self.shift_columns = ("overlap",) + tuple("d_" + c for c in self.columns)
+        final = self._user_table(rows)
+        return final, self._format(self.shift_columns, self.group_labels, final)
+
+
 class ProxyEvaluator(object):
     def __init__(self, dataset, user_train_dict, user_test_dict, user_neg_test=None, metric=None, group_view=None,
                  top_k=50, batch_size=1024, num_thread=8):

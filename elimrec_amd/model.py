@@ -1443,6 +1443,51 @@ class EliMRec(BasicModel):
         """similar_items over the user rows: the k users closest to each given user."""
         return self._similar("user", user_ids, k, space, exclude)
 
+    @torch.no_grad()
+    def list_similarity_device(self, lists, out, side="item"):
+        """Intra-list similarity: per list of item ids (side "item") or user ids ("user") the mean pairwise cosine of the listed
+        rows in the fused space and in every head's space, from ONE launch over the side's rows of the cached Y (csrc/lists.hip).
+        lists int32 [B x K] on the device, 1 <= K <= ops.LIST_MAX_K; an entry outside the side's rows (-1 fillers) is not listed,
+        duplicates are pairs. out float32 [B x (1 + S)] on the device: column 0 = the fused rows predict() scores with, column
+        1 + h = head self._mods[h]; NaN where fewer than two entries are listed. Tables as neighbours_device."""
+        dev = self._require_gpu()
+        if side not in ("item", "user"):
+            raise ValueError("side must be 'item' or 'user', got %r" % (side,))
+        self._plugin.realise_forward()
+        if self._ws is None or self._cache is None:
+            raise RuntimeError("list_similarity() needs the tables cached by a training forward (call bpr_loss or compute first)")
+        self._ensure_tables()
+        if self.__dict__.get("_eval_shard") is not None:
+            raise CandidateScoringError("list similarity needs the whole cached tables on this rank; the tables are item-sharded "
+                                        "(lean / multi-rank evaluation)")
+        U, d, nb = self.num_users, self.latent_dim, 1 + self.S
+        lo, n = (U, self.num_items) if side == "item" else (0, U)
+        sqn = self._block_sqnorms(dev)
+        ops.list_pair_cosine(self._ws["Y"][lo:lo + n, :nb * d], sqn[lo:lo + n], lists, out, blocks=nb)
+        return out
+
+    def list_similarity(self, item_lists, space=None):
+        """How alike the items of each list are: CPU fp32 [B x (1 + S)] -- column 0 the fused space, column 1 + h head
+        self._mods[h] -- or [B] for one named space ("fused" or a head letter, as similar_items). item_lists: one sequence of item
+        ids per list, of any lengths up to ops.LIST_MAX_K (shorter ones are padded, the padding is not listed); an id outside the
+        catalogue raises IndexError. The value is the mean cosine over the list's position pairs; NaN below two items."""
+        h = None if space is None else self._neighbour_space(space)
+        lists = [[int(i) for i in x] for x in item_lists]
+        K = max([len(x) for x in lists] + [1])
+        if K > ops.LIST_MAX_K:
+            raise ValueError("a list may hold at most %d items, got %d" % (ops.LIST_MAX_K, K))
+        padded = np.full((len(lists), K), -1, dtype=np.int32)
+        for b, x in enumerate(lists):
+            padded[b, :len(x)] = x
+        listed = np.arange(K)[None, :] < np.asarray([len(x) for x in lists], dtype=np.int64).reshape(-1, 1)
+        if listed.any() and (padded[listed].min() < 0 or padded[listed].max() >= self.num_items):
+            raise IndexError("item ids must lie in [0, %d)" % self.num_items)
+        dev = self._require_gpu()
+        out = torch.empty(len(lists), 1 + self.S, dtype=torch.float32, device=dev)
+        self.list_similarity_device(torch.from_numpy(padded).to(dev), out, side="item")
+        out = out.cpu()
+        return out if h is None else out[:, h].contiguous()
+
     def predict(self, user_ids, candidate_items=None):
         """:96-113. CPU fp32 tensor [len(user_ids) x I]; `candidate_items` is ignored as in the reference."""
         dev = self._require_gpu()

@@ -899,6 +899,8 @@ def __getattr__(name):
         return int(_lib.load().elimrec_cosine_topk_chunk())
     if name == "KNN_TILE":               # query rows one workgroup of cosine_topk holds (16 when K > 64)
         return int(_lib.load().elimrec_cosine_topk_tile())
+    if name == "LIST_SMALL_K":           # lists up to this K take one wave of list_pair_cosine, longer ones four
+        return int(_lib.load().elimrec_list_pair_cosine_small_k())
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 
@@ -1221,3 +1223,88 @@ def neighbour_columns(mods):
     mods = tuple(str(m) for m in mods)
     return (tuple("overlap_" + m for m in mods) + ("cos_fused",) + tuple("cos_" + m for m in mods)
             + ("pop_fused",) + tuple("pop_" + m for m in mods))
+
+
+LIST_MAX_K, LIST_MAX_BLOCKS = 256, 8
+
+
+def list_chunk_cols(K, d):
+    """Columns of one LDS stage of list_pair_cosine for lists of K ids over blocks of d columns (host arithmetic only)."""
+    return int(_lib.load().elimrec_list_pair_cosine_chunk_cols(int(K), int(d)))
+
+
+def _int_lists(lists, name, what):
+    p = _dev(lists, name, torch.int32)
+    if lists.dim() != 2 or not lists.is_contiguous() or lists.shape[1] < 1:
+        raise ValueError("elimrec_amd.ops.%s: %s must be a contiguous [B x K] tensor, K >= 1" % (what, name))
+    return p
+
+
+def list_pair_cosine(table, sqnorm, lists, out, blocks=1):
+    """elimrec_list_pair_cosine: out[b, h] float32 <- the mean, over the position pairs i < j of lists[b] whose entries are both
+    listed, of the cosine of the two rows in column block h of `table` (intra-list similarity); NaN with fewer than two listed
+    entries. table [n x blocks * d] float32 with unit column stride (a column block of a wider matrix is fine), block h = columns
+    [h * d, (h + 1) * d), d % 4 == 0, 4 <= d <= 256, 1 <= blocks <= 8; sqnorm [n x blocks] float32 with unit column stride (row_sqnorms'
+    table or a column slice of it; 1-D with any stride when blocks == 1): the rows' squared norms per block. lists int32 [B x K]
+    contiguous on the table's device, 1 <= K <= LIST_MAX_K: an entry < 0 or >= n is not listed (the kernel checks every entry, no
+    host check is needed), duplicates are pairs. out: float32, contiguous, [>= B x blocks] or 1-D with at least B * blocks entries;
+    entries beyond [B x blocks] are left alone. A list's bits depend on its entries alone (csrc/lists.hip)."""
+    if not isinstance(table, torch.Tensor) or not table.is_cuda:
+        _dev(table, "table")
+    tp, ld = _rowmajor(table, "table")
+    n, width = table.shape
+    blocks = int(blocks)
+    if not 1 <= blocks <= LIST_MAX_BLOCKS:
+        raise ValueError("elimrec_amd.ops.list_pair_cosine: 1 <= blocks <= %d, got %d" % (LIST_MAX_BLOCKS, blocks))
+    if width % blocks != 0:
+        raise ValueError("elimrec_amd.ops.list_pair_cosine: the table's %d columns do not split into %d equal blocks" % (width, blocks))
+    d = width // blocks
+    if d % 4 != 0 or not 4 <= d <= KNN_MAX_D:
+        raise ValueError("elimrec_amd.ops.list_pair_cosine: a block needs d %% 4 == 0 and 4 <= d <= %d columns, got %d" % (KNN_MAX_D, d))
+    sp = _dev(sqnorm, "sqnorm")
+    if sqnorm.device != table.device:
+        raise ValueError("elimrec_amd.ops.list_pair_cosine: sqnorm must live on the table's device")
+    if sqnorm.dim() == 1 and blocks == 1 and sqnorm.numel() == n:
+        ld_sq = max(1, int(sqnorm.stride(0)))
+    elif sqnorm.dim() == 2 and tuple(sqnorm.shape) == (n, blocks) and (sqnorm.stride(1) == 1 or blocks == 1):
+        ld_sq = max(blocks, int(sqnorm.stride(0)))
+    else:
+        raise ValueError("elimrec_amd.ops.list_pair_cosine: sqnorm must be [%d x %d] with unit column stride (or 1-D with %d entries "
+                         "when blocks == 1)" % (n, blocks, n))
+    lp = _int_lists(lists, "lists", "list_pair_cosine")
+    if lists.device != table.device:
+        raise ValueError("elimrec_amd.ops.list_pair_cosine: lists must live on the table's device")
+    B, K = lists.shape
+    if not 1 <= K <= LIST_MAX_K:
+        raise ValueError("elimrec_amd.ops.list_pair_cosine: 1 <= K <= %d, got %d" % (LIST_MAX_K, K))
+    op = _dev(out, "out")
+    ok = out.is_contiguous() and out.device == table.device and (
+        (out.dim() == 2 and out.shape[1] == blocks and out.shape[0] >= B) or (out.dim() == 1 and out.numel() >= B * blocks))
+    if not ok:
+        raise ValueError("elimrec_amd.ops.list_pair_cosine: out must be contiguous on the table's device, [>= %d x %d] or 1-D with at "
+                         "least %d entries" % (B, blocks, B * blocks))
+    if B == 0:
+        return out
+    _lib.check(_lib.load().elimrec_list_pair_cosine(tp, ld, n, blocks, d, sp, ld_sq, lp, B, K, op, _stream()), "list_pair_cosine")
+    return out
+
+
+def list_exposure(lists, counts):
+    """elimrec_list_exposure: counts[i] += the number of entries of lists (int32 [B x K] contiguous) equal to i, for i in
+    [0, len(counts)); entries outside are skipped. counts: int32, 1-D, contiguous, on the lists' device; it ACCUMULATES over calls
+    (zero it first). Integer atomics: exact, whatever the order."""
+    lp = _int_lists(lists, "lists", "list_exposure")
+    cp = _dev(counts, "counts", torch.int32)
+    if counts.dim() != 1 or not counts.is_contiguous() or counts.device != lists.device:
+        raise ValueError("elimrec_amd.ops.list_exposure: counts must be a contiguous 1-D tensor on the lists' device")
+    B, K = lists.shape
+    if B and counts.numel():
+        _lib.check(_lib.load().elimrec_list_exposure(lp, B, K, counts.numel(), cp, _stream()), "list_exposure")
+    return counts
+
+
+def list_columns(mods):
+    """Column names of the list report's user rows: ils_fused and ils_<m> per single-modal head (the mean pairwise cosine of the
+    user's list in that space), then pop (the mean training-interaction count of the listed items); mods: the heads' modality
+    letters in head order."""
+    return ("ils_fused",) + tuple("ils_" + str(m) for m in mods) + ("pop",)

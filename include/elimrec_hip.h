@@ -641,6 +641,32 @@ int elimrec_cosine_topk_tile(void);
  * distinct ids and -1 fillers, 1 <= K <= 1024. One wave per row, the integers are exact. */
 int elimrec_list_overlap(const int32_t *d_a, const int32_t *d_b, int64_t n_rows, int K, int32_t *d_count, void *stream);
 
+/* The lists themselves (csrc/lists.hip): intra-list similarity and catalogue exposure. No counterpart in the reference.
+ * elimrec_list_pair_cosine: d_T points at row 0, column 0 of an [n_rows x blocks * d] slice of a row-major float32 matrix with row
+ * stride ld >= blocks * d: `blocks` equal column blocks of d floats, block h = columns [h * d, (h + 1) * d) (the item rows of the
+ * cached Y: the fused block and the heads' blocks side by side). d_sqnorm[r * ld_sq + h] = the squared norm of row r of block h
+ * (elimrec_row_sqnorms' table). d_lists int32 [B x K] contiguous. d_out float32 [B x blocks] contiguous:
+ *     out[b, h] = mean over the position pairs i < j of list b whose entries a, c are both listed of
+ *                 ((T_h[a] . T_h[c]) * inv(sq[a, h])) * inv(sq[c, h]),      inv(x) = 1 / max(sqrt(x), 1e-12)
+ * -- the pair score of elimrec_cosine_topk. An entry < 0 or >= n_rows is "not listed" wherever it stands in the list, and nothing
+ * outside the table is read for any list content. Duplicates are kept as given: a pair of equal ids is a pair. Fewer than two
+ * listed entries give NaN. d % 4 == 0, 4 <= d <= 256, 1 <= blocks <= 8, 1 <= K <= elimrec_list_max_k() = 256, B >= 0 (B == 0
+ * launches nothing); the rows of the slice need not be 16-byte aligned.
+ * One workgroup per list (one wave for K <= elimrec_list_pair_cosine_small_k(), four above); per block the list's rows are
+ * gathered once into LDS in chunks of elimrec_list_pair_cosine_chunk_cols(K, d) columns (host arithmetic; 0 for bad arguments) and
+ * the K x K upper triangle is formed as 16 x 16 tiles on the fp32 matrix cores; nothing of size K x K is written. The pair scores
+ * are summed in float64 in an order fixed by (K, d), divided in float64 and rounded once: a list's bits depend on its entries
+ * alone -- not on B, its position, the grid or the other lists. One launch on `stream`; exactly B * blocks floats are written. */
+int elimrec_list_pair_cosine(const float *d_T, int64_t ld, int64_t n_rows, int blocks, int d, const float *d_sqnorm, int64_t ld_sq,
+                             const int32_t *d_lists, int64_t B, int K, float *d_out, void *stream);
+int elimrec_list_max_k(void);
+int elimrec_list_pair_cosine_small_k(void);
+int elimrec_list_pair_cosine_chunk_cols(int K, int d);
+/* d_counts[i] += the number of entries of d_lists (int32 [B x K] contiguous) equal to i, for every i in [0, n_rows); entries
+ * outside [0, n_rows) are skipped. Accumulates over calls: the caller zeroes the counters. Integer atomics: exact and
+ * order-free. K >= 1. */
+int elimrec_list_exposure(const int32_t *d_lists, int64_t B, int K, int64_t n_rows, int32_t *d_counts, void *stream);
+
 /* ---------------------------------------------------------------- pairwise sampler (K20)
  * n triplets: user uniform over the `n_train_users` users with >= 1 training item (with
  * replacement), positive uniform over that user's training items, negative uniform over [0,I)

@@ -6,7 +6,7 @@
 Behaviour kept from the reference's `Net.run`: one pass of the pairwise sampler per epoch, validation every
 `test_step` epochs with predict_type TIE, a checkpoint + TE/TIE test pass whenever validation recall improves
 (not on epoch 0), early stop after `stop_cnt` epochs without improvement, the same log lines (`--group_view=[10,30,50,100]` adds
-the per-user-group table under each test line, `--effect_report=K` the effect breakdown of the top-K lists, `--rank_report=1` the test items' exact catalogue ranks, `--neighbour_report=K` the items' cosine neighbourhoods, fused against single-modal; validation and model selection stay on the overall metrics). The per-batch work,
+the per-user-group table under each test line, `--effect_report=K` the effect breakdown of the top-K lists, `--rank_report=1` the test items' exact catalogue ranks, `--neighbour_report=K` the items' cosine neighbourhoods, fused against single-modal, `--list_report=K` the top-K lists' intra-list similarity and catalogue exposure; validation and model selection stay on the overall metrics). The per-batch work,
 the sampler and the evaluator run on the GPU (elimrec_amd). `--data.input.dataset=synthetic` uses the seeded
 Tiktok-shape generator instead of reading files.
 
@@ -106,6 +106,11 @@ class Net(object):
         self.neighbour_report = int(cfg["neighbour_report"]) if "neighbour_report" in cfg else 0
         if self.neighbour_report and self.world > 1:
             raise ValueError("--neighbour_report needs the whole cached item table on one rank: it is single-GPU")
+        # --list_report=K (default 0: off): under each [TEST] line the top-K lists' intra-list similarity, popularity and catalogue
+        # exposure, after both effects how the lists change from TE to TIE
+        self.list_report = int(cfg["list_report"]) if "list_report" in cfg else 0
+        if self.list_report and self.world > 1:
+            raise ValueError("--list_report needs the whole cached item table on one rank: it is single-GPU")
         Logger.info(count_parameters(self.recommender))
         self.opt = FusedAdam(self.recommender.parameters(), lr=cfg.lr, weight_decay=cfg.weight_decay)
         self.loss_name = str(cfg.loss)
@@ -230,7 +235,7 @@ class Net(object):
 
     def test_all_effects(self):
         """TE and TIE metrics on the test split, formatted as the reference prints them."""
-        rec, lines, ranks = self.recommender, {}, {}
+        rec, lines, ranks, shown = self.recommender, {}, {}, {}
         if self.grouped:
             Logger.info(rec.test_evaluator.metrics_info())
         for effect in EFFECTS:
@@ -246,8 +251,15 @@ class Net(object):
             if self.rank_report:           # where the test items stand in the full ranking under this effect
                 ranks[effect] = rec.rank_reporter.pair_ranks(rec)
                 Logger.info("  [{}] catalogue rank of the test items:\n{}".format(effect, rec.rank_reporter.evaluate(rec, ranks[effect])[1]))
+            if self.list_report:           # the lists themselves under this effect: how alike, how popular, how much of the catalogue
+                shown[effect] = rec.list_reporter.list_rows(rec)
+                Logger.info("  [{}] top-{} lists: similarity, popularity, exposure:\n{}".format(
+                    effect, self.list_report, rec.list_reporter.evaluate(rec, shown[effect])[1]))
         if self.rank_report:               # positive delta: TIE ranks the test item higher than TE does
             Logger.info("  [TE->TIE] rank shift of the test items:\n{}".format(rec.rank_reporter.shift(ranks["TE"], ranks["TIE"])[1]))
+        if self.list_report:               # overlap: the share of the TE list that TIE keeps; d_<column>: TIE - TE
+            a, b = shown["TE"], shown["TIE"]
+            Logger.info("  [TE->TIE] list shift:\n{}".format(rec.list_reporter.shift(a[0], a[2], b[0], b[2])[1]))
         if self.neighbour_report:
             Logger.info("  [neighbours] top-{} cosine neighbours of every item, fused space against the heads:\n{}".format(
                 self.neighbour_report, rec.neighbour_reporter.evaluate(rec)[1]))
