@@ -7,7 +7,8 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import ops
-from .evaluator import EffectReport, ListReport, NeighbourReport, ProxyEvaluator, RankReport
+from .evaluator import ProxyEvaluator
+from .reports import EffectReport, ListReport, NeighbourReport, RankReport
 
 
 class BasicModel(nn.Module):
@@ -38,14 +39,14 @@ class BasicModel(nn.Module):
             for ev in (self.valid_evaluator, self.test_evaluator):
                 ev.evaluator.tie_order = str(config["tie_order"])
         # --effect_report=K (CLI-only, default 0 = off): the effect breakdown of the test users' top-K lists, its column means
-        # overall and per user group (evaluator.EffectReport)
+        # overall and per user group (reports.EffectReport)
         k_report = int(config["effect_report"]) if "effect_report" in config else 0
         if k_report < 0:
             raise ValueError("effect_report must be 0 (off) or the K of the lists to break down")
         self.effect_reporter = EffectReport(dataset, train, dataset.get_user_test_dict(), k_report,
                                             group_view=config["group_view"]) if k_report else None
         # --rank_report=1 (CLI-only, default 0 = off): the exact catalogue rank of every (test user, test item) pair and its means
-        # overall, per user group and -- with --item_group_view=[...] -- per item popularity group (evaluator.RankReport)
+        # overall, per user group and -- with --item_group_view=[...] -- per item popularity group (reports.RankReport)
         item_view = config["item_group_view"] if "item_group_view" in config else None
         if "rank_report" in config and int(config["rank_report"]) not in (0, 1):
             raise ValueError("rank_report must be 0 (off) or 1")
@@ -53,14 +54,14 @@ class BasicModel(nn.Module):
                                         item_group_view=item_view) if "rank_report" in config and int(config["rank_report"]) else None
         # --neighbour_report=K (CLI-only, default 0 = off): every item's top-K cosine neighbours in the fused space and in each head's
         # space -- how much of the fused list a head's list repeats, the lists' mean cosine and popularity -- as means overall and,
-        # with --item_group_view=[...], per item popularity group (evaluator.NeighbourReport)
+        # with --item_group_view=[...], per item popularity group (reports.NeighbourReport)
         k_near = int(config["neighbour_report"]) if "neighbour_report" in config else 0
         if k_near < 0:
             raise ValueError("neighbour_report must be 0 (off) or the K of the neighbour lists")
         self.neighbour_reporter = NeighbourReport(dataset, train, k_near, item_group_view=item_view) if k_near else None
         # --list_report=K (CLI-only, default 0 = off): the test users' top-K lists themselves -- intra-list similarity in the fused
         # space and in each head's space, popularity of the listed items, catalogue coverage / Gini / entropy of the exposure --
-        # overall, per user group (--group_view) and per item popularity group (--item_group_view) (evaluator.ListReport)
+        # overall, per user group (--group_view) and per item popularity group (--item_group_view) (reports.ListReport)
         k_list = int(config["list_report"]) if "list_report" in config else 0
         if k_list and not 2 <= k_list <= min(ops.LIST_MAX_K, int(dataset.num_items)):
             raise ValueError("list_report must be 0 (off) or the K of the lists, 2 <= K <= min(%d, the catalogue's %d items), got %d"
@@ -100,7 +101,7 @@ class BasicModel(nn.Module):
         return self.test_evaluator.evaluate_with_overall(self)
 
     def effect_report(self):
-        """(final, buf) of evaluator.EffectReport over the test users under the current predict type; None when --effect_report is off."""
+        """(final, buf) of reports.EffectReport over the test users under the current predict type; None when --effect_report is off."""
         return self.effect_reporter.evaluate(self) if self.effect_reporter is not None else None
 
     # ---- generic losses on top of getEmbedding (BasicModel.py:59-113). EliMRec overrides bpr_loss; these are the

@@ -24,6 +24,7 @@
 // stage 16 rows <= 16.3 KiB, A columns <= 16 KiB: at most 69 KiB, two workgroups per CU at K = 256 and any d.
 // list_overlap_kernel: one wave per row, list b in LDS, every lane counts its entries of a; integer, exact.
 #include "common.h"
+#include "cosine.h"
 
 namespace elimrec {
 
@@ -31,15 +32,9 @@ constexpr int KNN_CHUNK = 4096, KNN_TILE = 64, KNN_MAXK = 256, KNN_MAXD = 256, K
 constexpr int KNN_OVERLAP_MAXK = 1024;
 typedef float knn_v4f __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ void knn_wave_sync() {          // LDS written by other lanes of this wave is read next
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 __device__ __forceinline__ bool knn_before(float va, int ia, float vb, int ib) {   // a ranks before b (elimrec_topk_merge's order)
     return va > vb || (va == vb && ia < ib);
 }
-__device__ __forceinline__ float knn_inv_norm(float sq) { return 1.f / fmaxf(sqrtf(sq), 1e-12f); }
 
 struct KnnArgs {
     const float *T; int64_t ld, n_rows; int d;
@@ -76,7 +71,7 @@ __device__ __forceinline__ void knn_compact(float *lv, int *li_, int *cnt, float
 #pragma unroll
         for (int e = 0; e < E; ++e) rk[e] += knn_before(vj, ij, v[e], id[e]) ? 1 : 0;
     }
-    knn_wave_sync();                                        // every lane has read the list
+    wave_lds_sync();                                        // every lane has read the list
 #pragma unroll
     for (int e = 0; e < E; ++e)
         if (lane + 64 * e < n && rk[e] < K) {
@@ -85,7 +80,7 @@ __device__ __forceinline__ void knn_compact(float *lv, int *li_, int *cnt, float
             if (rk[e] == K - 1) *thr = v[e];
         }
     if (lane == 0) *cnt = n < K ? n : K;
-    knn_wave_sync();
+    wave_lds_sync();
 }
 
 // D: 32 / 64 / 128 = the dimension at compile time, query operands in registers; 0 = any d % 4 == 0 up to KNN_MAXD.
@@ -135,7 +130,7 @@ __global__ __launch_bounds__(64 * W) void knn_chunk_kernel(KnnArgs a) {
         int64_t qr = q < a.Q ? (int64_t)a.qrows[q] : -1;
         if (qr >= a.n_rows) qr = -1;
         qid[r] = (int)qr;
-        invq[r] = qr >= 0 ? knn_inv_norm(a.sq[qr * a.ld_sq]) : 0.f;
+        invq[r] = qr >= 0 ? inv_norm(a.sq[qr * a.ld_sq]) : 0.f;
         thr[r] = qr >= 0 ? NEG : POS;
     }
     if (lane < 16) {
@@ -157,11 +152,7 @@ __global__ __launch_bounds__(64 * W) void knn_chunk_kernel(KnnArgs a) {
                 const int r = e / d, c = e - r * d;
                 const int64_t cand = s0 + r;
                 float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (cand < c_end) {
-                    const float *src = a.T + cand * a.ld + c;
-                    if (a.vec) x = *reinterpret_cast<const float4 *>(src);
-                    else x = make_float4(src[0], src[1], src[2], src[3]);
-                }
+                if (cand < c_end) ELIMREC_LOAD_ROW4(x, a.T + cand * a.ld + c, a.vec);
                 pf[p] = x;
             }
         }
@@ -176,7 +167,7 @@ __global__ __launch_bounds__(64 * W) void knn_chunk_kernel(KnnArgs a) {
                 *reinterpret_cast<float4 *>(s_b + r * LD + c) = pf[p];
             }
         }
-        if (tid < SR) s_invc[tid] = knn_inv_norm(sq_pf);
+        if (tid < SR) s_invc[tid] = inv_norm(sq_pf);
     };
 
     float *my_lv = s_lv + wave * 16 * CAP;
@@ -232,7 +223,7 @@ __global__ __launch_bounds__(64 * W) void knn_chunk_kernel(KnnArgs a) {
                     my_li[row * CAP + pos] = (int)cand;
                 }
             }
-            knn_wave_sync();
+            wave_lds_sync();
             unsigned long long full = __ballot(lane < 16 && my_cnt[lane & 15] > CAP - 16) & 0xffffull;
             if (full) {                                      // wave-uniform
                 while (full) {
@@ -271,7 +262,7 @@ __global__ __launch_bounds__(256) void list_overlap_kernel(const int32_t *__rest
     if (r >= n_rows) return;                                 // (wave-uniform; no workgroup barrier below)
     int *b = s_list + wave * K;
     for (int k = lane; k < K; k += 64) b[k] = lb[r * K + k];
-    knn_wave_sync();
+    wave_lds_sync();
     int n = 0;
     for (int k = lane; k < K; k += 64) {
         const int x = la[r * K + k];

@@ -8,7 +8,7 @@
 // DC + 4 floats: 16-byte aligned b128 stores, operand reads two-way at worst), and the K x K upper triangle is formed as 16 x 16
 // tiles (ti <= tj) on v_mfma_f32_16x16x4_f32: wave w takes tiles w, w + W, ... in row-major triangle order; A = the rows of tile
 // ti, B = the rows of tile tj, so lane (li, kq) ends with positions i = 16 ti + 4 kq + r against j = 16 tj + li. A pair i < j adds
-//     (double)((dot * inv(sq_i)) * inv(sq_j)),   inv(x) = 1 / max(sqrt(x), 1e-12)            (knn.hip's knn_inv_norm)
+//     (double)((dot * inv(sq_i)) * inv(sq_j)),   inv(x) = 1 / max(sqrt(x), 1e-12)            (cosine.h's inv_norm)
 // to the lane's float64 sum; with several column chunks `dot` is the chunk's part of the dot product (the cosine is linear in it).
 // The lane sums are folded by a fixed butterfly, the wave sums added in wave order, divided by the number of listed pairs in
 // float64 and rounded ONCE to fp32: the sum's order is fixed by (K, d) alone, so a list's bits depend on its entries only -- not on
@@ -18,14 +18,13 @@
 // norms, 1 KiB of ids, 32 B of wave sums: 62.1 KiB, two workgroups per CU. K = 10, d = 64: 16 x 68 floats = 4.3 KiB, one chunk.
 // list_exposure_kernel: counts[id] += 1 per listed entry, integer vector atomics: exact, whatever the order.
 #include "common.h"
+#include "cosine.h"
 
 namespace elimrec {
 
 constexpr int LIST_MAXK = 256, LIST_MAXD = 256, LIST_MAXBLOCKS = 8, LIST_SMALLK = 32;
 constexpr int LIST_ROW_FLOATS = 15 * 1024;                   // LDS floats for the staged rows (60 KiB)
 typedef float list_v4f __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float list_inv_norm(float sq) { return 1.f / fmaxf(sqrtf(sq), 1e-12f); }
 
 // columns of one LDS stage for KP padded list positions: all d when they fit, else the largest multiple of 4 that does
 static inline int list_chunk_cols(int KP, int d) {
@@ -75,17 +74,13 @@ __global__ __launch_bounds__(64 * W) void list_pair_cosine_kernel(ListArgs a) {
             if (c0 == 0)
                 for (int k = tid; k < KP; k += NT) {
                     const int id = s_ids[k];
-                    s_inv[k] = id >= 0 ? list_inv_norm(a.sq[(int64_t)id * a.ld_sq + h]) : 0.f;
+                    s_inv[k] = id >= 0 ? inv_norm(a.sq[(int64_t)id * a.ld_sq + h]) : 0.f;
                 }
             for (int e = tid; e < KP * c4n; e += NT) {
                 const int r = e / c4n, c = (e - r * c4n) << 2;
                 const int id = s_ids[r];
                 float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (id >= 0) {
-                    const float *src = a.T + (int64_t)id * a.ld + (int64_t)h * d + c0 + c;
-                    if (a.vec) x = *reinterpret_cast<const float4 *>(src);
-                    else x = make_float4(src[0], src[1], src[2], src[3]);
-                }
+                if (id >= 0) ELIMREC_LOAD_ROW4(x, a.T + (int64_t)id * a.ld + (int64_t)h * d + c0 + c, a.vec);
                 *reinterpret_cast<float4 *>(s_rows + r * LD + c) = x;
             }
             __syncthreads();

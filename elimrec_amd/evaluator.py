@@ -14,21 +14,18 @@ algorithm is replayed on the device, one wave per user, inside the scoring call 
 ref_order_kernel) -- same cost as tie_order = "id", the device's own rule (score descending, item
 id ascending). The two agree on every row without tied scores at or across the K boundary.
 """
-import collections
-
 import numpy as np
 import torch
 
 from . import ops
 from .data_iterator import DataIterator
+from .ops import CandidateScoringError                                                                      # noqa: F401
+# (the reports and their pure functions live in reports.py; they stay importable from here)
+from .reports import (EXPOSURE_COLUMNS, EffectReport, ListReport, ListTables, NeighbourReport, RankReport, RankTables,   # noqa: F401
+                      assign_item_groups, assign_user_groups, exposure_summary, format_rows, group_index, group_table, lists_csr)
 
 metric_dict = {"Precision": 1, "Recall": 2, "MAP": 3, "NDCG": 4, "MRR": 5}
 re_metric_dict = {v: k for k, v in metric_dict.items()}
-
-
-class CandidateScoringError(ValueError):
-    """A candidate-list (sampled-negative) evaluation or scoring call this package does not run: item-sharded / lean tables,
-    or a top-K beyond the shortest candidate list."""
 
 
 class UniEvaluator(object):
@@ -170,11 +167,7 @@ class UniEvaluator(object):
         return "metrics:\t%s" % "\t".join(cols)
 
     def _batch_csr(self, users, table, device, unique):
-        lists = [sorted(set(table.get(u, []))) if unique else table.get(u, []) for u in users]
-        ptr = np.zeros(len(users) + 1, dtype=np.int64)
-        np.cumsum([len(x) for x in lists], out=ptr[1:])
-        flat = np.fromiter((i for x in lists for i in x), dtype=np.int32, count=int(ptr[-1]))
-        return torch.from_numpy(ptr).to(device), torch.from_numpy(flat).to(device)
+        return lists_csr(users, table, device, unique=unique)
 
     def evaluate(self, model, test_users=None, shard=None):
         """shard = (rank, world): this process scores a contiguous 1/world slice of the users and the per-user metric rows
@@ -277,13 +270,9 @@ class UniEvaluator(object):
             if hit is None:
                 lists = [list(self.user_pos_test[u]) + list(self.user_neg_test[u]) for u in batch_users]
                 npos = [len(self.user_pos_test[u]) for u in batch_users]
-                lens = np.fromiter((len(x) for x in lists), dtype=np.int64, count=len(lists))
-                ptr = np.zeros(len(lists) + 1, dtype=np.int64)
-                np.cumsum(lens, out=ptr[1:])
-                flat = np.fromiter((i for x in lists for i in x), dtype=np.int32, count=int(ptr[-1]))
-                tptr = np.zeros(len(lists) + 1, dtype=np.int64)
-                np.cumsum(npos, out=tptr[1:])
-                titems = np.concatenate([np.arange(p, dtype=np.int32) for p in npos]) if tptr[-1] else np.zeros(1, dtype=np.int32)
+                ptr, flat, lens = ops.ragged(lists, dtype=np.int32)
+                tptr, titems, _ = ops.ragged([np.arange(p, dtype=np.int32) for p in npos], dtype=np.int32)
+                titems = titems if titems.size else np.zeros(1, dtype=np.int32)
                 width = int(lens.max())
                 users_t = torch.as_tensor(np.asarray(batch_users, dtype=np.int64)).to(device)
                 pos_t = torch.arange(width, dtype=torch.int32, device=device).expand(len(lists), width).contiguous() \
@@ -391,33 +380,6 @@ class UniEvaluator(object):
         return (out, idx, val) if return_topk else out
 
 
-def assign_user_groups(test_users, user_train_dict, group_view):
-    """The reference's user groups (evaluator/grouped_evaluator.py:63-80) without pandas: bounds [0] + group_view, a test user's
-    group is np.searchsorted(group_view, n_train) -- n_train in (lo, hi], so a user without training items lands in the first
-    group -- users beyond the last bound are discarded, groups without users are omitted; groups in ascending order of their
-    bounds, a group's users in the order of `test_users`.
-    -> (labels ["(lo,hi]:".ljust(12)], positions [int64 arrays of indices into test_users], number of discarded users)."""
-    if not isinstance(group_view, list):
-        raise TypeError("The type of 'group_view' must be `list`!")
-    for b in group_view:
-        if isinstance(b, bool) or not isinstance(b, (int, np.integer)) or b <= 0:
-            raise ValueError("group_view must hold strictly ascending positive integers, got %r" % (group_view,))
-    if any(hi <= lo for lo, hi in zip(group_view[:-1], group_view[1:])):
-        raise ValueError("group_view must hold strictly ascending positive integers, got %r" % (group_view,))
-    bounds = [0] + [int(b) for b in group_view]
-    n_train = np.fromiter((len(user_train_dict.get(u, [])) for u in test_users), dtype=np.int64, count=len(test_users))
-    group = np.searchsorted(np.asarray(bounds[1:], dtype=np.int64), n_train)
-    labels, positions = [], []
-    for g in range(len(group_view)):
-        at = np.flatnonzero(group == g)
-        if at.size:
-            labels.append(("(%d,%d]:" % (bounds[g], bounds[g + 1])).ljust(12))
-            positions.append(at.astype(np.int64))
-    if not labels:
-        raise ValueError("The splitting of user groups is not suitable!")
-    return labels, positions, int((group >= len(group_view)).sum())
-
-
 class GroupedEvaluator(object):
     """Ranking quality per user group, the users bucketed by their number of TRAINING interactions (the reference's
     evaluator/grouped_evaluator.py:12-112; group_view = [10, 30, 50, 100] -> (0,10], (10,30], (30,50], (50,100], heavier users
@@ -454,23 +416,17 @@ class GroupedEvaluator(object):
         return self.evaluator.metrics_info()
 
     def _group_index(self, device):
-        hit = self._index.get(str(device))
-        if hit is None:
-            ptr = np.zeros(len(self._positions) + 1, dtype=np.int64)
-            np.cumsum(self.group_sizes, out=ptr[1:])
-            hit = ops.GroupIndex(ptr, np.concatenate(self._positions).astype(np.int32), len(self.evaluator.default_users()), device)
-            self._index[str(device)] = hit
-        return hit
+        if str(device) not in self._index:
+            self._index[str(device)] = group_index(self._positions, len(self.evaluator.default_users()), device)
+        return self._index[str(device)]
 
     def group_means(self, rows):
         """Device rows [default users x metrics*K] (UniEvaluator.metric_rows) -> host float32 [groups x metrics*K]."""
-        out = torch.empty(len(self.group_labels), rows.shape[1], dtype=torch.float32, device=rows.device)
-        return ops.group_metric_means(rows, self._group_index(rows.device), None, out).cpu().numpy()
+        return group_table(rows, self._group_index(rows.device), len(self.group_labels))
 
     def format_groups(self, final):
         """[groups x shown columns] -> the reference's multi-line string (grouped_evaluator.py:107-112)."""
-        return "".join("\n%s\t%s" % (label, "\t".join(("%.8f" % x).ljust(12) for x in row))
-                       for label, row in zip(self.group_labels, final))
+        return format_rows(self.group_labels, final)
 
     def evaluate_rows(self, rows):
         """(final [groups x metrics*len(top_show)] float32, buf) from the metric rows of the default users."""
@@ -491,540 +447,6 @@ class GroupedEvaluator(object):
         group_final, group_buf = self.evaluate_rows(rows)
         final, buf = ev._summary(rows.cpu().numpy())
         return final, buf, group_final, group_buf
-
-
-class EffectReport(object):
-    """What the test users' top-K lists are made of (--effect_report=K): per (user, rank <= K) pair the effect breakdown of
-    EliMRec.effects_device -- ui, its catalogue mean, te, nde, the TE / TIE scores, the heads' cosines -- and its column means
-    over all pairs and, with group_view, per user group (assign_user_groups). The lists are the model's top-K under its current
-    predict type with train items masked, in user blocks as metric_rows takes them; the means are ops.group_metric_means over
-    the [users*K x C] block (float64 sums, the segments = rows of that block): only [1 + groups x C] floats reach the host."""
-
-    def __init__(self, dataset, user_train_dict, user_test_dict, top_k, group_view=None):
-        if not isinstance(user_train_dict, dict) or not isinstance(user_test_dict, dict):
-            raise TypeError("user_train_dict and user_test_dict must be dicts")
-        if isinstance(top_k, bool) or not isinstance(top_k, (int, np.integer)) or top_k < 1:
-            raise ValueError("top_k must be a positive integer, got %r" % (top_k,))
-        self.dataset = dataset
-        self.user_pos_train = user_train_dict
-        self.user_pos_test = user_test_dict
-        self.top_k = int(top_k)
-        self.users = list(user_test_dict.keys())
-        self.block_users = 8192
-        self.tie_order = "id"
-        self.group_labels, self._positions = ["all:".ljust(12)], [np.arange(len(self.users), dtype=np.int64)]
-        if group_view is not None:
-            labels, positions, self.num_discarded = assign_user_groups(self.users, user_train_dict, group_view)
-            self.group_labels += labels
-            self._positions += positions
-        self._index = {}                   # device -> ops.GroupIndex over the rows of the [users*K x C] block
-
-    def _group_index(self, device):
-        hit = self._index.get(str(device))
-        if hit is None:
-            K = self.top_k
-            rows = [(p[:, None] * K + np.arange(K, dtype=np.int64)[None, :]).reshape(-1) for p in self._positions]
-            ptr = np.zeros(len(rows) + 1, dtype=np.int64)
-            np.cumsum([r.size for r in rows], out=ptr[1:])
-            hit = ops.GroupIndex(ptr, np.concatenate(rows).astype(np.int32), len(self.users) * K, device)
-            self._index[str(device)] = hit
-        return hit
-
-    def effect_rows(self, model):
-        """The breakdown of every test user's top-K list on the device: ([users*K x C] float32, column names)."""
-        if not hasattr(model, "effects_device"):
-            raise TypeError("model must expose effects_device()")
-        if hasattr(model, "_ensure_tables") and getattr(model, "_cache", None) is not None:
-            model._ensure_tables()
-        if getattr(model, "_eval_shard", None) is not None:
-            raise CandidateScoringError("the effect report needs the whole cached item table on this rank; the tables are "
-                                        "item-sharded (lean / multi-rank evaluation): run without --effect_report")
-        if self.top_k > model.num_items:
-            raise CandidateScoringError("effect report of the top-%d lists: the catalogue has %d items" % (self.top_k, model.num_items))
-        device = model._require_gpu()
-        columns = ops.effect_columns(model._mods)
-        K, C = self.top_k, len(columns)
-        rows = torch.empty(len(self.users) * K, C, dtype=torch.float32, device=device)
-        at = 0
-        for batch_users in DataIterator(self.users, batch_size=self.block_users, shuffle=False, drop_last=False):
-            B = len(batch_users)
-            lists = [self.user_pos_train.get(u, []) for u in batch_users]
-            ptr = np.zeros(B + 1, dtype=np.int64)
-            np.cumsum([len(x) for x in lists], out=ptr[1:])
-            flat = np.fromiter((i for x in lists for i in x), dtype=np.int32, count=int(ptr[-1]))
-            users_t = torch.as_tensor(np.asarray(batch_users, dtype=np.int64)).to(device)
-            idx, _ = model.predict_device(users_t, top_k=K, train_ptr=torch.from_numpy(ptr).to(device),
-                                          train_items=torch.from_numpy(flat).to(device), tie_order=self.tie_order)
-            cand_ptr = torch.arange(B + 1, dtype=torch.int64, device=device) * K
-            model.effects_device(users_t, cand_ptr, idx.reshape(-1), rows[at * K:(at + B) * K].view(B, K, C))
-            at += B
-        return rows, columns
-
-    def columns_info(self, columns):
-        return "columns:\t%s" % "\t".join(str(c).ljust(12) for c in columns)
-
-    def evaluate(self, model):
-        """(final [1 + groups x C] float32: row 0 = all pairs, then one row per user group; buf: a header of column names and
-        one line per row in the grouped evaluator's format)."""
-        rows, columns = self.effect_rows(model)
-        out = torch.empty(len(self.group_labels), rows.shape[1], dtype=torch.float32, device=rows.device)
-        final = ops.group_metric_means(rows, self._group_index(rows.device), None, out).cpu().numpy()
-        buf = self.columns_info(columns) + "".join("\n%s\t%s" % (label, "\t".join(("%.8f" % x).ljust(12) for x in row))
-                                                    for label, row in zip(self.group_labels, final))
-        return final, buf
-
-
-def assign_item_groups(item_ids, train_item_counts, item_group_view):
-    """Items bucketed by popularity, the counterpart of assign_user_groups: item_group_view = [b1..bn] (strictly ascending
-    positive integers) gives `cold` (0 training interactions), (0,b1], ..., (b(n-1),bn] and the open (bn,inf); an entry of
-    item_ids lands in the bucket of train_item_counts[its id]. Groups without entries are omitted; groups in that order, a
-    group's entries in the order of item_ids.
-    -> (labels ["cold:" / "(lo,hi]:" / "(bn,inf):", each .ljust(12)], positions [int64 arrays of indices into item_ids])."""
-    if not isinstance(item_group_view, list) or not item_group_view:
-        raise TypeError("The type of 'item_group_view' must be a non-empty `list`!")
-    for b in item_group_view:
-        if isinstance(b, bool) or not isinstance(b, (int, np.integer)) or b <= 0:
-            raise ValueError("item_group_view must hold strictly ascending positive integers, got %r" % (item_group_view,))
-    if any(hi <= lo for lo, hi in zip(item_group_view[:-1], item_group_view[1:])):
-        raise ValueError("item_group_view must hold strictly ascending positive integers, got %r" % (item_group_view,))
-    bounds = [int(b) for b in item_group_view]
-    ids = np.asarray(item_ids, dtype=np.int64).reshape(-1)
-    counts = np.asarray(train_item_counts, dtype=np.int64).reshape(-1)
-    if ids.size and (ids.min() < 0 or ids.max() >= counts.size):
-        raise IndexError("item ids must lie in [0, %d)" % counts.size)
-    n = counts[ids]
-    # 0 = cold, 1 + g = (bounds[g - 1], bounds[g]] (count in (lo, hi], as the user groups), 1 + len(bounds) = beyond the last bound
-    group = np.where(n == 0, 0, 1 + np.searchsorted(np.asarray(bounds, dtype=np.int64), n))
-    names = ["cold:"] + ["(%d,%d]:" % (lo, hi) for lo, hi in zip([0] + bounds[:-1], bounds)] + ["(%d,inf):" % bounds[-1]]
-    labels, positions = [], []
-    for g, name in enumerate(names):
-        at = np.flatnonzero(group == g)
-        if at.size:
-            labels.append(name.ljust(12))
-            positions.append(at.astype(np.int64))
-    return labels, positions
-
-
-RankTables = collections.namedtuple("RankTables", ("pair_columns", "pair_labels", "pairs", "user_columns", "user_labels", "users"))
-
-
-class RankReport(object):
-    """Where the held-out items stand in the FULL ranking (--rank_report=1): every (test user, test item) pair's exact catalogue
-    rank under the model's current predict type with the train items masked (EliMRec.rank_items_device: the evaluator's scoring
-    call into a score block, then csrc/rank.hip's count over it), and from the ranks
-      per pair: rank, rr = 1 / (rank + 1), pct = rank / (candidates - 1), hit@K for every K of top_k;
-      per user: auc, mrr_full = 1 / (first_rank + 1), first_rank = the best rank among the user's test items
-    as means over all pairs / users, per user group (group_view, assign_user_groups) and -- pair columns -- per item popularity
-    group (item_group_view, assign_item_groups over the items' training interactions). The pair means are MICRO-averages: every
-    pair weighs the same, so a user with many test items weighs more, and hit@K here is NOT the evaluator's per-user recall
-    (a mean of per-user ratios). Ranks order equal scores by item id whatever the evaluator's tie_order is.
-    Pairs are all (user, item) of user_test_dict in dict order; a pair whose item is also in the user's train list is dropped
-    (num_dropped), then a user without a pair or without a candidate besides its test items (num_skipped_users). Users go in
-    blocks whose [users x items] score block stays within block_bytes; the row and mean kernels leave only the tables to the host."""
-
-    def __init__(self, dataset, user_train_dict, user_test_dict, top_k, group_view=None, item_group_view=None):
-        if not isinstance(user_train_dict, dict) or not isinstance(user_test_dict, dict):
-            raise TypeError("user_train_dict and user_test_dict must be dicts")
-        ks = [top_k] if isinstance(top_k, (int, np.integer)) and not isinstance(top_k, bool) else list(top_k)
-        if not ks or any(isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1 for k in ks):
-            raise ValueError("top_k must be a positive integer or a list of them, got %r" % (top_k,))
-        self.dataset = dataset
-        self.num_items = I = int(dataset.num_items)
-        self.user_pos_train = user_train_dict
-        self.user_pos_test = user_test_dict
-        self.ks = [int(k) for k in ks]
-        self.block_bytes = 2 << 30
-        self.num_dropped = self.num_skipped_users = 0
-        self.users, pair_items, lens, n_cand = [], [], [], []
-        for u, test_items in user_test_dict.items():
-            seen = set(int(i) for i in user_train_dict.get(u, []))
-            kept = [int(i) for i in test_items if int(i) not in seen]
-            self.num_dropped += len(test_items) - len(kept)
-            if not kept or I - len(seen) - len(kept) <= 0:
-                self.num_skipped_users += 1
-                continue
-            self.users.append(u)
-            pair_items.append(kept)
-            lens.append(len(kept))
-            n_cand.append(I - len(seen))
-        if not self.users:
-            raise ValueError("the rank report has no (test user, test item) pair left to rank")
-        self.pair_ptr = np.zeros(len(self.users) + 1, dtype=np.int64)
-        np.cumsum(lens, out=self.pair_ptr[1:])
-        self.pair_items = np.fromiter((i for x in pair_items for i in x), dtype=np.int32, count=int(self.pair_ptr[-1]))
-        if self.pair_items.min() < 0 or self.pair_items.max() >= I:
-            raise IndexError("test item ids must lie in [0, %d)" % I)
-        self.pair_user = np.repeat(np.arange(len(self.users), dtype=np.int64), lens)       # position in self.users
-        self.user_n_cand = np.asarray(n_cand, dtype=np.int32)
-        self.pair_n_cand = self.user_n_cand[self.pair_user]
-        self.num_pairs = int(self.pair_items.size)
-        # groups: rows of the user block / of the pair block
-        self.user_labels, user_pos = ["all:".ljust(12)], [np.arange(len(self.users), dtype=np.int64)]
-        self.pair_labels, pair_pos = ["all:".ljust(12)], [np.arange(self.num_pairs, dtype=np.int64)]
-        if group_view is not None:
-            labels, positions, self.num_discarded = assign_user_groups(self.users, user_train_dict, group_view)
-            self.user_labels += labels
-            user_pos += positions
-            self.pair_labels += labels
-            pair_pos += [np.flatnonzero(np.isin(self.pair_user, p)) for p in positions]
-        if item_group_view is not None:
-            counts = np.zeros(I, dtype=np.int64)
-            for items in user_train_dict.values():
-                np.add.at(counts, np.asarray(list(items), dtype=np.int64), 1)
-            labels, positions = assign_item_groups(self.pair_items, counts, item_group_view)
-            self.pair_labels += [("item " + x.strip()).ljust(12) for x in labels]
-            pair_pos += positions
-        self._user_pos, self._pair_pos = user_pos, pair_pos
-        self._device = {}                  # device -> the CSRs, candidate counts and group indices resident there
-
-    @property
-    def block_users(self):
-        """Users per scoring call: as many as keep the [users x items] float32 block (rows padded to 16 bytes) within block_bytes."""
-        return max(1, int(self.block_bytes) // ((self.num_items + 3) // 4 * 16))
-
-    def _resident(self, device):
-        hit = self._device.get(str(device))
-        if hit is None:
-            def index(positions, n_rows):
-                ptr = np.zeros(len(positions) + 1, dtype=np.int64)
-                np.cumsum([p.size for p in positions], out=ptr[1:])
-                return ops.GroupIndex(ptr, np.concatenate(positions).astype(np.int32), n_rows, device)
-            hit = dict(pair_ptr=torch.from_numpy(self.pair_ptr).to(device), user_n_cand=torch.from_numpy(self.user_n_cand).to(device),
-                       pair_n_cand=torch.from_numpy(np.ascontiguousarray(self.pair_n_cand)).to(device),
-                       user_groups=index(self._user_pos, len(self.users)), pair_groups=index(self._pair_pos, self.num_pairs), blocks={})
-            self._device[str(device)] = hit
-        return hit
-
-    def _block(self, res, a, b, device):
-        """Users [a, b) of self.users as one scoring call's inputs, kept on the device: (users, TargetIndex, train_ptr, train_items)."""
-        hit = res["blocks"].get((a, b))
-        if hit is None:
-            ptr = self.pair_ptr[a:b + 1] - self.pair_ptr[a]
-            target = ops.TargetIndex(ptr, self.pair_items[self.pair_ptr[a]:self.pair_ptr[b]], b - a, self.num_items, device)
-            lists = [self.user_pos_train.get(u, []) for u in self.users[a:b]]
-            tptr = np.zeros(b - a + 1, dtype=np.int64)
-            np.cumsum([len(x) for x in lists], out=tptr[1:])
-            flat = np.fromiter((int(i) for x in lists for i in x), dtype=np.int32, count=int(tptr[-1]))
-            train = (torch.from_numpy(tptr).to(device), torch.from_numpy(flat).to(device)) if flat.size else (None, None)
-            hit = (torch.as_tensor(np.asarray(self.users[a:b], dtype=np.int64)).to(device), target) + train
-            res["blocks"][(a, b)] = hit
-        return hit
-
-    def pair_ranks(self, model):
-        """The exact catalogue rank of every pair under the model's current predict type: int32 [num_pairs] on the device."""
-        if not hasattr(model, "rank_items_device"):
-            raise TypeError("model must expose rank_items_device()")
-        if hasattr(model, "_ensure_tables") and getattr(model, "_cache", None) is not None:
-            model._ensure_tables()
-        if getattr(model, "_eval_shard", None) is not None:
-            raise CandidateScoringError("the rank report needs the whole cached item table on this rank; the tables are "
-                                        "item-sharded (lean / multi-rank evaluation): run without --rank_report")
-        if model.num_items != self.num_items:
-            raise ValueError("the report was built for %d items, the model has %d" % (self.num_items, model.num_items))
-        device = model._require_gpu()
-        res = self._resident(device)
-        ranks = torch.empty(self.num_pairs, dtype=torch.int32, device=device)
-        step = self.block_users
-        for a in range(0, len(self.users), step):
-            b = min(a + step, len(self.users))
-            users, target, tptr, titems = self._block(res, a, b, device)
-            ranks[self.pair_ptr[a]:self.pair_ptr[b]] = model.rank_items_device(users, target, tptr, titems)[0]
-        return ranks
-
-    def _tables(self, pair_rows, pair_columns, user_rows, user_columns, res):
-        pairs = torch.empty(len(self.pair_labels), pair_rows.shape[1], dtype=torch.float32, device=pair_rows.device)
-        ops.group_metric_means(pair_rows, res["pair_groups"], None, pairs)
-        users = None
-        if user_rows is not None:
-            users = torch.empty(len(self.user_labels), user_rows.shape[1], dtype=torch.float32, device=user_rows.device)
-            users = ops.group_metric_means(user_rows, res["user_groups"], None, users).cpu().numpy()
-        final = RankTables(tuple(pair_columns), list(self.pair_labels), pairs.cpu().numpy(), tuple(user_columns),
-                           list(self.user_labels) if users is not None else [], users)
-        buf = self._format(final.pair_columns, final.pair_labels, final.pairs)
-        if users is not None:
-            buf += "\n" + self._format(final.user_columns, final.user_labels, final.users)
-        return final, buf
-
-    @staticmethod
-    def _format(columns, labels, table):
-        return "columns:\t%s" % "\t".join(str(c).ljust(12) for c in columns) + "".join(
-            "\n%s\t%s" % (label, "\t".join(("%.8f" % x).ljust(12) for x in row)) for label, row in zip(labels, table))
-
-    def evaluate(self, model, ranks=None):
-        """(final, buf). final = RankTables: pairs [1 + user groups + item groups x (3 + len(ks))] float32 -- row 0 = all pairs --
-        the means of rank, rr, pct, hit@K; users [1 + user groups x 3] the means of auc, mrr_full, first_rank. The pair means are
-        micro-averages (see the class). buf: per table a header of column names and one "%.8f" line per row, in the grouped
-        evaluator's format. ranks: pair_ranks(model) if the caller already holds it."""
-        if ranks is None:
-            ranks = self.pair_ranks(model)
-        res = self._resident(ranks.device)
-        pair_rows = torch.empty(self.num_pairs, 3 + len(self.ks), dtype=torch.float32, device=ranks.device)
-        ops.rank_pair_rows(ranks, res["pair_n_cand"], self.ks, pair_rows)
-        user_rows = torch.empty(len(self.users), 3, dtype=torch.float32, device=ranks.device)
-        ops.rank_user_rows(ranks, res["pair_ptr"], res["user_n_cand"], user_rows)
-        return self._tables(pair_rows, ops.rank_pair_columns(self.ks), user_rows, ops.RANK_USER_COLUMNS, res)
-
-    def shift(self, ranks_a, ranks_b):
-        """How far the pairs move from ranking a to ranking b (e.g. TE -> TIE): (final, buf) in evaluate()'s pair grouping over
-        delta = a - b (positive: b ranks the test item higher), improved = (b < a), worsened = (b > a)."""
-        if ranks_a.shape != (self.num_pairs,) or ranks_b.shape != (self.num_pairs,) or ranks_a.device != ranks_b.device:
-            raise ValueError("shift() takes two pair_ranks() results of this report on one device")
-        rows = torch.stack(((ranks_a - ranks_b).float(), (ranks_b < ranks_a).float(), (ranks_b > ranks_a).float()), dim=1)
-        return self._tables(rows, ("delta", "improved", "worsened"), None, (), self._resident(ranks_a.device))
-
-
-class NeighbourReport(object):
-    """Whose neighbourhood the fused space copies (--neighbour_report=K): for EVERY item its top-k neighbour lists by cosine in the
-    fused space and in each single-modal head's space (EliMRec.neighbours_device, csrc/knn.hip), items in blocks of block_items,
-    and per item the columns of ops.neighbour_columns(mods):
-      overlap_<m> = |fused list & head m's list| / k (ops.list_overlap); cos_fused, cos_<m> = the mean score of the list;
-      pop_fused, pop_<m> = the mean training-interaction count of the listed neighbours
-    (fillers skipped; a column of a row without neighbours is NaN). Their means over all items and -- item_group_view -- per item
-    popularity group (assign_item_groups over the items' training interactions) are ops.group_metric_means over the
-    [items x C] block: only the [1 + groups x C] table reaches the host. The lists do not depend on the predict type."""
-
-    def __init__(self, dataset, user_train_dict, k, item_group_view=None):
-        if not isinstance(user_train_dict, dict):
-            raise TypeError("user_train_dict must be a dict")
-        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1 or k > ops.KNN_MAX_K:
-            raise ValueError("k must be an integer in [1, %d], got %r" % (ops.KNN_MAX_K, k))
-        self.dataset = dataset
-        self.num_items = I = int(dataset.num_items)
-        self.k = int(k)
-        self.block_items = 8192
-        self.item_counts = np.zeros(I, dtype=np.int64)
-        for items in user_train_dict.values():
-            np.add.at(self.item_counts, np.asarray(list(items), dtype=np.int64), 1)
-        self.group_labels, self._positions = ["all:".ljust(12)], [np.arange(I, dtype=np.int64)]
-        if item_group_view is not None:
-            labels, positions = assign_item_groups(np.arange(I, dtype=np.int64), self.item_counts, item_group_view)
-            self.group_labels += labels
-            self._positions += positions
-        self._device = {}                  # device -> the group index, the counts and the blocks' checked queries resident there
-
-    def _resident(self, device):
-        hit = self._device.get(str(device))
-        if hit is None:
-            ptr = np.zeros(len(self._positions) + 1, dtype=np.int64)
-            np.cumsum([p.size for p in self._positions], out=ptr[1:])
-            hit = dict(groups=ops.GroupIndex(ptr, np.concatenate(self._positions).astype(np.int32), self.num_items, device),
-                       counts=torch.from_numpy(self.item_counts.astype(np.float64)).to(device), queries={})
-            self._device[str(device)] = hit
-        return hit
-
-    def neighbour_rows(self, model):
-        """Every item's row of the report on the device: ([items x C] float32, column names)."""
-        if not hasattr(model, "neighbours_device"):
-            raise TypeError("model must expose neighbours_device()")
-        if hasattr(model, "_ensure_tables") and getattr(model, "_cache", None) is not None:
-            model._ensure_tables()
-        if getattr(model, "_eval_shard", None) is not None:
-            raise CandidateScoringError("the neighbour report needs the whole cached item table on this rank; the tables are "
-                                        "item-sharded (lean / multi-rank evaluation): run without --neighbour_report")
-        if model.num_items != self.num_items:
-            raise ValueError("the report was built for %d items, the model has %d" % (self.num_items, model.num_items))
-        device = model._require_gpu()
-        res = self._resident(device)
-        mods = tuple(model._mods)
-        columns = ops.neighbour_columns(mods)
-        S, k, I = len(mods), self.k, self.num_items
-        rows = torch.empty(I, len(columns), dtype=torch.float32, device=device)
-        step = max(1, int(self.block_items))
-        idx = torch.empty(1 + S, min(step, I), k, dtype=torch.int32, device=device)
-        val = torch.empty(1 + S, min(step, I), k, dtype=torch.float32, device=device)
-        cnt = torch.empty(min(step, I), dtype=torch.int32, device=device)
-        nan = torch.full((), float("nan"), dtype=torch.float64, device=device)
-        for a in range(0, I, step):
-            b = min(a + step, I)
-            query = res["queries"].get((a, b))
-            if query is None:
-                query = res["queries"][(a, b)] = ops.NeighbourQuery(np.arange(a, b, dtype=np.int32), I, device)
-            for h, space in enumerate(("fused",) + mods):
-                model.neighbours_device("item", None, k, space, idx[h, :b - a], val[h, :b - a], query=query)
-            listed = idx[:, :b - a] >= 0                                           # [1 + S x B x k]
-            n = listed.sum(dim=2).double()
-            out = rows[a:b]
-            for h in range(S):
-                ops.list_overlap(idx[0, :b - a], idx[1 + h, :b - a], cnt)
-                out[:, h] = torch.where(n[0] > 0, cnt[:b - a].double() / k, nan).float()
-            out[:, S:2 * S + 1] = (torch.where(listed, val[:, :b - a].double(), 0.0).sum(dim=2) / n).t().float()
-            pop = res["counts"][idx[:, :b - a].clamp(min=0).long()]
-            out[:, 2 * S + 1:] = (torch.where(listed, pop, 0.0).sum(dim=2) / n).t().float()
-        return rows, columns
-
-    def evaluate(self, model):
-        """(final [1 + item groups x C] float32: row 0 = all items, then one row per item popularity group; buf: a header of column
-        names and one "%.8f" line per row, in the effect report's format)."""
-        rows, columns = self.neighbour_rows(model)
-        out = torch.empty(len(self.group_labels), rows.shape[1], dtype=torch.float32, device=rows.device)
-        final = ops.group_metric_means(rows, self._resident(rows.device)["groups"], None, out).cpu().numpy()
-        buf = "columns:\t%s" % "\t".join(str(c).ljust(12) for c in columns) + "".join(
-            "\n%s\t%s" % (label, "\t".join(("%.8f" % x).ljust(12) for x in row)) for label, row in zip(self.group_labels, final))
-        return final, buf
-
-
-EXPOSURE_COLUMNS = ("items", "coverage", "gini", "entropy", "slot_share")
-
-
-def exposure_summary(counts, positions):
-    """How the list slots spread over the catalogue: float64 [len(positions) x 5], per group of item positions (index arrays into
-    counts) the columns EXPOSURE_COLUMNS:
-      items = the group's size; coverage = the share of its items with count > 0;
-      gini = the Gini coefficient of its counts, sum_i (2 i - n - 1) c_(i) / (n sum c) over the ascending counts c_(1..n)
-             (0 = every item listed equally often, (n - 1) / n = one item takes every slot; 0 for an empty or all-zero group);
-      entropy = -sum p log2 p in bits over p = c / sum c of the group (0 for an empty or all-zero group);
-      slot_share = the group's counts over ALL counts (0 when nothing is listed at all).
-    counts: how often each item is listed (ops.list_exposure). Pure numpy, float64."""
-    c_all = np.asarray(counts, dtype=np.float64).reshape(-1)
-    total = c_all.sum()
-    out = np.zeros((len(positions), len(EXPOSURE_COLUMNS)), dtype=np.float64)
-    for g, at in enumerate(positions):
-        c = np.sort(c_all[np.asarray(at, dtype=np.int64).reshape(-1)])
-        n, s = c.size, c.sum()
-        out[g, 0] = n
-        if n:
-            out[g, 1] = np.count_nonzero(c > 0) / float(n)
-        if n and s > 0:
-            out[g, 2] = ((2.0 * np.arange(1, n + 1) - n - 1.0) * c).sum() / (n * s)
-            p = c[c > 0] / s
-            out[g, 3] = 0.0 - (p * np.log2(p)).sum()
-        if total > 0:
-            out[g, 4] = s / total
-    return out
-
-
-ListTables = collections.namedtuple("ListTables", ("user_columns", "user_labels", "users", "item_columns", "item_labels", "items"))
-
-
-class ListReport(object):
-    """The recommendation lists themselves (--list_report=K): every test user's top-K list under the model's current predict
-    type with the train items masked (predict_device, users in blocks of block_users as EffectReport takes them), and
-      per user the columns of ops.list_columns(mods): ils_fused, ils_<m> = the mean pairwise cosine of the K listed items in the
-        fused space and in each head's space (EliMRec.list_similarity_device, csrc/lists.hip: one launch per block for all
-        spaces), pop = the mean training-interaction count of the listed items (float64 quotient; NaN for an empty list);
-      per item how often it is listed (ops.list_exposure, int32 counters filled block after block).
-    The user table is ops.group_metric_means over the rows: all users, then the group_view groups (assign_user_groups). The
-    item table is exposure_summary of the counters over all items, then the item_group_view groups (assign_item_groups over the
-    items' training interactions); the counters come to the host once per evaluate(): num_items int32 values."""
-
-    def __init__(self, dataset, user_train_dict, user_test_dict, top_k, group_view=None, item_group_view=None):
-        if not isinstance(user_train_dict, dict) or not isinstance(user_test_dict, dict):
-            raise TypeError("user_train_dict and user_test_dict must be dicts")
-        if isinstance(top_k, bool) or not isinstance(top_k, (int, np.integer)) or top_k < 2 or top_k > ops.LIST_MAX_K:
-            raise ValueError("top_k must be an integer in [2, %d], got %r" % (ops.LIST_MAX_K, top_k))
-        self.dataset = dataset
-        self.num_items = I = int(dataset.num_items)
-        self.user_pos_train = user_train_dict
-        self.user_pos_test = user_test_dict
-        self.top_k = int(top_k)
-        self.users = list(user_test_dict.keys())
-        self.block_users = 8192
-        self.tie_order = "id"
-        self.item_counts = np.zeros(I, dtype=np.int64)
-        for items in user_train_dict.values():
-            np.add.at(self.item_counts, np.asarray(list(items), dtype=np.int64), 1)
-        self.group_labels, self._positions = ["all:".ljust(12)], [np.arange(len(self.users), dtype=np.int64)]
-        if group_view is not None:
-            labels, positions, self.num_discarded = assign_user_groups(self.users, user_train_dict, group_view)
-            self.group_labels += labels
-            self._positions += positions
-        self.item_labels, self._item_positions = ["all:".ljust(12)], [np.arange(I, dtype=np.int64)]
-        if item_group_view is not None:
-            labels, positions = assign_item_groups(np.arange(I, dtype=np.int64), self.item_counts, item_group_view)
-            self.item_labels += [("item " + x.strip()).ljust(12) for x in labels]
-            self._item_positions += positions
-        self.columns = self.shift_columns = None   # ops.list_columns of the model list_rows() last saw; ("overlap", "d_<column>"...)
-        self._device = {}                  # device -> the user group index and the items' training counts resident there
-
-    def _resident(self, device):
-        hit = self._device.get(str(device))
-        if hit is None:
-            ptr = np.zeros(len(self._positions) + 1, dtype=np.int64)
-            np.cumsum([p.size for p in self._positions], out=ptr[1:])
-            hit = dict(groups=ops.GroupIndex(ptr, np.concatenate(self._positions).astype(np.int32), len(self.users), device),
-                       counts=torch.from_numpy(self.item_counts.astype(np.float64)).to(device))
-            self._device[str(device)] = hit
-        return hit
-
-    def list_rows(self, model):
-        """Every test user's row, list and the catalogue's exposure on the device: ([users x C] float32, column names,
-        lists int32 [users x K], counts int32 [num_items])."""
-        if not hasattr(model, "list_similarity_device"):
-            raise TypeError("model must expose list_similarity_device()")
-        if hasattr(model, "_ensure_tables") and getattr(model, "_cache", None) is not None:
-            model._ensure_tables()
-        if getattr(model, "_eval_shard", None) is not None:
-            raise CandidateScoringError("the list report needs the whole cached item table on this rank; the tables are "
-                                        "item-sharded (lean / multi-rank evaluation): run without --list_report")
-        if model.num_items != self.num_items:
-            raise ValueError("the report was built for %d items, the model has %d" % (self.num_items, model.num_items))
-        if self.top_k > model.num_items:
-            raise CandidateScoringError("list report of the top-%d lists: the catalogue has %d items" % (self.top_k, model.num_items))
-        device = model._require_gpu()
-        res = self._resident(device)
-        columns = self.columns = ops.list_columns(model._mods)
-        K, nb, n_users = self.top_k, len(columns) - 1, len(self.users)
-        rows = torch.empty(n_users, len(columns), dtype=torch.float32, device=device)
-        ils = torch.empty(n_users, nb, dtype=torch.float32, device=device)
-        lists = torch.empty(n_users, K, dtype=torch.int32, device=device)
-        counts = torch.zeros(self.num_items, dtype=torch.int32, device=device)
-        at = 0
-        for batch_users in DataIterator(self.users, batch_size=self.block_users, shuffle=False, drop_last=False):
-            B = len(batch_users)
-            train = [self.user_pos_train.get(u, []) for u in batch_users]
-            ptr = np.zeros(B + 1, dtype=np.int64)
-            np.cumsum([len(x) for x in train], out=ptr[1:])
-            flat = np.fromiter((i for x in train for i in x), dtype=np.int32, count=int(ptr[-1]))
-            users_t = torch.as_tensor(np.asarray(batch_users, dtype=np.int64)).to(device)
-            idx, _ = model.predict_device(users_t, top_k=K, train_ptr=torch.from_numpy(ptr).to(device),
-                                          train_items=torch.from_numpy(flat).to(device), tie_order=self.tie_order)
-            lists[at:at + B] = idx
-            model.list_similarity_device(lists[at:at + B], ils[at:at + B], side="item")
-            ops.list_exposure(lists[at:at + B], counts)
-            at += B
-        listed = lists >= 0
-        pop = torch.where(listed, res["counts"][lists.clamp(min=0).long()], 0.0).sum(dim=1) / listed.sum(dim=1).double()
-        rows[:, :nb] = ils
-        rows[:, nb] = pop.float()
-        return rows, columns, lists, counts
-
-    def _user_table(self, rows):
-        out = torch.empty(len(self.group_labels), rows.shape[1], dtype=torch.float32, device=rows.device)
-        return ops.group_metric_means(rows, self._resident(rows.device)["groups"], None, out).cpu().numpy()
-
-    @staticmethod
-    def _format(columns, labels, table):
-        return "columns:\t%s" % "\t".join(str(c).ljust(12) for c in columns) + "".join(
-            "\n%s\t%s" % (label, "\t".join(("%.8f" % x).ljust(12) for x in row)) for label, row in zip(labels, table))
-
-    def evaluate(self, model, rows=None):
-        """(final, buf). final = ListTables: users [1 + user groups x C] float32 -- row 0 = all test users -- the means of
-        ops.list_columns; items [1 + item groups x 5] float64 -- row 0 = the whole catalogue -- exposure_summary of the counters,
-        columns EXPOSURE_COLUMNS. buf: per table a header of column names and one "%.8f" line per row, in the grouped evaluator's
-        format. rows: list_rows(model) if the caller already holds it."""
-        rows, columns, _, counts = self.list_rows(model) if rows is None else rows
-        items = exposure_summary(counts.cpu().numpy(), self._item_positions)
-        final = ListTables(tuple(columns), list(self.group_labels), self._user_table(rows), EXPOSURE_COLUMNS, list(self.item_labels), items)
-        buf = self._format(final.user_columns, final.user_labels, final.users) + "\n" + self._format(
-            final.item_columns, final.item_labels, final.items)
-        return final, buf
-
-    def shift(self, rows_a, lists_a, rows_b, lists_b):
-        """How the lists change from a to b (e.g. TE -> TIE): (final [1 + user groups x 1 + C] float32, buf) in evaluate()'s user
-        grouping over the columns self.shift_columns: overlap = |list a & list b| / K (ops.list_overlap) and d_<column> = b - a for
-        every user column."""
-        n, K = len(self.users), self.top_k
-        if (tuple(lists_a.shape) != (n, K) or lists_a.shape != lists_b.shape or rows_a.shape != rows_b.shape or rows_a.shape[0] != n
-                or len({t.device for t in (rows_a, rows_b, lists_a, lists_b)}) != 1):
-            raise ValueError("shift() takes the rows and lists of two list_rows() results of this report on one device")
-        cnt = torch.empty(n, dtype=torch.int32, device=lists_a.device)
-        ops.list_overlap(lists_a, lists_b, cnt)
-        rows = torch.cat(((cnt.double() / K).float()[:, None], rows_b - rows_a), dim=1)
-        if self.columns is None or len(self.columns) != rows_a.shape[1]:
-            raise ValueError("shift() takes rows of this report's list_rows()")
-        self.shift_columns = ("overlap",) + tuple("d_" + c for c in self.columns)
-        final = self._user_table(rows)
-        return final, self._format(self.shift_columns, self.group_labels, final)
 
 
 class ProxyEvaluator(object):

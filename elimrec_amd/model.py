@@ -1131,16 +1131,46 @@ class EliMRec(BasicModel):
         modality = "v" if self.is_kwai else self.modality
         return sum(1 << h for h, m in enumerate(self._mods) if m in modality)
 
+    def _cached_tables(self, what, sharded_msg=None):
+        """The one way into the cached tables for everything that reads them: a GPU model, the pending step made real, tables
+        cached by a training forward (`what`: the caller's words for the error) and materialised; sharded_msg: the refusal of
+        item-sharded tables by a caller that needs them whole on this rank. -> the device."""
+        dev = self._require_gpu()
+        self._plugin.realise_forward()
+        if self._ws is None or self._cache is None:
+            raise RuntimeError("%s the tables cached by a training forward (call bpr_loss or compute first)" % what)
+        self._ensure_tables()
+        if sharded_msg is not None and self.__dict__.get("_eval_shard") is not None:
+            raise CandidateScoringError(sharded_msg)
+        return dev
+
+    def _score_workspace(self, dev, B, top_k, topk_only):
+        """The scorer's workspace for B users (grow-only, kept in the model's workspace)."""
+        need = ops.score_workspace(B, self.num_users, self.num_items, self.S, top_k, topk_only=topk_only, d=self.latent_dim)
+        if self._ws.get("score_ws") is None or self._ws["score_ws"].numel() < need:
+            self._ws["score_ws"] = torch.empty(need, dtype=torch.uint8, device=dev)
+        return self._ws["score_ws"]
+
+    def _catalogue_row_sum(self, dev, users, predict_type, sqn):
+        """The scorer's pass 1 only, the whole catalogue as the one shard: sum_i sigmoid(u . i) per user (one launch)."""
+        I = self.num_items
+        row_sum = torch.empty(users.numel(), dtype=torch.float32, device=dev)
+        ops.score_topk_shard(self._ws["Y"], self.num_users, I, users, self.latent_dim, self.S, self._head_mask(), self.fusion_mode,
+                             predict_type, self._score_workspace(dev, users.numel(), 1, True), 1, row_sum, I, 0, sqnorm=sqn)
+        return row_sum
+
+    def _side_rows(self, side):
+        """(first row, number of rows) of the item rows (side "item") or the user rows ("user") in the cached Y."""
+        if side not in ("item", "user"):
+            raise ValueError("side must be 'item' or 'user', got %r" % (side,))
+        return (self.num_users, self.num_items) if side == "item" else (0, self.num_users)
+
     @torch.no_grad()
     def predict_device(self, user_ids, scores=None, top_k=0, train_ptr=None, train_items=None, tie_order="id"):
         """Device-side predict (+ optional train-item masking and top-K). Uses the tables cached
         by the LAST training forward, like the reference (:98-99). tie_order: the lists' order among equal
         scores -- "id" (lowest item id first) or "reference" (evaluate.h:26-33's partial_sort_copy, replayed on the device)."""
-        dev = self._require_gpu()
-        self._plugin.realise_forward()
-        if self._ws is None or self._cache is None:
-            raise RuntimeError("predict() needs the tables cached by a training forward (call bpr_loss or compute first)")
-        self._ensure_tables()
+        dev = self._cached_tables("predict() needs")
         users = torch.as_tensor(user_ids, device=dev).long().contiguous()
         B, I = users.numel(), self.num_items
         sh = self.__dict__.get("_eval_shard")
@@ -1153,18 +1183,14 @@ class EliMRec(BasicModel):
                 return sh.topk(users, top_k, train_ptr, train_items)
             return None, None
         # top-K only (the evaluator): no [B x I] score block in the workspace, the catalogue is scored in chunks
-        import os
-        chunked = scores is None and top_k > 0
-        need = ops.score_workspace(B, self.num_users, I, self.S, max(top_k, 1), topk_only=chunked, d=self.latent_dim)
-        if self._ws.get("score_ws") is None or self._ws["score_ws"].numel() < need:
-            self._ws["score_ws"] = torch.empty(need, dtype=torch.uint8, device=dev)
+        score_ws = self._score_workspace(dev, B, max(top_k, 1), scores is None and top_k > 0)
         idx = val = None
         if top_k:
             idx = torch.empty(B, top_k, dtype=torch.int32, device=dev)
             val = torch.empty(B, top_k, dtype=torch.float32, device=dev)
         self._block_sqnorms(dev)
         ops.score_topk(self._ws["Y"], self.num_users, I, users, self.latent_dim, self.S, self._head_mask(),
-                       self.fusion_mode, self.predict_type, self._ws["score_ws"], scores=scores, K=top_k,
+                       self.fusion_mode, self.predict_type, score_ws, scores=scores, K=top_k,
                        topk_idx=idx, topk_val=val, train_ptr=train_ptr, train_items=train_items, sqnorm=self._ws["sqn"],
                        tie_order=tie_order)
         return idx, val
@@ -1184,29 +1210,27 @@ class EliMRec(BasicModel):
         out [B x width] (float32, rows contiguous) = each user's candidate scores in list order, then -inf (csrc/eval.hip
         score_cand_kernel). Score of candidate (u, i) = predict([u])[0, i]; TIE's catalogue mean comes from the scorer's pass 1
         over the whole catalogue (one launch per call)."""
-        dev = self._require_gpu()
-        self._plugin.realise_forward()
-        if self._ws is None or self._cache is None:
-            raise RuntimeError("predict_candidates() needs the tables cached by a training forward (call bpr_loss or compute first)")
-        self._ensure_tables()
-        if self.__dict__.get("_eval_shard") is not None:
-            raise CandidateScoringError("candidate scoring needs the whole cached item table on this rank; the tables are item-sharded "
-                                        "(lean / multi-rank evaluation): score the full catalogue instead")
+        dev = self._cached_tables("predict_candidates() needs", "candidate scoring needs the whole cached item table on this rank; the "
+                                  "tables are item-sharded (lean / multi-rank evaluation): score the full catalogue instead")
         users = torch.as_tensor(user_ids, device=dev).long().contiguous()
-        B, I = users.numel(), self.num_items
+        I = self.num_items
         sqn = self._block_sqnorms(dev)
         row_sum = None
-        if ops.PREDICT_TYPES.get(self.predict_type, 0) == 2 and B:
-            # pass 1 only, the whole catalogue as the one shard: sum_i sigmoid(u . i) per user
-            need = ops.score_workspace(B, self.num_users, I, self.S, 1, topk_only=True, d=self.latent_dim)
-            if self._ws.get("score_ws") is None or self._ws["score_ws"].numel() < need:
-                self._ws["score_ws"] = torch.empty(need, dtype=torch.uint8, device=dev)
-            row_sum = torch.empty(B, dtype=torch.float32, device=dev)
-            ops.score_topk_shard(self._ws["Y"], self.num_users, I, users, self.latent_dim, self.S, self._head_mask(), self.fusion_mode,
-                                 self.predict_type, self._ws["score_ws"], 1, row_sum, I, 0, sqnorm=sqn)
+        if ops.PREDICT_TYPES.get(self.predict_type, 0) == 2 and users.numel():
+            row_sum = self._catalogue_row_sum(dev, users, self.predict_type, sqn)
         ops.score_candidates(self._ws["Y"], self.num_users, I, users, self.latent_dim, self.S, self._head_mask(), self.fusion_mode,
                              self.predict_type, cand_ptr, cand_items, out, sqnorm=sqn, row_sum=row_sum, I_total=I)
         return out
+
+    def _id_lists(self, lists, what, bound=None):
+        """One list of ids per row as CSR on the host, every id checked against [0, bound) (default: the catalogue):
+        (ptr int64, flat int64, lens) -- ops.ragged with this front's IndexError."""
+        bound = self.num_items if bound is None else bound
+        return ops.ragged(lists, check=(bound, "%s ids must lie in [0, %d)" % (what, bound)), cast=int)
+
+    def _excluded(self, exclude, ids, what, bound=None):
+        """`exclude` (dict id -> ids to leave out, or None) for the rows `ids`, checked: (ptr int64, flat int64)."""
+        return self._id_lists([(exclude or {}).get(int(i), []) for i in ids], "excluded " + what, bound)[:2]
 
     def predict_candidates(self, user_ids, candidate_items):
         """Scores of given candidate lists: CPU fp32 [len(user_ids) x longest list], row b = predict([u_b])[0, candidate_items[b]]
@@ -1214,14 +1238,8 @@ class EliMRec(BasicModel):
         dev = self._require_gpu()
         if len(candidate_items) != len(user_ids):
             raise ValueError("one candidate list per user: %d lists for %d users" % (len(candidate_items), len(user_ids)))
-        lens = np.fromiter((len(c) for c in candidate_items), dtype=np.int64, count=len(candidate_items))
-        ptr = np.zeros(len(lens) + 1, dtype=np.int64)
-        np.cumsum(lens, out=ptr[1:])
-        flat = np.fromiter((int(i) for c in candidate_items for i in c), dtype=np.int64, count=int(ptr[-1]))
-        if flat.size and (flat.min() < 0 or flat.max() >= self.num_items):
-            raise IndexError("candidate item ids must lie in [0, %d)" % self.num_items)
-        width = int(lens.max()) if lens.size else 0
-        out = torch.empty(len(user_ids), width, dtype=torch.float32, device=dev)
+        ptr, flat, lens = self._id_lists(candidate_items, "candidate item")
+        out = torch.empty(len(user_ids), int(lens.max()) if lens.size else 0, dtype=torch.float32, device=dev)
         self.predict_candidates_device(user_ids, torch.from_numpy(ptr).to(dev), torch.from_numpy(flat.astype(np.int32)).to(dev), out)
         return out.cpu()
 
@@ -1232,27 +1250,15 @@ class EliMRec(BasicModel):
         te, nde, the TE and TIE scores (the bits predict_candidates gives under either type) and every head's cosine; NaN beyond a
         list's length (csrc/eval.hip score_cand_kernel, FX form). The catalogue mean comes from the scorer's pass 1 over the whole
         catalogue whatever self.predict_type is (one launch per call)."""
-        dev = self._require_gpu()
-        self._plugin.realise_forward()
-        if self._ws is None or self._cache is None:
-            raise RuntimeError("explain() needs the tables cached by a training forward (call bpr_loss or compute first)")
-        self._ensure_tables()
-        if self.__dict__.get("_eval_shard") is not None:
-            raise CandidateScoringError("the effect breakdown needs the whole cached item table on this rank; the tables are "
-                                        "item-sharded (lean / multi-rank evaluation)")
+        dev = self._cached_tables("explain() needs", "the effect breakdown needs the whole cached item table on this rank; the tables "
+                                  "are item-sharded (lean / multi-rank evaluation)")
         users = torch.as_tensor(user_ids, device=dev).long().contiguous()
-        B, I = users.numel(), self.num_items
-        if not B:
+        if not users.numel():
             return out
         sqn = self._block_sqnorms(dev)
-        need = ops.score_workspace(B, self.num_users, I, self.S, 1, topk_only=True, d=self.latent_dim)
-        if self._ws.get("score_ws") is None or self._ws["score_ws"].numel() < need:
-            self._ws["score_ws"] = torch.empty(need, dtype=torch.uint8, device=dev)
-        row_sum = torch.empty(B, dtype=torch.float32, device=dev)
-        ops.score_topk_shard(self._ws["Y"], self.num_users, I, users, self.latent_dim, self.S, self._head_mask(), self.fusion_mode,
-                             "TIE", self._ws["score_ws"], 1, row_sum, I, 0, sqnorm=sqn)
-        ops.score_effects(self._ws["Y"], self.num_users, I, users, self.latent_dim, self.S, self._head_mask(), self.fusion_mode,
-                          cand_ptr, cand_items, out, sqn, row_sum, I)
+        row_sum = self._catalogue_row_sum(dev, users, "TIE", sqn)
+        ops.score_effects(self._ws["Y"], self.num_users, self.num_items, users, self.latent_dim, self.S, self._head_mask(),
+                          self.fusion_mode, cand_ptr, cand_items, out, sqn, row_sum, self.num_items)
         return out
 
     def explain(self, user_ids, candidate_items=None, top_k=None, exclude=None, tie_order="id"):
@@ -1269,29 +1275,16 @@ class EliMRec(BasicModel):
                 raise ValueError("exclude applies to top_k lists; candidate_items are taken as given")
             if len(candidate_items) != n:
                 raise ValueError("one candidate list per user: %d lists for %d users" % (len(candidate_items), n))
-            lens = np.fromiter((len(c) for c in candidate_items), dtype=np.int64, count=n)
-            ptr = np.zeros(n + 1, dtype=np.int64)
-            np.cumsum(lens, out=ptr[1:])
-            flat = np.fromiter((int(i) for c in candidate_items for i in c), dtype=np.int64, count=int(ptr[-1]))
-            if flat.size and (flat.min() < 0 or flat.max() >= self.num_items):
-                raise IndexError("candidate item ids must lie in [0, %d)" % self.num_items)
-            width = int(lens.max()) if n else 0
-            items = np.full((n, width), -1, dtype=np.int32)
-            items[np.arange(width)[None, :] < lens[:, None]] = flat
+            ptr, flat, lens = self._id_lists(candidate_items, "candidate item")
+            items = ops.ragged_padded(flat, lens)
             dev = self._require_gpu()
             cand_ptr, cand_items = torch.from_numpy(ptr).to(dev), torch.from_numpy(flat.astype(np.int32)).to(dev)
         else:
             top_k = int(top_k)
             if top_k < 1 or top_k > self.num_items:
                 raise ValueError("top_k must lie in [1, %d]" % self.num_items)
-            lists = [(exclude or {}).get(int(u), []) for u in user_ids]
-            tptr = np.zeros(n + 1, dtype=np.int64)
-            np.cumsum([len(x) for x in lists], out=tptr[1:])
-            tflat = np.fromiter((int(i) for x in lists for i in x), dtype=np.int64, count=int(tptr[-1]))
-            if tflat.size and (tflat.min() < 0 or tflat.max() >= self.num_items):
-                raise IndexError("excluded item ids must lie in [0, %d)" % self.num_items)
+            tptr, tflat = self._excluded(exclude, user_ids, "item")
             dev = self._require_gpu()
-            width = top_k
             if n:
                 idx, _ = self.predict_device(user_ids, top_k=top_k, train_ptr=torch.from_numpy(tptr).to(dev),
                                              train_items=torch.from_numpy(tflat.astype(np.int32)).to(dev), tie_order=tie_order)
@@ -1300,7 +1293,7 @@ class EliMRec(BasicModel):
             items = idx.cpu().numpy()
             cand_ptr = torch.arange(n + 1, dtype=torch.int64, device=dev) * top_k
             cand_items = idx.reshape(-1)
-        out = torch.empty(n, width, len(columns), dtype=torch.float32, device=dev)
+        out = torch.empty(n, items.shape[1], len(columns), dtype=torch.float32, device=dev)
         self.effects_device(user_ids, cand_ptr, cand_items, out)
         return Effects(columns, torch.from_numpy(np.ascontiguousarray(items)), out.cpu())
 
@@ -1313,16 +1306,11 @@ class EliMRec(BasicModel):
         predict_device call into a [B x I] block -- scored and masked as the evaluator's lists are -- then ops.rank_targets over
         that block (csrc/rank.hip). top_k > 0: idx / val [B x top_k] are the top-K lists selected from the same block by the same
         call (tie order "id"), so rank < top_k exactly for the listed targets; None otherwise."""
-        dev = self._require_gpu()
+        self._require_gpu()
         if not isinstance(tgt_index, ops.TargetIndex):
             raise TypeError("rank_items_device takes the targets as an ops.TargetIndex (checked on the host once)")
-        self._plugin.realise_forward()
-        if self._ws is None or self._cache is None:
-            raise RuntimeError("rank_items() needs the tables cached by a training forward (call bpr_loss or compute first)")
-        self._ensure_tables()
-        if self.__dict__.get("_eval_shard") is not None:
-            raise CandidateScoringError("exact ranks need the whole cached item table on this rank; the tables are item-sharded "
-                                        "(lean / multi-rank evaluation)")
+        dev = self._cached_tables("rank_items() needs", "exact ranks need the whole cached item table on this rank; the tables are "
+                                  "item-sharded (lean / multi-rank evaluation)")
         users = torch.as_tensor(user_ids, device=dev).long().contiguous()
         B, I = users.numel(), self.num_items
         if tgt_index.n_rows != B or tgt_index.n_items != I:
@@ -1346,27 +1334,15 @@ class EliMRec(BasicModel):
         n = len(user_ids)
         if len(items) != n:
             raise ValueError("one item list per user: %d lists for %d users" % (len(items), n))
-        lens = np.fromiter((len(c) for c in items), dtype=np.int64, count=n)
-        ptr = np.zeros(n + 1, dtype=np.int64)
-        np.cumsum(lens, out=ptr[1:])
-        flat = np.fromiter((int(i) for c in items for i in c), dtype=np.int64, count=int(ptr[-1]))
-        if flat.size and (flat.min() < 0 or flat.max() >= self.num_items):
-            raise IndexError("item ids must lie in [0, %d)" % self.num_items)
-        lists = [(exclude or {}).get(int(u), []) for u in user_ids]
-        tptr = np.zeros(n + 1, dtype=np.int64)
-        np.cumsum([len(x) for x in lists], out=tptr[1:])
-        tflat = np.fromiter((int(i) for x in lists for i in x), dtype=np.int64, count=int(tptr[-1]))
-        if tflat.size and (tflat.min() < 0 or tflat.max() >= self.num_items):
-            raise IndexError("excluded item ids must lie in [0, %d)" % self.num_items)
+        ptr, flat, lens = self._id_lists(items, "item")
+        tptr, tflat = self._excluded(exclude, user_ids, "item")
         dev = self._require_gpu()
-        width = int(lens.max()) if n else 0
-        out = np.full((n, width), -1, dtype=np.int32)
+        rank = np.zeros(0, dtype=np.int32)
         if flat.size:
             index = ops.TargetIndex(ptr, flat.astype(np.int32), n, self.num_items, dev)
             masked = (torch.from_numpy(tptr).to(dev), torch.from_numpy(tflat.astype(np.int32)).to(dev)) if tflat.size else (None, None)
-            rank, _, _ = self.rank_items_device(user_ids, index, *masked)
-            out[np.arange(width)[None, :] < lens[:, None]] = rank.cpu().numpy()
-        return torch.from_numpy(out)
+            rank = self.rank_items_device(user_ids, index, *masked)[0].cpu().numpy()
+        return torch.from_numpy(ops.ragged_padded(rank, lens))
 
     def _neighbour_space(self, space):
         """Head block of the cached Y a neighbour space names: 0 = the fused rows predict() scores with, 1 + h = head h."""
@@ -1384,20 +1360,12 @@ class EliMRec(BasicModel):
         (csrc/knn.hip). rows: the query ids (host array or tensor, checked on the host; the row itself is always left out) -- or
         query = an ops.NeighbourQuery over the side's rows, checked once, which may carry per-query exclusion lists. Tables as
         predict_device: those of the last training forward."""
-        dev = self._require_gpu()
-        if side not in ("item", "user"):
-            raise ValueError("side must be 'item' or 'user', got %r" % (side,))
+        self._require_gpu()
+        lo, n = self._side_rows(side)
         h = self._neighbour_space(space)
-        self._plugin.realise_forward()
-        if self._ws is None or self._cache is None:
-            raise RuntimeError("similar_items() / similar_users() need the tables cached by a training forward (call bpr_loss or "
-                               "compute first)")
-        self._ensure_tables()
-        if self.__dict__.get("_eval_shard") is not None:
-            raise CandidateScoringError("neighbour lists need the whole cached tables on this rank; the tables are item-sharded "
-                                        "(lean / multi-rank evaluation)")
-        U, d = self.num_users, self.latent_dim
-        lo, n = (U, self.num_items) if side == "item" else (0, U)
+        dev = self._cached_tables("similar_items() / similar_users() need", "neighbour lists need the whole cached tables on this rank; "
+                                  "the tables are item-sharded (lean / multi-rank evaluation)")
+        d = self.latent_dim
         sqn = self._block_sqnorms(dev)
         if query is None:
             query = ops.NeighbourQuery(rows, n, dev)
@@ -1416,15 +1384,8 @@ class EliMRec(BasicModel):
         if not 1 <= k <= ops.KNN_MAX_K:
             raise ValueError("k must lie in [1, %d]" % ops.KNN_MAX_K)
         self._neighbour_space(space)
-        ids = np.asarray([int(i) for i in ids], dtype=np.int64)
-        if ids.size and (ids.min() < 0 or ids.max() >= n_rows):
-            raise IndexError("%s ids must lie in [0, %d)" % (side, n_rows))
-        lists = [(exclude or {}).get(int(i), []) for i in ids]
-        ptr = np.zeros(ids.size + 1, dtype=np.int64)
-        np.cumsum([len(x) for x in lists], out=ptr[1:])
-        flat = np.fromiter((int(i) for x in lists for i in x), dtype=np.int64, count=int(ptr[-1]))
-        if flat.size and (flat.min() < 0 or flat.max() >= n_rows):
-            raise IndexError("excluded %s ids must lie in [0, %d)" % (side, n_rows))
+        ids = self._id_lists([ids], side, n_rows)[1]
+        ptr, flat = self._excluded(exclude, ids, side, n_rows)
         dev = self._require_gpu()
         idx = torch.empty(ids.size, k, dtype=torch.int32, device=dev)
         val = torch.empty(ids.size, k, dtype=torch.float32, device=dev)
@@ -1450,18 +1411,11 @@ class EliMRec(BasicModel):
         lists int32 [B x K] on the device, 1 <= K <= ops.LIST_MAX_K; an entry outside the side's rows (-1 fillers) is not listed,
         duplicates are pairs. out float32 [B x (1 + S)] on the device: column 0 = the fused rows predict() scores with, column
         1 + h = head self._mods[h]; NaN where fewer than two entries are listed. Tables as neighbours_device."""
-        dev = self._require_gpu()
-        if side not in ("item", "user"):
-            raise ValueError("side must be 'item' or 'user', got %r" % (side,))
-        self._plugin.realise_forward()
-        if self._ws is None or self._cache is None:
-            raise RuntimeError("list_similarity() needs the tables cached by a training forward (call bpr_loss or compute first)")
-        self._ensure_tables()
-        if self.__dict__.get("_eval_shard") is not None:
-            raise CandidateScoringError("list similarity needs the whole cached tables on this rank; the tables are item-sharded "
-                                        "(lean / multi-rank evaluation)")
-        U, d, nb = self.num_users, self.latent_dim, 1 + self.S
-        lo, n = (U, self.num_items) if side == "item" else (0, U)
+        self._require_gpu()
+        lo, n = self._side_rows(side)
+        dev = self._cached_tables("list_similarity() needs", "list similarity needs the whole cached tables on this rank; the tables "
+                                  "are item-sharded (lean / multi-rank evaluation)")
+        d, nb = self.latent_dim, 1 + self.S
         sqn = self._block_sqnorms(dev)
         ops.list_pair_cosine(self._ws["Y"][lo:lo + n, :nb * d], sqn[lo:lo + n], lists, out, blocks=nb)
         return out
@@ -1476,15 +1430,10 @@ class EliMRec(BasicModel):
         K = max([len(x) for x in lists] + [1])
         if K > ops.LIST_MAX_K:
             raise ValueError("a list may hold at most %d items, got %d" % (ops.LIST_MAX_K, K))
-        padded = np.full((len(lists), K), -1, dtype=np.int32)
-        for b, x in enumerate(lists):
-            padded[b, :len(x)] = x
-        listed = np.arange(K)[None, :] < np.asarray([len(x) for x in lists], dtype=np.int64).reshape(-1, 1)
-        if listed.any() and (padded[listed].min() < 0 or padded[listed].max() >= self.num_items):
-            raise IndexError("item ids must lie in [0, %d)" % self.num_items)
+        _, flat, lens = ops.ragged(lists, dtype=np.int32, check=(self.num_items, "item ids must lie in [0, %d)" % self.num_items))
         dev = self._require_gpu()
         out = torch.empty(len(lists), 1 + self.S, dtype=torch.float32, device=dev)
-        self.list_similarity_device(torch.from_numpy(padded).to(dev), out, side="item")
+        self.list_similarity_device(torch.from_numpy(ops.ragged_padded(flat, lens, K)).to(dev), out, side="item")
         out = out.cpu()
         return out if h is None else out[:, h].contiguous()
 

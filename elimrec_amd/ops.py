@@ -738,32 +738,95 @@ def rank_metrics(topk_idx, truth_ptr, truth_items, metric_ids, out):
     return out
 
 
+class CandidateScoringError(ValueError):
+    """A candidate-list (sampled-negative) evaluation or scoring call this package does not run: item-sharded / lean tables,
+    or a top-K beyond the shortest candidate list."""
+
+
 class GroupIndex(object):
     """Groups of rows as CSR (group_ptr [G + 1], group_rows: row indices into a block of n_rows rows), CHECKED ON THE HOST --
     ptr[0] = 0, ascending, ptr[G] = len(group_rows), every index in [0, n_rows) -- and then resident on `device`:
     group_metric_means takes it as is, call after call, and no unchecked index ever reaches a kernel."""
 
     def __init__(self, group_ptr, group_rows, n_rows, device):
-        ptr = np.ascontiguousarray(_host(group_ptr), dtype=np.int64).reshape(-1)
-        rows = _host(group_rows).reshape(-1)
-        if ptr.size < 2:
-            raise ValueError("elimrec_amd.ops.GroupIndex: group_ptr needs G + 1 >= 2 entries")
-        if rows.size and not np.issubdtype(rows.dtype, np.integer):
-            raise TypeError("elimrec_amd.ops.GroupIndex: group_rows must hold integers, got %s" % rows.dtype)
-        if ptr[0] != 0 or ptr[-1] != rows.size or (np.diff(ptr) < 0).any():
-            raise ValueError("elimrec_amd.ops.GroupIndex: group_ptr must ascend from 0 to len(group_rows) = %d" % rows.size)
-        if rows.size and (int(rows.min()) < 0 or int(rows.max()) >= int(n_rows)):
-            raise IndexError("elimrec_amd.ops.GroupIndex: row indices span [%d, %d], the block has %d rows"
-                             % (int(rows.min()), int(rows.max()), int(n_rows)))
+        ptr, rows = _checked_csr(group_ptr, group_rows, None, n_rows, "GroupIndex",
+                                 ("group_ptr", "group_rows", "G", "row indices span [%d, %d], the block has %d rows"))
         self.n_rows, self.n_groups, self.n_listed = int(n_rows), int(ptr.size - 1), int(rows.size)
         self.sizes = np.diff(ptr)
         self.ptr = torch.from_numpy(ptr).to(device)
-        # (never empty: the kernels read nothing of it when n_listed = 0, the binding still wants a device tensor)
-        self.rows = torch.from_numpy(np.ascontiguousarray(rows if rows.size else np.zeros(1), dtype=np.int32)).to(device)
+        self.rows = _resident_ids(rows, device)
 
 
 def _host(x):
     return x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+
+
+def _checked_ids(ids, bound, who, name, span):
+    """Host array of ids (flat): an integer dtype, every id in [0, bound). span: the IndexError's words, %% (min, max, bound)."""
+    ids = _host(ids).reshape(-1)
+    _integer_ids(ids, who, name)
+    _ids_in_range(ids, bound, who, span)
+    return ids
+
+
+def _integer_ids(ids, who, name):
+    if ids.size and not np.issubdtype(ids.dtype, np.integer):
+        raise TypeError("elimrec_amd.ops.%s: %s must hold integers, got %s" % (who, name, ids.dtype))
+
+
+def _ids_in_range(ids, bound, who, span):
+    if ids.size and (int(ids.min()) < 0 or int(ids.max()) >= int(bound)):
+        raise IndexError("elimrec_amd.ops.%s: " % who + span % (int(ids.min()), int(ids.max()), int(bound)))
+
+
+def _checked_csr(ptr, ids, n_lists, bound, who, names):
+    """The host checks of a CSR of ids, in this order: entry count of ptr (n_lists + 1; n_lists = None: any number of lists >= 1),
+    integer ids, ptr ascending from 0 to len(ids), every id in [0, bound). names = (ptr's name, ids' name, the letter of the list
+    count, the range error's words). -> (ptr int64, ids) as flat host arrays."""
+    ptr_name, ids_name, letter, span = names
+    p = np.ascontiguousarray(_host(ptr), dtype=np.int64).reshape(-1)
+    ids = _host(ids).reshape(-1)
+    if n_lists is None:
+        if p.size < 2:
+            raise ValueError("elimrec_amd.ops.%s: %s needs %s + 1 >= 2 entries" % (who, ptr_name, letter))
+    elif p.size != int(n_lists) + 1:
+        raise ValueError("elimrec_amd.ops.%s: %s needs %s + 1 = %d entries, got %d" % (who, ptr_name, letter, int(n_lists) + 1, p.size))
+    _integer_ids(ids, who, ids_name)
+    if p[0] != 0 or p[-1] != ids.size or (np.diff(p) < 0).any():
+        raise ValueError("elimrec_amd.ops.%s: %s must ascend from 0 to len(%s) = %d" % (who, ptr_name, ids_name, ids.size))
+    _ids_in_range(ids, bound, who, span)
+    return p, ids
+
+
+def _resident_ids(ids, device):
+    """Checked ids as an int32 device tensor (never empty: the kernels read nothing of it when there are no ids, the binding still
+    wants a device tensor)."""
+    return torch.from_numpy(np.ascontiguousarray(ids if ids.size else np.zeros(1), dtype=np.int32)).to(device)
+
+
+def ragged(lists, dtype=np.int64, check=None, cast=None):
+    """A list of lists (or of arrays) of ids as CSR on the host: (ptr int64 [n + 1], flat ids of `dtype` in list order, lens int64 [n]). cast:
+    applied to every id before it is stored (int: a Python integer beyond `dtype` raises OverflowError instead of wrapping).
+    check = (bound, message): every id must lie in [0, bound), else IndexError(message); None: nothing is checked."""
+    lens = np.fromiter((len(x) for x in lists), dtype=np.int64, count=len(lists))
+    ptr = np.zeros(len(lists) + 1, dtype=np.int64)
+    np.cumsum(lens, out=ptr[1:])
+    if cast is None and len(lists) and all(isinstance(x, np.ndarray) for x in lists):
+        flat = np.concatenate(lists).astype(dtype)
+    else:
+        ids = (i for x in lists for i in x) if cast is None else (cast(i) for x in lists for i in x)
+        flat = np.fromiter(ids, dtype=dtype, count=int(ptr[-1]))
+    if check is not None and flat.size and (flat.min() < 0 or flat.max() >= check[0]):
+        raise IndexError(check[1])
+    return ptr, flat, lens
+
+
+def ragged_padded(flat, lens, width=None, dtype=np.int32):
+    """ragged()'s ids as [n x width] rows of `dtype` (width default: the longest list), -1 beyond each list's length."""
+    width = (int(lens.max()) if lens.size else 0) if width is None else int(width)
+    out = np.full((lens.size, width), -1, dtype=dtype)
+    out[np.arange(width)[None, :] < lens[:, None]] = flat
+    return out
 
 
 def group_metric_means(rows, group_ptr, group_rows, out, workspace=None):
@@ -803,22 +866,11 @@ class TargetIndex(object):
     it as is, call after call, and no unchecked id ever reaches a kernel (the counterpart of GroupIndex)."""
 
     def __init__(self, ptr, items, B, I, device):
-        p = np.ascontiguousarray(_host(ptr), dtype=np.int64).reshape(-1)
-        it = _host(items).reshape(-1)
-        if p.size != int(B) + 1:
-            raise ValueError("elimrec_amd.ops.TargetIndex: ptr needs B + 1 = %d entries, got %d" % (int(B) + 1, p.size))
-        if it.size and not np.issubdtype(it.dtype, np.integer):
-            raise TypeError("elimrec_amd.ops.TargetIndex: items must hold integers, got %s" % it.dtype)
-        if p[0] != 0 or p[-1] != it.size or (np.diff(p) < 0).any():
-            raise ValueError("elimrec_amd.ops.TargetIndex: ptr must ascend from 0 to len(items) = %d" % it.size)
-        if it.size and (int(it.min()) < 0 or int(it.max()) >= int(I)):
-            raise IndexError("elimrec_amd.ops.TargetIndex: item ids span [%d, %d], the catalogue has %d items"
-                             % (int(it.min()), int(it.max()), int(I)))
+        p, it = _checked_csr(ptr, items, B, I, "TargetIndex", ("ptr", "items", "B", "item ids span [%d, %d], the catalogue has %d items"))
         self.n_rows, self.n_items, self.n_targets = int(B), int(I), int(it.size)
         self.sizes = np.diff(p)
         self.ptr = torch.from_numpy(p).to(device)
-        # (never empty: the kernels read nothing of it when n_targets = 0, the binding still wants a device tensor)
-        self.items = torch.from_numpy(np.ascontiguousarray(it if it.size else np.zeros(1), dtype=np.int32)).to(device)
+        self.items = _resident_ids(it, device)
 
 
 def rank_targets(scores, tgt_ptr, tgt_items, out):
@@ -1107,31 +1159,17 @@ class NeighbourQuery(object):
     ever reaches a kernel (the counterpart of TargetIndex). Exclusion lists may repeat ids, in any order, and may be empty."""
 
     def __init__(self, rows, n_rows, device, excl_ptr=None, excl_rows=None):
-        q = _host(rows).reshape(-1)
-        if q.size and not np.issubdtype(q.dtype, np.integer):
-            raise TypeError("elimrec_amd.ops.NeighbourQuery: rows must hold integers, got %s" % q.dtype)
-        if q.size and (int(q.min()) < 0 or int(q.max()) >= int(n_rows)):
-            raise IndexError("elimrec_amd.ops.NeighbourQuery: query rows span [%d, %d], the table has %d rows"
-                             % (int(q.min()), int(q.max()), int(n_rows)))
+        q = _checked_ids(rows, n_rows, "NeighbourQuery", "rows", "query rows span [%d, %d], the table has %d rows")
         if (excl_ptr is None) != (excl_rows is None):
             raise ValueError("elimrec_amd.ops.NeighbourQuery: the exclusion CSR needs excl_ptr and excl_rows, or neither")
         self.n_rows, self.n_queries = int(n_rows), int(q.size)
-        self.rows = torch.from_numpy(np.ascontiguousarray(q if q.size else np.zeros(1), dtype=np.int32)).to(device)
+        self.rows = _resident_ids(q, device)
         self.excl_ptr = self.excl_rows = None
         if excl_ptr is not None:
-            p = np.ascontiguousarray(_host(excl_ptr), dtype=np.int64).reshape(-1)
-            e = _host(excl_rows).reshape(-1)
-            if p.size != q.size + 1:
-                raise ValueError("elimrec_amd.ops.NeighbourQuery: excl_ptr needs Q + 1 = %d entries, got %d" % (q.size + 1, p.size))
-            if e.size and not np.issubdtype(e.dtype, np.integer):
-                raise TypeError("elimrec_amd.ops.NeighbourQuery: excl_rows must hold integers, got %s" % e.dtype)
-            if p[0] != 0 or p[-1] != e.size or (np.diff(p) < 0).any():
-                raise ValueError("elimrec_amd.ops.NeighbourQuery: excl_ptr must ascend from 0 to len(excl_rows) = %d" % e.size)
-            if e.size and (int(e.min()) < 0 or int(e.max()) >= int(n_rows)):
-                raise IndexError("elimrec_amd.ops.NeighbourQuery: excluded rows span [%d, %d], the table has %d rows"
-                                 % (int(e.min()), int(e.max()), int(n_rows)))
+            p, e = _checked_csr(excl_ptr, excl_rows, q.size, n_rows, "NeighbourQuery",
+                                ("excl_ptr", "excl_rows", "Q", "excluded rows span [%d, %d], the table has %d rows"))
             self.excl_ptr = torch.from_numpy(p).to(device)
-            self.excl_rows = torch.from_numpy(np.ascontiguousarray(e if e.size else np.zeros(1), dtype=np.int32)).to(device)
+            self.excl_rows = _resident_ids(e, device)
 
 
 def cosine_topk_workspace(Q, n_rows, K):
@@ -1139,16 +1177,18 @@ def cosine_topk_workspace(Q, n_rows, K):
     return int(_lib.load().elimrec_cosine_topk_workspace(int(Q), int(n_rows), int(K)))
 
 
-def _knn_out(t, name, dtype, Q, K):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+def _rows_out(t, name, dtype, B, K, who, device=None):
+    """Device pointer of an output of B rows of K entries: `dtype`, contiguous, [>= B x K] or 1-D with at least B * K entries
+    (device: and on that device, the table's)."""
+    if t is None:
         raise RuntimeError("elimrec_amd.ops: '%s' must be a HIP device tensor (the hot path has no CPU implementation)" % name)
-    if t.dtype != dtype:
-        raise TypeError("elimrec_amd.ops: '%s' must be %s, got %s" % (name, dtype, t.dtype))
-    ok = t.is_contiguous() and ((t.dim() == 2 and t.shape[1] == K and t.shape[0] >= Q) or (t.dim() == 1 and t.numel() >= Q * K))
+    p = _dev(t, name, dtype)
+    ok = t.is_contiguous() and (device is None or t.device == device) and (
+        (t.dim() == 2 and t.shape[1] == K and t.shape[0] >= B) or (t.dim() == 1 and t.numel() >= B * K))
     if not ok:
-        raise ValueError("elimrec_amd.ops.cosine_topk: %s must be contiguous, [>= %d x %d] or 1-D with at least %d entries"
-                         % (name, Q, K, Q * K))
-    return t.data_ptr()
+        raise ValueError("elimrec_amd.ops.%s: %s must be contiguous%s, [>= %d x %d] or 1-D with at least %d entries"
+                         % (who, name, "" if device is None else " on the table's device", B, K, B * K))
+    return p
 
 
 def cosine_topk(table, sqnorm, query_rows, K, out_idx, out_val=None, exclude_self=True, excl_ptr=None, excl_rows=None,
@@ -1184,8 +1224,8 @@ def cosine_topk(table, sqnorm, query_rows, K, out_idx, out_val=None, exclude_sel
     else:
         query = NeighbourQuery(query_rows, n, table.device, excl_ptr, excl_rows)
     Q = query.n_queries
-    ip = _knn_out(out_idx, "out_idx", torch.int32, Q, K)
-    vp = _knn_out(out_val, "out_val", torch.float32, Q, K) if out_val is not None else None
+    ip = _rows_out(out_idx, "out_idx", torch.int32, Q, K, "cosine_topk")
+    vp = _rows_out(out_val, "out_val", torch.float32, Q, K, "cosine_topk") if out_val is not None else None
     lib = _lib.load()
     need = int(lib.elimrec_cosine_topk_workspace(Q, n, K))
     if workspace is None:
@@ -1277,12 +1317,7 @@ def list_pair_cosine(table, sqnorm, lists, out, blocks=1):
     B, K = lists.shape
     if not 1 <= K <= LIST_MAX_K:
         raise ValueError("elimrec_amd.ops.list_pair_cosine: 1 <= K <= %d, got %d" % (LIST_MAX_K, K))
-    op = _dev(out, "out")
-    ok = out.is_contiguous() and out.device == table.device and (
-        (out.dim() == 2 and out.shape[1] == blocks and out.shape[0] >= B) or (out.dim() == 1 and out.numel() >= B * blocks))
-    if not ok:
-        raise ValueError("elimrec_amd.ops.list_pair_cosine: out must be contiguous on the table's device, [>= %d x %d] or 1-D with at "
-                         "least %d entries" % (B, blocks, B * blocks))
+    op = _rows_out(out, "out", torch.float32, B, blocks, "list_pair_cosine", device=table.device)
     if B == 0:
         return out
     _lib.check(_lib.load().elimrec_list_pair_cosine(tp, ld, n, blocks, d, sp, ld_sq, lp, B, K, op, _stream()), "list_pair_cosine")

@@ -1,0 +1,539 @@
+"""The reports over the cached tables -- what the lists are made of (EffectReport), where the held-out items stand (RankReport),
+whose neighbourhood the fused space copies (NeighbourReport), the lists themselves (ListReport) -- and what they share: the user /
+item groups, the groups as a checked index on the device, the group means, the table format, the model preflight and the block-wise
+top-K lists. The rows come from the model's *_device readers (model.py), the means from ops.group_metric_means."""
+import collections
+
+import numpy as np
+import torch
+
+from . import ops
+from .data_iterator import DataIterator
+from .ops import CandidateScoringError
+
+ALL = "all:".ljust(12)
+
+
+def assign_user_groups(test_users, user_train_dict, group_view):
+    """The reference's user groups (evaluator/grouped_evaluator.py:63-80) without pandas: bounds [0] + group_view, a test user's
+    group is np.searchsorted(group_view, n_train) -- n_train in (lo, hi], so a user without training items lands in the first
+    group -- users beyond the last bound are discarded, groups without users are omitted; groups in ascending order of their
+    bounds, a group's users in the order of `test_users`.
+    -> (labels ["(lo,hi]:".ljust(12)], positions [int64 arrays of indices into test_users], number of discarded users)."""
+    if not isinstance(group_view, list):
+        raise TypeError("The type of 'group_view' must be `list`!")
+    for b in group_view:
+        if isinstance(b, bool) or not isinstance(b, (int, np.integer)) or b <= 0:
+            raise ValueError("group_view must hold strictly ascending positive integers, got %r" % (group_view,))
+    if any(hi <= lo for lo, hi in zip(group_view[:-1], group_view[1:])):
+        raise ValueError("group_view must hold strictly ascending positive integers, got %r" % (group_view,))
+    bounds = [0] + [int(b) for b in group_view]
+    n_train = np.fromiter((len(user_train_dict.get(u, [])) for u in test_users), dtype=np.int64, count=len(test_users))
+    group = np.searchsorted(np.asarray(bounds[1:], dtype=np.int64), n_train)
+    labels, positions = [], []
+    for g in range(len(group_view)):
+        at = np.flatnonzero(group == g)
+        if at.size:
+            labels.append(("(%d,%d]:" % (bounds[g], bounds[g + 1])).ljust(12))
+            positions.append(at.astype(np.int64))
+    if not labels:
+        raise ValueError("The splitting of user groups is not suitable!")
+    return labels, positions, int((group >= len(group_view)).sum())
+
+
+def assign_item_groups(item_ids, train_item_counts, item_group_view):
+    """Items bucketed by popularity, the counterpart of assign_user_groups: item_group_view = [b1..bn] (strictly ascending
+    positive integers) gives `cold` (0 training interactions), (0,b1], ..., (b(n-1),bn] and the open (bn,inf); an entry of
+    item_ids lands in the bucket of train_item_counts[its id]. Groups without entries are omitted; groups in that order, a
+    group's entries in the order of item_ids.
+    -> (labels ["cold:" / "(lo,hi]:" / "(bn,inf):", each .ljust(12)], positions [int64 arrays of indices into item_ids])."""
+    if not isinstance(item_group_view, list) or not item_group_view:
+        raise TypeError("The type of 'item_group_view' must be a non-empty `list`!")
+    for b in item_group_view:
+        if isinstance(b, bool) or not isinstance(b, (int, np.integer)) or b <= 0:
+            raise ValueError("item_group_view must hold strictly ascending positive integers, got %r" % (item_group_view,))
+    if any(hi <= lo for lo, hi in zip(item_group_view[:-1], item_group_view[1:])):
+        raise ValueError("item_group_view must hold strictly ascending positive integers, got %r" % (item_group_view,))
+    bounds = [int(b) for b in item_group_view]
+    ids = np.asarray(item_ids, dtype=np.int64).reshape(-1)
+    counts = np.asarray(train_item_counts, dtype=np.int64).reshape(-1)
+    if ids.size and (ids.min() < 0 or ids.max() >= counts.size):
+        raise IndexError("item ids must lie in [0, %d)" % counts.size)
+    n = counts[ids]
+    # 0 = cold, 1 + g = (bounds[g - 1], bounds[g]] (count in (lo, hi], as the user groups), 1 + len(bounds) = beyond the last bound
+    group = np.where(n == 0, 0, 1 + np.searchsorted(np.asarray(bounds, dtype=np.int64), n))
+    names = ["cold:"] + ["(%d,%d]:" % (lo, hi) for lo, hi in zip([0] + bounds[:-1], bounds)] + ["(%d,inf):" % bounds[-1]]
+    labels, positions = [], []
+    for g, name in enumerate(names):
+        at = np.flatnonzero(group == g)
+        if at.size:
+            labels.append(name.ljust(12))
+            positions.append(at.astype(np.int64))
+    return labels, positions
+
+
+def item_train_counts(user_train_dict, num_items):
+    """Training interactions per item: int64 [num_items] (an item listed twice by one user counts twice)."""
+    counts = np.zeros(num_items, dtype=np.int64)
+    for items in user_train_dict.values():
+        np.add.at(counts, np.asarray(list(items), dtype=np.int64), 1)
+    return counts
+
+
+def lists_csr(keys, table, device, unique=False, cast=None):
+    """table[k] (missing: empty) of every key as CSR on the device: (ptr int64 [n + 1], ids int32, unchecked); unique: each list's
+    distinct ids in ascending order; cast: ops.ragged's."""
+    lists = [sorted(set(table.get(k, []))) if unique else table.get(k, []) for k in keys]
+    ptr, flat, _ = ops.ragged(lists, dtype=np.int32, cast=cast)
+    return torch.from_numpy(ptr).to(device), torch.from_numpy(flat).to(device)
+
+
+def group_index(positions, n_rows, device):
+    """Groups given as arrays of row positions into a block of n_rows rows -> the checked ops.GroupIndex resident on `device`."""
+    ptr, rows, _ = ops.ragged(positions, dtype=np.int32)
+    return ops.GroupIndex(ptr, rows, n_rows, device)
+
+
+def group_table(rows, index, n_groups):
+    """Device rows [n x C] -> host float32 [n_groups x C]: the groups' column means (ops.group_metric_means)."""
+    out = torch.empty(n_groups, rows.shape[1], dtype=torch.float32, device=rows.device)
+    return ops.group_metric_means(rows, index, None, out).cpu().numpy()
+
+
+def format_rows(labels, table):
+    """One "\\n<label>\\t<%.8f values>" line per row (the reference's grouped_evaluator.py:107-112)."""
+    return "".join("\n%s\t%s" % (label, "\t".join(("%.8f" % x).ljust(12) for x in row)) for label, row in zip(labels, table))
+
+
+def format_table(columns, labels, table):
+    """A header of column names and format_rows' lines."""
+    return "columns:\t%s" % "\t".join(str(c).ljust(12) for c in columns) + format_rows(labels, table)
+
+
+class _Report(object):
+    """What the reports share. A subclass names itself (`name`: its word in the messages and its --<name>_report switch), the model
+    method it needs (`needs`), sets num_items / top_k where the model has to match them, and builds what it keeps on a device in
+    _make_resident(device)."""
+    name = needs = num_items = top_k = None
+    block_users, tie_order = 8192, "id"
+
+    def _user_groups(self, users, user_train_dict, group_view):
+        """("all:" + the group_view groups' labels, their positions into `users`); sets num_discarded when there is a view."""
+        labels, positions = [ALL], [np.arange(len(users), dtype=np.int64)]
+        if group_view is not None:
+            more, at, self.num_discarded = assign_user_groups(users, user_train_dict, group_view)
+            labels, positions = labels + more, positions + at
+        return labels, positions
+
+    def _item_groups(self, item_ids, item_counts, item_group_view, prefix=""):
+        """The same over item_ids by popularity (assign_item_groups), the groups' labels prefixed."""
+        labels, positions = [ALL], [np.arange(len(item_ids), dtype=np.int64)]
+        if item_group_view is not None:
+            more, at = assign_item_groups(item_ids, item_counts, item_group_view)
+            labels, positions = labels + [(prefix + x.strip()).ljust(12) if prefix else x for x in more], positions + at
+        return labels, positions
+
+    def _resident(self, device):
+        """What the report keeps on `device` (_make_resident), built once per device."""
+        hit = self.__dict__.setdefault("_device", {}).get(str(device))
+        if hit is None:
+            hit = self._device[str(device)] = self._make_resident(device)
+        return hit
+
+    def _preflight(self, model):
+        """The model can serve this report: it has the reader, its tables are whole on this rank and of the report's catalogue.
+        -> the device."""
+        if not hasattr(model, self.needs):
+            raise TypeError("model must expose %s()" % self.needs)
+        if hasattr(model, "_ensure_tables") and getattr(model, "_cache", None) is not None:
+            model._ensure_tables()
+        if getattr(model, "_eval_shard", None) is not None:
+            raise CandidateScoringError("the %s report needs the whole cached item table on this rank; the tables are "
+                                        "item-sharded (lean / multi-rank evaluation): run without --%s_report" % (self.name, self.name))
+        if self.num_items is not None and model.num_items != self.num_items:
+            raise ValueError("the report was built for %d items, the model has %d" % (self.num_items, model.num_items))
+        if self.top_k is not None and self.top_k > model.num_items:
+            raise CandidateScoringError("%s report of the top-%d lists: the catalogue has %d items" % (self.name, self.top_k, model.num_items))
+        return model._require_gpu()
+
+    def top_lists(self, model, users, K, block_users, tie_order):
+        """The users' top-K lists under the model's current predict type with their train items masked, in blocks of block_users:
+        yields (a, b, users [b - a] int64, lists [b - a x K] int32) per block, on the device."""
+        device = model._require_gpu()
+        a = 0
+        for batch_users in DataIterator(users, batch_size=block_users, shuffle=False, drop_last=False):
+            train_ptr, train_items = lists_csr(batch_users, self.user_pos_train, device)
+            users_t = torch.as_tensor(np.asarray(batch_users, dtype=np.int64)).to(device)
+            idx, _ = model.predict_device(users_t, top_k=K, train_ptr=train_ptr, train_items=train_items, tie_order=tie_order)
+            yield a, a + len(batch_users), users_t, idx
+            a += len(batch_users)
+
+
+class EffectReport(_Report):
+    """What the test users' top-K lists are made of (--effect_report=K): per (user, rank <= K) pair the effect breakdown of
+    EliMRec.effects_device -- ui, its catalogue mean, te, nde, the TE / TIE scores, the heads' cosines -- and its column means
+    over all pairs and, with group_view, per user group (assign_user_groups). The lists are the model's top-K under its current
+    predict type with train items masked, in user blocks as metric_rows takes them; the means are ops.group_metric_means over
+    the [users*K x C] block (float64 sums, the segments = rows of that block): only [1 + groups x C] floats reach the host."""
+
+    name, needs = "effect", "effects_device"
+
+    def __init__(self, dataset, user_train_dict, user_test_dict, top_k, group_view=None):
+        if not isinstance(user_train_dict, dict) or not isinstance(user_test_dict, dict):
+            raise TypeError("user_train_dict and user_test_dict must be dicts")
+        if isinstance(top_k, bool) or not isinstance(top_k, (int, np.integer)) or top_k < 1:
+            raise ValueError("top_k must be a positive integer, got %r" % (top_k,))
+        self.dataset = dataset
+        self.user_pos_train = user_train_dict
+        self.user_pos_test = user_test_dict
+        self.top_k = int(top_k)
+        self.users = list(user_test_dict.keys())
+        self.group_labels, self._positions = self._user_groups(self.users, user_train_dict, group_view)
+
+    def _make_resident(self, device):
+        """The groups over the rows of the [users*K x C] block: user position p holds rows p K .. p K + K - 1."""
+        K = self.top_k
+        rows = [(p[:, None] * K + np.arange(K, dtype=np.int64)[None, :]).reshape(-1) for p in self._positions]
+        return group_index(rows, len(self.users) * K, device)
+
+    def _group_index(self, device):
+        return self._resident(device)
+
+    def effect_rows(self, model):
+        """The breakdown of every test user's top-K list on the device: ([users*K x C] float32, column names)."""
+        device = self._preflight(model)
+        columns = ops.effect_columns(model._mods)
+        K, C = self.top_k, len(columns)
+        rows = torch.empty(len(self.users) * K, C, dtype=torch.float32, device=device)
+        for a, b, users_t, idx in self.top_lists(model, self.users, K, self.block_users, self.tie_order):
+            cand_ptr = torch.arange(b - a + 1, dtype=torch.int64, device=device) * K
+            model.effects_device(users_t, cand_ptr, idx.reshape(-1), rows[a * K:b * K].view(b - a, K, C))
+        return rows, columns
+
+    def evaluate(self, model):
+        """(final [1 + groups x C] float32: row 0 = all pairs, then one row per user group; buf: a header of column names and
+        one line per row in the grouped evaluator's format)."""
+        rows, columns = self.effect_rows(model)
+        final = group_table(rows, self._group_index(rows.device), len(self.group_labels))
+        return final, format_table(columns, self.group_labels, final)
+
+
+RankTables = collections.namedtuple("RankTables", ("pair_columns", "pair_labels", "pairs", "user_columns", "user_labels", "users"))
+
+
+class RankReport(_Report):
+    """Where the held-out items stand in the FULL ranking (--rank_report=1): every (test user, test item) pair's exact catalogue
+    rank under the model's current predict type with the train items masked (EliMRec.rank_items_device: the evaluator's scoring
+    call into a score block, then csrc/rank.hip's count over it), and from the ranks
+      per pair: rank, rr = 1 / (rank + 1), pct = rank / (candidates - 1), hit@K for every K of top_k;
+      per user: auc, mrr_full = 1 / (first_rank + 1), first_rank = the best rank among the user's test items
+    as means over all pairs / users, per user group (group_view, assign_user_groups) and -- pair columns -- per item popularity
+    group (item_group_view, assign_item_groups over the items' training interactions). The pair means are MICRO-averages: every
+    pair weighs the same, so a user with many test items weighs more, and hit@K here is NOT the evaluator's per-user recall
+    (a mean of per-user ratios). Ranks order equal scores by item id whatever the evaluator's tie_order is.
+    Pairs are all (user, item) of user_test_dict in dict order; a pair whose item is also in the user's train list is dropped
+    (num_dropped), then a user without a pair or without a candidate besides its test items (num_skipped_users). Users go in
+    blocks whose [users x items] score block stays within block_bytes; the row and mean kernels leave only the tables to the host."""
+
+    name, needs = "rank", "rank_items_device"
+
+    def __init__(self, dataset, user_train_dict, user_test_dict, top_k, group_view=None, item_group_view=None):
+        if not isinstance(user_train_dict, dict) or not isinstance(user_test_dict, dict):
+            raise TypeError("user_train_dict and user_test_dict must be dicts")
+        ks = [top_k] if isinstance(top_k, (int, np.integer)) and not isinstance(top_k, bool) else list(top_k)
+        if not ks or any(isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1 for k in ks):
+            raise ValueError("top_k must be a positive integer or a list of them, got %r" % (top_k,))
+        self.dataset = dataset
+        self.num_items = I = int(dataset.num_items)
+        self.user_pos_train = user_train_dict
+        self.user_pos_test = user_test_dict
+        self.ks = [int(k) for k in ks]
+        self.block_bytes = 2 << 30
+        self.num_dropped = self.num_skipped_users = 0
+        self.users, pair_items, lens, n_cand = [], [], [], []
+        for u, test_items in user_test_dict.items():
+            seen = set(int(i) for i in user_train_dict.get(u, []))
+            kept = [int(i) for i in test_items if int(i) not in seen]
+            self.num_dropped += len(test_items) - len(kept)
+            if not kept or I - len(seen) - len(kept) <= 0:
+                self.num_skipped_users += 1
+                continue
+            self.users.append(u)
+            pair_items.append(kept)
+            lens.append(len(kept))
+            n_cand.append(I - len(seen))
+        if not self.users:
+            raise ValueError("the rank report has no (test user, test item) pair left to rank")
+        self.pair_ptr, self.pair_items, _ = ops.ragged(pair_items, dtype=np.int32, check=(I, "test item ids must lie in [0, %d)" % I))
+        self.pair_user = np.repeat(np.arange(len(self.users), dtype=np.int64), lens)       # position in self.users
+        self.user_n_cand = np.asarray(n_cand, dtype=np.int32)
+        self.pair_n_cand = self.user_n_cand[self.pair_user]
+        self.num_pairs = int(self.pair_items.size)
+        # groups: rows of the user block / of the pair block (a user group's pairs; the pairs by their item's popularity)
+        self.user_labels, self._user_pos = self._user_groups(self.users, user_train_dict, group_view)
+        by_user = [np.flatnonzero(np.isin(self.pair_user, p)) for p in self._user_pos[1:]]
+        counts = item_train_counts(user_train_dict, I) if item_group_view is not None else None
+        self.pair_labels, self._pair_pos = self._item_groups(self.pair_items, counts, item_group_view, prefix="item ")
+        self.pair_labels[1:1] = self.user_labels[1:]
+        self._pair_pos[1:1] = by_user
+
+    @property
+    def block_users(self):
+        """Users per scoring call: as many as keep the [users x items] float32 block (rows padded to 16 bytes) within block_bytes."""
+        return max(1, int(self.block_bytes) // ((self.num_items + 3) // 4 * 16))
+
+    def _make_resident(self, device):
+        """The CSRs, candidate counts and group indices resident on the device; blocks: _block's scoring inputs."""
+        return dict(pair_ptr=torch.from_numpy(self.pair_ptr).to(device), user_n_cand=torch.from_numpy(self.user_n_cand).to(device),
+                    pair_n_cand=torch.from_numpy(np.ascontiguousarray(self.pair_n_cand)).to(device),
+                    user_groups=group_index(self._user_pos, len(self.users), device),
+                    pair_groups=group_index(self._pair_pos, self.num_pairs, device), blocks={})
+
+    def _block(self, res, a, b, device):
+        """Users [a, b) of self.users as one scoring call's inputs, kept on the device: (users, TargetIndex, train_ptr, train_items)."""
+        hit = res["blocks"].get((a, b))
+        if hit is None:
+            ptr = self.pair_ptr[a:b + 1] - self.pair_ptr[a]
+            target = ops.TargetIndex(ptr, self.pair_items[self.pair_ptr[a]:self.pair_ptr[b]], b - a, self.num_items, device)
+            train = lists_csr(self.users[a:b], self.user_pos_train, device, cast=int)
+            hit = (torch.as_tensor(np.asarray(self.users[a:b], dtype=np.int64)).to(device), target) + (train if train[1].numel() else (None, None))
+            res["blocks"][(a, b)] = hit
+        return hit
+
+    def pair_ranks(self, model):
+        """The exact catalogue rank of every pair under the model's current predict type: int32 [num_pairs] on the device."""
+        device = self._preflight(model)
+        res = self._resident(device)
+        ranks = torch.empty(self.num_pairs, dtype=torch.int32, device=device)
+        step = self.block_users
+        for a in range(0, len(self.users), step):
+            b = min(a + step, len(self.users))
+            users, target, tptr, titems = self._block(res, a, b, device)
+            ranks[self.pair_ptr[a]:self.pair_ptr[b]] = model.rank_items_device(users, target, tptr, titems)[0]
+        return ranks
+
+    def _tables(self, pair_rows, pair_columns, user_rows, user_columns, res):
+        pairs = group_table(pair_rows, res["pair_groups"], len(self.pair_labels))
+        users = group_table(user_rows, res["user_groups"], len(self.user_labels)) if user_rows is not None else None
+        final = RankTables(tuple(pair_columns), list(self.pair_labels), pairs, tuple(user_columns),
+                           list(self.user_labels) if users is not None else [], users)
+        buf = format_table(final.pair_columns, final.pair_labels, final.pairs)
+        if users is not None:
+            buf += "\n" + format_table(final.user_columns, final.user_labels, final.users)
+        return final, buf
+
+    _format = staticmethod(format_table)
+
+    def evaluate(self, model, ranks=None):
+        """(final, buf). final = RankTables: pairs [1 + user groups + item groups x (3 + len(ks))] float32 -- row 0 = all pairs --
+        the means of rank, rr, pct, hit@K; users [1 + user groups x 3] the means of auc, mrr_full, first_rank. The pair means are
+        micro-averages (see the class). buf: per table a header of column names and one "%.8f" line per row, in the grouped
+        evaluator's format. ranks: pair_ranks(model) if the caller already holds it."""
+        if ranks is None:
+            ranks = self.pair_ranks(model)
+        res = self._resident(ranks.device)
+        pair_rows = torch.empty(self.num_pairs, 3 + len(self.ks), dtype=torch.float32, device=ranks.device)
+        ops.rank_pair_rows(ranks, res["pair_n_cand"], self.ks, pair_rows)
+        user_rows = torch.empty(len(self.users), 3, dtype=torch.float32, device=ranks.device)
+        ops.rank_user_rows(ranks, res["pair_ptr"], res["user_n_cand"], user_rows)
+        return self._tables(pair_rows, ops.rank_pair_columns(self.ks), user_rows, ops.RANK_USER_COLUMNS, res)
+
+    def shift(self, ranks_a, ranks_b):
+        """How far the pairs move from ranking a to ranking b (e.g. TE -> TIE): (final, buf) in evaluate()'s pair grouping over
+        delta = a - b (positive: b ranks the test item higher), improved = (b < a), worsened = (b > a)."""
+        if ranks_a.shape != (self.num_pairs,) or ranks_b.shape != (self.num_pairs,) or ranks_a.device != ranks_b.device:
+            raise ValueError("shift() takes two pair_ranks() results of this report on one device")
+        rows = torch.stack(((ranks_a - ranks_b).float(), (ranks_b < ranks_a).float(), (ranks_b > ranks_a).float()), dim=1)
+        return self._tables(rows, ("delta", "improved", "worsened"), None, (), self._resident(ranks_a.device))
+
+
+class NeighbourReport(_Report):
+    """Whose neighbourhood the fused space copies (--neighbour_report=K): for EVERY item its top-k neighbour lists by cosine in the
+    fused space and in each single-modal head's space (EliMRec.neighbours_device, csrc/knn.hip), items in blocks of block_items,
+    and per item the columns of ops.neighbour_columns(mods):
+      overlap_<m> = |fused list & head m's list| / k (ops.list_overlap); cos_fused, cos_<m> = the mean score of the list;
+      pop_fused, pop_<m> = the mean training-interaction count of the listed neighbours
+    (fillers skipped; a column of a row without neighbours is NaN). Their means over all items and -- item_group_view -- per item
+    popularity group (assign_item_groups over the items' training interactions) are ops.group_metric_means over the
+    [items x C] block: only the [1 + groups x C] table reaches the host. The lists do not depend on the predict type."""
+
+    name, needs = "neighbour", "neighbours_device"
+
+    def __init__(self, dataset, user_train_dict, k, item_group_view=None):
+        if not isinstance(user_train_dict, dict):
+            raise TypeError("user_train_dict must be a dict")
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1 or k > ops.KNN_MAX_K:
+            raise ValueError("k must be an integer in [1, %d], got %r" % (ops.KNN_MAX_K, k))
+        self.dataset = dataset
+        self.num_items = I = int(dataset.num_items)
+        self.k = int(k)
+        self.block_items = 8192
+        self.item_counts = item_train_counts(user_train_dict, I)
+        self.group_labels, self._positions = self._item_groups(np.arange(I, dtype=np.int64), self.item_counts, item_group_view)
+
+    def _make_resident(self, device):
+        """The group index, the items' training counts and the blocks' checked queries resident on the device."""
+        return dict(groups=group_index(self._positions, self.num_items, device),
+                    counts=torch.from_numpy(self.item_counts.astype(np.float64)).to(device), queries={})
+
+    def neighbour_rows(self, model):
+        """Every item's row of the report on the device: ([items x C] float32, column names)."""
+        device = self._preflight(model)
+        res = self._resident(device)
+        mods = tuple(model._mods)
+        columns = ops.neighbour_columns(mods)
+        S, k, I = len(mods), self.k, self.num_items
+        rows = torch.empty(I, len(columns), dtype=torch.float32, device=device)
+        step = max(1, int(self.block_items))
+        idx = torch.empty(1 + S, min(step, I), k, dtype=torch.int32, device=device)
+        val = torch.empty(1 + S, min(step, I), k, dtype=torch.float32, device=device)
+        cnt = torch.empty(min(step, I), dtype=torch.int32, device=device)
+        nan = torch.full((), float("nan"), dtype=torch.float64, device=device)
+        for a in range(0, I, step):
+            b = min(a + step, I)
+            query = res["queries"].get((a, b))
+            if query is None:
+                query = res["queries"][(a, b)] = ops.NeighbourQuery(np.arange(a, b, dtype=np.int32), I, device)
+            for h, space in enumerate(("fused",) + mods):
+                model.neighbours_device("item", None, k, space, idx[h, :b - a], val[h, :b - a], query=query)
+            listed = idx[:, :b - a] >= 0                                           # [1 + S x B x k]
+            n = listed.sum(dim=2).double()
+            out = rows[a:b]
+            for h in range(S):
+                ops.list_overlap(idx[0, :b - a], idx[1 + h, :b - a], cnt)
+                out[:, h] = torch.where(n[0] > 0, cnt[:b - a].double() / k, nan).float()
+            out[:, S:2 * S + 1] = (torch.where(listed, val[:, :b - a].double(), 0.0).sum(dim=2) / n).t().float()
+            pop = res["counts"][idx[:, :b - a].clamp(min=0).long()]
+            out[:, 2 * S + 1:] = (torch.where(listed, pop, 0.0).sum(dim=2) / n).t().float()
+        return rows, columns
+
+    def evaluate(self, model):
+        """(final [1 + item groups x C] float32: row 0 = all items, then one row per item popularity group; buf: a header of column
+        names and one "%.8f" line per row, in the effect report's format)."""
+        rows, columns = self.neighbour_rows(model)
+        final = group_table(rows, self._resident(rows.device)["groups"], len(self.group_labels))
+        return final, format_table(columns, self.group_labels, final)
+
+
+EXPOSURE_COLUMNS = ("items", "coverage", "gini", "entropy", "slot_share")
+
+
+def exposure_summary(counts, positions):
+    """How the list slots spread over the catalogue: float64 [len(positions) x 5], per group of item positions (index arrays into
+    counts) the columns EXPOSURE_COLUMNS:
+      items = the group's size; coverage = the share of its items with count > 0;
+      gini = the Gini coefficient of its counts, sum_i (2 i - n - 1) c_(i) / (n sum c) over the ascending counts c_(1..n)
+             (0 = every item listed equally often, (n - 1) / n = one item takes every slot; 0 for an empty or all-zero group);
+      entropy = -sum p log2 p in bits over p = c / sum c of the group (0 for an empty or all-zero group);
+      slot_share = the group's counts over ALL counts (0 when nothing is listed at all).
+    counts: how often each item is listed (ops.list_exposure). Pure numpy, float64."""
+    c_all = np.asarray(counts, dtype=np.float64).reshape(-1)
+    total = c_all.sum()
+    out = np.zeros((len(positions), len(EXPOSURE_COLUMNS)), dtype=np.float64)
+    for g, at in enumerate(positions):
+        c = np.sort(c_all[np.asarray(at, dtype=np.int64).reshape(-1)])
+        n, s = c.size, c.sum()
+        out[g, 0] = n
+        if n:
+            out[g, 1] = np.count_nonzero(c > 0) / float(n)
+        if n and s > 0:
+            out[g, 2] = ((2.0 * np.arange(1, n + 1) - n - 1.0) * c).sum() / (n * s)
+            p = c[c > 0] / s
+            out[g, 3] = 0.0 - (p * np.log2(p)).sum()
+        if total > 0:
+            out[g, 4] = s / total
+    return out
+
+
+ListTables = collections.namedtuple("ListTables", ("user_columns", "user_labels", "users", "item_columns", "item_labels", "items"))
+
+
+class ListReport(_Report):
+    """The recommendation lists themselves (--list_report=K): every test user's top-K list under the model's current predict
+    type with the train items masked (predict_device, users in blocks of block_users as EffectReport takes them), and
+      per user the columns of ops.list_columns(mods): ils_fused, ils_<m> = the mean pairwise cosine of the K listed items in the
+        fused space and in each head's space (EliMRec.list_similarity_device, csrc/lists.hip: one launch per block for all
+        spaces), pop = the mean training-interaction count of the listed items (float64 quotient; NaN for an empty list);
+      per item how often it is listed (ops.list_exposure, int32 counters filled block after block).
+    The user table is ops.group_metric_means over the rows: all users, then the group_view groups (assign_user_groups). The
+    item table is exposure_summary of the counters over all items, then the item_group_view groups (assign_item_groups over the
+    items' training interactions); the counters come to the host once per evaluate(): num_items int32 values."""
+
+    name, needs = "list", "list_similarity_device"
+
+    def __init__(self, dataset, user_train_dict, user_test_dict, top_k, group_view=None, item_group_view=None):
+        if not isinstance(user_train_dict, dict) or not isinstance(user_test_dict, dict):
+            raise TypeError("user_train_dict and user_test_dict must be dicts")
+        if isinstance(top_k, bool) or not isinstance(top_k, (int, np.integer)) or top_k < 2 or top_k > ops.LIST_MAX_K:
+            raise ValueError("top_k must be an integer in [2, %d], got %r" % (ops.LIST_MAX_K, top_k))
+        self.dataset = dataset
+        self.num_items = I = int(dataset.num_items)
+        self.user_pos_train = user_train_dict
+        self.user_pos_test = user_test_dict
+        self.top_k = int(top_k)
+        self.users = list(user_test_dict.keys())
+        self.item_counts = item_train_counts(user_train_dict, I)
+        self.group_labels, self._positions = self._user_groups(self.users, user_train_dict, group_view)
+        self.item_labels, self._item_positions = self._item_groups(np.arange(I, dtype=np.int64), self.item_counts, item_group_view,
+                                                                   prefix="item ")
+        self.columns = self.shift_columns = None   # ops.list_columns of the model list_rows() last saw; ("overlap", "d_<column>"...)
+
+    def _make_resident(self, device):
+        """The user group index and the items' training counts resident on the device."""
+        return dict(groups=group_index(self._positions, len(self.users), device),
+                    counts=torch.from_numpy(self.item_counts.astype(np.float64)).to(device))
+
+    def list_rows(self, model):
+        """Every test user's row, list and the catalogue's exposure on the device: ([users x C] float32, column names,
+        lists int32 [users x K], counts int32 [num_items])."""
+        device = self._preflight(model)
+        res = self._resident(device)
+        columns = self.columns = ops.list_columns(model._mods)
+        K, nb, n_users = self.top_k, len(columns) - 1, len(self.users)
+        rows = torch.empty(n_users, len(columns), dtype=torch.float32, device=device)
+        ils = torch.empty(n_users, nb, dtype=torch.float32, device=device)
+        lists = torch.empty(n_users, K, dtype=torch.int32, device=device)
+        counts = torch.zeros(self.num_items, dtype=torch.int32, device=device)
+        for a, b, _, idx in self.top_lists(model, self.users, K, self.block_users, self.tie_order):
+            lists[a:b] = idx
+            model.list_similarity_device(lists[a:b], ils[a:b], side="item")
+            ops.list_exposure(lists[a:b], counts)
+        listed = lists >= 0
+        pop = torch.where(listed, res["counts"][lists.clamp(min=0).long()], 0.0).sum(dim=1) / listed.sum(dim=1).double()
+        rows[:, :nb] = ils
+        rows[:, nb] = pop.float()
+        return rows, columns, lists, counts
+
+    def _user_table(self, rows):
+        return group_table(rows, self._resident(rows.device)["groups"], len(self.group_labels))
+
+    _format = staticmethod(format_table)
+
+    def evaluate(self, model, rows=None):
+        """(final, buf). final = ListTables: users [1 + user groups x C] float32 -- row 0 = all test users -- the means of
+        ops.list_columns; items [1 + item groups x 5] float64 -- row 0 = the whole catalogue -- exposure_summary of the counters,
+        columns EXPOSURE_COLUMNS. buf: per table a header of column names and one "%.8f" line per row, in the grouped evaluator's
+        format. rows: list_rows(model) if the caller already holds it."""
+        rows, columns, _, counts = self.list_rows(model) if rows is None else rows
+        items = exposure_summary(counts.cpu().numpy(), self._item_positions)
+        final = ListTables(tuple(columns), list(self.group_labels), self._user_table(rows), EXPOSURE_COLUMNS, list(self.item_labels), items)
+        buf = format_table(final.user_columns, final.user_labels, final.users) + "\n" + format_table(
+            final.item_columns, final.item_labels, final.items)
+        return final, buf
+
+    def shift(self, rows_a, lists_a, rows_b, lists_b):
+        """How the lists change from a to b (e.g. TE -> TIE): (final [1 + user groups x 1 + C] float32, buf) in evaluate()'s user
+        grouping over the columns self.shift_columns: overlap = |list a & list b| / K (ops.list_overlap) and d_<column> = b - a for
+        every user column."""
+        n, K = len(self.users), self.top_k
+        if (tuple(lists_a.shape) != (n, K) or lists_a.shape != lists_b.shape or rows_a.shape != rows_b.shape or rows_a.shape[0] != n
+                or len({t.device for t in (rows_a, rows_b, lists_a, lists_b)}) != 1):
+            raise ValueError("shift() takes the rows and lists of two list_rows() results of this report on one device")
+        cnt = torch.empty(n, dtype=torch.int32, device=lists_a.device)
+        ops.list_overlap(lists_a, lists_b, cnt)
+        rows = torch.cat(((cnt.double() / K).float()[:, None], rows_b - rows_a), dim=1)
+        if self.columns is None or len(self.columns) != rows_a.shape[1]:
+            raise ValueError("shift() takes rows of this report's list_rows()")
+        self.shift_columns = ("overlap",) + tuple("d_" + c for c in self.columns)
+        final = self._user_table(rows)
+        return final, format_table(self.shift_columns, self.group_labels, final)

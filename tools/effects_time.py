@@ -11,43 +11,13 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-
-def _setup():
-    import torch
-    import bench
-    from elimrec_amd import ColumnShardEngine, ColumnShardTrainer, FusedAdam, PairwiseSamplerV2
-    cfg, ds, model = bench.build(None, "cuda:0")
-    model = model.to("cuda:0")
-    opt = FusedAdam(model.parameters(), lr=cfg["lr"], weight_decay=cfg["weight_decay"])
-    tr = ColumnShardTrainer(ColumnShardEngine(model), opt)
-    u, p, n = PairwiseSamplerV2(ds, batch_size=2048, device="cuda:0").sample_epoch()
-    for i in range(3):
-        tr.step(u[i * 2048:(i + 1) * 2048], p[i * 2048:(i + 1) * 2048], n[i * 2048:(i + 1) * 2048])
-    torch.cuda.synchronize()
-    return ds, model
-
-
-def _time(fn, calls, reps):
-    """Seconds per call: (best, median) over `reps` groups of `calls` launches between two events."""
-    import torch
-    fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(calls):
-            fn()
-        b.record()
-        b.synchronize()
-        ts.append(a.elapsed_time(b) * 1e-3 / calls)
-    return min(ts), sorted(ts)[len(ts) // 2]
+from _timing import _events, _setup  # noqa: E402
 
 
 def run(args):
     import torch
     from elimrec_amd import _lib, ops
-    ds, model = _setup()
+    _, ds, model = _setup()
     dev = "cuda:0"
     B, K = min(args.users, ds.num_users), args.k
     U, I, d, S = model.num_users, model.num_items, model.latent_dim, model.S
@@ -76,7 +46,7 @@ def run(args):
                      "columns": C}, "fusion": fusion, "math": "fast" if int(_lib.load().elimrec_score_get_math()) else "exact",
            "calls": args.calls, "reps": args.reps, "gathered_bytes": gathered, "launches": {}}
     for name, fn in launches.items():
-        best, med = _time(fn, args.calls, args.reps)
+        best, med = _events(fn, args.calls, args.reps)
         rec = {"best_s": best, "median_s": med}
         if name != "pass1_row_sums":
             rec["stored_bytes"] = B * K * 4 * (C if name == "effects" else 1)

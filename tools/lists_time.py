@@ -16,9 +16,8 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
 
-from neighbours_time import _events, _setup, _wall  # noqa: E402
+from _timing import _events, _setup, _wall  # noqa: E402
 
 
 def main():
