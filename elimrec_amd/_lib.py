@@ -83,6 +83,32 @@ class HeadSrc16(ctypes.Structure):
                 ("d_S_out", ctypes.c_void_p), ("ld_S_out", ctypes.c_int64), ("d_c_out", ctypes.c_void_p)]
 
 
+HEAD_MAX_TABLES = 3
+
+
+class HeadWeights(ctypes.Structure):
+    """struct elimrec_head_weights."""
+    _fields_ = [("n_mod", ctypes.c_int32), ("recdim", ctypes.c_int32), ("D", ctypes.c_int32 * HEAD_MAX_TABLES),
+                ("d_Wm", ctypes.c_void_p * HEAD_MAX_TABLES), ("d_bm", ctypes.c_void_p * HEAD_MAX_TABLES),
+                ("d_Ws", ctypes.c_void_p * HEAD_MAX_TABLES), ("d_bs", ctypes.c_void_p * HEAD_MAX_TABLES),
+                ("d_Wf_user", ctypes.c_void_p), ("d_bf_user", ctypes.c_void_p), ("d_Wf_item", ctypes.c_void_p),
+                ("d_bf_item", ctypes.c_void_p), ("d_pack", ctypes.c_void_p), ("pack_floats", ctypes.c_size_t)]
+
+
+class HeadFwdIn(ctypes.Structure):
+    """struct elimrec_head_fwd_in."""
+    _fields_ = [("d_out0", ctypes.c_void_p), ("ld_out0", ctypes.c_int64), ("d_narrow", ctypes.c_void_p), ("ld_nar", ctypes.c_int64),
+                ("d_c", ctypes.c_void_p), ("d_S", ctypes.c_void_p * HEAD_MAX_TABLES), ("ldS", ctypes.c_int64 * HEAD_MAX_TABLES),
+                ("d_recv", ctypes.c_void_p), ("world", ctypes.c_int32), ("dl", ctypes.c_int64), ("src16", HeadSrc16),
+                ("rows", HeadRows)]
+
+
+class HeadBwdSinks(ctypes.Structure):
+    """struct elimrec_head_bwd_sinks."""
+    _fields_ = [("d_SrcA", ctypes.c_void_p), ("d_SrcB", ctypes.c_void_p), ("N", ctypes.c_int64), ("ns", ctypes.c_int32),
+                ("w", ctypes.c_int32), ("d_split", ctypes.c_void_p), ("n_max", ctypes.c_int64), ("world", ctypes.c_int32)]
+
+
 class ProgramOp(ctypes.Structure):
     """struct elimrec_op."""
     _fields_ = [("kind", ctypes.c_int32), ("fn", ctypes.c_int32), ("args", ctypes.c_uint64 * PROGRAM_MAX_ARGS)]
@@ -138,11 +164,8 @@ SIGNATURES = {
     "elimrec_copy_cols": (c_i32, [c_ptr, c_i64, c_ptr, c_i64, c_i64, c_i32, c_ptr]),
     "elimrec_bpr_head": (c_i32, [c_ptr, c_i64, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_i32, c_i32, c_i32,
                                  ctypes.POINTER(c_f32), c_ptr, c_ptr, c_ptr, c_ptr]),
-    "elimrec_bpr_head_rows": (c_i32, [c_ptr, c_i64, c_ptr, c_i32, c_i32, c_i32, ctypes.POINTER(c_f32), c_ptr, c_ptr, c_ptr]),
-    "elimrec_bpr_head_rows_sum": (c_i32, [c_ptr, c_i64, c_ptr, c_i32, c_i32, c_i32, ctypes.POINTER(c_f32), c_ptr, c_ptr, c_ptr, c_ptr,
-                                          c_ptr]),
-    "elimrec_bpr_head_rows_sum_pub": (c_i32, [c_ptr, c_i64, c_ptr, c_i32, c_i32, c_i32, ctypes.POINTER(c_f32), c_ptr, c_ptr, c_ptr, c_ptr,
-                                              c_ptr, c_ptr]),
+    "elimrec_bpr_head_rows": (c_i32, [c_ptr, c_i64, c_ptr, c_i32, c_i32, c_i32, ctypes.POINTER(c_f32), c_ptr, c_ptr, c_ptr, c_ptr,
+                                      c_ptr, c_ptr]),
     "elimrec_loss_pub_create": (c_i32, [c_i32, ctypes.POINTER(c_ptr)]),
     "elimrec_loss_pub_destroy": (c_i32, [c_ptr]),
     "elimrec_loss_pub_issued": (c_u32, [c_ptr]),
@@ -153,16 +176,7 @@ SIGNATURES = {
     "elimrec_segment_plan": (c_i32, [c_ptr, c_i64, c_i32, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
     "elimrec_segment_apply_head_bwd": (c_i32, [c_ptr, c_i64, c_i32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_i64, c_i32,
                                                c_i32, c_i32, ctypes.POINTER(c_i32), c_ptr, c_ptr, ctypes.POINTER(c_ptr), c_ptr,
-                                               c_ptr]),
-    "elimrec_segment_apply_head_bwd_packed": (c_i32, [c_ptr, c_i64, c_i32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_i64, c_i32,
-                                               c_i32, c_i32, ctypes.POINTER(c_i32), c_ptr, c_ptr, ctypes.POINTER(c_ptr), c_ptr,
-                                               c_ptr, c_ptr]),
-    "elimrec_segment_apply_head_bwd_sources": (c_i32, [c_ptr, c_i64, c_i32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_i64, c_i32,
-                                                c_i32, c_i32, ctypes.POINTER(c_i32), c_ptr, c_ptr, ctypes.POINTER(c_ptr), c_ptr,
-                                                c_ptr, c_i64, c_i32, c_i32, c_ptr, c_ptr, c_ptr]),
-    "elimrec_segment_apply_head_bwd_split": (c_i32, [c_ptr, c_i64, c_i32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_i64, c_i32,
-                                              c_i32, c_i32, ctypes.POINTER(c_i32), c_ptr, c_ptr, ctypes.POINTER(c_ptr), c_ptr,
-                                              c_ptr, c_i64, c_i32, c_ptr, c_ptr]),
+                                               c_ptr, ctypes.POINTER(HeadBwdSinks), c_ptr]),
     "elimrec_segment_apply": (c_i32, [c_ptr, c_i64, c_i32, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
     "elimrec_segment_reduce_rows": (c_i32, [c_ptr, c_ptr, c_i64, c_i32, c_i32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
     "elimrec_head_bwd_input": (c_i32, [c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_i64, c_i32, c_i32, c_i32,
@@ -235,22 +249,8 @@ SIGNATURES = {
                                       c_ptr]),
     "elimrec_head_pack_floats": (c_size, [c_i32, ctypes.POINTER(c_i32)]),
     "elimrec_head_pack_bwd_offset": (c_size, [c_i32, ctypes.POINTER(c_i32)]),
-    "elimrec_head_fwd_fused": (c_i32, [c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i32, ctypes.POINTER(c_ptr),
-                                       ctypes.POINTER(c_i64), ctypes.POINTER(c_i32), ctypes.POINTER(c_ptr), ctypes.POINTER(c_ptr),
-                                       c_ptr, c_ptr, c_ptr, c_ptr, ctypes.POINTER(c_ptr), ctypes.POINTER(c_ptr), c_ptr, c_size,
-                                       c_ptr, c_i64, c_ptr, c_i64, c_i32, c_i32, c_ptr]),
-    "elimrec_head_fwd_fused_peers": (c_i32, [c_ptr, c_ptr, c_i64, c_ptr, c_i32, c_i64, c_ptr, c_i32, ctypes.POINTER(c_ptr),
-                                             ctypes.POINTER(c_i64), ctypes.POINTER(c_i32), ctypes.POINTER(c_ptr), ctypes.POINTER(c_ptr),
-                                             c_ptr, c_ptr, c_ptr, c_ptr, ctypes.POINTER(c_ptr), ctypes.POINTER(c_ptr), c_ptr, c_size,
-                                             c_ptr, c_i64, c_ptr, c_i64, c_i32, c_i32, c_ptr]),
-    "elimrec_head_fwd_fused_rows": (c_i32, [ctypes.POINTER(HeadRows), c_ptr, c_ptr, c_i64, c_ptr, c_i32, ctypes.POINTER(c_ptr),
-                                            ctypes.POINTER(c_i64), ctypes.POINTER(c_i32), ctypes.POINTER(c_ptr), ctypes.POINTER(c_ptr),
-                                            c_ptr, c_ptr, c_ptr, c_ptr, ctypes.POINTER(c_ptr), ctypes.POINTER(c_ptr), c_ptr, c_size,
-                                            c_ptr, c_i64, c_ptr, c_i64, c_i32, c_ptr]),
-    "elimrec_head_fwd_fused_src16": (c_i32, [ctypes.POINTER(HeadSrc16), c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_i32,
-                                             ctypes.POINTER(c_i32), ctypes.POINTER(c_ptr), ctypes.POINTER(c_ptr), c_ptr, c_ptr, c_ptr, c_ptr,
-                                             ctypes.POINTER(c_ptr), ctypes.POINTER(c_ptr), c_ptr, c_size, c_ptr, c_i64, c_ptr, c_i64,
-                                             c_i32, c_i32, c_ptr]),
+    "elimrec_head_fwd_fused": (c_i32, [ctypes.POINTER(HeadFwdIn), ctypes.POINTER(HeadWeights), c_ptr, c_ptr, c_i64, c_ptr, c_i64,
+                                       c_ptr, c_i64, c_i32, c_ptr]),
     "elimrec_score_range_violations": (c_i32, [ctypes.POINTER(c_i64), c_i32, c_ptr]),
     "elimrec_score_range_check": (c_i32, [c_ptr, c_ptr, c_i32, c_i32, c_i32, c_i32, c_ptr, c_ptr]),
     "elimrec_score_set_math": (None, [c_i32]),
@@ -321,7 +321,7 @@ def load():
             raise HipLibraryError("elimrec_amd: %s does not export %s (stale build?)" % (LIB_PATH, name))
         fn.restype = res
         fn.argtypes = args
-    if lib.elimrec_abi_version() != 1:
+    if lib.elimrec_abi_version() != 2:
         raise HipLibraryError("elimrec_amd: ABI version mismatch")
     _lib = _Recording(lib)
     return _lib

@@ -896,34 +896,14 @@ __global__ __launch_bounds__(512) void head_bwd_input_mfma_kernel(const float *_
     }
 }
 
-// The same kernel on 16-row tiles (taken when the caller hands over the packed operands, see the launch site): twice the workgroups
-// at half the threads, a quarter of the LDS, v_mfma_f32_16x16x4_f32, four 16-column output tiles per wave.
+// The same kernel on 16-row tiles with the segment reduce always fused in front and the weight operands always from the packed
+// copy (taken when the caller hands them over, see the launch site; recdim 64): twice the workgroups at half the threads, a
+// quarter of the LDS, v_mfma_f32_16x16x4_f32, four 16-column output tiles per wave.
 typedef float v4f_ __attribute__((ext_vector_type(4)));
 constexpr int HM16 = 16;
 
-__device__ __forceinline__ v4f_ hm16_accumulate(v4f_ acc, const float *__restrict__ a_row, const float *__restrict__ Wp,
-                                                int64_t ldw, int K, int kq) {
-    // acc[row i][col j] += sum_k a_row[k] * Wp[k*ldw]   (a_row = this lane's LDS row, Wp = this lane's column)
-    constexpr int PF = 16;
-    for (int k0 = 0; k0 < K; k0 += 4 * PF) {
-        float b[PF];
-#pragma unroll
-        for (int q = 0; q < PF; ++q) {
-            const int k = k0 + 4 * q + kq;
-            b[q] = (k < K) ? Wp[(int64_t)k * ldw] : 0.f;
-        }
-#pragma unroll
-        for (int q = 0; q < PF; ++q) {
-            const int k = k0 + 4 * q + kq;
-            const float a = (k < K) ? a_row[k] : 0.f;
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b[q], acc, 0, 0, 0);
-        }
-    }
-    return acc;
-}
-
-// the same with the B operand from the packed copy (head.hip, common.h head_pack_layout): bp = start of the column tile +
-// lane, one coalesced 256-B load per MFMA; K = 64
+// acc[row i][col j] += sum_k a_row[k] * B[k][j], the B operand from the packed copy (head.hip, common.h head_pack_layout):
+// a_row = this lane's LDS row, bp = start of the column tile + lane, one coalesced 256-B load per MFMA; K = 64
 __device__ __forceinline__ v4f_ hm16_accumulate_packed(v4f_ acc, const float *__restrict__ a_row, const float *__restrict__ bp, int kq) {
     float b[16];
 #pragma unroll
@@ -940,26 +920,14 @@ __device__ __forceinline__ v4f_ hm16_accumulate_packed(v4f_ acc, const float *__
 // elimrec_source_rows_split makes of the compact rows)
 struct SlabSources { float *A, *B; int64_t N; int w, w_shift; float *split; int64_t n_max; int dl; };
 
-struct HeadPackPtrs { const float *f[2]; const float *s[kMaxHeads]; };      // null f[0]: weights read unpacked
+struct HeadPackPtrs { const float *f[2]; const float *s[kMaxHeads]; };
+struct HeadBlocks { int mblock[kMaxHeads]; };      // HeadPtrs without the unpacked weights
 
-// SEG: the segment reduce of the slot rows fused in front (the dY rows are formed here); !SEG: dY rows given (a reduce launch of its
-// own ran before: large batches, where the launch is paced by how many tiles a CU holds and the staging registers cost a third
-// of them)
-// PACKED: the operands from the packed copy, recdim 64 (the caller checked): the instantiation carries no code for weights read
-// unpacked
-// (Measured in round 5, B = 32768 = 65 k active rows, the same bits each time: 32- and 64-row tiles of this kernel -- every operand
-// load feeding 2 / 4 MFMAs on independent accumulators -- are SLOWER at every batch size (B = 2048 0.289 -> 0.302 / 0.326 ms per
-// step, B = 32768 0.758 -> 0.765 / 0.779); the segment sums as a launch of their own (a wave per segment, sixteen members in
-// flight) + this kernel with SEG = false: 73.6 + 73.0 us against 133 fused, step 0.743 -> 0.764 ms -- the sums' launch is the
-// chain of the batch's most popular item (604 members), which the fused form hides under the other tiles.)
-template <bool SEG, bool PACKED>
-__global__ __launch_bounds__(256) void head_bwd_input16_kernel(const float *__restrict__ dY, int64_t lddy,
-                                                               const int32_t *__restrict__ active_rows,
+// (32- and 64-row tiles of this kernel, and the segment sums as a launch of their own, were measured and are slower at every batch
+// size: docs/REJECTED.md.)
+__global__ __launch_bounds__(256) void head_bwd_input16_kernel(int64_t lddy, const int32_t *__restrict__ active_rows,
                                                                const int32_t *__restrict__ seg_info, int64_t n_max,
-                                                               int64_t U, int d, int C, int S, HeadPtrs hp,
-                                                               const float *__restrict__ W_user,
-                                                               const float *__restrict__ W_item, float gscale,
-                                                               float *__restrict__ G0, int64_t ldg, int scatter_cols,
+                                                               int64_t U, int d, int C, int S, HeadBlocks hp,
                                                                float *__restrict__ compact, SegSrc seg, HeadPackPtrs pk,
                                                                SlabSources src) {
     extern __shared__ float dys[];                       // [16][Cy + 4]
@@ -971,8 +939,7 @@ __global__ __launch_bounds__(256) void head_bwd_input16_kernel(const float *__re
     if (n_act > n_max) n_act = n_max;
     if (s0 >= n_act) return;
     const int rows = (int)((n_act - s0) < HM16 ? (n_act - s0) : HM16);
-    const bool segd = SEG && seg.rows != nullptr;
-    const float seg_scale = (segd && seg.scale) ? seg.scale[0] : 1.f;
+    const float seg_scale = seg.scale ? seg.scale[0] : 1.f;
     // staging as in the 32-row kernel: the dependent loads of the fused segment reduce in batches of 4 per thread
     constexpr int ST = 4;
     for (int e0 = tid * 4; e0 < HM16 * Cy; e0 += 1024 * ST) {
@@ -985,28 +952,23 @@ __global__ __launch_bounds__(256) void head_bwd_input16_kernel(const float *__re
             r[q] = e / Cy; c[q] = e - r[q] * Cy;
             in[q] = e < HM16 * Cy && r[q] < rows;
             beg[q] = 0; end[q] = 0;
-            if (in[q] && segd) { beg[q] = seg.seg_start[s0 + r[q]]; end[q] = seg.seg_start[s0 + r[q] + 1]; }
+            if (in[q]) { beg[q] = seg.seg_start[s0 + r[q]]; end[q] = seg.seg_start[s0 + r[q] + 1]; }
         }
-        if (segd) {
 #pragma unroll
-            for (int q = 0; q < ST; ++q) mem[q] = (in[q] && beg[q] < end[q]) ? seg.members[beg[q]] : 0;
-        }
+        for (int q = 0; q < ST; ++q) mem[q] = (in[q] && beg[q] < end[q]) ? seg.members[beg[q]] : 0;
 #pragma unroll
         for (int q = 0; q < ST; ++q) {
             v[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (in[q]) {
-                if (!segd) v[q] = ld4(dY + (s0 + r[q]) * lddy + c[q]);
-                else if (beg[q] < end[q]) {
-                    const float4 x = ld4(seg.rows + (int64_t)mem[q] * Cy + c[q]);
-                    v[q].x += x.x; v[q].y += x.y; v[q].z += x.z; v[q].w += x.w;    // 0 + x, as the serial loop does
-                }
+            if (in[q] && beg[q] < end[q]) {
+                const float4 x = ld4(seg.rows + (int64_t)mem[q] * Cy + c[q]);
+                v[q].x += x.x; v[q].y += x.y; v[q].z += x.z; v[q].w += x.w;    // 0 + x, as the serial loop does
             }
         }
 #pragma unroll
         for (int q = 0; q < ST; ++q) {
             const int e = e0 + 1024 * q;
             if (e >= HM16 * Cy) continue;
-            if (in[q] && segd) {
+            if (in[q]) {
                 // a popular item is listed by dozens of slots (48 of 6144 at the Tiktok shape), and walking them one dependent load
                 // pair at a time was the launch's longest chain (26 us; 19.5 with sixteen, then four, members' rows in flight --
                 // added in member order, as before)
@@ -1060,8 +1022,7 @@ __global__ __launch_bounds__(256) void head_bwd_input16_kernel(const float *__re
             const int row = 4 * kq + r;
             if (row < rows) {
                 const int64_t nd = node[row];
-                const float v = ((mixed && nd >= U) ? acc2[r] : acc[r]) * gscale;
-                if (G0 && c0 + li < scatter_cols) G0[nd * ldg + c0 + li] = v;
+                const float v = (mixed && nd >= U) ? acc2[r] : acc[r];
                 if (compact) compact[(s0 + row) * C + c0 + li] = v;
                 if (src.A || src.split) {
                     const int cb = c0 - mb * d + li;                 // column within the block
@@ -1081,7 +1042,7 @@ __global__ __launch_bounds__(256) void head_bwd_input16_kernel(const float *__re
             }
         }
     };
-    if (PACKED && !mixed && C <= 256) {
+    if (!mixed && C <= 256) {
         // Packed operands, one weight matrix for the whole tile (every tile but the one that straddles the user / item boundary):
         // wave w owns column tile w of every table block k (t = w + 4k), i.e. up to 8 rounds of 16 MFMAs -- the fusion operand of
         // block k, then the single-modal head that feeds block k -- each behind one 16-register operand load from L2. The loads of
@@ -1137,25 +1098,14 @@ __global__ __launch_bounds__(256) void head_bwd_input16_kernel(const float *__re
         const int c0 = t * 16;
         const int mb = c0 / d;
         v4f_ acc = {0.f, 0.f, 0.f, 0.f}, acc2 = {0.f, 0.f, 0.f, 0.f};
-        if (PACKED) {
-            const int64_t ft = (int64_t)t * 16 * 64 + lane;                       // column tile t of the [C x 64] fusion operand
-            acc = hm16_accumulate_packed(acc, a_row, pk.f[any_user ? 0 : 1] + ft, kq);
-            if (mixed) acc2 = hm16_accumulate_packed(acc2, a_row, pk.f[1] + ft, kq);
-            for (int h = 0; h < S; ++h) {
-                if (hp.mblock[h] != mb) continue;
-                const float *bp = pk.s[h] + (int64_t)((c0 - mb * d) / 16) * 16 * 64 + lane;
-                acc = hm16_accumulate_packed(acc, a_row + (1 + h) * d, bp, kq);
-                if (mixed) acc2 = hm16_accumulate_packed(acc2, a_row + (1 + h) * d, bp, kq);
-            }
-        } else if (!PACKED) {
-            acc = hm16_accumulate(acc, a_row, (any_user ? W_user : W_item) + c0 + li, C, d, kq);
-            if (mixed) acc2 = hm16_accumulate(acc2, a_row, W_item + c0 + li, C, d, kq);
-            for (int h = 0; h < S; ++h) {
-                if (hp.mblock[h] != mb) continue;
-                const float *Wh = hp.w[h] + (c0 - mb * d) + li;
-                acc = hm16_accumulate(acc, a_row + (1 + h) * d, Wh, d, d, kq);
-                if (mixed) acc2 = hm16_accumulate(acc2, a_row + (1 + h) * d, Wh, d, d, kq);
-            }
+        const int64_t ft = (int64_t)t * 16 * 64 + lane;                       // column tile t of the [C x 64] fusion operand
+        acc = hm16_accumulate_packed(acc, a_row, pk.f[any_user ? 0 : 1] + ft, kq);
+        if (mixed) acc2 = hm16_accumulate_packed(acc2, a_row, pk.f[1] + ft, kq);
+        for (int h = 0; h < S; ++h) {
+            if (hp.mblock[h] != mb) continue;
+            const float *bp = pk.s[h] + (int64_t)((c0 - mb * d) / 16) * 16 * 64 + lane;
+            acc = hm16_accumulate_packed(acc, a_row + (1 + h) * d, bp, kq);
+            if (mixed) acc2 = hm16_accumulate_packed(acc2, a_row + (1 + h) * d, bp, kq);
         }
         emit(c0, mb, acc, acc2);
     }
@@ -1273,19 +1223,26 @@ static int bpr_group_lanes(int d) {      // lanes per head block: pow2 >= d/4, a
     return lb;
 }
 
+// the checks every BPR entry shares, and the block weights as the kernels take them
+static int bpr_block_weights(const char *what, int64_t ldy, int d, int n_blocks, const float *block_weights, BlockWeights &bw) {
+    ELIMREC_REQUIRE(d > 0 && d % 4 == 0, "%s: recdim must be a positive multiple of 4", what);
+    ELIMREC_REQUIRE(n_blocks >= 1 && n_blocks <= kMaxBlocks, "%s: 1..%d head blocks supported", what, kMaxBlocks);
+    ELIMREC_REQUIRE(ldy % 4 == 0 && ldy >= (int64_t)n_blocks * d, "%s: bad ldy", what);
+    for (int k = 0; k < kMaxBlocks; ++k) bw.w[k] = k < n_blocks ? block_weights[k] : 0.f;
+    return 0;
+}
+
 extern "C" int elimrec_bpr_head(const float *d_Y, int64_t ldy, int64_t U, int64_t I, const int64_t *d_users,
                                 const int64_t *d_pos, const int64_t *d_neg, int B, int d, int n_blocks,
                                 const float *block_weights, float *d_loss_rows, float *d_grad_rows, int32_t *d_keys,
                                 void *stream) {
     ELIMREC_REQUIRE(d_Y && d_users && d_pos && d_neg && d_loss_rows && block_weights, "bpr_head: null pointer");
-    ELIMREC_REQUIRE(d > 0 && d % 4 == 0, "bpr_head: recdim must be a positive multiple of 4");
-    ELIMREC_REQUIRE(n_blocks >= 1 && n_blocks <= kMaxBlocks, "bpr_head: 1..%d head blocks supported", kMaxBlocks);
-    ELIMREC_REQUIRE(ldy % 4 == 0 && ldy >= (int64_t)n_blocks * d, "bpr_head: bad ldy");
+    BlockWeights bw;
+    int rc = bpr_block_weights("bpr_head", ldy, d, n_blocks, block_weights, bw);
+    if (rc) return rc;
     ELIMREC_REQUIRE(U + I < (int64_t)INT32_MAX, "bpr_head: node ids must fit int32");
     ELIMREC_REQUIRE(!d_grad_rows || d_keys, "bpr_head: keys required with grad_rows");
     if (B <= 0) return 0;
-    BlockWeights bw;
-    for (int k = 0; k < kMaxBlocks; ++k) bw.w[k] = k < n_blocks ? block_weights[k] : 0.f;
     hipLaunchKernelGGL(bpr_head_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, d_Y, ldy, U, d_users,
                        d_pos, d_neg, B, d, n_blocks, bw, 1.0f / (float)B, d_loss_rows, d_grad_rows, d_keys,
                        (const int32_t *)nullptr, bpr_group_lanes(d));
@@ -1293,60 +1250,35 @@ extern "C" int elimrec_bpr_head(const float *d_Y, int64_t ldy, int64_t U, int64_
     return 0;
 }
 
-extern "C" int elimrec_bpr_head_rows(const float *d_Y, int64_t ldy, const int32_t *d_slot_rows, int B, int d,
-                                     int n_blocks, const float *block_weights, float *d_loss_rows, float *d_grad_rows,
-                                     void *stream) {
-    ELIMREC_REQUIRE(d_Y && d_slot_rows && d_loss_rows && block_weights, "bpr_head_rows: null pointer");
-    ELIMREC_REQUIRE(d > 0 && d % 4 == 0, "bpr_head_rows: recdim must be a positive multiple of 4");
-    ELIMREC_REQUIRE(n_blocks >= 1 && n_blocks <= kMaxBlocks, "bpr_head_rows: 1..%d head blocks supported", kMaxBlocks);
-    ELIMREC_REQUIRE(ldy % 4 == 0 && ldy >= (int64_t)n_blocks * d, "bpr_head_rows: bad ldy");
-    if (B <= 0) return 0;
-    BlockWeights bw;
-    for (int k = 0; k < kMaxBlocks; ++k) bw.w[k] = k < n_blocks ? block_weights[k] : 0.f;
-    hipLaunchKernelGGL(bpr_head_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, d_Y, ldy, (int64_t)0,
-                       (const int64_t *)nullptr, (const int64_t *)nullptr, (const int64_t *)nullptr, B, d, n_blocks, bw,
-                       1.0f / (float)B, d_loss_rows, d_grad_rows, (int32_t *)nullptr, d_slot_rows, bpr_group_lanes(d));
-    ELIMREC_LAUNCH_CHECK("bpr_head_rows");
-    return 0;
-}
-
-extern "C" int elimrec_bpr_head_rows_sum(const float *d_Y, int64_t ldy, const int32_t *d_slot_rows, int B, int d,
-                                         int n_blocks, const float *block_weights, float *d_loss_rows, float *d_grad_rows,
-                                         float *d_loss, int32_t *d_ticket, void *stream) {
-    ELIMREC_REQUIRE(d_Y && d_slot_rows && d_loss_rows && block_weights && d_loss && d_ticket, "bpr_head_rows_sum: null pointer");
-    ELIMREC_REQUIRE(d > 0 && d % 4 == 0, "bpr_head_rows_sum: recdim must be a positive multiple of 4");
-    ELIMREC_REQUIRE(n_blocks >= 1 && n_blocks <= kMaxBlocks, "bpr_head_rows_sum: 1..%d head blocks supported", kMaxBlocks);
-    ELIMREC_REQUIRE(ldy % 4 == 0 && ldy >= (int64_t)n_blocks * d, "bpr_head_rows_sum: bad ldy");
-    if (B <= 0) return check_hip(hipMemsetAsync(d_loss, 0, sizeof(float), (hipStream_t)stream), "memset(loss)");
-    BlockWeights bw;
-    for (int k = 0; k < kMaxBlocks; ++k) bw.w[k] = k < n_blocks ? block_weights[k] : 0.f;
-    hipLaunchKernelGGL(bpr_head_sum_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, d_Y, ldy, B, d, n_blocks, bw,
-                       1.0f / (float)B, d_loss_rows, d_grad_rows, d_slot_rows, bpr_group_lanes(d), d_loss, d_ticket,
-                       (unsigned long long *)nullptr, 0, (uint32_t *)nullptr);
-    ELIMREC_LAUNCH_CHECK("bpr_head_rows_sum");
-    return 0;
-}
-
-// ... and the loss PUBLISHED to the host from that launch (main.py:102 of the reference reads `loss.cpu().item()` after every
-// step: a read of the device tensor waits for the whole step -- adjoint hops, Adam -- and the host cannot enqueue step t + 1
-// under step t). pub: elimrec_loss_pub_create's block; the host waits on the slot with elimrec_loss_pub_wait, not on the stream.
+// pub: elimrec_loss_pub_create's block; the host waits on the slot with elimrec_loss_pub_wait, not on the stream (main.py:102 of
+// the reference reads `loss.cpu().item()` after every step: a read of the device tensor waits for the whole step -- adjoint
+// hops, Adam -- and the host cannot enqueue step t + 1 under step t)
 struct LossPub { unsigned long long *h_slots; unsigned long long *d_slots; uint32_t *d_counter; int n; uint32_t issued; };
 
-extern "C" int elimrec_bpr_head_rows_sum_pub(const float *d_Y, int64_t ldy, const int32_t *d_slot_rows, int B, int d,
-                                             int n_blocks, const float *block_weights, float *d_loss_rows, float *d_grad_rows,
-                                             float *d_loss, int32_t *d_ticket, void *pub, void *stream) {
-    ELIMREC_REQUIRE(d_Y && d_slot_rows && d_loss_rows && block_weights && d_loss && d_ticket && pub, "bpr_head_rows_sum_pub: null pointer");
-    ELIMREC_REQUIRE(d > 0 && d % 4 == 0, "bpr_head_rows_sum_pub: recdim must be a positive multiple of 4");
-    ELIMREC_REQUIRE(n_blocks >= 1 && n_blocks <= kMaxBlocks, "bpr_head_rows_sum_pub: 1..%d head blocks supported", kMaxBlocks);
-    ELIMREC_REQUIRE(ldy % 4 == 0 && ldy >= (int64_t)n_blocks * d && B > 0, "bpr_head_rows_sum_pub: bad ldy / empty batch");
-    LossPub *lp = (LossPub *)pub;
+extern "C" int elimrec_bpr_head_rows(const float *d_Y, int64_t ldy, const int32_t *d_slot_rows, int B, int d,
+                                     int n_blocks, const float *block_weights, float *d_loss_rows, float *d_grad_rows,
+                                     float *d_loss, int32_t *d_ticket, void *pub, void *stream) {
+    const char *what = pub ? "bpr_head_rows (publishing)" : d_loss ? "bpr_head_rows (sum)" : "bpr_head_rows";
+    ELIMREC_REQUIRE(d_Y && d_slot_rows && d_loss_rows && block_weights, "%s: null pointer", what);
+    ELIMREC_REQUIRE(d_loss ? d_ticket != nullptr : (!d_ticket && !pub), "%s: the loss and its ticket go together, a publisher needs both", what);
     BlockWeights bw;
-    for (int k = 0; k < kMaxBlocks; ++k) bw.w[k] = k < n_blocks ? block_weights[k] : 0.f;
+    int rc = bpr_block_weights(what, ldy, d, n_blocks, block_weights, bw);
+    if (rc) return rc;
+    ELIMREC_REQUIRE(!pub || B > 0, "%s: empty batch", what);
+    if (B <= 0) return d_loss ? check_hip(hipMemsetAsync(d_loss, 0, sizeof(float), (hipStream_t)stream), "memset(loss)") : 0;
+    if (!d_loss) {
+        hipLaunchKernelGGL(bpr_head_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, d_Y, ldy, (int64_t)0,
+                           (const int64_t *)nullptr, (const int64_t *)nullptr, (const int64_t *)nullptr, B, d, n_blocks, bw,
+                           1.0f / (float)B, d_loss_rows, d_grad_rows, (int32_t *)nullptr, d_slot_rows, bpr_group_lanes(d));
+        ELIMREC_LAUNCH_CHECK(what);
+        return 0;
+    }
+    LossPub *lp = (LossPub *)pub;
     hipLaunchKernelGGL(bpr_head_sum_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, d_Y, ldy, B, d, n_blocks, bw,
                        1.0f / (float)B, d_loss_rows, d_grad_rows, d_slot_rows, bpr_group_lanes(d), d_loss, d_ticket,
-                       lp->d_slots, lp->n, lp->d_counter);
-    ELIMREC_LAUNCH_CHECK("bpr_head_rows_sum_pub");
-    lp->issued += 1;                       // (the sequence number the launch just enqueued will publish)
+                       lp ? lp->d_slots : (unsigned long long *)nullptr, lp ? lp->n : 0, lp ? lp->d_counter : (uint32_t *)nullptr);
+    ELIMREC_LAUNCH_CHECK(what);
+    if (lp) lp->issued += 1;               // (the sequence number the launch just enqueued will publish)
     return 0;
 }
 
@@ -1625,80 +1557,34 @@ extern "C" int elimrec_head_bwd_input(const float *d_dY, int64_t lddy, const int
 // segment_apply + head_bwd_input in one launch (the MFMA form stages the dY rows in LDS anyway: it sums them
 // from the member gradient rows instead of reading them back). Falls back to the two launches when the MFMA
 // form does not apply.
-static int segment_apply_head_bwd_impl(const float *d_rows, int64_t n, int ld, const int32_t *d_active_rows,
-                                       const int32_t *d_seg_info, const float *d_scale, float *d_reduced,
-                                       const void *d_plan_workspace, size_t plan_workspace_bytes, int64_t U, int d,
-                                       int C, int S, const int *head_mblock, const float *d_W_user,
-                                       const float *d_W_item, const float *const *d_W_heads, float *d_compact,
-                                       const float *d_pack_bwd, const SlabSources *src, void *stream);
-
 extern "C" int elimrec_segment_apply_head_bwd(const float *d_rows, int64_t n, int ld, const int32_t *d_active_rows,
                                               const int32_t *d_seg_info, const float *d_scale, float *d_reduced,
                                               const void *d_plan_workspace, size_t plan_workspace_bytes, int64_t U, int d,
                                               int C, int S, const int *head_mblock, const float *d_W_user,
                                               const float *d_W_item, const float *const *d_W_heads, float *d_compact,
-                                              void *stream) {
-    return segment_apply_head_bwd_impl(d_rows, n, ld, d_active_rows, d_seg_info, d_scale, d_reduced, d_plan_workspace,
-                                       plan_workspace_bytes, U, d, C, S, head_mblock, d_W_user, d_W_item, d_W_heads, d_compact,
-                                       nullptr, nullptr, stream);
-}
-
-extern "C" int elimrec_segment_apply_head_bwd_packed(const float *d_rows, int64_t n, int ld, const int32_t *d_active_rows,
-                                                     const int32_t *d_seg_info, const float *d_scale, float *d_reduced,
-                                                     const void *d_plan_workspace, size_t plan_workspace_bytes, int64_t U,
-                                                     int d, int C, int S, const int *head_mblock, const float *d_W_user,
-                                                     const float *d_W_item, const float *const *d_W_heads,
-                                                     float *d_compact, const float *d_pack_bwd, void *stream) {
-    ELIMREC_REQUIRE(d_pack_bwd, "segment_apply_head_bwd_packed: null pack pointer");
-    return segment_apply_head_bwd_impl(d_rows, n, ld, d_active_rows, d_seg_info, d_scale, d_reduced, d_plan_workspace,
-                                       plan_workspace_bytes, U, d, C, S, head_mblock, d_W_user, d_W_item, d_W_heads, d_compact,
-                                       d_pack_bwd, nullptr, stream);
-}
-
-extern "C" int elimrec_segment_apply_head_bwd_sources(const float *d_rows, int64_t n, int ld, const int32_t *d_active_rows,
-                                                      const int32_t *d_seg_info, const float *d_scale, float *d_reduced,
-                                                      const void *d_plan_workspace, size_t plan_workspace_bytes, int64_t U,
-                                                      int d, int C, int S, const int *head_mblock, const float *d_W_user,
-                                                      const float *d_W_item, const float *const *d_W_heads,
-                                                      float *d_compact, const float *d_pack_bwd, int64_t N, int ns, int w,
-                                                      float *d_SrcA, float *d_SrcB, void *stream) {
-    ELIMREC_REQUIRE(d_pack_bwd && d_SrcA && d_SrcB, "segment_apply_head_bwd_sources: null pointer");
-    ELIMREC_REQUIRE(d == 64 && w >= 4 && (w & (w - 1)) == 0 && ns * w == d && N >= U,
-                    "segment_apply_head_bwd_sources: recdim 64 in [ns x N x w] slabs (d=%d, ns=%d, w=%d)", d, ns, w);
-    SlabSources src = {d_SrcA, d_SrcB, N, w, 0, nullptr, 0, 0};
-    while ((1 << src.w_shift) < w) ++src.w_shift;
-    return segment_apply_head_bwd_impl(d_rows, n, ld, d_active_rows, d_seg_info, d_scale, d_reduced, d_plan_workspace,
-                                       plan_workspace_bytes, U, d, C, S, head_mblock, d_W_user, d_W_item, d_W_heads, d_compact,
-                                       d_pack_bwd, &src, stream);
-}
-
-extern "C" int elimrec_segment_apply_head_bwd_split(const float *d_rows, int64_t n, int ld, const int32_t *d_active_rows,
-                                                    const int32_t *d_seg_info, const float *d_scale, float *d_reduced,
-                                                    const void *d_plan_workspace, size_t plan_workspace_bytes, int64_t U,
-                                                    int d, int C, int S, const int *head_mblock, const float *d_W_user,
-                                                    const float *d_W_item, const float *const *d_W_heads,
-                                                    float *d_compact, const float *d_pack_bwd, int64_t n_max, int world,
-                                                    float *d_out, void *stream) {
-    ELIMREC_REQUIRE(d_pack_bwd && d_out, "segment_apply_head_bwd_split: null pointer");
-    ELIMREC_REQUIRE(d == 64 && world >= 1 && d % world == 0 && (d / world) % 4 == 0 && n_max >= n,
-                    "segment_apply_head_bwd_split: recdim 64 in %d column slices, n_max >= n", world);
-    SlabSources src = {nullptr, nullptr, 0, 0, 0, d_out, n_max, d / world};
-    return segment_apply_head_bwd_impl(d_rows, n, ld, d_active_rows, d_seg_info, d_scale, d_reduced, d_plan_workspace,
-                                       plan_workspace_bytes, U, d, C, S, head_mblock, d_W_user, d_W_item, d_W_heads, d_compact,
-                                       d_pack_bwd, &src, stream);
-}
-
-static int segment_apply_head_bwd_impl(const float *d_rows, int64_t n, int ld, const int32_t *d_active_rows,
-                                       const int32_t *d_seg_info, const float *d_scale, float *d_reduced,
-                                       const void *d_plan_workspace, size_t plan_workspace_bytes, int64_t U, int d,
-                                       int C, int S, const int *head_mblock, const float *d_W_user,
-                                       const float *d_W_item, const float *const *d_W_heads, float *d_compact,
-                                       const float *d_pack_bwd, const SlabSources *src, void *stream) {
+                                              const float *d_pack_bwd, const elimrec_head_bwd_sinks *sinks, void *stream) {
     ELIMREC_REQUIRE(d_rows && d_active_rows && d_seg_info && d_reduced && d_plan_workspace && d_W_user && d_W_item &&
                     d_compact, "segment_apply_head_bwd: null pointer");
     ELIMREC_REQUIRE(n > 0 && n < INT32_MAX && ld > 0 && ld % 4 == 0, "segment_apply_head_bwd: bad n/ld");
     ELIMREC_REQUIRE(S >= 0 && S <= kMaxHeads && d > 0 && d % 4 == 0 && C % d == 0 && ld == (1 + S) * d,
                     "segment_apply_head_bwd: bad d/C/S/ld");
+    SlabSources src = {};
+    const bool to_slabs = sinks && sinks->d_SrcA, to_split = sinks && sinks->d_split;
+    ELIMREC_REQUIRE(!(to_slabs && to_split), "segment_apply_head_bwd: slab sources or column slices, not both");
+    if (to_slabs) {
+        const int w = sinks->w;
+        ELIMREC_REQUIRE(d_pack_bwd && sinks->d_SrcB, "segment_apply_head_bwd (sources): null pointer");
+        ELIMREC_REQUIRE(d == 64 && w >= 4 && (w & (w - 1)) == 0 && sinks->ns * w == d && sinks->N >= U,
+                        "segment_apply_head_bwd (sources): recdim 64 in [ns x N x w] slabs (d=%d, ns=%d, w=%d)", d, sinks->ns, w);
+        src.A = sinks->d_SrcA; src.B = sinks->d_SrcB; src.N = sinks->N; src.w = w;
+        while ((1 << src.w_shift) < w) ++src.w_shift;
+    } else if (to_split) {
+        const int world = sinks->world;
+        ELIMREC_REQUIRE(d_pack_bwd, "segment_apply_head_bwd (split): null pointer");
+        ELIMREC_REQUIRE(d == 64 && world >= 1 && d % world == 0 && (d / world) % 4 == 0 && sinks->n_max >= n,
+                        "segment_apply_head_bwd (split): recdim 64 in %d column slices, n_max >= n", world);
+        src.split = sinks->d_split; src.n_max = sinks->n_max; src.dl = d / world;
+    }
     const size_t lds_m = (size_t)HM_ROWS * ((1 + S) * d + 1) * sizeof(float);
     if (!(d % 32 == 0 && lds_m <= 96 * 1024)) {
         int rc = elimrec_segment_apply(d_rows, n, ld, d_seg_info, d_scale, d_reduced, d_plan_workspace,
@@ -1716,39 +1602,29 @@ static int segment_apply_head_bwd_impl(const float *d_rows, int64_t n, int ld, c
     }
     const char *ws = (const char *)d_plan_workspace;
     SegSrc seg = {d_rows, (const int32_t *)(ws + L.vals_sorted), (const int32_t *)(ws + L.seg_start), d_scale, d_reduced};
+    // 16-row tiles: with the weights read unpacked from L2 the smaller MFMA doubles the operand loads (32.4 us against
+    // 28.5 for the 32-row kernel at the Tiktok shape) -- used when the caller hands over the packed operands
+    // (recdim 64; C is then a multiple of the 16-column tile)
+    if (d_pack_bwd && d == 64) {
+        const size_t lds16 = (size_t)HM16 * ((1 + S) * d + 4) * sizeof(float);
+        HeadBlocks hb;
+        for (int h = 0; h < kMaxHeads; ++h) hb.mblock[h] = h < S ? head_mblock[h] : -1;
+        HeadPackPtrs pk = {};
+        pk.f[0] = d_pack_bwd; pk.f[1] = d_pack_bwd + (int64_t)C * 64;
+        for (int h = 0; h < S; ++h) pk.s[h] = d_pack_bwd + (int64_t)2 * C * 64 + (int64_t)h * 64 * 64;
+        hipLaunchKernelGGL(head_bwd_input16_kernel, dim3((unsigned)((n + HM16 - 1) / HM16)), dim3(256), lds16,
+                           (hipStream_t)stream, (int64_t)ld, d_active_rows, d_seg_info, n, U, d, C, S, hb, d_compact, seg, pk, src);
+        ELIMREC_LAUNCH_CHECK("segment_apply_head_bwd16");
+        return 0;
+    }
     HeadPtrs hp;
     for (int h = 0; h < kMaxHeads; ++h) {
         hp.w[h] = h < S ? d_W_heads[h] : nullptr;
         hp.mblock[h] = h < S ? head_mblock[h] : -1;
     }
-    // 16-row tiles: with the weights read unpacked from L2 the smaller MFMA doubles the operand loads (32.4 us against
-    // 28.5 for the 32-row kernel at the Tiktok shape) -- used when the caller hands over the packed operands
-    // (recdim 64)
-    const bool packed = d_pack_bwd && d == 64;
-    if (packed && C % 16 == 0 && (1 + S) * d % 4 == 0) {
-        const size_t lds16 = (size_t)HM16 * ((1 + S) * d + 4) * sizeof(float);
-        HeadPackPtrs pk = {};
-        if (packed) {
-            pk.f[0] = d_pack_bwd; pk.f[1] = d_pack_bwd + (int64_t)C * 64;
-            for (int h = 0; h < S && h < kMaxHeads; ++h) pk.s[h] = d_pack_bwd + (int64_t)2 * C * 64 + (int64_t)h * 64 * 64;
-        }
-        SlabSources ss = src ? *src : SlabSources{};
-        if (packed)
-            hipLaunchKernelGGL((head_bwd_input16_kernel<true, true>), dim3((unsigned)((n + HM16 - 1) / HM16)), dim3(256), lds16,
-                               (hipStream_t)stream, (const float *)d_reduced, (int64_t)ld, d_active_rows, d_seg_info, n, U, d, C, S, hp,
-                               d_W_user, d_W_item, 1.0f, (float *)nullptr, (int64_t)0, 0, d_compact, seg, pk, ss);
-        else
-            hipLaunchKernelGGL((head_bwd_input16_kernel<true, false>), dim3((unsigned)((n + HM16 - 1) / HM16)), dim3(256), lds16,
-                               (hipStream_t)stream, (const float *)d_reduced, (int64_t)ld, d_active_rows, d_seg_info, n, U, d, C, S, hp,
-                               d_W_user, d_W_item, 1.0f, (float *)nullptr, (int64_t)0, 0, d_compact, seg, pk, ss);
-        ELIMREC_LAUNCH_CHECK("segment_apply_head_bwd16");
-        return 0;
-    }
-    ELIMREC_REQUIRE(!src, "segment_apply_head_bwd_sources: needs the packed operands of the 16-row head (recdim 64)");
     hipLaunchKernelGGL(head_bwd_input_mfma_kernel, dim3((unsigned)((n + HM_ROWS - 1) / HM_ROWS)), dim3(512), lds_m,
                        (hipStream_t)stream, (const float *)d_reduced, (int64_t)ld, d_active_rows, d_seg_info, n, U, d, C, S, hp,
                        d_W_user, d_W_item, 1.0f, (float *)nullptr, (int64_t)0, 0, d_compact, seg);
     ELIMREC_LAUNCH_CHECK("segment_apply_head_bwd");
     return 0;
 }
-

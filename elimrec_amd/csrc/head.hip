@@ -18,7 +18,7 @@
 namespace elimrec {
 
 constexpr int HD = 64;            // recdim
-constexpr int HMAXM = 3;
+constexpr int HMAXM = ELIMREC_HEAD_MAX_TABLES;
 
 struct PackJob { const float *W; int64_t ld; int K; int64_t dst; int N; int64_t sn, sk; };   // 16-row form: element (n, k) = W[n*sn + k*sk], N columns
 struct PackJobs { PackJob j[16]; int n; int first_block[17]; };
@@ -41,12 +41,12 @@ struct HeadFwdArgs {
     int stage;                                      // head_fwd16_kernel: 0 = whole head; 1 = the feature blocks only, WITHOUT the
                                                     // shared part (needs nothing of the graph: can run beside the forward hops);
                                                     // 2 = the rest (shared part added to what stage 1 left in OutAct, fusion, heads)
-    // 16-bit constants read where they lie (elimrec_head_fwd_fused_src16): rows [S_1 | .. | S_n | c_hi c_lo] of fp16 (1) / bf16 (2)
+    // 16-bit constants read where they lie (elimrec_head_fwd_in::src16): rows [S_1 | .. | S_n | c_hi c_lo] of fp16 (1) / bf16 (2)
     // elements, widened in registers -- no separate widening pass over the batch's rows in front of the head. s_out / c_out
     // (nullable): the widened rows in active-row order, for the weight-gradient launches of the backward half.
     int sdtype; const uint16_t *tab16; int64_t row_elems; int s_off[HMAXM]; int c_off;
     float *s_out; int64_t ld_sout; float *c_out;
-    // out0 / narrow as the forward exchange delivers them (elimrec_head_fwd_fused_peers): peer q's piece of row r, columns
+    // out0 / narrow as the forward exchange delivers them (elimrec_head_fwd_in::d_recv): peer q's piece of row r, columns
     // [q*dl, (q+1)*dl), at out0 + q * peer_stride + r * ld_out0 -- the received [W][R][out0 dl | narrow dl] buffer read in place
     int peer_dl; int64_t peer_stride;
 };
@@ -273,22 +273,40 @@ extern "C" size_t elimrec_head_pack_bwd_offset(int n_mod, const int *D) {
     return (size_t)head_pack_layout(n_mod, D).fwd_total;
 }
 
-static int head_fwd_fused_impl(int peer_world, int64_t peer_dl, const elimrec_head_src16 *src, const elimrec_head_rows *rows, const int32_t *d_act, const int32_t *d_seg_info, int64_t R, const float *d_out0,
-                                      int64_t ld_out0, const float *d_narrow, int64_t ld_nar, const float *d_c, int n_mod,
-                                      const float *const *d_S, const int64_t *ldS, const int *D, const float *const *d_Wm,
-                                      const float *const *d_bm, const float *d_Wf_user, const float *d_bf_user,
-                                      const float *d_Wf_item, const float *d_bf_item, const float *const *d_Ws,
-                                      const float *const *d_bs, float *d_pack, size_t pack_floats, float *d_OutAct,
-                                      int64_t ld_out, float *d_YAct, int64_t ld_y, int recdim, int phase, void *stream) {
-    ELIMREC_REQUIRE(d_act && d_seg_info && d_out0 && d_narrow && (src || (d_c && d_S)) && d_Wm && d_Wf_user && d_Wf_item && d_Ws && d_pack &&
+// One entry for the four input forms (elimrec_head_fwd_in): plain; peers = out0 / narrow read where the forward exchange of the
+// column shards left them, d_recv = [world][R][out0 dl | narrow dl], peer q's columns of MY rows (ops.peer_cols_to_rows + the
+// plain form without the pass in between; same bits); 16-bit source = the feature constants read from their 16-bit storage
+// (lookup.hip's packed rows, one rank holding every row: HeadFwdArgs::sdtype; the bits of elimrec_lookup_unpack(direct) followed
+// by the plain form on its rows); rows = phase 4 with out0 / narrow evaluated by the launch itself.
+extern "C" int elimrec_head_fwd_fused(const elimrec_head_fwd_in *in, const elimrec_head_weights *w, const int32_t *d_act,
+                                      const int32_t *d_seg_info, int64_t R, float *d_OutAct, int64_t ld_out, float *d_YAct,
+                                      int64_t ld_y, int phase, void *stream) {
+    ELIMREC_REQUIRE(in && w, "head_fwd_fused: null pointer");
+    const elimrec_head_src16 *src = in->src16.d_table ? &in->src16 : nullptr;
+    const elimrec_head_rows *rows = in->rows.A ? &in->rows : nullptr;
+    const int peer_world = in->d_recv ? in->world : 0;
+    const int64_t peer_dl = in->dl;
+    ELIMREC_REQUIRE((src != nullptr) + (rows != nullptr) + (in->d_recv != nullptr) <= 1, "head_fwd_fused: one input form at a time");
+    const float *d_out0 = in->d_out0, *d_narrow = in->d_narrow;
+    int64_t ld_out0 = in->ld_out0, ld_nar = in->ld_nar;
+    if (in->d_recv) {
+        ELIMREC_REQUIRE(peer_world > 0 && peer_dl > 0 && (phase == 0 || phase == 2 || phase == 4), "head_fwd_fused_peers: a received buffer, phase 0, 2 or 4");
+        d_out0 = in->d_recv; d_narrow = in->d_recv + peer_dl; ld_out0 = ld_nar = 2 * peer_dl;
+    } else if (rows) {
+        // (out0 / narrow of the plain form are the buffers this launch fills itself: block 0 of OutAct and rows->d_narrow_out)
+        d_out0 = d_OutAct; ld_out0 = ld_out; d_narrow = rows->d_narrow_out; ld_nar = rows->ld_narrow_out;
+        phase = 4;
+    }
+    const int n_mod = w->n_mod;
+    const int *D = w->D;
+    ELIMREC_REQUIRE(d_act && d_seg_info && d_out0 && d_narrow && (src || in->d_c) && w->d_Wf_user && w->d_Wf_item && w->d_pack &&
                         d_OutAct && d_YAct, "head_fwd_fused: null pointer");
-    ELIMREC_REQUIRE(!src || (src->d_table && (src->dtype == 1 || src->dtype == 2) && src->row_elems % 8 == 0 &&
-                             (!src->d_S_out || src->ld_S_out % 4 == 0)),
+    ELIMREC_REQUIRE(!src || ((src->dtype == 1 || src->dtype == 2) && src->row_elems % 8 == 0 && (!src->d_S_out || src->ld_S_out % 4 == 0)),
                     "head_fwd_fused_src16: a table of fp16 (1) / bf16 (2) rows, 16-byte aligned rows");
-    if (recdim != HD || n_mod < 1 || n_mod > HMAXM) { set_error("head_fwd_fused: recdim must be %d and 1..%d feature tables", HD, HMAXM); return ELIMREC_E_UNSUPPORTED; }
+    if (w->recdim != HD || n_mod < 1 || n_mod > HMAXM) { set_error("head_fwd_fused: recdim must be %d and 1..%d feature tables", HD, HMAXM); return ELIMREC_E_UNSUPPORTED; }
     const int C = (1 + n_mod) * HD;
     ELIMREC_REQUIRE(ld_out0 % 4 == 0 && ld_nar % 4 == 0 && ld_out >= C && ld_y >= C, "head_fwd_fused: bad leading dimensions");
-    ELIMREC_REQUIRE(pack_floats >= elimrec_head_pack_floats(n_mod, D), "head_fwd_fused: packed-weight buffer too small");
+    ELIMREC_REQUIRE(w->pack_floats >= elimrec_head_pack_floats(n_mod, D), "head_fwd_fused: packed-weight buffer too small");
     ELIMREC_REQUIRE(phase >= 0 && phase <= 4, "head_fwd_fused: phase 0 (pack + head), 1 (pack only), 2 (head only), 3 / 4 (head in two launches)");
     if (R <= 0) return 0;
     HeadFwdArgs a = {};
@@ -309,21 +327,21 @@ static int head_fwd_fused_impl(int peer_world, int64_t peer_dl, const elimrec_he
     auto add_job = [&](const float *W, int K) { return add_job_g(W, HD, K, K, 1); };
     constexpr int rows_t = H16;
     for (int m = 0; m < n_mod; ++m) {
-        ELIMREC_REQUIRE((src || (d_S[m] && ldS[m] % 4 == 0)) && d_Wm[m] && d_Ws[m] && D[m] > 0 && D[m] % 4 == 0, "head_fwd_fused: bad feature table %d", m);
-        if (!src) { a.S[m] = d_S[m]; a.ldS[m] = ldS[m]; }
+        ELIMREC_REQUIRE((src || (in->d_S[m] && in->ldS[m] % 4 == 0)) && w->d_Wm[m] && w->d_Ws[m] && D[m] > 0 && D[m] % 4 == 0, "head_fwd_fused: bad feature table %d", m);
+        if (!src) { a.S[m] = in->d_S[m]; a.ldS[m] = in->ldS[m]; }
         a.s_off[m] = m == 0 ? 0 : a.s_off[m - 1] + D[m - 1];
-        a.D[m] = D[m]; a.bias_m[m] = d_bm ? d_bm[m] : nullptr;
+        a.D[m] = D[m]; a.bias_m[m] = w->d_bm[m];
         a.a_off[m] = lds_f;
         lds_f += rows_t * (D[m] + 4);
-        a.off_Wm[m] = add_job(d_Wm[m], D[m]);
+        a.off_Wm[m] = add_job(w->d_Wm[m], D[m]);
     }
-    a.off_Wf[0] = add_job(d_Wf_user, C);
-    a.off_Wf[1] = add_job(d_Wf_item, C);
-    for (int m = 0; m < n_mod; ++m) { a.off_Ws[m] = add_job(d_Ws[m], HD); a.bias_s[m] = d_bs ? d_bs[m] : nullptr; }
+    a.off_Wf[0] = add_job(w->d_Wf_user, C);
+    a.off_Wf[1] = add_job(w->d_Wf_item, C);
+    for (int m = 0; m < n_mod; ++m) { a.off_Ws[m] = add_job(w->d_Ws[m], HD); a.bias_s[m] = w->d_bs[m]; }
     // the head backward's operands B[k][c] = W[k][c] (common.h: head_pack_layout)
-    add_job_g(d_Wf_user, C, HD, 1, C);
-    add_job_g(d_Wf_item, C, HD, 1, C);
-    for (int m = 0; m < n_mod; ++m) add_job_g(d_Ws[m], HD, HD, 1, HD);
+    add_job_g(w->d_Wf_user, C, HD, 1, C);
+    add_job_g(w->d_Wf_item, C, HD, 1, C);
+    for (int m = 0; m < n_mod; ++m) add_job_g(w->d_Ws[m], HD, HD, 1, HD);
     ELIMREC_REQUIRE(off == head_pack_layout(n_mod, D).total, "head_fwd_fused: pack layout mismatch");
     pj.first_block[pj.n] = blocks;
     a.out_off = lds_f; lds_f += rows_t * (C + 4);
@@ -342,7 +360,7 @@ static int head_fwd_fused_impl(int peer_world, int64_t peer_dl, const elimrec_he
     }
     const size_t lds_bytes = (size_t)lds_f * sizeof(float);
     if (lds_bytes > 158 * 1024) { set_error("head_fwd_fused: feature widths need %zu B of LDS", lds_bytes); return ELIMREC_E_UNSUPPORTED; }
-    a.act = d_act; a.seg_info = d_seg_info; a.out0 = d_out0; a.ld_out0 = ld_out0; a.narrow = d_narrow; a.ld_nar = ld_nar; a.c = d_c;
+    a.act = d_act; a.seg_info = d_seg_info; a.out0 = d_out0; a.ld_out0 = ld_out0; a.narrow = d_narrow; a.ld_nar = ld_nar; a.c = in->d_c;
     if (peer_world > 0) {
         ELIMREC_REQUIRE(!rows && peer_dl > 0 && peer_dl % 4 == 0 && peer_world * peer_dl == HD && ld_out0 == 2 * peer_dl && ld_nar == ld_out0,
                         "head_fwd_fused_peers: %d peers x %lld columns (a multiple of 4) must make the %d columns of a row", peer_world, (long long)peer_dl, HD);
@@ -354,12 +372,12 @@ static int head_fwd_fused_impl(int peer_world, int64_t peer_dl, const elimrec_he
         ELIMREC_REQUIRE(a.c_off + 2 <= src->row_elems && a.c_off % 2 == 0, "head_fwd_fused_src16: rows shorter than sum(D) + 2 elements");
         a.s_out = src->d_S_out; a.ld_sout = src->ld_S_out; a.c_out = src->d_c_out;
     }
-    a.n_mod = n_mod; a.pk = d_pack; a.bias_f[0] = d_bf_user; a.bias_f[1] = d_bf_item;
+    a.n_mod = n_mod; a.pk = w->d_pack; a.bias_f[0] = w->d_bf_user; a.bias_f[1] = w->d_bf_item;
     a.OutAct = d_OutAct; a.ld_out = ld_out; a.YAct = d_YAct; a.ld_y = ld_y;
     hipStream_t s = (hipStream_t)stream;
     a.stage = phase == 3 ? 1 : (phase == 4 ? 2 : 0);
     if (phase < 2) {
-        hipLaunchKernelGGL(pack_head_weights16_kernel, dim3((unsigned)blocks), dim3(256), 0, s, pj, d_pack);
+        hipLaunchKernelGGL(pack_head_weights16_kernel, dim3((unsigned)blocks), dim3(256), 0, s, pj, w->d_pack);
         ELIMREC_LAUNCH_CHECK("pack_head_weights");
     }
     if (phase == 1) return 0;
@@ -392,55 +410,3 @@ static int head_fwd_fused_impl(int peer_world, int64_t peer_dl, const elimrec_he
     return 0;
 }
 
-extern "C" int elimrec_head_fwd_fused(const int32_t *d_act, const int32_t *d_seg_info, int64_t R, const float *d_out0,
-                                      int64_t ld_out0, const float *d_narrow, int64_t ld_nar, const float *d_c, int n_mod,
-                                      const float *const *d_S, const int64_t *ldS, const int *D, const float *const *d_Wm,
-                                      const float *const *d_bm, const float *d_Wf_user, const float *d_bf_user,
-                                      const float *d_Wf_item, const float *d_bf_item, const float *const *d_Ws,
-                                      const float *const *d_bs, float *d_pack, size_t pack_floats, float *d_OutAct,
-                                      int64_t ld_out, float *d_YAct, int64_t ld_y, int recdim, int phase, void *stream) {
-    return head_fwd_fused_impl(0, 0, nullptr, nullptr, d_act, d_seg_info, R, d_out0, ld_out0, d_narrow, ld_nar, d_c, n_mod, d_S, ldS, D, d_Wm, d_bm,
-                               d_Wf_user, d_bf_user, d_Wf_item, d_bf_item, d_Ws, d_bs, d_pack, pack_floats, d_OutAct, ld_out, d_YAct,
-                               ld_y, recdim, phase, stream);
-}
-
-// ... with out0 / narrow read where the forward exchange of the column shards left them: d_recv = [world][R][out0 dl | narrow dl],
-// peer q's columns of MY rows (ops.peer_cols_to_rows + elimrec_head_fwd_fused without the pass in between; same bits).
-extern "C" int elimrec_head_fwd_fused_peers(const int32_t *d_act, const int32_t *d_seg_info, int64_t R, const float *d_recv, int world,
-                                            int64_t dl, const float *d_c, int n_mod, const float *const *d_S, const int64_t *ldS,
-                                            const int *D, const float *const *d_Wm, const float *const *d_bm, const float *d_Wf_user,
-                                            const float *d_bf_user, const float *d_Wf_item, const float *d_bf_item,
-                                            const float *const *d_Ws, const float *const *d_bs, float *d_pack, size_t pack_floats,
-                                            float *d_OutAct, int64_t ld_out, float *d_YAct, int64_t ld_y, int recdim, int phase, void *stream) {
-    ELIMREC_REQUIRE(d_recv && world > 0 && dl > 0 && (phase == 0 || phase == 2 || phase == 4), "head_fwd_fused_peers: a received buffer, phase 0, 2 or 4");
-    return head_fwd_fused_impl(world, dl, nullptr, nullptr, d_act, d_seg_info, R, d_recv, 2 * dl, d_recv + dl, 2 * dl, d_c, n_mod, d_S, ldS, D,
-                               d_Wm, d_bm, d_Wf_user, d_bf_user, d_Wf_item, d_bf_item, d_Ws, d_bs, d_pack, pack_floats, d_OutAct, ld_out,
-                               d_YAct, ld_y, recdim, phase, stream);
-}
-
-// ... with the feature constants read from their 16-bit storage (lookup.hip's packed rows, one rank holding every row): see
-// HeadFwdArgs::sdtype. Same phases; the same bits as elimrec_lookup_unpack(direct) followed by elimrec_head_fwd_fused on its rows.
-extern "C" int elimrec_head_fwd_fused_src16(const elimrec_head_src16 *src, const int32_t *d_act, const int32_t *d_seg_info, int64_t R,
-                                            const float *d_out0, int64_t ld_out0, const float *d_narrow, int64_t ld_nar, int n_mod,
-                                            const int *D, const float *const *d_Wm, const float *const *d_bm, const float *d_Wf_user,
-                                            const float *d_bf_user, const float *d_Wf_item, const float *d_bf_item,
-                                            const float *const *d_Ws, const float *const *d_bs, float *d_pack, size_t pack_floats,
-                                            float *d_OutAct, int64_t ld_out, float *d_YAct, int64_t ld_y, int recdim, int phase, void *stream) {
-    ELIMREC_REQUIRE(src, "head_fwd_fused_src16: null source");
-    return head_fwd_fused_impl(0, 0, src, nullptr, d_act, d_seg_info, R, d_out0, ld_out0, d_narrow, ld_nar, nullptr, n_mod, nullptr, nullptr, D, d_Wm,
-                               d_bm, d_Wf_user, d_bf_user, d_Wf_item, d_bf_item, d_Ws, d_bs, d_pack, pack_floats, d_OutAct, ld_out, d_YAct,
-                               ld_y, recdim, phase, stream);
-}
-
-extern "C" int elimrec_head_fwd_fused_rows(const elimrec_head_rows *rows, const int32_t *d_act, const int32_t *d_seg_info, int64_t R,
-                                           const float *d_c, int n_mod, const float *const *d_S, const int64_t *ldS, const int *D,
-                                           const float *const *d_Wm, const float *const *d_bm, const float *d_Wf_user,
-                                           const float *d_bf_user, const float *d_Wf_item, const float *d_bf_item,
-                                           const float *const *d_Ws, const float *const *d_bs, float *d_pack, size_t pack_floats,
-                                           float *d_OutAct, int64_t ld_out, float *d_YAct, int64_t ld_y, int recdim, void *stream) {
-    ELIMREC_REQUIRE(rows && d_OutAct, "head_fwd_fused_rows: null pointer");
-    // (out0 / narrow of the plain entry are the buffers this launch fills itself: block 0 of OutAct and rows->d_narrow_out)
-    return head_fwd_fused_impl(0, 0, nullptr, rows, d_act, d_seg_info, R, d_OutAct, ld_out, rows->d_narrow_out, rows->ld_narrow_out, d_c, n_mod, d_S, ldS, D,
-                               d_Wm, d_bm, d_Wf_user, d_bf_user, d_Wf_item, d_bf_item, d_Ws, d_bs, d_pack, pack_floats, d_OutAct, ld_out,
-                               d_YAct, ld_y, recdim, 4, stream);
-}

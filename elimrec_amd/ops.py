@@ -426,40 +426,35 @@ def bpr_head(Y, U, I, users, pos, neg, d, block_weights, loss_rows, grad_rows=No
                "bpr_head")
 
 
-def bpr_head_rows(Y, slot_rows, d, block_weights, loss_rows, grad_rows=None):
-    """bpr_head over a compact table: slot 3b+j of triplet b reads row slot_rows[3b+j] of Y."""
+def _bpr_head_rows(Y, slot_rows, d, block_weights, loss_rows, grad_rows, loss_out, ticket, pub, what):
     y, ldy = _rowmajor(Y, "Y")
     nb = len(block_weights)
     w = (ctypes.c_float * nb)(*[float(x) for x in block_weights])
     B = slot_rows.numel() // 3
     _lib.check(_lib.load().elimrec_bpr_head_rows(y, ldy, _dev(slot_rows, "slot_rows", torch.int32), B, d, nb, w,
-                                                 _dev(loss_rows, "loss_rows"), _dev(grad_rows, "grad_rows"), _stream()),
-               "bpr_head_rows")
+                                                 _dev(loss_rows, "loss_rows"), _dev(grad_rows, "grad_rows"),
+                                                 _dev(loss_out, "loss_out"), _dev(ticket, "ticket", torch.int32), pub, _stream()),
+               what)
+
+
+def bpr_head_rows(Y, slot_rows, d, block_weights, loss_rows, grad_rows=None):
+    """bpr_head over a compact table: slot 3b+j of triplet b reads row slot_rows[3b+j] of Y."""
+    _bpr_head_rows(Y, slot_rows, d, block_weights, loss_rows, grad_rows, None, None, None, "bpr_head_rows")
 
 
 def bpr_head_rows_sum(Y, slot_rows, d, block_weights, loss_rows, grad_rows, loss_out, ticket):
     """bpr_head_rows + the fixed-order sum of its loss rows into loss_out (0-dim / 1-element fp32) in one launch; ticket: a
     zero-initialised int32 the kernel leaves at zero."""
-    y, ldy = _rowmajor(Y, "Y")
-    nb = len(block_weights)
-    w = (ctypes.c_float * nb)(*[float(x) for x in block_weights])
-    B = slot_rows.numel() // 3
-    _lib.check(_lib.load().elimrec_bpr_head_rows_sum(y, ldy, _dev(slot_rows, "slot_rows", torch.int32), B, d, nb, w,
-                                                     _dev(loss_rows, "loss_rows"), _dev(grad_rows, "grad_rows"),
-                                                     _dev(loss_out, "loss_out"), _dev(ticket, "ticket", torch.int32), _stream()),
-               "bpr_head_rows_sum")
+    if loss_out is None or ticket is None:
+        raise ValueError("bpr_head_rows_sum: loss_out and ticket are required")
+    _bpr_head_rows(Y, slot_rows, d, block_weights, loss_rows, grad_rows, loss_out, ticket, None, "bpr_head_rows_sum")
 
 
 def bpr_head_rows_sum_pub(Y, slot_rows, d, block_weights, loss_rows, grad_rows, loss_out, ticket, pub):
     """bpr_head_rows_sum whose summing workgroup also publishes the loss to the host (pub: LossPublisher.handle)."""
-    y, ldy = _rowmajor(Y, "Y")
-    nb = len(block_weights)
-    w = (ctypes.c_float * nb)(*[float(x) for x in block_weights])
-    B = slot_rows.numel() // 3
-    _lib.check(_lib.load().elimrec_bpr_head_rows_sum_pub(y, ldy, _dev(slot_rows, "slot_rows", torch.int32), B, d, nb, w,
-                                                         _dev(loss_rows, "loss_rows"), _dev(grad_rows, "grad_rows"),
-                                                         _dev(loss_out, "loss_out"), _dev(ticket, "ticket", torch.int32), pub, _stream()),
-               "bpr_head_rows_sum_pub")
+    if loss_out is None or ticket is None or not pub:
+        raise ValueError("bpr_head_rows_sum_pub: loss_out, ticket and pub are required")
+    _bpr_head_rows(Y, slot_rows, d, block_weights, loss_rows, grad_rows, loss_out, ticket, pub, "bpr_head_rows_sum_pub")
 
 
 class LossPublisher(object):
@@ -567,7 +562,7 @@ def segment_apply_head_bwd(rows, active_rows, seg_info, reduced, plan_workspace,
     """segment_apply + head_bwd_input(compact=...) in one launch; `reduced` receives dY. pack_bwd: the backward region of
     the fused head's packed weights (a view starting at head_pack_bwd_offset floats), if the forward left it behind.
     sources = (srcA, srcB) slab tables: the kernel also fills the adjoint sources at the active rows (one rank, recdim 64,
-    packed weights: elimrec_segment_apply_head_bwd_sources); ("split", send, world): the peers' [H | G] column slices."""
+    packed weights: elimrec_head_bwd_sinks); ("split", send, world): the peers' [H | G] column slices."""
     n, ld = rows.shape
     S = len(W_heads)
     assert rows.is_contiguous() and reduced.is_contiguous() and reduced.shape[1] == ld and compact.is_contiguous()
@@ -576,38 +571,21 @@ def segment_apply_head_bwd(rows, active_rows, seg_info, reduced, plan_workspace,
     wp = (ctypes.c_void_p * max(S, 1))(*[_dev(w, "W_head") for w in W_heads]) if S else (ctypes.c_void_p * 1)(None)
     for w in list(W_heads) + [W_user, W_item]:
         assert w.is_contiguous()
+    sinks = None
     if sources is not None and sources[0] == "split":          # ("split", send [W x n_max x 2*dl], W)
         _, send, world = sources
         assert pack_bwd is not None and send.is_contiguous() and send.shape == (world, send.shape[1], 2 * (d // world)) and send.shape[1] >= n
-        _lib.check(_lib.load().elimrec_segment_apply_head_bwd_split(
-            _dev(rows, "rows"), n, ld, _dev(active_rows, "active_rows", torch.int32), _dev(seg_info, "seg_info", torch.int32),
-            _dev(scale, "scale"), _dev(reduced, "reduced"), _dev(plan_workspace, "plan_workspace", torch.uint8),
-            plan_workspace.numel(), U, d, C, S, mb, _dev(W_user, "W_user"), _dev(W_item, "W_item"), wp,
-            _dev(compact, "compact"), _dev(pack_bwd, "pack_bwd"), send.shape[1], int(world), _dev(send, "send"), _stream()),
-            "segment_apply_head_bwd_split")
-        return
-    if sources is not None:
+        sinks = _lib.HeadBwdSinks(d_split=_dev(send, "send"), n_max=send.shape[1], world=int(world))
+    elif sources is not None:
         srcA, srcB = sources
         assert pack_bwd is not None and srcA.ns == srcB.ns and srcA.w == srcB.w and srcA.n == srcB.n
-        _lib.check(_lib.load().elimrec_segment_apply_head_bwd_sources(
-            _dev(rows, "rows"), n, ld, _dev(active_rows, "active_rows", torch.int32), _dev(seg_info, "seg_info", torch.int32),
-            _dev(scale, "scale"), _dev(reduced, "reduced"), _dev(plan_workspace, "plan_workspace", torch.uint8),
-            plan_workspace.numel(), U, d, C, S, mb, _dev(W_user, "W_user"), _dev(W_item, "W_item"), wp,
-            _dev(compact, "compact"), _dev(pack_bwd, "pack_bwd"), srcA.n, srcA.ns, srcA.w, _dev(srcA.data, "srcA"),
-            _dev(srcB.data, "srcB"), _stream()), "segment_apply_head_bwd_sources")
-        return
-    if pack_bwd is not None:
-        _lib.check(_lib.load().elimrec_segment_apply_head_bwd_packed(
-            _dev(rows, "rows"), n, ld, _dev(active_rows, "active_rows", torch.int32), _dev(seg_info, "seg_info", torch.int32),
-            _dev(scale, "scale"), _dev(reduced, "reduced"), _dev(plan_workspace, "plan_workspace", torch.uint8),
-            plan_workspace.numel(), U, d, C, S, mb, _dev(W_user, "W_user"), _dev(W_item, "W_item"), wp,
-            _dev(compact, "compact"), _dev(pack_bwd, "pack_bwd"), _stream()), "segment_apply_head_bwd_packed")
-        return
+        sinks = _lib.HeadBwdSinks(d_SrcA=_dev(srcA.data, "srcA"), d_SrcB=_dev(srcB.data, "srcB"), N=srcA.n, ns=srcA.ns, w=srcA.w)
     _lib.check(_lib.load().elimrec_segment_apply_head_bwd(
         _dev(rows, "rows"), n, ld, _dev(active_rows, "active_rows", torch.int32), _dev(seg_info, "seg_info", torch.int32),
         _dev(scale, "scale"), _dev(reduced, "reduced"), _dev(plan_workspace, "plan_workspace", torch.uint8),
         plan_workspace.numel(), U, d, C, S, mb, _dev(W_user, "W_user"), _dev(W_item, "W_item"), wp,
-        _dev(compact, "compact"), _stream()), "segment_apply_head_bwd")
+        _dev(compact, "compact"), _dev(pack_bwd, "pack_bwd"), None if sinks is None else ctypes.byref(sinks), _stream()),
+        "segment_apply_head_bwd")
 
 
 def embed_grad(G, U, I, d, M, grad_user, grad_item):
@@ -1051,13 +1029,41 @@ def head_pack_bwd_offset(dims):
     return int(_lib.load().elimrec_head_pack_bwd_offset(len(dims), arr))
 
 
+def _head_weights(D, Wm, bm, Wf_user, bf_user, Wf_item, bf_item, Ws, bs, pack, d):
+    """struct elimrec_head_weights of the lists over the feature tables (more tables than the struct holds: n_mod says so and
+    the library answers ELIMREC_E_UNSUPPORTED)."""
+    for t in list(Wm) + list(Ws) + [Wf_user, Wf_item]:
+        assert t.is_contiguous()
+    hw = _lib.HeadWeights(n_mod=len(D), recdim=int(d), d_Wf_user=_dev(Wf_user, "Wf_user"), d_bf_user=_dev(bf_user, "bf_user"),
+                          d_Wf_item=_dev(Wf_item, "Wf_item"), d_bf_item=_dev(bf_item, "bf_item"), d_pack=_dev(pack, "pack"),
+                          pack_floats=pack.numel())
+    for m in range(min(len(D), _lib.HEAD_MAX_TABLES)):
+        hw.D[m] = D[m]
+        hw.d_Wm[m], hw.d_bm[m], hw.d_Ws[m], hw.d_bs[m] = (_dev(ts[m], "table") for ts in (Wm, bm, Ws, bs))
+    return hw
+
+
+def _head_fwd_fused(hin, hw, act, seg_info, OutAct, YAct, phase, what, c=None, S=()):
+    """The one call behind the four head_fwd_fused* forms. c / S: the fp32 constants of the forms that read them. Returns False
+    when the shape is outside the fused kernel's range."""
+    hin.d_c = _dev(c, "c")
+    for m, t in enumerate(S[:_lib.HEAD_MAX_TABLES]):
+        hin.d_S[m], hin.ldS[m] = _dev(t, "table"), t.stride(0)
+    rc = _lib.load().elimrec_head_fwd_fused(
+        ctypes.byref(hin), ctypes.byref(hw), _dev(act, "act", torch.int32), _dev(seg_info, "seg_info", torch.int32), act.numel(),
+        _dev(OutAct, "OutAct"), OutAct.stride(0), _dev(YAct, "YAct"), YAct.stride(0), int(phase), _stream())
+    if rc == 10002:           # ELIMREC_E_UNSUPPORTED
+        return False
+    _lib.check(rc, what)
+    return True
+
+
 def head_fwd_fused_rows(rows, act, seg_info, c, S, Wm, bm, Wf_user, bf_user, Wf_item, bf_item, Ws, bs, pack, OutAct, YAct, d):
-    """elimrec_head_fwd_fused_rows: phase 4 of head_fwd_fused with the rows launch folded in. rows: dict(plan, ns, w, L, U,
-    layers (L + 1 flat tensors, the last may be None), long_tab, narrow). Returns (ok, the host struct the call read -- kept by
-    the caller for as long as a recorded program refers to it)."""
-    n = len(S)
-    R = act.numel()
-    hr = _lib.HeadRows()
+    """elimrec_head_fwd_fused, rows form: phase 4 of head_fwd_fused with the rows launch folded in. rows: dict(plan, ns, w, L, U,
+    layers (L + 1 flat tensors, the last may be None), long_tab, narrow). Returns False when the shape is outside the fused
+    kernel's range."""
+    hin = _lib.HeadFwdIn()
+    hr = hin.rows
     hr.A = ctypes.pointer(rows["plan"].desc)
     hr.ns, hr.w, hr.L, hr.U = int(rows["ns"]), int(rows["w"]), int(rows["L"]), int(rows["U"])
     for k, t in enumerate(rows["layers"]):
@@ -1066,18 +1072,8 @@ def head_fwd_fused_rows(rows, act, seg_info, c, S, Wm, bm, Wf_user, bf_user, Wf_
     nar = rows["narrow"]
     assert nar.stride(1) == 1
     hr.d_narrow_out, hr.ld_narrow_out = _dev(nar, "narrow"), nar.stride(0)
-    ptr = lambda ts: (ctypes.c_void_p * max(n, 1))(*[_dev(t, "table") for t in ts])
-    ldS = (ctypes.c_int64 * max(n, 1))(*[t.stride(0) for t in S])
-    D = (ctypes.c_int * max(n, 1))(*[t.shape[1] for t in S])
-    rc = _lib.load().elimrec_head_fwd_fused_rows(
-        ctypes.byref(hr), _dev(act, "act", torch.int32), _dev(seg_info, "seg_info", torch.int32), R, _dev(c, "c"), n, ptr(S), ldS, D,
-        ptr(Wm), ptr(bm), _dev(Wf_user, "Wf_user"), _dev(bf_user, "bf_user"), _dev(Wf_item, "Wf_item"), _dev(bf_item, "bf_item"),
-        ptr(Ws), ptr(bs), _dev(pack, "pack"), pack.numel(), _dev(OutAct, "OutAct"), OutAct.stride(0), _dev(YAct, "YAct"),
-        YAct.stride(0), int(d), _stream())
-    if rc == 10002:           # ELIMREC_E_UNSUPPORTED
-        return False
-    _lib.check(rc, "head_fwd_fused_rows")
-    return True
+    hw = _head_weights([t.shape[1] for t in S], Wm, bm, Wf_user, bf_user, Wf_item, bf_item, Ws, bs, pack, d)
+    return _head_fwd_fused(hin, hw, act, seg_info, OutAct, YAct, 4, "head_fwd_fused_rows", c, S)
 
 
 def head_fwd_fused(act, seg_info, out0, narrow, c, S, Wm, bm, Wf_user, bf_user, Wf_item, bf_item, Ws, bs, pack, OutAct, YAct, d, phase=0,
@@ -1086,58 +1082,29 @@ def head_fwd_fused(act, seg_info, out0, narrow, c, S, Wm, bm, Wf_user, bf_user, 
     run the head; 1: pack only; 2: head only (pack holds the packed weights); 3 / 4: the head in two launches (the feature
     blocks without the shared part -- no out0 / narrow needed --, then the rest). Returns False when the shape is outside the
     fused kernel's range (the caller keeps the batched GEMMs). peers: the forward exchange's received buffer [W, R, 2 * dl]
-    (out0 | narrow pieces of every peer) read in place of out0 / narrow (elimrec_head_fwd_fused_peers)."""
-    n = len(S)
-    R = act.numel()
-    ptr = lambda ts: (ctypes.c_void_p * max(n, 1))(*[_dev(t, "table") for t in ts])
-    ldS = (ctypes.c_int64 * max(n, 1))(*[t.stride(0) for t in S])
-    D = (ctypes.c_int * max(n, 1))(*[t.shape[1] for t in S])
-    for w in list(Wm) + list(Ws) + [Wf_user, Wf_item]:
-        assert w.is_contiguous()
+    (out0 | narrow pieces of every peer) read in place of out0 / narrow (elimrec_head_fwd_in::d_recv)."""
+    hw = _head_weights([t.shape[1] for t in S], Wm, bm, Wf_user, bf_user, Wf_item, bf_item, Ws, bs, pack, d)
     if peers is not None:
-        assert peers.dim() == 3 and peers.is_contiguous() and peers.shape[1] == R and peers.shape[2] % 2 == 0
-        rc = _lib.load().elimrec_head_fwd_fused_peers(
-            _dev(act, "act", torch.int32), _dev(seg_info, "seg_info", torch.int32), R, _dev(peers, "peers"), peers.shape[0],
-            peers.shape[2] // 2, _dev(c, "c"), n, ptr(S), ldS, D, ptr(Wm), ptr(bm), _dev(Wf_user, "Wf_user"),
-            _dev(bf_user, "bf_user"), _dev(Wf_item, "Wf_item"), _dev(bf_item, "bf_item"), ptr(Ws), ptr(bs), _dev(pack, "pack"),
-            pack.numel(), _dev(OutAct, "OutAct"), OutAct.stride(0), _dev(YAct, "YAct"), YAct.stride(0), int(d), int(phase), _stream())
-        if rc == 10002:
-            return False
-        _lib.check(rc, "head_fwd_fused_peers")
-        return True
-    rc = _lib.load().elimrec_head_fwd_fused(
-        _dev(act, "act", torch.int32), _dev(seg_info, "seg_info", torch.int32), R, _dev(out0, "out0"), out0.stride(0),
-        _dev(narrow, "narrow"), narrow.stride(0), _dev(c, "c"), n, ptr(S), ldS, D, ptr(Wm), ptr(bm), _dev(Wf_user, "Wf_user"),
-        _dev(bf_user, "bf_user"), _dev(Wf_item, "Wf_item"), _dev(bf_item, "bf_item"), ptr(Ws), ptr(bs), _dev(pack, "pack"),
-        pack.numel(), _dev(OutAct, "OutAct"), OutAct.stride(0), _dev(YAct, "YAct"), YAct.stride(0), int(d), int(phase), _stream())
-    if rc == 10002:           # ELIMREC_E_UNSUPPORTED
-        return False
-    _lib.check(rc, "head_fwd_fused")
-    return True
+        assert peers.dim() == 3 and peers.is_contiguous() and peers.shape[1] == act.numel() and peers.shape[2] % 2 == 0
+        hin = _lib.HeadFwdIn(d_recv=_dev(peers, "peers"), world=peers.shape[0], dl=peers.shape[2] // 2)
+        return _head_fwd_fused(hin, hw, act, seg_info, OutAct, YAct, phase, "head_fwd_fused_peers", c, S)
+    hin = _lib.HeadFwdIn(d_out0=_dev(out0, "out0"), ld_out0=out0.stride(0), d_narrow=_dev(narrow, "narrow"), ld_nar=narrow.stride(0))
+    return _head_fwd_fused(hin, hw, act, seg_info, OutAct, YAct, phase, "head_fwd_fused", c, S)
 
 
 def head_fwd_fused_src16(fshard, S_out, c_out, act, seg_info, out0, narrow, Wm, bm, Wf_user, bf_user, Wf_item, bf_item, Ws, bs, pack,
                          OutAct, YAct, d, phase=0):
-    """elimrec_head_fwd_fused_src16: head_fwd_fused with the feature constants read from `fshard`'s 16-bit rows (lookup.FeatureShard
-    holding EVERY row: one rank); S_out [R x sum_d] / c_out [R] (or None) receive the widened rows of the active nodes."""
-    n = len(fshard.dims)
-    R = act.numel()
-    src = _lib.HeadSrc16()
+    """elimrec_head_fwd_fused, 16-bit source: head_fwd_fused with the feature constants read from `fshard`'s 16-bit rows
+    (lookup.FeatureShard holding EVERY row: one rank); S_out [R x sum_d] / c_out [R] (or None) receive the widened rows of the
+    active nodes."""
+    hin = _lib.HeadFwdIn(d_out0=_dev(out0, "out0"), ld_out0=out0.stride(0), d_narrow=_dev(narrow, "narrow"), ld_nar=narrow.stride(0))
+    src = hin.src16
     src.d_table, src.row_elems, src.dtype = fshard.table.data_ptr(), fshard.row_elems, fshard.code
     if S_out is not None:
-        assert S_out.stride(1) == 1 and S_out.shape[0] >= R and S_out.shape[1] == fshard.sum_d and c_out.numel() >= R
+        assert S_out.stride(1) == 1 and S_out.shape[0] >= act.numel() and S_out.shape[1] == fshard.sum_d and c_out.numel() >= act.numel()
         src.d_S_out, src.ld_S_out, src.d_c_out = _dev(S_out, "S_out"), S_out.stride(0), _dev(c_out, "c_out")
-    ptr = lambda ts: (ctypes.c_void_p * max(n, 1))(*[_dev(t, "table") for t in ts])
-    D = (ctypes.c_int * max(n, 1))(*fshard.dims)
-    rc = _lib.load().elimrec_head_fwd_fused_src16(
-        ctypes.byref(src), _dev(act, "act", torch.int32), _dev(seg_info, "seg_info", torch.int32), R, _dev(out0, "out0"), out0.stride(0),
-        _dev(narrow, "narrow"), narrow.stride(0), n, D, ptr(Wm), ptr(bm), _dev(Wf_user, "Wf_user"), _dev(bf_user, "bf_user"),
-        _dev(Wf_item, "Wf_item"), _dev(bf_item, "bf_item"), ptr(Ws), ptr(bs), _dev(pack, "pack"), pack.numel(), _dev(OutAct, "OutAct"),
-        OutAct.stride(0), _dev(YAct, "YAct"), YAct.stride(0), int(d), int(phase), _stream())
-    if rc == 10002:           # ELIMREC_E_UNSUPPORTED
-        return False
-    _lib.check(rc, "head_fwd_fused_src16")
-    return True
+    hw = _head_weights(fshard.dims, Wm, bm, Wf_user, bf_user, Wf_item, bf_item, Ws, bs, pack, d)
+    return _head_fwd_fused(hin, hw, act, seg_info, OutAct, YAct, phase, "head_fwd_fused_src16")
 
 
 def peer_cols_to_rows(recv, out0, out1):

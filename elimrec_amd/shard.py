@@ -807,7 +807,7 @@ class ColumnShardEngine(object):
             self.lookup_row_bytes = self.fshard.row_bytes
             self._lookup_bufs = {}
         # ONE rank holding every row of 16-bit constants: the fused head reads them where they lie and widens in registers
-        # (elimrec_head_fwd_fused_src16) -- no widening pass over the batch's rows in front of the head, and the step keeps the
+        # (elimrec_head_fwd_fused (16-bit source form)) -- no widening pass over the batch's rows in front of the head, and the step keeps the
         # shape of the fp32 one (feature blocks beside the forward hops, rows evaluated by the head's launch); the head's feature
         # launch leaves the widened rows behind for the backward half's weight gradients
         self._direct16 = bool(self.lookup and self.fshard is not None and self.fshard.code != 0 and not self.multi
@@ -1260,7 +1260,7 @@ class ColumnShardEngine(object):
                 assert not by_node
                 slab.wide_rows([t.data for t in tabs], tabs[0].n, self.ns, self.w, acts.reshape(-1), W * R, out0, narrow)
             elif self._rows_in_head:
-                pass                  # the head's launch evaluates the rows itself (cs_head: elimrec_head_fwd_fused_rows)
+                pass                  # the head's launch evaluates the rows itself (cs_head: elimrec_head_fwd_fused (rows form))
             else:
                 slab.rows(self.plan, self.ns, self.w, L, U, [t.data for t in tabs] + [None], self.long_tab, acts, counts, R, W,
                           out0, narrow, by_node)

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define ELIMREC_ABI_VERSION 1
+#define ELIMREC_ABI_VERSION 2
 #define ELIMREC_E_BADARG 10001
 #define ELIMREC_E_UNSUPPORTED 10002
 #define ELIMREC_E_WORKSPACE 10003
@@ -293,32 +293,27 @@ int elimrec_bpr_head(const float *d_Y, int64_t ldy, int64_t U, int64_t I,
                      float *d_loss_rows, float *d_grad_rows, int32_t *d_keys, void *stream);
 
 /* The same loss over a COMPACT table: slot 3b+j of triplet b reads row d_slot_rows[3b+j] of d_Y (the rows of the
- * batch's active nodes, elimrec_segment_plan's slot -> segment map). No keys are written. */
-int elimrec_bpr_head_rows(const float *d_Y, int64_t ldy, const int32_t *d_slot_rows, int B, int d, int n_blocks,
-                          const float *block_weights /* host, n_blocks */, float *d_loss_rows, float *d_grad_rows,
-                          void *stream);
-/* elimrec_bpr_head_rows + elimrec_sum of its loss rows in ONE launch: the workgroup that finishes last adds the B loss
- * rows in elimrec_sum's order (same bits) into *d_loss. d_ticket: one int32, zero before the first call (the kernel
- * leaves it zero). */
-int elimrec_bpr_head_rows_sum(const float *d_Y, int64_t ldy, const int32_t *d_slot_rows, int B, int d,
-                              int n_blocks, const float *block_weights, float *d_loss_rows, float *d_grad_rows,
-                              float *d_loss, int32_t *d_ticket, void *stream);
-
-/* ... and the batch loss PUBLISHED to the host from that launch. /root/reference/main.py:102 reads `loss.cpu().item()` after
- * every step; a read of the device tensor waits for the whole step (adjoint hops, Adam), so the host could not enqueue step t + 1
- * under step t. Here the launch that sums the loss (about 120 us into a 280 us step) also stores (sequence number, value) as one
- * 8-byte system-scope word into coherent host memory, and the caller's `.item()` waits on that word -- not on the stream.
- * pub: elimrec_loss_pub_create(n_slots) (a ring of n_slots host words + a device-side launch counter). Every
- * elimrec_bpr_head_rows_sum_pub enqueue publishes under the next sequence number (elimrec_loss_pub_issued right after the enqueue);
+ * batch's active nodes, elimrec_segment_plan's slot -> segment map). No keys are written. Three forms, by what is handed over:
+ *   d_loss == NULL (then d_ticket and pub must be NULL too): the loss rows and the gradient rows only.
+ *   d_loss and d_ticket: + elimrec_sum of the loss rows in the SAME launch: the workgroup that finishes last adds the B loss
+ *     rows in elimrec_sum's order (same bits) into *d_loss. d_ticket: one int32, zero before the first call (the kernel
+ *     leaves it zero). An empty batch sets *d_loss to zero.
+ *   ... and pub: the batch loss PUBLISHED to the host from that launch. main.py:102 of the reference reads `loss.cpu().item()`
+ *     after every step; a read of the device tensor waits for the whole step (adjoint hops, Adam), so the host could not enqueue
+ *     step t + 1 under step t. Here the launch that sums the loss (about 120 us into a 280 us step) also stores (sequence
+ *     number, value) as one 8-byte system-scope word into coherent host memory, and the caller's `.item()` waits on that word --
+ *     not on the stream. B must be positive.
+ * pub: elimrec_loss_pub_create(n_slots) (a ring of n_slots host words + a device-side launch counter). Every publishing enqueue
+ * publishes under the next sequence number (elimrec_loss_pub_issued right after the enqueue);
  * elimrec_loss_pub_wait(pub, seq, timeout_s, &value) spins until launch `seq` has published: 0 = value is its loss (the bits of
  * *d_loss); ELIMREC_E_UNSUPPORTED = the ring has wrapped past it (read the device tensor); ELIMREC_E_WORKSPACE = timed out. */
 int elimrec_loss_pub_create(int n_slots, void **out_pub);
 int elimrec_loss_pub_destroy(void *pub);
 uint32_t elimrec_loss_pub_issued(void *pub);
 int elimrec_loss_pub_wait(void *pub, uint32_t seq, double timeout_s, float *value);
-int elimrec_bpr_head_rows_sum_pub(const float *d_Y, int64_t ldy, const int32_t *d_slot_rows, int B, int d,
-                                  int n_blocks, const float *block_weights, float *d_loss_rows, float *d_grad_rows,
-                                  float *d_loss, int32_t *d_ticket, void *pub, void *stream);
+int elimrec_bpr_head_rows(const float *d_Y, int64_t ldy, const int32_t *d_slot_rows, int B, int d, int n_blocks,
+                          const float *block_weights /* host, n_blocks */, float *d_loss_rows, float *d_grad_rows,
+                          float *d_loss, int32_t *d_ticket, void *pub, void *stream);
 
 /* out[0] = sum_i x[i] in a fixed order (single workgroup, deterministic). */
 int elimrec_sum(const float *d_x, int64_t n, float *d_out, void *stream);
@@ -367,42 +362,32 @@ int elimrec_head_bwd_input(const float *d_dY, int64_t lddy, const int32_t *d_act
 
 /* elimrec_segment_apply followed by elimrec_head_bwd_input (compact output only) as ONE launch: the rows of dY are
  * summed from their member gradient rows while they are staged for the contraction; d_reduced still receives dY
- * (elimrec_linear_bwd_w reads it). Same results as the two calls, bit for bit. ld = (1+S)*d. */
+ * (elimrec_linear_bwd_w reads it). Same results as the two calls, bit for bit. ld = (1+S)*d.
+ * d_pack_bwd (nullable): the weight operands taken from the packed copy elimrec_head_fwd_fused (phase 0/1) leaves behind,
+ * d_pack + elimrec_head_pack_bwd_offset(n_mod, D) floats; recdim 64, head h = feature table h (16-row tiles).
+ * sinks (nullable; needs d_pack_bwd and recdim 64): what the launch writes besides d_compact -- values and device pointers only.
+ *   d_SrcA / d_SrcB, N, ns, w: ONE rank owns every table column: what elimrec_slab_merge_rows(world = 1, M = C / d) would make
+ *     of d_compact -- the slab-major adjoint sources [ns x N x w] (H = sum of a row's column blocks in block order, G = block 0;
+ *     users: H -> SrcA, G -> SrcB, items the other way round) at the active rows. Every active row is listed once, so there is
+ *     nothing to accumulate; the row bitmap of the sources is the planner's key bitmap (elimrec_batch_plan). IndexBackward's
+ *     index_put into the adjoint sources (models/EliMRec.py:239-256 under autograd) without a launch of its own.
+ *   d_split, n_max, world: with peers: what elimrec_source_rows_split(d_compact) would write -- the [H | G] rows cut into the
+ *     `world` column slices of a column-sharded job, d_split [world x n_max x 2*(d/world)] -- ready for the all-to-all.
+ * Setting both d_SrcA and d_split is an error. */
+typedef struct elimrec_head_bwd_sinks {
+    float *d_SrcA, *d_SrcB;
+    int64_t N;
+    int32_t ns, w;
+    float *d_split;
+    int64_t n_max;
+    int32_t world;
+} elimrec_head_bwd_sinks;
 int elimrec_segment_apply_head_bwd(const float *d_rows, int64_t n, int ld, const int32_t *d_active_rows,
                                    const int32_t *d_seg_info, const float *d_scale, float *d_reduced,
                                    const void *d_plan_workspace, size_t plan_workspace_bytes, int64_t U, int d, int C,
                                    int S, const int *head_mblock, const float *d_W_user, const float *d_W_item,
-                                   const float *const *d_W_heads, float *d_compact, void *stream);
-/* The same with the weight operands taken from the packed copy elimrec_head_fwd_fused (phase 0/1, 16-row form) leaves
- * behind: d_pack_bwd = d_pack + elimrec_head_pack_bwd_offset(n_mod, D) floats; recdim 64, head h = feature table h. */
-int elimrec_segment_apply_head_bwd_packed(const float *d_rows, int64_t n, int ld, const int32_t *d_active_rows,
-                                          const int32_t *d_seg_info, const float *d_scale, float *d_reduced,
-                                          const void *d_plan_workspace, size_t plan_workspace_bytes, int64_t U,
-                                          int d, int C, int S, const int *head_mblock, const float *d_W_user,
-                                          const float *d_W_item, const float *const *d_W_heads,
-                                          float *d_compact, const float *d_pack_bwd, void *stream);
-/* The packed form for ONE rank that owns every table column (recdim 64): the kernel also writes what
- * elimrec_slab_merge_rows(world = 1, M = C / d) would make of d_compact -- the slab-major adjoint sources [ns x N x w]
- * (H = sum of a row's column blocks in block order, G = block 0; users: H -> SrcA, G -> SrcB, items the other way round)
- * at the active rows. Every active row is listed once, so there is nothing to accumulate; the row bitmap of the
- * sources is the planner's key bitmap (elimrec_batch_plan). IndexBackward's index_put into the adjoint sources
- * (/root/reference/models/EliMRec.py:239-256 under autograd) without a launch of its own. */
-int elimrec_segment_apply_head_bwd_sources(const float *d_rows, int64_t n, int ld, const int32_t *d_active_rows,
-                                           const int32_t *d_seg_info, const float *d_scale, float *d_reduced,
-                                           const void *d_plan_workspace, size_t plan_workspace_bytes, int64_t U,
-                                           int d, int C, int S, const int *head_mblock, const float *d_W_user,
-                                           const float *d_W_item, const float *const *d_W_heads,
-                                           float *d_compact, const float *d_pack_bwd, int64_t N, int ns, int w,
-                                           float *d_SrcA, float *d_SrcB, void *stream);
-/* ... and with peers: the kernel also writes what elimrec_source_rows_split(d_compact) would -- the [H | G] rows cut into
- * the `world` column slices of a column-sharded job, d_out [world x n_max x 2*(d/world)] -- ready for the all-to-all. */
-int elimrec_segment_apply_head_bwd_split(const float *d_rows, int64_t n, int ld, const int32_t *d_active_rows,
-                                         const int32_t *d_seg_info, const float *d_scale, float *d_reduced,
-                                         const void *d_plan_workspace, size_t plan_workspace_bytes, int64_t U,
-                                         int d, int C, int S, const int *head_mblock, const float *d_W_user,
-                                         const float *d_W_item, const float *const *d_W_heads,
-                                         float *d_compact, const float *d_pack_bwd, int64_t n_max, int world,
-                                         float *d_out, void *stream);
+                                   const float *const *d_W_heads, float *d_compact, const float *d_pack_bwd,
+                                   const elimrec_head_bwd_sinks *sinks, void *stream);
 
 /* ---------------------------------------------------------------- embedding gradients (K2 bwd)
  * dE_user[u, j] = sum_m G[u, m*d + j];  dE_item[i, j] = G[U+i, j]   (CatBackward of :239). */
@@ -920,31 +905,24 @@ int elimrec_adam_step_out(const float *d_p_in, float *d_p_out, const float *d_g,
  * recdim must be 64 and the row tiles must fit LDS, else ELIMREC_E_UNSUPPORTED (callers keep the batched GEMMs). */
 size_t elimrec_head_pack_floats(int n_mod, const int *D);
 size_t elimrec_head_pack_bwd_offset(int n_mod, const int *D);   /* first float of the head BACKWARD's operands */
-int elimrec_head_fwd_fused(const int32_t *d_act, const int32_t *d_seg_info, int64_t R, const float *d_out0,
-                           int64_t ld_out0, const float *d_narrow, int64_t ld_nar, const float *d_c, int n_mod,
-                           const float *const *d_S, const int64_t *ldS, const int *D, const float *const *d_Wm,
-                           const float *const *d_bm, const float *d_Wf_user, const float *d_bf_user,
-                           const float *d_Wf_item, const float *d_bf_item, const float *const *d_Ws,
-                           const float *const *d_bs, float *d_pack, size_t pack_floats, float *d_OutAct,
-                           int64_t ld_out, float *d_YAct, int64_t ld_y, int recdim, int phase, void *stream);
 
-/* elimrec_head_fwd_fused with d_out0 / d_narrow read where the column shards' forward exchange left them (SURVEY section 8(e):
- * each rank evaluates models/EliMRec.py:255-261's layer means on its recdim / world columns and sends every peer the rows that
- * peer's triplets name). d_recv = [world][R][out0: dl | narrow: dl] fp32, piece q = rank q's columns [q*dl, (q+1)*dl) of MY R
- * active rows, world * dl = recdim = 64, dl a multiple of 4. Phases 0, 2, 4. The bits of elimrec_peer_cols_to_rows followed by
- * elimrec_head_fwd_fused on its rows, without that pass over the rows. */
-int elimrec_head_fwd_fused_peers(const int32_t *d_act, const int32_t *d_seg_info, int64_t R, const float *d_recv, int world,
-                                 int64_t dl, const float *d_c, int n_mod, const float *const *d_S, const int64_t *ldS,
-                                 const int *D, const float *const *d_Wm, const float *const *d_bm, const float *d_Wf_user,
-                                 const float *d_bf_user, const float *d_Wf_item, const float *d_bf_item,
-                                 const float *const *d_Ws, const float *const *d_bs, float *d_pack, size_t pack_floats,
-                                 float *d_OutAct, int64_t ld_out, float *d_YAct, int64_t ld_y, int recdim, int phase, void *stream);
+/* The arguments every form of the head repeats (host struct: values and device pointers only, arrays inline). */
+#define ELIMREC_HEAD_MAX_TABLES 3
+typedef struct elimrec_head_weights {
+    int32_t n_mod, recdim;
+    int32_t D[ELIMREC_HEAD_MAX_TABLES];
+    const float *d_Wm[ELIMREC_HEAD_MAX_TABLES], *d_bm[ELIMREC_HEAD_MAX_TABLES];     /* d_bm / d_bs entries nullable */
+    const float *d_Ws[ELIMREC_HEAD_MAX_TABLES], *d_bs[ELIMREC_HEAD_MAX_TABLES];
+    const float *d_Wf_user, *d_bf_user, *d_Wf_item, *d_bf_item;
+    float *d_pack;
+    size_t pack_floats;
+} elimrec_head_weights;
 
-/* elimrec_head_fwd_fused with the feature constants read from 16-bit storage where they lie (BASELINE.json configs[1] "bf16";
- * models/EliMRec.py:233-236's v/a/t_dense inputs in their folded form): src->d_table holds one packed row per node,
+/* 16-bit source: the feature constants read from 16-bit storage where they lie (BASELINE.json configs[1] "bf16";
+ * models/EliMRec.py:233-236's v/a/t_dense inputs in their folded form): d_table holds one packed row per node,
  * [S_1 | .. | S_n | c_hi c_lo] of fp16 (dtype 1) or bf16 (dtype 2) elements, row_elems elements per row (a multiple of 8) -- the
  * layout elimrec_lookup_pack / _unpack use, this rank holding every row. Rows are widened in registers (exactly; c = hi + lo);
- * arithmetic and results are those of elimrec_lookup_unpack(direct) + elimrec_head_fwd_fused on its fp32 rows, without that pass.
+ * arithmetic and results are those of elimrec_lookup_unpack(direct) + the plain form on its fp32 rows, without that pass.
  * d_S_out [R x ld_S_out] / d_c_out [R] (nullable): the widened rows of the launch's active rows, written by the phases that
  * read them (0, 2, 3) for the backward half's weight-gradient launches. */
 typedef struct elimrec_head_src16 {
@@ -955,18 +933,12 @@ typedef struct elimrec_head_src16 {
     int64_t ld_S_out;
     float *d_c_out;
 } elimrec_head_src16;
-int elimrec_head_fwd_fused_src16(const elimrec_head_src16 *src, const int32_t *d_act, const int32_t *d_seg_info, int64_t R,
-                                 const float *d_out0, int64_t ld_out0, const float *d_narrow, int64_t ld_nar, int n_mod,
-                                 const int *D, const float *const *d_Wm, const float *const *d_bm, const float *d_Wf_user,
-                                 const float *d_bf_user, const float *d_Wf_item, const float *d_bf_item,
-                                 const float *const *d_Ws, const float *const *d_bs, float *d_pack, size_t pack_floats,
-                                 float *d_OutAct, int64_t ld_out, float *d_YAct, int64_t ld_y, int recdim, int phase, void *stream);
 
-/* Phase 4 of elimrec_head_fwd_fused with the layer means of the active rows EVALUATED by the same launch instead of read back
- * from elimrec_slab_rows (one rank owning every table column, recdim 64 = ns * w): the arguments of that call in a host
- * struct -- plan, slab geometry, layer tables X^0 .. X^L (layers[L] NULL: hop L inline through the plain CSR, split rows
- * from d_long), and where the shared part of the rows is kept (d_narrow_out [R x ld_narrow_out], as elimrec_slab_rows
- * leaves it). Block 0 of d_OutAct is written here. Same bits as elimrec_slab_rows followed by phase 4. */
+/* Rows: phase 4 with the layer means of the active rows EVALUATED by the same launch instead of read back from
+ * elimrec_slab_rows (one rank owning every table column, recdim 64 = ns * w): the arguments of that call -- plan, slab
+ * geometry, layer tables X^0 .. X^L (layers[L] NULL: hop L inline through the plain CSR, split rows from d_long), and where
+ * the shared part of the rows is kept (d_narrow_out [R x ld_narrow_out], as elimrec_slab_rows leaves it). Block 0 of d_OutAct
+ * is written here. Same bits as elimrec_slab_rows followed by phase 4 of the plain form. */
 typedef struct elimrec_head_rows {
     const elimrec_sell *A;
     int32_t ns, w, L;
@@ -976,12 +948,28 @@ typedef struct elimrec_head_rows {
     float *d_narrow_out;
     int64_t ld_narrow_out;
 } elimrec_head_rows;
-int elimrec_head_fwd_fused_rows(const elimrec_head_rows *rows, const int32_t *d_act, const int32_t *d_seg_info, int64_t R,
-                                const float *d_c, int n_mod, const float *const *d_S, const int64_t *ldS, const int *D,
-                                const float *const *d_Wm, const float *const *d_bm, const float *d_Wf_user,
-                                const float *d_bf_user, const float *d_Wf_item, const float *d_bf_item,
-                                const float *const *d_Ws, const float *const *d_bs, float *d_pack, size_t pack_floats,
-                                float *d_OutAct, int64_t ld_out, float *d_YAct, int64_t ld_y, int recdim, void *stream);
+
+/* Where the head's inputs come from; at most one of d_recv, src16.d_table and rows.A is set (none: the plain form).
+ *   plain: d_out0 / d_narrow with their leading dimensions, d_c, d_S, ldS.
+ *   peers (d_recv): d_out0 / d_narrow read where the column shards' forward exchange left them (each rank
+ *     evaluates models/EliMRec.py:255-261's layer means on its recdim / world columns and sends every peer the rows that peer's
+ *     triplets name). d_recv = [world][R][out0: dl | narrow: dl] fp32, piece q = rank q's columns [q*dl, (q+1)*dl) of MY R
+ *     active rows, world * dl = recdim = 64, dl a multiple of 4. Phases 0, 2, 4; d_c, d_S, ldS as in the plain form. The bits of
+ *     elimrec_peer_cols_to_rows followed by the plain form on its rows, without that pass over the rows.
+ *   16-bit source (src16.d_table): d_out0 / d_narrow as in the plain form; d_c, d_S, ldS unused.
+ *   rows (rows.A): d_c, d_S, ldS as in the plain form; phase is taken as 4. */
+typedef struct elimrec_head_fwd_in {
+    const float *d_out0; int64_t ld_out0;
+    const float *d_narrow; int64_t ld_nar;
+    const float *d_c;
+    const float *d_S[ELIMREC_HEAD_MAX_TABLES]; int64_t ldS[ELIMREC_HEAD_MAX_TABLES];
+    const float *d_recv; int32_t world; int64_t dl;
+    elimrec_head_src16 src16;
+    elimrec_head_rows rows;
+} elimrec_head_fwd_in;
+int elimrec_head_fwd_fused(const elimrec_head_fwd_in *in, const elimrec_head_weights *w, const int32_t *d_act,
+                           const int32_t *d_seg_info, int64_t R, float *d_OutAct, int64_t ld_out, float *d_YAct, int64_t ld_y,
+                           int phase, void *stream);
 
 /* ---------------------------------------------------------------- propagation matrix on the device (N3)
  * create_adj_mat (models/EliMRec.py:309-354) from the UNIQUE training interactions d_users / d_items [E] (int64):

@@ -1,6 +1,6 @@
 """The training step's head kernels against plain float64 math at their edge shapes: the fused head forward (csrc/head.hip:
 head_fwd16_kernel, head_rows_fwd16_kernel), the head input gradient (csrc/bpr.hip: head_bwd_input_kernel,
-head_bwd_input_mfma_kernel, head_bwd_input16_kernel<SEG, PACKED>) and the BPR loss head over compact rows (bpr_head_kernel,
+head_bwd_input_mfma_kernel, head_bwd_input16_kernel) and the BPR loss head over compact rows (bpr_head_kernel,
 bpr_head_sum_kernel). The references below never call a project kernel; every output buffer starts as NaN, so a row or
 column a call must not write is seen to stay untouched. The tolerance self-tests at the top run without a GPU."""
 import types
@@ -365,7 +365,7 @@ def _src16_table(t, dtype, seed):
     ("bf16", (4,), 24, 1, 1, (0,)),
 ])
 def test_fused_head_forward_on_16bit_constants(dtype, dims, R, n_act, n_lo, phases):
-    """elimrec_head_fwd_fused_src16: S_out / c_out are the exactly widened rows of the active nodes (c = fp32(hi) + fp32(lo)),
+    """elimrec_head_fwd_fused (16-bit source form): S_out / c_out are the exactly widened rows of the active nodes (c = fp32(hi) + fp32(lo)),
     OutAct / YAct meet the fp64 reference of the widened values, and have the bits of the plain head on the widened tables."""
     from elimrec_amd import ops
     t = _fwd_case(dims, R, n_act, n_lo, "all", seed=7 + n_act)
@@ -394,7 +394,7 @@ def test_fused_head_forward_on_16bit_constants(dtype, dims, R, n_act, n_lo, phas
 @pytest.mark.gpu
 @pytest.mark.parametrize("W", [1, 2, 4, 8])
 def test_fused_head_forward_reading_the_peers_pieces(W):
-    """elimrec_head_fwd_fused_peers on a received [W x R x (out0 dl | narrow dl)] buffer: the fp64 reference, and the bits of
+    """elimrec_head_fwd_fused (peers form) on a received [W x R x (out0 dl | narrow dl)] buffer: the fp64 reference, and the bits of
     ops.peer_cols_to_rows followed by the plain head (phases 0 and 1, 3, 4)."""
     from elimrec_amd import ops
     t = _fwd_case((60, 128), 40, 37, 21, "all", seed=W)
@@ -434,7 +434,7 @@ def _random_graph(n, U, seed):
 @pytest.mark.gpu
 @pytest.mark.parametrize("n_act,n_lo", [(45, 17), (16, 0)])
 def test_fused_head_forward_with_the_rows_inline(n_act, n_lo):
-    """elimrec_head_fwd_fused_rows, head_rows_fwd16_kernel: out0 = the layer means (L + 1 layers, the last A x_{L-1} evaluated
+    """elimrec_head_fwd_fused (rows form), head_rows_fwd16_kernel: out0 = the layer means (L + 1 layers, the last A x_{L-1} evaluated
     inline: SELL rows from the tables, long rows from the seg_only launch's table) and narrow = the side's alternating layers
     (users: layers 0, 2, ..; items: 1, 3, ..) / (L + 1), against an fp64 A @ x; then the head over them."""
     from elimrec_amd import ops, slab
@@ -739,7 +739,7 @@ def test_segment_apply_head_bwd_unpacked_vs_fp64(d, S, mblock, n_users, n_items,
     (1, [1], 0, 1, 0, 0),                # n_act 1
 ])
 def test_segment_apply_head_bwd_packed_vs_fp64(S, mblock, n_users, n_items, extra, hot):
-    """head_bwd_input16_kernel<true, true> (recdim 64, the pack of ops.head_fwd_fused at head_pack_bwd_offset): the fast path
+    """head_bwd_input16_kernel (recdim 64, the pack of ops.head_fwd_fused at head_pack_bwd_offset): the fast path
     (PACKED && !mixed && C <= 256) for tiles on one side, the in-kernel fallback for the straddling tile."""
     c = _seg_case(HD, S, n_users, n_items, extra, hot, seed=S * 31 + n_users)
     _seg_run(c, HD, S, mblock, "packed")

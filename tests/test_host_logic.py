@@ -122,10 +122,23 @@ def test_c_abi_library_exports_every_declared_symbol():
         assert hasattr(lib, name), name
         assert name in _lib.SIGNATURES, name
     assert declared == set(_lib.SIGNATURES.keys())
-    assert lib.elimrec_abi_version() == 1
+    assert lib.elimrec_abi_version() == 2
     # size queries are host-only and must work without a GPU
     assert lib.elimrec_linear_bwd_w_workspace(76085, 64, 128) > 0
     assert lib.elimrec_score_workspace(128, 76085, 10) > 0
+
+
+def test_native_function_table_matches_the_binding():
+    """Every entry of the native program's function table (csrc/program.hip) takes as many arguments as the ctypes binding
+    declares for it, and no more than a program op holds: header, binding and table cannot drift apart unnoticed."""
+    from elimrec_amd import _lib
+    lib = _lib.load()
+    n = lib.elimrec_program_fn_count()
+    assert n > 0
+    for i in range(n):
+        name = lib.elimrec_program_fn_name(i).decode()
+        assert lib.elimrec_program_fn_args(i) == len(_lib.SIGNATURES[name][1]), name
+        assert lib.elimrec_program_fn_args(i) <= _lib.PROGRAM_MAX_ARGS, name
 
 
 def test_checkpoint_name_and_metrics_info():

@@ -1333,7 +1333,7 @@ def test_16bit_feature_storage_equals_fp32_engine_on_rounded_constants(dtype, na
 @pytest.mark.parametrize("dtype", ["f16", "bf16"])
 def test_16bit_constants_read_by_the_head_equal_the_widening_pass_bitwise(dtype, form, monkeypatch):
     """One rank, 16-bit constants: by default the fused head reads the packed 16-bit rows where they lie and widens in registers
-    (elimrec_head_fwd_fused_src16; the step keeps the fp32 step's shape: feature blocks beside the hops, rows evaluated in the
+    (elimrec_head_fwd_fused (16-bit source form); the step keeps the fp32 step's shape: feature blocks beside the hops, rows evaluated in the
     head's launch); ELIMREC_DIRECT16=0 keeps the earlier form -- a widening pass over the batch's rows (elimrec_lookup_unpack)
     in front of a head that reads its fp32 output. The same arithmetic on the same values: 14 steps (the one-call program takes
     over midway), every loss, the embedding tables, every other parameter and both Adam moments bit for bit."""
@@ -1576,7 +1576,7 @@ def test_peer_cols_to_rows_and_rows_bitmap_vs_torch(W, R, dl):
 
 @pytest.mark.parametrize("W", [1, 2, 4, 8])
 def test_fused_head_reads_the_peers_pieces_in_place(W):
-    """elimrec_head_fwd_fused_peers: the fused head on the forward exchange's received buffer [W x R x (out0 dl | narrow dl)]
+    """elimrec_head_fwd_fused (peers form): the fused head on the forward exchange's received buffer [W x R x (out0 dl | narrow dl)]
     leaves the bits of elimrec_peer_cols_to_rows followed by elimrec_head_fwd_fused on its two row views -- OutAct (block 0
     included, which the launch writes itself) and YAct, phases 0 and 2; a buffer whose pieces are not 4-float multiples or
     do not make 64 columns is refused."""
