@@ -215,6 +215,10 @@ SIGNATURES = {
     "elimrec_list_pair_cosine_small_k": (c_i32, []),
     "elimrec_list_pair_cosine_chunk_cols": (c_i32, [c_i32, c_i32]),
     "elimrec_list_exposure": (c_i32, [c_ptr, c_i64, c_i32, c_i64, c_ptr, c_ptr]),
+    "elimrec_mmr_rerank": (c_i32, [c_ptr, c_i64, c_i64, c_i32, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_i32, c_i32, c_f32, c_ptr, c_ptr,
+                                   c_ptr, c_ptr]),
+    "elimrec_mmr_max_pool": (c_i32, []),
+    "elimrec_mmr_rows_in_lds": (c_i32, [c_i32, c_i32]),
     "elimrec_slab_partials_bytes": (c_size, [c_sell, c_i32, c_i32]),
     "elimrec_slab_hop": (c_i32, [c_sell, c_i32, c_i32, c_i32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_f32, c_ptr, c_size, c_i32,
                                  c_ptr]),
@@ -345,6 +349,7 @@ class _Recording(object):
                              "elimrec_rank_segment", "elimrec_rank_targets_per_pass",
                              "elimrec_cosine_topk_chunk", "elimrec_cosine_topk_tile",
                              "elimrec_list_max_k", "elimrec_list_pair_cosine_small_k", "elimrec_list_pair_cosine_chunk_cols",
+                             "elimrec_mmr_max_pool", "elimrec_mmr_rows_in_lds",
                              "elimrec_comm_create", "elimrec_comm_destroy", "elimrec_comm_nranks") or name.startswith("elimrec_program_")
             setattr(self, name, self._wrap(fn, name) if res is c_i32 and not plain else fn)
 

@@ -8,7 +8,7 @@ from torch import nn
 
 from . import ops
 from .evaluator import ProxyEvaluator
-from .reports import EffectReport, ListReport, NeighbourReport, RankReport
+from .reports import DiversifyReport, EffectReport, ListReport, NeighbourReport, RankReport
 
 
 class BasicModel(nn.Module):
@@ -68,6 +68,17 @@ class BasicModel(nn.Module):
                              % (ops.LIST_MAX_K, int(dataset.num_items), k_list))
         self.list_reporter = ListReport(dataset, train, dataset.get_user_test_dict(), k_list, group_view=config["group_view"],
                                         item_group_view=item_view) if k_list else None
+        # --diversify_report=K (CLI-only, default 0 = off): the test users' top-N pools (--diversify_pool=N, default min(4K, 256,
+        # the catalogue)) re-ranked to K items by greedy MMR at every --diversify_lambda (default [1.0,0.9,0.7,0.5]): what the trade
+        # costs in recall / NDCG and buys in intra-list similarity and catalogue exposure, overall and per user group
+        # (reports.DiversifyReport)
+        k_div = int(config["diversify_report"]) if "diversify_report" in config else 0
+        self.diversify_reporter = None
+        if k_div:
+            pool = config["diversify_pool"] if "diversify_pool" in config else None
+            lambdas = config["diversify_lambda"] if "diversify_lambda" in config else [1.0, 0.9, 0.7, 0.5]
+            self.diversify_reporter = DiversifyReport(dataset, train, dataset.get_user_test_dict(), k_div, pool=pool, lambdas=lambdas,
+                                                      group_view=config["group_view"])
         self.infonce_criterion = nn.CrossEntropyLoss()          # BasicModel.py:32
 
     def getFileName(self):

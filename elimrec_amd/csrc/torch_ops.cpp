@@ -21,6 +21,8 @@
 //   list_pair_cosine(table f32[n x blocks*d], sqnorm f32[n x blocks], lists i32[B x K], blocks) -> f32[B x blocks]: per list and
 //       column block the mean pairwise cosine of the listed rows (entries outside [0, n) are not listed; NaN below two)
 //   list_exposure(lists i32[B x K], n_rows) -> i32[n_rows]: how often every row is listed
+//   mmr_rerank(table f32[n x d], sqnorm f32[n], pool_idx i32[B x N], pool_val f32[B x N], K, lam) -> (idx i32, pos i32, val f32) [B x K]:
+//       greedy maximal-marginal-relevance re-ranking of each pool (unlisted entries are never picked; -1 / -1 / -inf fillers)
 //   sample_triplets(user_ids, ptr, items, num_items, n, seed, epoch) -> (users, pos, neg)
 //   score_candidates(Y, U, I, users, d, S, head_mask, fusion_mode, predict_type, cand_ptr, cand_items, width) -> f32[B x width]
 //       (each row: its candidates' scores in list order, then -inf)
@@ -438,6 +440,28 @@ at::Tensor list_exposure(const at::Tensor &lists, int64_t n_rows) {
     return counts;
 }
 
+// ---- diversified re-ranking of top-N pools (greedy MMR)
+std::tuple<at::Tensor, at::Tensor, at::Tensor> mmr_rerank(const at::Tensor &table, const at::Tensor &sqnorm, const at::Tensor &pool_idx,
+                                                          const at::Tensor &pool_val, int64_t K, double lam) {
+    const at::Tensor t = rowmajor(table, "table");
+    need(sqnorm, "sqnorm", at::kFloat, 1); need(pool_idx, "pool_idx", at::kInt, 2); need(pool_val, "pool_val", at::kFloat, 2);
+    const at::Tensor pi = pool_idx.contiguous(), pv = pool_val.contiguous();
+    const int64_t n = t.size(0), d = t.size(1), B = pi.size(0), N = pi.size(1);
+    TORCH_CHECK(pi.sizes() == pv.sizes(), "elimrec::mmr_rerank: pool_idx and pool_val must have one shape [B x N]");
+    TORCH_CHECK(K >= 1 && K <= N && N <= elimrec_mmr_max_pool(), "elimrec::mmr_rerank: 1 <= K <= N <= ", elimrec_mmr_max_pool(), ", got K ", K,
+                ", N ", N);
+    TORCH_CHECK(d % 4 == 0 && d >= 4 && d <= 256, "elimrec::mmr_rerank: the table needs d % 4 == 0 and 4 <= d <= 256 columns, got ", d);
+    TORCH_CHECK(lam >= 0.0 && lam <= 1.0, "elimrec::mmr_rerank: 0 <= lam <= 1, got ", lam);
+    TORCH_CHECK(sqnorm.numel() == n, "elimrec::mmr_rerank: sqnorm needs one entry per table row (", n, "), got ", sqnorm.numel());
+    at::Tensor idx = at::empty({B, K}, pi.options()), pos = at::empty({B, K}, pi.options()), val = at::empty({B, K}, pv.options());
+    if (B == 0) return {idx, pos, val};
+    check(elimrec_mmr_rerank(t.data_ptr<float>(), t.stride(0), n, (int)d, sqnorm.data_ptr<float>(), n > 1 ? sqnorm.stride(0) : 1,
+                             pi.data_ptr<int32_t>(), pv.data_ptr<float>(), B, (int)N, (int)K, (float)lam, idx.data_ptr<int32_t>(),
+                             pos.data_ptr<int32_t>(), val.data_ptr<float>(), cur_stream()),
+          "mmr_rerank");
+    return {idx, pos, val};
+}
+
 at::Tensor sample_negatives(const at::Tensor &excl_ptr, const at::Tensor &excl_items, int64_t num_items, int64_t n_neg, int64_t seed) {
     need(excl_ptr, "excl_ptr", at::kLong, 1); need(excl_items, "excl_items", at::kInt, 1);
     const at::Tensor p = excl_ptr.contiguous(), it = excl_items.contiguous();
@@ -561,6 +585,7 @@ TORCH_LIBRARY(elimrec, m) {
     m.def("list_overlap(Tensor a, Tensor b) -> Tensor");
     m.def("list_pair_cosine(Tensor table, Tensor sqnorm, Tensor lists, int blocks) -> Tensor");
     m.def("list_exposure(Tensor lists, int n_rows) -> Tensor");
+    m.def("mmr_rerank(Tensor table, Tensor sqnorm, Tensor pool_idx, Tensor pool_val, int K, float lam) -> (Tensor, Tensor, Tensor)");
     m.def("sample_negatives(Tensor excl_ptr, Tensor excl_items, int num_items, int n_neg, int seed) -> Tensor");
     m.def("lookup_counts(Tensor acts, int U, int I, int[] user_bounds, int[] item_bounds) -> Tensor");
     m.def("lookup_pack(Tensor acts, int U, int I, int[] user_bounds, int[] item_bounds, int me, Tensor shard, int row_bytes) -> (Tensor, Tensor)");
@@ -589,6 +614,7 @@ TORCH_LIBRARY_IMPL(elimrec, CUDA, m) {
     m.impl("list_overlap", &list_overlap);
     m.impl("list_pair_cosine", &list_pair_cosine);
     m.impl("list_exposure", &list_exposure);
+    m.impl("mmr_rerank", &mmr_rerank);
     m.impl("sample_negatives", &sample_negatives);
     m.impl("lookup_counts", &lookup_counts);
     m.impl("lookup_pack", &lookup_pack);

@@ -1437,6 +1437,62 @@ class EliMRec(BasicModel):
         out = out.cpu()
         return out if h is None else out[:, h].contiguous()
 
+    @torch.no_grad()
+    def rerank_device(self, lists_idx, lists_val, k, lam, space="fused", out_idx=None, out_pos=None, out_val=None):
+        """Diversified re-ranking of top-N pools: greedy maximal marginal relevance over the item rows of one block of the cached
+        tables, ONE launch (csrc/rerank.hip). lists_idx int32 / lists_val float32 [B x N] on the device: per user a pool of items
+        with their scores (predict_device(top_k=N) gives both), 1 <= k <= N <= ops.MMR_MAX_POOL; an entry outside the catalogue or
+        with a score that is not finite (the -1 / -inf fillers) is never picked. With the pool's scores scaled to rel in [0, 1],
+        step t takes the item with the largest lam * rel - (1 - lam) * (its largest cosine to the items taken so far), the lowest
+        pool position among equals; lam = 1 keeps the pool's order. space: "fused" or a head letter, as neighbours_device.
+        -> (out_idx int32 [B x k] the picked items, out_pos int32 their pool positions, out_val float32 their objectives), -1 / -1
+        / -inf once no listed item is left; allocated here unless given. Tables as neighbours_device."""
+        self._require_gpu()
+        lo, n = self._side_rows("item")
+        h = self._neighbour_space(space)
+        dev = self._cached_tables("rerank_device() / recommend_diverse() need", "re-ranking needs the whole cached item table on this "
+                                  "rank; the tables are item-sharded (lean / multi-rank evaluation)")
+        d = self.latent_dim
+        sqn = self._block_sqnorms(dev)
+        B, k = lists_idx.shape[0], int(k)
+        if out_idx is None:
+            out_idx = torch.empty(B, k, dtype=torch.int32, device=dev)
+        if out_pos is None:
+            out_pos = torch.empty(B, k, dtype=torch.int32, device=dev)
+        if out_val is None:
+            out_val = torch.empty(B, k, dtype=torch.float32, device=dev)
+        ops.mmr_rerank(self._ws["Y"][lo:lo + n, h * d:(h + 1) * d], sqn[lo:lo + n, h], lists_idx, lists_val, k, lam, out_idx, out_pos,
+                       out_val)
+        return out_idx, out_pos, out_val
+
+    def recommend_diverse(self, user_ids, k, pool=None, lam=0.7, space="fused", exclude=None):
+        """k items per user from the user's top-`pool` list, trading relevance against similarity to what is already picked
+        (greedy MMR, rerank_device): CPU (ids int32 [B x k], scores fp32 [B x k]) in pick order -- scores are the model's scores
+        of the picked items under the current predict type. One predict_device(top_k=pool) call and one re-rank launch. pool
+        defaults to min(4 k, 256, num_items); lam in [0, 1]: 1 = the plain top-k, 0 = similarity alone; space as similar_items;
+        `exclude` = dict user -> item ids left out of the ranking, as explain() takes it. -1 / -inf where a user has fewer than k
+        items left."""
+        k = int(k)
+        pool = min(4 * k, ops.MMR_MAX_POOL, self.num_items) if pool is None else int(pool)
+        if not 1 <= k <= pool <= min(ops.MMR_MAX_POOL, self.num_items):
+            raise ValueError("need 1 <= k <= pool <= min(%d, num_items = %d), got k %d, pool %d"
+                             % (ops.MMR_MAX_POOL, self.num_items, k, pool))
+        lam = float(lam)
+        if not 0.0 <= lam <= 1.0:
+            raise ValueError("lam must lie in [0, 1], got %r" % lam)
+        self._neighbour_space(space)
+        tptr, tflat = self._excluded(exclude, user_ids, "item")
+        dev = self._cached_tables("rerank_device() / recommend_diverse() need", "re-ranking needs the whole cached item table on this "
+                                  "rank; the tables are item-sharded (lean / multi-rank evaluation)")
+        n = len(user_ids)
+        if not n:
+            return torch.empty(0, k, dtype=torch.int32), torch.empty(0, k, dtype=torch.float32)
+        masked = (torch.from_numpy(tptr).to(dev), torch.from_numpy(tflat.astype(np.int32)).to(dev)) if tflat.size else (None, None)
+        idx, val = self.predict_device(user_ids, top_k=pool, train_ptr=masked[0], train_items=masked[1])
+        out_idx, out_pos, _ = self.rerank_device(idx, val, k, lam, space=space)
+        scores = torch.gather(val, 1, out_pos.clamp(min=0).long()).masked_fill_(out_pos < 0, float("-inf"))
+        return out_idx.cpu(), scores.cpu()
+
     def predict(self, user_ids, candidate_items=None):
         """:96-113. CPU fp32 tensor [len(user_ids) x I]; `candidate_items` is ignored as in the reference."""
         dev = self._require_gpu()

@@ -931,6 +931,8 @@ def __getattr__(name):
         return int(_lib.load().elimrec_cosine_topk_tile())
     if name == "LIST_SMALL_K":           # lists up to this K take one wave of list_pair_cosine, longer ones four
         return int(_lib.load().elimrec_list_pair_cosine_small_k())
+    if name == "MMR_MAX_POOL":           # positions of a pool mmr_rerank takes (one thread each)
+        return int(_lib.load().elimrec_mmr_max_pool())
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 
@@ -1310,3 +1312,61 @@ def list_columns(mods):
     user's list in that space), then pop (the mean training-interaction count of the listed items); mods: the heads' modality
     letters in head order."""
     return ("ils_fused",) + tuple("ils_" + str(m) for m in mods) + ("pop",)
+
+
+def mmr_rows_in_lds(N, d):
+    """Which form mmr_rerank takes for pools of N positions over d columns (host arithmetic only): True = the pool's rows are
+    gathered once into LDS, False = the candidates' rows are read from global memory at every step. ValueError outside the limits."""
+    form = int(_lib.load().elimrec_mmr_rows_in_lds(int(N), int(d)))
+    if form < 0:
+        raise ValueError("elimrec_amd.ops.mmr_rows_in_lds: 1 <= N <= %d, d %% 4 == 0 and 4 <= d <= %d, got N %d, d %d"
+                         % (_lib.load().elimrec_mmr_max_pool(), KNN_MAX_D, N, d))
+    return bool(form)
+
+
+def mmr_rerank(table, sqnorm, pool_idx, pool_val, K, lam, out_idx, out_pos=None, out_val=None):
+    """elimrec_mmr_rerank: greedy maximal-marginal-relevance re-ranking of each row's pool. pool_idx int32 / pool_val float32
+    [B x N] contiguous on the table's device, 1 <= K <= N <= MMR_MAX_POOL: a position is listed when its id lies in [0, n) and its
+    score is finite (the kernel checks every entry, no host check is needed). With rel = the listed scores scaled to [0, 1] per pool
+    (0 when they are all equal), step t picks the listed, not yet picked position with the largest
+    lam * rel_i - (1 - lam) * max_{picked j} cos(i, j) (no penalty at t = 0), the lowest position among equals; 0 <= lam <= 1.
+    table [n x d] float32 with unit column stride (a column block of a wider matrix is fine), d % 4 == 0, 4 <= d <= 256; sqnorm: 1-D
+    float32, n entries, any stride: the rows' squared norms. out_idx int32 [B x K] <- the picked ids, out_pos int32 (optional) their
+    pool positions, out_val float32 (optional) their objectives at pick time; -1 / -1 / -inf once no listed position is left.
+    Outputs: contiguous, [>= B x K] or 1-D with at least B * K entries; entries beyond [B x K] are left alone. A row's bits depend
+    on its pool, N, K, d and lam alone (csrc/rerank.hip)."""
+    for t, name in ((table, "table"), (sqnorm, "sqnorm"), (pool_idx, "pool_idx"), (pool_val, "pool_val"), (out_idx, "out_idx")):
+        if not isinstance(t, torch.Tensor):
+            raise RuntimeError("elimrec_amd.ops: '%s' must be a HIP device tensor (the hot path has no CPU implementation)" % name)
+    if table.dim() != 2 or table.stride(1) != 1:
+        raise ValueError("elimrec_amd.ops.mmr_rerank: table must be 2-D with unit column stride")
+    n, d = table.shape
+    if d % 4 != 0 or not 4 <= d <= KNN_MAX_D:
+        raise ValueError("elimrec_amd.ops.mmr_rerank: the table needs d %% 4 == 0 and 4 <= d <= %d columns, got %d" % (KNN_MAX_D, d))
+    if sqnorm.dim() != 1 or sqnorm.numel() != n or sqnorm.device != table.device:
+        raise ValueError("elimrec_amd.ops.mmr_rerank: sqnorm must be 1-D with one entry per table row (%d) on the table's device" % n)
+    if (pool_idx.dim() != 2 or pool_idx.shape != pool_val.shape or not pool_idx.is_contiguous() or not pool_val.is_contiguous()
+            or pool_idx.device != table.device or pool_val.device != table.device):
+        raise ValueError("elimrec_amd.ops.mmr_rerank: pool_idx and pool_val must be contiguous [B x N] tensors of one shape on the "
+                         "table's device")
+    B, N = pool_idx.shape
+    if isinstance(K, bool) or int(K) != K:
+        raise ValueError("elimrec_amd.ops.mmr_rerank: K must be an integer, got %r" % (K,))
+    K = int(K)
+    max_pool = int(_lib.load().elimrec_mmr_max_pool())
+    if not 1 <= K <= N <= max_pool:
+        raise ValueError("elimrec_amd.ops.mmr_rerank: 1 <= K <= N <= %d, got K %d, N %d" % (max_pool, K, N))
+    lam = float(lam)
+    if not 0.0 <= lam <= 1.0:                                        # (NaN fails too)
+        raise ValueError("elimrec_amd.ops.mmr_rerank: 0 <= lam <= 1, got %r" % lam)
+    tp, ld = _rowmajor(table, "table")
+    sp = _dev(sqnorm, "sqnorm")
+    ld_sq = max(1, int(sqnorm.stride(0)))
+    pi, pv = _dev(pool_idx, "pool_idx", torch.int32), _dev(pool_val, "pool_val", torch.float32)
+    ip = _rows_out(out_idx, "out_idx", torch.int32, B, K, "mmr_rerank", device=table.device)
+    pp = _rows_out(out_pos, "out_pos", torch.int32, B, K, "mmr_rerank", device=table.device) if out_pos is not None else None
+    vp = _rows_out(out_val, "out_val", torch.float32, B, K, "mmr_rerank", device=table.device) if out_val is not None else None
+    if B == 0:
+        return out_idx
+    _lib.check(_lib.load().elimrec_mmr_rerank(tp, ld, n, d, sp, ld_sq, pi, pv, B, N, K, lam, ip, pp, vp, _stream()), "mmr_rerank")
+    return out_idx

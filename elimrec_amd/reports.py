@@ -1,5 +1,6 @@
 """The reports over the cached tables -- what the lists are made of (EffectReport), where the held-out items stand (RankReport),
-whose neighbourhood the fused space copies (NeighbourReport), the lists themselves (ListReport) -- and what they share: the user /
+whose neighbourhood the fused space copies (NeighbourReport), the lists themselves (ListReport), what diversifying them costs and
+buys (DiversifyReport) -- and what they share: the user /
 item groups, the groups as a checked index on the device, the group means, the table format, the model preflight and the block-wise
 top-K lists. The rows come from the model's *_device readers (model.py), the means from ops.group_metric_means."""
 import collections
@@ -156,16 +157,17 @@ class _Report(object):
             raise CandidateScoringError("%s report of the top-%d lists: the catalogue has %d items" % (self.name, self.top_k, model.num_items))
         return model._require_gpu()
 
-    def top_lists(self, model, users, K, block_users, tie_order):
+    def top_lists(self, model, users, K, block_users, tie_order, with_values=False):
         """The users' top-K lists under the model's current predict type with their train items masked, in blocks of block_users:
-        yields (a, b, users [b - a] int64, lists [b - a x K] int32) per block, on the device."""
+        yields (a, b, users [b - a] int64, lists [b - a x K] int32) per block, on the device; with_values: and the lists' scores
+        float32 [b - a x K] as a fifth entry."""
         device = model._require_gpu()
         a = 0
         for batch_users in DataIterator(users, batch_size=block_users, shuffle=False, drop_last=False):
             train_ptr, train_items = lists_csr(batch_users, self.user_pos_train, device)
             users_t = torch.as_tensor(np.asarray(batch_users, dtype=np.int64)).to(device)
-            idx, _ = model.predict_device(users_t, top_k=K, train_ptr=train_ptr, train_items=train_items, tie_order=tie_order)
-            yield a, a + len(batch_users), users_t, idx
+            idx, val = model.predict_device(users_t, top_k=K, train_ptr=train_ptr, train_items=train_items, tie_order=tie_order)
+            yield (a, a + len(batch_users), users_t, idx) + ((val,) if with_values else ())
             a += len(batch_users)
 
 
@@ -537,3 +539,111 @@ class ListReport(_Report):
         self.shift_columns = ("overlap",) + tuple("d_" + c for c in self.columns)
         final = self._user_table(rows)
         return final, format_table(self.shift_columns, self.group_labels, final)
+
+
+DIVERSIFY_COLUMNS = ("lambda", "recall", "ndcg", "ils_fused", "pop", "overlap", "coverage", "gini", "entropy")
+DiversifyTables = collections.namedtuple("DiversifyTables", ("columns", "labels", "table"))
+
+
+class DiversifyReport(_Report):
+    """What diversified re-ranking costs and buys (--diversify_report=K): every test user's top-`pool` list under the model's
+    current predict type with the train items masked (ONE top_lists pass with the scores, shared by all lambdas), re-ranked to K
+    items per lambda by greedy MMR in the fused space (EliMRec.rerank_device, csrc/rerank.hip: one launch per user block and
+    lambda), and per lambda
+      per user recall and ndcg at K (ops.rank_metrics), ils_fused = the list's mean pairwise cosine in the fused space
+        (list_similarity_device, column 0), pop = the mean training-interaction count of its items (as ListReport), overlap = the
+        share of the plain top-K list it keeps (ops.list_overlap);
+      coverage, gini, entropy = exposure_summary of how often each item is listed (ops.list_exposure) over the whole catalogue.
+    The table has one row per lambda -- DIVERSIFY_COLUMNS: the lambda, the user means (ops.group_metric_means), the three exposure
+    columns -- for all test users, then one such block per group_view group (assign_user_groups; the exposure columns from that
+    group's lists). lambda = 1 keeps the pool's order: its row holds the plain lists' numbers."""
+
+    name, needs = "diversify", "rerank_device"
+    metrics = (2, 4)                     # Recall, NDCG (evaluator.metric_dict)
+
+    def __init__(self, dataset, user_train_dict, user_test_dict, top_k, pool=None, lambdas=(1.0, 0.9, 0.7, 0.5), group_view=None):
+        if not isinstance(user_train_dict, dict) or not isinstance(user_test_dict, dict):
+            raise TypeError("user_train_dict and user_test_dict must be dicts")
+        self.num_items = I = int(dataset.num_items)
+        cap = min(ops.LIST_MAX_K, I)
+        for what, v in (("top_k", top_k), ("pool", pool)):
+            if (v is not None or what == "top_k") and (isinstance(v, bool) or not isinstance(v, (int, np.integer))):
+                raise ValueError("%s must be an integer, got %r" % (what, v))
+        if pool is None:
+            pool = min(4 * int(top_k), cap)
+        if not 2 <= top_k <= pool <= cap:
+            raise ValueError("need 2 <= top_k <= pool <= min(%d, the catalogue's %d items), got top_k %r, pool %r"
+                             % (ops.LIST_MAX_K, I, top_k, pool))
+        if isinstance(lambdas, (str, bytes)) or not hasattr(lambdas, "__len__") or not len(lambdas):
+            raise ValueError("lambdas must be a non-empty list of numbers in [0, 1], got %r" % (lambdas,))
+        for lam in lambdas:
+            if isinstance(lam, bool) or not isinstance(lam, (int, float, np.integer, np.floating)) or not 0.0 <= float(lam) <= 1.0:
+                raise ValueError("lambdas must be a non-empty list of numbers in [0, 1], got %r" % (lambdas,))
+        self.dataset = dataset
+        self.user_pos_train = user_train_dict
+        self.user_pos_test = user_test_dict
+        self.top_k, self.pool = int(top_k), int(pool)
+        self.lambdas = tuple(float(lam) for lam in lambdas)
+        self.users = list(user_test_dict.keys())
+        self.item_counts = item_train_counts(user_train_dict, I)
+        self.group_labels, self._positions = self._user_groups(self.users, user_train_dict, group_view)
+        self.columns = DIVERSIFY_COLUMNS
+
+    def _make_resident(self, device):
+        """The user group index, each group's user positions and the items' training counts resident on the device."""
+        return dict(groups=group_index(self._positions, len(self.users), device),
+                    positions=[torch.from_numpy(p).to(device) for p in self._positions],
+                    counts=torch.from_numpy(self.item_counts.astype(np.float64)).to(device))
+
+    def rerank_rows(self, model):
+        """Per lambda every test user's row and list on the device: (rows float32 [lambdas x users x 5] -- recall, ndcg,
+        ils_fused, pop, overlap --, lists int32 [lambdas x users x K], counts int32 [lambdas x num_items])."""
+        device = self._preflight(model)
+        res = self._resident(device)
+        K, N, L, n_users, nb = self.top_k, self.pool, len(self.lambdas), len(self.users), 1 + model.S
+        rows = torch.empty(L, n_users, 5, dtype=torch.float32, device=device)
+        lists = torch.empty(L, n_users, K, dtype=torch.int32, device=device)
+        counts = torch.zeros(L, self.num_items, dtype=torch.int32, device=device)
+        block = min(self.block_users, max(n_users, 1))
+        met = torch.empty(block, len(self.metrics), K, dtype=torch.float32, device=device)
+        ils = torch.empty(block, nb, dtype=torch.float32, device=device)
+        cnt = torch.empty(block, dtype=torch.int32, device=device)
+        for a, b, _, idx, val in self.top_lists(model, self.users, N, self.block_users, self.tie_order, with_values=True):
+            truth_ptr, truth_items = lists_csr(self.users[a:b], self.user_pos_test, device, unique=True)
+            plain = idx[:, :K].contiguous()
+            for li, lam in enumerate(self.lambdas):
+                out = lists[li, a:b]
+                model.rerank_device(idx, val, K, lam, space="fused", out_idx=out)
+                ops.rank_metrics(out, truth_ptr, truth_items, self.metrics, met[:b - a])
+                model.list_similarity_device(out, ils[:b - a], side="item")
+                ops.list_exposure(out, counts[li])
+                ops.list_overlap(plain, out, cnt[:b - a])
+                listed = out >= 0
+                pop = torch.where(listed, res["counts"][out.clamp(min=0).long()], 0.0).sum(dim=1) / listed.sum(dim=1).double()
+                rows[li, a:b, 0:2] = met[:b - a, :, K - 1]
+                rows[li, a:b, 2] = ils[:b - a, 0]
+                rows[li, a:b, 3] = pop.float()
+                rows[li, a:b, 4] = (cnt[:b - a].double() / K).float()
+        return rows, lists, counts
+
+    def evaluate(self, model, rows=None):
+        """(final, buf). final = DiversifyTables(columns, labels, table float64 [(1 + user groups) * lambdas x 9]): per group (row
+        block 0 = all test users) one row per lambda in self.lambdas' order. buf: a header of column names and one "%.8f" line per
+        row, in the grouped evaluator's format. rows: rerank_rows(model) if the caller already holds it."""
+        rows, lists, counts = self.rerank_rows(model) if rows is None else rows
+        res = self._resident(rows.device)
+        L, G = len(self.lambdas), len(self.group_labels)
+        every = [np.arange(self.num_items, dtype=np.int64)]
+        table = np.zeros((G * L, len(DIVERSIFY_COLUMNS)), dtype=np.float64)
+        for li, lam in enumerate(self.lambdas):
+            means = group_table(rows[li], res["groups"], G)
+            for g in range(G):
+                c = counts[li]
+                if g:                                  # a group's exposure: its own users' lists
+                    c = ops.list_exposure(lists[li].index_select(0, res["positions"][g]).contiguous(), torch.zeros_like(c))
+                table[g * L + li, 0] = lam
+                table[g * L + li, 1:6] = means[g]
+                table[g * L + li, 6:9] = exposure_summary(c.cpu().numpy(), every)[0, 1:4]
+        labels = [label for label in self.group_labels for _ in self.lambdas]
+        final = DiversifyTables(DIVERSIFY_COLUMNS, labels, table)
+        return final, format_table(final.columns, final.labels, final.table)

@@ -652,6 +652,32 @@ int elimrec_list_pair_cosine_chunk_cols(int K, int d);
  * order-free. K >= 1. */
 int elimrec_list_exposure(const int32_t *d_lists, int64_t B, int K, int64_t n_rows, int32_t *d_counts, void *stream);
 
+/* Diversified re-ranking (csrc/rerank.hip): greedy maximal marginal relevance (MMR) over top-N pools. No counterpart in the
+ * reference. d_T points at row 0, column 0 of an [n_rows x d] column block of a row-major float32 matrix with row stride ld >= d
+ * (as elimrec_cosine_topk takes it); d_sqnorm[r * ld_sq] = the squared norm of its row r. d_pool_idx int32 / d_pool_val float32
+ * [B x N] contiguous: per user a pool of N (id, score) positions. A position is listed when its id lies in [0, n_rows) and its
+ * score is finite; every entry is checked, an unlisted position is never dereferenced and never picked. Over the listed positions
+ *     rel_i = (s_i - s_min) / (s_max - s_min)   (fp32; 0 when s_max == s_min)
+ * and step t = 0 .. K - 1 picks, among the listed positions not picked yet, the largest
+ *     obj_t(i) = lambda * rel_i - (1 - lambda) * pen_t(i),   pen_0 = 0,   pen_t(i) = max over the picks j so far of cos(i, j),
+ *     cos(i, j) = ((T[i] . T[j]) * inv(sq_i)) * inv(sq_j),   inv(x) = 1 / max(sqrt(x), 1e-12)
+ * the lowest pool position winning among equal objectives; it stops after K picks or when no listed position is left. Duplicate
+ * ids are positions like any other. d_out_idx int32 [B x K] = the picked ids, d_out_pos int32 (nullable) their pool positions,
+ * d_out_val float32 (nullable) their objectives at pick time; unfilled slots are -1, -1, -inf; exactly B * K entries of each are
+ * written. d % 4 == 0, 4 <= d <= 256, 1 <= K <= N <= elimrec_mmr_max_pool() = 256, 0 <= lambda <= 1 (anything else: an error, no
+ * launch); B == 0 launches nothing; the rows of the block need not be 16-byte aligned.
+ * One workgroup per user (one wave for N <= 64, four above), one thread per pool position. elimrec_mmr_rows_in_lds(N, d) (host
+ * arithmetic; -1 for bad arguments) tells the form: 1 = the pool's rows are gathered once into LDS (N * (d + 4) floats fit
+ * 60 KiB) and every step reads them there; 0 = only the picked row is staged per step and the candidates' rows are read from
+ * global memory again. A dot product's summation order is fixed by d alone, the argmax is a wave reduction on (objective,
+ * -position) and then across the waves in wave order: no atomics, no workspace, and a user's outputs depend bit for bit on that
+ * user's pool, N, K, d and lambda only -- not on B, the user's place in the batch or the grid. One launch on `stream`. */
+int elimrec_mmr_rerank(const float *d_T, int64_t ld, int64_t n_rows, int d, const float *d_sqnorm, int64_t ld_sq,
+                       const int32_t *d_pool_idx, const float *d_pool_val, int64_t B, int N, int K, float lambda,
+                       int32_t *d_out_idx, int32_t *d_out_pos, float *d_out_val, void *stream);
+int elimrec_mmr_max_pool(void);
+int elimrec_mmr_rows_in_lds(int N, int d);
+
 /* ---------------------------------------------------------------- pairwise sampler (K20)
  * n triplets: user uniform over the `n_train_users` users with >= 1 training item (with
  * replacement), positive uniform over that user's training items, negative uniform over [0,I)

@@ -6,7 +6,7 @@
 Behaviour kept from the reference's `Net.run`: one pass of the pairwise sampler per epoch, validation every
 `test_step` epochs with predict_type TIE, a checkpoint + TE/TIE test pass whenever validation recall improves
 (not on epoch 0), early stop after `stop_cnt` epochs without improvement, the same log lines (`--group_view=[10,30,50,100]` adds
-the per-user-group table under each test line, `--effect_report=K` the effect breakdown of the top-K lists, `--rank_report=1` the test items' exact catalogue ranks, `--neighbour_report=K` the items' cosine neighbourhoods, fused against single-modal, `--list_report=K` the top-K lists' intra-list similarity and catalogue exposure; validation and model selection stay on the overall metrics). The per-batch work,
+the per-user-group table under each test line, `--effect_report=K` the effect breakdown of the top-K lists, `--rank_report=1` the test items' exact catalogue ranks, `--neighbour_report=K` the items' cosine neighbourhoods, fused against single-modal, `--list_report=K` the top-K lists' intra-list similarity and catalogue exposure, `--diversify_report=K` the top-N pools re-ranked to K items by greedy MMR per lambda; validation and model selection stay on the overall metrics). The per-batch work,
 the sampler and the evaluator run on the GPU (elimrec_amd). `--data.input.dataset=synthetic` uses the seeded
 Tiktok-shape generator instead of reading files.
 
@@ -111,6 +111,11 @@ class Net(object):
         self.list_report = int(cfg["list_report"]) if "list_report" in cfg else 0
         if self.list_report and self.world > 1:
             raise ValueError("--list_report needs the whole cached item table on one rank: it is single-GPU")
+        # --diversify_report=K (default 0: off): under each [TEST] line the top-N pools (--diversify_pool) re-ranked to K items by
+        # greedy MMR at every --diversify_lambda: recall / NDCG against intra-list similarity, popularity and exposure
+        self.diversify_report = int(cfg["diversify_report"]) if "diversify_report" in cfg else 0
+        if self.diversify_report and self.world > 1:
+            raise ValueError("--diversify_report needs the whole cached item table on one rank: it is single-GPU")
         Logger.info(count_parameters(self.recommender))
         self.opt = FusedAdam(self.recommender.parameters(), lr=cfg.lr, weight_decay=cfg.weight_decay)
         self.loss_name = str(cfg.loss)
@@ -255,6 +260,10 @@ class Net(object):
                 shown[effect] = rec.list_reporter.list_rows(rec)
                 Logger.info("  [{}] top-{} lists: similarity, popularity, exposure:\n{}".format(
                     effect, self.list_report, rec.list_reporter.evaluate(rec, shown[effect])[1]))
+            if self.diversify_report:      # the top-N pools under this effect re-ranked to K by greedy MMR, one row per lambda
+                reporter = rec.diversify_reporter
+                Logger.info("  [{}] top-{} of the top-{} pools by MMR, per lambda:\n{}".format(
+                    effect, reporter.top_k, reporter.pool, reporter.evaluate(rec)[1]))
         if self.rank_report:               # positive delta: TIE ranks the test item higher than TE does
             Logger.info("  [TE->TIE] rank shift of the test items:\n{}".format(rec.rank_reporter.shift(ranks["TE"], ranks["TIE"])[1]))
         if self.list_report:               # overlap: the share of the TE list that TIE keeps; d_<column>: TIE - TE
