@@ -219,6 +219,8 @@ SIGNATURES = {
                                    c_ptr, c_ptr]),
     "elimrec_mmr_max_pool": (c_i32, []),
     "elimrec_mmr_rows_in_lds": (c_i32, [c_i32, c_i32]),
+    "elimrec_pick_hard_negatives": (c_i32, [c_ptr, c_i64, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_i64, c_ptr, c_i64, c_i32, c_i32,
+                                            ctypes.POINTER(c_f32), c_ptr, c_ptr, c_i64, c_i32, c_ptr, c_ptr, c_ptr, c_ptr]),
     "elimrec_slab_partials_bytes": (c_size, [c_sell, c_i32, c_i32]),
     "elimrec_slab_hop": (c_i32, [c_sell, c_i32, c_i32, c_i32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_f32, c_ptr, c_size, c_i32,
                                  c_ptr]),
@@ -291,6 +293,8 @@ SIGNATURES = {
     "elimrec_comm_all_to_all": (c_i32, [c_ptr, c_ptr, c_ptr, c_i64, c_ptr]),
     "elimrec_comm_all_to_all_v": (c_i32, [c_ptr, c_ptr, c_ptr, ctypes.POINTER(c_i64), c_ptr]),
     "elimrec_sample_triplets": (c_i32, [c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_u64, c_u64, c_ptr, c_ptr, c_ptr, c_ptr]),
+    "elimrec_sample_triplet_candidates": (c_i32, [c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_u64, c_u64, c_i32, c_ptr, c_ptr, c_ptr,
+                                                  c_ptr]),
     "elimrec_sample_negatives": (c_i32, [c_ptr, c_ptr, c_i64, c_i64, c_i32, c_u64, c_ptr, c_ptr]),
     "elimrec_score_candidates": (c_i32, [c_ptr, c_i64, c_i64, c_i64, c_ptr, c_i32, c_i32, c_i32, c_u32, c_i32, c_i32,
                                          c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_i64, c_ptr]),

@@ -29,29 +29,14 @@ struct Philox {
     }
 };
 
-__global__ void sample_triplets_kernel(const int32_t *__restrict__ user_ids, const int64_t *__restrict__ ptr,
-                                       const int32_t *__restrict__ items, int64_t n_train_users, int64_t I, int64_t n,
-                                       uint64_t seed, uint64_t epoch, int64_t *__restrict__ users,
-                                       int64_t *__restrict__ pos, int64_t *__restrict__ neg) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    Philox ph;
-    ph.k[0] = (uint32_t)seed; ph.k[1] = (uint32_t)(seed >> 32);
-    ph.c[0] = (uint32_t)i; ph.c[1] = (uint32_t)((uint64_t)i >> 32);
-    ph.c[2] = (uint32_t)epoch; ph.c[3] = (uint32_t)(epoch >> 32) & 0x00FFFFFFu;   // top byte = draw round
+// One id uniform over [0, I) outside the sorted training items [beg, end): rejection over the draw rounds 1 .. 255 of the stream
+// whose counter word 3 is c3_low (low 24 bits) | round << 24, two 64-bit draws per round; ph.c[0 .. 2] and the key are the caller's.
+__device__ inline int64_t draw_outside(Philox &ph, uint32_t c3_low, const int32_t *__restrict__ items, int64_t beg, int64_t end,
+                                       int64_t I) {
     uint32_t r[4];
-    ph.generate(r);
-    const uint64_t ru = ((uint64_t)r[0] << 32) | r[1];
-    const uint64_t rp = ((uint64_t)r[2] << 32) | r[3];
-    const int64_t ui = (int64_t)(ru % (uint64_t)n_train_users);
-    const int64_t beg = ptr[ui], end = ptr[ui + 1];
-    const int64_t cnt = end - beg;
-    users[i] = user_ids[ui];
-    pos[i] = items[beg + (int64_t)(rp % (uint64_t)cnt)];
-    // negatives: uniform over [0, I), rejected while in the user's (sorted) training items
     int64_t cand = -1;
     for (uint32_t round = 1; round < 256 && cand < 0; ++round) {
-        ph.c[3] = ((uint32_t)(epoch >> 32) & 0x00FFFFFFu) | (round << 24);
+        ph.c[3] = c3_low | (round << 24);
         ph.generate(r);
 #pragma unroll
         for (int t = 0; t < 2 && cand < 0; ++t) {
@@ -69,11 +54,64 @@ __global__ void sample_triplets_kernel(const int32_t *__restrict__ user_ids, con
         }
     }
     if (cand < 0) {   // a user who interacted with almost every item: the first id missing from the sorted list
+        const int64_t cnt = end - beg;
         int64_t k = 0;
         while (k < cnt && items[beg + k] == (int32_t)k) ++k;
         cand = k;      // < I: the host rejects users with >= I training items
     }
-    neg[i] = cand;
+    return cand;
+}
+
+// The user and the positive of triplet i: the stream's round 0 (counter word 3 = the epoch's bits 32 .. 55, top byte 0).
+// -> the user's slice [beg, end) of items; ph is left keyed by seed with c[0 .. 2] = (i, epoch's low word).
+__device__ inline void draw_user_pos(Philox &ph, int64_t i, uint64_t seed, uint64_t epoch, const int32_t *__restrict__ user_ids,
+                                     const int64_t *__restrict__ ptr, const int32_t *__restrict__ items, int64_t n_train_users,
+                                     int64_t &user, int64_t &pos, int64_t &beg, int64_t &end) {
+    ph.k[0] = (uint32_t)seed; ph.k[1] = (uint32_t)(seed >> 32);
+    ph.c[0] = (uint32_t)i; ph.c[1] = (uint32_t)((uint64_t)i >> 32);
+    ph.c[2] = (uint32_t)epoch; ph.c[3] = (uint32_t)(epoch >> 32) & 0x00FFFFFFu;   // top byte = draw round
+    uint32_t r[4];
+    ph.generate(r);
+    const uint64_t ru = ((uint64_t)r[0] << 32) | r[1];
+    const uint64_t rp = ((uint64_t)r[2] << 32) | r[3];
+    const int64_t ui = (int64_t)(ru % (uint64_t)n_train_users);
+    beg = ptr[ui]; end = ptr[ui + 1];
+    user = user_ids[ui];
+    pos = items[beg + (int64_t)(rp % (uint64_t)(end - beg))];
+}
+
+__global__ void sample_triplets_kernel(const int32_t *__restrict__ user_ids, const int64_t *__restrict__ ptr,
+                                       const int32_t *__restrict__ items, int64_t n_train_users, int64_t I, int64_t n,
+                                       uint64_t seed, uint64_t epoch, int64_t *__restrict__ users,
+                                       int64_t *__restrict__ pos, int64_t *__restrict__ neg) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Philox ph;
+    int64_t beg, end;
+    draw_user_pos(ph, i, seed, epoch, user_ids, ptr, items, n_train_users, users[i], pos[i], beg, end);
+    // negatives: uniform over [0, I), rejected while in the user's (sorted) training items
+    neg[i] = draw_outside(ph, (uint32_t)(epoch >> 32) & 0x00FFFFFFu, items, beg, end, I);
+}
+
+// M candidate negatives per triplet (hard-negative sampling, csrc/hardneg.hip picks among them): one thread per (triplet i,
+// column j). Users, positives and column 0 are the words of sample_triplets_kernel for the same (seed, epoch, i). Column j > 0 is
+// an independent draw of the same kind from a stream of its own: the LOW 24 BITS OF COUNTER WORD 3 CARRY j (1 .. 63), the top
+// byte the draw round, words 0 .. 2 stay (i, the epoch's low word) and the key the seed. sample_triplets_kernel has the epoch's
+// bits 32 .. 55 in those 24 bits -- zero for every epoch < 2^32 -- so no (i, epoch < 2^32, round) of it reaches a counter of a
+// column j > 0, round 0 (the user / positive draw) included; two columns differ in word 3, two epochs in word 2.
+__global__ void sample_triplet_candidates_kernel(const int32_t *__restrict__ user_ids, const int64_t *__restrict__ ptr,
+                                                 const int32_t *__restrict__ items, int64_t n_train_users, int64_t I, int64_t n,
+                                                 uint64_t seed, uint64_t epoch, int M, int64_t *__restrict__ users,
+                                                 int64_t *__restrict__ pos, int32_t *__restrict__ cands) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= n * M) return;
+    const int64_t i = idx / M;
+    const int j = (int)(idx - i * M);
+    Philox ph;
+    int64_t user, p, beg, end;
+    draw_user_pos(ph, i, seed, epoch, user_ids, ptr, items, n_train_users, user, p, beg, end);
+    if (j == 0) { users[i] = user; pos[i] = p; }
+    cands[idx] = (int32_t)draw_outside(ph, j == 0 ? (uint32_t)(epoch >> 32) & 0x00FFFFFFu : (uint32_t)j, items, beg, end, I);
 }
 
 
@@ -152,6 +190,22 @@ extern "C" int elimrec_sample_triplets(const int32_t *d_user_ids, const int64_t 
     hipLaunchKernelGGL(sample_triplets_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        d_user_ids, d_ptr, d_items, n_train_users, I, n, seed, epoch, d_users, d_pos, d_neg);
     ELIMREC_LAUNCH_CHECK("sample_triplets");
+    return 0;
+}
+
+extern "C" int elimrec_sample_triplet_candidates(const int32_t *d_user_ids, const int64_t *d_ptr, const int32_t *d_items,
+                                                 int64_t n_train_users, int64_t I, int64_t n, uint64_t seed, uint64_t epoch,
+                                                 int n_cand, int64_t *d_users, int64_t *d_pos, int32_t *d_cands, void *stream) {
+    ELIMREC_REQUIRE(d_user_ids && d_ptr && d_items && d_users && d_pos && d_cands, "sample_triplet_candidates: null pointer");
+    ELIMREC_REQUIRE(n_train_users > 0 && I > 0, "sample_triplet_candidates: 'user_pos_dict' cannot be empty.");
+    ELIMREC_REQUIRE(I < (int64_t)INT32_MAX, "sample_triplet_candidates: the candidates are int32, I < 2^31 - 1");
+    ELIMREC_REQUIRE(n_cand >= 1 && n_cand <= 64, "sample_triplet_candidates: 1 <= n_cand <= 64, got %d", n_cand);
+    if (n <= 0) return 0;
+    ELIMREC_REQUIRE(n < ((int64_t)1 << 31), "sample_triplet_candidates: n < 2^31");
+    hipLaunchKernelGGL(sample_triplet_candidates_kernel, dim3((unsigned)((n * n_cand + 255) / 256)), dim3(256), 0,
+                       (hipStream_t)stream, d_user_ids, d_ptr, d_items, n_train_users, I, n, seed, epoch, n_cand, d_users, d_pos,
+                       d_cands);
+    ELIMREC_LAUNCH_CHECK("sample_triplet_candidates");
     return 0;
 }
 

@@ -23,6 +23,9 @@
 //   list_exposure(lists i32[B x K], n_rows) -> i32[n_rows]: how often every row is listed
 //   mmr_rerank(table f32[n x d], sqnorm f32[n], pool_idx i32[B x N], pool_val f32[B x N], K, lam) -> (idx i32, pos i32, val f32) [B x K]:
 //       greedy maximal-marginal-relevance re-ranking of each pool (unlisted entries are never picked; -1 / -1 / -inf fillers)
+//   pick_hard_negatives(user_table f32[U x blocks*d], user_sqnorm f32[U x blocks], item_table f32[I x blocks*d], item_sqnorm, weights
+//     float[blocks], users i64[n], cands i32[n x M]) -> (neg i64, pos i32, score f32) [n]: per triplet the listed candidate with the largest
+//     sum_b w_b cos_b(u, i), the lowest column among equals; -1 / -1 / -inf without one (csrc/hardneg.hip)
 //   sample_triplets(user_ids, ptr, items, num_items, n, seed, epoch) -> (users, pos, neg)
 //   score_candidates(Y, U, I, users, d, S, head_mask, fusion_mode, predict_type, cand_ptr, cand_items, width) -> f32[B x width]
 //       (each row: its candidates' scores in list order, then -inf)
@@ -462,6 +465,37 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> mmr_rerank(const at::Tensor &tabl
     return {idx, pos, val};
 }
 
+// ---- hard-negative pick: per triplet the best of M candidates over the tables' column blocks
+std::tuple<at::Tensor, at::Tensor, at::Tensor> pick_hard_negatives(const at::Tensor &user_table, const at::Tensor &user_sqnorm,
+                                                                   const at::Tensor &item_table, const at::Tensor &item_sqnorm,
+                                                                   at::ArrayRef<double> weights, const at::Tensor &users,
+                                                                   const at::Tensor &cands) {
+    const at::Tensor ut = rowmajor(user_table, "user_table"), it = rowmajor(item_table, "item_table");
+    need(user_sqnorm, "user_sqnorm", at::kFloat); need(item_sqnorm, "item_sqnorm", at::kFloat);
+    need(users, "users", at::kLong, 1); need(cands, "cands", at::kInt, 2);
+    const at::Tensor us = users.contiguous(), c = cands.contiguous();
+    const int64_t blocks = (int64_t)weights.size(), n = c.size(0), M = c.size(1), U = ut.size(0), I = it.size(0);
+    TORCH_CHECK(blocks >= 1 && blocks <= 8 && ut.size(1) % blocks == 0 && ut.size(1) == it.size(1),
+                "elimrec::pick_hard_negatives: 1 <= blocks <= 8 weights, and two tables of one width that splits into as many blocks");
+    const int64_t d = ut.size(1) / blocks;
+    TORCH_CHECK(d % 4 == 0 && d >= 4 && d <= 256, "elimrec::pick_hard_negatives: a block needs d % 4 == 0 and 4 <= d <= 256 columns, got ", d);
+    TORCH_CHECK(M >= 1 && M <= 64 && us.numel() == n, "elimrec::pick_hard_negatives: cands [n x M] with 1 <= M <= 64 and users [n]");
+    TORCH_CHECK(user_sqnorm.numel() == U * blocks && item_sqnorm.numel() == I * blocks && (blocks == 1 || (user_sqnorm.dim() == 2 && item_sqnorm.dim() == 2)),
+                "elimrec::pick_hard_negatives: the sqnorms must be [rows x ", blocks, "]");
+    const at::Tensor su = (user_sqnorm.dim() == 1 || user_sqnorm.stride(1) == 1 || blocks == 1) ? user_sqnorm : user_sqnorm.contiguous();
+    const at::Tensor si = (item_sqnorm.dim() == 1 || item_sqnorm.stride(1) == 1 || blocks == 1) ? item_sqnorm : item_sqnorm.contiguous();
+    float w[8];
+    for (int64_t b = 0; b < blocks; ++b) w[b] = (float)weights[b];
+    at::Tensor neg = at::empty({n}, us.options()), pos = at::empty({n}, c.options()), score = at::empty({n}, ut.options());
+    if (n == 0) return {neg, pos, score};
+    check(elimrec_pick_hard_negatives(ut.data_ptr<float>(), ut.stride(0), U, su.data_ptr<float>(), std::max<int64_t>(blocks, U > 1 ? su.stride(0) : blocks),
+                                      it.data_ptr<float>(), it.stride(0), I, si.data_ptr<float>(), std::max<int64_t>(blocks, I > 1 ? si.stride(0) : blocks),
+                                      (int)blocks, (int)d, w, us.data_ptr<int64_t>(), c.data_ptr<int32_t>(), n, (int)M,
+                                      neg.data_ptr<int64_t>(), pos.data_ptr<int32_t>(), score.data_ptr<float>(), cur_stream()),
+          "pick_hard_negatives");
+    return {neg, pos, score};
+}
+
 at::Tensor sample_negatives(const at::Tensor &excl_ptr, const at::Tensor &excl_items, int64_t num_items, int64_t n_neg, int64_t seed) {
     need(excl_ptr, "excl_ptr", at::kLong, 1); need(excl_items, "excl_items", at::kInt, 1);
     const at::Tensor p = excl_ptr.contiguous(), it = excl_items.contiguous();
@@ -586,6 +620,8 @@ TORCH_LIBRARY(elimrec, m) {
     m.def("list_pair_cosine(Tensor table, Tensor sqnorm, Tensor lists, int blocks) -> Tensor");
     m.def("list_exposure(Tensor lists, int n_rows) -> Tensor");
     m.def("mmr_rerank(Tensor table, Tensor sqnorm, Tensor pool_idx, Tensor pool_val, int K, float lam) -> (Tensor, Tensor, Tensor)");
+    m.def("pick_hard_negatives(Tensor user_table, Tensor user_sqnorm, Tensor item_table, Tensor item_sqnorm, float[] weights, Tensor users, "
+          "Tensor cands) -> (Tensor, Tensor, Tensor)");
     m.def("sample_negatives(Tensor excl_ptr, Tensor excl_items, int num_items, int n_neg, int seed) -> Tensor");
     m.def("lookup_counts(Tensor acts, int U, int I, int[] user_bounds, int[] item_bounds) -> Tensor");
     m.def("lookup_pack(Tensor acts, int U, int I, int[] user_bounds, int[] item_bounds, int me, Tensor shard, int row_bytes) -> (Tensor, Tensor)");
@@ -615,6 +651,7 @@ TORCH_LIBRARY_IMPL(elimrec, CUDA, m) {
     m.impl("list_pair_cosine", &list_pair_cosine);
     m.impl("list_exposure", &list_exposure);
     m.impl("mmr_rerank", &mmr_rerank);
+    m.impl("pick_hard_negatives", &pick_hard_negatives);
     m.impl("sample_negatives", &sample_negatives);
     m.impl("lookup_counts", &lookup_counts);
     m.impl("lookup_pack", &lookup_pack);

@@ -1465,6 +1465,49 @@ class EliMRec(BasicModel):
                        out_val)
         return out_idx, out_pos, out_val
 
+    def has_cached_tables(self):
+        """Whether a training forward has cached tables -- what predict() and every reader of the cached Y need (a bpr_loss whose
+        step is still pending counts: _cached_tables makes it real). Never raises."""
+        if getattr(self._plugin, "pending", None) is not None:
+            return True
+        return self._ws is not None and self._cache is not None
+
+    def hard_negative_weights(self, space):
+        """Per block of the cached Y the weight a hard-negative space puts on its cosine: "fused" / a head letter: that block
+        alone; "loss": the logits of the training loss (:125-142) -- 1 on the fused block, alpha on every active head
+        (_block_weights; under predict_type "normal" there are no single-modal terms and "loss" is "fused")."""
+        if space == "loss":
+            return [float(w) for w in self._block_weights()]
+        h = self._neighbour_space(space)
+        return [1.0 if b == h else 0.0 for b in range(1 + self.S)]
+
+    @torch.no_grad()
+    def hard_negatives_device(self, users, cands, space="fused", out_neg=None, out_pos=None, out_score=None):
+        """Dynamic negative sampling's pick: per triplet the candidate item the cached tables score highest, ONE launch
+        (csrc/hardneg.hip). users int64 [n], cands int32 [n x M] on the device, 1 <= M <= ops.HARD_NEG_MAX_CANDIDATES; a candidate
+        outside the catalogue is never picked. The score of (u, i) is the weighted sum of the blocks' cosines between user row u
+        and item row i of the cached Y; space: "fused" (block 0, the rows predict() scores with), a head letter of self._mods
+        (that block alone), or "loss" (the training loss's logits: the fused block plus alpha times every active head).
+        -> (out_neg int64 [n] the picked ids, out_pos int32 [n] their columns, out_score float32 [n] their scores), the lowest
+        column among equal scores, -1 / -1 / -inf for a row without a listed candidate; allocated here unless given. Tables as
+        predict_device: those of the last training forward."""
+        w = self.hard_negative_weights(space)
+        self._require_gpu()
+        dev = self._cached_tables("hard_negatives_device() needs", "hard-negative sampling needs the whole cached item table on this "
+                                  "rank; the tables are item-sharded (lean / multi-rank evaluation)")
+        U, I, d, nb = self.num_users, self.num_items, self.latent_dim, 1 + self.S
+        sqn = self._block_sqnorms(dev)
+        n = users.numel()
+        if out_neg is None:
+            out_neg = torch.empty(n, dtype=torch.int64, device=dev)
+        if out_pos is None:
+            out_pos = torch.empty(n, dtype=torch.int32, device=dev)
+        if out_score is None:
+            out_score = torch.empty(n, dtype=torch.float32, device=dev)
+        Y = self._ws["Y"]
+        ops.pick_hard_negatives(Y[:U, :nb * d], sqn[:U], Y[U:U + I, :nb * d], sqn[U:U + I], w, users, cands, out_neg, out_pos, out_score)
+        return out_neg, out_pos, out_score
+
     def recommend_diverse(self, user_ids, k, pool=None, lam=0.7, space="fused", exclude=None):
         """k items per user from the user's top-`pool` list, trading relevance against similarity to what is already picked
         (greedy MMR, rerank_device): CPU (ids int32 [B x k], scores fp32 [B x k]) in pick order -- scores are the model's scores

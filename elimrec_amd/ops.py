@@ -944,6 +944,27 @@ def sample_triplets(user_ids, ptr, items, num_items, n, seed, epoch, users, pos,
                                                    _stream()), "sample_triplets")
 
 
+HARD_NEG_MAX_CANDIDATES = 64            # candidates per triplet sample_triplet_candidates draws and pick_hard_negatives takes
+
+
+def sample_triplet_candidates(user_ids, ptr, items, num_items, n, seed, epoch, n_cand, users, pos, cands):
+    """elimrec_sample_triplet_candidates: sample_triplets with n_cand candidate negatives per triplet. users / pos int64 [n]: bit
+    for bit sample_triplets' for the same (seed, epoch); cands int32 [n x n_cand] contiguous: column 0 is sample_triplets' negative,
+    every further column an independent draw of the same kind from a Philox stream of its own (duplicates within a row are
+    allowed). 1 <= n_cand <= HARD_NEG_MAX_CANDIDATES."""
+    n, n_cand = int(n), int(n_cand)
+    if not 1 <= n_cand <= HARD_NEG_MAX_CANDIDATES:
+        raise ValueError("elimrec_amd.ops.sample_triplet_candidates: 1 <= n_cand <= %d, got %d" % (HARD_NEG_MAX_CANDIDATES, n_cand))
+    if not (isinstance(cands, torch.Tensor) and cands.is_contiguous() and tuple(cands.shape) == (n, n_cand)):
+        raise ValueError("elimrec_amd.ops.sample_triplet_candidates: cands must be a contiguous [%d x %d] tensor" % (n, n_cand))
+    if users.numel() < n or pos.numel() < n or not users.is_contiguous() or not pos.is_contiguous():
+        raise ValueError("elimrec_amd.ops.sample_triplet_candidates: users and pos must be contiguous with at least %d entries" % n)
+    _lib.check(_lib.load().elimrec_sample_triplet_candidates(
+        _dev(user_ids, "user_ids", torch.int32), _dev(ptr, "ptr", torch.int64), _dev(items, "items", torch.int32), user_ids.numel(),
+        num_items, n, int(seed), int(epoch), n_cand, _dev(users, "users", torch.int64), _dev(pos, "pos", torch.int64),
+        _dev(cands, "cands", torch.int32), _stream()), "sample_triplet_candidates")
+
+
 def score_candidates(Y, U, I, users, d, S, head_mask, fusion_mode, predict_type, cand_ptr, cand_items, out, sqnorm=None,
                      row_sum=None, I_total=0):
     """elimrec_score_candidates: out [B x width] (rows contiguous) = each user's candidate scores in list order, then -inf.
@@ -1370,3 +1391,70 @@ def mmr_rerank(table, sqnorm, pool_idx, pool_val, K, lam, out_idx, out_pos=None,
         return out_idx
     _lib.check(_lib.load().elimrec_mmr_rerank(tp, ld, n, d, sp, ld_sq, pi, pv, B, N, K, lam, ip, pp, vp, _stream()), "mmr_rerank")
     return out_idx
+
+
+def _block_table(table, sqnorm, blocks, name, who):
+    """(pointer, ld, rows, d, norm pointer, norm ld) of a [rows x blocks * d] table with its [rows x blocks] squared norms, as
+    list_pair_cosine takes the pair."""
+    if not isinstance(table, torch.Tensor) or not isinstance(sqnorm, torch.Tensor):
+        raise RuntimeError("elimrec_amd.ops: '%s' and its sqnorm must be HIP device tensors (the hot path has no CPU implementation)" % name)
+    if table.dim() != 2 or table.stride(1) != 1:
+        raise ValueError("elimrec_amd.ops.%s: %s must be 2-D with unit column stride" % (who, name))
+    rows, width = table.shape
+    if width % blocks != 0:
+        raise ValueError("elimrec_amd.ops.%s: the %d columns of %s do not split into %d equal blocks" % (who, width, name, blocks))
+    d = width // blocks
+    if d % 4 != 0 or not 4 <= d <= KNN_MAX_D:
+        raise ValueError("elimrec_amd.ops.%s: a block needs d %% 4 == 0 and 4 <= d <= %d columns, got %d" % (who, KNN_MAX_D, d))
+    if sqnorm.dim() == 1 and blocks == 1 and sqnorm.numel() == rows:
+        ld_sq = max(1, int(sqnorm.stride(0)))
+    elif sqnorm.dim() == 2 and tuple(sqnorm.shape) == (rows, blocks) and (sqnorm.stride(1) == 1 or blocks == 1):
+        ld_sq = max(blocks, int(sqnorm.stride(0)))
+    else:
+        raise ValueError("elimrec_amd.ops.%s: the sqnorm of %s must be [%d x %d] with unit column stride (or 1-D with %d entries when "
+                         "blocks == 1)" % (who, name, rows, blocks, rows))
+    if sqnorm.device != table.device:
+        raise ValueError("elimrec_amd.ops.%s: the sqnorm of %s must live on its device" % (who, name))
+    tp, ld = _rowmajor(table, name)
+    return tp, ld, rows, d, _dev(sqnorm, name + " sqnorm"), ld_sq
+
+
+def pick_hard_negatives(user_table, user_sqnorm, item_table, item_sqnorm, weights, users, cands, out_neg, out_pos=None, out_score=None):
+    """elimrec_pick_hard_negatives: per triplet the candidate the tables score highest. user_table [U x blocks * d] / item_table
+    [I x blocks * d] float32 with unit column stride (column slices of wider matrices are fine), block b = columns
+    [b * d, (b + 1) * d), d % 4 == 0, 4 <= d <= 256; user_sqnorm [U x blocks] / item_sqnorm [I x blocks] with unit column stride
+    (1-D with any stride when blocks == 1): the rows' squared norms per block (row_sqnorms' table or a slice of it). weights: a HOST
+    sequence of 1 <= blocks <= 8 floats; score(u, i) = sum_b weights[b] * cos_b(u, i) over the blocks with a non-zero weight, in
+    block order -- a block with zero weight is not read. users int64 [n], cands int32 [n x M] contiguous, 1 <= M <=
+    HARD_NEG_MAX_CANDIDATES, on the tables' device: a candidate outside [0, I) is not listed (the kernel checks every entry, no host
+    check is needed). out_neg int64 [n] <- the id of the listed candidate with the largest score, the lowest column among equals;
+    out_pos int32 [n] (optional) its column, out_score float32 [n] (optional) its score; -1 / -1 / -inf for a row with no listed
+    candidate or a user outside [0, U). Outputs: contiguous 1-D with at least n entries; entries beyond n are left alone. A
+    triplet's bits depend on its rows, d, blocks and weights alone (csrc/hardneg.hip)."""
+    w = [float(x) for x in (weights.tolist() if hasattr(weights, "tolist") else weights)]
+    blocks = len(w)
+    if not 1 <= blocks <= LIST_MAX_BLOCKS:
+        raise ValueError("elimrec_amd.ops.pick_hard_negatives: weights needs 1 <= blocks <= %d entries, got %d" % (LIST_MAX_BLOCKS, blocks))
+    up, ld_u, U, d, squ, ldsq_u = _block_table(user_table, user_sqnorm, blocks, "user_table", "pick_hard_negatives")
+    ip, ld_i, I, d_i, sqi, ldsq_i = _block_table(item_table, item_sqnorm, blocks, "item_table", "pick_hard_negatives")
+    if d_i != d or item_table.device != user_table.device:
+        raise ValueError("elimrec_amd.ops.pick_hard_negatives: the two tables need one block width and one device")
+    cp = _int_lists(cands, "cands", "pick_hard_negatives")
+    n, M = cands.shape
+    if not 1 <= M <= HARD_NEG_MAX_CANDIDATES:
+        raise ValueError("elimrec_amd.ops.pick_hard_negatives: 1 <= M <= %d, got %d" % (HARD_NEG_MAX_CANDIDATES, M))
+    usp = _dev(users, "users", torch.int64)
+    if users.dim() != 1 or users.numel() != n or not users.is_contiguous() or users.device != user_table.device \
+            or cands.device != user_table.device:
+        raise ValueError("elimrec_amd.ops.pick_hard_negatives: users must be a contiguous [%d] tensor, one per row of cands, both on "
+                         "the tables' device" % n)
+    dev = user_table.device
+    np_ = _rows_out(out_neg, "out_neg", torch.int64, n, 1, "pick_hard_negatives", device=dev)
+    pp = _rows_out(out_pos, "out_pos", torch.int32, n, 1, "pick_hard_negatives", device=dev) if out_pos is not None else None
+    sp = _rows_out(out_score, "out_score", torch.float32, n, 1, "pick_hard_negatives", device=dev) if out_score is not None else None
+    if n == 0:
+        return out_neg
+    _lib.check(_lib.load().elimrec_pick_hard_negatives(up, ld_u, U, squ, ldsq_u, ip, ld_i, I, sqi, ldsq_i, blocks, d,
+                                                       (ctypes.c_float * blocks)(*w), usp, cp, n, M, np_, pp, sp, _stream()),
+               "pick_hard_negatives")
+    return out_neg

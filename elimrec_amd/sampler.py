@@ -10,6 +10,12 @@ catalogue minus the user's training items. The draws are i.i.d., so the referenc
 `shuffle` pass is a distributional no-op and is not repeated. The random stream is Philox keyed
 by (seed, epoch) -- the reference's libc rand() stream cannot be reproduced on a GPU and is
 never seeded there either (random_choice.pyx:8).
+
+neg_sampling="hard" (dynamic negative sampling, not in the reference): M = neg_candidates uniform candidates are drawn per triplet
+-- column 0 is the uniform sampler's negative -- and the epoch trains on the one the model's cached tables score highest
+(EliMRec.hard_negatives_device, csrc/hardneg.hip). The tables are those of the last training forward, so an epoch's negatives are
+picked by the model as it stood at the end of the epoch before; while no forward has cached tables (the first epoch of a run, the
+first one after a resume) the epoch is the uniform one, bit for bit.
 """
 import numpy as np
 import torch
@@ -19,13 +25,26 @@ from . import ops
 
 class PairwiseSamplerV2(object):
     def __init__(self, dataset, neg_num=1, batch_size=1024, shuffle=True, drop_last=False, device=None, seed=2022,
-                 shard=None):
+                 shard=None, neg_sampling="uniform", neg_candidates=8, neg_space="fused", model=None):
         """shard = (rank, world): this process draws its 1/world share of the epoch's `num_trainings` triplets (rounded
-        up, so every rank runs the same number of batches); give every rank its own seed."""
+        up, so every rank runs the same number of batches); give every rank its own seed.
+        neg_sampling: "uniform" (one uniform negative) or "hard" (the best of neg_candidates uniform candidates under `model`'s
+        cached tables, scored in neg_space: "fused", "loss" or a head letter -- EliMRec.hard_negatives_device)."""
         if neg_num <= 0:
             raise ValueError("'neg_num' must be a positive integer.")
         if neg_num != 1:
             raise NotImplementedError("neg_num > 1 is not used by the EliMRec driver (main.py:59)")
+        if neg_sampling not in ("uniform", "hard"):
+            raise ValueError("neg_sampling must be 'uniform' or 'hard', got %r" % (neg_sampling,))
+        if isinstance(neg_candidates, bool) or int(neg_candidates) != neg_candidates \
+                or not 1 <= int(neg_candidates) <= ops.HARD_NEG_MAX_CANDIDATES:
+            raise ValueError("neg_candidates must be an integer in [1, %d], got %r" % (ops.HARD_NEG_MAX_CANDIDATES, neg_candidates))
+        if neg_sampling == "hard":
+            if model is None:
+                raise ValueError("neg_sampling='hard' needs the model whose cached tables score the candidates (model=...)")
+            model.hard_negative_weights(neg_space)             # ValueError for a space the model does not have
+        self.neg_sampling, self.neg_candidates, self.neg_space, self.model = neg_sampling, int(neg_candidates), neg_space, model
+        self.last_stats = None                                 # of the last hard epoch: hard, moved, score_picked, score_first
         self.batch_size, self.drop_last, self.shuffle, self.neg_num = batch_size, drop_last, shuffle, neg_num
         self.item_num = dataset.num_items
         user_pos = dataset.get_user_train_dict()
@@ -70,10 +89,29 @@ class PairwiseSamplerV2(object):
         n = self.num_trainings
         u = torch.empty(n, dtype=torch.int64, device=device)
         p = torch.empty_like(u)
+        if self.neg_sampling == "hard":
+            return u, p, self._hard_negatives(u, p, device)
         q = torch.empty_like(u)
         ops.sample_triplets(self._dev[0], self._dev[1], self._dev[2], self.item_num, n, self.seed, self.epoch, u, p, q)
         self.epoch += 1
         return u, p, q
+
+    def _hard_negatives(self, u, p, device):
+        """Draws users, positives (into u, p) and [n x M] candidates, and picks per triplet the candidate the model's cached
+        tables score highest; candidate 0 -- the uniform negative -- while the model has no cached tables. Fills last_stats."""
+        n, M = self.num_trainings, self.neg_candidates
+        cands = torch.empty(n, M, dtype=torch.int32, device=device)
+        ops.sample_triplet_candidates(self._dev[0], self._dev[1], self._dev[2], self.item_num, n, self.seed, self.epoch, M, u, p, cands)
+        self.epoch += 1
+        if not self.model.has_cached_tables():
+            self.last_stats = dict(hard=False, moved=0.0, score_picked=float("nan"), score_first=float("nan"))
+            return cands[:, 0].long()
+        neg, pos, score = self.model.hard_negatives_device(u, cands, space=self.neg_space)
+        first = self.model.hard_negatives_device(u, cands[:, :1].contiguous(), space=self.neg_space)[2]
+        self.last_stats = dict(hard=True, moved=float((pos != 0).float().mean().item()) if n else 0.0,
+                               score_picked=float(score.mean().item()) if n else float("nan"),
+                               score_first=float(first.mean().item()) if n else float("nan"))
+        return neg
 
     def __iter__(self):
         u, p, q = self.sample_epoch()

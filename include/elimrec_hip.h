@@ -678,6 +678,26 @@ int elimrec_mmr_rerank(const float *d_T, int64_t ld, int64_t n_rows, int d, cons
 int elimrec_mmr_max_pool(void);
 int elimrec_mmr_rows_in_lds(int N, int d);
 
+/* Hard-negative pick (csrc/hardneg.hip): per triplet the best of M candidate items under the current tables. No counterpart in
+ * the reference. d_U / d_T point at row 0, column 0 of an [n_users x blocks * d] / [n_items x blocks * d] slice of a row-major
+ * float32 matrix with row stride ld_u / ld_i >= blocks * d, block b = columns [b * d, (b + 1) * d); d_sq_u[r * ldsq_u + b] /
+ * d_sq_i[r * ldsq_i + b] = the squared norm of row r of block b (as elimrec_list_pair_cosine takes them). h_weights: `blocks`
+ * floats ON THE HOST (they travel in the launch's arguments). d_users int64 [n], d_cands int32 [n x M] contiguous.
+ *     score(u, i) = sum over the blocks b with w_b != 0, in block order, of w_b * ((U_b[u] . T_b[i]) * inv(squ[u, b])) * inv(sqi[i, b]),
+ *     inv(x) = 1 / max(sqrt(x), 1e-12);   a block with zero weight is not read.
+ * A candidate is listed when its id lies in [0, n_items); every entry is checked, an unlisted one is never dereferenced. Per
+ * triplet the listed candidate with the largest score wins, the lowest column among equal scores: d_out_neg int64 [n] = its id,
+ * d_out_pos int32 [n] (nullable) = its column, d_out_score float32 [n] (nullable) = its score; a triplet with no listed candidate,
+ * or with a user id outside [0, n_users), gets -1 / -1 / -inf. d % 4 == 0, 4 <= d <= 256, 1 <= blocks <= 8, 1 <= M <= 64,
+ * 0 <= n < 2^31 - 1 (n == 0 launches nothing); the rows of either slice need not be 16-byte aligned.
+ * 16 lanes per triplet, the user's block held in registers; a dot product's summation order is fixed by d alone and the argmax
+ * is a lane-group reduction on (score, -column): no atomics, no workspace, and a triplet's outputs depend bit for bit on its
+ * rows, d, blocks and the weights only -- not on M, the candidate's column, n or the grid. One launch on `stream`. */
+int elimrec_pick_hard_negatives(const float *d_U, int64_t ld_u, int64_t n_users, const float *d_sq_u, int64_t ldsq_u,
+                                const float *d_T, int64_t ld_i, int64_t n_items, const float *d_sq_i, int64_t ldsq_i,
+                                int blocks, int d, const float *h_weights, const int64_t *d_users, const int32_t *d_cands,
+                                int64_t n, int M, int64_t *d_out_neg, int32_t *d_out_pos, float *d_out_score, void *stream);
+
 /* ---------------------------------------------------------------- pairwise sampler (K20)
  * n triplets: user uniform over the `n_train_users` users with >= 1 training item (with
  * replacement), positive uniform over that user's training items, negative uniform over [0,I)
@@ -689,6 +709,17 @@ int elimrec_sample_triplets(const int32_t *d_user_ids, const int64_t *d_ptr, con
                             int64_t n_train_users, int64_t I, int64_t n, uint64_t seed,
                             uint64_t epoch, int64_t *d_users, int64_t *d_pos, int64_t *d_neg,
                             void *stream);
+
+/* n_cand candidate negatives per triplet (dynamic negative sampling; elimrec_pick_hard_negatives picks among them), same contract
+ * and arguments as elimrec_sample_triplets. d_users / d_pos: bit for bit what elimrec_sample_triplets writes for the same
+ * (seed, epoch, i). d_cands int32 [n x n_cand] contiguous: column 0 is bit for bit elimrec_sample_triplets' negative; every column
+ * j > 0 is an independent uniform draw over [0, I) minus the user's training items, by the same rejection loop and fallback, from
+ * the Philox stream whose counter word 3 carries j in its low 24 bits (elimrec_sample_triplets has the epoch's bits 32 .. 55 there:
+ * no (i, epoch < 2^32, round) of it reaches such a counter; csrc/sampler.hip). Drawn with replacement: a triplet may list an id
+ * twice. 1 <= n_cand <= 64, I < 2^31 - 1, n < 2^31. */
+int elimrec_sample_triplet_candidates(const int32_t *d_user_ids, const int64_t *d_ptr, const int32_t *d_items,
+                                      int64_t n_train_users, int64_t I, int64_t n, uint64_t seed, uint64_t epoch, int n_cand,
+                                      int64_t *d_users, int64_t *d_pos, int32_t *d_cands, void *stream);
 
 /* Negatives of sampled-negative evaluation (the reference's data/dataset.py:270-288; util/cython/random_choice.pyx:20-62,
  * replace=False): per user row u, n_neg DISTINCT ids uniform over [0, I) minus the row's exclusion list d_excl_items

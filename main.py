@@ -6,7 +6,7 @@
 Behaviour kept from the reference's `Net.run`: one pass of the pairwise sampler per epoch, validation every
 `test_step` epochs with predict_type TIE, a checkpoint + TE/TIE test pass whenever validation recall improves
 (not on epoch 0), early stop after `stop_cnt` epochs without improvement, the same log lines (`--group_view=[10,30,50,100]` adds
-the per-user-group table under each test line, `--effect_report=K` the effect breakdown of the top-K lists, `--rank_report=1` the test items' exact catalogue ranks, `--neighbour_report=K` the items' cosine neighbourhoods, fused against single-modal, `--list_report=K` the top-K lists' intra-list similarity and catalogue exposure, `--diversify_report=K` the top-N pools re-ranked to K items by greedy MMR per lambda; validation and model selection stay on the overall metrics). The per-batch work,
+the per-user-group table under each test line, `--effect_report=K` the effect breakdown of the top-K lists, `--rank_report=1` the test items' exact catalogue ranks, `--neighbour_report=K` the items' cosine neighbourhoods, fused against single-modal, `--list_report=K` the top-K lists' intra-list similarity and catalogue exposure, `--diversify_report=K` the top-N pools re-ranked to K items by greedy MMR per lambda, `--neg_sampling=hard` trains on the best of `--neg_candidates=M` uniform negatives per triplet under the last forward's tables; validation and model selection stay on the overall metrics). The per-batch work,
 the sampler and the evaluator run on the GPU (elimrec_amd). `--data.input.dataset=synthetic` uses the seeded
 Tiktok-shape generator instead of reading files.
 
@@ -116,6 +116,14 @@ class Net(object):
         self.diversify_report = int(cfg["diversify_report"]) if "diversify_report" in cfg else 0
         if self.diversify_report and self.world > 1:
             raise ValueError("--diversify_report needs the whole cached item table on one rank: it is single-GPU")
+        # --neg_sampling=hard (default uniform): every epoch trains on the best of --neg_candidates=M (8) uniform candidates per
+        # triplet under the tables of the last training forward, scored in --neg_space=fused|loss|<head> (fused); the first epoch
+        # of a run -- no tables yet -- is the uniform one
+        self.neg_sampling = str(cfg["neg_sampling"]) if "neg_sampling" in cfg else "uniform"
+        if self.neg_sampling not in ("uniform", "hard"):
+            raise ValueError("--neg_sampling must be uniform or hard, got %r" % self.neg_sampling)
+        if self.neg_sampling == "hard" and self.world > 1:
+            raise ValueError("--neg_sampling=hard needs the whole cached item table on one rank: it is single-GPU")
         Logger.info(count_parameters(self.recommender))
         self.opt = FusedAdam(self.recommender.parameters(), lr=cfg.lr, weight_decay=cfg.weight_decay)
         self.loss_name = str(cfg.loss)
@@ -283,9 +291,13 @@ class Net(object):
         meters = {"recall": Meter("R@" + k, id=stamp), "precision": Meter("P@" + k, id=stamp), "ndcg": Meter("N@" + k, id=stamp)}
         if cfg.batch_size % self.world != 0:
             raise ValueError("batch_size %d is not a multiple of the %d ranks" % (cfg.batch_size, self.world))
+        hard = {}
+        if self.neg_sampling == "hard":
+            hard = dict(neg_sampling="hard", neg_candidates=cfg["neg_candidates"] if "neg_candidates" in cfg else 8,
+                        neg_space=str(cfg["neg_space"]) if "neg_space" in cfg else "fused", model=rec)
         batches = PairwiseSamplerV2(self.dataset, neg_num=1, batch_size=cfg.batch_size // self.world, shuffle=True,
                                     device=cfg.device, seed=cfg.seed + self.rank,
-                                    shard=(self.rank, self.world) if self.world > 1 else None)
+                                    shard=(self.rank, self.world) if self.world > 1 else None, **hard)
         batches.epoch = self.start_epoch
         best_recall = dict.fromkeys(EFFECTS, 0)
         best_epoch = dict.fromkeys(EFFECTS, 0)
@@ -299,6 +311,12 @@ class Net(object):
             Logger.info("EPOCH[%d/%d]" % (epoch, cfg.num_epoch))
             loss_meter.reset_time()
             epoch_loss = self.train_epoch(batches)
+            if hard:
+                st = batches.last_stats
+                Logger.info("[hard negatives] " + ("best of %d in '%s': %.4f of the triplets moved off the uniform negative, mean score "
+                                                   "%.4f against %.4f" % (batches.neg_candidates, batches.neg_space, st["moved"],
+                                                                          st["score_picked"], st["score_first"])
+                                                   if st["hard"] else "uniform (no tables yet)"))
             if (epoch + 1) % cfg["test_step"] == 0:
                 result = self.validate(epoch, meters)
                 if meters["recall"].val > best_recall["TIE"] and epoch != 0:
