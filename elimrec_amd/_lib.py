@@ -221,6 +221,9 @@ SIGNATURES = {
     "elimrec_mmr_rows_in_lds": (c_i32, [c_i32, c_i32]),
     "elimrec_pick_hard_negatives": (c_i32, [c_ptr, c_i64, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_i64, c_ptr, c_i64, c_i32, c_i32,
                                             ctypes.POINTER(c_f32), c_ptr, c_ptr, c_i64, c_i32, c_ptr, c_ptr, c_ptr, c_ptr]),
+    "elimrec_history_support": (c_i32, [c_ptr, c_i64, c_i64, c_i32, c_i32, c_ptr, c_i64, ctypes.POINTER(c_f32), c_ptr, c_ptr, c_i64,
+                                        c_i32, c_ptr, c_ptr, c_i64, c_i32, c_i32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
+    "elimrec_history_max_top": (c_i32, []),
     "elimrec_slab_partials_bytes": (c_size, [c_sell, c_i32, c_i32]),
     "elimrec_slab_hop": (c_i32, [c_sell, c_i32, c_i32, c_i32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_f32, c_ptr, c_size, c_i32,
                                  c_ptr]),

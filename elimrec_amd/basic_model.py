@@ -8,7 +8,7 @@ from torch import nn
 
 from . import ops
 from .evaluator import ProxyEvaluator
-from .reports import DiversifyReport, EffectReport, ListReport, NeighbourReport, RankReport
+from .reports import DiversifyReport, EffectReport, HistoryReport, ListReport, NeighbourReport, RankReport
 
 
 class BasicModel(nn.Module):
@@ -79,6 +79,15 @@ class BasicModel(nn.Module):
             lambdas = config["diversify_lambda"] if "diversify_lambda" in config else [1.0, 0.9, 0.7, 0.5]
             self.diversify_reporter = DiversifyReport(dataset, train, dataset.get_user_test_dict(), k_div, pool=pool, lambdas=lambdas,
                                                       group_view=config["group_view"])
+        # --history_report=K (CLI-only, default 0 = off): which items of the test users' training histories back their top-K lists
+        # (--history_top=T entries named per pair, default 3): the largest and the mean cosine of the history to each listed item
+        # and the unexpectedness 1 - max, in the fused space and in each head's, overall and per user group (reports.HistoryReport)
+        k_hist = int(config["history_report"]) if "history_report" in config else 0
+        self.history_reporter = None
+        if k_hist:
+            t_hist = config["history_top"] if "history_top" in config else 3
+            self.history_reporter = HistoryReport(dataset, train, dataset.get_user_test_dict(), k_hist, top=t_hist,
+                                                  group_view=config["group_view"])
         self.infonce_criterion = nn.CrossEntropyLoss()          # BasicModel.py:32
 
     def getFileName(self):

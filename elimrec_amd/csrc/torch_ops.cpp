@@ -26,6 +26,10 @@
 //   pick_hard_negatives(user_table f32[U x blocks*d], user_sqnorm f32[U x blocks], item_table f32[I x blocks*d], item_sqnorm, weights
 //     float[blocks], users i64[n], cands i32[n x M]) -> (neg i64, pos i32, score f32) [n]: per triplet the listed candidate with the largest
 //     sum_b w_b cos_b(u, i), the lowest column among equals; -1 / -1 / -inf without one (csrc/hardneg.hip)
+//   history_support(table f32[I x blocks*d], sqnorm f32[I x blocks], weights float[blocks], users i64[B], lists i32[B x K], hist_ptr i64[R + 1],
+//     hist_items i32, top, exclude_self) -> (idx i32 [B x K x top], val f32 [B x K x top], cnt i32 [B x K], mean f32 [B x K]): per target the
+//     `top` entries of its user's history (segment users[b] of the CSR) with the largest sum_b w_b cos_b, the lower position among equals;
+//     -1 / -inf fillers, cnt / mean over the listed entries (csrc/history.hip)
 //   sample_triplets(user_ids, ptr, items, num_items, n, seed, epoch) -> (users, pos, neg)
 //   score_candidates(Y, U, I, users, d, S, head_mask, fusion_mode, predict_type, cand_ptr, cand_items, width) -> f32[B x width]
 //       (each row: its candidates' scores in list order, then -inf)
@@ -496,6 +500,46 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> pick_hard_negatives(const at::Ten
     return {neg, pos, score};
 }
 
+// ---- history support: per (user, target) the closest entries of the user's own history
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> history_support(const at::Tensor &table, const at::Tensor &sqnorm,
+                                                                           at::ArrayRef<double> weights, const at::Tensor &users,
+                                                                           const at::Tensor &lists, const at::Tensor &hist_ptr,
+                                                                           const at::Tensor &hist_items, int64_t top, bool exclude_self) {
+    const at::Tensor t = rowmajor(table, "table");
+    need(sqnorm, "sqnorm", at::kFloat); need(users, "users", at::kLong, 1); need(lists, "lists", at::kInt, 2);
+    need(hist_ptr, "hist_ptr", at::kLong, 1); need(hist_items, "hist_items", at::kInt, 1);
+    const at::Tensor us = users.contiguous(), l = lists.contiguous(), hp = hist_ptr.contiguous(), hi = hist_items.contiguous();
+    const int64_t blocks = (int64_t)weights.size(), B = l.size(0), K = l.size(1), I = t.size(0), R = hp.numel() - 1, n = hi.numel();
+    TORCH_CHECK(blocks >= 1 && blocks <= 8 && t.size(1) % blocks == 0,
+                "elimrec::history_support: 1 <= blocks <= 8 weights, and a table whose width splits into as many blocks");
+    const int64_t d = t.size(1) / blocks;
+    TORCH_CHECK(d % 4 == 0 && d >= 4 && d <= 256, "elimrec::history_support: a block needs d % 4 == 0 and 4 <= d <= 256 columns, got ", d);
+    TORCH_CHECK(K >= 1 && K <= 256 && us.numel() == B, "elimrec::history_support: lists [B x K] with 1 <= K <= 256 and users [B]");
+    TORCH_CHECK(top >= 1 && top <= elimrec_history_max_top(), "elimrec::history_support: 1 <= top <= ", elimrec_history_max_top(), ", got ", top);
+    TORCH_CHECK(sqnorm.numel() == I * blocks && (blocks == 1 || sqnorm.dim() == 2),
+                "elimrec::history_support: sqnorm must be [rows x ", blocks, "]");
+    const at::Tensor sq = (sqnorm.dim() == 1 || sqnorm.stride(1) == 1 || blocks == 1) ? sqnorm : sqnorm.contiguous();
+    TORCH_CHECK(R >= 1, "elimrec::history_support: hist_ptr needs n_rows + 1 >= 2 entries");
+    {   // the segments are validated on the host; the ids' range is the kernel's to check
+        const at::Tensor h = hp.cpu();
+        const int64_t *p = h.data_ptr<int64_t>();
+        bool ok = p[0] == 0 && p[R] == n;
+        for (int64_t r = 0; r < R && ok; ++r) ok = p[r + 1] >= p[r];
+        TORCH_CHECK(ok, "elimrec::history_support: hist_ptr must ascend from 0 to len(hist_items) = ", n);
+    }
+    float w[8];
+    for (int64_t b = 0; b < blocks; ++b) w[b] = (float)weights[b];
+    at::Tensor idx = at::empty({B, K, top}, l.options()), val = at::empty({B, K, top}, t.options());
+    at::Tensor cnt = at::empty({B, K}, l.options()), mean = at::empty({B, K}, t.options());
+    if (B == 0) return {idx, val, cnt, mean};
+    check(elimrec_history_support(t.data_ptr<float>(), t.stride(0), I, (int)blocks, (int)d, sq.data_ptr<float>(),
+                                  std::max<int64_t>(blocks, I > 1 ? sq.stride(0) : blocks), w, us.data_ptr<int64_t>(), l.data_ptr<int32_t>(), B,
+                                  (int)K, hp.data_ptr<int64_t>(), n ? hi.data_ptr<int32_t>() : nullptr, R, (int)top, exclude_self ? 1 : 0,
+                                  idx.data_ptr<int32_t>(), val.data_ptr<float>(), cnt.data_ptr<int32_t>(), mean.data_ptr<float>(), cur_stream()),
+          "history_support");
+    return {idx, val, cnt, mean};
+}
+
 at::Tensor sample_negatives(const at::Tensor &excl_ptr, const at::Tensor &excl_items, int64_t num_items, int64_t n_neg, int64_t seed) {
     need(excl_ptr, "excl_ptr", at::kLong, 1); need(excl_items, "excl_items", at::kInt, 1);
     const at::Tensor p = excl_ptr.contiguous(), it = excl_items.contiguous();
@@ -622,6 +666,8 @@ TORCH_LIBRARY(elimrec, m) {
     m.def("mmr_rerank(Tensor table, Tensor sqnorm, Tensor pool_idx, Tensor pool_val, int K, float lam) -> (Tensor, Tensor, Tensor)");
     m.def("pick_hard_negatives(Tensor user_table, Tensor user_sqnorm, Tensor item_table, Tensor item_sqnorm, float[] weights, Tensor users, "
           "Tensor cands) -> (Tensor, Tensor, Tensor)");
+    m.def("history_support(Tensor table, Tensor sqnorm, float[] weights, Tensor users, Tensor lists, Tensor hist_ptr, Tensor hist_items, int top, "
+          "bool exclude_self) -> (Tensor, Tensor, Tensor, Tensor)");
     m.def("sample_negatives(Tensor excl_ptr, Tensor excl_items, int num_items, int n_neg, int seed) -> Tensor");
     m.def("lookup_counts(Tensor acts, int U, int I, int[] user_bounds, int[] item_bounds) -> Tensor");
     m.def("lookup_pack(Tensor acts, int U, int I, int[] user_bounds, int[] item_bounds, int me, Tensor shard, int row_bytes) -> (Tensor, Tensor)");
@@ -652,6 +698,7 @@ TORCH_LIBRARY_IMPL(elimrec, CUDA, m) {
     m.impl("list_exposure", &list_exposure);
     m.impl("mmr_rerank", &mmr_rerank);
     m.impl("pick_hard_negatives", &pick_hard_negatives);
+    m.impl("history_support", &history_support);
     m.impl("sample_negatives", &sample_negatives);
     m.impl("lookup_counts", &lookup_counts);
     m.impl("lookup_pack", &lookup_pack);

@@ -40,6 +40,7 @@ from .plugin import EmbeddingParameter, LazyGradParameter, StepController
 # EliMRec.explain's result: column names, item ids CPU int32 [B x W] (-1 = padding), values CPU fp32 [B x W x C]
 Effects = collections.namedtuple("Effects", ("columns", "items", "values"))
 Neighbours = collections.namedtuple("Neighbours", ("ids", "scores"))
+HistorySupport = collections.namedtuple("HistorySupport", ("items", "history", "scores", "count", "mean"))
 
 
 def create_adj_mat(train_users, train_items, num_users, num_items, adj_type):
@@ -1507,6 +1508,88 @@ class EliMRec(BasicModel):
         Y = self._ws["Y"]
         ops.pick_hard_negatives(Y[:U, :nb * d], sqn[:U], Y[U:U + I, :nb * d], sqn[U:U + I], w, users, cands, out_neg, out_pos, out_score)
         return out_neg, out_pos, out_score
+
+    @torch.no_grad()
+    def history_support_device(self, users, lists, hist, top=3, space="fused", exclude_self=True, out_idx=None, out_val=None,
+                               out_cnt=None, out_mean=None):
+        """"Because you interacted with what?": per (row b, target lists[b, k]) the entries of a history that sit closest to the
+        target, ONE launch (csrc/history.hip). users int64 [B] / lists int32 [B x K] on the device, 1 <= K <= ops.LIST_MAX_K; hist:
+        an ops.HistoryIndex on the device, users[b] names its segment (for the train dict laid out by user id that is the user id).
+        The score of a history item against the target is the weighted sum of the blocks' cosines between the two item rows of the
+        cached Y; space as hard_negative_weights: "fused", a head letter, or "loss". A target outside the catalogue, or a row whose
+        user is outside the index, is not listed; nor is a history id outside the catalogue or -- with exclude_self -- equal to the
+        target. -> (idx int32 [B x K x top] the history items' ids, best first, the earlier history position among equal scores;
+        val float32 [B x K x top] their scores; cnt int32 [B x K] the listed history entries; mean float32 [B x K] their mean
+        score), -1 / -inf / 0 / NaN where there is nothing; allocated here unless given. 1 - val[..., 0] is the pair's
+        unexpectedness. Tables as similar_items: those of the last training forward, whole on this rank."""
+        w = self.hard_negative_weights(space)
+        self._require_gpu()
+        lo, n = self._side_rows("item")
+        dev = self._cached_tables("history_support_device() / explain_history() need", "history support needs the whole cached item "
+                                  "table on this rank; the tables are item-sharded (lean / multi-rank evaluation)")
+        d, nb = self.latent_dim, 1 + self.S
+        sqn = self._block_sqnorms(dev)
+        B, K = lists.shape
+        top = int(top)
+        if out_idx is None:
+            out_idx = torch.empty(B, K, top, dtype=torch.int32, device=dev)
+        if out_val is None:
+            out_val = torch.empty(B, K, top, dtype=torch.float32, device=dev)
+        if out_cnt is None:
+            out_cnt = torch.empty(B, K, dtype=torch.int32, device=dev)
+        if out_mean is None:
+            out_mean = torch.empty(B, K, dtype=torch.float32, device=dev)
+        ops.history_support(self._ws["Y"][lo:lo + n, :nb * d], sqn[lo:lo + n], w, users, lists, hist, top, out_idx, out_val, out_cnt,
+                            out_mean, exclude_self=exclude_self)
+        return out_idx, out_val, out_cnt, out_mean
+
+    def explain_history(self, user_ids, items=None, top_k=None, top=3, space="fused", history=None, exclude=None):
+        """Which items of each user's history back a recommendation: HistorySupport(items int32 [B x W] (-1 padded), history int32
+        [B x W x top] -- per listed item the `top` history items closest to it, best first, -1 padded --, scores fp32 [B x W x top]
+        (-inf padded), count int32 [B x W] the history entries compared, mean fp32 [B x W] their mean score (NaN without one)) on
+        the CPU. items: one list of item ids per user, of any lengths up to ops.LIST_MAX_K -- those pairs; top_k: each user's top-K
+        list under the current predict type, `exclude` = dict user -> item ids left out of the ranking, as explain() takes it.
+        history: dict user -> item ids (default: the data set's train dict; a user absent from it has an empty history); the
+        listed item itself is never its own support. space as history_support_device; 1 <= top <= ops.HISTORY_MAX_TOP. An id
+        outside the catalogue raises IndexError."""
+        if (items is None) == (top_k is None):
+            raise ValueError("explain_history() takes exactly one of items and top_k")
+        if isinstance(top, bool) or not isinstance(top, (int, np.integer)) or not 1 <= top <= 16:
+            raise ValueError("top must be an integer in [1, 16], got %r" % (top,))
+        self.hard_negative_weights(space)
+        n = len(user_ids)
+        if history is None:
+            history = self.dataset.get_user_train_dict()
+        elif not isinstance(history, dict):
+            raise TypeError("history must be a dict user -> item ids")
+        hptr, hflat, _ = self._id_lists([history.get(int(u), []) for u in user_ids], "history item")
+        if items is not None:
+            if exclude is not None:
+                raise ValueError("exclude applies to top_k lists; items are taken as given")
+            if len(items) != n:
+                raise ValueError("one item list per user: %d lists for %d users" % (len(items), n))
+            K = max([len(x) for x in items] + [1])
+            if K > ops.LIST_MAX_K:
+                raise ValueError("a list may hold at most %d items, got %d" % (ops.LIST_MAX_K, K))
+            _, flat, lens = self._id_lists(items, "item")
+            dev = self._require_gpu()
+            lists = torch.from_numpy(ops.ragged_padded(flat, lens, K)).to(dev)
+        else:
+            top_k = int(top_k)
+            if not 1 <= top_k <= min(ops.LIST_MAX_K, self.num_items):
+                raise ValueError("top_k must lie in [1, min(%d, num_items = %d)], got %d" % (ops.LIST_MAX_K, self.num_items, top_k))
+            tptr, tflat = self._excluded(exclude, user_ids, "item")
+            dev = self._cached_tables("history_support_device() / explain_history() need", "history support needs the whole cached "
+                                      "item table on this rank; the tables are item-sharded (lean / multi-rank evaluation)")
+            if n:
+                lists, _ = self.predict_device(user_ids, top_k=top_k, train_ptr=torch.from_numpy(tptr).to(dev),
+                                               train_items=torch.from_numpy(tflat.astype(np.int32)).to(dev))
+            else:
+                lists = torch.empty(0, top_k, dtype=torch.int32, device=dev)
+        hist = ops.HistoryIndex(hptr if n else np.zeros(2, dtype=np.int64), hflat, dev, n_items=self.num_items)
+        rows = torch.arange(n, dtype=torch.int64, device=dev)                  # row b's history is segment b
+        idx, val, cnt, mean = self.history_support_device(rows, lists, hist, top=int(top), space=space)
+        return HistorySupport(lists.cpu(), idx.cpu(), val.cpu(), cnt.cpu(), mean.cpu())
 
     def recommend_diverse(self, user_ids, k, pool=None, lam=0.7, space="fused", exclude=None):
         """k items per user from the user's top-`pool` list, trading relevance against similarity to what is already picked

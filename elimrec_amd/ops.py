@@ -759,7 +759,7 @@ def _ids_in_range(ids, bound, who, span):
 
 def _checked_csr(ptr, ids, n_lists, bound, who, names):
     """The host checks of a CSR of ids, in this order: entry count of ptr (n_lists + 1; n_lists = None: any number of lists >= 1),
-    integer ids, ptr ascending from 0 to len(ids), every id in [0, bound). names = (ptr's name, ids' name, the letter of the list
+    integer ids, ptr ascending from 0 to len(ids), every id in [0, bound) (bound = None: the ids' range is left to the kernel). names = (ptr's name, ids' name, the letter of the list
     count, the range error's words). -> (ptr int64, ids) as flat host arrays."""
     ptr_name, ids_name, letter, span = names
     p = np.ascontiguousarray(_host(ptr), dtype=np.int64).reshape(-1)
@@ -772,7 +772,8 @@ def _checked_csr(ptr, ids, n_lists, bound, who, names):
     _integer_ids(ids, who, ids_name)
     if p[0] != 0 or p[-1] != ids.size or (np.diff(p) < 0).any():
         raise ValueError("elimrec_amd.ops.%s: %s must ascend from 0 to len(%s) = %d" % (who, ptr_name, ids_name, ids.size))
-    _ids_in_range(ids, bound, who, span)
+    if bound is not None:
+        _ids_in_range(ids, bound, who, span)
     return p, ids
 
 
@@ -931,6 +932,8 @@ def __getattr__(name):
         return int(_lib.load().elimrec_cosine_topk_tile())
     if name == "LIST_SMALL_K":           # lists up to this K take one wave of list_pair_cosine, longer ones four
         return int(_lib.load().elimrec_list_pair_cosine_small_k())
+    if name == "HISTORY_MAX_TOP":        # entries of a history history_support names per target
+        return int(_lib.load().elimrec_history_max_top())
     if name == "MMR_MAX_POOL":           # positions of a pool mmr_rerank takes (one thread each)
         return int(_lib.load().elimrec_mmr_max_pool())
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
@@ -1458,3 +1461,92 @@ def pick_hard_negatives(user_table, user_sqnorm, item_table, item_sqnorm, weight
                                                        (ctypes.c_float * blocks)(*w), usp, cp, n, M, np_, pp, sp, _stream()),
                "pick_hard_negatives")
     return out_neg
+
+
+class HistoryIndex(object):
+    """The users' histories as CSR (ptr [n_rows + 1], items: item ids), CHECKED ON THE HOST -- at least two entries of ptr,
+    ptr[0] = 0, ascending, ptr[n_rows] = len(items), integer ids that fit int32 -- and then resident on `device`: history_support
+    takes it as is, call after call (the counterpart of TargetIndex). n_items = None: the ids' range is left to the kernel, which
+    checks every entry and never dereferences one outside its table; n_items = I: every id must lie in [0, I) (IndexError).
+    Segments may repeat ids, in any order, and may be empty."""
+
+    def __init__(self, ptr, items, device, n_items=None):
+        p, it = _checked_csr(ptr, items, None, n_items, "HistoryIndex",
+                             ("ptr", "items", "n_rows", "item ids span [%d, %d], the catalogue has %d items"))
+        if it.size and (int(it.min()) < -2 ** 31 or int(it.max()) >= 2 ** 31):
+            raise IndexError("elimrec_amd.ops.HistoryIndex: item ids span [%d, %d]: they must fit int32" % (int(it.min()), int(it.max())))
+        self.n_rows, self.n_items, self.n_entries = int(p.size - 1), (None if n_items is None else int(n_items)), int(it.size)
+        self.sizes = np.diff(p)
+        self.ptr = torch.from_numpy(p).to(device)
+        self.items = _resident_ids(it, device)
+
+
+def history_columns(mods):
+    """Column names of the history report: per space (fused, then the heads' modality letters in head order) sup_max_<space> (the
+    largest score of a history entry against the listed item), sup_mean_<space> (the mean over the history) and unexpected_<space>
+    (1 - sup_max_<space>), then hist_n (the number of history entries behind the pair)."""
+    spaces = ("fused",) + tuple(str(m) for m in mods)
+    return (tuple("sup_max_" + s for s in spaces) + tuple("sup_mean_" + s for s in spaces)
+            + tuple("unexpected_" + s for s in spaces) + ("hist_n",))
+
+
+def _flat_out(t, name, dtype, n, who, device):
+    """Device pointer of an output of n entries: `dtype`, contiguous, any shape with at least n entries, on `device`."""
+    if t is None:
+        raise RuntimeError("elimrec_amd.ops: '%s' must be a HIP device tensor (the hot path has no CPU implementation)" % name)
+    p = _dev(t, name, dtype)
+    if not t.is_contiguous() or t.device != device or t.numel() < n:
+        raise ValueError("elimrec_amd.ops.%s: %s must be contiguous on the table's device with at least %d entries" % (who, name, n))
+    return p
+
+
+def history_support(table, sqnorm, weights, users, lists, hist, top, out_idx, out_val, out_cnt=None, out_mean=None, exclude_self=True):
+    """elimrec_history_support: per (row b, target lists[b, k]) the entries of user users[b]'s history that score highest against
+    the target. table [I x blocks * d] float32 with unit column stride (a column slice of a wider matrix is fine), block b = columns
+    [b * d, (b + 1) * d), d % 4 == 0, 4 <= d <= 256; sqnorm [I x blocks] with unit column stride (1-D with any stride when blocks
+    == 1): the rows' squared norms per block; weights: a HOST sequence of 1 <= blocks <= 8 floats, score(j, i) = sum_b weights[b] *
+    cos_b(j, i) over the blocks with a non-zero weight, in block order -- a block with zero weight is not read (pick_hard_negatives'
+    expression). users int64 [B], lists int32 [B x K] contiguous, 1 <= K <= LIST_MAX_K, on the table's device; hist: a HistoryIndex
+    on that device, users[b] names its segment. A target is listed when its id lies in [0, I) and its user in [0, hist.n_rows); an
+    entry when its id lies in [0, I) and, with exclude_self, differs from the target (the kernel checks every id, no host check is
+    needed); a repeated id is an entry of its own. 1 <= top <= HISTORY_MAX_TOP. out_idx int32 / out_val float32 [B x K x top] <- the
+    ids and scores of the `top` listed entries with the largest score, in that order, the lower position in the segment first among
+    equals, -1 / -inf where fewer exist or the target is not listed; out_cnt int32 / out_mean float32 [B x K] (optional) <- the
+    number of listed entries and their mean score (float64 sum in segment order, rounded once), 0 / NaN without one. Outputs:
+    contiguous with at least B * K * top (B * K) entries; entries beyond are left alone. A pair's bits depend on the target's row,
+    the segment in order, d, blocks, weights, top and exclude_self alone (csrc/history.hip)."""
+    w = [float(x) for x in (weights.tolist() if hasattr(weights, "tolist") else weights)]
+    blocks = len(w)
+    if not 1 <= blocks <= LIST_MAX_BLOCKS:
+        raise ValueError("elimrec_amd.ops.history_support: weights needs 1 <= blocks <= %d entries, got %d" % (LIST_MAX_BLOCKS, blocks))
+    if not isinstance(hist, HistoryIndex):
+        raise TypeError("elimrec_amd.ops.history_support: hist must be an ops.HistoryIndex, got %s" % type(hist).__name__)
+    if isinstance(top, bool) or not isinstance(top, (int, np.integer)):
+        raise ValueError("elimrec_amd.ops.history_support: top must be an integer, got %r" % (top,))
+    top = int(top)
+    max_top = int(_lib.load().elimrec_history_max_top())
+    if not 1 <= top <= max_top:
+        raise ValueError("elimrec_amd.ops.history_support: 1 <= top <= %d, got %d" % (max_top, top))
+    tp, ld, I, d, sqp, ld_sq = _block_table(table, sqnorm, blocks, "table", "history_support")
+    lp = _int_lists(lists, "lists", "history_support")
+    B, K = lists.shape
+    if K > LIST_MAX_K:
+        raise ValueError("elimrec_amd.ops.history_support: 1 <= K <= %d, got %d" % (LIST_MAX_K, K))
+    up = _dev(users, "users", torch.int64)
+    dev = table.device
+    if users.dim() != 1 or users.numel() != B or not users.is_contiguous() or users.device != dev or lists.device != dev:
+        raise ValueError("elimrec_amd.ops.history_support: users must be a contiguous [%d] tensor, one per row of lists, both on the "
+                         "table's device" % B)
+    if hist.ptr.device != dev:
+        raise ValueError("elimrec_amd.ops.history_support: the HistoryIndex lives on %s, the table on %s" % (hist.ptr.device, dev))
+    ip = _flat_out(out_idx, "out_idx", torch.int32, B * K * top, "history_support", dev)
+    vp = _flat_out(out_val, "out_val", torch.float32, B * K * top, "history_support", dev)
+    cp = _flat_out(out_cnt, "out_cnt", torch.int32, B * K, "history_support", dev) if out_cnt is not None else None
+    mp = _flat_out(out_mean, "out_mean", torch.float32, B * K, "history_support", dev) if out_mean is not None else None
+    if B == 0:
+        return out_idx
+    _lib.check(_lib.load().elimrec_history_support(tp, ld, I, blocks, d, sqp, ld_sq, (ctypes.c_float * blocks)(*w), up, lp, B, K,
+                                                   _dev(hist.ptr, "hist_ptr", torch.int64), _dev(hist.items, "hist_items", torch.int32),
+                                                   hist.n_rows, top, 1 if exclude_self else 0, ip, vp, cp, mp, _stream()),
+               "history_support")
+    return out_idx

@@ -1,6 +1,6 @@
 """The reports over the cached tables -- what the lists are made of (EffectReport), where the held-out items stand (RankReport),
 whose neighbourhood the fused space copies (NeighbourReport), the lists themselves (ListReport), what diversifying them costs and
-buys (DiversifyReport) -- and what they share: the user /
+buys (DiversifyReport), which items of a user's history back them (HistoryReport) -- and what they share: the user /
 item groups, the groups as a checked index on the device, the group means, the table format, the model preflight and the block-wise
 top-K lists. The rows come from the model's *_device readers (model.py), the means from ops.group_metric_means."""
 import collections
@@ -647,3 +647,92 @@ class DiversifyReport(_Report):
         labels = [label for label in self.group_labels for _ in self.lambdas]
         final = DiversifyTables(DIVERSIFY_COLUMNS, labels, table)
         return final, format_table(final.columns, final.labels, final.table)
+
+
+class HistoryReport(_Report):
+    """Which past items back the lists (--history_report=K): per (test user, rank <= K) pair of the top-K lists under the model's
+    current predict type with the train items masked, the support the user's own training history gives the listed item
+    (EliMRec.history_support_device, csrc/history.hip): per space -- fused, then every head; one launch per space and user block,
+    one-hot weights -- sup_max_<space> = the largest score of a history item against the listed item, sup_mean_<space> = the mean
+    over the history, unexpected_<space> = 1 - sup_max_<space> (the usual unexpectedness / serendipity measure), and hist_n = the
+    number of history items compared; columns ops.history_columns(mods). The table is ops.group_metric_means over the [users*K x C]
+    block: all pairs of the test users with a non-empty training history, then the group_view groups (assign_user_groups) of those
+    users. A pair beyond the end of a list that came out short (-1) has no support: its row is -inf / NaN and so is every mean it
+    enters. Users go in blocks of block_users; only the tables reach the host."""
+
+    name, needs = "history", "history_support_device"
+
+    def __init__(self, dataset, user_train_dict, user_test_dict, top_k, top=3, group_view=None):
+        if not isinstance(user_train_dict, dict) or not isinstance(user_test_dict, dict):
+            raise TypeError("user_train_dict and user_test_dict must be dicts")
+        self.num_items = I = int(dataset.num_items)
+        cap, max_top = min(ops.LIST_MAX_K, I), ops.HISTORY_MAX_TOP
+        if isinstance(top_k, bool) or not isinstance(top_k, (int, np.integer)) or not 1 <= top_k <= cap:
+            raise ValueError("top_k must be an integer in [1, min(%d, the catalogue's %d items)], got %r" % (ops.LIST_MAX_K, I, top_k))
+        if isinstance(top, bool) or not isinstance(top, (int, np.integer)) or not 1 <= top <= max_top:
+            raise ValueError("top must be an integer in [1, %d], got %r" % (max_top, top))
+        self.dataset = dataset
+        self.user_pos_train = user_train_dict
+        self.user_pos_test = user_test_dict
+        self.top_k, self.top = int(top_k), int(top)
+        self.users = list(user_test_dict.keys())
+        self.group_labels, self._positions = self._user_groups(self.users, user_train_dict, group_view)
+        has = np.fromiter((len(user_train_dict.get(u, [])) > 0 for u in self.users), dtype=bool, count=len(self.users))
+        self._positions = [p[has[p]] for p in self._positions]             # the users whose pairs have a history to compare with
+        self.columns = self.shift_columns = None    # ops.history_columns of the model history_rows() last saw; "d_<column>"...
+
+    def _make_resident(self, device):
+        """The groups over the rows of the [users*K x C] block (user position p holds rows p K .. p K + K - 1) and the test users'
+        training histories, segment p = user position p, checked against the catalogue."""
+        K = self.top_k
+        rows = [(p[:, None] * K + np.arange(K, dtype=np.int64)[None, :]).reshape(-1) for p in self._positions]
+        ptr, flat, _ = ops.ragged([self.user_pos_train.get(u, []) for u in self.users], dtype=np.int64, cast=int)
+        if not self.users:
+            ptr = np.zeros(2, dtype=np.int64)
+        return dict(groups=group_index(rows, len(self.users) * K, device), hist=ops.HistoryIndex(ptr, flat, device, n_items=self.num_items))
+
+    def history_rows(self, model):
+        """Every (test user, rank <= K) pair's row on the device: [users*K x C] float32, columns self.columns."""
+        device = self._preflight(model)
+        res = self._resident(device)
+        columns = self.columns = ops.history_columns(model._mods)
+        spaces = ("fused",) + tuple(model._mods)
+        K, nb, n_users = self.top_k, len(spaces), len(self.users)
+        rows = torch.empty(n_users * K, len(columns), dtype=torch.float32, device=device)
+        block = min(self.block_users, max(n_users, 1))
+        idx = torch.empty(block, K, self.top, dtype=torch.int32, device=device)
+        val = torch.empty(block, K, self.top, dtype=torch.float32, device=device)
+        cnt = torch.empty(block, K, dtype=torch.int32, device=device)
+        mean = torch.empty(block, K, dtype=torch.float32, device=device)
+        for a, b, _, lists in self.top_lists(model, self.users, K, self.block_users, self.tie_order):
+            at = torch.arange(a, b, dtype=torch.int64, device=device)
+            out = rows[a * K:b * K]
+            for s, space in enumerate(spaces):
+                model.history_support_device(at, lists, res["hist"], top=self.top, space=space, out_idx=idx, out_val=val, out_cnt=cnt,
+                                             out_mean=mean)
+                best = val[:b - a, :, 0].reshape(-1)
+                out[:, s] = best
+                out[:, nb + s] = mean[:b - a].reshape(-1)
+                out[:, 2 * nb + s] = 1.0 - best
+            out[:, 3 * nb] = cnt[:b - a].reshape(-1).float()
+        return rows
+
+    def _table(self, rows):
+        return group_table(rows, self._resident(rows.device)["groups"], len(self.group_labels))
+
+    def evaluate(self, model, rows=None):
+        """(final [1 + groups x C] float32: row 0 = all pairs with a history, then one row per user group; buf: a header of column
+        names and one "%.8f" line per row, in the grouped evaluator's format). rows: history_rows(model) if the caller holds it."""
+        rows = self.history_rows(model) if rows is None else rows
+        final = self._table(rows)
+        return final, format_table(self.columns, self.group_labels, final)
+
+    def shift(self, rows_a, rows_b):
+        """How the support changes from a to b (e.g. TE -> TIE): (final [1 + groups x C] float32, buf) -- the means of b - a per
+        column, named d_<column> (self.shift_columns), in evaluate()'s grouping. rows_a / rows_b: two history_rows() results."""
+        if self.columns is None or rows_a.shape != rows_b.shape or tuple(rows_a.shape) != (len(self.users) * self.top_k, len(self.columns)) \
+                or rows_a.device != rows_b.device:
+            raise ValueError("shift() takes the rows of two history_rows() results of this report on one device")
+        self.shift_columns = tuple("d_" + c for c in self.columns)
+        final = self._table(rows_b - rows_a)
+        return final, format_table(self.shift_columns, self.group_labels, final)

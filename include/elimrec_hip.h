@@ -698,6 +698,36 @@ int elimrec_pick_hard_negatives(const float *d_U, int64_t ld_u, int64_t n_users,
                                 int blocks, int d, const float *h_weights, const int64_t *d_users, const int32_t *d_cands,
                                 int64_t n, int M, int64_t *d_out_neg, int32_t *d_out_pos, float *d_out_score, void *stream);
 
+/* History support (csrc/history.hip): which entries of a user's own history sit closest to a recommended item. No counterpart in
+ * the reference. d_T / d_sqnorm: an [n_items x blocks * d] column slice of a row-major float32 matrix (row stride ld) and its
+ * [n_items x blocks] squared norms (row stride ld_sq), exactly as elimrec_pick_hard_negatives takes the item side; h_weights:
+ * `blocks` floats ON THE HOST. d_lists int32 [B x K] contiguous: the target items, one row per entry of d_users int64 [B];
+ * d_hist_ptr int64 [n_hist_rows + 1] / d_hist_items int32: the histories as CSR (ptr[0] = 0, ascending), d_users[b] names the
+ * segment of row b.
+ *     score(j, i) = sum over the blocks b with w_b != 0, in block order, of w_b * ((T_b[i] . T_b[j]) * inv(sq[i, b])) * inv(sq[j, b]),
+ *     inv(x) = 1 / max(sqrt(x), 1e-12);   a zero row gives 0, a block with zero weight is not read.
+ * A target (b, k) is listed when 0 <= lists[b, k] < n_items and 0 <= users[b] < n_hist_rows; an entry of the segment is listed
+ * when its id lies in [0, n_items) and, with exclude_self, differs from the target; an unlisted id is never dereferenced, a
+ * repeated id is an entry of its own. d_out_idx int32 / d_out_val float32 [B x K x top]: the ids and scores of the `top` listed
+ * entries with the largest score, in that order, the lower position in the segment first among equal scores; -1 / -inf fill what
+ * is short, and the whole row of an unlisted target. d_out_cnt int32 / d_out_mean float32 [B x K] (either nullable): the number
+ * of listed entries and their mean score (a float64 sum in segment order, rounded once); 0 / NaN for an unlisted target or one
+ * without a listed entry. 1 <= K <= 256, 1 <= top <= elimrec_history_max_top() = 16, d % 4 == 0, 4 <= d <= 256, 1 <= blocks <= 8,
+ * segments of any length < 2^31; B == 0 returns 0 whatever the pointers; rows that are not 16-byte aligned (base or ld % 4 != 0)
+ * are read with scalar loads.
+ * One workgroup per (row b, tile of 16 targets), 16 lanes per target: the segment is walked once per tile in chunks whose rows
+ * are gathered once into LDS (16 KiB) and scored against all 16 targets; the running top lists live in registers. No atomics, no
+ * workspace. A dot product's summation order is fixed by d alone; the four outputs of a (user, target) pair depend bit for bit on
+ * the target's row, the segment's entries in order, d, blocks, the weights, top and exclude_self only -- not on K, the target's
+ * column, B or the grid. One launch on `stream`. */
+int elimrec_history_support(const float *d_T, int64_t ld, int64_t n_items, int blocks, int d,
+                            const float *d_sqnorm, int64_t ld_sq, const float *h_weights,
+                            const int64_t *d_users, const int32_t *d_lists, int64_t B, int K,
+                            const int64_t *d_hist_ptr, const int32_t *d_hist_items, int64_t n_hist_rows,
+                            int top, int exclude_self,
+                            int32_t *d_out_idx, float *d_out_val, int32_t *d_out_cnt, float *d_out_mean, void *stream);
+int elimrec_history_max_top(void);
+
 /* ---------------------------------------------------------------- pairwise sampler (K20)
  * n triplets: user uniform over the `n_train_users` users with >= 1 training item (with
  * replacement), positive uniform over that user's training items, negative uniform over [0,I)

@@ -6,7 +6,7 @@
 Behaviour kept from the reference's `Net.run`: one pass of the pairwise sampler per epoch, validation every
 `test_step` epochs with predict_type TIE, a checkpoint + TE/TIE test pass whenever validation recall improves
 (not on epoch 0), early stop after `stop_cnt` epochs without improvement, the same log lines (`--group_view=[10,30,50,100]` adds
-the per-user-group table under each test line, `--effect_report=K` the effect breakdown of the top-K lists, `--rank_report=1` the test items' exact catalogue ranks, `--neighbour_report=K` the items' cosine neighbourhoods, fused against single-modal, `--list_report=K` the top-K lists' intra-list similarity and catalogue exposure, `--diversify_report=K` the top-N pools re-ranked to K items by greedy MMR per lambda, `--neg_sampling=hard` trains on the best of `--neg_candidates=M` uniform negatives per triplet under the last forward's tables; validation and model selection stay on the overall metrics). The per-batch work,
+the per-user-group table under each test line, `--effect_report=K` the effect breakdown of the top-K lists, `--rank_report=1` the test items' exact catalogue ranks, `--neighbour_report=K` the items' cosine neighbourhoods, fused against single-modal, `--list_report=K` the top-K lists' intra-list similarity and catalogue exposure, `--diversify_report=K` the top-N pools re-ranked to K items by greedy MMR per lambda, `--history_report=K` which items of the users' training histories back the top-K lists (`--history_top=T` named per pair), `--neg_sampling=hard` trains on the best of `--neg_candidates=M` uniform negatives per triplet under the last forward's tables; validation and model selection stay on the overall metrics). The per-batch work,
 the sampler and the evaluator run on the GPU (elimrec_amd). `--data.input.dataset=synthetic` uses the seeded
 Tiktok-shape generator instead of reading files.
 
@@ -124,6 +124,11 @@ class Net(object):
             raise ValueError("--neg_sampling must be uniform or hard, got %r" % self.neg_sampling)
         if self.neg_sampling == "hard" and self.world > 1:
             raise ValueError("--neg_sampling=hard needs the whole cached item table on one rank: it is single-GPU")
+        # --history_report=K (default 0: off): under each [TEST] line the support the users' own training histories give their top-K
+        # lists -- largest / mean cosine to the history and the unexpectedness 1 - max, per space -- and the TE -> TIE shift after both
+        self.history_report = int(cfg["history_report"]) if "history_report" in cfg else 0
+        if self.history_report and self.world > 1:
+            raise ValueError("--history_report needs the whole cached item table on one rank: it is single-GPU")
         Logger.info(count_parameters(self.recommender))
         self.opt = FusedAdam(self.recommender.parameters(), lr=cfg.lr, weight_decay=cfg.weight_decay)
         self.loss_name = str(cfg.loss)
@@ -248,7 +253,7 @@ class Net(object):
 
     def test_all_effects(self):
         """TE and TIE metrics on the test split, formatted as the reference prints them."""
-        rec, lines, ranks, shown = self.recommender, {}, {}, {}
+        rec, lines, ranks, shown, backed = self.recommender, {}, {}, {}, {}
         if self.grouped:
             Logger.info(rec.test_evaluator.metrics_info())
         for effect in EFFECTS:
@@ -272,11 +277,17 @@ class Net(object):
                 reporter = rec.diversify_reporter
                 Logger.info("  [{}] top-{} of the top-{} pools by MMR, per lambda:\n{}".format(
                     effect, reporter.top_k, reporter.pool, reporter.evaluate(rec)[1]))
+            if self.history_report:        # how close the users' training histories sit to the lists under this effect, per space
+                backed[effect] = rec.history_reporter.history_rows(rec)
+                Logger.info("  [{}] support of the top-{} lists in the users' histories:\n{}".format(
+                    effect, self.history_report, rec.history_reporter.evaluate(rec, backed[effect])[1]))
         if self.rank_report:               # positive delta: TIE ranks the test item higher than TE does
             Logger.info("  [TE->TIE] rank shift of the test items:\n{}".format(rec.rank_reporter.shift(ranks["TE"], ranks["TIE"])[1]))
         if self.list_report:               # overlap: the share of the TE list that TIE keeps; d_<column>: TIE - TE
             a, b = shown["TE"], shown["TIE"]
             Logger.info("  [TE->TIE] list shift:\n{}".format(rec.list_reporter.shift(a[0], a[2], b[0], b[2])[1]))
+        if self.history_report:            # d_<column>: TIE - TE; a positive d_unexpected_<space>: TIE strays further from the history
+            Logger.info("  [TE->TIE] history support shift:\n{}".format(rec.history_reporter.shift(backed["TE"], backed["TIE"])[1]))
         if self.neighbour_report:
             Logger.info("  [neighbours] top-{} cosine neighbours of every item, fused space against the heads:\n{}".format(
                 self.neighbour_report, rec.neighbour_reporter.evaluate(rec)[1]))
