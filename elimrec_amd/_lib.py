@@ -249,6 +249,10 @@ SIGNATURES = {
     "elimrec_slab_hop_adam": (c_i32, [c_sell, c_i32, c_i32, c_i32, c_ptr, c_ptr, c_ptr, c_ptr, c_f32, c_ptr, c_size, c_ptr, c_ptr,
                                       c_ptr, c_ptr, c_f32, c_f32, c_f32, c_f32, c_f32, c_i64, ctypes.POINTER(AdamJob), c_i32, c_ptr, c_i64,
                                       c_ptr, c_ptr]),
+    "elimrec_slab_hop_adam_wgrad": (c_i32, [c_sell, c_i32, c_i32, c_i32, c_ptr, c_ptr, c_ptr, c_ptr, c_f32, c_ptr, c_size, c_ptr, c_ptr,
+                                            c_ptr, c_ptr, c_f32, c_f32, c_f32, c_f32, c_f32, c_i64, ctypes.POINTER(AdamJob), c_i32, c_ptr,
+                                            c_i64, c_ptr, ctypes.POINTER(LinearBwdDesc), c_i32, c_ptr, c_size, c_ptr]),
+    "elimrec_slab_hop_adam_wgrad_jobs": (c_i32, [ctypes.POINTER(AdamJob), c_i32, ctypes.POINTER(LinearBwdDesc), c_i32]),
     "elimrec_slab_rows": (c_i32, [c_sell, c_i32, c_i32, c_i32, c_i64, ctypes.POINTER(c_ptr), c_ptr, c_ptr, c_ptr, c_i64, c_i32,
                                   c_ptr, c_i64, c_ptr, c_i64, c_i32, c_ptr]),
     "elimrec_slab_from_rows": (c_i32, [c_ptr, c_i64, c_i64, c_i64, c_i32, c_i32, c_ptr, c_ptr]),
@@ -353,7 +357,7 @@ class _Recording(object):
             fn = getattr(lib, name)
             plain = name in ("elimrec_abi_version", "elimrec_program_fn_count", "elimrec_program_fn_args", "elimrec_comm_unique_id",
                              "elimrec_score_get_math", "elimrec_score_get_bf16x3", "elimrec_group_metric_means_chunk",
-                             "elimrec_rank_segment", "elimrec_rank_targets_per_pass",
+                             "elimrec_rank_segment", "elimrec_rank_targets_per_pass", "elimrec_slab_hop_adam_wgrad_jobs",
                              "elimrec_cosine_topk_chunk", "elimrec_cosine_topk_tile",
                              "elimrec_list_max_k", "elimrec_list_pair_cosine_small_k", "elimrec_list_pair_cosine_chunk_cols",
                              "elimrec_mmr_max_pool", "elimrec_mmr_rows_in_lds",

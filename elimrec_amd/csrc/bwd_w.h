@@ -147,6 +147,19 @@ __device__ __forceinline__ void bwd_w_partial_body(const BwdBatch &batch, int bl
     if (colsum_slabs && tile_z == 0 && tid < TN1) colsum_slabs[(size_t)chunk * n1_pad + i_base + tid] = csum;
 }
 
+// lane q of an output element's four: chunks q, q+4, q+8, ... in that order, four loads in flight
+__device__ __forceinline__ float slab_lane_sum(const float *src, size_t stride, int chunks, int q) {
+    float s = 0.f;
+    int c = q;
+    for (; c + 12 < chunks; c += 16) {
+        const float v0 = src[(size_t)c * stride], v1 = src[(size_t)(c + 4) * stride];
+        const float v2 = src[(size_t)(c + 8) * stride], v3 = src[(size_t)(c + 12) * stride];
+        s += v0; s += v1; s += v2; s += v3;
+    }
+    for (; c < chunks; c += 4) s += src[(size_t)c * stride];
+    return s;
+}
+
 // out[e] (+)= sum over chunks of slab[chunk][e] in a FIXED order: four adjacent lanes share one output
 // element, lane q adds chunks q, q+4, q+8, ... (4 loads in flight each), then (q0+q1)+(q2+q3).
 // by selects the problem; 256 threads per workgroup.
@@ -173,19 +186,77 @@ __device__ __forceinline__ void reduce_slabs_body(const BwdBatch &batch, int bx,
         stride = (size_t)n1_pad;
         dst = pb.d.d_colsum + (idx - total);
     }
-    float s = 0.f;
-    if (src) {
-        int c = q;
-        for (; c + 12 < chunks; c += 16) {
-            const float v0 = src[(size_t)c * stride], v1 = src[(size_t)(c + 4) * stride];
-            const float v2 = src[(size_t)(c + 8) * stride], v3 = src[(size_t)(c + 12) * stride];
-            s += v0; s += v1; s += v2; s += v3;
-        }
-        for (; c < chunks; c += 4) s += src[(size_t)c * stride];
-    }
+    float s = src ? slab_lane_sum(src, stride, chunks, q) : 0.f;
     s += __shfl_xor(s, 1, 64);       // (q0+q1), (q2+q3)
     s += __shfl_xor(s, 2, 64);       // sum of the two pairs
     if (src && q == 0) *dst = pb.d.accumulate ? (*dst + s) : s;
+}
+
+
+// The slab reduce with the optimizer behind it (the last adjoint hop's launch, slab.hip: sell_tier_adam_fold_kernel): what the
+// projection weights' optimizer spans need of a problem. The thread group that owns an output element forms the gradient as
+// reduce_slabs_body does, stores it, and applies Adam to the element at once -- the reduced gradient is not read back by a later
+// launch. A span's pointers are those of the element the problem's output element 0 updates; p_in == nullptr: store only.
+struct FoldSpan {
+    const float *p_in;
+    float *p_out, *m, *v, *copy_dst;       // copy_dst nullable: the pre-update parameters (the weight snapshot)
+    float step_size, inv_sqrt_bc2;
+};
+struct FoldProblem {
+    const float *slabs, *cslabs;           // cslabs == nullptr: no column sum
+    const int32_t *range;
+    float *out, *colsum;
+    int64_t R, ldo;
+    int chunk_rows, n1, n2, n1_pad, n2_pad, accumulate;
+    FoldSpan w, b;                         // out's / colsum's elements
+};
+struct FoldBatch { FoldProblem p[kMaxBatch]; int n, gx; };
+
+__device__ __forceinline__ void reduce_adam_body(const FoldBatch &batch, int bx, int by, float beta1, float beta2, float eps, float wd) {
+    const FoldProblem &pb = batch.p[by];
+    const int gid = bx * 256 + (int)threadIdx.x;
+    const int idx = gid >> 2, q = gid & 3;
+    const int total = pb.n1 * pb.n2;
+    int64_t rows = pb.range ? (int64_t)pb.range[1] - pb.range[0] : pb.R;
+    if (rows < 0) rows = 0;
+    const int chunks = (int)((rows + pb.chunk_rows - 1) / pb.chunk_rows);
+    // (the span's fields are picked by value: a pointer into the by-value argument block would put the whole block into scratch)
+    const bool is_w = idx < total, is_b = !is_w && pb.cslabs && idx < total + pb.n1;
+    const float *src = nullptr;
+    size_t stride = 0;
+    int64_t at = 0;
+    if (is_w) {
+        const int i = idx / pb.n2, j = idx - i * pb.n2;
+        src = pb.slabs + (size_t)i * pb.n2_pad + j;
+        stride = (size_t)pb.n1_pad * pb.n2_pad;
+        at = (int64_t)i * pb.ldo + j;
+    } else if (is_b) {
+        src = pb.cslabs + (idx - total);
+        stride = (size_t)pb.n1_pad;
+        at = idx - total;
+    }
+    float s = src ? slab_lane_sum(src, stride, chunks, q) : 0.f;
+    s += __shfl_xor(s, 1, 64);       // (q0+q1), (q2+q3)
+    s += __shfl_xor(s, 2, 64);       // sum of the two pairs
+    if (!src || q != 0) return;
+    float *dst = (is_w ? pb.out : pb.colsum) + at;
+    const float g = pb.accumulate ? (*dst + s) : s;
+    *dst = g;
+    const float *p_in = is_w ? pb.w.p_in : pb.b.p_in;
+    if (!p_in) return;
+    float *p_out = is_w ? pb.w.p_out : pb.b.p_out, *m = is_w ? pb.w.m : pb.b.m, *v = is_w ? pb.w.v : pb.b.v;
+    float *copy_dst = is_w ? pb.w.copy_dst : pb.b.copy_dst;
+    const float step_size = is_w ? pb.w.step_size : pb.b.step_size, inv_sqrt_bc2 = is_w ? pb.w.inv_sqrt_bc2 : pb.b.inv_sqrt_bc2;
+    const float pi = p_in[at];                              // arithmetic of adam_jobs_body (slab.hip), element for element
+    if (copy_dst) copy_dst[at] = pi;
+    const float gi = fmaf(wd, pi, g);
+    const float mo = m[at];
+    const float mi = mo + (1.f - beta1) * (gi - mo);
+    const float vi = fmaf(1.f - beta2, gi * gi, beta2 * v[at]);
+    const float denom = sqrtf(vi) * inv_sqrt_bc2 + eps;
+    m[at] = mi;
+    v[at] = vi;
+    p_out[at] = pi - step_size * (mi / denom);
 }
 
 

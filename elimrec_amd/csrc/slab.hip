@@ -759,6 +759,27 @@ __global__ __launch_bounds__(256) void sell_tier_adam_kernel(TierArgs t, AdamJob
     tier_body<LPR, 4, false, false, false, true, true>(t, scratch);
 }
 
+// ... and with the weight gradients' slab reduce folded into the projection weights' spans (bwd_w.h: reduce_adam_body): those
+// workgroups come FIRST (`front` of them, a multiple of 8) -- each is a short chain of dependent loads that needs nothing of this
+// hop, begun at once it ends under the tiles --, the spans no problem writes, the weight snapshot's copy-only spans and the loss sum
+// stay behind the tiles. A kernel of its own: the launch without a fold keeps its argument block.
+template <int LPR>
+__global__ __launch_bounds__(256) void sell_tier_adam_fold_kernel(TierArgs t, AdamJobs tail, int tail_block0, FoldBatch fold, int front) {
+    __shared__ float scratch[4 * 64 * 8];
+    if ((int)blockIdx.x < front) {
+        const int b = (int)blockIdx.x;
+        if (b < fold.gx * fold.n) reduce_adam_body(fold, b % fold.gx, b / fold.gx, t.s.ad_beta1, t.s.ad_beta2, t.s.ad_eps, t.s.ad_wd);
+        return;
+    }
+    if ((int)blockIdx.x >= tail_block0) {
+        const int b = (int)blockIdx.x - tail_block0;
+        if (b < tail.blocks) adam_jobs_body(tail, b, t.s.ad_beta1, t.s.ad_beta2, t.s.ad_eps, t.s.ad_wd);
+        else fixed_order_sum_body(tail.sum_src, tail.sum_n, tail.sum_dst, scratch);
+        return;
+    }
+    tier_body<LPR, 4, false, false, false, true, true>(t, scratch, (unsigned)front);
+}
+
 // An adjoint hop with a phase of the projections' weight gradients (bwd_w.h) as extra workgroups behind the tiles: the
 // partial launch (tail_mode 2; it needs the head backward's rows, as the adjoint's first hop does) or the fixed-order slab
 // reduce (tail_mode 1; needs the partial launch, is needed by the optimizer only). Neither reads what the hop writes.
@@ -811,6 +832,7 @@ struct AdamEpilogue {
     float step_size, inv_sqrt_bc2, beta1, beta2, eps, wd;
     int keep_grad;
     const AdamJobs *tail;          // nullable
+    const FoldBatch *fold;         // nullable: the weight gradients' slab reduce + their spans' Adam, ahead of the tiles
 };
 
 static int launch_tier(const elimrec_sell *A, int ns, int wl, int wl_shift, int gs, int spg, int lpr, const void *Xin,
@@ -866,7 +888,11 @@ static int launch_tier(const elimrec_sell *A, int ns, int wl, int wl_shift, int 
     AdamJobs tail = {};
     if (adam && adam->tail && (adam->tail->n > 0 || adam->tail->sum_src)) tail = *adam->tail;
     if (tail.n <= 0) tail.blocks = 0;
-    const dim3 grid((unsigned)(per_group * gs)), grid_adam((unsigned)(per_group * gs) + (unsigned)tail.blocks + (tail.sum_src ? 1u : 0u));
+    const FoldBatch *fold = (adam && adam->fold && adam->fold->n > 0) ? adam->fold : nullptr;
+    const int fold_front = fold ? (fold->gx * fold->n + 7) & ~7 : 0;
+    if (fold) tail_block0 += fold_front;
+    const dim3 grid((unsigned)(per_group * gs)),
+        grid_adam((unsigned)fold_front + (unsigned)(per_group * gs) + (unsigned)tail.blocks + (tail.sum_src ? 1u : 0u));
     const bool masked = src_mask != nullptr;
     if (masked) {
         ELIMREC_REQUIRE(A->tile_kmax > 0, "slab_hop: bad tile plan (tile_kmax)");
@@ -879,7 +905,10 @@ static int launch_tier(const elimrec_sell *A, int ns, int wl, int wl_shift, int 
     }
 #define ELIMREC_TIER(LPR)                                                                                                     \
     do {                                                                                                                      \
-        if (adam) hipLaunchKernelGGL((sell_tier_adam_kernel<LPR>), grid_adam, dim3(256), 0, s, t, tail, tail_block0);         \
+        if (fold)                                                                                                             \
+            hipLaunchKernelGGL((sell_tier_adam_fold_kernel<LPR>), grid_adam, dim3(256), 0, s, t, tail, tail_block0, *fold,    \
+                               fold_front);                                                                                   \
+        else if (adam) hipLaunchKernelGGL((sell_tier_adam_kernel<LPR>), grid_adam, dim3(256), 0, s, t, tail, tail_block0);    \
         else if (bwdw && masked)                                                                                              \
             hipLaunchKernelGGL((sell_tier_bwdw_kernel<LPR, true>), dim3(grid.x + (unsigned)tail_blocks), dim3(256), 0, s, t,  \
                                *bwdw, tail_block0, tail_mode, reduce_gx);                                                     \
@@ -1053,22 +1082,94 @@ extern "C" int elimrec_slab_hop_bwd_w(const elimrec_sell *A, int ns, int w, int 
                        d_partials, flags, (hipStream_t)stream, nullptr, &batch, phase == 0 ? 2 : 1, phase == 0 ? blocks : gx * n, gx);
 }
 
-extern "C" int elimrec_slab_hop_adam(const elimrec_sell *A, int ns, int w, int gs, const float *d_Xin, float *d_grad_out,
-                                     const float *d_add, const uint32_t *d_add_mask, float scale, float *d_partials,
-                                     size_t partials_bytes, const float *d_p_in, float *d_p_out, float *d_m, float *d_v, float lr,
-                                     float beta1, float beta2, float eps, float weight_decay, int64_t step,
-                                     const elimrec_adam_job *tail_jobs, int n_tail_jobs, const float *d_sum_src, int64_t sum_n,
-                                     float *d_sum_dst, void *stream) {
-    ELIMREC_REQUIRE(A && d_Xin && d_p_in && d_p_out && d_m && d_v, "slab_hop_adam: null pointer");
-    ELIMREC_REQUIRE(!d_sum_src || (d_sum_dst && sum_n >= 0 && sum_n < INT32_MAX), "slab_hop_adam: the sum needs a destination");
-    ELIMREC_REQUIRE(A->tiered, "slab_hop_adam: needs a tiered (wave-tile) plan");
-    ELIMREC_REQUIRE(step >= 1, "slab_hop_adam: 1-based step");
+// The fold of the weight gradients' slab reduce into the optimizer spans, host side. An output of a problem (out: n1 * n2
+// contiguous elements, colsum: n1) that lies inside the gradient range of ONE updating job is bound to it: reduce_adam_body updates
+// those elements, and the job keeps only what no problem writes (the pieces in between, as jobs of their own). An output outside
+// every job is reduced and stored only. Returns the number of jobs left, or -1 where the fold does not apply: a strided output, an
+// output that straddles a job's end, two outputs that overlap, more than 8 jobs left.
+struct FoldBind { int job; int64_t off, len; };
+static int fold_split(const elimrec_adam_job *jobs, int n_jobs, const elimrec_linear_bwd_desc *descs, int n, elimrec_adam_job *left,
+                      FoldBind (*binds)[2]) {
+    if (!descs || n < 1 || n > kMaxBatch || n_jobs < 0 || n_jobs > 8 || (n_jobs > 0 && !jobs)) return -1;
+    struct Piece { int64_t off, len; };
+    Piece cover[8][2 * kMaxBatch];
+    int n_cover[8] = {0};
+    const float *seen_lo[2 * kMaxBatch], *seen_hi[2 * kMaxBatch];
+    int n_seen = 0;
+    for (int i = 0; i < n; ++i) {
+        const elimrec_linear_bwd_desc &d = descs[i];
+        if (!d.d_out || d.n1 <= 0 || d.n2 <= 0 || d.ldo != d.n2) return -1;
+        for (int h = 0; h < 2; ++h) {
+            FoldBind &b = binds[i][h];
+            b.job = -1; b.off = 0; b.len = 0;
+            const float *lo = h == 0 ? d.d_out : d.d_colsum;
+            if (!lo) continue;
+            const float *hi = lo + (h == 0 ? (int64_t)d.n1 * d.n2 : (int64_t)d.n1);
+            for (int k = 0; k < n_seen; ++k)
+                if (lo < seen_hi[k] && seen_lo[k] < hi) return -1;
+            seen_lo[n_seen] = lo; seen_hi[n_seen] = hi; ++n_seen;
+            for (int k = 0; k < n_jobs; ++k) {
+                const elimrec_adam_job &j = jobs[k];
+                if (j.n <= 0 || !j.d_g) continue;
+                if (hi <= j.d_g || j.d_g + j.n <= lo) continue;
+                if (lo < j.d_g || j.d_g + j.n < hi) return -1;
+                b.job = k; b.off = lo - j.d_g; b.len = hi - lo;
+                cover[k][n_cover[k]++] = Piece{b.off, b.len};
+                break;
+            }
+        }
+    }
+    int n_left = 0;
+    for (int k = 0; k < n_jobs; ++k) {
+        const elimrec_adam_job &j = jobs[k];
+        if (j.n <= 0) continue;
+        if (n_cover[k] == 0) {
+            if (n_left == 8) return -1;
+            left[n_left++] = j;
+            continue;
+        }
+        for (int a = 1; a < n_cover[k]; ++a)               // by offset (they do not overlap)
+            for (int b = a; b > 0 && cover[k][b].off < cover[k][b - 1].off; --b) { const Piece t = cover[k][b]; cover[k][b] = cover[k][b - 1]; cover[k][b - 1] = t; }
+        int64_t at = 0;
+        for (int a = 0; a <= n_cover[k]; ++a) {
+            const int64_t end = a < n_cover[k] ? cover[k][a].off : j.n;
+            if (end > at) {
+                if (n_left == 8) return -1;
+                elimrec_adam_job g = j;
+                g.d_p_in = j.d_p_in + at; g.d_p_out = j.d_p_out + at; g.d_g = j.d_g + at; g.d_m = j.d_m + at; g.d_v = j.d_v + at;
+                g.d_copy_dst = j.d_copy_dst ? j.d_copy_dst + at : nullptr;
+                g.n = end - at;
+                left[n_left++] = g;
+            }
+            if (a < n_cover[k]) at = cover[k][a].off + cover[k][a].len;
+        }
+    }
+    return n_left;
+}
+
+extern "C" int elimrec_slab_hop_adam_wgrad_jobs(const elimrec_adam_job *tail_jobs, int n_tail_jobs, const elimrec_linear_bwd_desc *descs,
+                                                int n) {
+    elimrec_adam_job left[8];
+    FoldBind binds[kMaxBatch][2];
+    return fold_split(tail_jobs, n_tail_jobs, descs, n, left, binds);
+}
+
+static int slab_hop_adam(const char *who, const elimrec_sell *A, int ns, int w, int gs, const float *d_Xin, float *d_grad_out,
+                         const float *d_add, const uint32_t *d_add_mask, float scale, float *d_partials, size_t partials_bytes,
+                         const float *d_p_in, float *d_p_out, float *d_m, float *d_v, float lr, float beta1, float beta2, float eps,
+                         float weight_decay, int64_t step, const elimrec_adam_job *tail_jobs, int n_tail_jobs, const float *d_sum_src,
+                         int64_t sum_n, float *d_sum_dst, const elimrec_linear_bwd_desc *descs, int n, void *d_workspace,
+                         size_t workspace_bytes, void *stream) {
+    ELIMREC_REQUIRE(A && d_Xin && d_p_in && d_p_out && d_m && d_v, "%s: null pointer", who);
+    ELIMREC_REQUIRE(!d_sum_src || (d_sum_dst && sum_n >= 0 && sum_n < INT32_MAX), "%s: the sum needs a destination", who);
+    ELIMREC_REQUIRE(A->tiered, "%s: needs a tiered (wave-tile) plan", who);
+    ELIMREC_REQUIRE(step >= 1, "%s: 1-based step", who);
     ELIMREC_REQUIRE((const void *)d_Xin != (const void *)d_p_out && (const void *)d_Xin != (const void *)d_m &&
-                        (const void *)d_Xin != (const void *)d_v, "slab_hop_adam: the gathered table must not be written");
+                        (const void *)d_Xin != (const void *)d_v, "%s: the gathered table must not be written", who);
     int w4_shift, spg, lpr, rc;
-    if ((rc = slab_geometry("slab_hop_adam", ns, w, gs, w4_shift, spg, lpr))) return rc;
+    if ((rc = slab_geometry(who, ns, w, gs, w4_shift, spg, lpr))) return rc;
     if (!d_partials || partials_bytes < elimrec_slab_partials_bytes(A, ns, w)) {
-        set_error("slab_hop_adam: partial-row scratch too small");
+        set_error("%s: partial-row scratch too small", who);
         return ELIMREC_E_WORKSPACE;
     }
     AdamEpilogue ad;
@@ -1078,15 +1179,82 @@ extern "C" int elimrec_slab_hop_adam(const elimrec_sell *A, int ns, int w, int g
     ad.inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
     ad.beta1 = beta1; ad.beta2 = beta2; ad.eps = eps; ad.wd = weight_decay; ad.keep_grad = d_grad_out ? 1 : 0;
     AdamJobs tail = {};
+    FoldBatch fold = {};
     ad.tail = nullptr;
+    ad.fold = nullptr;
+    elimrec_adam_job left[8];
+    if (descs) {
+        ELIMREC_REQUIRE(n >= 1 && n <= kMaxBatch, "%s: 1..%d weight-gradient problems", who, kMaxBatch);
+        ELIMREC_REQUIRE(n_tail_jobs >= 0 && n_tail_jobs <= 8, "%s: at most 8 tail jobs", who);
+        ELIMREC_REQUIRE(d_workspace && workspace_bytes >= bwd_w_batched_bytes(descs, n), "%s: weight-gradient workspace", who);
+        FoldBind binds[kMaxBatch][2];
+        const int n_left = fold_split(tail_jobs, n_tail_jobs, descs, n, left, binds);
+        if (n_left < 0) {
+            set_error("%s: the weight gradients do not fold into these optimizer spans (elimrec_slab_hop_adam_wgrad_jobs)", who);
+            return ELIMREC_E_BADARG;
+        }
+        BwdBatch batch;
+        int blocks = 0, max_out = 0;
+        if ((rc = bwd_w_build_batch(descs, n, d_workspace, batch, blocks, max_out))) return rc;
+        fold.n = n;
+        fold.gx = (4 * max_out + 255) / 256;
+        for (int i = 0; i < n; ++i) {
+            const BwdProblem &pb = batch.p[i];
+            FoldProblem &f = fold.p[i];
+            f.slabs = pb.slabs; f.cslabs = pb.d.d_colsum ? pb.cslabs : nullptr; f.range = pb.d.d_range;
+            f.out = pb.d.d_out; f.colsum = pb.d.d_colsum; f.R = pb.d.R; f.ldo = pb.d.ldo;
+            f.chunk_rows = pb.chunk_rows; f.n1 = pb.d.n1; f.n2 = pb.d.n2; f.n1_pad = pb.t1 * TN1; f.n2_pad = pb.t2 * TN2;
+            f.accumulate = pb.d.accumulate;
+            for (int h = 0; h < 2; ++h) {
+                FoldSpan &sp = h == 0 ? f.w : f.b;
+                sp = FoldSpan{};
+                const FoldBind &b = binds[i][h];
+                if (b.job < 0) continue;
+                const elimrec_adam_job &j = tail_jobs[b.job];
+                ELIMREC_REQUIRE(j.d_p_in && j.d_p_out && j.d_m && j.d_v && j.step >= 1, "%s: job %d: an update needs p_out, m, v and a 1-based step",
+                                who, b.job);
+                sp.p_in = j.d_p_in + b.off; sp.p_out = j.d_p_out + b.off; sp.m = j.d_m + b.off; sp.v = j.d_v + b.off;
+                sp.copy_dst = j.d_copy_dst ? j.d_copy_dst + b.off : nullptr;
+                sp.step_size = (float)((double)lr / (1.0 - pow((double)beta1, (double)j.step)));
+                sp.inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow((double)beta2, (double)j.step)));
+            }
+        }
+        ad.fold = &fold;
+        tail_jobs = left;
+        n_tail_jobs = n_left;
+    }
     if (tail_jobs && n_tail_jobs > 0) {
-        ELIMREC_REQUIRE(n_tail_jobs <= 8, "slab_hop_adam: at most 8 tail jobs");
-        if ((rc = build_adam_jobs("slab_hop_adam", tail_jobs, n_tail_jobs, lr, beta1, beta2, tail))) return rc;
+        ELIMREC_REQUIRE(n_tail_jobs <= 8, "%s: at most 8 tail jobs", who);
+        if ((rc = build_adam_jobs(who, tail_jobs, n_tail_jobs, lr, beta1, beta2, tail))) return rc;
         ad.tail = &tail;
     }
     if (d_sum_src) { tail.sum_src = d_sum_src; tail.sum_dst = d_sum_dst; tail.sum_n = (int)sum_n; ad.tail = &tail; }
     return launch_tier(A, ns, w / 4, w4_shift, gs, spg, lpr, d_Xin, nullptr, d_grad_out, d_add, d_add_mask, scale,
                        d_partials, 0, (hipStream_t)stream, &ad);
+}
+
+extern "C" int elimrec_slab_hop_adam(const elimrec_sell *A, int ns, int w, int gs, const float *d_Xin, float *d_grad_out,
+                                     const float *d_add, const uint32_t *d_add_mask, float scale, float *d_partials,
+                                     size_t partials_bytes, const float *d_p_in, float *d_p_out, float *d_m, float *d_v, float lr,
+                                     float beta1, float beta2, float eps, float weight_decay, int64_t step,
+                                     const elimrec_adam_job *tail_jobs, int n_tail_jobs, const float *d_sum_src, int64_t sum_n,
+                                     float *d_sum_dst, void *stream) {
+    return slab_hop_adam("slab_hop_adam", A, ns, w, gs, d_Xin, d_grad_out, d_add, d_add_mask, scale, d_partials, partials_bytes, d_p_in,
+                         d_p_out, d_m, d_v, lr, beta1, beta2, eps, weight_decay, step, tail_jobs, n_tail_jobs, d_sum_src, sum_n, d_sum_dst,
+                         nullptr, 0, nullptr, 0, stream);
+}
+
+extern "C" int elimrec_slab_hop_adam_wgrad(const elimrec_sell *A, int ns, int w, int gs, const float *d_Xin, float *d_grad_out,
+                                           const float *d_add, const uint32_t *d_add_mask, float scale, float *d_partials,
+                                           size_t partials_bytes, const float *d_p_in, float *d_p_out, float *d_m, float *d_v, float lr,
+                                           float beta1, float beta2, float eps, float weight_decay, int64_t step,
+                                           const elimrec_adam_job *tail_jobs, int n_tail_jobs, const float *d_sum_src, int64_t sum_n,
+                                           float *d_sum_dst, const elimrec_linear_bwd_desc *descs, int n, void *d_workspace,
+                                           size_t workspace_bytes, void *stream) {
+    ELIMREC_REQUIRE(descs, "slab_hop_adam_wgrad: no weight-gradient problems");
+    return slab_hop_adam("slab_hop_adam_wgrad", A, ns, w, gs, d_Xin, d_grad_out, d_add, d_add_mask, scale, d_partials, partials_bytes,
+                         d_p_in, d_p_out, d_m, d_v, lr, beta1, beta2, eps, weight_decay, step, tail_jobs, n_tail_jobs, d_sum_src, sum_n,
+                         d_sum_dst, descs, n, d_workspace, workspace_bytes, stream);
 }
 
 extern "C" int elimrec_slab_rows(const elimrec_sell *A, int ns, int w, int L, int64_t U, const float *const *layers,

@@ -979,6 +979,15 @@ class ColumnShardEngine(object):
         return os.environ.get("ELIMREC_FUSE_BWDW", "1") != "0" and hops_in_region >= 2
 
     @_once
+    def _fuse_wgrad_fold(self):
+        """The weight gradients' slab reduce folded into the projection weights' optimizer spans, ahead of the Adam hop's tiles:
+        one rank with both phases riding in hop launches and the Adam hop to take it; the adjoint's second hop is then a plain
+        one (ELIMREC_FUSE_WGRAD_FOLD=0: the reduce stays behind the second hop's tiles)."""
+        import os
+        return (os.environ.get("ELIMREC_FUSE_WGRAD_FOLD", "1") != "0" and not self.multi and not self.sweep and self._fuse_adam()
+                and self._fuse_reduce() and self._fuse_bwd_w())
+
+    @_once
     def _sources_in_head(self):
         """One rank, recdim 64, packed head weights: the head backward's kernel writes the adjoint sources at the active rows
         (each listed once) and the planner's key bitmap is their row bitmap -- no merge at all (ELIMREC_HEAD_SOURCES=0: the
@@ -1561,6 +1570,16 @@ class ColumnShardEngine(object):
                 self.wgrads_handle = reduce_wgrads()
             return
 
+        # one rank, both phases deferred: the reduce rides with the optimizer spans it feeds, ahead of the last hop's tiles, where
+        # the spans it covers allow it (the span list is fixed for a given set of gradients: asked once per list)
+        fold, tail_early = False, None
+        if single and fuse and reduce is not None and reduce[1] == 0 and self._fuse_wgrad_fold():
+            tail_early = self._tail_jobs()                       # (advances the weights' step counts: called once per step)
+            fkey = (self._tail_plan[0], ctypes.addressof(reduce[0][0]), reduce[0][1])
+            if getattr(self, "_fold_ok", (None, False))[0] != fkey:
+                self._fold_ok = (fkey, len(tail_early) <= 8 and slab.wgrad_fold_jobs(tail_early, reduce[0]) >= 0)
+            fold = self._fold_ok[1]
+
         def hops():
             phase = None if reduce is None else reduce[1]
             if merged:
@@ -1574,11 +1593,11 @@ class ColumnShardEngine(object):
                 dst = self.grad if k == 0 else self.tmp[k & 1]
                 slab.hop(self.planT, t, dst, gs=self.gs, src_mask=tmask, add=self.srcB if (k & 1) else self.srcA,
                          add_mask=self.mask, scale=inv if k == 0 else 1.0, bits_ready=tmask is not None and self._bits_ready,
-                         bwd_w=reduce[0] if phase is not None and phase <= 1 else None, bwd_w_phase=phase)
+                         bwd_w=reduce[0] if phase is not None and phase <= (0 if fold else 1) else None, bwd_w_phase=phase)
                 phase = None if phase is None else phase + 1
                 t, tmask = dst, None
         self._timed(lambda: m._region("cs_bwd_hops", (m._ws_gen, recv2.data_ptr(), acts.data_ptr(), R, W, fuse, self._bits_ready, merged,
-                                                               0 if reduce is None else ctypes.addressof(reduce[0][0]), 0 if reduce is None else reduce[1]), hops), L - last)
+                                                               0 if reduce is None else ctypes.addressof(reduce[0][0]), 0 if reduce is None else reduce[1], fold), hops), L - last)
         self._adam_in_hop = fuse
         self._tail_in_hop = False
         if fuse:
@@ -1596,7 +1615,10 @@ class ColumnShardEngine(object):
                 in_hop = False
             if grads_ready is not None:
                 grads_ready.wait()                            # reduced under the hops issued so far
-            tail = self._tail_jobs() if in_hop else []        # (advances the weights' step counts: called once per step)
+            if tail_early is not None:
+                tail = tail_early
+            else:
+                tail = self._tail_jobs() if in_hop else []    # (advances the weights' step counts: called once per step)
             if len(tail) > 8:
                 raise RuntimeError("more than 8 optimizer spans")
             if getattr(self, "_tail_arr", None) is None:
@@ -1611,7 +1633,7 @@ class ColumnShardEngine(object):
             self._timed(lambda: slab.hop_adam(self.planT, self.tmp[1], self.grad if self.keep_grad else None, self.gs, self.srcA,
                                               self.mask, inv, self.master[self.cur].data, self.master[nxt].data, self.m1, self.m2,
                                               g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"],
-                                              self.step_count + 1, tail_jobs=tail, loss_sum=late), 1)
+                                              self.step_count + 1, tail_jobs=tail, loss_sum=late, wgrad=reduce[0] if fold else None), 1)
 
     @torch.no_grad()
     def cs_update(self):

@@ -555,17 +555,21 @@ def hop(plan, xin, xout, gs=None, src_mask=None, add=None, add_mask=None, scale=
 
 
 def hop_adam(plan, xin, grad_out, gs, add, add_mask, scale, p_in, p_out, m, v, lr, beta1, beta2, eps, weight_decay, step, tail_jobs=(),
-             loss_sum=None):
+             loss_sum=None, wgrad=None):
     """elimrec_slab_hop_adam: the hop whose output is the gradient of the fp32 slab table p_in, consumed in place by an
     Adam step (p_out / m / v flat fp32 of the table's geometry). grad_out: a table to also receive the gradient, or None.
     tail_jobs: _lib.AdamJob spans (the projection weights) updated by extra workgroups of the same launch.
-    loss_sum = (loss_rows, loss_out): one more workgroup adds the loss rows in elimrec_sum's order into loss_out."""
+    loss_sum = (loss_rows, loss_out): one more workgroup adds the loss rows in elimrec_sum's order into loss_out.
+    wgrad: the handle of a weight-gradient batch whose partial launch has run (ops.linear_bwd_w_batched(defer_reduce=True), or
+    hop(bwd_w=, bwd_w_phase=0)) -- its slab reduce is folded into the tail jobs it feeds and leads the grid
+    (elimrec_slab_hop_adam_wgrad; wgrad_fold_jobs says whether the fold applies)."""
     if isinstance(tail_jobs, tuple) and len(tail_jobs) == 2 and not isinstance(tail_jobs[0], _lib.AdamJob):
         arr, n_tail = tail_jobs                      # (persistent AdamJob array, count): the caller keeps it alive and in place
     else:
         arr, n_tail = ((_lib.AdamJob * len(tail_jobs))(*tail_jobs) if tail_jobs else None), len(tail_jobs)
     ns, w = xin.ns, xin.w
     if _swept(plan, xin):
+        assert wgrad is None, "hop_adam: the swept form carries no weight-gradient fold"
         # the other side's rows by the tile hop (with the optimizer spans and the loss sum as its extra workgroups), the swept side's
         # by the window sweep: both with the Adam step as their epilogue, on disjoint rows of the same buffers
         hop_adam(plan.sweep.items, xin, grad_out, gs, add, add_mask, scale, p_in, p_out, m, v, lr, beta1, beta2, eps, weight_decay, step,
@@ -573,13 +577,26 @@ def hop_adam(plan, xin, grad_out, gs, add, add_mask, scale, p_in, p_out, m, v, l
         plan.sweep.hop_adam(xin, grad_out, add, add_mask, scale, p_in, p_out, m, v, lr, beta1, beta2, eps, weight_decay, step)
         return
     part = plan.partials(ns, w)
-    _lib.check(_lib.load().elimrec_slab_hop_adam(
-        plan.ref(), ns, w, int(gs), _dev(xin.data, "xin"), _dev(None if grad_out is None else grad_out.data, "grad"),
-        _dev(None if add is None else add.data, "add"), _dev(add_mask, "add_mask", torch.int32), float(scale), _dev(part, "partials"),
-        part.numel() * 4, _dev(p_in, "p_in"), _dev(p_out, "p_out"), _dev(m, "m"), _dev(v, "v"), float(lr), float(beta1), float(beta2),
-        float(eps), float(weight_decay), int(step), arr, n_tail, _dev(None if loss_sum is None else loss_sum[0], "loss_rows"),
-        0 if loss_sum is None else loss_sum[0].numel(), _dev(None if loss_sum is None else loss_sum[1], "loss_out"), _stream()),
-        "slab_hop_adam")
+    args = (plan.ref(), ns, w, int(gs), _dev(xin.data, "xin"), _dev(None if grad_out is None else grad_out.data, "grad"),
+            _dev(None if add is None else add.data, "add"), _dev(add_mask, "add_mask", torch.int32), float(scale), _dev(part, "partials"),
+            part.numel() * 4, _dev(p_in, "p_in"), _dev(p_out, "p_out"), _dev(m, "m"), _dev(v, "v"), float(lr), float(beta1), float(beta2),
+            float(eps), float(weight_decay), int(step), arr, n_tail, _dev(None if loss_sum is None else loss_sum[0], "loss_rows"),
+            0 if loss_sum is None else loss_sum[0].numel(), _dev(None if loss_sum is None else loss_sum[1], "loss_out"))
+    if wgrad is not None:
+        descs, n, wsp = wgrad
+        _lib.check(_lib.load().elimrec_slab_hop_adam_wgrad(*(args + (descs, n, _dev(wsp, "workspace", torch.uint8), wsp.numel(), _stream()))),
+                   "slab_hop_adam_wgrad")
+        return
+    _lib.check(_lib.load().elimrec_slab_hop_adam(*(args + (_stream(),))), "slab_hop_adam")
+
+
+def wgrad_fold_jobs(tail_jobs, wgrad):
+    """Tail jobs left when hop_adam(wgrad=) folds this weight-gradient batch into them (0..8), or -1: the fold does not apply."""
+    if isinstance(tail_jobs, tuple) and len(tail_jobs) == 2 and not isinstance(tail_jobs[0], _lib.AdamJob):
+        arr, n_tail = tail_jobs
+    else:
+        arr, n_tail = ((_lib.AdamJob * len(tail_jobs))(*tail_jobs) if tail_jobs else None), len(tail_jobs)
+    return int(_lib.load().elimrec_slab_hop_adam_wgrad_jobs(arr, n_tail, wgrad[0], wgrad[1]))
 
 
 

@@ -929,6 +929,24 @@ int elimrec_slab_hop_adam(const elimrec_sell *A, int ns, int w, int gs, const fl
                           float beta1, float beta2, float eps, float weight_decay, int64_t step,
                           const struct elimrec_adam_job *tail_jobs, int n_tail_jobs, const float *d_sum_src, int64_t sum_n,
                           float *d_sum_dst, void *stream);
+/* The same launch with the fixed-order slab reduce of a weight-gradient batch (descs / workspace of the partial launch that ran
+ * before, elimrec_linear_bwd_w_batched_merge(defer_reduce) or elimrec_slab_hop_bwd_w phase 0) folded into the tail jobs: the thread
+ * group that owns an output element adds its slabs exactly as elimrec_linear_bwd_w_reduce does, stores the gradient to d_out /
+ * d_colsum, and -- where the element lies inside the gradient range [d_g, d_g + n) of an updating tail job -- applies that job's
+ * Adam step (and its d_copy_dst copy) to it at once; the job itself then covers only the elements no problem writes. These
+ * workgroups lead the grid. Same bits as elimrec_linear_bwd_w_reduce followed by elimrec_slab_hop_adam with the same jobs.
+ * Every d_out must be contiguous (ldo == n2) and every output inside a job's gradient range entirely or not at all;
+ * elimrec_slab_hop_adam_wgrad_jobs (host only) returns the number of tail jobs left after the fold, 0..8, or -1 where it does
+ * not apply (the launch then fails with ELIMREC_E_BADARG and the caller keeps the two calls). */
+int elimrec_slab_hop_adam_wgrad(const elimrec_sell *A, int ns, int w, int gs, const float *d_Xin, float *d_grad_out,
+                                const float *d_add, const uint32_t *d_add_mask, float scale, float *d_partials,
+                                size_t partials_bytes, const float *d_p_in, float *d_p_out, float *d_m, float *d_v, float lr,
+                                float beta1, float beta2, float eps, float weight_decay, int64_t step,
+                                const struct elimrec_adam_job *tail_jobs, int n_tail_jobs, const float *d_sum_src, int64_t sum_n,
+                                float *d_sum_dst, const elimrec_linear_bwd_desc *descs /* host array */, int n, void *d_workspace,
+                                size_t workspace_bytes, void *stream);
+int elimrec_slab_hop_adam_wgrad_jobs(const struct elimrec_adam_job *tail_jobs /* host array */, int n_tail_jobs,
+                                     const elimrec_linear_bwd_desc *descs /* host array */, int n);
 
 /* Layer means (models/EliMRec.py:246-247) of the folded propagation at a list of rows, from slab-major layer
  * tables X^0..X^L (host array of L+1 device pointers):

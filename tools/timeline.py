@@ -5,7 +5,7 @@ rows = list(csv.DictReader(open(sys.argv[1])))
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))
 # a step = the launches after one Adam hop (the optimizer's launch ends a step on the main queue) up to and including the next;
 # traces without it (other optimizers): from one batch planner to the next
-ends = [i for i, r in enumerate(rows) if "sell_tier_adam_kernel" in r["Kernel_Name"]]
+ends = [i for i, r in enumerate(rows) if "sell_tier_adam_" in r["Kernel_Name"]]      # ..._kernel / ..._fold_kernel
 k = int(sys.argv[2]) if len(sys.argv) > 2 else 3
 if len(ends) > k + 1:
     a, b = ends[-k - 1] + 1, ends[-k] + 1
