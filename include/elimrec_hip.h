@@ -535,7 +535,13 @@ int elimrec_score_effects(const float *d_Y, int64_t ldy, int64_t U, int64_t I, c
 
 /* Precision/Recall/MAP/NDCG/MRR prefix curves @1..K from ranked lists (metric.h:17-106).
  * d_truth_ptr int64[B+1], d_truth_items int32 (unique per row). metric_ids host int[n_metrics]
- * (1..5 as in cpp/uni_evaluator.py:14). d_out [B x n_metrics x K]. */
+ * (1..5 as in cpp/uni_evaluator.py:14), 1 <= n_metrics <= 8. d_out [B x n_metrics x K]. 1 <= K <= 256 (anything else is an
+ * error and d_out is not written).
+ * PRECONDITION: a row's truth ids are distinct. The reference counts them in an unordered_set; here recall's divisor and the
+ * iDCG limit are the LENGTH of the row's segment, so a repeated id would count twice. The callers build the segments from sets
+ * (elimrec_amd/reports.py lists_csr(unique=True); the sampled evaluator's positions 0 .. npos - 1).
+ * A row with no truth ids is allowed and gives the reference's values: recall and NDCG 0 / 0 = NaN, the other three 0.
+ * A listed id < 0 (an unfilled rank) matches nothing. */
 int elimrec_rank_metrics(const int32_t *d_topk_idx, int B, int K, const int64_t *d_truth_ptr,
                          const int32_t *d_truth_items, const int *metric_ids, int n_metrics,
                          float *d_out, void *stream);

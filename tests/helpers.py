@@ -147,3 +147,21 @@ def build_model_from_fixture(g, device, params_prefix="init", extra_argv=()):
     sd = {k: torch.from_numpy(v.copy()) for k, v in sub(g, params_prefix).items()}
     model.load_state_dict(sd, strict=True)
     return model.to(device), cfg
+
+
+def tie_free(scores, k):
+    """rows whose k+1 largest values are pairwise distinct (no tie at or across the K boundary)."""
+    s = -np.sort(-scores, axis=1)[:, :k + 1]
+    return np.all(s[:, :-1] != s[:, 1:], axis=1)
+
+
+def reference_lists(sc, K):
+    """The oracle's lists of rows of scores: the C restatement of evaluate.h:26-33 and, where it was built, the reference's own
+    compiled header (both must agree)."""
+    from oracle import eval_oracle as ev
+    tp, ti = ev.truth_to_csr([[0]] * sc.shape[0])
+    _, port = ev.evaluate_matrix(sc.copy(), tp, ti, [1], K)
+    if ev.ref_lib() is not None:
+        _, ref = ev.evaluate_matrix(sc.copy(), tp, ti, [1], K, use_ref=True)
+        assert np.array_equal(port, ref)
+    return port

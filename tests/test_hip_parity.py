@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from helpers import assert_grad_close, build_model_from_fixture, csr_dict, load_golden, rel_err, sub
+from helpers import reference_lists as _reference_lists, tie_free as _tie_free
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -187,12 +188,6 @@ def test_step_regions_replayed_equal_eager(monkeypatch):
         assert out[mode][0] == out["eager"][0], mode
         for k, v in out["eager"][1].items():
             assert torch.equal(out[mode][1][k], v), (mode, k)
-
-
-def _tie_free(scores, k):
-    """rows whose k+1 largest values are pairwise distinct (no tie at or across the K boundary)."""
-    s = -np.sort(-scores, axis=1)[:, :k + 1]
-    return np.all(s[:, :-1] != s[:, 1:], axis=1)
 
 
 def _my_rule_topk(scores, K):
@@ -1472,18 +1467,6 @@ def test_reference_tie_order_is_reproduced_on_request(fixture_name, eval_math):
     ov = torch.empty(len(users), K, device=DEV)
     ops.topk_reference_order(dev_scores, K, oi, ov)
     assert np.array_equal(oi.cpu().numpy(), ref_topk) and np.array_equal(ov.cpu().numpy(), val_ref.cpu().numpy())
-
-
-def _reference_lists(sc, K):
-    """The oracle's lists of rows of scores: the C restatement of evaluate.h:26-33 and, where it was built, the reference's own
-    compiled header (both must agree)."""
-    from oracle import eval_oracle as ev
-    tp, ti = ev.truth_to_csr([[0]] * sc.shape[0])
-    _, port = ev.evaluate_matrix(sc.copy(), tp, ti, [1], K)
-    if ev.ref_lib() is not None:
-        _, ref = ev.evaluate_matrix(sc.copy(), tp, ti, [1], K, use_ref=True)
-        assert np.array_equal(port, ref)
-    return port
 
 
 @pytest.mark.gpu
