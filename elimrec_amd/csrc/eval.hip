@@ -2,6 +2,7 @@
 // metrics, all on device (models/EliMRec.py:96-113,155-212; cpp/uni_evaluator.py:131-185;
 // evaluate.h:23-42; metric.h:17-106). Removes the [B_t x I] device->host copy of the reference.
 #include "common.h"
+#include "dispatch.h"
 #include <cstdlib>
 #include <type_traits>
 
@@ -1786,7 +1787,6 @@ extern "C" int elimrec_row_sqnorms(const float *d_Y, int64_t ldy, int64_t n_rows
 }
 
 // ---- run-time value -> template argument: f is a generic lambda called with std::integral_constants (the sets ARE the code object's)
-template <int V> using int_c = std::integral_constant<int, V>;
 template <bool HEADLESS, class F> static void with_nb(int S, F f) {       // NB = 1 + S head blocks (NB = 1: the candidate scorer only)
     if constexpr (HEADLESS) { if (S == 0) return f(int_c<1>{}); }
     if (S == 1) f(int_c<2>{}); else if (S == 2) f(int_c<3>{}); else f(int_c<4>{});
@@ -1804,7 +1804,6 @@ template <class F> static void with_pt_fm(int pt, int fm, F f) {          // (pr
     else if (fm == 1) f(int_c<2>{}, int_c<1>{});
     else f(int_c<2>{}, int_c<2>{});
 }
-template <class F> static void with_fast(bool fast, F f) { if (fast) f(std::true_type{}); else f(std::false_type{}); }
 
 // score_t16_kernel: 16 users per wave, 128 per workgroup, a persistent grid over 16-item tiles (two workgroups per CU)
 constexpr size_t t16_lds(int pass, int nb, int d) {
@@ -1813,10 +1812,6 @@ constexpr size_t t16_lds(int pass, int nb, int d) {
 static dim3 t16_grid(int tiles, int B) {                   // tiles dealt evenly to at most 512 workgroups
     const int per = (tiles + 511) / 512;
     return dim3((unsigned)((tiles + per - 1) / per), (B + TW * TU - 1) / (TW * TU));
-}
-template <auto KERNEL> static void allow_lds(size_t lds) {      // beyond 64 KiB of dynamic LDS: once per kernel instantiation
-    static bool done = false;
-    if (!done) { (void)hipFuncSetAttribute((const void *)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); done = true; }
 }
 template <int PASS, int NB, int PT, int FM, bool FAST, int D>
 static void launch_t16(dim3 grid, const ScoreArgs &a, int tiles, hipStream_t s) {

@@ -12,6 +12,7 @@
 // decreasing length; a lane group of LPR = spg*w/4 lanes owns one item, a wave 64/LPR items of similar length, and
 // the (col, val) of step j of the wave's items are consecutive in memory. HBM/L2-bound (9 flop per 4-B gathered).
 #include "common.h"
+#include "dispatch.h"
 #include "merge_rows.h"
 #include "rows_args.h"
 #include "bwd_w.h"
@@ -903,32 +904,24 @@ static int launch_tier(const elimrec_sell *A, int ns, int wl, int wl_shift, int 
         hipLaunchKernelGGL(tile_ballot_kernel, dim3((unsigned)per_group, (unsigned)t.kmax), dim3(256), 0, s, t.tile_off, t.tcol, src_mask, 64 / lpr,
                            t.n_tiles_run, t.kmax, ballots);
     }
-#define ELIMREC_TIER(LPR)                                                                                                     \
-    do {                                                                                                                      \
-        if (fold)                                                                                                             \
-            hipLaunchKernelGGL((sell_tier_adam_fold_kernel<LPR>), grid_adam, dim3(256), 0, s, t, tail, tail_block0, *fold,    \
-                               fold_front);                                                                                   \
-        else if (adam) hipLaunchKernelGGL((sell_tier_adam_kernel<LPR>), grid_adam, dim3(256), 0, s, t, tail, tail_block0);    \
-        else if (bwdw && masked)                                                                                              \
-            hipLaunchKernelGGL((sell_tier_bwdw_kernel<LPR, true>), dim3(grid.x + (unsigned)tail_blocks), dim3(256), 0, s, t,  \
-                               *bwdw, tail_block0, tail_mode, reduce_gx);                                                     \
-        else if (bwdw)                                                                                                        \
-            hipLaunchKernelGGL((sell_tier_bwdw_kernel<LPR, false>), dim3(grid.x + (unsigned)tail_blocks), dim3(256), 0, s, t, \
-                               *bwdw, tail_block0, tail_mode, reduce_gx);                                                     \
-        else if (masked) hipLaunchKernelGGL((sell_tier_kernel<LPR, 4, false, false, true>), grid, dim3(256), 0, s, t);        \
-        else hipLaunchKernelGGL((sell_tier_kernel<LPR, 4, false, false, false>), grid, dim3(256), 0, s, t);                   \
-    } while (0)
-    switch (lpr) {
-        case 1: ELIMREC_TIER(1); break;
-        case 2: ELIMREC_TIER(2); break;
-        case 4: ELIMREC_TIER(4); break;
-        case 8: ELIMREC_TIER(8); break;
-        case 16: ELIMREC_TIER(16); break;
-        case 32: ELIMREC_TIER(32); break;
-        default: ELIMREC_TIER(64); break;
-    }
-#undef ELIMREC_TIER
-    return check_hip(hipGetLastError(), "slab_hop(tiered)");
+    return with_pow2<1>("slab_hop", lpr, [&](auto L) {
+        constexpr int LPR = decltype(L)::value;
+        if (fold)
+            hipLaunchKernelGGL((sell_tier_adam_fold_kernel<LPR>), grid_adam, dim3(256), 0, s, t, tail, tail_block0, *fold, fold_front);
+        else if (adam)
+            hipLaunchKernelGGL((sell_tier_adam_kernel<LPR>), grid_adam, dim3(256), 0, s, t, tail, tail_block0);
+        else if (bwdw && masked)
+            hipLaunchKernelGGL((sell_tier_bwdw_kernel<LPR, true>), dim3(grid.x + (unsigned)tail_blocks), dim3(256), 0, s, t, *bwdw,
+                               tail_block0, tail_mode, reduce_gx);
+        else if (bwdw)
+            hipLaunchKernelGGL((sell_tier_bwdw_kernel<LPR, false>), dim3(grid.x + (unsigned)tail_blocks), dim3(256), 0, s, t, *bwdw,
+                               tail_block0, tail_mode, reduce_gx);
+        else if (masked)
+            hipLaunchKernelGGL((sell_tier_kernel<LPR, 4, false, false, true>), grid, dim3(256), 0, s, t);
+        else
+            hipLaunchKernelGGL((sell_tier_kernel<LPR, 4, false, false, false>), grid, dim3(256), 0, s, t);
+        return check_hip(hipGetLastError(), "slab_hop(tiered)");
+    });
 }
 
 static int slab_geometry(const char *who, int ns, int w, int gs, int &w4_shift, int &spg, int &lpr) {
@@ -982,35 +975,20 @@ extern "C" int elimrec_slab_hop(const elimrec_sell *A, int ns, int w, int gs, co
     if (n_it > 0) {
         const int ipw = 64 / lpr;
         const unsigned blocks = (unsigned)(((int64_t)n_it / ipw + 3) / 4) * (unsigned)gs;
-#define ELIMREC_SELL_LAUNCH(LPR)                                                                          \
-    do {                                                                                                  \
-        if (d_src_mask) hipLaunchKernelGGL((sell_hop_kernel<LPR, true, 8, false>), dim3(blocks), dim3(256), 0, s, a); \
-        else hipLaunchKernelGGL((sell_hop_kernel<LPR, false, 4, true>), dim3(blocks), dim3(256), 0, s, a);            \
-    } while (0)
-        switch (lpr) {
-            case 1: ELIMREC_SELL_LAUNCH(1); break;
-            case 2: ELIMREC_SELL_LAUNCH(2); break;
-            case 4: ELIMREC_SELL_LAUNCH(4); break;
-            case 8: ELIMREC_SELL_LAUNCH(8); break;
-            case 16: ELIMREC_SELL_LAUNCH(16); break;
-            case 32: ELIMREC_SELL_LAUNCH(32); break;
-            default: ELIMREC_SELL_LAUNCH(64); break;
-        }
-#undef ELIMREC_SELL_LAUNCH
-        ELIMREC_LAUNCH_CHECK("slab_hop");
+        rc = with_pow2<1>("slab_hop", lpr, [&](auto L) {
+            constexpr int LPR = decltype(L)::value;
+            if (d_src_mask) hipLaunchKernelGGL((sell_hop_kernel<LPR, true, 8, false>), dim3(blocks), dim3(256), 0, s, a);
+            else hipLaunchKernelGGL((sell_hop_kernel<LPR, false, 4, true>), dim3(blocks), dim3(256), 0, s, a);
+            return check_hip(hipGetLastError(), "slab_hop");
+        });
+        if (rc) return rc;
     }
     if (A->n_long > 0) {
         const unsigned blocks = (unsigned)((A->n_long + 3) / 4) * (unsigned)gs;
-        switch (lpr) {
-            case 1: hipLaunchKernelGGL((sell_fixup_kernel<1>), dim3(blocks), dim3(256), 0, s, a); break;
-            case 2: hipLaunchKernelGGL((sell_fixup_kernel<2>), dim3(blocks), dim3(256), 0, s, a); break;
-            case 4: hipLaunchKernelGGL((sell_fixup_kernel<4>), dim3(blocks), dim3(256), 0, s, a); break;
-            case 8: hipLaunchKernelGGL((sell_fixup_kernel<8>), dim3(blocks), dim3(256), 0, s, a); break;
-            case 16: hipLaunchKernelGGL((sell_fixup_kernel<16>), dim3(blocks), dim3(256), 0, s, a); break;
-            case 32: hipLaunchKernelGGL((sell_fixup_kernel<32>), dim3(blocks), dim3(256), 0, s, a); break;
-            default: hipLaunchKernelGGL((sell_fixup_kernel<64>), dim3(blocks), dim3(256), 0, s, a); break;
-        }
-        ELIMREC_LAUNCH_CHECK("slab_hop(fixup)");
+        return with_pow2<1>("slab_hop", lpr, [&](auto L) {
+            hipLaunchKernelGGL((sell_fixup_kernel<decltype(L)::value>), dim3(blocks), dim3(256), 0, s, a);
+            return check_hip(hipGetLastError(), "slab_hop(fixup)");
+        });
     }
     return 0;
 }
@@ -1275,17 +1253,10 @@ extern "C" int elimrec_slab_rows(const elimrec_sell *A, int ns, int w, int L, in
     while (lr < a.nc4 && lr < 64) lr *= 2;
     hipStream_t s = (hipStream_t)stream;
     const unsigned blocks = (unsigned)((total + (256 / lr) - 1) / (256 / lr));
-    switch (lr) {
-        case 1: hipLaunchKernelGGL((slab_rows_kernel<1>), dim3(blocks), dim3(256), 0, s, a); break;
-        case 2: hipLaunchKernelGGL((slab_rows_kernel<2>), dim3(blocks), dim3(256), 0, s, a); break;
-        case 4: hipLaunchKernelGGL((slab_rows_kernel<4>), dim3(blocks), dim3(256), 0, s, a); break;
-        case 8: hipLaunchKernelGGL((slab_rows_kernel<8>), dim3(blocks), dim3(256), 0, s, a); break;
-        case 16: hipLaunchKernelGGL((slab_rows_kernel<16>), dim3(blocks), dim3(256), 0, s, a); break;
-        case 32: hipLaunchKernelGGL((slab_rows_kernel<32>), dim3(blocks), dim3(256), 0, s, a); break;
-        default: hipLaunchKernelGGL((slab_rows_kernel<64>), dim3(blocks), dim3(256), 0, s, a); break;
-    }
-    ELIMREC_LAUNCH_CHECK("slab_rows");
-    return 0;
+    return with_pow2<1>("slab_rows", lr, [&](auto L) {
+        hipLaunchKernelGGL((slab_rows_kernel<decltype(L)::value>), dim3(blocks), dim3(256), 0, s, a);
+        return check_hip(hipGetLastError(), "slab_rows");
+    });
 }
 
 extern "C" int elimrec_slab_from_rows(const float *d_src, int64_t ld, int64_t col0, int64_t n, int ns, int w,

@@ -5,6 +5,7 @@
 // over the CSR structure serves every table. HBM-bound: per hop read C*4 B per non-zero
 // (+ 8 B of CSR), write C*4 B per row.
 #include "common.h"
+#include "dispatch.h"
 #include <cstdlib>
 
 namespace elimrec {
@@ -671,38 +672,30 @@ static int launch_half(const elimrec_csr *m, HalfArgs a, size_t partials_offset,
     const int rpw = 64 / lpr;
     const int waves = 4;
     auto blocks = [&](int64_t n) { return dim3((unsigned)((n + (int64_t)waves * rpw - 1) / (waves * rpw))); };
-#define ELIMREC_HALF_LAUNCH(LPR)                                                                                     \
-    do {                                                                                                             \
-        const unsigned seg_blocks = has_split ? blocks(a.n_seg).x : 0u;                                              \
-        if (a.src_mask)                                                                                              \
-            hipLaunchKernelGGL((half_hop_kernel<LPR, 8, true>), dim3(seg_blocks + blocks(a.n_rows).x),               \
-                               dim3(64 * waves), 0, s, a, (int)seg_blocks);                                          \
-        else {                                                                                                       \
-            /* streaming rows: a persistent grid (stream_wgs workgroups walk all items) */                           \
-            unsigned row_blocks = blocks(a.row_list ? a.row_list_cap : a.n_rows).x;                                  \
-            if (LPR >= 8 && a.row_items && !a.row_list && a.W4 <= LPR) {                                             \
-                row_blocks = blocks(a.n_row_items).x;                                                                \
-                if (row_blocks > (unsigned)stream_wgs()) row_blocks = (unsigned)stream_wgs();                        \
-                if (row_blocks == 0) row_blocks = 1;                                                                 \
-            }                                                                                                        \
-            hipLaunchKernelGGL((half_hop_kernel<LPR, 8, false>), dim3(seg_blocks + row_blocks),                      \
-                               dim3(64 * waves), 0, s, a, (int)seg_blocks);                                          \
-        }                                                                                                            \
-        ELIMREC_LAUNCH_CHECK("half_hop");                                                                            \
-        if (has_split && !a.tickets) {                                                                               \
-            hipLaunchKernelGGL((half_fixup_kernel<LPR>), dim3((unsigned)((a.n_long + waves - 1) / waves)), dim3(64 * waves), 0, s, a);               \
-            ELIMREC_LAUNCH_CHECK("half_fixup");                                                                      \
-        }                                                                                                            \
-    } while (0)
-    switch (lpr) {
-        case 64: ELIMREC_HALF_LAUNCH(64); break;
-        case 32: ELIMREC_HALF_LAUNCH(32); break;
-        case 16: ELIMREC_HALF_LAUNCH(16); break;
-        case 8: ELIMREC_HALF_LAUNCH(8); break;
-        default: ELIMREC_HALF_LAUNCH(4); break;
-    }
-#undef ELIMREC_HALF_LAUNCH
-    return 0;
+    return with_pow2<4>("half_hop", lpr, [&](auto L) {
+        constexpr int LPR = decltype(L)::value;
+        const unsigned seg_blocks = has_split ? blocks(a.n_seg).x : 0u;
+        if (a.src_mask)
+            hipLaunchKernelGGL((half_hop_kernel<LPR, 8, true>), dim3(seg_blocks + blocks(a.n_rows).x), dim3(64 * waves), 0, s, a,
+                               (int)seg_blocks);
+        else {
+            // streaming rows: a persistent grid (stream_wgs workgroups walk all items)
+            unsigned row_blocks = blocks(a.row_list ? a.row_list_cap : a.n_rows).x;
+            if (LPR >= 8 && a.row_items && !a.row_list && a.W4 <= LPR) {
+                row_blocks = blocks(a.n_row_items).x;
+                if (row_blocks > (unsigned)stream_wgs()) row_blocks = (unsigned)stream_wgs();
+                if (row_blocks == 0) row_blocks = 1;
+            }
+            hipLaunchKernelGGL((half_hop_kernel<LPR, 8, false>), dim3(seg_blocks + row_blocks), dim3(64 * waves), 0, s, a,
+                               (int)seg_blocks);
+        }
+        ELIMREC_LAUNCH_CHECK("half_hop");
+        if (has_split && !a.tickets) {
+            hipLaunchKernelGGL((half_fixup_kernel<LPR>), dim3((unsigned)((a.n_long + waves - 1) / waves)), dim3(64 * waves), 0, s, a);
+            ELIMREC_LAUNCH_CHECK("half_fixup");
+        }
+        return 0;
+    });
 }
 
 static HalfArgs half_args(int W4, const float *Xin, const uint32_t *src_mask, float *Xout, const float *Add1,

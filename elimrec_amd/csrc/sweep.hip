@@ -28,6 +28,7 @@
 // Placement: workgroup b takes the role of XCD b % 8 (workgroups b and b + 8 share an XCD on this chip; another placement
 // costs speed only).
 #include "common.h"
+#include "dispatch.h"
 #include <cmath>
 
 namespace elimrec {
@@ -199,18 +200,13 @@ static int sweep_launch(const char *who, const int64_t *d_slot_ptr, const void *
     const size_t lds = (size_t)(max_block_rows + 1) * (size_t)w * 4;
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((unsigned)(8 * bpx));
-#define ELIMREC_SWEEP(LPR_, ADAM_)                                                                                                       \
-    do {                                                                                                                                 \
-        static bool attr = false;                                                                                                        \
-        if (!attr) {                                                                                                                     \
-            (void)hipFuncSetAttribute((const void *)sweep_rows_kernel<LPR_, ADAM_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-            attr = true;                                                                                                                 \
-        }                                                                                                                                \
-        hipLaunchKernelGGL((sweep_rows_kernel<LPR_, ADAM_>), grid, dim3(64 * LPR_), lds, s, a);                                          \
-    } while (0)
-    if (w == 32) { if (adam) ELIMREC_SWEEP(8, true); else ELIMREC_SWEEP(8, false); }
-    else { if (adam) ELIMREC_SWEEP(4, true); else ELIMREC_SWEEP(4, false); }
-#undef ELIMREC_SWEEP
+    const auto launch = [&](auto L, auto ad) {
+        constexpr int LPR = decltype(L)::value;
+        constexpr bool ADAM = decltype(ad)::value;
+        allow_lds<sweep_rows_kernel<LPR, ADAM>>(160 * 1024);
+        hipLaunchKernelGGL((sweep_rows_kernel<LPR, ADAM>), grid, dim3(64 * LPR), lds, s, a);
+    };
+    with_fast(adam != nullptr, [&](auto ad) { if (w == 32) launch(int_c<8>{}, ad); else launch(int_c<4>{}, ad); });
     return check_hip(hipGetLastError(), who);
 }
 

@@ -319,6 +319,29 @@ def test_two_launch_form(d, w, gs, T):
     assert same_bits(lt, c.out0[rows].contiguous()), c.what + ": seg_only differs from the plain hop's rows"
 
 
+@pytest.mark.parametrize("d,w,gs", [(64, 32, 2), (256, 32, 1)])
+def test_two_launch_form_without_split_rows(d, w, gs):
+    """No row above T (n_long == 0): the SELL launch alone, no fix-up launch; LPR 8 and LPR 64 (one row piece per wave)."""
+    slab = _slab()
+    T, G, ns = 32, 64 // _lpr(d, w, gs), d // w
+    m, plan = _plan("flat", T, G, tiered=False)
+    n = m.shape[0]
+    assert not plan.tiered and plan.n_long == 0
+    what = "(d %d, w %d, gs %d) LPR %d T %d two-launch, flat ladder" % (d, w, gs, _lpr(d, w, gs), T)
+    X, K = _rand(d + T, n, d), sm.hop_K(m)
+    (r, rs), _ = sm.hop(m, X)
+    y = _nan_table(n, ns, w)
+    slab.hop(plan, _table(X, ns, w), y, gs=gs)
+    _close("two-launch", y.dense(), r, rs, K, what + " plain")
+    for name, mask in (("every 64th", np.arange(n) % 64 == 0), ("none", np.zeros(n, dtype=bool))):
+        Sn = _keep(X, mask)
+        src, bm = _table(Sn, ns, w), _bits(mask)
+        _, (ref, scale) = sm.hop(m, Sn, add1=Sn, add1_mask=mask, scale=0.5, src_mask=mask)
+        y.data.fill_(NAN)
+        slab.hop(plan, src, y, gs=gs, src_mask=bm, add=src, add_mask=bm, scale=0.5)
+        _close("two-launch", y.dense(), ref, scale, K, "%s masked, %s" % (what, name))
+
+
 # ============================================================================= the window sweep
 SWEEP_GEOMS = [(32, 32), (64, 32), (256, 32), (512, 32), (16, 16), (64, 16)]
 SWEEP_LADDERS = [(29, 700), (37, 700), (523, 1100)]  # fewer swept rows than row blocks (29: at every geometry; 37: below 8 slabs); several
