@@ -224,6 +224,11 @@ SIGNATURES = {
     "elimrec_history_support": (c_i32, [c_ptr, c_i64, c_i64, c_i32, c_i32, c_ptr, c_i64, ctypes.POINTER(c_f32), c_ptr, c_ptr, c_i64,
                                         c_i32, c_ptr, c_ptr, c_i64, c_i32, c_i32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
     "elimrec_history_max_top": (c_i32, []),
+    "elimrec_bootstrap_means": (c_i32, [c_ptr, c_ptr, c_i64, c_i32, c_i64, c_ptr, c_ptr, c_i64, c_i32, c_i64, c_u64, c_ptr, c_i64, c_i32,
+                                        c_ptr]),
+    "elimrec_bootstrap_max_columns": (c_i32, []),
+    "elimrec_bootstrap_replicate_tile": (c_i32, []),
+    "elimrec_bootstrap_rows_in_lds": (c_i32, [c_i64, c_i32]),
     "elimrec_slab_partials_bytes": (c_size, [c_sell, c_i32, c_i32]),
     "elimrec_slab_hop": (c_i32, [c_sell, c_i32, c_i32, c_i32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_f32, c_ptr, c_size, c_i32,
                                  c_ptr]),

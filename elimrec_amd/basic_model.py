@@ -7,8 +7,8 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import ops
-from .evaluator import ProxyEvaluator
-from .reports import DiversifyReport, EffectReport, HistoryReport, ListReport, NeighbourReport, RankReport
+from .evaluator import ProxyEvaluator, UniEvaluator
+from .reports import DiversifyReport, EffectReport, HistoryReport, ListReport, NeighbourReport, RankReport, SignificanceReport
 
 
 class BasicModel(nn.Module):
@@ -88,6 +88,22 @@ class BasicModel(nn.Module):
             t_hist = config["history_top"] if "history_top" in config else 3
             self.history_reporter = HistoryReport(dataset, train, dataset.get_user_test_dict(), k_hist, top=t_hist,
                                                   group_view=config["group_view"])
+        # --significance_report=R (CLI-only, default 0 = off): R bootstrap replicates over the test users of the evaluator's own metric
+        # rows: standard error and percentile interval (--significance_level, default 0.95; --significance_seed, default 2022) of
+        # every shown metric, overall and per user group, and the paired TE -> TIE difference with its p-value
+        # (reports.SignificanceReport). Its evaluator is one of its own -- the test pass's arguments, not its state
+        n_rep = config["significance_report"] if "significance_report" in config else 0
+        if isinstance(n_rep, bool) or not isinstance(n_rep, int) or n_rep < 0:
+            raise ValueError("significance_report must be 0 (off) or the number of bootstrap replicates, got %r" % (n_rep,))
+        self.significance_reporter = None
+        if n_rep:
+            ev = UniEvaluator(dataset, train, dataset.get_user_test_dict(), test_neg, metric=config["metric"], top_k=config["topks"],
+                              batch_size=config["test_batch_size"], num_thread=config["num_thread"])
+            ev.tie_order = self.test_evaluator.evaluator.tie_order
+            self.significance_reporter = SignificanceReport(
+                dataset, train, dataset.get_user_test_dict(), config["topks"], metric=config["metric"], group_view=config["group_view"],
+                replicates=n_rep, level=config["significance_level"] if "significance_level" in config else 0.95,
+                seed=config["significance_seed"] if "significance_seed" in config else 2022, evaluator=ev)
         self.infonce_criterion = nn.CrossEntropyLoss()          # BasicModel.py:32
 
     def getFileName(self):

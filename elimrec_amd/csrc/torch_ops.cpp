@@ -30,6 +30,9 @@
 //     hist_items i32, top, exclude_self) -> (idx i32 [B x K x top], val f32 [B x K x top], cnt i32 [B x K], mean f32 [B x K]): per target the
 //     `top` entries of its user's history (segment users[b] of the CSR) with the largest sum_b w_b cos_b, the lower position among equals;
 //     -1 / -inf fillers, cnt / mean over the listed entries (csrc/history.hip)
+//   bootstrap_means(rows f32[n x C], group_ptr i64[G+1], group_rows i32, R, seed) -> f64[R x G x C]: R bootstrap replicates of every
+//     group's column means, the draws fixed by Philox4x32-10 at (seed, r, g, t); bootstrap_diff_means(rows_a, rows_b, ...): the same of
+//     the paired differences rows_b - rows_a, taken in float64; blocks wider than 16 columns go through in slices (csrc/bootstrap.hip)
 //   sample_triplets(user_ids, ptr, items, num_items, n, seed, epoch) -> (users, pos, neg)
 //   score_candidates(Y, U, I, users, d, S, head_mask, fusion_mode, predict_type, cand_ptr, cand_items, width) -> f32[B x width]
 //       (each row: its candidates' scores in list order, then -inf)
@@ -540,6 +543,50 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> history_support(const
     return {idx, val, cnt, mean};
 }
 
+// ---- bootstrap replicates of group means (one resample per (replicate, group), shared by the columns)
+static at::Tensor bootstrap_impl(const at::Tensor &rows, const at::Tensor *rows_b, const at::Tensor &group_ptr, const at::Tensor &group_rows,
+                                 int64_t R, int64_t seed, const char *who) {
+    at::Tensor r = rowmajor(rows, "rows"), b;
+    need(group_ptr, "group_ptr", at::kLong, 1); need(group_rows, "group_rows", at::kInt, 1);
+    if (rows_b) {
+        TORCH_CHECK(rows_b->sizes() == rows.sizes(), "elimrec::", who, ": rows_a and rows_b must have one shape");
+        r = r.contiguous(); b = rowmajor(*rows_b, "rows_b").contiguous();                     // (one row stride for both)
+    }
+    const at::Tensor gp = group_ptr.contiguous(), gr = group_rows.contiguous();
+    const int64_t G = gp.numel() - 1, n_listed = gr.numel(), n = r.size(0), C = r.size(1);
+    TORCH_CHECK(G >= 1, "elimrec::", who, ": group_ptr needs G + 1 >= 2 entries");
+    TORCH_CHECK(R >= 1 && R < ((int64_t)1 << 31), "elimrec::", who, ": 1 <= R < 2^31, got ", R);
+    TORCH_CHECK(C >= 1, "elimrec::", who, ": rows needs at least one column");
+    {   // no unchecked index reaches the kernel: the CSR is validated on the host
+        const at::Tensor hp = gp.cpu();
+        const int64_t *p = hp.data_ptr<int64_t>();
+        bool ok = p[0] == 0 && p[G] == n_listed;
+        for (int64_t g = 0; g < G && ok; ++g) ok = p[g] <= p[g + 1];
+        TORCH_CHECK(ok, "elimrec::", who, ": group_ptr must ascend from 0 to len(group_rows) = ", n_listed);
+        if (n_listed > 0) {
+            const int64_t lo = gr.min().item<int64_t>(), hi = gr.max().item<int64_t>();
+            TORCH_CHECK(lo >= 0 && hi < n, "elimrec::", who, ": row indices span [", lo, ", ", hi, "], the block has ", n, " rows");
+        }
+    }
+    at::Tensor out = at::empty({R, G, C}, r.options().dtype(at::kDouble));
+    at::Tensor none = at::zeros({1}, gr.options());
+    const int64_t step = elimrec_bootstrap_max_columns(), ld = n > 1 ? r.stride(0) : C;
+    for (int64_t c0 = 0; c0 < C; c0 += step)
+        check(elimrec_bootstrap_means(r.data_ptr<float>() + c0, rows_b ? b.data_ptr<float>() + c0 : nullptr, n, (int)std::min(step, C - c0), ld,
+                                      gp.data_ptr<int64_t>(), n_listed ? gr.data_ptr<int32_t>() : none.data_ptr<int32_t>(), n_listed, (int)G, R,
+                                      (uint64_t)seed, out.data_ptr<double>() + c0, C, 1, cur_stream()), who);
+    return out;
+}
+
+at::Tensor bootstrap_means(const at::Tensor &rows, const at::Tensor &group_ptr, const at::Tensor &group_rows, int64_t R, int64_t seed) {
+    return bootstrap_impl(rows, nullptr, group_ptr, group_rows, R, seed, "bootstrap_means");
+}
+
+at::Tensor bootstrap_diff_means(const at::Tensor &rows_a, const at::Tensor &rows_b, const at::Tensor &group_ptr, const at::Tensor &group_rows,
+                                int64_t R, int64_t seed) {
+    return bootstrap_impl(rows_a, &rows_b, group_ptr, group_rows, R, seed, "bootstrap_diff_means");
+}
+
 at::Tensor sample_negatives(const at::Tensor &excl_ptr, const at::Tensor &excl_items, int64_t num_items, int64_t n_neg, int64_t seed) {
     need(excl_ptr, "excl_ptr", at::kLong, 1); need(excl_items, "excl_items", at::kInt, 1);
     const at::Tensor p = excl_ptr.contiguous(), it = excl_items.contiguous();
@@ -668,6 +715,8 @@ TORCH_LIBRARY(elimrec, m) {
           "Tensor cands) -> (Tensor, Tensor, Tensor)");
     m.def("history_support(Tensor table, Tensor sqnorm, float[] weights, Tensor users, Tensor lists, Tensor hist_ptr, Tensor hist_items, int top, "
           "bool exclude_self) -> (Tensor, Tensor, Tensor, Tensor)");
+    m.def("bootstrap_means(Tensor rows, Tensor group_ptr, Tensor group_rows, int R, int seed) -> Tensor");
+    m.def("bootstrap_diff_means(Tensor rows_a, Tensor rows_b, Tensor group_ptr, Tensor group_rows, int R, int seed) -> Tensor");
     m.def("sample_negatives(Tensor excl_ptr, Tensor excl_items, int num_items, int n_neg, int seed) -> Tensor");
     m.def("lookup_counts(Tensor acts, int U, int I, int[] user_bounds, int[] item_bounds) -> Tensor");
     m.def("lookup_pack(Tensor acts, int U, int I, int[] user_bounds, int[] item_bounds, int me, Tensor shard, int row_bytes) -> (Tensor, Tensor)");
@@ -699,6 +748,8 @@ TORCH_LIBRARY_IMPL(elimrec, CUDA, m) {
     m.impl("mmr_rerank", &mmr_rerank);
     m.impl("pick_hard_negatives", &pick_hard_negatives);
     m.impl("history_support", &history_support);
+    m.impl("bootstrap_means", &bootstrap_means);
+    m.impl("bootstrap_diff_means", &bootstrap_diff_means);
     m.impl("sample_negatives", &sample_negatives);
     m.impl("lookup_counts", &lookup_counts);
     m.impl("lookup_pack", &lookup_pack);

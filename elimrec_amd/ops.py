@@ -808,6 +808,20 @@ def ragged_padded(flat, lens, width=None, dtype=np.int32):
     return out
 
 
+def _group_index_for(who, rows, group_ptr, group_rows):
+    """group_metric_means' reading of its group arguments: a GroupIndex (checked once) as is, raw arrays checked on the host now."""
+    n = rows.shape[0]
+    if isinstance(group_ptr, GroupIndex):
+        index = group_ptr
+        if group_rows is not None and group_rows is not index.rows:
+            raise ValueError("elimrec_amd.ops.%s: a GroupIndex carries its own rows (pass group_rows=None)" % who)
+        if index.n_rows > n or index.ptr.device != rows.device:
+            raise IndexError("elimrec_amd.ops.%s: the GroupIndex was checked for %d rows on %s, the block has %d on %s"
+                             % (who, index.n_rows, index.ptr.device, n, rows.device))
+        return index
+    return GroupIndex(group_ptr, group_rows, n, rows.device)
+
+
 def group_metric_means(rows, group_ptr, group_rows, out, workspace=None):
     """out [G x C] (float32, contiguous) = per group the column means of rows [n x C] (a column slice of a wider block is
     fine): float64 sums in listed order, divided in float64, rounded once (elimrec_group_metric_means). group_ptr / group_rows:
@@ -817,15 +831,7 @@ def group_metric_means(rows, group_ptr, group_rows, out, workspace=None):
     lib = _lib.load()
     rp, ld = _rowmajor(rows, "rows")
     n, C = rows.shape
-    if isinstance(group_ptr, GroupIndex):
-        index = group_ptr
-        if group_rows is not None and group_rows is not index.rows:
-            raise ValueError("elimrec_amd.ops.group_metric_means: a GroupIndex carries its own rows (pass group_rows=None)")
-        if index.n_rows > n or index.ptr.device != rows.device:
-            raise IndexError("elimrec_amd.ops.group_metric_means: the GroupIndex was checked for %d rows on %s, the block has %d on %s"
-                             % (index.n_rows, index.ptr.device, n, rows.device))
-    else:
-        index = GroupIndex(group_ptr, group_rows, n, rows.device)
+    index = _group_index_for("group_metric_means", rows, group_ptr, group_rows)
     G = index.n_groups
     if not (isinstance(out, torch.Tensor) and out.is_contiguous() and tuple(out.shape) == (G, C)):
         raise ValueError("elimrec_amd.ops.group_metric_means: out must be a contiguous [%d x %d] tensor" % (G, C))
@@ -836,6 +842,67 @@ def group_metric_means(rows, group_ptr, group_rows, out, workspace=None):
                                               _dev(index.rows, "group_rows", torch.int32), index.n_listed, G, _dev(out, "out"),
                                               _dev(workspace, "workspace", torch.uint8), workspace.numel(), _stream()),
                "group_metric_means")
+    return out
+
+
+def bootstrap_rows_in_lds(n_g, C):
+    """Which form bootstrap_means takes for a group of n_g listed rows in a call (or column slice) of C columns (host arithmetic
+    only): True = the group's values are staged once per workgroup into LDS, False = every draw gathers from global memory. Both
+    forms give the same bits. ValueError outside 0 <= n_g < 2^31, 1 <= C <= BOOTSTRAP_MAX_COLUMNS."""
+    form = int(_lib.load().elimrec_bootstrap_rows_in_lds(int(n_g), int(C)))
+    if form < 0:
+        raise ValueError("elimrec_amd.ops.bootstrap_rows_in_lds: 0 <= n_g < 2^31 and 1 <= C <= %d, got n_g %d, C %d"
+                         % (_lib.load().elimrec_bootstrap_max_columns(), n_g, C))
+    return bool(form)
+
+
+def bootstrap_means(rows, group_ptr, group_rows, R, seed, out=None, rows_b=None, lds=True):
+    """elimrec_bootstrap_means: out float64 [R x G x C] on the rows' device <- R bootstrap replicates of every group's column means
+    of rows [n x C] float32 (unit column stride; a column slice of a wider block is fine) -- with rows_b (same shape, strides,
+    device) of the paired differences rows_b - rows, taken exactly in float64. Replicate r of group g draws n_g of the group's
+    listed rows with replacement: draw t is position (uint64(word) * n_g) >> 32, word = output t & 3 of Philox4x32-10 keyed by the
+    64-bit seed at counter (t >> 2, r, g, 0x626F6F74); one draw takes the whole row, so the columns share a resample. NaN for an
+    empty group. group_ptr / group_rows: the groups as group_metric_means takes them (host arrays or tensors, checked on the host at
+    every call, or a GroupIndex with group_rows = None). A block wider than BOOTSTRAP_MAX_COLUMNS goes through in column slices:
+    the same bits, the resample does not depend on the column. lds = False keeps every group on the global-memory form (the
+    default takes the LDS form where bootstrap_rows_in_lds says so; both give the same bits). No workspace, no atomics: a
+    replicate's bits depend on the seed, r, g, the group's rows in order and the values alone (csrc/bootstrap.hip)."""
+    who = "bootstrap_means"
+    for t, name in ((rows, "rows"),) + (((rows_b, "rows_b"),) if rows_b is not None else ()):
+        if not isinstance(t, torch.Tensor):
+            raise RuntimeError("elimrec_amd.ops: '%s' must be a HIP device tensor (the hot path has no CPU implementation)" % name)
+        if t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
+            raise ValueError("elimrec_amd.ops.%s: %s must be 2-D with unit column stride" % (who, name))
+        if t.dtype != torch.float32:
+            raise TypeError("elimrec_amd.ops.%s: %s must be float32, got %s" % (who, name, t.dtype))
+    n, C = rows.shape
+    if rows_b is not None and (rows_b.shape != rows.shape or rows_b.stride(0) != rows.stride(0) or rows_b.device != rows.device):
+        raise ValueError("elimrec_amd.ops.%s: rows_b must have the shape, row stride and device of rows" % who)
+    if isinstance(R, bool) or not isinstance(R, (int, np.integer)) or not 1 <= R < 2 ** 31:
+        raise ValueError("elimrec_amd.ops.%s: R must be an integer in [1, 2^31), got %r" % (who, R))
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= seed < 2 ** 64:
+        raise ValueError("elimrec_amd.ops.%s: seed must be an integer in [0, 2^64), got %r" % (who, seed))
+    if C < 1 or n >= 2 ** 31:
+        raise ValueError("elimrec_amd.ops.%s: rows needs at least one column and fewer than 2^31 rows, got [%d x %d]" % (who, n, C))
+    index = _group_index_for(who, rows, group_ptr, group_rows)
+    G, R = index.n_groups, int(R)
+    if out is None:
+        if not rows.is_cuda:
+            raise RuntimeError("elimrec_amd.ops: 'rows' must be a HIP device tensor (the hot path has no CPU implementation)")
+        out = torch.empty(R, G, C, dtype=torch.float64, device=rows.device)
+    elif not (isinstance(out, torch.Tensor) and out.is_contiguous() and tuple(out.shape) == (R, G, C) and out.dtype == torch.float64
+              and out.device == rows.device):
+        raise ValueError("elimrec_amd.ops.%s: out must be a contiguous float64 [%d x %d x %d] tensor on the rows' device" % (who, R, G, C))
+    lib = _lib.load()
+    rp, bp, op = _dev(rows, "rows"), _dev(rows_b, "rows_b"), _dev(out, "out", torch.float64)
+    ld = int(rows.stride(0)) if n > 1 else C
+    if ld < C:
+        raise ValueError("elimrec_amd.ops.%s: rows must be 2-D with unit column stride and rows that do not overlap" % who)
+    step = int(lib.elimrec_bootstrap_max_columns())
+    for c0 in range(0, C, step):
+        _lib.check(lib.elimrec_bootstrap_means(rp + 4 * c0, bp + 4 * c0 if bp is not None else None, n, min(step, C - c0), ld,
+                                               _dev(index.ptr, "group_ptr", torch.int64), _dev(index.rows, "group_rows", torch.int32),
+                                               index.n_listed, G, R, int(seed), op + 8 * c0, C, 1 if lds else 0, _stream()), who)
     return out
 
 
@@ -934,6 +1001,10 @@ def __getattr__(name):
         return int(_lib.load().elimrec_list_pair_cosine_small_k())
     if name == "HISTORY_MAX_TOP":        # entries of a history history_support names per target
         return int(_lib.load().elimrec_history_max_top())
+    if name == "BOOTSTRAP_MAX_COLUMNS":  # columns one bootstrap_means launch takes (wider blocks go through in slices)
+        return int(_lib.load().elimrec_bootstrap_max_columns())
+    if name == "BOOTSTRAP_TILE":         # replicates one workgroup of bootstrap_means serves
+        return int(_lib.load().elimrec_bootstrap_replicate_tile())
     if name == "MMR_MAX_POOL":           # positions of a pool mmr_rerank takes (one thread each)
         return int(_lib.load().elimrec_mmr_max_pool())
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

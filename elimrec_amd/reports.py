@@ -1,6 +1,7 @@
 """The reports over the cached tables -- what the lists are made of (EffectReport), where the held-out items stand (RankReport),
 whose neighbourhood the fused space copies (NeighbourReport), the lists themselves (ListReport), what diversifying them costs and
-buys (DiversifyReport), which items of a user's history back them (HistoryReport) -- and what they share: the user /
+buys (DiversifyReport), which items of a user's history back them (HistoryReport), how sure the evaluation metrics are
+(SignificanceReport) -- and what they share: the user /
 item groups, the groups as a checked index on the device, the group means, the table format, the model preflight and the block-wise
 top-K lists. The rows come from the model's *_device readers (model.py), the means from ops.group_metric_means."""
 import collections
@@ -736,3 +737,131 @@ class HistoryReport(_Report):
         self.shift_columns = tuple("d_" + c for c in self.columns)
         final = self._table(rows_b - rows_a)
         return final, format_table(self.shift_columns, self.group_labels, final)
+
+
+BootstrapSummary = collections.namedtuple("BootstrapSummary", ("mean", "se", "lo", "hi", "p"))
+
+
+def bootstrap_summary(reps, point, level=0.95):
+    """Bootstrap replicates float64 [R x G x C] (ops.bootstrap_means) and the point estimates [G x C] -> BootstrapSummary of
+    [G x C] arrays: mean = the point estimate as passed in; se = the replicates' standard deviation (ddof = 1; NaN when R = 1);
+    lo, hi = the percentile interval, np.quantile at (1 - level) / 2 and 1 - (1 - level) / 2 with linear interpolation;
+    p = min(1, 2 min((#{rep <= 0} + 1) / (R + 1), (#{rep >= 0} + 1) / (R + 1))), the two-sided bootstrap p-value of "the mean is 0"
+    (it only means something for differences). An entry with a NaN replicate is NaN in all five. Pure numpy, float64."""
+    if isinstance(level, bool) or not isinstance(level, (int, float, np.integer, np.floating)) or not 0.0 < float(level) < 1.0:
+        raise ValueError("level must be a number in (0, 1), got %r" % (level,))
+    reps = np.asarray(reps, dtype=np.float64)
+    if reps.ndim != 3 or reps.shape[0] < 1:
+        raise ValueError("reps must be [R x G x C] with R >= 1, got shape %r" % (reps.shape,))
+    R = reps.shape[0]
+    mean = np.array(point, dtype=np.float64)
+    if mean.shape != reps.shape[1:]:
+        raise ValueError("point must be [G x C] = %r, got shape %r" % (reps.shape[1:], mean.shape))
+    bad = np.isnan(reps).any(axis=0)
+    clean = np.where(bad[None], 0.0, reps)
+    tail = (1.0 - float(level)) / 2.0
+    se = np.std(clean, axis=0, ddof=1) if R > 1 else np.full(mean.shape, np.nan)
+    lo = np.quantile(clean, tail, axis=0)
+    hi = np.quantile(clean, 1.0 - tail, axis=0)
+    below, above = (clean <= 0).sum(axis=0), (clean >= 0).sum(axis=0)
+    p = np.minimum(1.0, 2.0 * np.minimum(below + 1.0, above + 1.0) / (R + 1.0))
+    return BootstrapSummary(*(np.where(bad, np.nan, x) for x in (mean, se, lo, hi, p)))
+
+
+SignificanceTables = collections.namedtuple("SignificanceTables", ("columns", "labels", "mean", "se", "lo", "hi", "p"), defaults=(None,))
+
+
+class SignificanceReport(_Report):
+    """How sure the evaluation metrics are (--significance_report=R): a non-parametric bootstrap over the test users of the
+    evaluator's own per-user metric rows. metric_rows() runs the evaluator's scoring pass under the model's current predict type
+    (UniEvaluator.metric_rows over default_users(), so every form of that pass applies) and compacts the rows to the shown columns
+    (top_show) on the device; ops.bootstrap_means (csrc/bootstrap.hip) resamples the users of every group -- all users, then the
+    group_view groups of assign_user_groups, as GroupedEvaluator splits them -- `replicates` times in ONE launch, one resample per
+    (replicate, group) shared by all columns, and only the [replicates x groups x columns] float64 means reach the host, where
+    bootstrap_summary turns them into the standard error and the percentile interval at `level`. shift() does the same for the
+    paired differences b - a of two passes (e.g. TE -> TIE; one launch, the difference taken in float64 per user) and adds the
+    two-sided bootstrap p-value of "no difference". The point estimates: row `all:` is UniEvaluator's own float32 mean of the rows,
+    the groups' are ops.group_metric_means -- the numbers the [TEST] lines and the group_view table print.
+    The report needs metric rows only, so unlike the other reports it does not ask for whole tables on one rank; it has been run
+    on one GPU only."""
+
+    name, needs = "significance", "predict_device"
+
+    def __init__(self, dataset, user_train_dict, user_test_dict, top_k, metric=None, group_view=None, replicates=2000, level=0.95,
+                 seed=2022, evaluator=None):
+        from .evaluator import UniEvaluator, re_metric_dict
+        if not isinstance(user_train_dict, dict) or not isinstance(user_test_dict, dict):
+            raise TypeError("user_train_dict and user_test_dict must be dicts")
+        if isinstance(replicates, bool) or not isinstance(replicates, (int, np.integer)) or not 1 <= replicates < 2 ** 31:
+            raise ValueError("replicates must be an integer in [1, 2^31), got %r" % (replicates,))
+        if isinstance(level, bool) or not isinstance(level, (int, float, np.integer, np.floating)) or not 0.0 < float(level) < 1.0:
+            raise ValueError("level must be a number in (0, 1), got %r" % (level,))
+        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= seed < 2 ** 64:
+            raise ValueError("seed must be an integer in [0, 2^64), got %r" % (seed,))
+        if evaluator is None:
+            evaluator = UniEvaluator(dataset, user_train_dict, user_test_dict, metric=metric, top_k=top_k)
+        elif not isinstance(evaluator, UniEvaluator):
+            raise TypeError("evaluator must be a UniEvaluator")
+        self.dataset = dataset
+        self.evaluator = ev = evaluator
+        self.user_pos_train = user_train_dict
+        self.user_pos_test = user_test_dict
+        self.replicates, self.level, self.seed = int(replicates), float(level), int(seed)
+        self.users = ev.default_users()
+        self.columns = tuple("%s@%d" % (re_metric_dict[m], k) for m in ev.metrics for k in ev.top_show)
+        # the shown columns of the [users x metrics*K] block, in metrics_info()'s order
+        self._shown = (np.arange(ev.metrics_num, dtype=np.int64)[:, None] * ev.max_top + (np.asarray(ev.top_show, dtype=np.int64) - 1)[None, :]).reshape(-1)
+        self.group_labels, self._positions = self._user_groups(self.users, user_train_dict, group_view)
+
+    def _make_resident(self, device):
+        """The user group index and the shown columns' indices resident on the device."""
+        return dict(groups=group_index(self._positions, len(self.users), device), shown=torch.from_numpy(self._shown).to(device))
+
+    def metric_rows(self, model):
+        """The test users' metric rows under the model's current predict type, compacted to the shown columns on the device:
+        ([users x Cs] float32 contiguous, column names like "Recall@10"). One evaluator scoring pass."""
+        ev = self.evaluator
+        rows = ev._rows_of(model, self.users, None)
+        return rows.index_select(1, self._resident(rows.device)["shown"]), self.columns
+
+    def _rows(self, rows, what):
+        rows = rows[0] if isinstance(rows, tuple) else rows
+        if not isinstance(rows, torch.Tensor) or tuple(rows.shape) != (len(self.users), len(self.columns)):
+            raise ValueError("%s takes the rows of this report's metric_rows(): [%d x %d]" % (what, len(self.users), len(self.columns)))
+        return rows
+
+    def _tables(self, summary, with_p):
+        names = ("mean", "se", "lo", "hi") + (("p",) if with_p else ())
+        labels = [("%s %s" % (label.strip(), name)).ljust(20) for label in self.group_labels for name in names]
+        table = np.stack([np.asarray(getattr(summary, name), dtype=np.float64) for name in names], axis=1).reshape(len(labels), -1)
+        final = SignificanceTables(self.columns, list(self.group_labels), summary.mean, summary.se, summary.lo, summary.hi,
+                                   summary.p if with_p else None)
+        return final, format_table(self.columns, labels, table)
+
+    def evaluate(self, model, rows=None):
+        """(SignificanceTables(columns, labels, mean float32, se, lo, hi float64 [1 + groups x Cs]), buf): per group -- row 0 = all
+        test users -- the point estimate, the bootstrap standard error and the percentile interval at `level` of every shown
+        metric. buf: a header of column names and one "%.8f" line per (group, statistic): "all: mean", "all: se", "all: lo",
+        "all: hi", ... rows: metric_rows(model) if the caller already holds it."""
+        rows = self._rows(self.metric_rows(model) if rows is None else rows, "evaluate()")
+        res = self._resident(rows.device)
+        reps = ops.bootstrap_means(rows, res["groups"], None, self.replicates, self.seed).cpu().numpy()
+        point = group_table(rows, res["groups"], len(self.group_labels))
+        point[0] = np.mean(rows.cpu().numpy(), axis=0)                     # UniEvaluator._summary's expression: the [TEST] line's bits
+        s = bootstrap_summary(reps, point, self.level)
+        return self._tables(s._replace(mean=point), False)
+
+    def shift(self, rows_a, rows_b):
+        """How the metrics move from pass a to pass b (e.g. TE -> TIE), paired per user: (SignificanceTables(..., p), buf) over the
+        differences b - a -- mean = ops.group_metric_means of the float32 difference rows, se / lo / hi from ONE launch over both
+        blocks (the difference of a drawn user taken in float64), p = the two-sided bootstrap p-value of "the mean difference is 0".
+        rows_a / rows_b: two metric_rows() results of this report on one device."""
+        a, b = self._rows(rows_a, "shift()"), self._rows(rows_b, "shift()")
+        if a.device != b.device:
+            raise ValueError("shift() takes two metric_rows() results of this report on one device")
+        res = self._resident(a.device)
+        a, b = a.contiguous(), b.contiguous()                              # (one row stride for both blocks)
+        reps = ops.bootstrap_means(a, res["groups"], None, self.replicates, self.seed, rows_b=b).cpu().numpy()
+        point = group_table(b - a, res["groups"], len(self.group_labels))
+        s = bootstrap_summary(reps, point, self.level)
+        return self._tables(s._replace(mean=point), True)

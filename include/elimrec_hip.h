@@ -734,6 +734,36 @@ int elimrec_history_support(const float *d_T, int64_t ld, int64_t n_items, int b
                             int32_t *d_out_idx, float *d_out_val, int32_t *d_out_cnt, float *d_out_mean, void *stream);
 int elimrec_history_max_top(void);
 
+/* Bootstrap of group means (csrc/bootstrap.hip): a paired, per-group, non-parametric bootstrap of a block of per-row values. No
+ * counterpart in the reference. d_rows float32 [n_rows x C], row stride ld >= C (a column slice of a wider block is fine, no
+ * alignment is asked); d_rows_b: nullable, the same shape and ld. The groups as CSR, as elimrec_group_metric_means takes them:
+ * d_group_ptr int64 [G + 1] (ptr[0] = 0, ascending, ptr[G] = n_listed_rows), d_group_rows int32 [n_listed_rows] row indices; a row
+ * may sit in several groups or several times in one. d_out float64 [R x G x C], row stride ld_out >= C between two (r, g).
+ * Replicate r of group g with n_g = ptr[g + 1] - ptr[g] listed rows makes the draws t = 0 .. n_g - 1:
+ *     word = output word (t & 3) of Philox4x32-10 with key (seed & 0xffffffff, seed >> 32) and counter (t >> 2, r, g, 0x626F6F74);
+ *     j = (uint64(word) * n_g) >> 32;   the drawn row is i = group_rows[ptr[g] + j].
+ * The mapping is deterministic and not exactly uniform: a position is drawn with probability floor or ceil of 2^32 / n_g over
+ * 2^32, so its bias is at most n_g / 2^32 relative (7.3e-6 at n_g = 31 504). One draw takes the whole row: all C columns of a
+ * replicate share one resample (the columns stay paired, and so do d_rows and d_rows_b). The value of an entry is
+ * (double)rows[i, c], with d_rows_b (double)rows_b[i, c] - (double)rows[i, c] -- the exact paired difference -- and NaN for an
+ * index outside [0, n_rows), which is never dereferenced. out[r, g, c] = the float64 sum of the n_g drawn values / n_g; NaN for
+ * an empty group (and for a segment that does not lie in [0, n_listed_rows]).
+ * 16 lanes per replicate, 16 replicates (elimrec_bootstrap_replicate_tile()) per workgroup: lane s adds the draws of the Philox
+ * calls s, s + 16, ... in ascending t, the 16 partials are added in a fixed tree. The summation order is a function of n_g alone;
+ * no atomics, NO WORKSPACE (hence no _workspace call). The bits of out[r, g, :] depend on the seed, r, g, the group's listed rows
+ * in order and the values only -- not on R, the other groups, C, ld, the column's place in a slice, the grid, timing or the form:
+ * with use_lds = 1 a group with elimrec_bootstrap_rows_in_lds(n_g, C) (n_g * C <= 8192) is staged once per workgroup into 64 KiB
+ * of LDS and resampled from there (a launch of its own), the other groups gather from global memory; use_lds = 0 takes the
+ * global form for every group. 1 <= R < 2^31, 1 <= C <= elimrec_bootstrap_max_columns() = 16 (wider blocks: call per column
+ * slice, the resample does not depend on the column), n_rows, n_listed_rows < 2^31, G >= 1, ceil(R / 16) * G < 2^31 - 1.
+ * elimrec_bootstrap_rows_in_lds: 1 / 0, -1 outside 0 <= n_g < 2^31, 1 <= C <= 16. One or two launches on `stream`. */
+int elimrec_bootstrap_means(const float *d_rows, const float *d_rows_b, int64_t n_rows, int C, int64_t ld,
+                            const int64_t *d_group_ptr, const int32_t *d_group_rows, int64_t n_listed_rows, int G,
+                            int64_t R, uint64_t seed, double *d_out, int64_t ld_out, int use_lds, void *stream);
+int elimrec_bootstrap_max_columns(void);
+int elimrec_bootstrap_replicate_tile(void);
+int elimrec_bootstrap_rows_in_lds(int64_t n_g, int C);
+
 /* ---------------------------------------------------------------- pairwise sampler (K20)
  * n triplets: user uniform over the `n_train_users` users with >= 1 training item (with
  * replacement), positive uniform over that user's training items, negative uniform over [0,I)

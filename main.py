@@ -6,7 +6,7 @@
 Behaviour kept from the reference's `Net.run`: one pass of the pairwise sampler per epoch, validation every
 `test_step` epochs with predict_type TIE, a checkpoint + TE/TIE test pass whenever validation recall improves
 (not on epoch 0), early stop after `stop_cnt` epochs without improvement, the same log lines (`--group_view=[10,30,50,100]` adds
-the per-user-group table under each test line, `--effect_report=K` the effect breakdown of the top-K lists, `--rank_report=1` the test items' exact catalogue ranks, `--neighbour_report=K` the items' cosine neighbourhoods, fused against single-modal, `--list_report=K` the top-K lists' intra-list similarity and catalogue exposure, `--diversify_report=K` the top-N pools re-ranked to K items by greedy MMR per lambda, `--history_report=K` which items of the users' training histories back the top-K lists (`--history_top=T` named per pair), `--neg_sampling=hard` trains on the best of `--neg_candidates=M` uniform negatives per triplet under the last forward's tables; validation and model selection stay on the overall metrics). The per-batch work,
+the per-user-group table under each test line, `--effect_report=K` the effect breakdown of the top-K lists, `--rank_report=1` the test items' exact catalogue ranks, `--neighbour_report=K` the items' cosine neighbourhoods, fused against single-modal, `--list_report=K` the top-K lists' intra-list similarity and catalogue exposure, `--diversify_report=K` the top-N pools re-ranked to K items by greedy MMR per lambda, `--history_report=K` which items of the users' training histories back the top-K lists (`--history_top=T` named per pair), `--significance_report=R` bootstrap intervals of the test metrics over the test users and the paired TE->TIE difference with its p-value, `--neg_sampling=hard` trains on the best of `--neg_candidates=M` uniform negatives per triplet under the last forward's tables; validation and model selection stay on the overall metrics). The per-batch work,
 the sampler and the evaluator run on the GPU (elimrec_amd). `--data.input.dataset=synthetic` uses the seeded
 Tiktok-shape generator instead of reading files.
 
@@ -129,6 +129,10 @@ class Net(object):
         self.history_report = int(cfg["history_report"]) if "history_report" in cfg else 0
         if self.history_report and self.world > 1:
             raise ValueError("--history_report needs the whole cached item table on one rank: it is single-GPU")
+        # --significance_report=R (default 0: off): under each [TEST] line the bootstrap standard error and percentile interval
+        # (--significance_level) of every shown metric over R resamples of the test users, overall and per user group; after both
+        # effects the paired TE -> TIE difference with its two-sided p-value. It needs metric rows only (run on one GPU only so far)
+        self.significance_report = int(cfg["significance_report"]) if "significance_report" in cfg else 0
         Logger.info(count_parameters(self.recommender))
         self.opt = FusedAdam(self.recommender.parameters(), lr=cfg.lr, weight_decay=cfg.weight_decay)
         self.loss_name = str(cfg.loss)
@@ -253,7 +257,7 @@ class Net(object):
 
     def test_all_effects(self):
         """TE and TIE metrics on the test split, formatted as the reference prints them."""
-        rec, lines, ranks, shown, backed = self.recommender, {}, {}, {}, {}
+        rec, lines, ranks, shown, backed, sure = self.recommender, {}, {}, {}, {}, {}
         if self.grouped:
             Logger.info(rec.test_evaluator.metrics_info())
         for effect in EFFECTS:
@@ -281,6 +285,11 @@ class Net(object):
                 backed[effect] = rec.history_reporter.history_rows(rec)
                 Logger.info("  [{}] support of the top-{} lists in the users' histories:\n{}".format(
                     effect, self.history_report, rec.history_reporter.evaluate(rec, backed[effect])[1]))
+            if self.significance_report:   # how far the metrics of this effect move under resampling of the test users
+                reporter = rec.significance_reporter
+                sure[effect] = reporter.metric_rows(rec)
+                Logger.info("  [{}] metric intervals ({} replicates, {:g} %):\n{}".format(
+                    effect, reporter.replicates, 100.0 * reporter.level, reporter.evaluate(rec, sure[effect])[1]))
         if self.rank_report:               # positive delta: TIE ranks the test item higher than TE does
             Logger.info("  [TE->TIE] rank shift of the test items:\n{}".format(rec.rank_reporter.shift(ranks["TE"], ranks["TIE"])[1]))
         if self.list_report:               # overlap: the share of the TE list that TIE keeps; d_<column>: TIE - TE
@@ -288,6 +297,9 @@ class Net(object):
             Logger.info("  [TE->TIE] list shift:\n{}".format(rec.list_reporter.shift(a[0], a[2], b[0], b[2])[1]))
         if self.history_report:            # d_<column>: TIE - TE; a positive d_unexpected_<space>: TIE strays further from the history
             Logger.info("  [TE->TIE] history support shift:\n{}".format(rec.history_reporter.shift(backed["TE"], backed["TIE"])[1]))
+        if self.significance_report:       # TIE - TE per user, the users resampled as pairs; p: two-sided, "no difference"
+            Logger.info("  [TE->TIE] metric difference, paired bootstrap:\n{}".format(
+                rec.significance_reporter.shift(sure["TE"], sure["TIE"])[1]))
         if self.neighbour_report:
             Logger.info("  [neighbours] top-{} cosine neighbours of every item, fused space against the heads:\n{}".format(
                 self.neighbour_report, rec.neighbour_reporter.evaluate(rec)[1]))
