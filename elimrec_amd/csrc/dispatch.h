@@ -37,6 +37,19 @@ template <int MIN, class F> int with_pow2(const char *who, int v, F f) {
     return ELIMREC_E_BADARG;
 }
 
+// The 16-lane group kernels' width (cosine.h): f(int_c<NQ>{}) for NQ = ceil(d / 64) float4s per lane, 1 <= NQ <= 4 (4 <= d <= 256).
+// Any other d: set_error + ELIMREC_E_BADARG, f not called -- the entry points check d first (table_dims), so that arm is not reached.
+template <class F> int with_quads(const char *who, int d, F f) {
+    switch (d >= 4 ? (d + 63) / 64 : 0) {
+    case 1: return f(int_c<1>{});
+    case 2: return f(int_c<2>{});
+    case 3: return f(int_c<3>{});
+    case 4: return f(int_c<4>{});
+    }
+    set_error("%s: d = %d is outside [4, 256]", who, d);
+    return ELIMREC_E_BADARG;
+}
+
 template <auto KERNEL> void allow_lds(size_t bytes) {      // beyond 64 KiB of dynamic LDS: once per kernel instantiation
     static bool done = false;
     if (!done) { ELIMREC_RAISE_LDS_LIMIT(KERNEL, bytes); done = true; }

@@ -4,15 +4,14 @@
 // owns ONE target (four targets per wave, 16 per workgroup). The score of history entry j against target i is
 //     sum over the blocks b with w_b != 0, in block order, of  w_b * cos_b(j, i),
 //     cos_b(j, i) = ((T_b[i] . T_b[j]) * inv(sq[i, b])) * inv(sq[j, b]),   inv(x) = 1 / max(sqrt(x), 1e-12)   (cosine.h's inv_norm)
-// -- hardneg.hip's expression, the target in the place of its user row, the history entry in the place of its candidate.
+// -- hardneg.hip's expression, the target in the place of its user row, the history entry in the place of its candidate: both
+// kernels form the dot product with cosine.h's group dot, whose summation order (fixed by d alone) is stated there.
 // The user's segment is walked ONCE per tile, in chunks of C = 64 / 32 / 16 / 16 entries (d <= 64 / 128 / 192 / 256: 16 KiB of rows
 // at most): per chunk the ids are checked and staged (an id outside [0, n_items) becomes -1 and is never dereferenced), then per
 // active block the workgroup gathers the chunk's rows of that block into LDS -- each row read from global memory once for all 16
-// targets -- with their inv norms; every group reloads its target's block into registers (lane g the float4s q = g, g + 16, ...:
-// 16 rows per workgroup, cache hits after the first chunk) and walks the chunk: lane g runs four fmaf chains over its float4s of
-// the LDS row in ascending q, folds them as (a0 + a1) + (a2 + a3), a 16-lane xor butterfly (8, 4, 2, 1) adds the lanes' sums -- the
-// order is fixed by d alone --, and the lane that owns the entry (entry e of the chunk: lane e % 16, register e / 16) adds
-// w_b * cos to the entry's running score. After the last block the group takes the chunk's entries in segment order: a listed one
+// targets -- with their inv norms; every group reloads its target's block into registers (ELIMREC_GROUP16_LOAD: 16 rows per workgroup,
+// cache hits after the first chunk) and walks the chunk: the group dot against the LDS row, and the lane that owns the entry
+// (entry e of the chunk: lane e % 16, register e / 16) adds w_b * cos to the entry's running score. After the last block the group takes the chunk's entries in segment order: a listed one
 // (staged id >= 0 and, with exclude_self, != the target) is counted, its score added to a float64 sum, and inserted into the
 // group's running top list when it beats the list's `top`-th value. The list lives in registers, slot g in lane g, descending;
 // an entry goes behind every slot with a value >= its own (the earlier position wins a tie), the slots behind it shift by one lane.
@@ -22,24 +21,25 @@
 #include <cmath>
 #include "common.h"
 #include "cosine.h"
+#include "dispatch.h"
 
 namespace elimrec {
 
-constexpr int HS_MAXK = 256, HS_MAXTOP = 16, HS_MAXD = 256, HS_MAXBLOCKS = 8;
-constexpr int HS_GROUP = 16;                                 // lanes per target
+constexpr int HS_MAXK = 256, HS_MAXTOP = 16;
+constexpr int HS_GROUP = GROUP16;                            // lanes per target
 constexpr int HS_THREADS = 256;
 constexpr int HS_TILE = HS_THREADS / HS_GROUP;               // targets per workgroup
 constexpr int HS_ROW_FLOATS = 4096;                          // LDS floats of a chunk's rows (16 KiB)
 
 struct HistoryArgs {
-    const float *T; int64_t ld, n_items; const float *sq; int64_t ld_sq;
-    float w[HS_MAXBLOCKS];
-    int blocks, d;
+    TableView t;
+    BlockWeights w;
+    int d;
     const int64_t *users; const int32_t *lists; int64_t B; int K;
     const int64_t *hist_ptr; const int32_t *hist_items; int64_t n_hist_rows;
     int top, exclude_self, tiles;
     int32_t *out_idx; float *out_val; int32_t *out_cnt; float *out_mean;
-    int vec;                             // the table is 16-byte aligned and its ld % 4 == 0 -> a row's float4s are single loads
+    int vec;                             // cosine.h's table_vec of the table
 };
 
 template <int NQ>
@@ -52,6 +52,7 @@ __global__ __launch_bounds__(HS_THREADS) void history_support_kernel(HistoryArgs
     const int tid = threadIdx.x, g = tid & (HS_GROUP - 1), grp = tid / HS_GROUP;
     const int64_t row = (int64_t)blockIdx.x / a.tiles;
     const int k = ((int)(blockIdx.x % a.tiles)) * HS_TILE + grp;
+    const TableView &T = a.t;
     const int d = a.d, nq = d >> 2, top = a.top;
     const bool have = k < a.K;                                // (group-uniform)
     const int64_t u = a.users[row];
@@ -59,7 +60,7 @@ __global__ __launch_bounds__(HS_THREADS) void history_support_kernel(HistoryArgs
     int tgt = -1;
     if (have && user_ok) {
         const int32_t t = a.lists[row * a.K + k];
-        if (t >= 0 && (int64_t)t < a.n_items) tgt = t;
+        if (t >= 0 && (int64_t)t < T.n_rows) tgt = t;
     }
     float val = -INFINITY, thr = -INFINITY;                   // slot g of the group's top list; the list's top-th value
     int vid = -1, nf = 0, cnt = 0;
@@ -73,7 +74,7 @@ __global__ __launch_bounds__(HS_THREADS) void history_support_kernel(HistoryArgs
                 int id = -1;
                 if (tid < cn) {
                     const int32_t h = a.hist_items[base + tid];
-                    if (h >= 0 && (int64_t)h < a.n_items) id = h;
+                    if (h >= 0 && (int64_t)h < T.n_rows) id = h;
                 }
                 s_id[tid] = id;
             }
@@ -81,32 +82,26 @@ __global__ __launch_bounds__(HS_THREADS) void history_support_kernel(HistoryArgs
             float part[NP];
 #pragma unroll
             for (int p = 0; p < NP; ++p) part[p] = 0.f;
-            for (int b = 0; b < a.blocks; ++b) {
-                const float w = a.w[b];
+            for (int b = 0; b < a.w.blocks; ++b) {
+                const float w = a.w.w[b];
                 if (w == 0.f) continue;                       // a block with zero weight is not read
                 for (int x = tid; x < cn * nq; x += HS_THREADS) {
                     const int e = x / nq, q = x - e * nq, id = s_id[e];
                     if (id >= 0) {
                         float4 y;
-                        ELIMREC_LOAD_ROW4(y, a.T + (int64_t)id * a.ld + (int64_t)b * d + 4 * q, a.vec);
+                        ELIMREC_LOAD_ROW4(y, T.T + (int64_t)id * T.ld + (int64_t)b * d + 4 * q, a.vec);
                         *reinterpret_cast<float4 *>(s_rows + e * d + 4 * q) = y;
                     }
                 }
                 if (tid < cn) {
                     const int id = s_id[tid];
-                    s_inv[tid] = id >= 0 ? inv_norm(a.sq[(int64_t)id * a.ld_sq + b]) : 0.f;
+                    s_inv[tid] = id >= 0 ? inv_norm(T.sq[(int64_t)id * T.ld_sq + b]) : 0.f;
                 }
                 __syncthreads();
                 if (tgt >= 0) {
                     float4 x[NQ];
-                    const float *trow = a.T + (int64_t)tgt * a.ld + (int64_t)b * d;
-#pragma unroll
-                    for (int s = 0; s < NQ; ++s) {
-                        const int q = g + s * HS_GROUP;
-                        x[s] = make_float4(0.f, 0.f, 0.f, 0.f);
-                        if (q < nq) ELIMREC_LOAD_ROW4(x[s], trow + 4 * q, a.vec);
-                    }
-                    const float it = inv_norm(a.sq[(int64_t)tgt * a.ld_sq + b]);
+                    ELIMREC_GROUP16_LOAD(x, NQ, T.T + (int64_t)tgt * T.ld + (int64_t)b * d, g, nq, a.vec);
+                    const float it = inv_norm(T.sq[(int64_t)tgt * T.ld_sq + b]);
 #pragma unroll
                     for (int p = 0; p < NP; ++p) {
                         const int lim = min(HS_GROUP, cn - p * HS_GROUP);         // (workgroup-uniform)
@@ -114,19 +109,8 @@ __global__ __launch_bounds__(HS_THREADS) void history_support_kernel(HistoryArgs
                             const int e = p * HS_GROUP + jj;
                             if (s_id[e] < 0) continue;                            // (workgroup-uniform) its row was not staged
                             const float *hrow = s_rows + e * d;
-                            float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-#pragma unroll
-                            for (int s = 0; s < NQ; ++s) {
-                                const int q = g + s * HS_GROUP;
-                                if (q < nq) {
-                                    const float4 y = *reinterpret_cast<const float4 *>(hrow + 4 * q);
-                                    a0 = fmaf(x[s].x, y.x, a0); a1 = fmaf(x[s].y, y.y, a1);
-                                    a2 = fmaf(x[s].z, y.z, a2); a3 = fmaf(x[s].w, y.w, a3);
-                                }
-                            }
-                            float dot = (a0 + a1) + (a2 + a3);
-#pragma unroll
-                            for (int m = HS_GROUP / 2; m >= 1; m >>= 1) dot += __shfl_xor(dot, m, HS_GROUP);
+                            float dot;
+                            ELIMREC_GROUP16_DOT(dot, x, NQ, g, nq, y = *reinterpret_cast<const float4 *>(hrow + 4 * q));
                             const float cosv = (dot * it) * s_inv[e];
                             if (g == jj) part[p] = part[p] + w * cosv;
                         }
@@ -175,13 +159,6 @@ __global__ __launch_bounds__(HS_THREADS) void history_support_kernel(HistoryArgs
 
 using namespace elimrec;
 
-template <int NQ>
-static int hs_launch(const HistoryArgs &a, hipStream_t s) {
-    hipLaunchKernelGGL((history_support_kernel<NQ>), dim3((unsigned)(a.B * a.tiles)), dim3(HS_THREADS), 0, s, a);
-    ELIMREC_LAUNCH_CHECK("history_support");
-    return 0;
-}
-
 extern "C" int elimrec_history_max_top(void) { return HS_MAXTOP; }
 
 extern "C" int elimrec_history_support(const float *d_T, int64_t ld, int64_t n_items, int blocks, int d, const float *d_sqnorm,
@@ -189,29 +166,30 @@ extern "C" int elimrec_history_support(const float *d_T, int64_t ld, int64_t n_i
                                        int64_t B, int K, const int64_t *d_hist_ptr, const int32_t *d_hist_items, int64_t n_hist_rows,
                                        int top, int exclude_self, int32_t *d_out_idx, float *d_out_val, int32_t *d_out_cnt,
                                        float *d_out_mean, void *stream) {
+    const char *who = "history_support";
     ELIMREC_REQUIRE(K >= 1 && K <= HS_MAXK, "history_support: 1 <= K <= %d, got %d", HS_MAXK, K);
     ELIMREC_REQUIRE(top >= 1 && top <= HS_MAXTOP, "history_support: 1 <= top <= %d, got %d", HS_MAXTOP, top);
-    ELIMREC_REQUIRE(d >= 4 && d <= HS_MAXD && d % 4 == 0, "history_support: d %% 4 == 0 and 4 <= d <= %d, got %d", HS_MAXD, d);
-    ELIMREC_REQUIRE(blocks >= 1 && blocks <= HS_MAXBLOCKS, "history_support: 1 <= blocks <= %d, got %d", HS_MAXBLOCKS, blocks);
+    if (int rc = table_dims(who, d, blocks)) return rc;
     const int tiles = (K + HS_TILE - 1) / HS_TILE;
     ELIMREC_REQUIRE(B >= 0 && B * tiles < (int64_t)INT32_MAX && n_hist_rows >= 0 && n_items >= 0 && n_items < (int64_t)INT32_MAX,
                     "history_support: need 0 <= B, B * ceil(K / %d) < 2^31 - 1, n_hist_rows >= 0 and 0 <= n_items < 2^31 - 1", HS_TILE);
     ELIMREC_REQUIRE(ld >= (int64_t)blocks * d && ld_sq >= blocks, "history_support: the row stride < blocks * d, or the norm stride < blocks");
     ELIMREC_REQUIRE(exclude_self == 0 || exclude_self == 1, "history_support: exclude_self is 0 or 1, got %d", exclude_self);
     if (B == 0) return 0;
-    ELIMREC_REQUIRE(h_weights, "history_support: null weights");
+    HistoryArgs a{};
+    if (int rc = load_weights(who, h_weights, blocks, &a.w)) return rc;
     ELIMREC_REQUIRE(d_users && d_lists && d_out_idx && d_out_val, "history_support: null pointer");
     ELIMREC_REQUIRE(n_hist_rows == 0 || d_hist_ptr, "history_support: null pointer");
-    ELIMREC_REQUIRE(n_items == 0 || (d_T && d_sqnorm), "history_support: null pointer");
-    HistoryArgs a{d_T, ld, n_items, d_sqnorm, ld_sq, {}, blocks, d, d_users, d_lists, B, K, d_hist_ptr, d_hist_items, n_hist_rows,
-                  top, exclude_self, tiles, d_out_idx, d_out_val, d_out_cnt, d_out_mean,
-                  (reinterpret_cast<uintptr_t>(d_T) % 16 == 0 && ld % 4 == 0) ? 1 : 0};
-    for (int b = 0; b < blocks; ++b) a.w[b] = h_weights[b];
-    hipStream_t s = (hipStream_t)stream;
-    switch ((d + 63) / 64) {
-        case 1: return hs_launch<1>(a, s);
-        case 2: return hs_launch<2>(a, s);
-        case 3: return hs_launch<3>(a, s);
-        default: return hs_launch<4>(a, s);
-    }
+    if (int rc = table_view(who, d_T, ld, n_items, d_sqnorm, ld_sq, &a.t, &a.vec)) return rc;
+    a.d = d;
+    a.users = d_users; a.lists = d_lists; a.B = B; a.K = K;
+    a.hist_ptr = d_hist_ptr; a.hist_items = d_hist_items; a.n_hist_rows = n_hist_rows;
+    a.top = top; a.exclude_self = exclude_self; a.tiles = tiles;
+    a.out_idx = d_out_idx; a.out_val = d_out_val; a.out_cnt = d_out_cnt; a.out_mean = d_out_mean;
+    return with_quads(who, d, [&](auto nq) {
+        hipLaunchKernelGGL((history_support_kernel<decltype(nq)::value>), dim3((unsigned)(B * tiles)), dim3(HS_THREADS), 0,
+                           (hipStream_t)stream, a);
+        ELIMREC_LAUNCH_CHECK("history_support");
+        return 0;
+    });
 }

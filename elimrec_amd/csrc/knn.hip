@@ -28,7 +28,7 @@
 
 namespace elimrec {
 
-constexpr int KNN_CHUNK = 4096, KNN_TILE = 64, KNN_MAXK = 256, KNN_MAXD = 256, KNN_SLACK = 32, KNN_SMALLK = 64;
+constexpr int KNN_CHUNK = 4096, KNN_TILE = 64, KNN_MAXK = 256, KNN_SLACK = 32, KNN_SMALLK = 64;
 constexpr int KNN_OVERLAP_MAXK = 1024;
 typedef float knn_v4f __attribute__((ext_vector_type(4)));
 
@@ -83,13 +83,13 @@ __device__ __forceinline__ void knn_compact(float *lv, int *li_, int *cnt, float
     wave_lds_sync();
 }
 
-// D: 32 / 64 / 128 = the dimension at compile time, query operands in registers; 0 = any d % 4 == 0 up to KNN_MAXD.
+// D: 32 / 64 / 128 = the dimension at compile time, query operands in registers; 0 = any d % 4 == 0 up to TABLE_MAXD.
 // W: waves per workgroup (4: K <= KNN_SMALLK; 1: larger K)
 template <int D, int W>
 __global__ __launch_bounds__(64 * W) void knn_chunk_kernel(KnnArgs a) {
     constexpr int SR = knn_stage_rows(D, W), NT = 64 * W, ROWS = 16 * W;
     constexpr int E = W == 4 ? (KNN_SMALLK + KNN_SLACK + 63) / 64 : (KNN_MAXK + KNN_SLACK + 63) / 64;
-    constexpr int PFN = (SR * (D ? D : KNN_MAXD) / 4 + NT - 1) / NT;
+    constexpr int PFN = (SR * (D ? D : TABLE_MAXD) / 4 + NT - 1) / NT;
     const int d = D ? D : a.d, LD = d + 4, K = a.K, CAP = K + KNN_SLACK;
     extern __shared__ float smem[];
     float *s_b = smem;                                       // [SR][LD] the stage's candidate rows
@@ -319,7 +319,7 @@ extern "C" int elimrec_cosine_topk(const float *d_T, int64_t ld, int64_t n_rows,
                                    const int32_t *d_excl_rows, int K, int32_t *d_idx, float *d_val, void *d_workspace,
                                    size_t workspace_bytes, void *stream) {
     ELIMREC_REQUIRE(K >= 1 && K <= KNN_MAXK, "cosine_topk: 1 <= K <= %d, got %d", KNN_MAXK, K);
-    ELIMREC_REQUIRE(d >= 4 && d <= KNN_MAXD && d % 4 == 0, "cosine_topk: d %% 4 == 0 and 4 <= d <= %d, got %d", KNN_MAXD, d);
+    if (int rc = table_dims("cosine_topk", d, 1)) return rc;
     ELIMREC_REQUIRE(Q >= 0 && n_rows >= 0 && n_rows < (int64_t)INT32_MAX - KNN_CHUNK, "cosine_topk: need Q >= 0 and 0 <= n_rows < 2^31 - %d",
                     KNN_CHUNK + 1);
     ELIMREC_REQUIRE(ld >= d && ld_sq >= 1, "cosine_topk: ld < d or ld_sq < 1");
@@ -346,7 +346,7 @@ extern "C" int elimrec_cosine_topk(const float *d_T, int64_t ld, int64_t n_rows,
     a.qrows = d_query_rows; a.Q = Q; a.exclude_self = exclude_self ? 1 : 0;
     a.excl_ptr = d_excl_ptr; a.excl_rows = d_excl_rows;
     a.K = K; a.n_chunks = (int)n_chunks;
-    a.vec = (((uintptr_t)d_T & 15) == 0 && ld % 4 == 0) ? 1 : 0;
+    a.vec = table_vec(d_T, ld);
     a.ws_val = (float *)d_workspace;
     a.ws_idx = (int32_t *)((char *)d_workspace + align_up(pairs * 4, 16));
     const int rows = K <= KNN_SMALLK ? KNN_TILE : 16;

@@ -22,7 +22,7 @@
 
 namespace elimrec {
 
-constexpr int LIST_MAXK = 256, LIST_MAXD = 256, LIST_MAXBLOCKS = 8, LIST_SMALLK = 32;
+constexpr int LIST_MAXK = 256, LIST_SMALLK = 32;
 constexpr int LIST_ROW_FLOATS = 15 * 1024;                   // LDS floats for the staged rows (60 KiB)
 typedef float list_v4f __attribute__((ext_vector_type(4)));
 
@@ -145,15 +145,14 @@ using namespace elimrec;
 extern "C" int elimrec_list_max_k(void) { return LIST_MAXK; }
 extern "C" int elimrec_list_pair_cosine_small_k(void) { return LIST_SMALLK; }
 extern "C" int elimrec_list_pair_cosine_chunk_cols(int K, int d) {
-    if (K < 1 || K > LIST_MAXK || d < 4 || d > LIST_MAXD || d % 4 != 0) return 0;
+    if (K < 1 || K > LIST_MAXK || d < 4 || d > TABLE_MAXD || d % 4 != 0) return 0;
     return list_chunk_cols(16 * ((K + 15) / 16), d);
 }
 
 extern "C" int elimrec_list_pair_cosine(const float *d_T, int64_t ld, int64_t n_rows, int blocks, int d, const float *d_sqnorm,
                                         int64_t ld_sq, const int32_t *d_lists, int64_t B, int K, float *d_out, void *stream) {
     ELIMREC_REQUIRE(K >= 1 && K <= LIST_MAXK, "list_pair_cosine: 1 <= K <= %d, got %d", LIST_MAXK, K);
-    ELIMREC_REQUIRE(d >= 4 && d <= LIST_MAXD && d % 4 == 0, "list_pair_cosine: d %% 4 == 0 and 4 <= d <= %d, got %d", LIST_MAXD, d);
-    ELIMREC_REQUIRE(blocks >= 1 && blocks <= LIST_MAXBLOCKS, "list_pair_cosine: 1 <= blocks <= %d, got %d", LIST_MAXBLOCKS, blocks);
+    if (int rc = table_dims("list_pair_cosine", d, blocks)) return rc;
     ELIMREC_REQUIRE(B >= 0 && B < (int64_t)INT32_MAX && n_rows >= 0 && n_rows < (int64_t)INT32_MAX,
                     "list_pair_cosine: need 0 <= B < 2^31 - 1 and 0 <= n_rows < 2^31 - 1");
     ELIMREC_REQUIRE(ld >= (int64_t)blocks * d && ld_sq >= blocks, "list_pair_cosine: ld < blocks * d or ld_sq < blocks");
@@ -165,7 +164,7 @@ extern "C" int elimrec_list_pair_cosine(const float *d_T, int64_t ld, int64_t n_
     a.sq = d_sqnorm; a.ld_sq = ld_sq;
     a.lists = d_lists; a.K = K;
     a.out = d_out;
-    a.vec = (((uintptr_t)d_T & 15) == 0 && ld % 4 == 0) ? 1 : 0;
+    a.vec = table_vec(d_T, ld);
     a.dc = list_chunk_cols(16 * ((K + 15) / 16), d);
     hipStream_t s = (hipStream_t)stream;
     return K <= LIST_SMALLK ? list_launch<1>(a, B, s) : list_launch<4>(a, B, s);

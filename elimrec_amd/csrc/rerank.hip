@@ -27,7 +27,7 @@
 
 namespace elimrec {
 
-constexpr int MMR_MAXN = 256, MMR_MAXD = 256, MMR_SMALLN = 64;
+constexpr int MMR_MAXN = 256, MMR_SMALLN = 64;
 constexpr int MMR_ROW_FLOATS = 15 * 1024;                    // LDS floats for the staged rows (60 KiB, as lists.hip)
 constexpr int MMR_NONE = 0x7fffffff;                         // position of "no candidate"
 
@@ -179,7 +179,7 @@ using namespace elimrec;
 
 extern "C" int elimrec_mmr_max_pool(void) { return MMR_MAXN; }
 extern "C" int elimrec_mmr_rows_in_lds(int N, int d) {
-    if (N < 1 || N > MMR_MAXN || d < 4 || d > MMR_MAXD || d % 4 != 0) return -1;
+    if (N < 1 || N > MMR_MAXN || d < 4 || d > TABLE_MAXD || d % 4 != 0) return -1;
     return mmr_rows_fit(N, d) ? 1 : 0;
 }
 
@@ -187,7 +187,7 @@ extern "C" int elimrec_mmr_rerank(const float *d_T, int64_t ld, int64_t n_rows, 
                                   const int32_t *d_pool_idx, const float *d_pool_val, int64_t B, int N, int K, float lambda,
                                   int32_t *d_out_idx, int32_t *d_out_pos, float *d_out_val, void *stream) {
     ELIMREC_REQUIRE(N >= 1 && N <= MMR_MAXN && K >= 1 && K <= N, "mmr_rerank: 1 <= K <= N <= %d, got K %d, N %d", MMR_MAXN, K, N);
-    ELIMREC_REQUIRE(d >= 4 && d <= MMR_MAXD && d % 4 == 0, "mmr_rerank: d %% 4 == 0 and 4 <= d <= %d, got %d", MMR_MAXD, d);
+    if (int rc = table_dims("mmr_rerank", d, 1)) return rc;
     ELIMREC_REQUIRE(lambda >= 0.f && lambda <= 1.f, "mmr_rerank: 0 <= lambda <= 1, got %g", (double)lambda);
     ELIMREC_REQUIRE(B >= 0 && B < (int64_t)INT32_MAX && n_rows >= 0 && n_rows < (int64_t)INT32_MAX,
                     "mmr_rerank: need 0 <= B < 2^31 - 1 and 0 <= n_rows < 2^31 - 1");
@@ -201,7 +201,7 @@ extern "C" int elimrec_mmr_rerank(const float *d_T, int64_t ld, int64_t n_rows, 
     a.pool_idx = d_pool_idx; a.pool_val = d_pool_val; a.N = N; a.K = K;
     a.lambda = lambda;
     a.out_idx = d_out_idx; a.out_pos = d_out_pos; a.out_val = d_out_val;
-    a.vec = (((uintptr_t)d_T & 15) == 0 && ld % 4 == 0) ? 1 : 0;
+    a.vec = table_vec(d_T, ld);
     hipStream_t s = (hipStream_t)stream;
     return N <= MMR_SMALLN ? mmr_launch<1>(a, B, s) : mmr_launch<4>(a, B, s);
 }

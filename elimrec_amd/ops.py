@@ -1493,6 +1493,24 @@ def _block_table(table, sqnorm, blocks, name, who):
     return tp, ld, rows, d, _dev(sqnorm, name + " sqnorm"), ld_sq
 
 
+def _weights(weights, who):
+    """(blocks, c_float[blocks]) of a host sequence of block weights."""
+    w = [float(x) for x in (weights.tolist() if hasattr(weights, "tolist") else weights)]
+    if not 1 <= len(w) <= LIST_MAX_BLOCKS:
+        raise ValueError("elimrec_amd.ops.%s: weights needs 1 <= blocks <= %d entries, got %d" % (who, LIST_MAX_BLOCKS, len(w)))
+    return len(w), (ctypes.c_float * len(w))(*w)
+
+
+def _users_beside(users, lists, name, dev, where, who):
+    """Device pointer of users int64 [n] beside `lists` ([n x .], called `name`), both on `dev` (`where` in the message)."""
+    p = _dev(users, "users", torch.int64)
+    n = lists.shape[0]
+    if users.dim() != 1 or users.numel() != n or not users.is_contiguous() or users.device != dev or lists.device != dev:
+        raise ValueError("elimrec_amd.ops.%s: users must be a contiguous [%d] tensor, one per row of %s, both on the %s device"
+                         % (who, n, name, where))
+    return p
+
+
 def pick_hard_negatives(user_table, user_sqnorm, item_table, item_sqnorm, weights, users, cands, out_neg, out_pos=None, out_score=None):
     """elimrec_pick_hard_negatives: per triplet the candidate the tables score highest. user_table [U x blocks * d] / item_table
     [I x blocks * d] float32 with unit column stride (column slices of wider matrices are fine), block b = columns
@@ -1505,10 +1523,7 @@ def pick_hard_negatives(user_table, user_sqnorm, item_table, item_sqnorm, weight
     out_pos int32 [n] (optional) its column, out_score float32 [n] (optional) its score; -1 / -1 / -inf for a row with no listed
     candidate or a user outside [0, U). Outputs: contiguous 1-D with at least n entries; entries beyond n are left alone. A
     triplet's bits depend on its rows, d, blocks and weights alone (csrc/hardneg.hip)."""
-    w = [float(x) for x in (weights.tolist() if hasattr(weights, "tolist") else weights)]
-    blocks = len(w)
-    if not 1 <= blocks <= LIST_MAX_BLOCKS:
-        raise ValueError("elimrec_amd.ops.pick_hard_negatives: weights needs 1 <= blocks <= %d entries, got %d" % (LIST_MAX_BLOCKS, blocks))
+    blocks, wp = _weights(weights, "pick_hard_negatives")
     up, ld_u, U, d, squ, ldsq_u = _block_table(user_table, user_sqnorm, blocks, "user_table", "pick_hard_negatives")
     ip, ld_i, I, d_i, sqi, ldsq_i = _block_table(item_table, item_sqnorm, blocks, "item_table", "pick_hard_negatives")
     if d_i != d or item_table.device != user_table.device:
@@ -1517,19 +1532,15 @@ def pick_hard_negatives(user_table, user_sqnorm, item_table, item_sqnorm, weight
     n, M = cands.shape
     if not 1 <= M <= HARD_NEG_MAX_CANDIDATES:
         raise ValueError("elimrec_amd.ops.pick_hard_negatives: 1 <= M <= %d, got %d" % (HARD_NEG_MAX_CANDIDATES, M))
-    usp = _dev(users, "users", torch.int64)
-    if users.dim() != 1 or users.numel() != n or not users.is_contiguous() or users.device != user_table.device \
-            or cands.device != user_table.device:
-        raise ValueError("elimrec_amd.ops.pick_hard_negatives: users must be a contiguous [%d] tensor, one per row of cands, both on "
-                         "the tables' device" % n)
     dev = user_table.device
+    usp = _users_beside(users, cands, "cands", dev, "tables'", "pick_hard_negatives")
     np_ = _rows_out(out_neg, "out_neg", torch.int64, n, 1, "pick_hard_negatives", device=dev)
     pp = _rows_out(out_pos, "out_pos", torch.int32, n, 1, "pick_hard_negatives", device=dev) if out_pos is not None else None
     sp = _rows_out(out_score, "out_score", torch.float32, n, 1, "pick_hard_negatives", device=dev) if out_score is not None else None
     if n == 0:
         return out_neg
     _lib.check(_lib.load().elimrec_pick_hard_negatives(up, ld_u, U, squ, ldsq_u, ip, ld_i, I, sqi, ldsq_i, blocks, d,
-                                                       (ctypes.c_float * blocks)(*w), usp, cp, n, M, np_, pp, sp, _stream()),
+                                                       wp, usp, cp, n, M, np_, pp, sp, _stream()),
                "pick_hard_negatives")
     return out_neg
 
@@ -1586,10 +1597,7 @@ def history_support(table, sqnorm, weights, users, lists, hist, top, out_idx, ou
     number of listed entries and their mean score (float64 sum in segment order, rounded once), 0 / NaN without one. Outputs:
     contiguous with at least B * K * top (B * K) entries; entries beyond are left alone. A pair's bits depend on the target's row,
     the segment in order, d, blocks, weights, top and exclude_self alone (csrc/history.hip)."""
-    w = [float(x) for x in (weights.tolist() if hasattr(weights, "tolist") else weights)]
-    blocks = len(w)
-    if not 1 <= blocks <= LIST_MAX_BLOCKS:
-        raise ValueError("elimrec_amd.ops.history_support: weights needs 1 <= blocks <= %d entries, got %d" % (LIST_MAX_BLOCKS, blocks))
+    blocks, wp = _weights(weights, "history_support")
     if not isinstance(hist, HistoryIndex):
         raise TypeError("elimrec_amd.ops.history_support: hist must be an ops.HistoryIndex, got %s" % type(hist).__name__)
     if isinstance(top, bool) or not isinstance(top, (int, np.integer)):
@@ -1603,11 +1611,8 @@ def history_support(table, sqnorm, weights, users, lists, hist, top, out_idx, ou
     B, K = lists.shape
     if K > LIST_MAX_K:
         raise ValueError("elimrec_amd.ops.history_support: 1 <= K <= %d, got %d" % (LIST_MAX_K, K))
-    up = _dev(users, "users", torch.int64)
     dev = table.device
-    if users.dim() != 1 or users.numel() != B or not users.is_contiguous() or users.device != dev or lists.device != dev:
-        raise ValueError("elimrec_amd.ops.history_support: users must be a contiguous [%d] tensor, one per row of lists, both on the "
-                         "table's device" % B)
+    up = _users_beside(users, lists, "lists", dev, "table's", "history_support")
     if hist.ptr.device != dev:
         raise ValueError("elimrec_amd.ops.history_support: the HistoryIndex lives on %s, the table on %s" % (hist.ptr.device, dev))
     ip = _flat_out(out_idx, "out_idx", torch.int32, B * K * top, "history_support", dev)
@@ -1616,7 +1621,7 @@ def history_support(table, sqnorm, weights, users, lists, hist, top, out_idx, ou
     mp = _flat_out(out_mean, "out_mean", torch.float32, B * K, "history_support", dev) if out_mean is not None else None
     if B == 0:
         return out_idx
-    _lib.check(_lib.load().elimrec_history_support(tp, ld, I, blocks, d, sqp, ld_sq, (ctypes.c_float * blocks)(*w), up, lp, B, K,
+    _lib.check(_lib.load().elimrec_history_support(tp, ld, I, blocks, d, sqp, ld_sq, wp, up, lp, B, K,
                                                    _dev(hist.ptr, "hist_ptr", torch.int64), _dev(hist.items, "hist_items", torch.int32),
                                                    hist.n_rows, top, 1 if exclude_self else 0, ip, vp, cp, mp, _stream()),
                "history_support")

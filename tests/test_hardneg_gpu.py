@@ -143,6 +143,20 @@ def test_misaligned_base_takes_the_scalar_row_load():
         assert a.tobytes() == b.tobytes()
 
 
+@pytest.mark.parametrize("d", (4, 64, 68, 128, 132, 192, 196, 256))
+def test_width_edges(d):
+    """Both sides of every boundary of NQ = ceil(d / 64), the float4s a lane holds: 3 triplets of M = 17 candidates (the 17th starts
+    a second 16-column group), two blocks with one zero weight on either side, through the 16-byte and the scalar row loads."""
+    M, blocks = 17, 2
+    tabs, aligned = _tables(d, blocks, col0=3), _tables(d, blocks)
+    users, cands = _triplets(3, M, np.random.default_rng(SEED + d))
+    for w in ([0.0, 1.0], [1.0, 0.0]):
+        got = _run(tabs, w, users, cands)
+        _verify(hm.scores(tabs[0], tabs[1], w, users, cands), cands, got, tol(d, w), ("width edge", d, tuple(w)))
+        for a, b in zip(got, _run(aligned, w, users, cands)):
+            assert a.tobytes() == b.tobytes()
+
+
 @pytest.mark.parametrize("case", ((17, 64, 4), (64, 20, 2), (5, 256, 1)), ids=lambda c: "M%d_d%d_b%d" % c)
 def test_exact_properties(case):
     M, d, blocks = case

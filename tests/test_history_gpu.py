@@ -156,6 +156,34 @@ def test_misaligned_base_takes_the_scalar_row_load(case):
         assert a.tobytes() == b.tobytes()
 
 
+@pytest.mark.parametrize("d", (4, 64, 68, 128, 132, 192, 196, 256))
+def test_width_edges(d):
+    """Both sides of every boundary of NQ = ceil(d / 64), the float4s a lane holds: B = 2, K = 3, top = 3 over histories of 0, 1 and
+    65 entries (65: a second chunk at NQ = 1), two blocks with one zero weight, through the 16-byte and the scalar row loads."""
+    from elimrec_amd import ops
+    blocks, w, K, top = 2, (0.0, 1.0), 3, 3
+    rng = np.random.default_rng(hm.SEED + d)
+    items = rng.integers(0, hm.ITEMS, 66).astype(np.int32)
+    ptr = np.array([0, 0, 1, 66], dtype=np.int64)
+    hist, t = ops.HistoryIndex(ptr, items, DEV), hm.tol(d, w)
+    for users in ((0, 2), (1, 2)):
+        users = np.array(users, dtype=np.int64)
+        lists = rng.integers(0, hm.ITEMS, (2, K)).astype(np.int32)
+        lists[1, 0], lists[0, 1] = items[40], items[0]                       # targets inside the histories
+        res = hm.support_full(hm.item_rows(d, blocks), w, users, lists, ptr, items, top, True)
+        got = _run(_tables(d, blocks, col0=3), w, users, lists, hist, top, True)
+        idx, val, cnt, mean = got
+        assert np.array_equal(cnt, res.cnt) and np.array_equal(idx >= 0, res.idx >= 0) and np.array_equal(np.isnan(mean), res.cnt == 0)
+        back = idx >= 0
+        assert (idx[~back] == -1).all() and np.isneginf(val[~back]).all()
+        assert np.abs(val[back].astype(np.float64) - res.val[back]).max() <= t / 2       # the k-th largest moves by no more than a score
+        assert np.abs(mean[cnt > 0].astype(np.float64) - res.mean[cnt > 0]).max() <= t / 2
+        clear = back & (res.margin > t)
+        assert (idx[clear] == res.idx[clear]).all()
+        for a, b in zip(got, _run(_tables(d, blocks), w, users, lists, hist, top, True)):
+            assert a.tobytes() == b.tobytes()
+
+
 def test_optional_outputs_and_empty_calls():
     from elimrec_amd import ops
     case = hm.CASES[2]

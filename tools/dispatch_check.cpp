@@ -43,6 +43,24 @@ template <int MIN> static void check_pow2() {
     }
 }
 
+static void check_quads() {
+    for (int d = -70; d <= 600; ++d) {
+        const bool ok = d >= 4 && d <= 256;                    // (d % 4 is the entry points' check, not the selector's)
+        for (int ret : {0, 7, ELIMREC_E_UNSUPPORTED}) {
+            int calls = 0, seen = -1;
+            const int errors = g_errors;
+            const int rc = elimrec::with_quads("check", d, [&](auto c) {
+                static_assert(decltype(c)::value >= 1 && decltype(c)::value <= 4, "no instantiation outside [1, 4]");
+                ++calls;
+                seen = decltype(c)::value;
+                return ret;
+            });
+            if (ok) EXPECT(calls == 1 && seen == (d + 63) / 64 && rc == ret && g_errors == errors);
+            else EXPECT(calls == 0 && rc == ELIMREC_E_BADARG && g_errors == errors + 1);
+        }
+    }
+}
+
 static void kernel_a() {}
 static void kernel_b() {}
 
@@ -55,6 +73,15 @@ int main() {
         EXPECT(elimrec::with_pow2<4>("check", v, [&](auto) { return ++calls; }) == ELIMREC_E_BADARG && calls == 0);
     }
     EXPECT(elimrec::with_pow2<1>("check", 2, [](auto c) { return 100 + decltype(c)::value; }) == 102);
+
+    check_quads();
+    // both sides of every width boundary, and the two ends, by name
+    for (int d : {4, 64, 68, 128, 132, 192, 196, 256})
+        EXPECT(elimrec::with_quads("check", d, [](auto c) { return 100 + decltype(c)::value; }) == 100 + (d + 63) / 64);
+    for (int d : {0, 3, -4, 257, 260, 320}) {
+        int calls = 0;
+        EXPECT(elimrec::with_quads("check", d, [&](auto) { return ++calls; }) == ELIMREC_E_BADARG && calls == 0);
+    }
 
     EXPECT(elimrec::with_fast(true, [](auto f) { return decltype(f)::value ? 1 : 2; }) == 1);
     EXPECT(elimrec::with_fast(false, [](auto f) { return decltype(f)::value ? 1 : 2; }) == 2);
