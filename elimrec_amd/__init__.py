@@ -11,7 +11,7 @@ from .data_iterator import DataIterator
 from .dataset import Dataset, SyntheticDataset, csr_to_user_dict
 from .logger import Logger, Meter
 from .basic_model import BasicModel
-from .model import EliMRec, HistorySupport, Neighbours
+from .model import Audience, EliMRec, HistorySupport, Neighbours
 from .mlp import MLP
 from .optim import FusedAdam
 from .sampler import PairwiseSamplerV2

@@ -210,6 +210,12 @@ SIGNATURES = {
     "elimrec_cosine_topk_chunk": (c_i32, []),
     "elimrec_cosine_topk_tile": (c_i32, []),
     "elimrec_list_overlap": (c_i32, [c_ptr, c_ptr, c_i64, c_i32, c_ptr, c_ptr]),
+    "elimrec_audience_topk": (c_i32, [c_ptr, c_i64, c_i64, c_i64, c_i32, c_i32, c_u32, c_i32, c_i32, c_ptr, c_ptr, c_i64, c_ptr, c_i64,
+                                      c_ptr, c_ptr, c_i32, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
+    "elimrec_audience_topk_workspace": (c_size, [c_i64, c_i64, c_i32]),
+    "elimrec_audience_topk_chunk": (c_i32, []),
+    "elimrec_audience_topk_tile": (c_i32, []),
+    "elimrec_audience_hits": (c_i32, [c_ptr, c_i64, c_i32, c_ptr, c_ptr, c_ptr, c_ptr]),
     "elimrec_list_pair_cosine": (c_i32, [c_ptr, c_i64, c_i64, c_i32, c_i32, c_ptr, c_i64, c_ptr, c_i64, c_i32, c_ptr, c_ptr]),
     "elimrec_list_max_k": (c_i32, []),
     "elimrec_list_pair_cosine_small_k": (c_i32, []),
@@ -364,6 +370,7 @@ class _Recording(object):
                              "elimrec_score_get_math", "elimrec_score_get_bf16x3", "elimrec_group_metric_means_chunk",
                              "elimrec_rank_segment", "elimrec_rank_targets_per_pass", "elimrec_slab_hop_adam_wgrad_jobs",
                              "elimrec_cosine_topk_chunk", "elimrec_cosine_topk_tile",
+                             "elimrec_audience_topk_chunk", "elimrec_audience_topk_tile",
                              "elimrec_list_max_k", "elimrec_list_pair_cosine_small_k", "elimrec_list_pair_cosine_chunk_cols",
                              "elimrec_mmr_max_pool", "elimrec_mmr_rows_in_lds",
                              "elimrec_comm_create", "elimrec_comm_destroy", "elimrec_comm_nranks") or name.startswith("elimrec_program_")

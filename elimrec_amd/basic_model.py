@@ -8,7 +8,7 @@ from torch import nn
 
 from . import ops
 from .evaluator import ProxyEvaluator, UniEvaluator
-from .reports import DiversifyReport, EffectReport, HistoryReport, ListReport, NeighbourReport, RankReport, SignificanceReport
+from .reports import AudienceReport, DiversifyReport, EffectReport, HistoryReport, ListReport, NeighbourReport, RankReport, SignificanceReport
 
 
 class BasicModel(nn.Module):
@@ -68,6 +68,14 @@ class BasicModel(nn.Module):
                              % (ops.LIST_MAX_K, int(dataset.num_items), k_list))
         self.list_reporter = ListReport(dataset, train, dataset.get_user_test_dict(), k_list, group_view=config["group_view"],
                                         item_group_view=item_view) if k_list else None
+        # --audience_report=K (CLI-only, default 0 = off): for every item with a test interaction the K users the model ranks highest
+        # for it, the item's training users left out -- how many of its test users it reaches, how active and how highly scored the
+        # listed users are, how the list slots spread over the users -- overall and per item popularity group (--item_group_view)
+        # (reports.AudienceReport)
+        k_aud = int(config["audience_report"]) if "audience_report" in config else 0
+        if k_aud and not 1 <= k_aud <= ops.AUDIENCE_MAX_K:
+            raise ValueError("audience_report must be 0 (off) or the K of the audience lists, 1 <= K <= %d, got %d" % (ops.AUDIENCE_MAX_K, k_aud))
+        self.audience_reporter = AudienceReport(dataset, train, dataset.get_user_test_dict(), k_aud, item_group_view=item_view) if k_aud else None
         # --diversify_report=K (CLI-only, default 0 = off): the test users' top-N pools (--diversify_pool=N, default min(4K, 256,
         # the catalogue)) re-ranked to K items by greedy MMR at every --diversify_lambda (default [1.0,0.9,0.7,0.5]): what the trade
         # costs in recall / NDCG and buys in intra-list similarity and catalogue exposure, overall and per user group

@@ -25,16 +25,13 @@
 // list_overlap_kernel: one wave per row, list b in LDS, every lane counts its entries of a; integer, exact.
 #include "common.h"
 #include "cosine.h"
+#include "knn_select.h"
 
 namespace elimrec {
 
-constexpr int KNN_CHUNK = 4096, KNN_TILE = 64, KNN_MAXK = 256, KNN_SLACK = 32, KNN_SMALLK = 64;
+constexpr int KNN_CHUNK = 4096, KNN_TILE = 64, KNN_MAXK = 256, KNN_SMALLK = 64;
 constexpr int KNN_OVERLAP_MAXK = 1024;
 typedef float knn_v4f __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ bool knn_before(float va, int ia, float vb, int ib) {   // a ranks before b (elimrec_topk_merge's order)
-    return va > vb || (va == vb && ia < ib);
-}
 
 struct KnnArgs {
     const float *T; int64_t ld, n_rows; int d;
@@ -50,37 +47,6 @@ constexpr int knn_stage_rows(int D, int W) { return (D == 0 || W == 1) ? 16 : (D
 static inline size_t knn_lds_bytes(int D, int W, int d, int K) {
     const size_t sr = (size_t)knn_stage_rows(D, W), cap = (size_t)K + KNN_SLACK, rows = 16 * (size_t)W;
     return sr * (d + 4) * 4 + sr * 4 + rows * cap * 8 + rows * 8 + (D == 0 ? (size_t)W * (d / 4) * 64 * 4 : 0);
-}
-
-// the whole wave ranks the n entries of one list, leaves the K best in rank order, the new length and threshold
-template <int E>
-__device__ __forceinline__ void knn_compact(float *lv, int *li_, int *cnt, float *thr, int K, int lane) {
-    const int n = *cnt;
-    float v[E];
-    int id[E], rk[E];
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-        const int c = lane + 64 * e;
-        v[e] = c < n ? lv[c] : 0.f;
-        id[e] = c < n ? li_[c] : 0;
-        rk[e] = 0;
-    }
-    for (int j = 0; j < n; ++j) {
-        const float vj = lv[j];
-        const int ij = li_[j];
-#pragma unroll
-        for (int e = 0; e < E; ++e) rk[e] += knn_before(vj, ij, v[e], id[e]) ? 1 : 0;
-    }
-    wave_lds_sync();                                        // every lane has read the list
-#pragma unroll
-    for (int e = 0; e < E; ++e)
-        if (lane + 64 * e < n && rk[e] < K) {
-            lv[rk[e]] = v[e];
-            li_[rk[e]] = id[e];
-            if (rk[e] == K - 1) *thr = v[e];
-        }
-    if (lane == 0) *cnt = n < K ? n : K;
-    wave_lds_sync();
 }
 
 // D: 32 / 64 / 128 = the dimension at compile time, query operands in registers; 0 = any d % 4 == 0 up to TABLE_MAXD.

@@ -33,6 +33,9 @@
 //   bootstrap_means(rows f32[n x C], group_ptr i64[G+1], group_rows i32, R, seed) -> f64[R x G x C]: R bootstrap replicates of every
 //     group's column means, the draws fixed by Philox4x32-10 at (seed, r, g, t); bootstrap_diff_means(rows_a, rows_b, ...): the same of
 //     the paired differences rows_b - rows_a, taken in float64; blocks wider than 16 columns go through in slices (csrc/bootstrap.hip)
+//   audience_topk(Y, U, I, items i32[Q], excl_ptr i64[Q + 1]?, excl_users i32?, d, S, head_mask, fusion_mode, predict_type, K, sqnorm?, row_sum
+//     f32[U]? (TIE), I_total) -> (idx i32, val f32) [Q x K]: per query item the K users with the largest predict() score, the item's excluded
+//     users left out; -1 / -inf fillers (the ids and the CSR are checked on the host first: a synchronisation; csrc/audience.hip)
 //   sample_triplets(user_ids, ptr, items, num_items, n, seed, epoch) -> (users, pos, neg)
 //   score_candidates(Y, U, I, users, d, S, head_mask, fusion_mode, predict_type, cand_ptr, cand_items, width) -> f32[B x width]
 //       (each row: its candidates' scores in list order, then -inf)
@@ -406,6 +409,72 @@ std::tuple<at::Tensor, at::Tensor> cosine_topk(const at::Tensor &table, const at
     return {idx, val};
 }
 
+// ---- audience lists: per query item the K users with the largest predict() score (csrc/audience.hip)
+std::tuple<at::Tensor, at::Tensor> audience_topk(const at::Tensor &Y, int64_t U, int64_t I, const at::Tensor &items,
+                                                 const c10::optional<at::Tensor> &excl_ptr, const c10::optional<at::Tensor> &excl_users, int64_t d,
+                                                 int64_t S, int64_t head_mask, int64_t fusion_mode, int64_t predict_type, int64_t K,
+                                                 const c10::optional<at::Tensor> &sqnorm, const c10::optional<at::Tensor> &row_sum,
+                                                 int64_t I_total) {
+    const at::Tensor y = rowmajor(Y, "Y");
+    need(items, "items", at::kInt, 1);
+    const at::Tensor q = items.contiguous();
+    const int64_t Q = q.numel();
+    TORCH_CHECK(K >= 1 && K <= 256, "elimrec::audience_topk: 1 <= K <= 256, got ", K);
+    TORCH_CHECK(d % 4 == 0 && d >= 4 && d <= 256, "elimrec::audience_topk: a block needs d % 4 == 0 and 4 <= d <= 256 columns, got ", d);
+    TORCH_CHECK(S >= 0 && S <= 3, "elimrec::audience_topk: 0 <= S <= 3, got ", S);
+    TORCH_CHECK(U >= 0 && I >= 0 && y.size(0) == U + I && y.size(1) >= (1 + S) * d, "elimrec::audience_topk: Y must be [U + I x >= (1 + S) d]");
+    TORCH_CHECK(excl_ptr.has_value() == excl_users.has_value(), "elimrec::audience_topk: the exclusion CSR needs excl_ptr and excl_users, or neither");
+    if (Q > 0) {    // no unchecked id reaches the kernel
+        const int64_t lo = q.min().item<int64_t>(), hi = q.max().item<int64_t>();
+        TORCH_CHECK_INDEX(lo >= 0 && hi < I, "elimrec::audience_topk: query items span [", lo, ", ", hi, "], the catalogue has ", I, " items");
+    }
+    at::Tensor ep, eu;
+    if (excl_ptr.has_value()) {   // ... and the CSR is validated on the host
+        need(*excl_ptr, "excl_ptr", at::kLong, 1); need(*excl_users, "excl_users", at::kInt, 1);
+        ep = excl_ptr->contiguous(); eu = excl_users->contiguous();
+        const int64_t n = eu.numel();
+        TORCH_CHECK(ep.numel() == Q + 1, "elimrec::audience_topk: excl_ptr needs Q + 1 = ", Q + 1, " entries, got ", ep.numel());
+        const at::Tensor hp = ep.cpu();
+        const int64_t *p = hp.data_ptr<int64_t>();
+        bool ok = p[0] == 0 && p[Q] == n;
+        for (int64_t b = 0; b < Q && ok; ++b) ok = p[b + 1] >= p[b];
+        TORCH_CHECK(ok, "elimrec::audience_topk: excl_ptr must ascend from 0 to len(excl_users) = ", n);
+        if (n > 0) {
+            const int64_t lo = eu.min().item<int64_t>(), hi = eu.max().item<int64_t>();
+            TORCH_CHECK_INDEX(lo >= 0 && hi < U, "elimrec::audience_topk: excluded users span [", lo, ", ", hi, "], the model has ", U, " users");
+        } else {
+            eu = at::zeros({1}, q.options());      // the binding wants a device tensor; nothing of it is read
+        }
+    }
+    at::Tensor idx = at::empty({Q, K}, q.options()), val = at::empty({Q, K}, y.options());
+    if (Q == 0) return {idx, val};
+    at::Tensor sqn;
+    if (sqnorm.has_value()) {
+        need(*sqnorm, "sqnorm", at::kFloat, 2);
+        TORCH_CHECK(sqnorm->size(0) == U + I && sqnorm->size(1) == S + 1, "elimrec::audience_topk: sqnorm must be [U + I x 1 + S]");
+        sqn = sqnorm->contiguous();
+    } else {
+        sqn = at::empty({U + I, S + 1}, y.options());
+        check(elimrec_row_sqnorms(y.data_ptr<float>(), y.stride(0), U + I, (int)d, (int)S + 1, sqn.data_ptr<float>(), cur_stream()),
+              "audience_topk(row_sqnorms)");
+    }
+    at::Tensor rs;
+    if (predict_type == 2) {
+        TORCH_CHECK(row_sum.has_value(), "elimrec::audience_topk: predict type TIE needs row_sum [U]");
+        need(*row_sum, "row_sum", at::kFloat, 1);
+        TORCH_CHECK(row_sum->numel() == U, "elimrec::audience_topk: row_sum needs one entry per user (", U, "), got ", row_sum->numel());
+        rs = row_sum->contiguous();
+    }
+    const size_t need_ws = elimrec_audience_topk_workspace(Q, U, (int)K);
+    at::Tensor ws = at::empty({(int64_t)need_ws}, y.options().dtype(at::kByte));
+    check(elimrec_audience_topk(y.data_ptr<float>(), y.stride(0), U, I, (int)d, (int)S, (uint32_t)head_mask, (int)fusion_mode, (int)predict_type,
+                                sqn.data_ptr<float>(), rs.defined() ? rs.data_ptr<float>() : nullptr, I_total, q.data_ptr<int32_t>(), Q,
+                                ep.defined() ? ep.data_ptr<int64_t>() : nullptr, eu.defined() ? eu.data_ptr<int32_t>() : nullptr, (int)K,
+                                idx.data_ptr<int32_t>(), val.data_ptr<float>(), ws.data_ptr(), (size_t)ws.numel(), cur_stream()),
+          "audience_topk");
+    return {idx, val};
+}
+
 at::Tensor list_overlap(const at::Tensor &a, const at::Tensor &b) {
     need(a, "a", at::kInt, 2); need(b, "b", at::kInt, 2);
     const at::Tensor x = a.contiguous(), y = b.contiguous();
@@ -707,6 +776,8 @@ TORCH_LIBRARY(elimrec, m) {
     m.def("score_effects(Tensor Y, int U, int I, Tensor users, int d, int S, int head_mask, int fusion_mode, Tensor cand_ptr, Tensor cand_items, int width) -> Tensor");
     m.def("rank_targets(Tensor scores, Tensor tgt_ptr, Tensor tgt_items) -> Tensor");
     m.def("cosine_topk(Tensor table, Tensor sqnorm, Tensor query_rows, int K, bool exclude_self) -> (Tensor, Tensor)");
+    m.def("audience_topk(Tensor Y, int U, int I, Tensor items, Tensor? excl_ptr, Tensor? excl_users, int d, int S, int head_mask, int fusion_mode, "
+          "int predict_type, int K, Tensor? sqnorm, Tensor? row_sum, int I_total) -> (Tensor, Tensor)");
     m.def("list_overlap(Tensor a, Tensor b) -> Tensor");
     m.def("list_pair_cosine(Tensor table, Tensor sqnorm, Tensor lists, int blocks) -> Tensor");
     m.def("list_exposure(Tensor lists, int n_rows) -> Tensor");
@@ -742,6 +813,7 @@ TORCH_LIBRARY_IMPL(elimrec, CUDA, m) {
     m.impl("score_effects", &score_effects);
     m.impl("rank_targets", &rank_targets);
     m.impl("cosine_topk", &cosine_topk);
+    m.impl("audience_topk", &audience_topk);
     m.impl("list_overlap", &list_overlap);
     m.impl("list_pair_cosine", &list_pair_cosine);
     m.impl("list_exposure", &list_exposure);

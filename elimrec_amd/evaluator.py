@@ -21,7 +21,7 @@ from . import ops
 from .data_iterator import DataIterator
 from .ops import CandidateScoringError                                                                      # noqa: F401
 # (the reports and their pure functions live in reports.py; they stay importable from here)
-from .reports import (DIVERSIFY_COLUMNS, EXPOSURE_COLUMNS, DiversifyReport, DiversifyTables, EffectReport, HistoryReport, ListReport,   # noqa: F401
+from .reports import (AUDIENCE_COLUMNS, AUDIENCE_EXPOSURE_COLUMNS, AudienceReport, AudienceTables, DIVERSIFY_COLUMNS, EXPOSURE_COLUMNS, DiversifyReport, DiversifyTables, EffectReport, HistoryReport, ListReport,   # noqa: F401
                       ListTables, NeighbourReport, RankReport, RankTables, SignificanceReport, SignificanceTables, assign_item_groups, assign_user_groups, bootstrap_summary, exposure_summary, format_rows, group_index, group_table, lists_csr)
 
 metric_dict = {"Precision": 1, "Recall": 2, "MAP": 3, "NDCG": 4, "MRR": 5}

@@ -40,6 +40,7 @@ from .plugin import EmbeddingParameter, LazyGradParameter, StepController
 # EliMRec.explain's result: column names, item ids CPU int32 [B x W] (-1 = padding), values CPU fp32 [B x W x C]
 Effects = collections.namedtuple("Effects", ("columns", "items", "values"))
 Neighbours = collections.namedtuple("Neighbours", ("ids", "scores"))
+Audience = collections.namedtuple("Audience", ("users", "scores"))
 HistorySupport = collections.namedtuple("HistorySupport", ("items", "history", "scores", "count", "mean"))
 
 
@@ -1404,6 +1405,69 @@ class EliMRec(BasicModel):
     def similar_users(self, user_ids, k, space="fused", exclude=None):
         """similar_items over the user rows: the k users closest to each given user."""
         return self._similar("user", user_ids, k, space, exclude)
+
+    def _audience_row_sum(self, dev, sqn):
+        """TIE's sum_i sigmoid(u . i) of EVERY user: the scorer's pass 1 in user blocks of at most 8192, computed once per table
+        version and kept in the workspace (as _block_sqnorms keeps the norms)."""
+        if self._ws.get("aud_row_sum_version") != self._table_version or self._ws.get("aud_row_sum") is None:
+            U = self.num_users
+            row_sum = torch.empty(U, dtype=torch.float32, device=dev)
+            for lo in range(0, U, 8192):
+                users = torch.arange(lo, min(U, lo + 8192), dtype=torch.int64, device=dev)
+                row_sum[lo:lo + users.numel()] = self._catalogue_row_sum(dev, users, "TIE", sqn)
+            self._ws["aud_row_sum"] = row_sum
+            self._ws["aud_row_sum_version"] = self._table_version
+        return self._ws["aud_row_sum"]
+
+    @torch.no_grad()
+    def audience_device(self, query, k, out_idx=None, out_val=None):
+        """The k users the model ranks highest for each query item -- predict() read from the item's side -- under the current
+        predict_type, fusion_mode and head mask: (idx int32 [Q x k], val float32 [Q x k]) on the device, (score descending, user id
+        ascending), -1 / -inf where fewer than k users are eligible (csrc/audience.hip; no [U x Q] score block is written). query:
+        an ops.AudienceQuery over this model's items and users (checked once; it may carry per-item lists of users to leave out),
+        or item ids (host array or tensor, checked on the host). Tables as predict_device: those of the last training forward."""
+        dev = self._cached_tables("audience() needs", "audience lists need the whole cached tables on this rank; the tables are "
+                                  "item-sharded (lean / multi-rank evaluation)")
+        k = int(k)
+        if not 1 <= k <= ops.AUDIENCE_MAX_K:
+            raise ValueError("k must lie in [1, %d]" % ops.AUDIENCE_MAX_K)
+        U, I = self.num_users, self.num_items
+        if not isinstance(query, ops.AudienceQuery):
+            query = ops.AudienceQuery(query, I, U, dev)
+        elif query.n_items != I or query.n_users != U:
+            raise ValueError("query must be an ops.AudienceQuery over the %d items and %d users" % (I, U))
+        Q = query.n_queries
+        if out_idx is None:
+            out_idx = torch.empty(Q, k, dtype=torch.int32, device=dev)
+        if out_val is None:
+            out_val = torch.empty(Q, k, dtype=torch.float32, device=dev)
+        if Q == 0:
+            return out_idx, out_val
+        sqn = self._block_sqnorms(dev)
+        row_sum = self._audience_row_sum(dev, sqn) if ops.PREDICT_TYPES.get(self.predict_type, 0) == 2 else None
+        need = ops.audience_topk_workspace(Q, U, k)
+        if self._ws.get("aud_ws") is None or self._ws["aud_ws"].numel() < need:
+            self._ws["aud_ws"] = torch.empty(need, dtype=torch.uint8, device=dev)
+        ops.audience_topk(self._ws["Y"], U, I, query, self.latent_dim, self.S, self._head_mask(), self.fusion_mode, self.predict_type, k,
+                          out_idx, out_val, sqnorm=sqn, row_sum=row_sum, I_total=I, workspace=self._ws["aud_ws"])
+        return out_idx, out_val
+
+    def audience(self, item_ids, k, exclude=None):
+        """The k users the model ranks highest for each given item: Audience(users CPU int32 [B x k] (-1 padded), scores CPU fp32
+        [B x k] (-inf padded)), by (score descending, user id ascending), under the current predict type -- whom would this item be
+        pushed to, and does TIE send it to other users than TE? `exclude` = dict item -> user ids to leave out (typically the
+        item's training users). 1 <= k <= 256."""
+        k = int(k)
+        if not 1 <= k <= ops.AUDIENCE_MAX_K:
+            raise ValueError("k must lie in [1, %d]" % ops.AUDIENCE_MAX_K)
+        ids = self._id_lists([item_ids], "item")[1]
+        ptr, flat = self._excluded(exclude, ids, "user", self.num_users)
+        dev = self._require_gpu()
+        if not ids.size:
+            return Audience(torch.empty(0, k, dtype=torch.int32), torch.empty(0, k, dtype=torch.float32))
+        query = ops.AudienceQuery(ids, self.num_items, self.num_users, dev, ptr if flat.size else None, flat if flat.size else None)
+        idx, val = self.audience_device(query, k)
+        return Audience(idx.cpu(), val.cpu())
 
     @torch.no_grad()
     def list_similarity_device(self, lists, out, side="item"):

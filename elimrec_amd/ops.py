@@ -997,7 +997,11 @@ def __getattr__(name):
         return int(_lib.load().elimrec_cosine_topk_chunk())
     if name == "KNN_TILE":               # query rows one workgroup of cosine_topk holds (16 when K > 64)
         return int(_lib.load().elimrec_cosine_topk_tile())
-    if name == "LIST_SMALL_K":           # lists up to this K take one wave of list_pair_cosine, longer ones four
+    if name == "AUDIENCE_CHUNK":         # user rows one workgroup of audience_topk streams
+        return int(_lib.load().elimrec_audience_topk_chunk())
+    if name == "AUDIENCE_TILE":          # query items one workgroup of audience_topk holds (16 when K > 64 or d is not 32 / 64)
+        return int(_lib.load().elimrec_audience_topk_tile())
+    if name == "LIST_SMALL_K":          # lists up to this K take one wave of list_pair_cosine, longer ones four
         return int(_lib.load().elimrec_list_pair_cosine_small_k())
     if name == "HISTORY_MAX_TOP":        # entries of a history history_support names per target
         return int(_lib.load().elimrec_history_max_top())
@@ -1317,6 +1321,113 @@ def list_overlap(a, b, out):
     if out.dim() != 1 or not out.is_contiguous() or out.numel() < n:
         raise ValueError("elimrec_amd.ops.list_overlap: out must be a contiguous 1-D tensor of at least %d entries" % n)
     _lib.check(_lib.load().elimrec_list_overlap(ap, bp, n, K, op, _stream()), "list_overlap")
+    return out
+
+
+AUDIENCE_MAX_K = 256
+
+
+class AudienceQuery(object):
+    """Query items of an n_items catalogue and, optionally, per item a list of users to leave out as CSR (excl_ptr [Q + 1],
+    excl_users: typically the item's training users), CHECKED ON THE HOST -- every item id in [0, n_items), every excluded user id
+    in [0, n_users), ptr[0] = 0, ascending, ptr[Q] = len(excl_users) -- and then resident on `device`: audience_topk takes it as is,
+    call after call, and no unchecked id ever reaches a kernel (the counterpart of NeighbourQuery). Exclusion lists may repeat ids,
+    in any order, and may be empty."""
+
+    def __init__(self, items, n_items, n_users, device, excl_ptr=None, excl_users=None):
+        q = _checked_ids(items, n_items, "AudienceQuery", "items", "query items span [%d, %d], the catalogue has %d items")
+        if (excl_ptr is None) != (excl_users is None):
+            raise ValueError("elimrec_amd.ops.AudienceQuery: the exclusion CSR needs excl_ptr and excl_users, or neither")
+        self.n_items, self.n_users, self.n_queries = int(n_items), int(n_users), int(q.size)
+        self.items = _resident_ids(q, device)
+        self.excl_ptr = self.excl_users = None
+        if excl_ptr is not None:
+            p, e = _checked_csr(excl_ptr, excl_users, q.size, n_users, "AudienceQuery",
+                                ("excl_ptr", "excl_users", "Q", "excluded users span [%d, %d], the model has %d users"))
+            self.excl_ptr = torch.from_numpy(p).to(device)
+            self.excl_users = _resident_ids(e, device)
+
+
+def audience_topk_workspace(Q, U, K):
+    """Bytes of workspace audience_topk needs (host arithmetic only)."""
+    return int(_lib.load().elimrec_audience_topk_workspace(int(Q), int(U), int(K)))
+
+
+def audience_topk(Y, U, I, query, d, S, head_mask, fusion_mode, predict_type, K, out_idx, out_val=None, sqnorm=None, row_sum=None,
+                  I_total=None, workspace=None):
+    """elimrec_audience_topk: per query item the K users with the largest predict() score for the (user, item) pair, by (score
+    descending, user id ascending): out_idx int32 / out_val float32 (optional) [Q x K], -1 / -inf where fewer than K users are
+    eligible; entries of the outputs beyond [Q x K] are left alone. Y [U + I x >= (1 + S) d] float32 with unit column stride, users
+    first (the table the scorers read); d % 4 == 0, 4 <= d <= 256, 0 <= S <= 3, 1 <= K <= 256. fusion_mode 'rubi' / 'hm' / 'sum',
+    head_mask as score_topk reads it, predict_type 'TE' / 'TIE' / anything else = normal. query: an AudienceQuery (checked once),
+    or host / device item ids, checked here at every call. sqnorm [(U + I) x (1 + S)]: row_sqnorms' table (default: computed here).
+    row_sum [U] float32 (TIE: required): the users' sums of sigmoid(u . i) over the catalogue of I_total items (default I), from
+    score_topk_shard phase 1. workspace: uint8 device tensor of at least audience_topk_workspace bytes, 16-byte aligned (default:
+    allocated here). The scores follow the evaluator's math mode (elimrec_score_set_math)."""
+    if not isinstance(Y, torch.Tensor) or not Y.is_cuda:
+        _dev(Y, "Y")
+    y, ldy = _rowmajor(Y, "Y")
+    U, I, d, S, K = int(U), int(I), int(d), int(S), int(K)
+    if not 1 <= K <= AUDIENCE_MAX_K:
+        raise ValueError("elimrec_amd.ops.audience_topk: 1 <= K <= %d, got %d" % (AUDIENCE_MAX_K, K))
+    if d % 4 != 0 or not 4 <= d <= KNN_MAX_D:
+        raise ValueError("elimrec_amd.ops.audience_topk: a block needs d %% 4 == 0 and 4 <= d <= %d columns, got %d" % (KNN_MAX_D, d))
+    if not 0 <= S <= 3:
+        raise ValueError("elimrec_amd.ops.audience_topk: 0 <= S <= 3, got %d" % S)
+    if fusion_mode not in FUSION_MODES:
+        raise ValueError("elimrec_amd.ops.audience_topk: fusion_mode is one of %s, got %r" % (sorted(FUSION_MODES), fusion_mode))
+    if U < 0 or I < 0 or Y.dim() != 2 or Y.shape[0] != U + I or Y.shape[1] < (1 + S) * d:
+        raise ValueError("elimrec_amd.ops.audience_topk: Y must be [U + I = %d x >= (1 + S) d = %d], got %s"
+                         % (U + I, (1 + S) * d, tuple(Y.shape)))
+    if isinstance(query, AudienceQuery):
+        if query.n_items > I or query.n_users > U or query.items.device != Y.device:
+            raise IndexError("elimrec_amd.ops.audience_topk: the AudienceQuery was checked for %d items and %d users on %s, the table "
+                             "has %d and %d on %s" % (query.n_items, query.n_users, query.items.device, I, U, Y.device))
+    else:
+        query = AudienceQuery(query, I, U, Y.device)
+    tie = PREDICT_TYPES.get(predict_type, 0) == 2
+    if tie:
+        if row_sum is None:
+            raise ValueError("elimrec_amd.ops.audience_topk: predict type TIE needs row_sum [U] (score_topk_shard phase 1 over all users)")
+        if row_sum.dim() != 1 or row_sum.numel() != U or not row_sum.is_contiguous() or row_sum.device != Y.device:
+            raise ValueError("elimrec_amd.ops.audience_topk: row_sum must be contiguous, 1-D with one entry per user (%d) on Y's device" % U)
+    I_total = I if I_total is None else int(I_total)
+    if sqnorm is None:
+        sqnorm = row_sqnorms(Y, d, 1 + S, torch.empty((U + I, 1 + S), dtype=torch.float32, device=Y.device))
+    elif tuple(sqnorm.shape) != (U + I, 1 + S) or not sqnorm.is_contiguous() or sqnorm.device != Y.device:
+        raise ValueError("elimrec_amd.ops.audience_topk: sqnorm must be contiguous [U + I x 1 + S] = [%d x %d] on Y's device" % (U + I, 1 + S))
+    Q = query.n_queries
+    ip = _rows_out(out_idx, "out_idx", torch.int32, Q, K, "audience_topk", Y.device)
+    vp = _rows_out(out_val, "out_val", torch.float32, Q, K, "audience_topk", Y.device) if out_val is not None else None
+    lib = _lib.load()
+    need = int(lib.elimrec_audience_topk_workspace(Q, U, K))
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=Y.device)
+    wp = _dev(workspace, "workspace", torch.uint8)
+    if workspace.numel() < need or not workspace.is_contiguous() or wp % 16:
+        raise ValueError("elimrec_amd.ops.audience_topk: the workspace needs %d contiguous bytes, 16-byte aligned (got %d)"
+                         % (need, workspace.numel()))
+    if Q == 0:
+        return out_idx
+    _lib.check(lib.elimrec_audience_topk(y, ldy, U, I, d, S, int(head_mask), FUSION_MODES[fusion_mode], PREDICT_TYPES.get(predict_type, 0),
+                                         _dev(sqnorm, "sqnorm"), _dev(row_sum, "row_sum") if tie else None, I_total,
+                                         _dev(query.items, "items", torch.int32), Q, _dev(query.excl_ptr, "excl_ptr", torch.int64),
+                                         _dev(query.excl_users, "excl_users", torch.int32), K, ip, vp, wp, workspace.numel(), _stream()),
+               "audience_topk")
+    return out_idx
+
+
+def audience_hits(lists, ptr, users, out):
+    """elimrec_audience_hits: out int32 [Q] <- per row the number of ids >= 0 of lists[q, :] (int32 [Q x K] contiguous) that occur in
+    segment q of the CSR ptr int64 [Q + 1] / users int32 (device tensors, checked by the caller: a TargetIndex-style host check)."""
+    lp = _dev(lists, "lists", torch.int32)
+    if lists.dim() != 2 or not lists.is_contiguous() or lists.shape[1] < 1:
+        raise ValueError("elimrec_amd.ops.audience_hits: lists must be a contiguous [Q x K] tensor, K >= 1")
+    Q, K = lists.shape
+    pp, up, op = _dev(ptr, "ptr", torch.int64), _dev(users, "users", torch.int32), _dev(out, "out", torch.int32)
+    if ptr.numel() != Q + 1 or not ptr.is_contiguous() or not users.is_contiguous() or out.dim() != 1 or not out.is_contiguous() or out.numel() < Q:
+        raise ValueError("elimrec_amd.ops.audience_hits: ptr needs Q + 1 = %d contiguous entries, out at least %d" % (Q + 1, Q))
+    _lib.check(_lib.load().elimrec_audience_hits(lp, Q, K, pp, up, op, _stream()), "audience_hits")
     return out
 
 

@@ -542,6 +542,154 @@ class ListReport(_Report):
         return final, format_table(self.shift_columns, self.group_labels, final)
 
 
+AUDIENCE_COLUMNS = ("hit", "first", "act", "score")
+AUDIENCE_EXPOSURE_COLUMNS = ("users", "coverage", "gini", "entropy")
+AudienceTables = collections.namedtuple("AudienceTables", ("item_columns", "item_labels", "items", "user_columns", "user_labels", "users"))
+
+
+def audience_item_rows(lists, scores, test_ptr, test_users, user_train_len):
+    """The audience report's row of every item, float64 [n x 4] in the columns AUDIENCE_COLUMNS, from its list of user ids (lists
+    int [n x k], -1 fillers) and their scores [n x k], its test users (segment i of the CSR test_ptr [n + 1] / test_users) and the
+    users' training-history lengths (user_train_len [U]):
+      hit = the share of the item's test users found in its list (an item-side recall at k; NaN without test users);
+      first = 1 if any test user is listed, else 0; act = the mean training-history length of the listed users;
+      score = the mean listed score (both NaN for a list of fillers only). Pure numpy."""
+    lists = np.asarray(lists, dtype=np.int64)
+    scores = np.asarray(scores, dtype=np.float64)
+    ptr = np.asarray(test_ptr, dtype=np.int64).reshape(-1)
+    users = np.asarray(test_users, dtype=np.int64).reshape(-1)
+    length = np.asarray(user_train_len, dtype=np.float64).reshape(-1)
+    n = lists.shape[0]
+    out = np.full((n, len(AUDIENCE_COLUMNS)), np.nan, dtype=np.float64)
+    for i in range(n):
+        listed = lists[i] >= 0
+        test = users[ptr[i]:ptr[i + 1]]
+        hits = int(np.isin(lists[i][listed], test).sum())
+        if test.size:
+            out[i, 0] = hits / float(test.size)
+        out[i, 1] = 1.0 if hits else 0.0
+        if listed.any():
+            out[i, 2] = length[lists[i][listed]].sum() / float(listed.sum())
+            out[i, 3] = scores[i][listed].sum() / float(listed.sum())
+    return out
+
+
+class AudienceReport(_Report):
+    """Whom the model sends an item to (--audience_report=K): for every item with at least one test interaction its top-k audience
+    under the model's current predict type with the item's training users left out (EliMRec.audience_device, csrc/audience.hip),
+    items in blocks of block_items, and
+      per item the columns AUDIENCE_COLUMNS (audience_item_rows; the hit counts are ops.audience_hits on the device), their means
+        over all those items and -- item_group_view -- per item popularity group (ops.group_metric_means: only the table reaches the
+        host);
+      per user how often they are listed (ops.list_exposure over the lists with n_rows = the number of users), summarised by
+        exposure_summary over all users in the columns AUDIENCE_EXPOSURE_COLUMNS."""
+
+    name, needs = "audience", "audience_device"
+
+    def __init__(self, dataset, user_train_dict, user_test_dict, k, item_group_view=None):
+        if not isinstance(user_train_dict, dict) or not isinstance(user_test_dict, dict):
+            raise TypeError("user_train_dict and user_test_dict must be dicts")
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1 or k > ops.AUDIENCE_MAX_K:
+            raise ValueError("k must be an integer in [1, %d], got %r" % (ops.AUDIENCE_MAX_K, k))
+        self.dataset = dataset
+        self.num_items, self.num_users = I, U = int(dataset.num_items), int(dataset.num_users)
+        self.k = int(k)
+        self.block_items = 8192
+        item_test, item_train = {}, {}
+        for table, src in ((item_test, user_test_dict), (item_train, user_train_dict)):
+            for u, items in src.items():
+                for i in items:
+                    table.setdefault(int(i), []).append(int(u))
+        self.items = sorted(item_test)
+        self.item_test = {i: sorted(set(item_test[i])) for i in self.items}
+        self.item_train = {i: sorted(set(item_train.get(i, []))) for i in self.items}
+        self.user_train_len = np.zeros(U, dtype=np.int64)
+        for u, items in user_train_dict.items():
+            self.user_train_len[int(u)] = len(items)
+        self.item_counts = item_train_counts(user_train_dict, I)
+        self.group_labels, self._positions = self._item_groups(np.asarray(self.items, dtype=np.int64), self.item_counts, item_group_view)
+        self.shift_columns = ("overlap",) + tuple("d_" + c for c in AUDIENCE_COLUMNS)
+
+    def test_csr(self):
+        """The items' test users as CSR on the host: (ptr int64 [n + 1], users int32)."""
+        return ops.ragged([self.item_test[i] for i in self.items], dtype=np.int32)[:2]
+
+    def _make_resident(self, device):
+        """The group index, the users' history lengths, the items' test users and the blocks' checked queries on the device."""
+        ptr, users = self.test_csr()
+        ops._checked_csr(ptr, users, len(self.items), self.num_users, "AudienceReport",
+                         ("test_ptr", "test_users", "n", "test users span [%d, %d], the model has %d users"))
+        return dict(groups=group_index(self._positions, len(self.items), device),
+                    length=torch.from_numpy(self.user_train_len.astype(np.float64)).to(device),
+                    test_ptr=torch.from_numpy(ptr).to(device), test_users=ops._resident_ids(users, device), queries={})
+
+    def audience_rows(self, model):
+        """Every reported item's row, list, scores and the users' exposure on the device: ([n x 4] float32, lists int32 [n x k],
+        scores float32 [n x k], counts int32 [num_users])."""
+        device = self._preflight(model)
+        if model.num_users != self.num_users:
+            raise ValueError("the report was built for %d users, the model has %d" % (self.num_users, model.num_users))
+        res = self._resident(device)
+        n, k, U = len(self.items), self.k, self.num_users
+        lists = torch.empty(n, k, dtype=torch.int32, device=device)
+        scores = torch.empty(n, k, dtype=torch.float32, device=device)
+        counts = torch.zeros(U, dtype=torch.int32, device=device)
+        hits = torch.zeros(max(n, 1), dtype=torch.int32, device=device)
+        step = max(1, int(self.block_items))
+        for a in range(0, n, step):
+            b = min(a + step, n)
+            query = res["queries"].get((a, b))
+            if query is None:
+                ptr, flat, _ = ops.ragged([self.item_train[i] for i in self.items[a:b]], dtype=np.int32)
+                query = res["queries"][(a, b)] = ops.AudienceQuery(np.asarray(self.items[a:b], dtype=np.int32), self.num_items, U, device,
+                                                                   ptr if flat.size else None, flat if flat.size else None)
+            model.audience_device(query, k, lists[a:b], scores[a:b])
+            ops.list_exposure(lists[a:b], counts)
+        rows = torch.empty(n, len(AUDIENCE_COLUMNS), dtype=torch.float32, device=device)
+        if n:
+            ops.audience_hits(lists, res["test_ptr"], res["test_users"], hits)
+            listed = lists >= 0
+            m = listed.sum(dim=1).double()
+            cnt = hits[:n].double()
+            rows[:, 0] = (cnt / (res["test_ptr"][1:] - res["test_ptr"][:-1]).double()).float()
+            rows[:, 1] = (cnt > 0).float()
+            rows[:, 2] = (torch.where(listed, res["length"][lists.clamp(min=0).long()], 0.0).sum(dim=1) / m).float()
+            rows[:, 3] = (torch.where(listed, scores.double(), 0.0).sum(dim=1) / m).float()
+        return rows, lists, scores, counts
+
+    def _item_table(self, rows):
+        return group_table(rows, self._resident(rows.device)["groups"], len(self.group_labels))
+
+    def evaluate(self, model, rows=None):
+        """(final, buf). final = AudienceTables: items [1 + item groups x 4] float32 -- row 0 = every item with a test interaction --
+        the means of AUDIENCE_COLUMNS; users [1 x 4] float64: exposure_summary of how often each user is listed, columns
+        AUDIENCE_EXPOSURE_COLUMNS. buf: per table a header of column names and one "%.8f" line per row (the shared table format).
+        rows: audience_rows(model) if the caller already holds it."""
+        rows, _, _, counts = self.audience_rows(model) if rows is None else rows
+        users = exposure_summary(counts.cpu().numpy(), [np.arange(self.num_users, dtype=np.int64)])[:, :len(AUDIENCE_EXPOSURE_COLUMNS)]
+        final = AudienceTables(AUDIENCE_COLUMNS, list(self.group_labels), self._item_table(rows), AUDIENCE_EXPOSURE_COLUMNS, [ALL], users)
+        buf = format_table(final.item_columns, final.item_labels, final.items) + "\n" + format_table(
+            final.user_columns, final.user_labels, final.users)
+        return final, buf
+
+    def shift(self, lists_te, lists_tie):
+        """How the audiences change from TE to TIE (two audience_rows() results of this report): (final [1 + item groups x 5]
+        float32, buf) over the columns self.shift_columns: overlap = |list a & list b| / k (ops.list_overlap) and d_<column> = TIE - TE
+        for every item column."""
+        rows_a, lists_a = lists_te[0], lists_te[1]
+        rows_b, lists_b = lists_tie[0], lists_tie[1]
+        n, k = len(self.items), self.k
+        if (tuple(lists_a.shape) != (n, k) or lists_a.shape != lists_b.shape or tuple(rows_a.shape) != (n, len(AUDIENCE_COLUMNS))
+                or rows_a.shape != rows_b.shape or len({t.device for t in (rows_a, rows_b, lists_a, lists_b)}) != 1):
+            raise ValueError("shift() takes two audience_rows() results of this report on one device")
+        cnt = torch.zeros(max(n, 1), dtype=torch.int32, device=lists_a.device)
+        if n:
+            ops.list_overlap(lists_a, lists_b, cnt)
+        rows = torch.cat(((cnt[:n].double() / k).float()[:, None], rows_b - rows_a), dim=1)
+        final = self._item_table(rows)
+        return final, format_table(self.shift_columns, self.group_labels, final)
+
+
 DIVERSIFY_COLUMNS = ("lambda", "recall", "ndcg", "ils_fused", "pop", "overlap", "coverage", "gini", "entropy")
 DiversifyTables = collections.namedtuple("DiversifyTables", ("columns", "labels", "table"))
 

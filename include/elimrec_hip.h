@@ -1218,6 +1218,39 @@ int elimrec_comm_all_reduce_f32(void *comm, float *d_buf, int64_t n, void *strea
 int elimrec_comm_all_to_all(void *comm, const void *d_send, void *d_recv, int64_t bytes_per_peer, void *stream);
 int elimrec_comm_all_to_all_v(void *comm, const void *d_send, void *d_recv, const int64_t *sizes, void *stream);
 
+/* Audience lists (csrc/audience.hip): per query item the K users with the largest predict() score for the (user, item) pair -- the
+ * reverse of elimrec_score_topk, which ranks items for users (models/EliMRec.py:96-113, 155-212); no counterpart in the reference.
+ * d_Y [U + I rows x >= (1 + S) d] as the scorers take it (users first, block 0 fused, block h + 1 head h), d_sqnorm
+ * [(U + I) x (1 + S)] from elimrec_row_sqnorms (needed when a head's cosine enters the score). fusion_mode 0 rubi / 1 hm / 2 sum,
+ * head_mask as elimrec_score_topk reads it (rubi multiplies the heads in the mask, hm and sum take every head), predict_type
+ * 0 normal / 1 TE / 2 TIE. For a pair (u, i):
+ *     ui = sigmoid(Y_u[block 0] . Y_i[block 0]),   cos_h = ((Y_u[h] . Y_i[h]) * inv(sq_u,h)) * inv(sq_i,h),  inv(x) = 1 / max(sqrt(x), 1e-12)
+ * fused as general_cm_fusion does, with the scorers' expressions in the math mode of elimrec_score_set_math; TIE subtracts the
+ * fusion at m_u = d_row_sum[u] / I_total, d_row_sum [U] from elimrec_score_topk_shard phase 1 over all users (not recomputed
+ * here). d_items int32 [Q]: the query items (duplicates allowed: identical lists). Per item d_idx / d_val (nullable) [Q x K] = the K
+ * best users by (score descending, user id ascending), -1 / -inf behind them when fewer than K users are eligible. Left out: the
+ * item's list of the nullable CSR d_excl_ptr int64 [Q + 1] / d_excl_users int32 (ids may repeat, in any order; a list may be
+ * empty). An item id outside [0, I) is not dereferenced and gives a row of fillers, an exclusion id outside [0, U) is ignored; the
+ * CSR pointers are the caller's to guarantee (the Python wrappers check all three on the host before any launch).
+ * d % 4 == 0, 4 <= d <= 256, 0 <= S <= 3, 1 <= K <= 256, U and I below 2^31. A block of a row is read only if the (fusion mode,
+ * head mask, predict type) uses it. No [U x Q] block is written: the grid is (item tiles x user chunks), a workgroup holds
+ * elimrec_audience_topk_tile() items (16 when K > 64 or d is neither 32 nor 64), streams elimrec_audience_topk_chunk() user rows
+ * through LDS and leaves each item's K best of the chunk in the workspace (16-byte aligned, elimrec_audience_topk_workspace bytes =
+ * Q * ceil(U / chunk) * K pairs, no initialisation needed; host-only, works without a GPU); elimrec_topk_merge ranks them.
+ * Deterministic: no float atomics; an item's list depends on its own row, the user table, d_row_sum, its exclusion list, K, d, S
+ * and the mode -- not on Q, its place in the query or the grid. Two launches on `stream`; exactly Q * K entries are written. */
+int elimrec_audience_topk(const float *d_Y, int64_t ldy, int64_t U, int64_t I, int d, int S, uint32_t head_mask, int fusion_mode,
+                          int predict_type, const float *d_sqnorm, const float *d_row_sum, int64_t I_total, const int32_t *d_items,
+                          int64_t Q, const int64_t *d_excl_ptr, const int32_t *d_excl_users, int K, int32_t *d_idx, float *d_val,
+                          void *d_workspace, size_t workspace_bytes, void *stream);
+size_t elimrec_audience_topk_workspace(int64_t Q, int64_t U, int K);
+int elimrec_audience_topk_chunk(void);
+int elimrec_audience_topk_tile(void);
+/* d_count[q] = the number of ids >= 0 of d_lists[q, :] (int32 [Q x K] contiguous) that occur in segment q of the CSR d_ptr int64
+ * [Q + 1] / d_users int32 (an item's test users, of any length). One wave per row, the integers are exact. K >= 1. */
+int elimrec_audience_hits(const int32_t *d_lists, int64_t Q, int K, const int64_t *d_ptr, const int32_t *d_users, int32_t *d_count,
+                          void *stream);
+
 #ifdef __cplusplus
 }
 #endif

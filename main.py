@@ -6,7 +6,7 @@
 Behaviour kept from the reference's `Net.run`: one pass of the pairwise sampler per epoch, validation every
 `test_step` epochs with predict_type TIE, a checkpoint + TE/TIE test pass whenever validation recall improves
 (not on epoch 0), early stop after `stop_cnt` epochs without improvement, the same log lines (`--group_view=[10,30,50,100]` adds
-the per-user-group table under each test line, `--effect_report=K` the effect breakdown of the top-K lists, `--rank_report=1` the test items' exact catalogue ranks, `--neighbour_report=K` the items' cosine neighbourhoods, fused against single-modal, `--list_report=K` the top-K lists' intra-list similarity and catalogue exposure, `--diversify_report=K` the top-N pools re-ranked to K items by greedy MMR per lambda, `--history_report=K` which items of the users' training histories back the top-K lists (`--history_top=T` named per pair), `--significance_report=R` bootstrap intervals of the test metrics over the test users and the paired TE->TIE difference with its p-value, `--neg_sampling=hard` trains on the best of `--neg_candidates=M` uniform negatives per triplet under the last forward's tables; validation and model selection stay on the overall metrics). The per-batch work,
+the per-user-group table under each test line, `--effect_report=K` the effect breakdown of the top-K lists, `--rank_report=1` the test items' exact catalogue ranks, `--neighbour_report=K` the items' cosine neighbourhoods, fused against single-modal, `--list_report=K` the top-K lists' intra-list similarity and catalogue exposure, `--audience_report=K` the test items' top-K audiences (the users the model ranks highest per item), `--diversify_report=K` the top-N pools re-ranked to K items by greedy MMR per lambda, `--history_report=K` which items of the users' training histories back the top-K lists (`--history_top=T` named per pair), `--significance_report=R` bootstrap intervals of the test metrics over the test users and the paired TE->TIE difference with its p-value, `--neg_sampling=hard` trains on the best of `--neg_candidates=M` uniform negatives per triplet under the last forward's tables; validation and model selection stay on the overall metrics). The per-batch work,
 the sampler and the evaluator run on the GPU (elimrec_amd). `--data.input.dataset=synthetic` uses the seeded
 Tiktok-shape generator instead of reading files.
 
@@ -111,6 +111,11 @@ class Net(object):
         self.list_report = int(cfg["list_report"]) if "list_report" in cfg else 0
         if self.list_report and self.world > 1:
             raise ValueError("--list_report needs the whole cached item table on one rank: it is single-GPU")
+        # --audience_report=K (default 0: off): under each [TEST] line the test items' top-K audiences (whom the item would be pushed
+        # to, its training users left out), after both effects how the audiences change from TE to TIE
+        self.audience_report = int(cfg["audience_report"]) if "audience_report" in cfg else 0
+        if self.audience_report and self.world > 1:
+            raise ValueError("--audience_report needs the whole cached tables on one rank: it is single-GPU")
         # --diversify_report=K (default 0: off): under each [TEST] line the top-N pools (--diversify_pool) re-ranked to K items by
         # greedy MMR at every --diversify_lambda: recall / NDCG against intra-list similarity, popularity and exposure
         self.diversify_report = int(cfg["diversify_report"]) if "diversify_report" in cfg else 0
@@ -257,7 +262,7 @@ class Net(object):
 
     def test_all_effects(self):
         """TE and TIE metrics on the test split, formatted as the reference prints them."""
-        rec, lines, ranks, shown, backed, sure = self.recommender, {}, {}, {}, {}, {}
+        rec, lines, ranks, shown, backed, sure, reached = self.recommender, {}, {}, {}, {}, {}, {}
         if self.grouped:
             Logger.info(rec.test_evaluator.metrics_info())
         for effect in EFFECTS:
@@ -277,6 +282,10 @@ class Net(object):
                 shown[effect] = rec.list_reporter.list_rows(rec)
                 Logger.info("  [{}] top-{} lists: similarity, popularity, exposure:\n{}".format(
                     effect, self.list_report, rec.list_reporter.evaluate(rec, shown[effect])[1]))
+            if self.audience_report:       # the reverse lists under this effect: whom each test item reaches
+                reached[effect] = rec.audience_reporter.audience_rows(rec)
+                Logger.info("  [{}] top-{} audiences of the test items: reach, activity, exposure over the users:\n{}".format(
+                    effect, self.audience_report, rec.audience_reporter.evaluate(rec, reached[effect])[1]))
             if self.diversify_report:      # the top-N pools under this effect re-ranked to K by greedy MMR, one row per lambda
                 reporter = rec.diversify_reporter
                 Logger.info("  [{}] top-{} of the top-{} pools by MMR, per lambda:\n{}".format(
@@ -295,6 +304,8 @@ class Net(object):
         if self.list_report:               # overlap: the share of the TE list that TIE keeps; d_<column>: TIE - TE
             a, b = shown["TE"], shown["TIE"]
             Logger.info("  [TE->TIE] list shift:\n{}".format(rec.list_reporter.shift(a[0], a[2], b[0], b[2])[1]))
+        if self.audience_report:           # overlap: the share of an item's TE audience that TIE keeps; d_<column>: TIE - TE
+            Logger.info("  [TE->TIE] audience shift:\n{}".format(rec.audience_reporter.shift(reached["TE"], reached["TIE"])[1]))
         if self.history_report:            # d_<column>: TIE - TE; a positive d_unexpected_<space>: TIE strays further from the history
             Logger.info("  [TE->TIE] history support shift:\n{}".format(rec.history_reporter.shift(backed["TE"], backed["TIE"])[1]))
         if self.significance_report:       # TIE - TE per user, the users resampled as pairs; p: two-sided, "no difference"
