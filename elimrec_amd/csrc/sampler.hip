@@ -7,7 +7,8 @@
 namespace elimrec {
 
 // One id uniform over [0, I) outside the sorted training items [beg, end): rejection over the draw rounds 1 .. 255 of the stream
-// whose counter word 3 is c3_low (low 24 bits) | round << 24, two 64-bit draws per round; ph.c[0 .. 2] and the key are the caller's.
+// whose counter word 3 is c3_low (low 24 bits) | round << 24, two 64-bit draws per round (output words 0, 1 and then 2, 3, high
+// word first, each % I); ph.c[0 .. 2] and the key are the caller's. tests/sampler_model.py is the executable form of the streams.
 __device__ inline int64_t draw_outside(Philox &ph, uint32_t c3_low, const int32_t *__restrict__ items, int64_t beg, int64_t end,
                                        int64_t I) {
     uint32_t r[4];
@@ -39,7 +40,8 @@ __device__ inline int64_t draw_outside(Philox &ph, uint32_t c3_low, const int32_
     return cand;
 }
 
-// The user and the positive of triplet i: the stream's round 0 (counter word 3 = the epoch's bits 32 .. 55, top byte 0).
+// The user and the positive of triplet i: the stream's round 0 (counter word 3 = the epoch's bits 32 .. 55, top byte 0): the user's
+// slot is the 64-bit draw of output words 0, 1 % n_train_users, the positive's place in the slice that of words 2, 3 % its length.
 // -> the user's slice [beg, end) of items; ph is left keyed by seed with c[0 .. 2] = (i, epoch's low word).
 __device__ inline void draw_user_pos(Philox &ph, int64_t i, uint64_t seed, uint64_t epoch, const int32_t *__restrict__ user_ids,
                                      const int64_t *__restrict__ ptr, const int32_t *__restrict__ items, int64_t n_train_users,
@@ -94,10 +96,16 @@ __global__ void sample_triplet_candidates_kernel(const int32_t *__restrict__ use
 
 // Distinct negatives per user for sampled-negative evaluation (data/dataset.py:270-288; random_choice.pyx:20-62 with
 // replace=False): n_neg distinct ids uniform over [0, I) minus the user's sorted exclusion list. One wave per user draws
-// RANKS in [0, M), M = I - |exclusion|, 64 at a time (Philox keyed by (seed, user), counter = draw round), keeps those not
+// RANKS in [0, M), M = I - |exclusion|, 64 at a time (Philox: the key is the seed's two words, the counter (u lo, u hi, draw
+// round, lane); the rank is the 64-bit draw of output words 0 and 1, % M), keeps those not
 // drawn before -- the accepted ranks in LDS, duplicates within a round resolved in lane order -- and maps rank r to the
 // r-th id not excluded (binary search over e_j - j, non-decreasing for a sorted unique list). Each kept rank is uniform
 // over the ranks not yet kept: the draws are a uniform random n_neg-subset, in draw order.
+// The closing fallback (NEG_ROUNDS rounds without n_neg distinct ranks) is UNREACHABLE for n_neg <= NEG_MAX and is kept as a
+// guard against an endless loop only. Dropping duplicates in lane order makes the rounds one sequence of T = 64 * 2^16 = 4.19e6
+// draws, and the fallback needs more than M - n_neg ranks undrawn after them. The slowest case the host admits is n_neg = 16000 of
+// M = 16001 (on average M (H_M - 1) = 1.48e5 draws, 2.3e3 rounds): two given ranks are both undrawn with probability
+// (1 - 2 / M)^T = e^-524, over M^2 / 2 = 1.3e8 pairs P < 1e-219; a smaller n_neg or a larger M lowers it further.
 constexpr int NEG_MAX = 16000;
 constexpr uint32_t NEG_ROUNDS = 1u << 16;
 
@@ -134,7 +142,7 @@ __global__ __launch_bounds__(64) void sample_negatives_kernel(const int64_t *__r
         n_acc = min(n_neg, n_acc + __popcll(ok));
         __syncthreads();
     }
-    if (n_acc < n_neg) {        // 2^16 rounds without completing (M barely above n_neg and large): the smallest ranks left
+    if (n_acc < n_neg) {        // 2^16 rounds without completing: the smallest ranks left (unreachable for n_neg <= NEG_MAX, see above)
         if (lane == 0)
             for (int32_t c = 0; n_acc < n_neg; ++c) {
                 bool in = false;

@@ -7,9 +7,23 @@ training loop does no per-batch host->device copy.
 Contract (tests/test_hip_parity.py::test_sampler_contract_on_device): users uniform with replacement over users that have >= 1
 training item; positives uniform over that user's training items; negatives uniform over the
 catalogue minus the user's training items. The draws are i.i.d., so the reference's extra
-`shuffle` pass is a distributional no-op and is not repeated. The random stream is Philox keyed
-by (seed, epoch) -- the reference's libc rand() stream cannot be reproduced on a GPU and is
+`shuffle` pass is a distributional no-op and is not repeated. The random stream is Philox, a function
+of (seed, epoch) -- the reference's libc rand() stream cannot be reproduced on a GPU and is
 never seeded there either (random_choice.pyx:8).
+
+The stream itself is pinned too (tests/test_sampler_gpu.py, bit for bit against tests/sampler_model.py, the executable form of
+include/elimrec_hip.h's comment), which is what lets a resumed run replay epoch e of its seed. Triplet i of epoch e takes the output
+words r0 .. r3 of Philox4x32-10 with key (seed & 0xffffffff, seed >> 32) and counter (i & 0xffffffff, i >> 32, e & 0xffffffff,
+low24 | round << 24), low24 = (e >> 32) & 0xffffff (bits 56 .. 63 of the epoch are dropped):
+  round 0: the user is the ((r0 << 32 | r1) % n_train_users)-th key of the training dict, the positive the ((r2 << 32 | r3) % count)-th
+    of its items in ascending order;
+  rounds 1 .. 255: the candidates (r0 << 32 | r1) % num_items and (r2 << 32 | r3) % num_items; the first one, in that order, outside
+    the user's training items is the negative;
+  after 510 rejected candidates: the smallest id the user does not hold. This fallback is biased (always the smallest missing id)
+    and reached only by users who hold nearly the whole catalogue: with probability (1 - f)^510 when the fraction f is missing.
+The `%` reductions carry a relative bias of at most m / 2^64. With shard=(rank, world) the process draws the first
+ceil(num_trainings / world) triplets of its own seed's stream. Candidate column j >= 1 of neg_sampling="hard" is the same rejection
+loop and fallback with low24 = j.
 
 neg_sampling="hard" (dynamic negative sampling, not in the reference): M = neg_candidates uniform candidates are drawn per triplet
 -- column 0 is the uniform sampler's negative -- and the epoch trains on the one the model's cached tables score highest

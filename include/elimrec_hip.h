@@ -768,9 +768,23 @@ int elimrec_bootstrap_rows_in_lds(int64_t n_g, int C);
  * n triplets: user uniform over the `n_train_users` users with >= 1 training item (with
  * replacement), positive uniform over that user's training items, negative uniform over [0,I)
  * rejecting the user's training items (data/sampler.py:93-126; random_choice.pyx:20-62).
- * Counter-based Philox4x32-10 keyed by (seed, epoch): the stream differs from libc rand() by
- * construction; the contract is distributional. d_user_ids int32[n_train_users]; d_ptr
- * int64[n_train_users+1]; d_items int32 sorted ascending within each user. */
+ * Counter-based Philox4x32-10, a function of (seed, epoch, i): the stream differs from libc rand() by
+ * construction; against the reference the contract is distributional. d_user_ids int32[n_train_users]; d_ptr
+ * int64[n_train_users+1]; d_items int32 sorted ascending within each user.
+ * The stream is part of the contract too (a resumed run replays epoch e of its seed); tests/sampler_model.py is its executable
+ * form. Triplet i = 0 .. n - 1, output words r0 .. r3 of Philox4x32-10 with
+ *     key (seed & 0xffffffff, seed >> 32) and counter (i & 0xffffffff, i >> 32, epoch & 0xffffffff, low24 | round << 24),
+ *     low24 = (epoch >> 32) & 0xffffff -- bits 56 .. 63 of the epoch are dropped; a 64-bit draw is (hi << 32 | lo) of two words:
+ *   round 0:         ui = (r0 << 32 | r1) % n_train_users, the user is d_user_ids[ui] with the slice [beg, end) = d_ptr[ui, ui + 1];
+ *                    the positive is d_items[beg + (r2 << 32 | r3) % (end - beg)];
+ *   rounds 1 .. 255: two candidates per round, (r0 << 32 | r1) % I and then (r2 << 32 | r3) % I; the negative is the first
+ *                    candidate, in round and then word order, that is not in the user's slice;
+ *   fallback:        all 510 candidates were the user's items: the negative is the smallest k >= 0 with d_items[beg + k] != k
+ *                    (k = end - beg if there is none), the smallest id the user does not hold.
+ * The `%` reductions are not exactly uniform: a value's probability is floor or ceil of 2^64 / m over 2^64, a relative bias of at
+ * most m / 2^64 (< 2^-33 for m < 2^31). The fallback is biased outright, always the smallest missing id, and is taken with
+ * probability (1 - f)^510 by a user with the fraction f of the catalogue missing: 6e-3 at f = 1 %, 0.78 with 2 of 4096 ids
+ * missing -- users who hold nearly the whole catalogue only. */
 int elimrec_sample_triplets(const int32_t *d_user_ids, const int64_t *d_ptr, const int32_t *d_items,
                             int64_t n_train_users, int64_t I, int64_t n, uint64_t seed,
                             uint64_t epoch, int64_t *d_users, int64_t *d_pos, int64_t *d_neg,
@@ -781,8 +795,10 @@ int elimrec_sample_triplets(const int32_t *d_user_ids, const int64_t *d_ptr, con
  * (seed, epoch, i). d_cands int32 [n x n_cand] contiguous: column 0 is bit for bit elimrec_sample_triplets' negative; every column
  * j > 0 is an independent uniform draw over [0, I) minus the user's training items, by the same rejection loop and fallback, from
  * the Philox stream whose counter word 3 carries j in its low 24 bits (elimrec_sample_triplets has the epoch's bits 32 .. 55 there:
- * no (i, epoch < 2^32, round) of it reaches such a counter; csrc/sampler.hip). Drawn with replacement: a triplet may list an id
- * twice. 1 <= n_cand <= 64, I < 2^31 - 1, n < 2^31. */
+ * no (i, epoch < 2^32, round) of it reaches such a counter; csrc/sampler.hip). In the terms of elimrec_sample_triplets' stream:
+ * column j >= 1 runs rounds 1 .. 255 and the fallback with low24 = j; round 0 (the user and the positive) is shared by all columns.
+ * At an epoch >= 2^32 whose bits 32 .. 55 equal j, 1 <= j < n_cand, column j repeats column 0. Drawn with replacement: a triplet
+ * may list an id twice. 1 <= n_cand <= 64, I < 2^31 - 1, n < 2^31. */
 int elimrec_sample_triplet_candidates(const int32_t *d_user_ids, const int64_t *d_ptr, const int32_t *d_items,
                                       int64_t n_train_users, int64_t I, int64_t n, uint64_t seed, uint64_t epoch, int n_cand,
                                       int64_t *d_users, int64_t *d_pos, int32_t *d_cands, void *stream);
@@ -790,9 +806,18 @@ int elimrec_sample_triplet_candidates(const int32_t *d_user_ids, const int64_t *
 /* Negatives of sampled-negative evaluation (the reference's data/dataset.py:270-288; util/cython/random_choice.pyx:20-62,
  * replace=False): per user row u, n_neg DISTINCT ids uniform over [0, I) minus the row's exclusion list d_excl_items
  * [d_excl_ptr[u], d_excl_ptr[u+1]) (sorted ascending, unique, inside [0, I): the user's train + valid + test items).
- * d_out int32 [n_users x n_neg], in draw order. Philox4x32-10 keyed by (seed, u): the contract is distributional, as for
- * elimrec_sample_triplets. The caller rejects I - |exclusion| <= n_neg ("There is not enough integers to be sampled.",
- * random_choice.pyx:35-37); such a row comes back as -1. 0 < n_neg <= 16000. */
+ * d_out int32 [n_users x n_neg], in draw order. Philox4x32-10, a function of (seed, u): against the reference the contract is
+ * distributional, as for elimrec_sample_triplets. The caller rejects I - |exclusion| <= n_neg ("There is not enough integers to be
+ * sampled.", random_choice.pyx:35-37); such a row comes back as -1. 0 < n_neg <= 16000.
+ * The stream (the evaluation negatives are a function of the seed alone; tests/sampler_model.py is the executable form): user u
+ * with the exclusion list e_0 < e_1 < ... of length m draws RANKS in [0, M), M = I - m. Draw (round, lane), round = 0, 1, ...,
+ * lane = 0 .. 63, is
+ *     (r0 << 32 | r1) % M   of Philox4x32-10 with key (seed & 0xffffffff, seed >> 32), counter (u & 0xffffffff, u >> 32, round, lane)
+ * (words r2, r3 are not used; the relative bias of the `%` is at most M / 2^64). The draws are taken round by round and within a
+ * round in lane order; a rank that was kept before, or that an earlier lane of the same round drew, is dropped, every other one
+ * is kept until n_neg are; the last round's surplus is dropped. Kept rank r becomes the id r + #{j : e_j - j <= r}, the r-th id
+ * (from 0) outside the list. A closing fallback after 2^16 rounds (the smallest ranks not kept) cannot be reached with
+ * n_neg <= 16000 (csrc/sampler.hip has the arithmetic). */
 int elimrec_sample_negatives(const int64_t *d_excl_ptr, const int32_t *d_excl_items, int64_t n_users, int64_t I,
                              int n_neg, uint64_t seed, int32_t *d_out, void *stream);
 
