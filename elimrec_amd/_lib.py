@@ -173,6 +173,7 @@ SIGNATURES = {
     "elimrec_sum": (c_i32, [c_ptr, c_i64, c_ptr, c_ptr]),
     "elimrec_segment_reduce_workspace": (c_size, [c_i64]),
     "elimrec_segment_plan_workspace": (c_size, [c_i64]),
+    "elimrec_segment_plan_form": (c_i32, [c_i64, c_i64]),
     "elimrec_segment_plan": (c_i32, [c_ptr, c_i64, c_i32, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
     "elimrec_segment_apply_head_bwd": (c_i32, [c_ptr, c_i64, c_i32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_i64, c_i32,
                                                c_i32, c_i32, ctypes.POINTER(c_i32), c_ptr, c_ptr, ctypes.POINTER(c_ptr), c_ptr,
@@ -372,7 +373,7 @@ class _Recording(object):
                              "elimrec_cosine_topk_chunk", "elimrec_cosine_topk_tile",
                              "elimrec_audience_topk_chunk", "elimrec_audience_topk_tile",
                              "elimrec_list_max_k", "elimrec_list_pair_cosine_small_k", "elimrec_list_pair_cosine_chunk_cols",
-                             "elimrec_mmr_max_pool", "elimrec_mmr_rows_in_lds",
+                             "elimrec_mmr_max_pool", "elimrec_mmr_rows_in_lds", "elimrec_segment_plan_form",
                              "elimrec_comm_create", "elimrec_comm_destroy", "elimrec_comm_nranks") or name.startswith("elimrec_program_")
             setattr(self, name, self._wrap(fn, name) if res is c_i32 and not plain else fn)
 

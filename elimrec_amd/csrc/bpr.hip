@@ -1348,6 +1348,24 @@ extern "C" size_t elimrec_segment_reduce_workspace(int64_t n) { return elimrec_s
 
 static int plan_fast_max_keys() { return 1 << 30; }          // (the one-workgroup planner for every batch size)
 
+// dynamic LDS of segment_plan_kernel: bitmap + prefix words, the scan's wave sums, the long-list table, counts, offsets, members
+static size_t plan_lds_bytes(int64_t key_space) {
+    return ((size_t)2 * ((key_space + 31) / 32) + 16 + 1024) * sizeof(uint32_t) + (size_t)(3 * PLAN_LDS_N + 1) * sizeof(int32_t);
+}
+
+// Which planner a key list gets: 0 = one workgroup (the slots and the key bitmap fit its LDS), 1 = the device-wide bitmap plan
+// (a bitmap word per slot at the most: the workspace holds it), 2 = the radix sort (key space unknown or too sparse, or
+// ELIMREC_PLAN_SORTED=1 -- read on every call, a host getenv).
+static int plan_form(int64_t n, int64_t key_space) {
+    if (key_space > 0 && key_space <= plan_fast_max_keys() && n <= PLAN_LDS_N && plan_lds_bytes(key_space) <= 160 * 1024) return 0;
+    const char *e = getenv("ELIMREC_PLAN_SORTED");
+    const bool sorted_only = e && e[0] == '1';
+    if (key_space > 0 && (key_space + 31) / 32 <= n && !sorted_only) return 1;
+    return 2;
+}
+
+extern "C" int elimrec_segment_plan_form(int64_t n, int64_t key_space) { return plan_form(n, key_space); }
+
 static int segment_plan_impl(const int32_t *d_keys, int64_t n, int32_t split_key, int64_t key_space,
                              int32_t *d_active_rows, int32_t *d_seg_info, int32_t *d_slot_seg,
                              uint32_t *d_key_bitmap, void *d_workspace, size_t workspace_bytes, void *stream,
@@ -1391,9 +1409,9 @@ static int segment_plan_impl(const int32_t *d_keys, int64_t n, int32_t split_key
     int32_t *vs = (int32_t *)(ws + L.vals_sorted), *flag = (int32_t *)(ws + L.flag);
     int32_t *segid = (int32_t *)(ws + L.segid), *seg_start = (int32_t *)(ws + L.seg_start);
     hipStream_t s = (hipStream_t)stream;
-    const size_t plan_lds = ((size_t)2 * ((key_space + 31) / 32) + 16 + 1024) * sizeof(uint32_t) +
-                            (size_t)(3 * PLAN_LDS_N + 1) * sizeof(int32_t);
-    if (key_space > 0 && key_space <= plan_fast_max_keys() && n <= PLAN_LDS_N && plan_lds <= 160 * 1024) {
+    const int form = plan_form(n, key_space);
+    if (form == 0) {
+        const size_t plan_lds = plan_lds_bytes(key_space);
         static size_t lds_set = 0;
         if (plan_lds > 64 * 1024 && plan_lds > lds_set) {
             hipError_t ea = hipFuncSetAttribute((const void *)segment_plan_kernel,
@@ -1407,9 +1425,7 @@ static int segment_plan_impl(const int32_t *d_keys, int64_t n, int32_t split_key
         return 0;
     }
     const int64_t nw_words = (key_space + 31) / 32;
-    static int sorted_only = -1;
-    if (sorted_only < 0) { const char *e = getenv("ELIMREC_PLAN_SORTED"); sorted_only = (e && e[0] == '1') ? 1 : 0; }
-    if (key_space > 0 && nw_words <= n && !sorted_only) {
+    if (form == 1) {
         // the bitmap plan, device-wide (see plan_bits_kernel): bm = the caller's key bitmap or the (unused) vals_in array, pre in
         // keys_sorted, counters in flag, the rank sort's scratch in segid, member lists in vals_sorted -- where segment_apply and
         // the head backward look for them

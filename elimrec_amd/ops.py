@@ -501,6 +501,12 @@ def segment_plan_workspace(n):
     return int(_lib.load().elimrec_segment_plan_workspace(n))
 
 
+def segment_plan_form(n, key_space):
+    """The planner segment_plan / batch_plan (n = 3B, key_space = U + I) runs for these sizes: 0 = one workgroup, 1 = the
+    device-wide bitmap plan, 2 = the radix sort (also under ELIMREC_PLAN_SORTED=1 wherever 1 would run). Host only."""
+    return int(_lib.load().elimrec_segment_plan_form(int(n), int(key_space)))
+
+
 def segment_plan(keys, split_key, key_space, active_rows, seg_info, slot_seg, workspace, key_bitmap=None):
     """Plan of a key list: active_rows (sorted unique keys), seg_info, slot_seg (segment of every slot); the member
     lists stay in `workspace` for segment_apply. key_bitmap (int32 words, >= key_space bits): bit k <=> k is active."""

@@ -333,6 +333,11 @@ size_t elimrec_segment_reduce_workspace(int64_t n);
  * 0 <= key < key_space and selects the one-workgroup bitmap planner for n <= 8192 when the bitmap fits LDS (same
  * output as the radix-sort path, which is used otherwise). APPLY sums rows per segment in ascending slot order, times *d_scale. */
 size_t elimrec_segment_plan_workspace(int64_t n);
+/* Which planner elimrec_segment_plan / elimrec_batch_plan (n = 3B, key_space = U + I) runs for these sizes -- host only, the very
+ * decision the planner takes: 0 = one workgroup (n <= 8192 and the key bitmap fits its LDS), 1 = the device-wide bitmap plan
+ * (key_space > 0 and (key_space + 31) / 32 <= n), 2 = the radix sort (otherwise, and wherever 1 would run under
+ * ELIMREC_PLAN_SORTED=1, which is read on every call). All three give the same plan bit for bit. */
+int elimrec_segment_plan_form(int64_t n, int64_t key_space);
 int elimrec_segment_plan(const int32_t *d_keys, int64_t n, int32_t split_key, int64_t key_space,
                          int32_t *d_active_rows, int32_t *d_seg_info, int32_t *d_slot_seg,
                          uint32_t *d_key_bitmap /* nullable [(key_space+31)/32]: bit k set <=> k is an active key */,

@@ -1806,7 +1806,7 @@ def test_large_batch_step_paths_vs_oracle_and_each_other(monkeypatch):
     alternating buffer sets. The first step's loss against the oracle (1e-5); eight steps -- losses, parameters, Adam moments --
     bitwise equal with and without prestage and with the radix-sort planner (ELIMREC_PLAN_SORTED=1)."""
     from oracle import elimrec_oracle as eo
-    from elimrec_amd import ColumnShardEngine, ColumnShardTrainer, EliMRec, FusedAdam, SyntheticDataset, set_seed
+    from elimrec_amd import ColumnShardEngine, ColumnShardTrainer, EliMRec, FusedAdam, SyntheticDataset, ops, set_seed
     cfg = make_config(["--data.input.dataset=synthetic", "--alpha=0.5", "--loss=bpr_loss", "--recdim=64", "--verbose=0"])
     U, I, B = 2000, 6000, 4096
     ds = SyntheticDataset(U, I, 60000, feat_dims=(16, 8, 12), seed=2)
@@ -1816,6 +1816,7 @@ def test_large_batch_step_paths_vs_oracle_and_each_other(monkeypatch):
     got = {}
     for form in ("prestaged", "plain", "sorted"):
         monkeypatch.setenv("ELIMREC_PLAN_SORTED", "1" if form == "sorted" else "0")
+        assert ops.segment_plan_form(3 * B, U + I) == (2 if form == "sorted" else 1)
         set_seed(5)
         model = EliMRec(cfg, ds)
         init = {k: v.detach().clone().numpy() for k, v in model.state_dict().items()}
