@@ -8,7 +8,7 @@ from torch import nn
 
 from . import ops
 from .evaluator import ProxyEvaluator, UniEvaluator
-from .reports import AudienceReport, DiversifyReport, EffectReport, HistoryReport, ListReport, NeighbourReport, RankReport, SignificanceReport
+from .reports import AudienceReport, CalibrationReport, DiversifyReport, EffectReport, HistoryReport, ListReport, NeighbourReport, RankReport, SignificanceReport
 
 
 class BasicModel(nn.Module):
@@ -87,6 +87,19 @@ class BasicModel(nn.Module):
             lambdas = config["diversify_lambda"] if "diversify_lambda" in config else [1.0, 0.9, 0.7, 0.5]
             self.diversify_reporter = DiversifyReport(dataset, train, dataset.get_user_test_dict(), k_div, pool=pool, lambdas=lambdas,
                                                       group_view=config["group_view"])
+        # --calibrate_report=K (CLI-only, default 0 = off): the test users' top-N pools (--calibrate_pool=N, default min(4K, 256, the
+        # catalogue)) re-ranked to K items towards each user's own mix of item popularity classes (--item_group_view, required) at
+        # every --calibrate_lambda (default [1.0,0.9,0.7,0.5]): the lists' miscalibration and class shares against recall / NDCG,
+        # overall and per user group (reports.CalibrationReport)
+        k_cal = int(config["calibrate_report"]) if "calibrate_report" in config else 0
+        self.calibrate_reporter = None
+        if k_cal:
+            if item_view is None:
+                raise ValueError("--calibrate_report needs --item_group_view=[...]: the item classes are its popularity buckets")
+            pool = config["calibrate_pool"] if "calibrate_pool" in config else None
+            lambdas = config["calibrate_lambda"] if "calibrate_lambda" in config else [1.0, 0.9, 0.7, 0.5]
+            self.calibrate_reporter = CalibrationReport(dataset, train, dataset.get_user_test_dict(), k_cal, item_view, pool=pool,
+                                                        lambdas=lambdas, group_view=config["group_view"])
         # --history_report=K (CLI-only, default 0 = off): which items of the test users' training histories back their top-K lists
         # (--history_top=T entries named per pair, default 3): the largest and the mean cosine of the history to each listed item
         # and the unexpectedness 1 - max, in the fused space and in each head's, overall and per user group (reports.HistoryReport)

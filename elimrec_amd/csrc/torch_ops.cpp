@@ -23,6 +23,11 @@
 //   list_exposure(lists i32[B x K], n_rows) -> i32[n_rows]: how often every row is listed
 //   mmr_rerank(table f32[n x d], sqnorm f32[n], pool_idx i32[B x N], pool_val f32[B x N], K, lam) -> (idx i32, pos i32, val f32) [B x K]:
 //       greedy maximal-marginal-relevance re-ranking of each pool (unlisted entries are never picked; -1 / -1 / -inf fillers)
+//   calibrate_rerank(pool_idx i32[B x N], pool_val f32[B x N], class_of i32[I], target f32[B x C], K, lam, smooth) -> (idx i32, pos i32, val f32)
+//       [B x K]: greedy calibrated re-ranking of each pool towards the row's target class shares, the objective in float64
+//       (lam weighs the relevance; csrc/calibrate.hip)
+//   list_calibration(lists i32[B x K], class_of i32[I], C, target f32[B x C], smooth) -> (shares f32[B x C], kl f32[B]): the class shares of
+//       every list and its miscalibration C_KL against the row's target
 //   pick_hard_negatives(user_table f32[U x blocks*d], user_sqnorm f32[U x blocks], item_table f32[I x blocks*d], item_sqnorm, weights
 //     float[blocks], users i64[n], cands i32[n x M]) -> (neg i64, pos i32, score f32) [n]: per triplet the listed candidate with the largest
 //     sum_b w_b cos_b(u, i), the lowest column among equals; -1 / -1 / -inf without one (csrc/hardneg.hip)
@@ -541,6 +546,46 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> mmr_rerank(const at::Tensor &tabl
     return {idx, pos, val};
 }
 
+// ---- calibrated re-ranking of top-N pools towards per-user class shares; class shares and miscalibration of lists
+std::tuple<at::Tensor, at::Tensor, at::Tensor> calibrate_rerank(const at::Tensor &pool_idx, const at::Tensor &pool_val, const at::Tensor &class_of,
+                                                                const at::Tensor &target, int64_t K, double lam, double smooth) {
+    need(pool_idx, "pool_idx", at::kInt, 2); need(pool_val, "pool_val", at::kFloat, 2); need(class_of, "class_of", at::kInt, 1);
+    const at::Tensor pi = pool_idx.contiguous(), pv = pool_val.contiguous(), cl = class_of.contiguous(), tg = rowmajor(target, "target");
+    const int64_t B = pi.size(0), N = pi.size(1), C = tg.size(1);
+    TORCH_CHECK(pi.sizes() == pv.sizes(), "elimrec::calibrate_rerank: pool_idx and pool_val must have one shape [B x N]");
+    TORCH_CHECK(K >= 1 && K <= N && N <= elimrec_mmr_max_pool(), "elimrec::calibrate_rerank: 1 <= K <= N <= ", elimrec_mmr_max_pool(),
+                ", got K ", K, ", N ", N);
+    TORCH_CHECK(tg.size(0) == B && C >= 1 && C <= elimrec_calibrate_max_classes(), "elimrec::calibrate_rerank: target must be [", B,
+                " x C], 1 <= C <= ", elimrec_calibrate_max_classes(), ", got [", tg.size(0), " x ", C, "]");
+    TORCH_CHECK(lam >= 0.0 && lam <= 1.0, "elimrec::calibrate_rerank: 0 <= lam <= 1, got ", lam);
+    TORCH_CHECK(smooth > 0.0 && smooth < 1.0, "elimrec::calibrate_rerank: 0 < smooth < 1, got ", smooth);
+    at::Tensor idx = at::empty({B, K}, pi.options()), pos = at::empty({B, K}, pi.options()), val = at::empty({B, K}, pv.options());
+    if (B == 0) return {idx, pos, val};
+    check(elimrec_calibrate_rerank(pi.data_ptr<int32_t>(), pv.data_ptr<float>(), B, (int)N, (int)K, cl.data_ptr<int32_t>(), cl.numel(),
+                                   tg.data_ptr<float>(), B > 1 ? std::max<int64_t>(C, tg.stride(0)) : C, (int)C, lam, smooth,
+                                   idx.data_ptr<int32_t>(), pos.data_ptr<int32_t>(), val.data_ptr<float>(), cur_stream()),
+          "calibrate_rerank");
+    return {idx, pos, val};
+}
+
+std::tuple<at::Tensor, at::Tensor> list_calibration(const at::Tensor &lists, const at::Tensor &class_of, int64_t C, const at::Tensor &target,
+                                                    double smooth) {
+    need(lists, "lists", at::kInt, 2); need(class_of, "class_of", at::kInt, 1);
+    const at::Tensor l = lists.contiguous(), cl = class_of.contiguous(), tg = rowmajor(target, "target");
+    const int64_t B = l.size(0), K = l.size(1);
+    TORCH_CHECK(K >= 1, "elimrec::list_calibration: lists [B x K] with K >= 1");
+    TORCH_CHECK(C >= 1 && C <= elimrec_calibrate_max_classes(), "elimrec::list_calibration: 1 <= C <= ", elimrec_calibrate_max_classes(), ", got ", C);
+    TORCH_CHECK(tg.size(0) == B && tg.size(1) == C, "elimrec::list_calibration: target must be [", B, " x ", C, "]");
+    TORCH_CHECK(smooth > 0.0 && smooth < 1.0, "elimrec::list_calibration: 0 < smooth < 1, got ", smooth);
+    at::Tensor shares = at::empty({B, C}, tg.options()), kl = at::empty({B}, tg.options());
+    if (B == 0) return {shares, kl};
+    check(elimrec_list_calibration(l.data_ptr<int32_t>(), B, (int)K, cl.data_ptr<int32_t>(), cl.numel(), (int)C, shares.data_ptr<float>(),
+                                   tg.data_ptr<float>(), B > 1 ? std::max<int64_t>(C, tg.stride(0)) : C, smooth, kl.data_ptr<float>(),
+                                   cur_stream()),
+          "list_calibration");
+    return {shares, kl};
+}
+
 // ---- hard-negative pick: per triplet the best of M candidates over the tables' column blocks
 std::tuple<at::Tensor, at::Tensor, at::Tensor> pick_hard_negatives(const at::Tensor &user_table, const at::Tensor &user_sqnorm,
                                                                    const at::Tensor &item_table, const at::Tensor &item_sqnorm,
@@ -782,6 +827,8 @@ TORCH_LIBRARY(elimrec, m) {
     m.def("list_pair_cosine(Tensor table, Tensor sqnorm, Tensor lists, int blocks) -> Tensor");
     m.def("list_exposure(Tensor lists, int n_rows) -> Tensor");
     m.def("mmr_rerank(Tensor table, Tensor sqnorm, Tensor pool_idx, Tensor pool_val, int K, float lam) -> (Tensor, Tensor, Tensor)");
+    m.def("calibrate_rerank(Tensor pool_idx, Tensor pool_val, Tensor class_of, Tensor target, int K, float lam, float smooth) -> (Tensor, Tensor, Tensor)");
+    m.def("list_calibration(Tensor lists, Tensor class_of, int C, Tensor target, float smooth) -> (Tensor, Tensor)");
     m.def("pick_hard_negatives(Tensor user_table, Tensor user_sqnorm, Tensor item_table, Tensor item_sqnorm, float[] weights, Tensor users, "
           "Tensor cands) -> (Tensor, Tensor, Tensor)");
     m.def("history_support(Tensor table, Tensor sqnorm, float[] weights, Tensor users, Tensor lists, Tensor hist_ptr, Tensor hist_items, int top, "
@@ -818,6 +865,8 @@ TORCH_LIBRARY_IMPL(elimrec, CUDA, m) {
     m.impl("list_pair_cosine", &list_pair_cosine);
     m.impl("list_exposure", &list_exposure);
     m.impl("mmr_rerank", &mmr_rerank);
+    m.impl("calibrate_rerank", &calibrate_rerank);
+    m.impl("list_calibration", &list_calibration);
     m.impl("pick_hard_negatives", &pick_hard_negatives);
     m.impl("history_support", &history_support);
     m.impl("bootstrap_means", &bootstrap_means);

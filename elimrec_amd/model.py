@@ -1683,6 +1683,86 @@ class EliMRec(BasicModel):
         scores = torch.gather(val, 1, out_pos.clamp(min=0).long()).masked_fill_(out_pos < 0, float("-inf"))
         return out_idx.cpu(), scores.cpu()
 
+    @torch.no_grad()
+    def calibrate_device(self, lists_idx, lists_val, k, lam, class_of, targets, smooth=0.01, out_idx=None, out_pos=None, out_val=None):
+        """Calibrated re-ranking of top-N pools (Steck, "Calibrated recommendations", RecSys 2018): k items per pool whose mix of
+        item classes follows the row's target mix, ONE launch (csrc/calibrate.hip). lists_idx int32 / lists_val float32 [B x N] on
+        the device (predict_device(top_k=N) gives both), 1 <= k <= N <= ops.MMR_MAX_POOL; class_of int32 [num_items] on the device:
+        every item's class in [0, C), C <= ops.CALIBRATE_MAX_CLASSES; targets float32 [B x C]: the class shares to aim at. An entry
+        outside the catalogue, with a score that is not finite (the -1 / -inf fillers) or with a class outside [0, C) is never
+        picked. With the pool's scores scaled to rel in [0, 1], step t takes the item with the largest
+        lam * rel - (1 - lam) * KL(targets || smoothed class shares of the picks so far plus the item), in float64, the lowest pool
+        position among equals. lam weighs the RELEVANCE, as in rerank_device -- Steck's lambda weighs the calibration term --:
+        lam = 1 keeps the pool's order, lam = 0 follows the targets alone. -> (out_idx int32 [B x k] the picked items, out_pos int32
+        their pool positions, out_val float32 their objectives), -1 / -1 / -inf once no listed item is left; allocated here unless
+        given. It reads no cached table itself."""
+        dev = self._require_gpu()
+        B, k = lists_idx.shape[0], int(k)
+        if out_idx is None:
+            out_idx = torch.empty(B, k, dtype=torch.int32, device=dev)
+        if out_pos is None:
+            out_pos = torch.empty(B, k, dtype=torch.int32, device=dev)
+        if out_val is None:
+            out_val = torch.empty(B, k, dtype=torch.float32, device=dev)
+        ops.calibrate_rerank(lists_idx, lists_val, class_of, targets, k, lam, out_idx, out_pos, out_val, smooth=smooth)
+        return out_idx, out_pos, out_val
+
+    def recommend_calibrated(self, user_ids, k, classes, pool=None, lam=0.5, targets=None, smooth=0.01, exclude=None):
+        """k items per user from the user's top-`pool` list whose mix of item classes follows the user's own (greedy calibrated
+        re-ranking, calibrate_device): CPU (ids int32 [B x k], scores fp32 [B x k], kl fp32 [B]) -- ids in pick order, scores the
+        model's scores of the picked items under the current predict type, kl the returned list's miscalibration C_KL against the
+        user's target (ops.list_calibration). One predict_device(top_k=pool) call, one re-rank launch. classes: int array
+        [num_items] with values in [0, C), C <= ops.CALIBRATE_MAX_CLASSES (reports.item_classes gives the popularity buckets);
+        targets: float array [B x C], default the class shares of each user's training items (one ops.class_shares launch); pool
+        defaults to min(4 k, 256, num_items); lam in [0, 1] weighs the RELEVANCE (1 = the plain top-k, 0 = the targets alone;
+        Steck's lambda weighs the calibration term); 0 < smooth < 1; `exclude` = dict user -> item ids left out of the ranking, as
+        explain() takes it. -1 / -inf where a user has fewer than k items left."""
+        k = int(k)
+        pool = min(4 * k, ops.MMR_MAX_POOL, self.num_items) if pool is None else int(pool)
+        if not 1 <= k <= pool <= min(ops.MMR_MAX_POOL, self.num_items):
+            raise ValueError("need 1 <= k <= pool <= min(%d, num_items = %d), got k %d, pool %d"
+                             % (ops.MMR_MAX_POOL, self.num_items, k, pool))
+        lam, smooth = float(lam), float(smooth)
+        if not 0.0 <= lam <= 1.0:
+            raise ValueError("lam must lie in [0, 1], got %r" % lam)
+        if not 0.0 < smooth < 1.0:
+            raise ValueError("smooth must lie in (0, 1), got %r" % smooth)
+        classes = np.asarray(classes)
+        if classes.ndim != 1 or classes.shape[0] != self.num_items or classes.dtype.kind not in "iu":
+            raise ValueError("classes must be an integer array with one class per item (%d)" % self.num_items)
+        max_c = ops.CALIBRATE_MAX_CLASSES
+        if classes.size and not 0 <= int(classes.min()) <= int(classes.max()) < max_c:
+            raise ValueError("classes must lie in [0, C) with C <= %d, got [%d, %d]" % (max_c, int(classes.min()), int(classes.max())))
+        C = int(classes.max()) + 1 if classes.size else 1
+        n = len(user_ids)
+        if targets is not None:
+            targets = np.asarray(targets, dtype=np.float32)
+            if targets.ndim != 2 or targets.shape[0] != n or not C <= targets.shape[1] <= max_c:
+                raise ValueError("targets must be [%d users x C], %d <= C <= %d, got %s" % (n, C, max_c, tuple(targets.shape)))
+            C = targets.shape[1]
+        tptr, tflat = self._excluded(exclude, user_ids, "item")
+        if targets is None:
+            train = self.dataset.get_user_train_dict()
+            hptr, hflat, _ = self._id_lists([train.get(int(u), []) for u in user_ids], "training item")
+        dev = self._cached_tables("calibrate_device() / recommend_calibrated() need", "calibrated re-ranking needs the whole cached item "
+                                  "table on this rank; the tables are item-sharded (lean / multi-rank evaluation)")
+        if not n:
+            return torch.empty(0, k, dtype=torch.int32), torch.empty(0, k, dtype=torch.float32), torch.empty(0, dtype=torch.float32)
+        class_of = torch.from_numpy(classes.astype(np.int32)).to(dev)
+        if targets is None:
+            targets_t = ops.class_shares(torch.from_numpy(hptr).to(dev), torch.from_numpy(hflat.astype(np.int32)).to(dev), class_of, C,
+                                         torch.empty(n, C, dtype=torch.float32, device=dev))
+        else:
+            targets_t = torch.from_numpy(np.ascontiguousarray(targets)).to(dev)
+        masked = (torch.from_numpy(tptr).to(dev), torch.from_numpy(tflat.astype(np.int32)).to(dev)) if tflat.size else (None, None)
+        idx, val = self.predict_device(user_ids, top_k=pool, train_ptr=masked[0], train_items=masked[1])
+        out_idx, out_pos, _ = self.calibrate_device(idx, val, k, lam, class_of, targets_t, smooth=smooth)
+        scores = torch.gather(val, 1, out_pos.clamp(min=0).long()).masked_fill_(out_pos < 0, float("-inf"))
+        kl = torch.empty(n, dtype=torch.float32, device=dev)
+        ops.list_calibration(out_idx, class_of, C, torch.empty(n, C, dtype=torch.float32, device=dev), target=targets_t, smooth=smooth,
+                             out_kl=kl)
+        return out_idx.cpu(), scores.cpu(), kl.cpu()
+
     def predict(self, user_ids, candidate_items=None):
         """:96-113. CPU fp32 tensor [len(user_ids) x I]; `candidate_items` is ignored as in the reference."""
         dev = self._require_gpu()

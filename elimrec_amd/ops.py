@@ -1017,6 +1017,8 @@ def __getattr__(name):
         return int(_lib.load().elimrec_bootstrap_replicate_tile())
     if name == "MMR_MAX_POOL":           # positions of a pool mmr_rerank takes (one thread each)
         return int(_lib.load().elimrec_mmr_max_pool())
+    if name == "CALIBRATE_MAX_CLASSES":  # item classes calibrate_rerank / class_shares / list_calibration take (one lane each)
+        return int(_lib.load().elimrec_calibrate_max_classes())
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 
@@ -1582,6 +1584,146 @@ def mmr_rerank(table, sqnorm, pool_idx, pool_val, K, lam, out_idx, out_pos=None,
         return out_idx
     _lib.check(_lib.load().elimrec_mmr_rerank(tp, ld, n, d, sp, ld_sq, pi, pv, B, N, K, lam, ip, pp, vp, _stream()), "mmr_rerank")
     return out_idx
+
+
+def _cal_tensors(who, *named):
+    for t, name in named:
+        if not isinstance(t, torch.Tensor):
+            raise RuntimeError("elimrec_amd.ops: '%s' must be a HIP device tensor (the hot path has no CPU implementation)" % name)
+
+
+def _cal_classes(who, class_of, C, device):
+    """(n_items, C) of a class table: int32, 1-D, contiguous, on `device`; 1 <= C <= CALIBRATE_MAX_CLASSES."""
+    if class_of.dim() != 1 or class_of.dtype != torch.int32 or not class_of.is_contiguous() or class_of.device != device:
+        raise ValueError("elimrec_amd.ops.%s: class_of must be a contiguous 1-D int32 tensor (one class per item) on the lists' device" % who)
+    if isinstance(C, bool) or int(C) != C:
+        raise ValueError("elimrec_amd.ops.%s: C must be an integer, got %r" % (who, C))
+    max_c = int(_lib.load().elimrec_calibrate_max_classes())
+    if not 1 <= int(C) <= max_c:
+        raise ValueError("elimrec_amd.ops.%s: 1 <= C <= %d, got %d" % (who, max_c, C))
+    return class_of.numel(), int(C)
+
+
+def _cal_target(who, target, B, C, device):
+    """Row stride of a target block: float32 [B x C] with unit column stride (a column block of a wider matrix is fine)."""
+    ok = target.dim() == 2 and target.dtype == torch.float32 and target.device == device and target.shape[0] == B and (
+        C is None or target.shape[1] == C) and (target.stride(1) == 1 or target.shape[1] == 1)
+    if not ok:
+        raise ValueError("elimrec_amd.ops.%s: target must be a float32 [%d x %s] tensor with unit column stride on the lists' device"
+                         % (who, B, "C" if C is None else C))
+    return max(int(target.shape[1]), int(target.stride(0))) if B > 1 else int(target.shape[1])
+
+
+def _cal_smooth(who, smooth):
+    smooth = float(smooth)
+    if not 0.0 < smooth < 1.0:                                       # (NaN fails too)
+        raise ValueError("elimrec_amd.ops.%s: 0 < smooth < 1, got %r" % (who, smooth))
+    return smooth
+
+
+def calibrate_rerank(pool_idx, pool_val, class_of, target, K, lam, out_idx, out_pos=None, out_val=None, smooth=0.01):
+    """elimrec_calibrate_rerank: greedy calibrated re-ranking of each row's pool (Steck, RecSys 2018): K items whose mix of item
+    classes follows the row's target mix. pool_idx int32 / pool_val float32 [B x N] contiguous on one device, 1 <= K <= N <=
+    MMR_MAX_POOL; class_of int32 [n_items]: every item's class; target float32 [B x C] with unit column stride (any row stride),
+    1 <= C <= CALIBRATE_MAX_CLASSES: the target share p_c of every class (a negative or non-finite entry counts as 0). A position
+    is listed when its id lies in [0, n_items), its score is finite and its class lies in [0, C) (the kernel checks every entry, no
+    host check is needed). With rel = the listed scores scaled to [0, 1] per pool and q~ = (1 - smooth) q + smooth p, q = the class
+    shares of the picks so far plus the candidate, step t picks the listed, not yet picked position with the largest
+    lam * rel_i - (1 - lam) * sum_{c: p_c > 0} p_c log(p_c / q~_c) -- all in float64 --, the lowest position among equals.
+    lam weighs the RELEVANCE, as in mmr_rerank (Steck's lambda weighs the calibration term): lam = 1 keeps a sorted pool's order;
+    0 <= lam <= 1, 0 < smooth < 1. out_idx int32 [B x K] <- the picked ids, out_pos int32 (optional) their pool positions, out_val
+    float32 (optional) their objectives at pick time; -1 / -1 / -inf once no listed position is left. Outputs: contiguous,
+    [>= B x K] or 1-D with at least B * K entries; entries beyond [B x K] are left alone. A row's bits depend on its pool, the
+    classes of its ids, its target row, N, K, C, lam and smooth alone (csrc/calibrate.hip)."""
+    who = "calibrate_rerank"
+    _cal_tensors(who, (pool_idx, "pool_idx"), (pool_val, "pool_val"), (class_of, "class_of"), (target, "target"), (out_idx, "out_idx"))
+    if (pool_idx.dim() != 2 or pool_idx.shape != pool_val.shape or not pool_idx.is_contiguous() or not pool_val.is_contiguous()
+            or pool_idx.dtype != torch.int32 or pool_val.dtype != torch.float32 or pool_idx.device != pool_val.device):
+        raise ValueError("elimrec_amd.ops.calibrate_rerank: pool_idx (int32) and pool_val (float32) must be contiguous [B x N] tensors "
+                         "of one shape on one device")
+    B, N = pool_idx.shape
+    dev = pool_idx.device
+    if target.dim() != 2:
+        raise ValueError("elimrec_amd.ops.calibrate_rerank: target must be a float32 [%d x C] tensor with unit column stride on the "
+                         "lists' device" % B)
+    n_items, C = _cal_classes(who, class_of, target.shape[1], dev)
+    ld_t = _cal_target(who, target, B, C, dev)
+    if isinstance(K, bool) or int(K) != K:
+        raise ValueError("elimrec_amd.ops.calibrate_rerank: K must be an integer, got %r" % (K,))
+    K = int(K)
+    max_pool = int(_lib.load().elimrec_mmr_max_pool())
+    if not 1 <= K <= N <= max_pool:
+        raise ValueError("elimrec_amd.ops.calibrate_rerank: 1 <= K <= N <= %d, got K %d, N %d" % (max_pool, K, N))
+    lam = float(lam)
+    if not 0.0 <= lam <= 1.0:                                        # (NaN fails too)
+        raise ValueError("elimrec_amd.ops.calibrate_rerank: 0 <= lam <= 1, got %r" % lam)
+    smooth = _cal_smooth(who, smooth)
+    pi, pv = _dev(pool_idx, "pool_idx", torch.int32), _dev(pool_val, "pool_val", torch.float32)
+    cp, tp = _dev(class_of, "class_of", torch.int32), _dev(target, "target")
+    ip = _rows_out(out_idx, "out_idx", torch.int32, B, K, who, device=dev)
+    pp = _rows_out(out_pos, "out_pos", torch.int32, B, K, who, device=dev) if out_pos is not None else None
+    vp = _rows_out(out_val, "out_val", torch.float32, B, K, who, device=dev) if out_val is not None else None
+    if B == 0:
+        return out_idx
+    _lib.check(_lib.load().elimrec_calibrate_rerank(pi, pv, B, N, K, cp, n_items, tp, ld_t, C, lam, smooth, ip, pp, vp, _stream()), who)
+    return out_idx
+
+
+def class_shares(ptr, items, class_of, C, out):
+    """elimrec_class_shares_csr: out float32 [B x C] <- per segment b of the CSR ptr int64 [B + 1] / items int32 the share of every
+    item class among its listed entries: float(count_c) / float(listed), one fp32 division; zeros for a segment without a listed
+    entry. class_of int32 [n_items]; an entry outside [0, n_items) or with a class outside [0, C) is skipped (the kernel checks
+    every entry and clips every segment to the items it is given: no host check is needed), a repeated id counts each time.
+    1 <= C <= CALIBRATE_MAX_CLASSES. out: contiguous, [>= B x C] or 1-D with at least B * C entries; entries beyond are left alone.
+    Integer counts: exact in any order (csrc/calibrate.hip)."""
+    who = "class_shares"
+    _cal_tensors(who, (ptr, "ptr"), (items, "items"), (class_of, "class_of"), (out, "out"))
+    if (ptr.dim() != 1 or ptr.numel() < 1 or ptr.dtype != torch.int64 or not ptr.is_contiguous() or items.dim() != 1
+            or items.dtype != torch.int32 or not items.is_contiguous() or items.device != ptr.device):
+        raise ValueError("elimrec_amd.ops.class_shares: ptr (int64, B + 1 entries) and items (int32) must be contiguous 1-D tensors on "
+                         "one device")
+    B = ptr.numel() - 1
+    n_items, C = _cal_classes(who, class_of, C, ptr.device)
+    pp, ip = _dev(ptr, "ptr", torch.int64), _dev(items, "items", torch.int32)
+    cp = _dev(class_of, "class_of", torch.int32)
+    op = _rows_out(out, "out", torch.float32, B, C, who, device=ptr.device)
+    if B == 0:
+        return out
+    _lib.check(_lib.load().elimrec_class_shares_csr(pp, ip, items.numel(), B, cp, n_items, C, op, _stream()), who)
+    return out
+
+
+def list_calibration(lists, class_of, C, out_shares, target=None, smooth=0.01, out_kl=None):
+    """elimrec_list_calibration: out_shares float32 [B x C] <- the class shares of every row of lists (int32 [B x K] contiguous,
+    K >= 1), as class_shares forms them (-1 fillers and ids outside the catalogue are skipped). With target (float32 [B x C], unit
+    column stride, any row stride) and out_kl (float32, at least B entries) -- both or neither -- also the rows' miscalibration
+    out_kl[b] = sum_{c: p_c > 0} p_c log(p_c / ((1 - smooth) q_c + smooth p_c)), q = the row's class shares in float64, p =
+    target[b] as calibrate_rerank reads it: Steck's C_KL, rounded once to fp32; 0 < smooth < 1."""
+    who = "list_calibration"
+    _cal_tensors(who, (lists, "lists"), (class_of, "class_of"), (out_shares, "out_shares"))
+    if lists.dim() != 2 or lists.dtype != torch.int32 or not lists.is_contiguous() or lists.shape[1] < 1:
+        raise ValueError("elimrec_amd.ops.list_calibration: lists must be a contiguous int32 [B x K] tensor, K >= 1")
+    B, K = lists.shape
+    dev = lists.device
+    n_items, C = _cal_classes(who, class_of, C, dev)
+    if (target is None) != (out_kl is None):
+        raise ValueError("elimrec_amd.ops.list_calibration: target and out_kl go together")
+    tp = kp = None
+    ld_t = C
+    if target is not None:
+        _cal_tensors(who, (target, "target"), (out_kl, "out_kl"))
+        ld_t = _cal_target(who, target, B, C, dev)
+        smooth = _cal_smooth(who, smooth)
+        if out_kl.dim() != 1 or out_kl.dtype != torch.float32 or not out_kl.is_contiguous() or out_kl.numel() < B or out_kl.device != dev:
+            raise ValueError("elimrec_amd.ops.list_calibration: out_kl must be a contiguous 1-D float32 tensor with at least %d entries "
+                             "on the lists' device" % B)
+        tp, kp = _dev(target, "target"), _dev(out_kl, "out_kl")
+    lp, cp = _dev(lists, "lists", torch.int32), _dev(class_of, "class_of", torch.int32)
+    op = _rows_out(out_shares, "out_shares", torch.float32, B, C, who, device=dev)
+    if B == 0:
+        return out_shares
+    _lib.check(_lib.load().elimrec_list_calibration(lp, B, K, cp, n_items, C, op, tp, ld_t, float(smooth), kp, _stream()), who)
+    return out_shares
 
 
 def _block_table(table, sqnorm, blocks, name, who):

@@ -1,6 +1,7 @@
 """The reports over the cached tables -- what the lists are made of (EffectReport), where the held-out items stand (RankReport),
 whose neighbourhood the fused space copies (NeighbourReport), the lists themselves (ListReport), what diversifying them costs and
-buys (DiversifyReport), which items of a user's history back them (HistoryReport), how sure the evaluation metrics are
+buys (DiversifyReport), whether they match each user's own popularity mix (CalibrationReport), which items of a user's history back
+them (HistoryReport), how sure the evaluation metrics are
 (SignificanceReport) -- and what they share: the user /
 item groups, the groups as a checked index on the device, the group means, the table format, the model preflight and the block-wise
 top-K lists. The rows come from the model's *_device readers (model.py), the means from ops.group_metric_means."""
@@ -796,6 +797,166 @@ class DiversifyReport(_Report):
         labels = [label for label in self.group_labels for _ in self.lambdas]
         final = DiversifyTables(DIVERSIFY_COLUMNS, labels, table)
         return final, format_table(final.columns, final.labels, final.table)
+
+
+def item_classes(item_ids_or_num_items, train_item_counts, item_group_view):
+    """The popularity buckets as item classes: (class_of int32 [I], names) -- class_of[k] = the index of the assign_item_groups
+    bucket (cold, (0,b1], ..., (bn,inf); empty buckets omitted, in that order) that entry k of the item ids falls into, names =
+    the buckets' labels. An int stands for the whole catalogue 0 .. I - 1. More classes than ops.CALIBRATE_MAX_CLASSES: ValueError."""
+    if isinstance(item_ids_or_num_items, (int, np.integer)) and not isinstance(item_ids_or_num_items, bool):
+        ids = np.arange(int(item_ids_or_num_items), dtype=np.int64)
+    else:
+        ids = np.asarray(item_ids_or_num_items, dtype=np.int64).reshape(-1)
+    labels, positions = assign_item_groups(ids, train_item_counts, item_group_view)
+    if len(labels) > ops.CALIBRATE_MAX_CLASSES:
+        raise ValueError("item_group_view gives %d item classes, at most %d are supported" % (len(labels), ops.CALIBRATE_MAX_CLASSES))
+    class_of = np.zeros(ids.size, dtype=np.int32)
+    for c, at in enumerate(positions):
+        class_of[at] = c
+    return class_of, labels
+
+
+def calibration_columns(names):
+    """Column names of the calibration report: lambda, recall, ndcg, ckl, pop, overlap, one share_<class> per item class (names:
+    the classes' labels, as item_classes gives them), then coverage, gini, entropy."""
+    return (("lambda", "recall", "ndcg", "ckl", "pop", "overlap") + tuple("share_" + str(n).strip().rstrip(":") for n in names)
+            + ("coverage", "gini", "entropy"))
+
+
+CalibrationTables = collections.namedtuple("CalibrationTables", ("columns", "labels", "table"))
+
+
+class CalibrationReport(_Report):
+    """Do the lists match each user's own popularity mix, and what does making them match cost (--calibrate_report=K): the items
+    are classed by training popularity (item_classes over item_group_view), a user's target is the class shares of their training
+    items (ops.class_shares, one launch), and every test user's top-`pool` list under the model's current predict type with the
+    train items masked (ONE top_lists pass with the scores, shared by all lambdas) is re-ranked to K items per lambda by greedy
+    calibrated re-ranking (EliMRec.calibrate_device, csrc/calibrate.hip: one launch per user block and lambda; Steck, "Calibrated
+    recommendations", RecSys 2018). lambda weighs the RELEVANCE, as in DiversifyReport (Steck's lambda weighs the calibration
+    term). Per lambda
+      per user recall and ndcg at K (ops.rank_metrics), ckl = the list's miscalibration C_KL(target || smoothed list shares) and
+        share_<class> = the list's share of every class (ops.list_calibration, one launch per user block and lambda), pop = the mean
+        training-interaction count of its items (as ListReport), overlap = the share of the plain top-K list it keeps;
+      coverage, gini, entropy = exposure_summary of how often each item is listed (ops.list_exposure) over the whole catalogue.
+    The table has one row per lambda -- calibration_columns(names): the lambda, the user means (ops.group_metric_means), the three
+    exposure columns -- for all test users, then one such block per group_view group (assign_user_groups; the exposure columns from
+    that group's lists). lambda = 1 keeps the pool's order: its row holds the plain lists' numbers -- read under TE and under TIE,
+    its ckl says whether TIE alone already moves the lists towards the users' own mix. Below the table one line `target:` holds the
+    mean target share of every class over all test users."""
+
+    name, needs = "calibrate", "predict_device"
+    metrics = (2, 4)                     # Recall, NDCG (evaluator.metric_dict)
+
+    def __init__(self, dataset, user_train_dict, user_test_dict, top_k, item_group_view, pool=None, lambdas=(1.0, 0.9, 0.7, 0.5),
+                 smooth=0.01, group_view=None):
+        if not isinstance(user_train_dict, dict) or not isinstance(user_test_dict, dict):
+            raise TypeError("user_train_dict and user_test_dict must be dicts")
+        self.num_items = I = int(dataset.num_items)
+        cap = min(ops.LIST_MAX_K, I)
+        for what, v in (("top_k", top_k), ("pool", pool)):
+            if (v is not None or what == "top_k") and (isinstance(v, bool) or not isinstance(v, (int, np.integer))):
+                raise ValueError("%s must be an integer, got %r" % (what, v))
+        if pool is None:
+            pool = min(4 * int(top_k), cap)
+        if not 2 <= top_k <= pool <= cap:
+            raise ValueError("need 2 <= top_k <= pool <= min(%d, the catalogue's %d items), got top_k %r, pool %r"
+                             % (ops.LIST_MAX_K, I, top_k, pool))
+        if isinstance(lambdas, (str, bytes)) or not hasattr(lambdas, "__len__") or not len(lambdas):
+            raise ValueError("lambdas must be a non-empty list of numbers in [0, 1], got %r" % (lambdas,))
+        for lam in lambdas:
+            if isinstance(lam, bool) or not isinstance(lam, (int, float, np.integer, np.floating)) or not 0.0 <= float(lam) <= 1.0:
+                raise ValueError("lambdas must be a non-empty list of numbers in [0, 1], got %r" % (lambdas,))
+        if isinstance(smooth, bool) or not isinstance(smooth, (int, float, np.integer, np.floating)) or not 0.0 < float(smooth) < 1.0:
+            raise ValueError("smooth must be a number in (0, 1), got %r" % (smooth,))
+        self.dataset = dataset
+        self.user_pos_train = user_train_dict
+        self.user_pos_test = user_test_dict
+        self.top_k, self.pool = int(top_k), int(pool)
+        self.lambdas = tuple(float(lam) for lam in lambdas)
+        self.smooth = float(smooth)
+        self.users = list(user_test_dict.keys())
+        self.item_counts = item_train_counts(user_train_dict, I)
+        self.class_of, self.class_names = item_classes(I, self.item_counts, item_group_view)
+        self.num_classes = len(self.class_names)
+        self.group_labels, self._positions = self._user_groups(self.users, user_train_dict, group_view)
+        self.columns = calibration_columns(self.class_names)
+
+    def _make_resident(self, device):
+        """The user group index, each group's user positions, the items' training counts and classes and every test user's target
+        (the class shares of their training items: one launch) resident on the device."""
+        class_of = torch.from_numpy(self.class_of).to(device)
+        ptr, items = lists_csr(self.users, self.user_pos_train, device)
+        targets = torch.zeros(len(self.users), self.num_classes, dtype=torch.float32, device=device)
+        ops.class_shares(ptr, items, class_of, self.num_classes, targets)
+        return dict(groups=group_index(self._positions, len(self.users), device),
+                    positions=[torch.from_numpy(p).to(device) for p in self._positions],
+                    counts=torch.from_numpy(self.item_counts.astype(np.float64)).to(device), class_of=class_of, targets=targets)
+
+    def targets(self, device):
+        """Every test user's target class shares on the device: float32 [users x C]."""
+        return self._resident(device)["targets"]
+
+    def calibrate_rows(self, model):
+        """Per lambda every test user's row and list on the device: (rows float32 [lambdas x users x (5 + C)] -- recall, ndcg,
+        ckl, pop, overlap, then the list's share of every class --, lists int32 [lambdas x users x K], counts int32
+        [lambdas x num_items])."""
+        device = self._preflight(model)
+        if not hasattr(model, "calibrate_device"):
+            raise TypeError("model must expose calibrate_device()")
+        res = self._resident(device)
+        K, N, L, n_users, C = self.top_k, self.pool, len(self.lambdas), len(self.users), self.num_classes
+        rows = torch.empty(L, n_users, 5 + C, dtype=torch.float32, device=device)
+        lists = torch.empty(L, n_users, K, dtype=torch.int32, device=device)
+        counts = torch.zeros(L, self.num_items, dtype=torch.int32, device=device)
+        block = min(self.block_users, max(n_users, 1))
+        met = torch.empty(block, len(self.metrics), K, dtype=torch.float32, device=device)
+        shares = torch.empty(block, C, dtype=torch.float32, device=device)
+        kl = torch.empty(block, dtype=torch.float32, device=device)
+        cnt = torch.empty(block, dtype=torch.int32, device=device)
+        for a, b, _, idx, val in self.top_lists(model, self.users, N, self.block_users, self.tie_order, with_values=True):
+            truth_ptr, truth_items = lists_csr(self.users[a:b], self.user_pos_test, device, unique=True)
+            plain = idx[:, :K].contiguous()
+            target = res["targets"][a:b]
+            for li, lam in enumerate(self.lambdas):
+                out = lists[li, a:b]
+                model.calibrate_device(idx, val, K, lam, res["class_of"], target, smooth=self.smooth, out_idx=out)
+                ops.list_calibration(out, res["class_of"], C, shares[:b - a], target=target, smooth=self.smooth, out_kl=kl[:b - a])
+                ops.rank_metrics(out, truth_ptr, truth_items, self.metrics, met[:b - a])
+                ops.list_exposure(out, counts[li])
+                ops.list_overlap(plain, out, cnt[:b - a])
+                listed = out >= 0
+                pop = torch.where(listed, res["counts"][out.clamp(min=0).long()], 0.0).sum(dim=1) / listed.sum(dim=1).double()
+                rows[li, a:b, 0:2] = met[:b - a, :, K - 1]
+                rows[li, a:b, 2] = kl[:b - a]
+                rows[li, a:b, 3] = pop.float()
+                rows[li, a:b, 4] = (cnt[:b - a].double() / K).float()
+                rows[li, a:b, 5:] = shares[:b - a]
+        return rows, lists, counts
+
+    def evaluate(self, model, rows=None):
+        """(final, buf). final = CalibrationTables(columns, labels, table float64 [(1 + user groups) * lambdas x (9 + C)]): per
+        group (row block 0 = all test users) one row per lambda in self.lambdas' order. buf: a header of column names, one "%.8f"
+        line per row in the grouped evaluator's format, and the line `target:` with the mean target share of every class. rows:
+        calibrate_rows(model) if the caller already holds it."""
+        rows, lists, counts = self.calibrate_rows(model) if rows is None else rows
+        res = self._resident(rows.device)
+        L, G, C = len(self.lambdas), len(self.group_labels), self.num_classes
+        every = [np.arange(self.num_items, dtype=np.int64)]
+        table = np.zeros((G * L, len(self.columns)), dtype=np.float64)
+        for li, lam in enumerate(self.lambdas):
+            means = group_table(rows[li], res["groups"], G)
+            for g in range(G):
+                c = counts[li]
+                if g:                                  # a group's exposure: its own users' lists
+                    c = ops.list_exposure(lists[li].index_select(0, res["positions"][g]).contiguous(), torch.zeros_like(c))
+                table[g * L + li, 0] = lam
+                table[g * L + li, 1:6 + C] = means[g]
+                table[g * L + li, 6 + C:9 + C] = exposure_summary(c.cpu().numpy(), every)[0, 1:4]
+        labels = [label for label in self.group_labels for _ in self.lambdas]
+        final = CalibrationTables(self.columns, labels, table)
+        self.target_mean = res["targets"].double().mean(dim=0).cpu().numpy() if len(self.users) else np.zeros(C)
+        buf = format_table(final.columns, final.labels, final.table) + format_rows(["target:".ljust(12)], [self.target_mean])
+        return final, buf
 
 
 class HistoryReport(_Report):

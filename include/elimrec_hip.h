@@ -689,6 +689,49 @@ int elimrec_mmr_rerank(const float *d_T, int64_t ld, int64_t n_rows, int d, cons
 int elimrec_mmr_max_pool(void);
 int elimrec_mmr_rows_in_lds(int N, int d);
 
+/* Calibrated re-ranking (csrc/calibrate.hip; Steck, "Calibrated recommendations", RecSys 2018): pick K items of a top-N pool so
+ * that the list's mix of item classes follows a target mix. No counterpart in the reference. d_pool_idx int32 / d_pool_val float32
+ * [B x N] contiguous, as elimrec_mmr_rerank takes them; d_class_of int32 [n_items]: every item's class; d_target float32: row b at
+ * d_target + b * ld_target holds the C target shares of user b (ld_target >= C: a column block of a wider matrix is fine). A
+ * position is listed when its id lies in [0, n_items), its score is finite and class_of[id] lies in [0, C); every entry is checked,
+ * an unlisted position is never dereferenced further and never picked. Over the listed positions, all in float64:
+ *     rel_i = (s_i - s_min) / (s_max - s_min)                            (0 when s_max == s_min)
+ *     p_c = target[b, c]                                                 (an entry that is negative or not finite counts as 0)
+ *     q_c = (n_c(t) + [c == c']) / (t + 1),  q~_c = (1 - smooth) q_c + smooth p_c     (n_c(t): the picks so far in class c)
+ *     KL_t(c') = sum over c ascending with p_c > 0 of p_c * log(p_c / q~_c)           (a row without a positive p_c: 0)
+ * and step t = 0 .. K - 1 picks, among the listed positions not picked yet, the largest
+ *     obj_t(i) = lambda * rel_i - (1 - lambda) * KL_t(class_i)
+ * the lowest pool position winning among equal objectives; it stops after K picks or when no listed position is left. lambda
+ * weighs the RELEVANCE, as in elimrec_mmr_rerank (Steck's lambda weighs the calibration term): lambda = 1 keeps the order of a
+ * pool sorted by descending score, and so does C = 1 or a target row of zeros. d_out_idx int32 [B x K] = the picked ids,
+ * d_out_pos int32 (nullable) their pool positions, d_out_val float32 (nullable) their objectives rounded once to fp32; unfilled
+ * slots are -1, -1, -inf; exactly B * K entries of each are written. 1 <= K <= N <= 256, 1 <= C <=
+ * elimrec_calibrate_max_classes() = 16, 0 <= lambda <= 1, 0 < smooth < 1 (anything else: an error, no launch); B == 0 launches
+ * nothing.
+ * One workgroup per user (one wave for N <= 64, four above), one thread per pool position; lane c of a wave keeps class c's count
+ * and forms its two possible terms (two logs per step), the C values KL_t(c') go round by wave shuffles; the argmax is a wave
+ * reduction on (objective, -position) and then across the waves in wave order. No atomics, no workspace: a user's outputs depend
+ * bit for bit on that user's pool, the classes of its ids, its target row, N, K, C, lambda and smooth only -- not on B, the user's
+ * place in the batch or the grid. One launch on `stream`. */
+int elimrec_calibrate_rerank(const int32_t *d_pool_idx, const float *d_pool_val, int64_t B, int N, int K, const int32_t *d_class_of,
+                             int64_t n_items, const float *d_target, int64_t ld_target, int C, double lambda, double smooth,
+                             int32_t *d_out_idx, int32_t *d_out_pos, float *d_out_val, void *stream);
+int elimrec_calibrate_max_classes(void);
+/* Class shares of item lists (csrc/calibrate.hip). d_shares float32 [B x C] contiguous: share_c = float(count_c) / float(listed)
+ * (one fp32 division), count_c = the entries of row b whose id lies in [0, n_items) and whose class is c, listed = their sum over
+ * the classes; all zeros when nothing is listed. Entries outside the catalogue or with a class outside [0, C) are skipped and never
+ * dereferenced further; a repeated id counts each time. Integer counts by wave ballots: exact, no atomics. One wave per row.
+ * elimrec_class_shares_csr: row b = d_items[d_ptr[b] .. d_ptr[b + 1]) of the CSR d_ptr int64 [B + 1] / d_items int32 [nnz]; a
+ * segment is clipped to [0, nnz), whatever d_ptr holds.
+ * elimrec_list_calibration: row b = d_lists[b, :] (int32 [B x K] contiguous, K >= 1). With d_target (rows of C floats at stride
+ * ld_target >= C) and d_kl (float32 [B]) -- both or neither -- also the row's miscalibration
+ *     kl[b] = sum over c ascending with p_c > 0 of p_c * log(p_c / ((1 - smooth) q_c + smooth p_c)),  q_c = count_c / listed
+ * in float64 (q = 0 when nothing is listed), p as elimrec_calibrate_rerank reads it, rounded once to fp32; 0 < smooth < 1. */
+int elimrec_class_shares_csr(const int64_t *d_ptr, const int32_t *d_items, int64_t nnz, int64_t B, const int32_t *d_class_of,
+                             int64_t n_items, int C, float *d_shares, void *stream);
+int elimrec_list_calibration(const int32_t *d_lists, int64_t B, int K, const int32_t *d_class_of, int64_t n_items, int C,
+                             float *d_shares, const float *d_target, int64_t ld_target, double smooth, float *d_kl, void *stream);
+
 /* Hard-negative pick (csrc/hardneg.hip): per triplet the best of M candidate items under the current tables. No counterpart in
  * the reference. d_U / d_T point at row 0, column 0 of an [n_users x blocks * d] / [n_items x blocks * d] slice of a row-major
  * float32 matrix with row stride ld_u / ld_i >= blocks * d, block b = columns [b * d, (b + 1) * d); d_sq_u[r * ldsq_u + b] /

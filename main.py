@@ -121,6 +121,12 @@ class Net(object):
         self.diversify_report = int(cfg["diversify_report"]) if "diversify_report" in cfg else 0
         if self.diversify_report and self.world > 1:
             raise ValueError("--diversify_report needs the whole cached item table on one rank: it is single-GPU")
+        # --calibrate_report=K (default 0: off): under each [TEST] line the top-N pools (--calibrate_pool) re-ranked to K items towards
+        # each user's own mix of item popularity classes (--item_group_view) at every --calibrate_lambda: miscalibration and class
+        # shares against recall / NDCG; the lambda = 1 rows under TE and TIE say whether TIE calibrates the lists by itself
+        self.calibrate_report = int(cfg["calibrate_report"]) if "calibrate_report" in cfg else 0
+        if self.calibrate_report and self.world > 1:
+            raise ValueError("--calibrate_report needs the whole cached item table on one rank: it is single-GPU")
         # --neg_sampling=hard (default uniform): every epoch trains on the best of --neg_candidates=M (8) uniform candidates per
         # triplet under the tables of the last training forward, scored in --neg_space=fused|loss|<head> (fused); the first epoch
         # of a run -- no tables yet -- is the uniform one
@@ -289,6 +295,10 @@ class Net(object):
             if self.diversify_report:      # the top-N pools under this effect re-ranked to K by greedy MMR, one row per lambda
                 reporter = rec.diversify_reporter
                 Logger.info("  [{}] top-{} of the top-{} pools by MMR, per lambda:\n{}".format(
+                    effect, reporter.top_k, reporter.pool, reporter.evaluate(rec)[1]))
+            if self.calibrate_report:      # the top-N pools under this effect re-ranked to K towards the users' own popularity mix
+                reporter = rec.calibrate_reporter
+                Logger.info("  [{}] top-{} of the top-{} pools calibrated to the users' popularity mix, per lambda:\n{}".format(
                     effect, reporter.top_k, reporter.pool, reporter.evaluate(rec)[1]))
             if self.history_report:        # how close the users' training histories sit to the lists under this effect, per space
                 backed[effect] = rec.history_reporter.history_rows(rec)
