@@ -488,6 +488,101 @@ def test_fused_head_forward_with_the_rows_inline(n_act, n_lo):
         assert same_bits(x[:n_act], y[:n_act])
 
 
+_LADDER_ROWS = {}
+
+
+def _ladder_rows_case(w):
+    """The rows ladder (tests/rows_model.py) at T = 64 on the tiered plan of a 64-column table in slabs of w floats (two slab
+    groups, as the engine's choose_groups gives them), with eight random layer tables: built once per session."""
+    import rows_model as rm
+    from elimrec_amd import slab
+    if w not in _LADDER_ROWS:
+        T, ns = 64, HD // w
+        gs = min(2, ns)
+        G = 64 // ((ns // gs) * (w // 4))
+        m, U, named = rm.rows_ladder(T, G)
+        N = m.shape[0]
+        plan = slab.SellPlan(m, DEV, threshold=T, side_split=U, tiered=True, ipw=G)
+        assert plan.tiered and min(plan.n_w1, plan.n_w4, plan.n_seg) > 0
+        g = torch.Generator().manual_seed(w)
+        X = [torch.randn(N, HD, generator=g) for _ in range(4)]
+        xs = [slab.SlabTable(N, ns, w, DEV).from_rows(x.to(DEV)) for x in X]
+        long_tabs = {}
+        for L in (1, 2, 3, 4):
+            long_tabs[L] = torch.full((ns * plan.n_long * w,), NAN, device=DEV)
+            slab.hop(plan, xs[L - 1], long_tabs[L], gs=gs, seg_only=True)
+        _LADDER_ROWS[w] = types.SimpleNamespace(m=m, U=U, N=N, named=named, plan=plan, ns=ns, w=w, X=X, xs=xs, long_tabs=long_tabs)
+    return _LADDER_ROWS[w]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("L", [1, 2, 3, 4])
+@pytest.mark.parametrize("w", [8, 16, 32, 64])
+def test_fused_head_rows_form_on_the_ladder_at_every_boundary_offset(w, L):
+    """elimrec_head_fwd_fused (rows form) on the tiered T = 64 plan: the batch holds every named row of the rows ladder on both
+    sides (the 16-wide groups' remainders, all three upper tiers out of the compact table), the user / item boundary of the sorted
+    active list sits at every offset 0..16 of a 16-row tile, the row count is no multiple of 16. OutAct (every block), YAct and the
+    narrow buffer are bit for bit those of slab.rows into the same buffers followed by the plain phase-4 head (the engine with
+    ELIMREC_ROWS_IN_HEAD=0); the out0 block and the narrow buffer lie inside the float64 bound of rows_model.rows_ref; rows past
+    the active count are untouched. A geometry the entry point refuses must write nothing."""
+    import rows_model as rm
+    from elimrec_amd import ops, slab
+    c = _ladder_rows_case(w)
+    R = 96
+    layers = [t.data for t in c.xs[:L]] + [None]
+    users = sorted(r for (s, _), r in c.named.items() if s == "user")
+    items = sorted(r for (s, _), r in c.named.items() if s == "item")
+    rs = np.random.RandomState(16 * w + L)
+    rest_u = np.setdiff1d(np.arange(c.U), users + [c.U - 1])
+    rest_i = np.setdiff1d(np.arange(c.U, c.N), items + [c.U])
+    for off in range(17):
+        n_lo = 32 + off
+        n_hi = 24 if (off + 23) % 16 == 0 else 23
+        n_act = n_lo + n_hi
+        assert n_act % 16 != 0 and n_act <= R
+        a_u = np.sort(np.concatenate([users, [c.U - 1], rs.choice(rest_u, n_lo - len(users) - 1, replace=False)]))
+        a_i = np.sort(np.concatenate([items, [c.U], rs.choice(rest_i, n_hi - len(items) - 1, replace=False)]))
+        nodes = np.concatenate([a_u, a_i]).astype(np.int64)
+        t = _fwd_case((24, 68), R, n_act, n_lo, "all", seed=3, N=c.N)
+        t["act"][:n_act] = torch.from_numpy(nodes).int()
+        o = _to_dev(t)
+        C = o["C"]
+        what = "w %d L %d boundary offset %d" % (w, L, off)
+        pack = torch.full((ops.head_pack_floats(o["dims"]),), NAN, device=DEV)
+        cnt = torch.tensor([n_act], dtype=torch.int32, device=DEV)
+        res = {}
+        for form in ("launches", "fused"):
+            ob, yb = _bufs(R, C)
+            nbuf = torch.full((R, HD + 4), NAN, device=DEV)
+            assert _fwd_call(o, pack, ob, yb, 1) and _fwd_call(o, pack, ob, yb, 3)
+            if form == "launches":
+                slab.rows(c.plan, c.ns, w, L, c.U, layers, c.long_tabs[L], o["act"].view(1, R), cnt, R, 1, ob[:, :HD], nbuf[:, :HD], False)
+                o2 = dict(o)
+                o2["out0"], o2["narrow"] = ob[:, :HD], nbuf[:, :HD]
+                assert _fwd_call(o2, pack, ob, yb, 4)
+            else:
+                rows = dict(plan=c.plan, ns=c.ns, w=w, L=L, U=c.U, layers=layers, long_tab=c.long_tabs[L], narrow=nbuf[:, :HD])
+                try:
+                    ok = ops.head_fwd_fused_rows(rows, o["act"], o["seg"], o["c"], o["S"], o["Wm"], o["bm"], o["Wf"][0], o["bf"][0],
+                                                 o["Wf"][1], o["bf"][1], o["Ws"], o["bs"], pack, ob[:, :C], yb[:, :C], HD)
+                except RuntimeError:
+                    ok = False
+                torch.cuda.synchronize()
+                if not ok:              # refused: nothing beyond what phase 3 left
+                    assert all_nan(yb) and all_nan(nbuf) and all_nan(ob[:, :HD]), what + ": refused, but something was written"
+                    pytest.fail(what + ": refused (the entry point takes every ns x w = 64 with w / 4 a power of two)")
+            torch.cuda.synchronize()
+            res[form] = (ob, yb, nbuf)
+        for name, x, y in zip(("OutAct", "YAct", "narrow"), res["launches"], res["fused"]):
+            assert same_bits(x, y), "%s: %s differs from slab.rows + the phase-4 head" % (what, name)
+        ob, yb, nbuf = res["fused"]
+        assert all_nan(ob[n_act:]) and all_nan(yb[n_act:]) and all_nan(nbuf[n_act:]) and all_nan(nbuf[:, HD:]) and all_nan(ob[:, C:])
+        assert not bool(torch.isnan(ob[:n_act, :C]).any()) and not bool(torch.isnan(yb[:n_act, :C]).any())
+        o64, s0, n64, sn, K = rm.rows_ref(c.m, c.X[:L], None, nodes, c.U)
+        assert_close(ob[:n_act, :HD], o64, s0, K, what + ": layer means")
+        assert_close(nbuf[:n_act, :HD], n64, sn, K, what + ": narrow")
+
+
 @pytest.mark.gpu
 def test_fused_head_gate_never_sends_a_shape_the_kernel_refuses():
     """ColumnShardEngine._fused_head_ok's LDS estimate (still the removed 32-row head's layout) against the 16-row kernel: every
