@@ -4,7 +4,7 @@
 // audience_chunk_kernel: the grid is (item tiles x user chunks). A workgroup of W waves holds 16 W query items -- a wave owns 16 of
 // them as the A operands of v_mfma_f32_16x16x4_f32, every block of the row that the (fusion mode, head mask) pair uses: (1 + S) d / 4
 // registers per lane for d = 32 / 64 (64 at d = 64, S = 3), a lane-private LDS column for any other d -- and streams the
-// AUD_CHUNK user rows of its chunk through ONE LDS stage of SR rows. A staged row holds the columns of every used block side by side
+// KNN_CHUNK user rows of its chunk through ONE LDS stage of SR rows. A staged row holds the columns of every used block side by side
 // (row stride + 4 floats: 16-byte aligned b128 stores, B-operand reads two-way at worst), so a user row is read once per chunk; the
 // next stage's rows, squared norms and row sums travel in registers while the current one is multiplied (two barriers per stage).
 // The general-d form is one wave and stages one used block of the 16 rows at a time (a panel: <= 16.3 KiB instead of 65), the
@@ -16,12 +16,10 @@
 // with the expressions of score_math.h in the library's evaluator math mode (elimrec_score_set_math), the ones eval.hip's
 // scorers use. The k-loop runs 0, 4, 8, ... for every pair and block: a pair's bits depend on the two rows, row_sum[u], d, S and
 // the mode alone (rows outside the tables are zero operands and never read), not on its tile, stage, chunk or grid.
-// Selection (per chunk) is knn.hip's: a K-list per item in LDS (knn_select.h), CAP = K + 32 slots touched by its own wave only; a
-// score > the row's threshold (-inf until K are kept, then the K-th best kept; users arrive in ascending id order, so an equal score
-// later in the chunk loses the tie and is rightly dropped) is checked against the item's exclusion list -- a linear scan of its CSR
-// list, reached only by scores that beat the threshold -- and appended; a nearly full list is ranked by (score descending, user id
-// ascending) and cut to K. A chunk leaves K (score, id) pairs per item (-inf / -1 where it has fewer) in the workspace, laid out
-// [Q][chunks x K]; elimrec_topk_merge ranks them by the same order into the result. No [U x Q] block exists anywhere.
+// Selection (per chunk) and everything else around the multiply is knn_select.h's, shared with knn.hip: the K-list per item in
+// LDS (CAP = K + 32 slots; ties go to the lower user id), the scan of the item's exclusion list, the cut to the K best, the flush
+// of K pairs per item and chunk into the workspace [Q][chunks x K], and the host front end down to elimrec_topk_merge. This kernel
+// has no exclusion clause of its own. No [U x Q] block exists anywhere.
 // Determinism: no float atomics. An item's list and scores depend on its own row, the user table, row_sum, its exclusion list, K,
 // d, S and the mode only -- not on Q, the item's place in the query, the grid, or the arrival order inside a list.
 // Tile and LDS per workgroup: K <= 64 and d = 32 / 64 -> 4 waves, 64 items: lists 64 x 96 x 8 B = 48 KiB, stage 32 rows at d = 32,
@@ -31,12 +29,13 @@
 // audience_hits_kernel: one wave per item, the number of listed users found in the item's CSR list of users; integer, exact.
 #include "common.h"
 #include "cosine.h"
+#include "dispatch.h"
 #include "knn_select.h"
 #include "score_math.h"
 
 namespace elimrec {
 
-constexpr int AUD_CHUNK = 4096, AUD_TILE = 64, AUD_MAXK = 256, AUD_SMALLK = 64, AUD_MAXB = 4;
+constexpr int AUD_MAXB = 4;                                 // chunk, tile and K ranges: knn_select.h's
 typedef float aud_v4f __attribute__((ext_vector_type(4)));
 
 struct AudArgs {
@@ -55,9 +54,9 @@ constexpr int aud_stage_rows(int D, int W) { return (W == 4 && D == 32) ? 32 : 1
 static inline int aud_popc(int x) { int n = 0; for (; x; x &= x - 1) ++n; return n; }
 // dynamic LDS of one workgroup, in bytes (host and device agree through this one function); n_used: blocks that enter the score
 static inline size_t aud_lds_bytes(int D, int W, int d, int n_used, int K) {
-    const size_t sr = (size_t)aud_stage_rows(D, W), cap = (size_t)K + KNN_SLACK, rows = 16 * (size_t)W;
+    const size_t sr = (size_t)aud_stage_rows(D, W);
     const size_t pw = D ? (size_t)n_used * d : (size_t)d;
-    return sr * (pw + 4) * 4 + sr * AUD_MAXB * 4 + sr * 4 + rows * cap * 8 + rows * 8 + (D == 0 ? (size_t)n_used * (d / 4) * 64 * 4 : 0);
+    return sr * (pw + 4) * 4 + sr * AUD_MAXB * 4 + sr * 4 + knn_list_bytes(16 * (size_t)W, K) + (D == 0 ? (size_t)n_used * (d / 4) * 64 * 4 : 0);
 }
 
 // the score of one pair from its block dots; z: the heads' cosines (0 for a head that is not used: no fusion reads it)
@@ -71,16 +70,16 @@ __device__ __forceinline__ float aud_score(int ptype, int fmode, int S, uint32_t
     return sig_out_<FAST>(fmode, te - nde);
 }
 
-// D: 32 / 64 = the dimension at compile time, item operands in registers, W = 4 (K <= AUD_SMALLK) or 1; 0 = any d % 4 == 0 up
+// D: 32 / 64 = the dimension at compile time, item operands in registers, W = 4 (K <= KNN_SMALLK) or 1; 0 = any d % 4 == 0 up
 // to TABLE_MAXD, W = 1, item operands in lane-private LDS columns, one used block per panel.
 template <int D, int W, bool FAST>
 __global__ __launch_bounds__(64 * W) void audience_chunk_kernel(AudArgs a) {
     constexpr int SR = aud_stage_rows(D, W), NT = 64 * W, ROWS = 16 * W;
-    constexpr int E = W == 4 ? (AUD_SMALLK + KNN_SLACK + 63) / 64 : (AUD_MAXK + KNN_SLACK + 63) / 64;
+    constexpr int E = knn_list_regs(W);
     constexpr int PFN = (SR * (D ? AUD_MAXB * D : TABLE_MAXD) / 4 + NT - 1) / NT;
     constexpr int KS = D ? D / 4 : 1;
     static_assert(D != 0 || (W == 1 && SR == 16), "the general form is one wave and one 16-row tile per stage");
-    const int d = D ? D : a.d, K = a.K, CAP = K + KNN_SLACK, S = a.S, NB = 1 + S;
+    const int d = D ? D : a.d, K = a.K, S = a.S, NB = 1 + S;
     // used blocks: their rank among the used ones fixes the column offset in a staged row / the A column in LDS
     int rank[AUD_MAXB], n_used = 0;
 #pragma unroll
@@ -94,18 +93,14 @@ __global__ __launch_bounds__(64 * W) void audience_chunk_kernel(AudArgs a) {
     float *s_b = smem;                                       // [SR][LD] the stage's user rows (this panel's columns)
     float *s_inv = s_b + SR * LD;                            // [SR][AUD_MAXB] reciprocal norms of their head blocks (entry 1 + h)
     float *s_mean = s_inv + SR * AUD_MAXB;                   // [SR]     their catalogue means of ui (TIE)
-    float *s_lv = s_mean + SR;                               // [ROWS][CAP] list scores
-    int *s_li = (int *)(s_lv + ROWS * CAP);                  // [ROWS][CAP] list ids
-    int *s_cnt = s_li + ROWS * CAP;                          // [ROWS]
-    float *s_thr = (float *)(s_cnt + ROWS);                  // [ROWS]
-    float *s_a = s_thr + ROWS;                               // D == 0: [n_used][d / 4][64] lane-private item operands
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const KnnLists my = knn_lists(s_mean + SR, ROWS, K, wave);   // knn_list_bytes(ROWS, K): the items' K-lists, this wave's 16
+    float *s_a = my.end;                                     // D == 0: [n_used][d / 4][64] lane-private item operands
     const int li = lane & 15, kq = lane >> 4;
     const int64_t q0 = (int64_t)blockIdx.x * ROWS + wave * 16;   // this wave's first query item
     const int chunk = blockIdx.y;
-    const int64_t c_begin = (int64_t)chunk * AUD_CHUNK;
-    const int64_t c_end = c_begin + AUD_CHUNK < a.U ? c_begin + AUD_CHUNK : a.U;
-    const float NEG = -__builtin_huge_valf(), POS = __builtin_huge_valf();
+    const int64_t c_begin = (int64_t)chunk * KNN_CHUNK;
+    const int64_t c_end = c_begin + KNN_CHUNK < a.U ? c_begin + KNN_CHUNK : a.U;
     const bool tie = a.predict_type == 2;
 
     // A operands: item (q0 + li), element k = 4 ks + kq of every used block; a query outside [0, Q) or an id outside the
@@ -137,14 +132,13 @@ __global__ __launch_bounds__(64 * W) void audience_chunk_kernel(AudArgs a) {
 #pragma unroll
         for (int h = 0; h < AUD_MAXB - 1; ++h)
             invq[r][h] = (it >= 0 && h < S && (a.used >> (h + 1) & 1)) ? inv_norm(a.sqn[(a.U + it) * NB + h + 1]) : 0.f;
-        thr[r] = it >= 0 ? NEG : POS;
+        thr[r] = knn_thr0(it >= 0);
     }
     if (lane < 16) {
         const int64_t q = q0 + lane;
         int64_t it = q < a.Q ? (int64_t)a.items[q] : -1;
         if (it >= a.I) it = -1;
-        s_cnt[wave * 16 + lane] = 0;
-        s_thr[wave * 16 + lane] = it >= 0 ? NEG : POS;
+        knn_list_reset(my, lane, it >= 0);
     }
 
     // a panel of a stage: its rows as float4 over the workgroup; the rows' squared head norms and row sums on the first SR threads
@@ -198,11 +192,6 @@ __global__ __launch_bounds__(64 * W) void audience_chunk_kernel(AudArgs a) {
             s_mean[tid] = rs_pf / a.I_total;
         }
     };
-
-    float *my_lv = s_lv + wave * 16 * CAP;
-    int *my_li = s_li + wave * 16 * CAP;
-    int *my_cnt = s_cnt + wave * 16;
-    float *my_thr = s_thr + wave * 16;
 
     aud_v4f acc[AUD_MAXB];
     int64_t s0 = c_begin;
@@ -262,33 +251,7 @@ __global__ __launch_bounds__(64 * W) void audience_chunk_kernel(AudArgs a) {
                 any = any || pass[r];
             }
             if (__ballot(any) == 0ull) continue;             // wave-uniform: the steady state
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                if (!pass[r]) continue;
-                bool keep = true;
-                if (a.excl_ptr) {
-                    const int64_t q = q0 + 4 * kq + r;
-                    const int64_t e1 = a.excl_ptr[q + 1];
-                    for (int64_t e = a.excl_ptr[q]; e < e1 && keep; ++e) keep = a.excl_users[e] != (int)cand;
-                }
-                if (keep) {
-                    const int row = 4 * kq + r;
-                    const int pos = atomicAdd(&my_cnt[row], 1);  // <= CAP - 16 before the tile, at most 16 adds per row and tile
-                    my_lv[row * CAP + pos] = s[r];
-                    my_li[row * CAP + pos] = (int)cand;
-                }
-            }
-            wave_lds_sync();
-            unsigned long long full = __ballot(lane < 16 && my_cnt[lane & 15] > CAP - 16) & 0xffffull;
-            if (full) {                                      // wave-uniform
-                while (full) {
-                    const int row = __builtin_ctzll(full);
-                    full &= full - 1;
-                    knn_compact<E>(my_lv + row * CAP, my_li + row * CAP, &my_cnt[row], &my_thr[row], K, lane);
-                }
-#pragma unroll
-                for (int r = 0; r < 4; ++r) thr[r] = my_thr[4 * kq + r];
-            }
+            KNN_OFFER(my, E, K, lane, kq, q0, cand, s, pass, thr, a.excl_ptr, a.excl_users, true);
         }
         __syncthreads();                                     // every wave is done with the panel
         if (more) store_stage(npanel);
@@ -298,18 +261,7 @@ __global__ __launch_bounds__(64 * W) void audience_chunk_kernel(AudArgs a) {
         panel = npanel;
     }
 
-    // the chunk's K best of every item of this wave, in rank order, fillers behind them
-    for (int row = 0; row < 16; ++row) {
-        const int64_t q = q0 + row;
-        if (q >= a.Q) break;                                 // wave-uniform
-        knn_compact<E>(my_lv + row * CAP, my_li + row * CAP, &my_cnt[row], &my_thr[row], K, lane);
-        const int n = my_cnt[row];
-        const int64_t o = (q * a.n_chunks + chunk) * K;
-        for (int k = lane; k < K; k += 64) {
-            a.ws_val[o + k] = k < n ? my_lv[row * CAP + k] : NEG;
-            a.ws_idx[o + k] = k < n ? my_li[row * CAP + k] : -1;
-        }
-    }
+    KNN_FLUSH(my, E, K, lane, q0, a.Q, a.n_chunks, chunk, a.ws_val, a.ws_idx);
 }
 
 __global__ __launch_bounds__(256) void audience_hits_kernel(const int32_t *__restrict__ lists, int64_t Q, int K,
@@ -334,21 +286,14 @@ __global__ __launch_bounds__(256) void audience_hits_kernel(const int32_t *__res
 
 template <int D, int W, bool FAST>
 static int aud_launch(const AudArgs &a, int64_t n_tiles, hipStream_t s) {
-    const size_t lds = aud_lds_bytes(D, W, a.d, aud_popc(a.used), a.K);
-    if (lds > 64 * 1024) {
-        int rc = check_hip(hipFuncSetAttribute((const void *)audience_chunk_kernel<D, W, FAST>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               (int)lds), "audience_topk (LDS)");
-        if (rc) return rc;
-    }
-    hipLaunchKernelGGL((audience_chunk_kernel<D, W, FAST>), dim3((unsigned)n_tiles, (unsigned)a.n_chunks), dim3(64 * W), lds, s, a);
-    ELIMREC_LAUNCH_CHECK("audience_topk");
-    return 0;
+    return knn_launch_chunks("audience_topk", audience_chunk_kernel<D, W, FAST>, a, n_tiles, a.n_chunks, 64 * W,
+                             aud_lds_bytes(D, W, a.d, aud_popc(a.used), a.K), s);
 }
 
 template <bool FAST>
 static int aud_dispatch(const AudArgs &a, int64_t Q, hipStream_t s) {
-    const bool wide = a.K <= AUD_SMALLK && (a.d == 32 || a.d == 64);
-    const int rows = wide ? AUD_TILE : 16;
+    const bool wide = a.K <= KNN_SMALLK && (a.d == 32 || a.d == 64);
+    const int rows = wide ? KNN_TILE : 16;
     const int64_t n_tiles = (Q + rows - 1) / rows;
     ELIMREC_REQUIRE(n_tiles < (int64_t)INT32_MAX, "audience_topk: too many item tiles for one launch");
     if (a.d == 32) return wide ? aud_launch<32, 4, FAST>(a, n_tiles, s) : aud_launch<32, 1, FAST>(a, n_tiles, s);
@@ -356,66 +301,51 @@ static int aud_dispatch(const AudArgs &a, int64_t Q, hipStream_t s) {
     return aud_launch<0, 1, FAST>(a, n_tiles, s);
 }
 
-static inline int64_t aud_chunks(int64_t U) { return (U + AUD_CHUNK - 1) / AUD_CHUNK; }
-
 }  // namespace elimrec
 
 using namespace elimrec;
 
-extern "C" int elimrec_audience_topk_chunk(void) { return AUD_CHUNK; }
-extern "C" int elimrec_audience_topk_tile(void) { return AUD_TILE; }
+extern "C" int elimrec_audience_topk_chunk(void) { return KNN_CHUNK; }
+extern "C" int elimrec_audience_topk_tile(void) { return KNN_TILE; }
 
 extern "C" size_t elimrec_audience_topk_workspace(int64_t Q, int64_t U, int K) {
-    if (Q <= 0 || U <= 0 || K <= 0) return 16;
-    const size_t pairs = (size_t)Q * (size_t)aud_chunks(U) * (size_t)K;
-    return align_up(pairs * 4, 16) + align_up(pairs * 4, 16);
+    return knn_workspace_bytes(Q, U, K);
 }
 
 extern "C" int elimrec_audience_topk(const float *d_Y, int64_t ldy, int64_t U, int64_t I, int d, int S, uint32_t head_mask, int fusion_mode,
                                      int predict_type, const float *d_sqnorm, const float *d_row_sum, int64_t I_total,
                                      const int32_t *d_items, int64_t Q, const int64_t *d_excl_ptr, const int32_t *d_excl_users, int K,
                                      int32_t *d_idx, float *d_val, void *d_workspace, size_t workspace_bytes, void *stream) {
-    ELIMREC_REQUIRE(K >= 1 && K <= AUD_MAXK, "audience_topk: 1 <= K <= %d, got %d", AUD_MAXK, K);
+    if (int rc = knn_check_k("audience_topk", K)) return rc;
     if (int rc = table_dims("audience_topk", d, 1)) return rc;
     ELIMREC_REQUIRE(S >= 0 && S <= AUD_MAXB - 1, "audience_topk: 0 <= S <= %d, got %d", AUD_MAXB - 1, S);
     ELIMREC_REQUIRE(fusion_mode >= 0 && fusion_mode <= 2 && predict_type >= 0 && predict_type <= 2,
                     "audience_topk: fusion mode %d / predict type %d outside 0 .. 2", fusion_mode, predict_type);
-    ELIMREC_REQUIRE(Q >= 0 && U >= 0 && I >= 0 && U < (int64_t)INT32_MAX - AUD_CHUNK && I < (int64_t)INT32_MAX,
-                    "audience_topk: need Q >= 0, 0 <= U < 2^31 - %d and 0 <= I < 2^31", AUD_CHUNK + 1);
+    ELIMREC_REQUIRE(Q >= 0 && U >= 0 && I >= 0 && U < (int64_t)INT32_MAX - KNN_CHUNK && I < (int64_t)INT32_MAX,
+                    "audience_topk: need Q >= 0, 0 <= U < 2^31 - %d and 0 <= I < 2^31", KNN_CHUNK + 1);
     ELIMREC_REQUIRE(ldy >= (int64_t)(1 + S) * d, "audience_topk: ldy < (1 + S) d");
     if (Q == 0) return 0;
     ELIMREC_REQUIRE(d_items && d_idx && d_workspace, "audience_topk: null pointer");
-    ELIMREC_REQUIRE((d_excl_ptr == nullptr) == (d_excl_users == nullptr), "audience_topk: the exclusion CSR needs both arrays or neither");
-    ELIMREC_REQUIRE(((uintptr_t)d_workspace & 15) == 0, "audience_topk: the workspace must be 16-byte aligned");
-    const size_t need = elimrec_audience_topk_workspace(Q, U, K);
-    ELIMREC_REQUIRE(workspace_bytes >= need, "audience_topk: workspace too small (%zu < %zu bytes)", workspace_bytes, need);
+    if (int rc = knn_check_buffers("audience_topk", d_excl_ptr, d_excl_users, d_workspace, workspace_bytes, Q, U, K)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    const int64_t n_chunks = aud_chunks(U);
-    if (n_chunks == 0 || I == 0) {                           // no users, or no catalogue to query: every list is fillers
-        int rc = check_hip(hipMemsetAsync(d_idx, 0xff, (size_t)Q * K * sizeof(int32_t), s), "audience_topk (fill)");
-        if (rc == 0 && d_val) rc = check_hip(hipMemsetD32Async((hipDeviceptr_t)d_val, (int)0xff800000u, (size_t)Q * K, s), "audience_topk (fill)");
-        return rc;
-    }
+    if (U == 0 || I == 0) return knn_fill_empty("audience_topk", d_idx, d_val, Q, K, s);    // no users, or no catalogue to query
     int used = 1;                                            // block 0 always; a head's block if the fusion reads its cosine
     for (int h = 0; h < S; ++h)
         if (predict_type != 0 && (fusion_mode != 0 || (head_mask >> h & 1u))) used |= 1 << (h + 1);
     ELIMREC_REQUIRE(d_Y, "audience_topk: null pointer");
     ELIMREC_REQUIRE(used == 1 || d_sqnorm, "audience_topk: the heads' cosines need d_sqnorm");
     ELIMREC_REQUIRE(predict_type != 2 || (d_row_sum && I_total > 0), "audience_topk: TIE needs d_row_sum and I_total > 0");
-    ELIMREC_REQUIRE(n_chunks <= 65535, "audience_topk: %lld chunks exceed one launch", (long long)n_chunks);
-    ELIMREC_REQUIRE(Q < (int64_t)INT32_MAX && n_chunks * K < (int64_t)INT32_MAX, "audience_topk: too many items or chunks for the merge");
-    const size_t pairs = (size_t)Q * (size_t)n_chunks * (size_t)K;
+    KnnWorkspace ws;
+    if (int rc = knn_carve("audience_topk", "items", Q, U, K, d_workspace, &ws)) return rc;
     AudArgs a;
     a.Y = d_Y; a.ldy = ldy; a.U = U; a.I = I; a.d = d; a.S = S;
     a.head_mask = head_mask; a.fusion_mode = fusion_mode; a.predict_type = predict_type;
     a.sqn = d_sqnorm; a.row_sum = d_row_sum; a.I_total = (float)(I_total > 0 ? I_total : 1);
     a.items = d_items; a.Q = Q; a.excl_ptr = d_excl_ptr; a.excl_users = d_excl_users;
-    a.K = K; a.n_chunks = (int)n_chunks; a.vec = table_vec(d_Y, ldy); a.used = used;
-    a.ws_val = (float *)d_workspace;
-    a.ws_idx = (int32_t *)((char *)d_workspace + align_up(pairs * 4, 16));
-    int rc = elimrec_score_get_math() ? aud_dispatch<true>(a, Q, s) : aud_dispatch<false>(a, Q, s);
-    if (rc) return rc;
-    return elimrec_topk_merge(a.ws_val, a.ws_idx, (int)Q, (int)(n_chunks * K), K, d_idx, d_val, stream);
+    a.K = K; a.n_chunks = (int)ws.n_chunks; a.vec = table_vec(d_Y, ldy); a.used = used;
+    a.ws_val = ws.val; a.ws_idx = ws.idx;
+    if (int rc = with_fast(elimrec_score_get_math() != 0, [&](auto fast) { return aud_dispatch<fast.value>(a, Q, s); })) return rc;
+    return knn_merge(ws, Q, K, d_idx, d_val, stream);
 }
 
 extern "C" int elimrec_audience_hits(const int32_t *d_lists, int64_t Q, int K, const int64_t *d_ptr, const int32_t *d_users,

@@ -9,15 +9,11 @@
 //     score = (dot * (1 / max(sqrt(sq_q), 1e-12))) * (1 / max(sqrt(sq_c), 1e-12))
 // in this order, IEEE division: a pair's bits depend on the two rows' values and d alone (the k-loop runs 0, 4, 8, ... for every
 // pair; rows outside the table are zero operands and never read), not on its tile, stage, chunk or grid.
-// Selection (per chunk): a query row's list lives in LDS, CAP = K + 32 (score, id) slots, touched by its own wave only. A lane
-// whose score is > the row's threshold (-inf until K are kept, then the K-th best kept score; candidates arrive in ascending id
-// order, so an equal score later in the chunk loses the tie and is rightly dropped) checks the exclusions -- the query row itself,
-// then a linear scan of the query's CSR list: only scores that beat the threshold get there -- and appends with an LDS integer
-// add (a tile appends at most 16 entries per row). When a row holds more than CAP - 16 entries its wave ranks them by (score
-// descending, id ascending) by counting, keeps the K best in rank order and raises the threshold; the order of arrival in the
-// list never reaches the result. After warm-up the epilogue is two multiplies and one compare per score.
-// A chunk leaves K (score, id) pairs per query (id -1 / -inf where it has fewer) in the workspace, laid out [Q][chunks x K];
-// elimrec_topk_merge ranks them by the same order into the result.
+// Selection (per chunk) and everything else around the multiply is knn_select.h's, shared with audience.hip: the K-list per query
+// row in LDS (CAP = K + 32 slots, its layout, the offer of a tile's scores with the exclusion scan, the cut to the K best, the
+// flush of K pairs per query and chunk into the workspace [Q][chunks x K]) and the host front end (chunks, workspace, the shared
+// requirements, the launch, elimrec_topk_merge). This kernel's own exclusion clause is the query row itself (exclude_self); after
+// warm-up its epilogue is two multiplies and one compare per score.
 // Query tile and LDS: K <= 64 -> 4 waves, 64 query rows, lists 64 x 96 x 8 B = 48 KiB, stage <= 17 KiB (64 rows at d <= 64, 32
 // at d = 128, 16 otherwise), lane-private A columns d x 256 B for the general d (64 KiB at d = 256: one workgroup per CU there,
 // two or more for every other shape). K > 64 -> the tile is cut to ONE wave, 16 query rows: lists 16 x 288 x 8 B = 36 KiB,
@@ -29,7 +25,6 @@
 
 namespace elimrec {
 
-constexpr int KNN_CHUNK = 4096, KNN_TILE = 64, KNN_MAXK = 256, KNN_SMALLK = 64;
 constexpr int KNN_OVERLAP_MAXK = 1024;
 typedef float knn_v4f __attribute__((ext_vector_type(4)));
 
@@ -45,8 +40,8 @@ struct KnnArgs {
 constexpr int knn_stage_rows(int D, int W) { return (D == 0 || W == 1) ? 16 : (D <= 64 ? 64 : 32); }
 // dynamic LDS of one workgroup, in bytes (host and device agree through this one function)
 static inline size_t knn_lds_bytes(int D, int W, int d, int K) {
-    const size_t sr = (size_t)knn_stage_rows(D, W), cap = (size_t)K + KNN_SLACK, rows = 16 * (size_t)W;
-    return sr * (d + 4) * 4 + sr * 4 + rows * cap * 8 + rows * 8 + (D == 0 ? (size_t)W * (d / 4) * 64 * 4 : 0);
+    const size_t sr = (size_t)knn_stage_rows(D, W);
+    return sr * (d + 4) * 4 + sr * 4 + knn_list_bytes(16 * (size_t)W, K) + (D == 0 ? (size_t)W * (d / 4) * 64 * 4 : 0);
 }
 
 // D: 32 / 64 / 128 = the dimension at compile time, query operands in registers; 0 = any d % 4 == 0 up to TABLE_MAXD.
@@ -54,24 +49,20 @@ static inline size_t knn_lds_bytes(int D, int W, int d, int K) {
 template <int D, int W>
 __global__ __launch_bounds__(64 * W) void knn_chunk_kernel(KnnArgs a) {
     constexpr int SR = knn_stage_rows(D, W), NT = 64 * W, ROWS = 16 * W;
-    constexpr int E = W == 4 ? (KNN_SMALLK + KNN_SLACK + 63) / 64 : (KNN_MAXK + KNN_SLACK + 63) / 64;
+    constexpr int E = knn_list_regs(W);
     constexpr int PFN = (SR * (D ? D : TABLE_MAXD) / 4 + NT - 1) / NT;
-    const int d = D ? D : a.d, LD = d + 4, K = a.K, CAP = K + KNN_SLACK;
+    const int d = D ? D : a.d, LD = d + 4, K = a.K;
     extern __shared__ float smem[];
     float *s_b = smem;                                       // [SR][LD] the stage's candidate rows
     float *s_invc = s_b + SR * LD;                           // [SR]     their reciprocal norms
-    float *s_lv = s_invc + SR;                               // [ROWS][CAP] list scores
-    int *s_li = (int *)(s_lv + ROWS * CAP);                  // [ROWS][CAP] list ids
-    int *s_cnt = s_li + ROWS * CAP;                          // [ROWS]
-    float *s_thr = (float *)(s_cnt + ROWS);                  // [ROWS]
-    float *s_a = s_thr + ROWS;                               // D == 0: [W][d / 4][64] lane-private query operands
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const KnnLists my = knn_lists(s_invc + SR, ROWS, K, wave);   // knn_list_bytes(ROWS, K): the query rows' K-lists, this wave's 16
+    float *s_a = my.end;                                     // D == 0: [W][d / 4][64] lane-private query operands
     const int li = lane & 15, kq = lane >> 4;
     const int64_t q0 = (int64_t)blockIdx.x * ROWS + wave * 16;   // this wave's first query
     const int chunk = blockIdx.y;
     const int64_t c_begin = (int64_t)chunk * KNN_CHUNK;
     const int64_t c_end = c_begin + KNN_CHUNK < a.n_rows ? c_begin + KNN_CHUNK : a.n_rows;
-    const float NEG = -__builtin_huge_valf(), POS = __builtin_huge_valf();
 
     // A operands: query (q0 + li), element k = 4 ks + kq; a query outside [0, Q) or with an id outside the table is all zeros
     float qa[D ? D / 4 : 1];
@@ -97,14 +88,13 @@ __global__ __launch_bounds__(64 * W) void knn_chunk_kernel(KnnArgs a) {
         if (qr >= a.n_rows) qr = -1;
         qid[r] = (int)qr;
         invq[r] = qr >= 0 ? inv_norm(a.sq[qr * a.ld_sq]) : 0.f;
-        thr[r] = qr >= 0 ? NEG : POS;
+        thr[r] = knn_thr0(qr >= 0);
     }
     if (lane < 16) {
         const int64_t q = q0 + lane;
         int64_t qr = q < a.Q ? (int64_t)a.qrows[q] : -1;
         if (qr >= a.n_rows) qr = -1;
-        s_cnt[wave * 16 + lane] = 0;
-        s_thr[wave * 16 + lane] = qr >= 0 ? NEG : POS;
+        knn_list_reset(my, lane, qr >= 0);
     }
 
     // a stage's rows as float4 over the workgroup, its squared norms on the first SR threads
@@ -135,11 +125,6 @@ __global__ __launch_bounds__(64 * W) void knn_chunk_kernel(KnnArgs a) {
         }
         if (tid < SR) s_invc[tid] = inv_norm(sq_pf);
     };
-
-    float *my_lv = s_lv + wave * 16 * CAP;
-    int *my_li = s_li + wave * 16 * CAP;
-    int *my_cnt = s_cnt + wave * 16;
-    float *my_thr = s_thr + wave * 16;
 
     load_stage(c_begin);
     store_stage();
@@ -173,51 +158,14 @@ __global__ __launch_bounds__(64 * W) void knn_chunk_kernel(KnnArgs a) {
                 any = any || pass[r];
             }
             if (__ballot(any) == 0ull) continue;             // wave-uniform: the steady state
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                if (!pass[r]) continue;
-                bool keep = !(a.exclude_self && (int)cand == qid[r]);
-                if (keep && a.excl_ptr) {
-                    const int64_t q = q0 + 4 * kq + r;
-                    const int64_t e1 = a.excl_ptr[q + 1];
-                    for (int64_t e = a.excl_ptr[q]; e < e1 && keep; ++e) keep = a.excl_rows[e] != (int)cand;
-                }
-                if (keep) {
-                    const int row = 4 * kq + r;
-                    const int pos = atomicAdd(&my_cnt[row], 1);  // <= CAP - 16 before the tile, at most 16 adds per row and tile
-                    my_lv[row * CAP + pos] = s[r];
-                    my_li[row * CAP + pos] = (int)cand;
-                }
-            }
-            wave_lds_sync();
-            unsigned long long full = __ballot(lane < 16 && my_cnt[lane & 15] > CAP - 16) & 0xffffull;
-            if (full) {                                      // wave-uniform
-                while (full) {
-                    const int row = __builtin_ctzll(full);
-                    full &= full - 1;
-                    knn_compact<E>(my_lv + row * CAP, my_li + row * CAP, &my_cnt[row], &my_thr[row], K, lane);
-                }
-#pragma unroll
-                for (int r = 0; r < 4; ++r) thr[r] = my_thr[4 * kq + r];
-            }
+            KNN_OFFER(my, E, K, lane, kq, q0, cand, s, pass, thr, a.excl_ptr, a.excl_rows, !(a.exclude_self && (int)cand == qid[r]));
         }
         __syncthreads();                                     // every wave is done with the stage
         if (more) store_stage();
         __syncthreads();
     }
 
-    // the chunk's K best of every query row of this wave, in rank order, fillers behind them
-    for (int row = 0; row < 16; ++row) {
-        const int64_t q = q0 + row;
-        if (q >= a.Q) break;                                 // wave-uniform
-        knn_compact<E>(my_lv + row * CAP, my_li + row * CAP, &my_cnt[row], &my_thr[row], K, lane);
-        const int n = my_cnt[row];
-        const int64_t o = (q * a.n_chunks + chunk) * K;
-        for (int k = lane; k < K; k += 64) {
-            a.ws_val[o + k] = k < n ? my_lv[row * CAP + k] : NEG;
-            a.ws_idx[o + k] = k < n ? my_li[row * CAP + k] : -1;
-        }
-    }
+    KNN_FLUSH(my, E, K, lane, q0, a.Q, a.n_chunks, chunk, a.ws_val, a.ws_idx);
 }
 
 __global__ __launch_bounds__(256) void list_overlap_kernel(const int32_t *__restrict__ la, const int32_t *__restrict__ lb, int64_t n_rows,
@@ -244,15 +192,7 @@ __global__ __launch_bounds__(256) void list_overlap_kernel(const int32_t *__rest
 
 template <int D, int W>
 static int knn_launch(const KnnArgs &a, int64_t n_tiles, hipStream_t s) {
-    const size_t lds = knn_lds_bytes(D, W, a.d, a.K);
-    if (lds > 64 * 1024) {
-        int rc = check_hip(hipFuncSetAttribute((const void *)knn_chunk_kernel<D, W>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-                           "cosine_topk (LDS)");
-        if (rc) return rc;
-    }
-    hipLaunchKernelGGL((knn_chunk_kernel<D, W>), dim3((unsigned)n_tiles, (unsigned)a.n_chunks), dim3(64 * W), lds, s, a);
-    ELIMREC_LAUNCH_CHECK("cosine_topk");
-    return 0;
+    return knn_launch_chunks("cosine_topk", knn_chunk_kernel<D, W>, a, n_tiles, a.n_chunks, 64 * W, knn_lds_bytes(D, W, a.d, a.K), s);
 }
 
 template <int W>
@@ -265,8 +205,6 @@ static int knn_dispatch(const KnnArgs &a, int64_t n_tiles, hipStream_t s) {
     }
 }
 
-static inline int64_t knn_chunks(int64_t n_rows) { return (n_rows + KNN_CHUNK - 1) / KNN_CHUNK; }
-
 }  // namespace elimrec
 
 using namespace elimrec;
@@ -275,16 +213,14 @@ extern "C" int elimrec_cosine_topk_chunk(void) { return KNN_CHUNK; }
 extern "C" int elimrec_cosine_topk_tile(void) { return KNN_TILE; }
 
 extern "C" size_t elimrec_cosine_topk_workspace(int64_t Q, int64_t n_rows, int K) {
-    if (Q <= 0 || n_rows <= 0 || K <= 0) return 16;
-    const size_t pairs = (size_t)Q * (size_t)knn_chunks(n_rows) * (size_t)K;
-    return align_up(pairs * 4, 16) + align_up(pairs * 4, 16);
+    return knn_workspace_bytes(Q, n_rows, K);
 }
 
 extern "C" int elimrec_cosine_topk(const float *d_T, int64_t ld, int64_t n_rows, int d, const float *d_sqnorm, int64_t ld_sq,
                                    const int32_t *d_query_rows, int64_t Q, int exclude_self, const int64_t *d_excl_ptr,
                                    const int32_t *d_excl_rows, int K, int32_t *d_idx, float *d_val, void *d_workspace,
                                    size_t workspace_bytes, void *stream) {
-    ELIMREC_REQUIRE(K >= 1 && K <= KNN_MAXK, "cosine_topk: 1 <= K <= %d, got %d", KNN_MAXK, K);
+    if (int rc = knn_check_k("cosine_topk", K)) return rc;
     if (int rc = table_dims("cosine_topk", d, 1)) return rc;
     ELIMREC_REQUIRE(Q >= 0 && n_rows >= 0 && n_rows < (int64_t)INT32_MAX - KNN_CHUNK, "cosine_topk: need Q >= 0 and 0 <= n_rows < 2^31 - %d",
                     KNN_CHUNK + 1);
@@ -292,35 +228,25 @@ extern "C" int elimrec_cosine_topk(const float *d_T, int64_t ld, int64_t n_rows,
     if (Q == 0) return 0;
     ELIMREC_REQUIRE(d_query_rows && d_idx && d_workspace, "cosine_topk: null pointer");
     ELIMREC_REQUIRE(n_rows == 0 || (d_T && d_sqnorm), "cosine_topk: null pointer");
-    ELIMREC_REQUIRE((d_excl_ptr == nullptr) == (d_excl_rows == nullptr), "cosine_topk: the exclusion CSR needs both arrays or neither");
-    ELIMREC_REQUIRE(((uintptr_t)d_workspace & 15) == 0, "cosine_topk: the workspace must be 16-byte aligned");
-    const size_t need = elimrec_cosine_topk_workspace(Q, n_rows, K);
-    ELIMREC_REQUIRE(workspace_bytes >= need, "cosine_topk: workspace too small (%zu < %zu bytes)", workspace_bytes, need);
+    if (int rc = knn_check_buffers("cosine_topk", d_excl_ptr, d_excl_rows, d_workspace, workspace_bytes, Q, n_rows, K)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    const int64_t n_chunks = knn_chunks(n_rows);
-    if (n_chunks == 0) {                                     // an empty table: every list is fillers
-        int rc = check_hip(hipMemsetAsync(d_idx, 0xff, (size_t)Q * K * sizeof(int32_t), s), "cosine_topk (fill)");
-        if (rc == 0 && d_val) rc = check_hip(hipMemsetD32Async((hipDeviceptr_t)d_val, (int)0xff800000u, (size_t)Q * K, s), "cosine_topk (fill)");
-        return rc;
-    }
-    ELIMREC_REQUIRE(n_chunks <= 65535, "cosine_topk: %lld chunks exceed one launch", (long long)n_chunks);
-    ELIMREC_REQUIRE(Q < (int64_t)INT32_MAX && n_chunks * K < (int64_t)INT32_MAX, "cosine_topk: too many queries or chunks for the merge");
-    const size_t pairs = (size_t)Q * (size_t)n_chunks * (size_t)K;
+    if (n_rows == 0) return knn_fill_empty("cosine_topk", d_idx, d_val, Q, K, s);       // an empty table
+    KnnWorkspace ws;
+    if (int rc = knn_carve("cosine_topk", "queries", Q, n_rows, K, d_workspace, &ws)) return rc;
     KnnArgs a;
     a.T = d_T; a.ld = ld; a.n_rows = n_rows; a.d = d;
     a.sq = d_sqnorm; a.ld_sq = ld_sq;
     a.qrows = d_query_rows; a.Q = Q; a.exclude_self = exclude_self ? 1 : 0;
     a.excl_ptr = d_excl_ptr; a.excl_rows = d_excl_rows;
-    a.K = K; a.n_chunks = (int)n_chunks;
+    a.K = K; a.n_chunks = (int)ws.n_chunks;
     a.vec = table_vec(d_T, ld);
-    a.ws_val = (float *)d_workspace;
-    a.ws_idx = (int32_t *)((char *)d_workspace + align_up(pairs * 4, 16));
+    a.ws_val = ws.val; a.ws_idx = ws.idx;
     const int rows = K <= KNN_SMALLK ? KNN_TILE : 16;
     const int64_t n_tiles = (Q + rows - 1) / rows;
     ELIMREC_REQUIRE(n_tiles < (int64_t)INT32_MAX, "cosine_topk: too many query tiles for one launch");
     int rc = K <= KNN_SMALLK ? knn_dispatch<4>(a, n_tiles, s) : knn_dispatch<1>(a, n_tiles, s);
     if (rc) return rc;
-    return elimrec_topk_merge(a.ws_val, a.ws_idx, (int)Q, (int)(n_chunks * K), K, d_idx, d_val, stream);
+    return knn_merge(ws, Q, K, d_idx, d_val, stream);
 }
 
 extern "C" int elimrec_list_overlap(const int32_t *d_a, const int32_t *d_b, int64_t n_rows, int K, int32_t *d_count, void *stream) {

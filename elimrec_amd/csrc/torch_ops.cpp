@@ -77,6 +77,32 @@ const at::Tensor rowmajor(const at::Tensor &t, const char *name) {
     return t.stride(1) == 1 ? t : t.contiguous();
 }
 
+// No unchecked id reaches a kernel: the host checks of id lists, in the ops' own words. index_error: the range failure is an
+// IndexError (the ops that mirror ops.py's checked queries) or the plain error of the older ops.
+// every id of t in [0, bound), else "elimrec::<who>: <what> span [lo, hi], <has> <bound> <unit>"
+void checked_ids(const at::Tensor &t, int64_t bound, bool index_error, const char *who, const char *what, const char *has, const char *unit) {
+    if (t.numel() == 0) return;
+    const int64_t lo = t.min().item<int64_t>(), hi = t.max().item<int64_t>();
+    if (index_error) TORCH_CHECK_INDEX(lo >= 0 && hi < bound, "elimrec::", who, ": ", what, " span [", lo, ", ", hi, "], ", has, " ", bound, " ", unit);
+    TORCH_CHECK(lo >= 0 && hi < bound, "elimrec::", who, ": ", what, " span [", lo, ", ", hi, "], ", has, " ", bound, " ", unit);
+}
+
+// ptr (n_lists + 1 entries, the caller's check) ascends from 0 to len(ids) ...
+void checked_csr(const at::Tensor &ptr, const at::Tensor &ids, int64_t n_lists, const char *who, const char *ptr_name, const char *ids_name) {
+    const at::Tensor hp = ptr.cpu();
+    const int64_t *p = hp.data_ptr<int64_t>();
+    bool ok = p[0] == 0 && p[n_lists] == ids.numel();
+    for (int64_t b = 0; b < n_lists && ok; ++b) ok = p[b + 1] >= p[b];
+    TORCH_CHECK(ok, "elimrec::", who, ": ", ptr_name, " must ascend from 0 to len(", ids_name, ") = ", ids.numel());
+}
+
+// ... and its ids lie in [0, bound)
+void checked_csr(const at::Tensor &ptr, const at::Tensor &ids, int64_t n_lists, int64_t bound, bool index_error, const char *who,
+                 const char *ptr_name, const char *ids_name, const char *what, const char *has, const char *unit) {
+    checked_csr(ptr, ids, n_lists, who, ptr_name, ids_name);
+    checked_ids(ids, bound, index_error, who, what, has, unit);
+}
+
 at::Tensor propagate(const at::Tensor &rowptr, const at::Tensor &col, const at::Tensor &val, const at::Tensor &X, int64_t L,
                      bool transpose) {
     need(rowptr, "rowptr", at::kInt, 1); need(col, "col", at::kInt, 1); need(val, "val", at::kFloat, 1);
@@ -203,18 +229,7 @@ at::Tensor group_metric_means(const at::Tensor &rows, const at::Tensor &group_pt
     const at::Tensor gp = group_ptr.contiguous(), gr = group_rows.contiguous();
     const int64_t G = gp.numel() - 1, n_listed = gr.numel();
     TORCH_CHECK(G >= 1, "elimrec::group_metric_means: group_ptr needs G + 1 >= 2 entries");
-    {   // no unchecked index reaches the kernel: the CSR is validated on the host
-        const at::Tensor hp = gp.cpu();
-        const int64_t *p = hp.data_ptr<int64_t>();
-        bool ok = p[0] == 0 && p[G] == n_listed;
-        for (int64_t g = 0; g < G && ok; ++g) ok = p[g] <= p[g + 1];
-        TORCH_CHECK(ok, "elimrec::group_metric_means: group_ptr must ascend from 0 to len(group_rows) = ", n_listed);
-        if (n_listed > 0) {
-            const int64_t lo = gr.min().item<int64_t>(), hi = gr.max().item<int64_t>();
-            TORCH_CHECK(lo >= 0 && hi < r.size(0), "elimrec::group_metric_means: row indices span [", lo, ", ", hi, "], the block has ",
-                        r.size(0), " rows");
-        }
-    }
+    checked_csr(gp, gr, G, r.size(0), false, "group_metric_means", "group_ptr", "group_rows", "row indices", "the block has", "rows");
     at::Tensor out = at::empty({G, r.size(1)}, r.options());
     const size_t need_ws = elimrec_group_metric_means_workspace(n_listed, (int)r.size(1), (int)G);
     at::Tensor ws = at::empty({(int64_t)(need_ws ? need_ws : 1)}, r.options().dtype(at::kByte));
@@ -370,17 +385,7 @@ at::Tensor rank_targets(const at::Tensor &scores, const at::Tensor &tgt_ptr, con
     const at::Tensor tp = tgt_ptr.contiguous(), ti = tgt_items.contiguous();
     const int64_t B = sc.size(0), I = sc.size(1), n = ti.numel();
     TORCH_CHECK(tp.numel() == B + 1, "elimrec::rank_targets: tgt_ptr needs B + 1 = ", B + 1, " entries, got ", tp.numel());
-    {   // no unchecked id reaches the kernel: the CSR is validated on the host
-        const at::Tensor hp = tp.cpu();
-        const int64_t *p = hp.data_ptr<int64_t>();
-        bool ok = p[0] == 0 && p[B] == n;
-        for (int64_t b = 0; b < B && ok; ++b) ok = p[b + 1] >= p[b];
-        TORCH_CHECK(ok, "elimrec::rank_targets: tgt_ptr must ascend from 0 to len(tgt_items) = ", n);
-        if (n > 0) {
-            const int64_t lo = ti.min().item<int64_t>(), hi = ti.max().item<int64_t>();
-            TORCH_CHECK(lo >= 0 && hi < I, "elimrec::rank_targets: item ids span [", lo, ", ", hi, "], the catalogue has ", I, " items");
-        }
-    }
+    checked_csr(tp, ti, B, I, false, "rank_targets", "tgt_ptr", "tgt_items", "item ids", "the catalogue has", "items");
     at::Tensor out = at::empty({n}, ti.options());
     if (n == 0 || B == 0) return out;
     check(elimrec_rank_targets(sc.data_ptr<float>(), B, I, sc.stride(0), tp.data_ptr<int64_t>(), ti.data_ptr<int32_t>(), n,
@@ -399,10 +404,7 @@ std::tuple<at::Tensor, at::Tensor> cosine_topk(const at::Tensor &table, const at
     TORCH_CHECK(K >= 1 && K <= 256, "elimrec::cosine_topk: 1 <= K <= 256, got ", K);
     TORCH_CHECK(d % 4 == 0 && d >= 4 && d <= 256, "elimrec::cosine_topk: the table needs d % 4 == 0 and 4 <= d <= 256 columns, got ", d);
     TORCH_CHECK(sqnorm.numel() == n, "elimrec::cosine_topk: sqnorm needs one entry per table row (", n, "), got ", sqnorm.numel());
-    if (Q > 0) {    // no unchecked id reaches the kernel
-        const int64_t lo = q.min().item<int64_t>(), hi = q.max().item<int64_t>();
-        TORCH_CHECK_INDEX(lo >= 0 && hi < n, "elimrec::cosine_topk: query rows span [", lo, ", ", hi, "], the table has ", n, " rows");
-    }
+    checked_ids(q, n, true, "cosine_topk", "query rows", "the table has", "rows");
     at::Tensor idx = at::empty({Q, K}, q.options()), val = at::empty({Q, K}, t.options());
     if (Q == 0) return {idx, val};
     const size_t need_ws = elimrec_cosine_topk_workspace(Q, n, (int)K);
@@ -429,27 +431,15 @@ std::tuple<at::Tensor, at::Tensor> audience_topk(const at::Tensor &Y, int64_t U,
     TORCH_CHECK(S >= 0 && S <= 3, "elimrec::audience_topk: 0 <= S <= 3, got ", S);
     TORCH_CHECK(U >= 0 && I >= 0 && y.size(0) == U + I && y.size(1) >= (1 + S) * d, "elimrec::audience_topk: Y must be [U + I x >= (1 + S) d]");
     TORCH_CHECK(excl_ptr.has_value() == excl_users.has_value(), "elimrec::audience_topk: the exclusion CSR needs excl_ptr and excl_users, or neither");
-    if (Q > 0) {    // no unchecked id reaches the kernel
-        const int64_t lo = q.min().item<int64_t>(), hi = q.max().item<int64_t>();
-        TORCH_CHECK_INDEX(lo >= 0 && hi < I, "elimrec::audience_topk: query items span [", lo, ", ", hi, "], the catalogue has ", I, " items");
-    }
+    checked_ids(q, I, true, "audience_topk", "query items", "the catalogue has", "items");
     at::Tensor ep, eu;
-    if (excl_ptr.has_value()) {   // ... and the CSR is validated on the host
+    if (excl_ptr.has_value()) {
         need(*excl_ptr, "excl_ptr", at::kLong, 1); need(*excl_users, "excl_users", at::kInt, 1);
         ep = excl_ptr->contiguous(); eu = excl_users->contiguous();
         const int64_t n = eu.numel();
         TORCH_CHECK(ep.numel() == Q + 1, "elimrec::audience_topk: excl_ptr needs Q + 1 = ", Q + 1, " entries, got ", ep.numel());
-        const at::Tensor hp = ep.cpu();
-        const int64_t *p = hp.data_ptr<int64_t>();
-        bool ok = p[0] == 0 && p[Q] == n;
-        for (int64_t b = 0; b < Q && ok; ++b) ok = p[b + 1] >= p[b];
-        TORCH_CHECK(ok, "elimrec::audience_topk: excl_ptr must ascend from 0 to len(excl_users) = ", n);
-        if (n > 0) {
-            const int64_t lo = eu.min().item<int64_t>(), hi = eu.max().item<int64_t>();
-            TORCH_CHECK_INDEX(lo >= 0 && hi < U, "elimrec::audience_topk: excluded users span [", lo, ", ", hi, "], the model has ", U, " users");
-        } else {
-            eu = at::zeros({1}, q.options());      // the binding wants a device tensor; nothing of it is read
-        }
+        checked_csr(ep, eu, Q, U, true, "audience_topk", "excl_ptr", "excl_users", "excluded users", "the model has", "users");
+        if (n == 0) eu = at::zeros({1}, q.options());      // the binding wants a device tensor; nothing of it is read
     }
     at::Tensor idx = at::empty({Q, K}, q.options()), val = at::empty({Q, K}, y.options());
     if (Q == 0) return {idx, val};
@@ -637,13 +627,7 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> history_support(const
                 "elimrec::history_support: sqnorm must be [rows x ", blocks, "]");
     const at::Tensor sq = (sqnorm.dim() == 1 || sqnorm.stride(1) == 1 || blocks == 1) ? sqnorm : sqnorm.contiguous();
     TORCH_CHECK(R >= 1, "elimrec::history_support: hist_ptr needs n_rows + 1 >= 2 entries");
-    {   // the segments are validated on the host; the ids' range is the kernel's to check
-        const at::Tensor h = hp.cpu();
-        const int64_t *p = h.data_ptr<int64_t>();
-        bool ok = p[0] == 0 && p[R] == n;
-        for (int64_t r = 0; r < R && ok; ++r) ok = p[r + 1] >= p[r];
-        TORCH_CHECK(ok, "elimrec::history_support: hist_ptr must ascend from 0 to len(hist_items) = ", n);
-    }
+    checked_csr(hp, hi, R, "history_support", "hist_ptr", "hist_items");     // the ids' range is the kernel's to check
     float w[8];
     for (int64_t b = 0; b < blocks; ++b) w[b] = (float)weights[b];
     at::Tensor idx = at::empty({B, K, top}, l.options()), val = at::empty({B, K, top}, t.options());
@@ -671,17 +655,7 @@ static at::Tensor bootstrap_impl(const at::Tensor &rows, const at::Tensor *rows_
     TORCH_CHECK(G >= 1, "elimrec::", who, ": group_ptr needs G + 1 >= 2 entries");
     TORCH_CHECK(R >= 1 && R < ((int64_t)1 << 31), "elimrec::", who, ": 1 <= R < 2^31, got ", R);
     TORCH_CHECK(C >= 1, "elimrec::", who, ": rows needs at least one column");
-    {   // no unchecked index reaches the kernel: the CSR is validated on the host
-        const at::Tensor hp = gp.cpu();
-        const int64_t *p = hp.data_ptr<int64_t>();
-        bool ok = p[0] == 0 && p[G] == n_listed;
-        for (int64_t g = 0; g < G && ok; ++g) ok = p[g] <= p[g + 1];
-        TORCH_CHECK(ok, "elimrec::", who, ": group_ptr must ascend from 0 to len(group_rows) = ", n_listed);
-        if (n_listed > 0) {
-            const int64_t lo = gr.min().item<int64_t>(), hi = gr.max().item<int64_t>();
-            TORCH_CHECK(lo >= 0 && hi < n, "elimrec::", who, ": row indices span [", lo, ", ", hi, "], the block has ", n, " rows");
-        }
-    }
+    checked_csr(gp, gr, G, n, false, who, "group_ptr", "group_rows", "row indices", "the block has", "rows");
     at::Tensor out = at::empty({R, G, C}, r.options().dtype(at::kDouble));
     at::Tensor none = at::zeros({1}, gr.options());
     const int64_t step = elimrec_bootstrap_max_columns(), ld = n > 1 ? r.stride(0) : C;

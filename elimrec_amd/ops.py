@@ -1228,24 +1228,36 @@ def peer_cols_to_rows(recv, out0, out1):
 KNN_MAX_K, KNN_MAX_D = 256, 256
 
 
-class NeighbourQuery(object):
+class _ListQuery(object):
+    """What NeighbourQuery and AudienceQuery share: query ids in [0, bound) and, optionally, per query a list of ids in
+    [0, excl_bound) to leave out as CSR, checked on the host and then resident on `device` as ids / excl_ptr / excl_ids. The two
+    classes give the nouns: names = (the ids' name, the excluded ids' name), spans = the two IndexErrors' words."""
+
+    def __init__(self, ids, bound, device, excl_ptr, excl_ids, excl_bound, names, spans):
+        who = type(self).__name__
+        q = _checked_ids(ids, bound, who, names[0], spans[0])
+        if (excl_ptr is None) != (excl_ids is None):
+            raise ValueError("elimrec_amd.ops.%s: the exclusion CSR needs excl_ptr and %s, or neither" % (who, names[1]))
+        self.n_queries = int(q.size)
+        self.ids = _resident_ids(q, device)
+        self.excl_ptr = self.excl_ids = None
+        if excl_ptr is not None:
+            p, e = _checked_csr(excl_ptr, excl_ids, q.size, excl_bound, who, ("excl_ptr", names[1], "Q", spans[1]))
+            self.excl_ptr = torch.from_numpy(p).to(device)
+            self.excl_ids = _resident_ids(e, device)
+
+
+class NeighbourQuery(_ListQuery):
     """Query rows of an n_rows-row table and, optionally, per query a list of rows to leave out as CSR (excl_ptr [Q + 1],
     excl_rows), CHECKED ON THE HOST -- every query id and every exclusion id in [0, n_rows), ptr[0] = 0, ascending,
     ptr[Q] = len(excl_rows) -- and then resident on `device`: cosine_topk takes it as is, call after call, and no unchecked id
     ever reaches a kernel (the counterpart of TargetIndex). Exclusion lists may repeat ids, in any order, and may be empty."""
 
     def __init__(self, rows, n_rows, device, excl_ptr=None, excl_rows=None):
-        q = _checked_ids(rows, n_rows, "NeighbourQuery", "rows", "query rows span [%d, %d], the table has %d rows")
-        if (excl_ptr is None) != (excl_rows is None):
-            raise ValueError("elimrec_amd.ops.NeighbourQuery: the exclusion CSR needs excl_ptr and excl_rows, or neither")
-        self.n_rows, self.n_queries = int(n_rows), int(q.size)
-        self.rows = _resident_ids(q, device)
-        self.excl_ptr = self.excl_rows = None
-        if excl_ptr is not None:
-            p, e = _checked_csr(excl_ptr, excl_rows, q.size, n_rows, "NeighbourQuery",
-                                ("excl_ptr", "excl_rows", "Q", "excluded rows span [%d, %d], the table has %d rows"))
-            self.excl_ptr = torch.from_numpy(p).to(device)
-            self.excl_rows = _resident_ids(e, device)
+        _ListQuery.__init__(self, rows, n_rows, device, excl_ptr, excl_rows, n_rows, ("rows", "excl_rows"),
+                            ("query rows span [%d, %d], the table has %d rows", "excluded rows span [%d, %d], the table has %d rows"))
+        self.n_rows = int(n_rows)
+        self.rows, self.excl_rows = self.ids, self.excl_ids
 
 
 def cosine_topk_workspace(Q, n_rows, K):
@@ -1267,6 +1279,35 @@ def _rows_out(t, name, dtype, B, K, who, device=None):
     return p
 
 
+def _topk_dims(who, K, max_k, d, what):
+    """The first two checks of cosine_topk / audience_topk, made before the query is looked at. what: the noun of the d message."""
+    if not 1 <= K <= max_k:
+        raise ValueError("elimrec_amd.ops.%s: 1 <= K <= %d, got %d" % (who, max_k, K))
+    if d % 4 != 0 or not 4 <= d <= KNN_MAX_D:
+        raise ValueError("elimrec_amd.ops.%s: %s needs d %% 4 == 0 and 4 <= d <= %d columns, got %d" % (who, what, KNN_MAX_D, d))
+
+
+def _topk_call(who, n_cand, query, K, out_idx, out_val, workspace, device, out_device, head):
+    """The back half of cosine_topk / audience_topk (elimrec_<who> and elimrec_<who>_workspace): the outputs, the workspace, the
+    empty query, the call. n_cand: the candidate rows the workspace is sized for; head(): the entry point's arguments before K,
+    built only when the call is made."""
+    lib = _lib.load()
+    Q = query.n_queries
+    ip = _rows_out(out_idx, "out_idx", torch.int32, Q, K, who, out_device)
+    vp = _rows_out(out_val, "out_val", torch.float32, Q, K, who, out_device) if out_val is not None else None
+    need = int(getattr(lib, "elimrec_%s_workspace" % who)(Q, n_cand, K))
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=device)
+    wp = _dev(workspace, "workspace", torch.uint8)
+    if workspace.numel() < need or not workspace.is_contiguous() or wp % 16:
+        raise ValueError("elimrec_amd.ops.%s: the workspace needs %d contiguous bytes, 16-byte aligned (got %d)"
+                         % (who, need, workspace.numel()))
+    if Q == 0:
+        return out_idx
+    _lib.check(getattr(lib, "elimrec_" + who)(*(head() + (K, ip, vp, wp, workspace.numel(), _stream()))), who)
+    return out_idx
+
+
 def cosine_topk(table, sqnorm, query_rows, K, out_idx, out_val=None, exclude_self=True, excl_ptr=None, excl_rows=None,
                 workspace=None):
     """elimrec_cosine_topk: per query row the K rows of `table` closest to it by cosine, by (score descending, row id ascending):
@@ -1286,10 +1327,7 @@ def cosine_topk(table, sqnorm, query_rows, K, out_idx, out_val=None, exclude_sel
         raise ValueError("elimrec_amd.ops.cosine_topk: sqnorm must be 1-D with one entry per table row (%d) on the table's device" % n)
     ld_sq = max(1, int(sqnorm.stride(0)))
     K = int(K)
-    if not 1 <= K <= KNN_MAX_K:
-        raise ValueError("elimrec_amd.ops.cosine_topk: 1 <= K <= %d, got %d" % (KNN_MAX_K, K))
-    if d % 4 != 0 or not 4 <= d <= KNN_MAX_D:
-        raise ValueError("elimrec_amd.ops.cosine_topk: the table needs d %% 4 == 0 and 4 <= d <= %d columns, got %d" % (KNN_MAX_D, d))
+    _topk_dims("cosine_topk", K, KNN_MAX_K, d, "the table")
     if isinstance(query_rows, NeighbourQuery):
         query = query_rows
         if excl_ptr is not None or excl_rows is not None:
@@ -1299,23 +1337,9 @@ def cosine_topk(table, sqnorm, query_rows, K, out_idx, out_val=None, exclude_sel
                              % (query.n_rows, query.rows.device, n, table.device))
     else:
         query = NeighbourQuery(query_rows, n, table.device, excl_ptr, excl_rows)
-    Q = query.n_queries
-    ip = _rows_out(out_idx, "out_idx", torch.int32, Q, K, "cosine_topk")
-    vp = _rows_out(out_val, "out_val", torch.float32, Q, K, "cosine_topk") if out_val is not None else None
-    lib = _lib.load()
-    need = int(lib.elimrec_cosine_topk_workspace(Q, n, K))
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.uint8, device=table.device)
-    wp = _dev(workspace, "workspace", torch.uint8)
-    if workspace.numel() < need or not workspace.is_contiguous() or wp % 16:
-        raise ValueError("elimrec_amd.ops.cosine_topk: the workspace needs %d contiguous bytes, 16-byte aligned (got %d)"
-                         % (need, workspace.numel()))
-    if Q == 0:
-        return out_idx
-    _lib.check(lib.elimrec_cosine_topk(tp, ld, n, d, sp, ld_sq, _dev(query.rows, "query_rows", torch.int32), Q, 1 if exclude_self else 0,
-                                       _dev(query.excl_ptr, "excl_ptr", torch.int64), _dev(query.excl_rows, "excl_rows", torch.int32),
-                                       K, ip, vp, wp, workspace.numel(), _stream()), "cosine_topk")
-    return out_idx
+    return _topk_call("cosine_topk", n, query, K, out_idx, out_val, workspace, table.device, None, lambda: (
+        tp, ld, n, d, sp, ld_sq, _dev(query.rows, "query_rows", torch.int32), query.n_queries, 1 if exclude_self else 0,
+        _dev(query.excl_ptr, "excl_ptr", torch.int64), _dev(query.excl_rows, "excl_rows", torch.int32)))
 
 
 def list_overlap(a, b, out):
@@ -1335,7 +1359,7 @@ def list_overlap(a, b, out):
 AUDIENCE_MAX_K = 256
 
 
-class AudienceQuery(object):
+class AudienceQuery(_ListQuery):
     """Query items of an n_items catalogue and, optionally, per item a list of users to leave out as CSR (excl_ptr [Q + 1],
     excl_users: typically the item's training users), CHECKED ON THE HOST -- every item id in [0, n_items), every excluded user id
     in [0, n_users), ptr[0] = 0, ascending, ptr[Q] = len(excl_users) -- and then resident on `device`: audience_topk takes it as is,
@@ -1343,17 +1367,10 @@ class AudienceQuery(object):
     in any order, and may be empty."""
 
     def __init__(self, items, n_items, n_users, device, excl_ptr=None, excl_users=None):
-        q = _checked_ids(items, n_items, "AudienceQuery", "items", "query items span [%d, %d], the catalogue has %d items")
-        if (excl_ptr is None) != (excl_users is None):
-            raise ValueError("elimrec_amd.ops.AudienceQuery: the exclusion CSR needs excl_ptr and excl_users, or neither")
-        self.n_items, self.n_users, self.n_queries = int(n_items), int(n_users), int(q.size)
-        self.items = _resident_ids(q, device)
-        self.excl_ptr = self.excl_users = None
-        if excl_ptr is not None:
-            p, e = _checked_csr(excl_ptr, excl_users, q.size, n_users, "AudienceQuery",
-                                ("excl_ptr", "excl_users", "Q", "excluded users span [%d, %d], the model has %d users"))
-            self.excl_ptr = torch.from_numpy(p).to(device)
-            self.excl_users = _resident_ids(e, device)
+        _ListQuery.__init__(self, items, n_items, device, excl_ptr, excl_users, n_users, ("items", "excl_users"),
+                            ("query items span [%d, %d], the catalogue has %d items", "excluded users span [%d, %d], the model has %d users"))
+        self.n_items, self.n_users = int(n_items), int(n_users)
+        self.items, self.excl_users = self.ids, self.excl_ids
 
 
 def audience_topk_workspace(Q, U, K):
@@ -1376,10 +1393,7 @@ def audience_topk(Y, U, I, query, d, S, head_mask, fusion_mode, predict_type, K,
         _dev(Y, "Y")
     y, ldy = _rowmajor(Y, "Y")
     U, I, d, S, K = int(U), int(I), int(d), int(S), int(K)
-    if not 1 <= K <= AUDIENCE_MAX_K:
-        raise ValueError("elimrec_amd.ops.audience_topk: 1 <= K <= %d, got %d" % (AUDIENCE_MAX_K, K))
-    if d % 4 != 0 or not 4 <= d <= KNN_MAX_D:
-        raise ValueError("elimrec_amd.ops.audience_topk: a block needs d %% 4 == 0 and 4 <= d <= %d columns, got %d" % (KNN_MAX_D, d))
+    _topk_dims("audience_topk", K, AUDIENCE_MAX_K, d, "a block")
     if not 0 <= S <= 3:
         raise ValueError("elimrec_amd.ops.audience_topk: 0 <= S <= 3, got %d" % S)
     if fusion_mode not in FUSION_MODES:
@@ -1404,25 +1418,10 @@ def audience_topk(Y, U, I, query, d, S, head_mask, fusion_mode, predict_type, K,
         sqnorm = row_sqnorms(Y, d, 1 + S, torch.empty((U + I, 1 + S), dtype=torch.float32, device=Y.device))
     elif tuple(sqnorm.shape) != (U + I, 1 + S) or not sqnorm.is_contiguous() or sqnorm.device != Y.device:
         raise ValueError("elimrec_amd.ops.audience_topk: sqnorm must be contiguous [U + I x 1 + S] = [%d x %d] on Y's device" % (U + I, 1 + S))
-    Q = query.n_queries
-    ip = _rows_out(out_idx, "out_idx", torch.int32, Q, K, "audience_topk", Y.device)
-    vp = _rows_out(out_val, "out_val", torch.float32, Q, K, "audience_topk", Y.device) if out_val is not None else None
-    lib = _lib.load()
-    need = int(lib.elimrec_audience_topk_workspace(Q, U, K))
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.uint8, device=Y.device)
-    wp = _dev(workspace, "workspace", torch.uint8)
-    if workspace.numel() < need or not workspace.is_contiguous() or wp % 16:
-        raise ValueError("elimrec_amd.ops.audience_topk: the workspace needs %d contiguous bytes, 16-byte aligned (got %d)"
-                         % (need, workspace.numel()))
-    if Q == 0:
-        return out_idx
-    _lib.check(lib.elimrec_audience_topk(y, ldy, U, I, d, S, int(head_mask), FUSION_MODES[fusion_mode], PREDICT_TYPES.get(predict_type, 0),
-                                         _dev(sqnorm, "sqnorm"), _dev(row_sum, "row_sum") if tie else None, I_total,
-                                         _dev(query.items, "items", torch.int32), Q, _dev(query.excl_ptr, "excl_ptr", torch.int64),
-                                         _dev(query.excl_users, "excl_users", torch.int32), K, ip, vp, wp, workspace.numel(), _stream()),
-               "audience_topk")
-    return out_idx
+    return _topk_call("audience_topk", U, query, K, out_idx, out_val, workspace, Y.device, Y.device, lambda: (
+        y, ldy, U, I, d, S, int(head_mask), FUSION_MODES[fusion_mode], PREDICT_TYPES.get(predict_type, 0), _dev(sqnorm, "sqnorm"),
+        _dev(row_sum, "row_sum") if tie else None, I_total, _dev(query.items, "items", torch.int32), query.n_queries,
+        _dev(query.excl_ptr, "excl_ptr", torch.int64), _dev(query.excl_users, "excl_users", torch.int32)))
 
 
 def audience_hits(lists, ptr, users, out):

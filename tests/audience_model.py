@@ -16,6 +16,37 @@ def columns(Y, U, items, d, S, head_mask, fusion, ptype, row_sum=None, I_total=N
     return full[:, torch.as_tensor(items, dtype=torch.long)]
 
 
+def rising_table(U, I, d, S, seed=0):
+    """float32 [U + I, (1 + S) d] in which the score of items 0 .. I / 2 - 1 rises strictly with the user id under every predict type.
+    Block 0: user u = t_u e with t_u evenly spaced over [-2, 2], item i = a_i e, a_i in [0.9, 1] for the first half of the catalogue
+    and the same values negated for the second half -- so the dots of a listed item spread over [-2 a_i, 2 a_i], and the catalogue
+    mean of sigmoid(dot) is 1 / 2 for every user (sigmoid(x) + sigmoid(-x) = 1): TIE's second term does not depend on the user.
+    Head blocks: every user holds the same direction per head at a random positive length, so a head's cosine depends on the item
+    alone and the fusions stay increasing in the dot."""
+    g = torch.Generator().manual_seed(seed)
+    Y = torch.randn(U + I, (1 + S) * d, generator=g, dtype=torch.float64) * 0.3
+    e = sm.unit(torch.randn(d, generator=g, dtype=torch.float64))
+    a = 0.9 + 0.1 * torch.arange(I // 2, dtype=torch.float64) / (I // 2 - 1)
+    Y[:U, :d] = torch.linspace(-2.0, 2.0, U, dtype=torch.float64)[:, None] * e
+    Y[U:U + I // 2, :d] = a[:, None] * e
+    Y[U + I // 2:U + 2 * (I // 2), :d] = -a[:, None] * e
+    for h in range(1, 1 + S):
+        w = torch.randn(d, generator=g, dtype=torch.float64)
+        Y[:U, h * d:(h + 1) * d] = (0.5 + torch.rand(U, generator=g, dtype=torch.float64))[:, None] * w
+    return Y.float()
+
+
+def rising_excl(U, Q):
+    """Exclusion lists of the rising case: query 0 nobody, query 1 the 300 users it would list first, query 2 every second user,
+    the others a few single users (one id twice)."""
+    return ([[], list(range(U - 300, U)), list(range(0, U, 2))] + [[U - 1 - q, 5 * q, U - 1 - q] for q in range(3, Q)])[:Q]
+
+
+def min_gap(s64, ok):
+    """The smallest difference between the float64 scores of two eligible users of one column."""
+    return min(float(np.diff(np.sort(s64[ok[:, q], q])).min()) for q in range(s64.shape[1]))
+
+
 def eligible_mask(U, Q, excl):
     """bool [U x Q]: user u may be listed for query q (excl: one iterable of user ids per query, or None)."""
     ok = np.ones((U, Q), dtype=bool)

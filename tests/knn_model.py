@@ -70,6 +70,24 @@ def csr(lists):
     return ptr, np.asarray([int(i) for x in lists for i in x], dtype=np.int32)
 
 
+def rising_case(n, d, Q):
+    """The case in which every candidate beats the running threshold: (T float32 [n x d], query rows [Q], exclusion lists). Rows
+    0 .. n - 2 are unit vectors at evenly spaced angles from 150 down to 30 degrees to the LAST row, in a random plane of R^d, so the
+    cosine to the last row rises strictly with the row id and adjacent scores differ by >= sin(30) * (120 degrees / (n - 2)) -- 2.5e-4
+    at n = 4113, against tol(32) = 4.8e-6. A query whose own score (1) has to be the largest can only be the last row: all Q
+    queries are that row, told apart by their exclusion lists -- none; the 300 best candidates; every second row; a few single ones."""
+    ang = np.concatenate([np.linspace(5 * np.pi / 6, np.pi / 6, n - 1), [0.0]])
+    basis, _ = np.linalg.qr(np.random.default_rng(0).standard_normal((d, d)))
+    T = (np.cos(ang)[:, None] * basis[:, 0] + np.sin(ang)[:, None] * basis[:, 1]).astype(np.float32)
+    excl = [[], list(range(n - 301, n - 1)), list(range(0, n, 2))] + [[n - 2 - b, 5 * b, n - 2 - b] for b in range(3, Q)]
+    return T, np.full(Q, n - 1, dtype=np.int64), excl[:Q]
+
+
+def min_gap(s):
+    """The smallest difference between two scores of one row of s (masked float64 scores), -inf entries left out."""
+    return min(float(np.diff(np.sort(r[r > -np.inf])).min()) for r in s if (r > -np.inf).sum() > 1)
+
+
 def report_rows(ids, vals, counts, k):
     """The neighbour report's rows from the lists: ids / vals [1 + S x I x k] (fused first), counts [I] training interactions.
     Columns: overlap per head, mean score per space, mean count per space; float64 quotients rounded to float32 (what a row

@@ -138,3 +138,21 @@ def test_the_float32_model_passes_the_gpu_cases(case):
         s32 = am.columns(Y, U, items, d, S, mask, fusion, ptype).numpy()
         idx, val = am.topk32(s32, ok, K)
         am.check_lists(idx, val, s64, s32, ok, K, False, (name, ptype, fusion))
+
+
+def test_the_rising_case_has_no_near_ties():
+    """A condition on the inputs of test_audience_gpu.py's rising case, met here: under both of its scorings every column's scores
+    rise strictly with the user id, and no two eligible users are closer than the comparison's near-tie allowance (2 tol)."""
+    import test_audience_gpu as tg
+    U, Q, d = tg.RISING_U, tg.RISING_Q, tg.RISING_D
+    items, excl = list(range(Q)), am.rising_excl(U, Q)
+    ok = am.eligible_mask(U, Q, excl)
+    for ptype, fusion, S, mask in tg.RISING_SCORINGS:
+        Y = am.rising_table(U, tg.I_CAT, d, S)
+        s64 = am.columns(Y.double(), U, items, d, S, mask, fusion, ptype).numpy()
+        s32 = am.columns(Y, U, items, d, S, mask, fusion, ptype).numpy()
+        assert (np.diff(s64, axis=0) > 0).all(), (ptype, fusion)
+        tol = max(sm.tolerance(torch.from_numpy(s64[:, q]), torch.from_numpy(s32[:, q]), True)[0] for q in range(Q))
+        gap = am.min_gap(s64, ok)
+        print("audience rising %s/%s: smallest gap %.3g, allowance %.3g" % (ptype, fusion, gap, 2 * tol))
+        assert gap > 2 * tol, (ptype, fusion, gap, tol)

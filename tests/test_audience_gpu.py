@@ -64,10 +64,10 @@ def _row_sum(Yd, U, I, d, S, mask, fusion, sqn):
 class _Table(object):
     """A table on the device with its norms, and per (fusion) the pass-1 row sums."""
 
-    def __init__(self, family, U, d, S, seed):
+    def __init__(self, family, U, d, S, seed, Y=None):
         from elimrec_amd import ops
         self.U, self.d, self.S = U, d, S
-        self.Y = sm.make_table(family, U, I_CAT, d, S, seed)
+        self.Y = sm.make_table(family, U, I_CAT, d, S, seed) if Y is None else Y
         self.Yd = self.Y.to(DEV)
         self.sqn = ops.row_sqnorms(self.Yd, d, 1 + S, torch.empty(U + I_CAT, 1 + S, dtype=torch.float32, device=DEV))
         self._rs = {}
@@ -159,6 +159,34 @@ def test_lists_at_the_kernel_edges(case):
     tab = _Table(family, U, d, S, 11 + case)
     for fast in modes:
         _check_case(tab, Q, K, mask, pairs, fast, 5 + case, (name, family, U, Q, K, d, S, mask))
+
+
+RISING_U, RISING_Q, RISING_D = 4096 + 17, 17, 32
+RISING_SCORINGS = [("normal", "rubi", 0, 0), ("TIE", "hm", 3, 7)]       # predict type, fusion, S, head mask
+
+
+@pytest.mark.parametrize("K", [1, 64, 65, 256])
+def test_rising_scores(K):
+    """Every user beats the running threshold (audience_model.rising_table): every 16-row tile appends to every live list, the lists
+    are cut in mid-chunk, a second chunk of 17 users and the merge take part. The scores' gaps are beyond the near-tie allowance
+    (test_audience_cpu.py asserts it on the float64 model), so the ids are the model's exactly."""
+    T, C = _edges()
+    U, Q, d = RISING_U, RISING_Q, RISING_D
+    assert U == C + 17 and Q == 17
+    items, excl = list(range(Q)), am.rising_excl(U, Q)
+    ok = am.eligible_mask(U, Q, excl)
+    for ptype, fusion, S, mask in RISING_SCORINGS:
+        tab = _Table("benign", U, d, S, 0, Y=am.rising_table(U, I_CAT, d, S))
+        s64, s32 = tab.models(items, mask, fusion, ptype)
+        for fast in (True, False):
+            with _math(fast):
+                idx, val = tab.run(items, mask, fusion, ptype, K, excl)
+            worst, tol = am.check_lists(idx, val, s64, s32, ok, K, fast, ("rising", ptype, fusion, K, fast))
+            print("audience rising %s/%s K=%d fast=%d: worst |val - fp64| %.3g, tol %.3g" % (ptype, fusion, K, fast, worst, tol))
+            assert am.min_gap(s64, ok) > 2 * tol
+            want = np.stack([np.flatnonzero(ok[:, q])[np.argsort(-s64[ok[:, q], q], kind="stable")][:K] for q in range(Q)])
+            assert np.array_equal(idx, want), ("rising", ptype, fusion, K, fast)
+        assert not set(idx[1].tolist()) & set(excl[1]) and idx[0, 0] == U - 1
 
 
 def test_exclusions():

@@ -122,3 +122,17 @@ def test_basic_model_switch():
     assert model._neighbour_space("fused") == 0 and model._neighbour_space(model._mods[0]) == 1
     from elimrec_amd import Neighbours
     assert Neighbours._fields == ("ids", "scores")
+
+
+def test_the_rising_case_has_no_near_ties():
+    """A condition on the inputs of test_knn_gpu.py's rising case, met here: every query's scores rise strictly with the candidate
+    id, and no two candidates of a query are closer than the comparison's near-tie allowance (2 tol)."""
+    n, d, Q = 4096 + 17, 32, 17
+    T, rows, excl = km.rising_case(n, d, Q)
+    assert len(excl) == Q and not excl[0] and len(excl[1]) == 300
+    s = km.cos64(T, rows)
+    assert (np.diff(s, axis=1) > 0).all()
+    for exclude_self in (True, False):
+        gap = km.min_gap(km.masked(s, rows, exclude_self, excl))
+        print("knn rising, exclude_self=%d: smallest gap %.3g, allowance %.3g" % (exclude_self, gap, 2 * km.tol(d)))
+        assert gap > 2 * km.tol(d)

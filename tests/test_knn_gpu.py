@@ -190,6 +190,23 @@ def test_exclusions(exclude_self):
     assert (ids[4] >= 0).sum() == 5                                          # rows 0 .. 4 are left (the query, row 150, is listed too)
 
 
+@pytest.mark.parametrize("exclude_self", [True, False])
+@pytest.mark.parametrize("K", [1, 64, 65, 256])
+def test_rising_scores(K, exclude_self):
+    """Every candidate beats the running threshold (knn_model.rising_case): every 16-row tile appends to every live list, the lists
+    are cut in mid-chunk, a second chunk of 17 rows and the merge take part. The scores' gaps are far beyond the near-tie allowance
+    (test_knn_cpu.py asserts it on the float64 model), so the ids are the model's exactly."""
+    T_, C = _edges()
+    d, n, Q = 32, C + 17, 17
+    T, rows, excl = km.rising_case(n, d, Q)
+    table, sqn = _place(T, 4)
+    ids, vals = _run(table, sqn, rows, K, exclude_self=exclude_self, excl=excl)
+    s = km.masked(km.cos64(T, rows), rows, exclude_self, excl)
+    _check_lists(ids, vals, s, K, d, ("rising", K, exclude_self))
+    assert np.array_equal(ids, km.topk64(s, K)[0])
+    assert (n - 1 in ids[0].tolist()) == (not exclude_self) and not set(ids[1].tolist()) & set(excl[1])
+
+
 def test_queries():
     from elimrec_amd import ops
     T_, C = _edges()
