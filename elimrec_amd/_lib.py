@@ -231,6 +231,11 @@ SIGNATURES = {
     "elimrec_calibrate_max_classes": (c_i32, []),
     "elimrec_class_shares_csr": (c_i32, [c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_i64, c_i32, c_ptr, c_ptr]),
     "elimrec_list_calibration": (c_i32, [c_ptr, c_i64, c_i32, c_ptr, c_i64, c_i32, c_ptr, c_ptr, c_i64, ctypes.c_double, c_ptr, c_ptr]),
+    "elimrec_kmeans_assign": (c_i32, [c_ptr, c_i64, c_i64, c_i32, c_ptr, c_i64, c_ptr, c_ptr, c_i32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
+    "elimrec_kmeans_update": (c_i32, [c_ptr, c_i64, c_i64, c_i32, c_ptr, c_i64, c_ptr, c_i32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
+    "elimrec_kmeans_max_clusters": (c_i32, []),
+    "elimrec_kmeans_segment": (c_i32, []),
+    "elimrec_kmeans_workspace": (c_size, [c_i64, c_i32, c_i32]),
     "elimrec_pick_hard_negatives": (c_i32, [c_ptr, c_i64, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_i64, c_ptr, c_i64, c_i32, c_i32,
                                             ctypes.POINTER(c_f32), c_ptr, c_ptr, c_i64, c_i32, c_ptr, c_ptr, c_ptr, c_ptr]),
     "elimrec_history_support": (c_i32, [c_ptr, c_i64, c_i64, c_i32, c_i32, c_ptr, c_i64, ctypes.POINTER(c_f32), c_ptr, c_ptr, c_i64,
@@ -378,7 +383,8 @@ class _Recording(object):
                              "elimrec_cosine_topk_chunk", "elimrec_cosine_topk_tile",
                              "elimrec_audience_topk_chunk", "elimrec_audience_topk_tile",
                              "elimrec_list_max_k", "elimrec_list_pair_cosine_small_k", "elimrec_list_pair_cosine_chunk_cols",
-                             "elimrec_mmr_max_pool", "elimrec_mmr_rows_in_lds", "elimrec_calibrate_max_classes", "elimrec_segment_plan_form",
+                             "elimrec_mmr_max_pool", "elimrec_mmr_rows_in_lds", "elimrec_calibrate_max_classes", "elimrec_kmeans_max_clusters", "elimrec_kmeans_segment",
+                             "elimrec_segment_plan_form",
                              "elimrec_comm_create", "elimrec_comm_destroy", "elimrec_comm_nranks") or name.startswith("elimrec_program_")
             setattr(self, name, self._wrap(fn, name) if res is c_i32 and not plain else fn)
 

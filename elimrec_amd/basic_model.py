@@ -8,7 +8,7 @@ from torch import nn
 
 from . import ops
 from .evaluator import ProxyEvaluator, UniEvaluator
-from .reports import AudienceReport, CalibrationReport, DiversifyReport, EffectReport, HistoryReport, ListReport, NeighbourReport, RankReport, SignificanceReport
+from .reports import AudienceReport, CalibrationReport, ClusterReport, DiversifyReport, EffectReport, HistoryReport, ListReport, NeighbourReport, RankReport, SignificanceReport
 
 
 class BasicModel(nn.Module):
@@ -100,6 +100,17 @@ class BasicModel(nn.Module):
             lambdas = config["calibrate_lambda"] if "calibrate_lambda" in config else [1.0, 0.9, 0.7, 0.5]
             self.calibrate_reporter = CalibrationReport(dataset, train, dataset.get_user_test_dict(), k_cal, item_view, pool=pool,
                                                         lambdas=lambdas, group_view=config["group_view"])
+        # --cluster_report=K (CLI-only, default 0 = off): the items grouped into --cluster_count=C (default 8, 2 <= C <= 16) content
+        # clusters by spherical k-means of their rows in --cluster_space=fused|<head> (default fused), once per table version; the
+        # test users' top-K lists read per cluster: size, pop, cohesion, train / test / slot share, and per user the clusters in a
+        # list and its miscalibration against the user's own cluster mix, overall and per user group (reports.ClusterReport)
+        k_clu = int(config["cluster_report"]) if "cluster_report" in config else 0
+        self.cluster_reporter = None
+        if k_clu:
+            n_clu = int(config["cluster_count"]) if "cluster_count" in config else 8
+            space = str(config["cluster_space"]) if "cluster_space" in config else "fused"
+            self.cluster_reporter = ClusterReport(dataset, train, dataset.get_user_test_dict(), k_clu, n_clusters=n_clu, space=space,
+                                                  group_view=config["group_view"])
         # --history_report=K (CLI-only, default 0 = off): which items of the test users' training histories back their top-K lists
         # (--history_top=T entries named per pair, default 3): the largest and the mean cosine of the history to each listed item
         # and the unexpectedness 1 - max, in the fused space and in each head's, overall and per user group (reports.HistoryReport)

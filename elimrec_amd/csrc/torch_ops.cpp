@@ -28,6 +28,10 @@
 //       (lam weighs the relevance; csrc/calibrate.hip)
 //   list_calibration(lists i32[B x K], class_of i32[I], C, target f32[B x C], smooth) -> (shares f32[B x C], kl f32[B]): the class shares of
 //       every list and its miscalibration C_KL against the row's target
+//   kmeans_assign(table f32[n x d], sqnorm f32[n], centroids f32[C x d], centroid_sqnorm f32[C], prev i32[n]?) -> (assign i32[n], cos f32[n],
+//       changed i32[1]): per row the centroid with the largest cosine, the lowest id among equals; -1 / -inf for a row without a norm
+//   kmeans_update(table, sqnorm, assign i32[n], centroids, centroid_sqnorm) -> (centroids f32[C x d], centroid_sqnorm f32[C], sums f64[C x d],
+//       counts i32[C]): the normalised float64 sums of the members' unit rows; an empty cluster keeps its centroid (csrc/kmeans.hip)
 //   pick_hard_negatives(user_table f32[U x blocks*d], user_sqnorm f32[U x blocks], item_table f32[I x blocks*d], item_sqnorm, weights
 //     float[blocks], users i64[n], cands i32[n x M]) -> (neg i64, pos i32, score f32) [n]: per triplet the listed candidate with the largest
 //     sum_b w_b cos_b(u, i), the lowest column among equals; -1 / -1 / -inf without one (csrc/hardneg.hip)
@@ -576,6 +580,59 @@ std::tuple<at::Tensor, at::Tensor> list_calibration(const at::Tensor &lists, con
     return {shares, kl};
 }
 
+// ---- spherical k-means over one block of a table: the assignment, and the new centroids (csrc/kmeans.hip)
+static void kmeans_table(const char *who, const at::Tensor &t, const at::Tensor &sqnorm, const at::Tensor &cen, const at::Tensor &csq) {
+    need(sqnorm, "sqnorm", at::kFloat, 1); need(cen, "centroids", at::kFloat, 2); need(csq, "centroid_sqnorm", at::kFloat, 1);
+    const int64_t n = t.size(0), d = t.size(1), C = cen.size(0);
+    TORCH_CHECK(d % 4 == 0 && d >= 4 && d <= 256, "elimrec::", who, ": the table needs d % 4 == 0 and 4 <= d <= 256 columns, got ", d);
+    TORCH_CHECK(sqnorm.numel() == n, "elimrec::", who, ": sqnorm needs one entry per table row (", n, "), got ", sqnorm.numel());
+    TORCH_CHECK(C >= 1 && C <= elimrec_kmeans_max_clusters() && cen.size(1) == d && csq.numel() == C, "elimrec::", who,
+                ": centroids must be [C x ", d, "] with C squared norms, 1 <= C <= ", elimrec_kmeans_max_clusters(), ", got [", C, " x ",
+                cen.size(1), "] and ", csq.numel());
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor> kmeans_assign(const at::Tensor &table, const at::Tensor &sqnorm, const at::Tensor &centroids,
+                                                             const at::Tensor &centroid_sqnorm, const c10::optional<at::Tensor> &prev) {
+    const at::Tensor t = rowmajor(table, "table");
+    kmeans_table("kmeans_assign", t, sqnorm, centroids, centroid_sqnorm);
+    const at::Tensor cen = centroids.contiguous(), csq = centroid_sqnorm.contiguous();
+    const int64_t n = t.size(0), d = t.size(1), C = cen.size(0);
+    at::Tensor pv;
+    if (prev.has_value()) {
+        need(*prev, "prev", at::kInt, 1);
+        TORCH_CHECK(prev->numel() == n, "elimrec::kmeans_assign: prev needs one entry per table row (", n, "), got ", prev->numel());
+        pv = prev->contiguous();
+    }
+    at::Tensor assign = at::empty({n}, t.options().dtype(at::kInt)), cos = at::empty({n}, t.options());
+    at::Tensor changed = at::zeros({1}, assign.options());
+    if (n == 0) return {assign, cos, changed};
+    check(elimrec_kmeans_assign(t.data_ptr<float>(), t.stride(0), n, (int)d, sqnorm.data_ptr<float>(), n > 1 ? sqnorm.stride(0) : 1,
+                                cen.data_ptr<float>(), csq.data_ptr<float>(), (int)C, pv.defined() ? pv.data_ptr<int32_t>() : nullptr,
+                                assign.data_ptr<int32_t>(), cos.data_ptr<float>(), changed.data_ptr<int32_t>(), cur_stream()),
+          "kmeans_assign");
+    return {assign, cos, changed};
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> kmeans_update(const at::Tensor &table, const at::Tensor &sqnorm, const at::Tensor &assign,
+                                                                         const at::Tensor &centroids, const at::Tensor &centroid_sqnorm) {
+    const at::Tensor t = rowmajor(table, "table");
+    kmeans_table("kmeans_update", t, sqnorm, centroids, centroid_sqnorm);
+    need(assign, "assign", at::kInt, 1);
+    const int64_t n = t.size(0), d = t.size(1), C = centroids.size(0);
+    TORCH_CHECK(assign.numel() == n, "elimrec::kmeans_update: assign needs one entry per table row (", n, "), got ", assign.numel());
+    const at::Tensor as = assign.contiguous();
+    at::Tensor cen = centroids.contiguous().clone(), csq = centroid_sqnorm.contiguous().clone();     // the C entry point works in place
+    at::Tensor sums = at::zeros({C, d}, t.options().dtype(at::kDouble)), counts = at::zeros({C}, as.options());
+    if (n == 0) return {cen, csq, sums, counts};
+    const size_t need_ws = elimrec_kmeans_workspace(n, (int)d, (int)C);
+    at::Tensor ws = at::empty({(int64_t)need_ws}, t.options().dtype(at::kByte));
+    check(elimrec_kmeans_update(t.data_ptr<float>(), t.stride(0), n, (int)d, sqnorm.data_ptr<float>(), n > 1 ? sqnorm.stride(0) : 1,
+                                as.data_ptr<int32_t>(), (int)C, cen.data_ptr<float>(), csq.data_ptr<float>(), sums.data_ptr<double>(),
+                                counts.data_ptr<int32_t>(), ws.data_ptr(), (size_t)ws.numel(), cur_stream()),
+          "kmeans_update");
+    return {cen, csq, sums, counts};
+}
+
 // ---- hard-negative pick: per triplet the best of M candidates over the tables' column blocks
 std::tuple<at::Tensor, at::Tensor, at::Tensor> pick_hard_negatives(const at::Tensor &user_table, const at::Tensor &user_sqnorm,
                                                                    const at::Tensor &item_table, const at::Tensor &item_sqnorm,
@@ -803,6 +860,8 @@ TORCH_LIBRARY(elimrec, m) {
     m.def("mmr_rerank(Tensor table, Tensor sqnorm, Tensor pool_idx, Tensor pool_val, int K, float lam) -> (Tensor, Tensor, Tensor)");
     m.def("calibrate_rerank(Tensor pool_idx, Tensor pool_val, Tensor class_of, Tensor target, int K, float lam, float smooth) -> (Tensor, Tensor, Tensor)");
     m.def("list_calibration(Tensor lists, Tensor class_of, int C, Tensor target, float smooth) -> (Tensor, Tensor)");
+    m.def("kmeans_assign(Tensor table, Tensor sqnorm, Tensor centroids, Tensor centroid_sqnorm, Tensor? prev) -> (Tensor, Tensor, Tensor)");
+    m.def("kmeans_update(Tensor table, Tensor sqnorm, Tensor assign, Tensor centroids, Tensor centroid_sqnorm) -> (Tensor, Tensor, Tensor, Tensor)");
     m.def("pick_hard_negatives(Tensor user_table, Tensor user_sqnorm, Tensor item_table, Tensor item_sqnorm, float[] weights, Tensor users, "
           "Tensor cands) -> (Tensor, Tensor, Tensor)");
     m.def("history_support(Tensor table, Tensor sqnorm, float[] weights, Tensor users, Tensor lists, Tensor hist_ptr, Tensor hist_items, int top, "
@@ -841,6 +900,8 @@ TORCH_LIBRARY_IMPL(elimrec, CUDA, m) {
     m.impl("mmr_rerank", &mmr_rerank);
     m.impl("calibrate_rerank", &calibrate_rerank);
     m.impl("list_calibration", &list_calibration);
+    m.impl("kmeans_assign", &kmeans_assign);
+    m.impl("kmeans_update", &kmeans_update);
     m.impl("pick_hard_negatives", &pick_hard_negatives);
     m.impl("history_support", &history_support);
     m.impl("bootstrap_means", &bootstrap_means);

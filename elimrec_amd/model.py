@@ -41,6 +41,17 @@ from .plugin import EmbeddingParameter, LazyGradParameter, StepController
 Effects = collections.namedtuple("Effects", ("columns", "items", "values"))
 Neighbours = collections.namedtuple("Neighbours", ("ids", "scores"))
 Audience = collections.namedtuple("Audience", ("users", "scores"))
+Clusters = collections.namedtuple("Clusters", ("assign", "cos", "centroids", "counts", "n_iter", "converged"))
+
+
+def classes_from_clusters(assign, n_clusters):
+    """The `classes` argument of recommend_calibrated from a cluster assignment (Clusters.assign, n_clusters <= 15 when a row has no
+    cluster, <= 16 otherwise): int32 [I] with the rows of no cluster (-1: a zero or non-finite norm) in a class of their own, the
+    LAST one (n_clusters); without such a row the assignment itself."""
+    a = np.asarray(assign.cpu() if isinstance(assign, torch.Tensor) else assign).astype(np.int32)
+    return np.where(a < 0, np.int32(n_clusters), a).astype(np.int32)
+
+
 HistorySupport = collections.namedtuple("HistorySupport", ("items", "history", "scores", "count", "mean"))
 
 
@@ -1405,6 +1416,42 @@ class EliMRec(BasicModel):
     def similar_users(self, user_ids, k, space="fused", exclude=None):
         """similar_items over the user rows: the k users closest to each given user."""
         return self._similar("user", user_ids, k, space, exclude)
+
+    @torch.no_grad()
+    def clusters_device(self, side, n_clusters, space="fused", iters=25, seed=2022, init=None):
+        """Spherical k-means of the item rows (side "item") or the user rows ("user") of one block of the cached tables -- space
+        "fused" or a head letter of self._mods, as neighbours_device takes it -- into n_clusters content clusters by cosine:
+        ops.KMeans(assign, cos, centroids, counts -- device tensors --, n_iter, converged, cohesion), Lloyd's loop on the device
+        (ops.spherical_kmeans, csrc/kmeans.hip: one assign and one update launch per iteration). 1 <= n_clusters <= 256,
+        iters >= 1; init: n_clusters row indices (default: drawn on the host from `seed`). Tables as predict_device: those of the
+        last training forward."""
+        n_clusters, iters = ops._kmeans_params("clusters_device", n_clusters, iters)
+        lo, n = self._side_rows(side)
+        h = self._neighbour_space(space)
+        dev = self._cached_tables("cluster_items() / cluster_users() need", "content clusters need the whole cached tables on this rank; "
+                                  "the tables are item-sharded (lean / multi-rank evaluation)")
+        d = self.latent_dim
+        sqn = self._block_sqnorms(dev)
+        return ops.spherical_kmeans(self._ws["Y"][lo:lo + n, h * d:(h + 1) * d], sqn[lo:lo + n, h], n_clusters, iters=iters, seed=seed,
+                                    init=init)
+
+    def _clusters(self, side, n_clusters, space, iters, seed):
+        km = self.clusters_device(side, n_clusters, space, iters, seed)
+        return Clusters(km.assign.cpu(), km.cos.cpu(), km.centroids.cpu(), km.counts.cpu(), km.n_iter, km.converged)
+
+    def cluster_items(self, n_clusters, space="fused", iters=25, seed=2022):
+        """Content clusters of the items: Clusters(assign CPU int32 [I] (-1: an item whose row has no norm), cos CPU fp32 [I] the
+        cosine to its centroid (-inf there), centroids CPU fp32 [n_clusters x d] unit rows, counts CPU int32 [n_clusters], n_iter,
+        converged) -- spherical k-means in the "fused" space predict() scores with, or in one single-modal head's (a letter of
+        self._mods: the visual clusters). Not converged after `iters` iterations: assign / cos were formed against the centroids'
+        predecessors (ops.spherical_kmeans). With n_clusters <= 16, classes_from_clusters(assign, n_clusters) -- the -1 entries, if
+        any, moved to a class of their own, n_clusters, which then has to stay <= 15 -- is a valid `classes` argument of
+        recommend_calibrated: lists calibrated to the user's own mix of content."""
+        return self._clusters("item", n_clusters, space, iters, seed)
+
+    def cluster_users(self, n_clusters, space="fused", iters=25, seed=2022):
+        """cluster_items over the user rows."""
+        return self._clusters("user", n_clusters, space, iters, seed)
 
     def _audience_row_sum(self, dev, sqn):
         """TIE's sum_i sigmoid(u . i) of EVERY user: the scorer's pass 1 in user blocks of at most 8192, computed once per table

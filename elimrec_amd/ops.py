@@ -4,6 +4,7 @@ torch is plumbing here: it owns device memory and the current HIP stream; every 
 hands raw device pointers to libelimrec_hip.so. Inputs must live on a HIP device -- anything
 else raises (no CPU path).
 """
+import collections
 import ctypes
 
 import numpy as np
@@ -1019,6 +1020,10 @@ def __getattr__(name):
         return int(_lib.load().elimrec_mmr_max_pool())
     if name == "CALIBRATE_MAX_CLASSES":  # item classes calibrate_rerank / class_shares / list_calibration take (one lane each)
         return int(_lib.load().elimrec_calibrate_max_classes())
+    if name == "KMEANS_MAX_CLUSTERS":    # centroids kmeans_assign / kmeans_update take
+        return int(_lib.load().elimrec_kmeans_max_clusters())
+    if name == "KMEANS_SEGMENT":         # consecutive table rows per partial sum of kmeans_update
+        return int(_lib.load().elimrec_kmeans_segment())
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 
@@ -1723,6 +1728,182 @@ def list_calibration(lists, class_of, C, out_shares, target=None, smooth=0.01, o
         return out_shares
     _lib.check(_lib.load().elimrec_list_calibration(lp, B, K, cp, n_items, C, op, tp, ld_t, float(smooth), kp, _stream()), who)
     return out_shares
+
+
+def kmeans_workspace(n, d, C):
+    """Bytes of workspace kmeans_update needs (host arithmetic only; 0 for arguments out of range)."""
+    return int(_lib.load().elimrec_kmeans_workspace(int(n), int(d), int(C)))
+
+
+def _kmeans_table(who, table, sqnorm, centroids, centroid_sqnorm):
+    """The checks kmeans_assign / kmeans_update share -> (table pointer, ld, n, d, norm pointer, norm ld, centroid pointer, centroid
+    norm pointer, C)."""
+    for t, name in ((table, "table"), (sqnorm, "sqnorm"), (centroids, "centroids"), (centroid_sqnorm, "centroid_sqnorm")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            _dev(t if isinstance(t, torch.Tensor) else 0, name)
+    tp, ld = _rowmajor(table, "table")
+    n, d = table.shape
+    if d % 4 != 0 or not 4 <= d <= KNN_MAX_D:
+        raise ValueError("elimrec_amd.ops.%s: the table needs d %% 4 == 0 and 4 <= d <= %d columns, got %d" % (who, KNN_MAX_D, d))
+    sp = _dev(sqnorm, "sqnorm")
+    if sqnorm.dim() != 1 or sqnorm.numel() != n or sqnorm.device != table.device:
+        raise ValueError("elimrec_amd.ops.%s: sqnorm must be 1-D with one entry per table row (%d) on the table's device" % (who, n))
+    max_c = int(_lib.load().elimrec_kmeans_max_clusters())
+    cp, qp = _dev(centroids, "centroids"), _dev(centroid_sqnorm, "centroid_sqnorm")
+    if (centroids.dim() != 2 or centroids.shape[1] != d or not 1 <= centroids.shape[0] <= max_c or not centroids.is_contiguous()
+            or centroids.device != table.device):
+        raise ValueError("elimrec_amd.ops.%s: centroids must be a contiguous float32 [C x %d] tensor on the table's device, 1 <= C <= %d, "
+                         "got %s" % (who, d, max_c, tuple(centroids.shape)))
+    C = centroids.shape[0]
+    if centroid_sqnorm.dim() != 1 or centroid_sqnorm.numel() != C or not centroid_sqnorm.is_contiguous() or centroid_sqnorm.device != table.device:
+        raise ValueError("elimrec_amd.ops.%s: centroid_sqnorm must be a contiguous 1-D float32 tensor with one entry per centroid (%d) on "
+                         "the table's device" % (who, C))
+    return tp, ld, n, d, sp, max(1, int(sqnorm.stride(0))), cp, qp, C
+
+
+def _kmeans_rows(who, t, name, dtype, n, device):
+    """Device pointer of a contiguous 1-D tensor with one entry per table row."""
+    p = _dev(t, name, dtype)
+    if t.dim() != 1 or t.numel() != n or not t.is_contiguous() or t.device != device:
+        raise ValueError("elimrec_amd.ops.%s: %s must be a contiguous 1-D tensor with one entry per table row (%d) on the table's device"
+                         % (who, name, n))
+    return p
+
+
+def kmeans_assign(table, sqnorm, centroids, centroid_sqnorm, out_assign, out_cos=None, prev=None):
+    """elimrec_kmeans_assign: out_assign int32 [n] <- per row of `table` the centroid with the largest cosine, the lowest id among
+    equal cosines; out_cos float32 [n] (optional) <- that cosine, (dot * 1 / max(|row|, 1e-12)) * 1 / max(|centroid|, 1e-12) as
+    cosine_topk forms it. table [n x d] float32 with unit column stride (a column block of a wider matrix is fine), d % 4 == 0,
+    4 <= d <= 256; sqnorm 1-D float32, n entries, any stride; centroids float32 [C x d] contiguous with their squared norms
+    centroid_sqnorm [C], 1 <= C <= KMEANS_MAX_CLUSTERS. A row whose squared norm is 0 or not finite gets -1 / -inf; a centroid whose
+    squared norm is 0 or not finite is never chosen. -> changed: the number of rows whose assignment differs from prev (int32 [n],
+    optional; without it every row counts, so changed == n) -- ONE integer read back from the device (a synchronisation). A row's
+    bits depend on that row, the centroids, d and C alone (csrc/kmeans.hip)."""
+    who = "kmeans_assign"
+    tp, ld, n, d, sp, ld_sq, cp, qp, C = _kmeans_table(who, table, sqnorm, centroids, centroid_sqnorm)
+    dev = table.device
+    if out_assign is None:
+        raise RuntimeError("elimrec_amd.ops: 'out_assign' must be a HIP device tensor (the hot path has no CPU implementation)")
+    ap = _kmeans_rows(who, out_assign, "out_assign", torch.int32, n, dev)
+    op = _kmeans_rows(who, out_cos, "out_cos", torch.float32, n, dev) if out_cos is not None else None
+    pp = _kmeans_rows(who, prev, "prev", torch.int32, n, dev) if prev is not None else None
+    if n == 0:
+        return 0
+    changed = torch.empty(1, dtype=torch.int32, device=dev)
+    _lib.check(_lib.load().elimrec_kmeans_assign(tp, ld, n, d, sp, ld_sq, cp, qp, C, pp, ap, op, changed.data_ptr(), _stream()), who)
+    return int(changed.item())
+
+
+def kmeans_update(table, sqnorm, assign, centroids, centroid_sqnorm, out_sums=None, out_counts=None, workspace=None):
+    """elimrec_kmeans_update: centroids float32 [C x d] and centroid_sqnorm float32 [C] are updated IN PLACE: centroid c <- the float64
+    sum of the unit rows x / max(|x|, 1e-12) (formed in fp32, as kmeans_assign sees them) of the rows with assign[r] == c, divided by
+    its float64 norm and rounded once; centroid_sqnorm[c] <- its squared norm. A cluster without a member, or whose sum has norm 0,
+    keeps both. assign int32 [n]: entries outside [0, C) are skipped, and so is a row whose squared norm is 0 or not finite. The sums
+    are formed over KMEANS_SEGMENT consecutive rows in row order and added in segment order, no floating-point atomics: the bits
+    depend on the table, assign, d and C alone. out_sums float64 [C x d] / out_counts int32 [C] (optional, contiguous) <- the sums and
+    the members. workspace: uint8 device tensor of at least kmeans_workspace(n, d, C) bytes, 16-byte aligned (default: allocated
+    here). -> centroids (csrc/kmeans.hip)."""
+    who = "kmeans_update"
+    tp, ld, n, d, sp, ld_sq, cp, qp, C = _kmeans_table(who, table, sqnorm, centroids, centroid_sqnorm)
+    dev = table.device
+    ap = _kmeans_rows(who, assign, "assign", torch.int32, n, dev)
+    up = kp = None
+    if out_sums is not None:
+        up = _dev(out_sums, "out_sums", torch.float64)
+        if tuple(out_sums.shape) != (C, d) or not out_sums.is_contiguous() or out_sums.device != dev:
+            raise ValueError("elimrec_amd.ops.kmeans_update: out_sums must be a contiguous float64 [%d x %d] tensor on the table's device" % (C, d))
+    if out_counts is not None:
+        kp = _dev(out_counts, "out_counts", torch.int32)
+        if tuple(out_counts.shape) != (C,) or not out_counts.is_contiguous() or out_counts.device != dev:
+            raise ValueError("elimrec_amd.ops.kmeans_update: out_counts must be a contiguous int32 [%d] tensor on the table's device" % C)
+    need = kmeans_workspace(n, d, C)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    wp = _dev(workspace, "workspace", torch.uint8)
+    if workspace.numel() < need or not workspace.is_contiguous() or wp % 16:
+        raise ValueError("elimrec_amd.ops.kmeans_update: the workspace needs %d contiguous bytes, 16-byte aligned (got %d)"
+                         % (need, workspace.numel()))
+    if n == 0:                                                       # no member anywhere: every cluster keeps its centroid
+        if out_sums is not None:
+            out_sums.zero_()
+        if out_counts is not None:
+            out_counts.zero_()
+        return centroids
+    _lib.check(_lib.load().elimrec_kmeans_update(tp, ld, n, d, sp, ld_sq, ap, C, cp, qp, up, kp, wp, workspace.numel(), _stream()), who)
+    return centroids
+
+
+KMeans = collections.namedtuple("KMeans", ("assign", "cos", "centroids", "counts", "n_iter", "converged", "cohesion"))
+
+
+def _kmeans_params(who, C, iters):
+    """(C, iters) as integers in range; checked before anything touches the device."""
+    for what, v in (("the number of clusters", C), ("iters", iters)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError("elimrec_amd.ops.%s: %s must be an integer, got %r" % (who, what, v))
+    if not 1 <= int(C) <= 256:                                       # KMEANS_MAX_CLUSTERS (csrc/kmeans.hip), known without the library
+        raise ValueError("elimrec_amd.ops.%s: 1 <= C <= 256 clusters, got %d" % (who, C))
+    if int(iters) < 1:
+        raise ValueError("elimrec_amd.ops.%s: iters >= 1, got %d" % (who, iters))
+    return int(C), int(iters)
+
+
+def spherical_kmeans(table, sqnorm, C, iters=25, seed=2022, init=None):
+    """Spherical k-means (Lloyd's loop on the device) of the rows of `table` -- as kmeans_assign takes it, with its squared norms --
+    into C clusters by cosine: KMeans(assign int32 [n], cos float32 [n], centroids float32 [C x d], counts int32 [C] -- device
+    tensors --, n_iter, converged, cohesion). init: C distinct row indices whose rows are the first centroids; default the first C
+    entries of np.random.default_rng(seed).permutation(rows with a finite, non-zero squared norm), drawn on the host (fewer than C
+    such rows: ValueError). Iteration i = 1, 2, ... is ONE kmeans_assign against the centroids of iteration i - 1 (the init rows
+    for i = 1), the read of its one `changed` integer, and -- unless it is 0 -- ONE kmeans_update. The loop stops when no assignment
+    changed (converged = True: the update is skipped, the centroids ARE the normalised sums of the returned assignment) or after
+    `iters` iterations (converged = False: assign and cos belong to the PREDECESSORS of the returned centroids, which are the
+    normalised sums of the returned assignment). n_iter = the assign launches made; counts = the members of the returned
+    assignment. A row whose squared norm is 0 or not finite belongs to no cluster (-1 / -inf); a cluster that loses every member
+    keeps its centroid. cohesion = the float64 mean of cos over the assigned rows, summed on the host in numpy's fixed pairwise
+    order (NaN without an assigned row). Same table, C, iters and init: same bits."""
+    who = "spherical_kmeans"
+    C, iters = _kmeans_params(who, C, iters)
+    if not isinstance(table, torch.Tensor) or not table.is_cuda:
+        _dev(table if isinstance(table, torch.Tensor) else 0, "table")
+    if table.dim() != 2:
+        raise ValueError("elimrec_amd.ops.spherical_kmeans: 'table' must be 2-D with unit column stride")
+    n, d = table.shape
+    dev = table.device
+    if d % 4 != 0 or not 4 <= d <= KNN_MAX_D:
+        raise ValueError("elimrec_amd.ops.spherical_kmeans: the table needs d %% 4 == 0 and 4 <= d <= %d columns, got %d" % (KNN_MAX_D, d))
+    _dev(sqnorm, "sqnorm")
+    if sqnorm.dim() != 1 or sqnorm.numel() != n or sqnorm.device != dev:
+        raise ValueError("elimrec_amd.ops.spherical_kmeans: sqnorm must be 1-D with one entry per table row (%d) on the table's device" % n)
+    if init is None:
+        sq = sqnorm.detach().cpu().numpy()
+        good = np.flatnonzero(np.isfinite(sq) & (sq > 0))
+        if good.size < C:
+            raise ValueError("elimrec_amd.ops.spherical_kmeans: %d clusters need as many rows with a finite, non-zero norm, the table "
+                             "has %d" % (C, good.size))
+        init = good[np.random.default_rng(seed).permutation(good.size)[:C]]
+    init = np.asarray(init)
+    if init.ndim != 1 or init.size != C or init.dtype.kind not in "iu" or (C and not 0 <= int(init.min()) <= int(init.max()) < n):
+        raise ValueError("elimrec_amd.ops.spherical_kmeans: init must hold %d row indices in [0, %d)" % (C, n))
+    rows = torch.from_numpy(init.astype(np.int64)).to(dev)
+    centroids = table.index_select(0, rows).contiguous()
+    csq = sqnorm.index_select(0, rows).contiguous()
+    assign = [torch.empty(n, dtype=torch.int32, device=dev) for _ in range(2)]
+    cos = torch.empty(n, dtype=torch.float32, device=dev)
+    counts = torch.empty(C, dtype=torch.int32, device=dev)
+    workspace = torch.empty(kmeans_workspace(n, d, C), dtype=torch.uint8, device=dev)
+    n_iter, converged, cur = 0, False, 0
+    for it in range(iters):
+        cur = it & 1
+        changed = kmeans_assign(table, sqnorm, centroids, csq, assign[cur], cos, prev=assign[1 - cur] if it else None)
+        n_iter += 1
+        if it and changed == 0:
+            converged = True
+            break
+        kmeans_update(table, sqnorm, assign[cur], centroids, csq, out_counts=counts, workspace=workspace)
+    a_host, c_host = assign[cur].cpu().numpy(), cos.cpu().numpy()
+    listed = a_host >= 0
+    cohesion = float(c_host[listed].astype(np.float64).sum() / listed.sum()) if listed.any() else float("nan")
+    return KMeans(assign[cur], cos, centroids, counts, n_iter, converged, cohesion)
 
 
 def _block_table(table, sqnorm, blocks, name, who):

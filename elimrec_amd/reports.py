@@ -959,6 +959,166 @@ class CalibrationReport(_Report):
         return final, buf
 
 
+CLUSTER_COLUMNS = ("size", "pop", "cohesion", "train_share", "test_share", "slot_share")
+CLUSTER_USER_COLUMNS = ("distinct", "ckl")
+ClusterTables = collections.namedtuple("ClusterTables", ("cluster_columns", "cluster_labels", "clusters", "user_columns", "user_labels", "users"))
+ClusterShift = collections.namedtuple("ClusterShift", ("cluster_columns", "cluster_labels", "clusters", "user_columns", "user_labels", "users"))
+
+
+def cluster_rows(assign, cos, item_counts, test_counts, exposure, n_clusters):
+    """The cluster report's item table in numpy: float64 [n_clusters x 6], columns CLUSTER_COLUMNS. assign [I] (-1 = no cluster) and
+    cos [I] as cluster_items gives them; item_counts / test_counts [I] = the items' training / test interactions, exposure [I] = how
+    often each is listed. size = the members; pop = their mean training interactions and cohesion = their mean cosine to the
+    centroid (NaN for an empty cluster); train_share / test_share / slot_share = the cluster's share of ALL training interactions,
+    test interactions and list slots (the items of no cluster hold the rest; 0 where the total is 0)."""
+    assign = np.asarray(assign, dtype=np.int64)
+    member = assign >= 0
+    at = assign[member]
+    out = np.zeros((n_clusters, len(CLUSTER_COLUMNS)), dtype=np.float64)
+    size = np.bincount(at, minlength=n_clusters).astype(np.float64)
+    out[:, 0] = size
+    with np.errstate(invalid="ignore", divide="ignore"):
+        out[:, 1] = np.bincount(at, weights=np.asarray(item_counts, dtype=np.float64)[member], minlength=n_clusters) / size
+        out[:, 2] = np.bincount(at, weights=np.asarray(cos, dtype=np.float64)[member], minlength=n_clusters) / size
+    for col, w in ((3, item_counts), (4, test_counts), (5, exposure)):
+        w = np.asarray(w, dtype=np.float64)
+        total = w.sum()
+        if total:
+            out[:, col] = np.bincount(at, weights=w[member], minlength=n_clusters) / total
+    return out
+
+
+def cluster_user_rows(lists, classes, n_clusters, targets, smooth=0.01):
+    """The cluster report's user rows in numpy: float64 [B x 2], columns CLUSTER_USER_COLUMNS. lists int [B x K] (-1 fillers),
+    classes [I] = every item's cluster (-1 = none: such an entry is not listed), targets [B x n_clusters] = the users' own mix.
+    distinct = the clusters present in the list; ckl = sum over c with p_c > 0 of p_c log(p_c / ((1 - smooth) q_c + smooth p_c)),
+    q = the list's cluster shares (0 when nothing is listed): ops.list_calibration's C_KL in float64."""
+    lists, classes = np.asarray(lists, dtype=np.int64), np.asarray(classes, dtype=np.int64)
+    out = np.zeros((lists.shape[0], 2), dtype=np.float64)
+    for b, row in enumerate(lists):
+        ids = row[(row >= 0) & (row < classes.size)]
+        cls = classes[ids]
+        cls = cls[(cls >= 0) & (cls < n_clusters)]
+        cnt = np.bincount(cls, minlength=n_clusters).astype(np.float64)
+        out[b, 0] = float((cnt > 0).sum())
+        q = cnt / cnt.sum() if cnt.sum() else cnt
+        p = np.asarray(targets[b], dtype=np.float64)
+        p = np.where(np.isfinite(p) & (p > 0), p, 0.0)
+        kl = 0.0
+        for c in range(n_clusters):
+            if p[c] > 0:
+                kl += p[c] * np.log(p[c] / ((1.0 - smooth) * q[c] + smooth * p[c]))
+        out[b, 1] = kl
+    return out
+
+
+class ClusterReport(_Report):
+    """Which kinds of content the lists concentrate on (--cluster_report=K): the items are grouped into n_clusters content clusters
+    by spherical k-means of their rows in one space of the cached tables -- "fused" or a single-modal head (EliMRec.clusters_device,
+    csrc/kmeans.hip) --, computed ONCE per table version and shared by the effects; every test user's top-K list under the model's
+    current predict type with the train items masked is then read per cluster. One row per cluster, columns CLUSTER_COLUMNS
+    (cluster_rows): size, pop, cohesion, train_share, test_share and slot_share = the cluster's share of the K x users list slots
+    (ops.list_exposure). Per user, columns CLUSTER_USER_COLUMNS: distinct = the clusters present in the list, ckl = the list's
+    miscalibration C_KL against the user's own training mix over the clusters (ops.class_shares + ops.list_calibration; an item of
+    no cluster is not listed): the user means (ops.group_metric_means) over all test users, then per group_view group. shift(te,
+    tie): d_slot_share per cluster and d_distinct, d_ckl -- does TIE move exposure between kinds of content. 2 <= n_clusters <=
+    ops.CALIBRATE_MAX_CLASSES, so that the calibration kernels apply."""
+
+    name, needs = "cluster", "clusters_device"
+
+    def __init__(self, dataset, user_train_dict, user_test_dict, top_k, n_clusters=8, space="fused", iters=25, seed=2022, group_view=None,
+                 smooth=0.01):
+        if not isinstance(user_train_dict, dict) or not isinstance(user_test_dict, dict):
+            raise TypeError("user_train_dict and user_test_dict must be dicts")
+        if isinstance(top_k, bool) or not isinstance(top_k, (int, np.integer)) or top_k < 1 or top_k > ops.LIST_MAX_K:
+            raise ValueError("top_k must be an integer in [1, %d], got %r" % (ops.LIST_MAX_K, top_k))
+        for what, v in (("n_clusters", n_clusters), ("iters", iters), ("seed", seed)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError("%s must be an integer, got %r" % (what, v))
+        if not 2 <= n_clusters <= 16:                # ops.CALIBRATE_MAX_CLASSES (csrc/calibrate.hip), known without the library
+            raise ValueError("n_clusters must lie in [2, 16] (the calibration kernels' classes), got %d" % n_clusters)
+        if iters < 1:
+            raise ValueError("iters must be >= 1, got %d" % iters)
+        if not isinstance(space, str) or not space:
+            raise ValueError("space must be 'fused' or one of the model's heads, got %r" % (space,))
+        if isinstance(smooth, bool) or not isinstance(smooth, (int, float, np.integer, np.floating)) or not 0.0 < float(smooth) < 1.0:
+            raise ValueError("smooth must be a number in (0, 1), got %r" % (smooth,))
+        self.dataset = dataset
+        self.num_items = I = int(dataset.num_items)
+        self.user_pos_train = user_train_dict
+        self.user_pos_test = user_test_dict
+        self.top_k, self.num_classes, self.space = int(top_k), int(n_clusters), space
+        self.iters, self.seed, self.smooth = int(iters), int(seed), float(smooth)
+        self.users = list(user_test_dict.keys())
+        self.item_counts = item_train_counts(user_train_dict, I)
+        self.test_counts = item_train_counts({u: set(user_test_dict[u]) for u in self.users}, I)
+        self.group_labels, self._positions = self._user_groups(self.users, user_train_dict, group_view)
+        self.cluster_labels = [("cluster %d:" % c).ljust(12) for c in range(self.num_classes)]
+        self._clusters = None                        # (table version, ops.KMeans, targets)
+
+    def _make_resident(self, device):
+        return dict(groups=group_index(self._positions, len(self.users), device))
+
+    def clusters(self, model):
+        """The item clusters of the model's current tables (ops.KMeans on the device): computed once per table version."""
+        device = self._preflight(model)
+        version = getattr(model, "_table_version", None)
+        if self._clusters is None or version is None or self._clusters[0] != version:
+            km = model.clusters_device("item", self.num_classes, self.space, self.iters, self.seed)
+            ptr, items = lists_csr(self.users, self.user_pos_train, device)
+            targets = torch.zeros(len(self.users), self.num_classes, dtype=torch.float32, device=device)
+            ops.class_shares(ptr, items, km.assign, self.num_classes, targets)
+            self._clusters = (version, km, targets)
+        return self._clusters[1]
+
+    def classes(self, model):
+        """Every item's cluster on the device, int32 [I] (-1 = none): the class table the calibration kernels read."""
+        return self.clusters(model).assign
+
+    def cluster_lists(self, model):
+        """(rows float32 [users x 2] -- distinct, ckl --, lists int32 [users x K], counts int32 [num_items]) on the device."""
+        km = self.clusters(model)
+        device, targets = km.assign.device, self._clusters[2]
+        K, n_users, C = self.top_k, len(self.users), self.num_classes
+        rows = torch.empty(n_users, 2, dtype=torch.float32, device=device)
+        lists = torch.empty(n_users, K, dtype=torch.int32, device=device)
+        counts = torch.zeros(self.num_items, dtype=torch.int32, device=device)
+        shares = torch.empty(n_users, C, dtype=torch.float32, device=device)
+        for a, b, _, idx in self.top_lists(model, self.users, K, self.block_users, self.tie_order):
+            lists[a:b] = idx
+            ops.list_exposure(lists[a:b], counts)
+        kl = torch.empty(n_users, dtype=torch.float32, device=device)
+        ops.list_calibration(lists, km.assign, C, shares, target=targets, smooth=self.smooth, out_kl=kl)     # one launch for all users
+        rows[:, 0] = (shares > 0).sum(dim=1).float()
+        rows[:, 1] = kl
+        return rows, lists, counts
+
+    def evaluate(self, model, rows=None):
+        """(final, buf). final = ClusterTables: clusters float64 [n_clusters x 6] (cluster_rows), users float32 [1 + user groups x 2]
+        -- row 0 = all test users -- the means of distinct and ckl. buf: per table a header of column names and one "%.8f" line
+        per row. rows: cluster_lists(model) if the caller already holds it."""
+        rows, _, counts = self.cluster_lists(model) if rows is None else rows
+        km = self.clusters(model)
+        table = cluster_rows(km.assign.cpu().numpy(), km.cos.cpu().numpy(), self.item_counts, self.test_counts, counts.cpu().numpy(),
+                             self.num_classes)
+        users = group_table(rows, self._resident(rows.device)["groups"], len(self.group_labels))
+        final = ClusterTables(CLUSTER_COLUMNS, list(self.cluster_labels), table, CLUSTER_USER_COLUMNS, list(self.group_labels), users)
+        buf = format_table(final.cluster_columns, final.cluster_labels, final.clusters) + "\n" + format_table(
+            final.user_columns, final.user_labels, final.users)
+        return final, buf
+
+    def shift(self, a, b):
+        """How the clusters' exposure and the user means change from a to b (two evaluate() finals, e.g. TE -> TIE): (ClusterShift,
+        buf) -- clusters float64 [n_clusters x 1] = d_slot_share, users [1 + user groups x 2] = d_distinct, d_ckl."""
+        if not isinstance(a, ClusterTables) or not isinstance(b, ClusterTables) or a.clusters.shape != b.clusters.shape or a.users.shape != b.users.shape:
+            raise ValueError("shift() takes two evaluate() results of this report")
+        final = ClusterShift(("d_slot_share",), list(self.cluster_labels), b.clusters[:, 5:6] - a.clusters[:, 5:6],
+                             tuple("d_" + c for c in CLUSTER_USER_COLUMNS), list(self.group_labels), b.users - a.users)
+        buf = format_table(final.cluster_columns, final.cluster_labels, final.clusters) + "\n" + format_table(
+            final.user_columns, final.user_labels, final.users)
+        return final, buf
+
+
 class HistoryReport(_Report):
     """Which past items back the lists (--history_report=K): per (test user, rank <= K) pair of the top-K lists under the model's
     current predict type with the train items masked, the support the user's own training history gives the listed item

@@ -732,6 +732,35 @@ int elimrec_class_shares_csr(const int64_t *d_ptr, const int32_t *d_items, int64
 int elimrec_list_calibration(const int32_t *d_lists, int64_t B, int K, const int32_t *d_class_of, int64_t n_items, int C,
                              float *d_shares, const float *d_target, int64_t ld_target, double smooth, float *d_kl, void *stream);
 
+/* Spherical k-means over one block of a table (csrc/kmeans.hip): content clusters of the item or user rows. No counterpart in the
+ * reference. The table as elimrec_cosine_topk takes it: d_T points at row 0, column 0 of an [n_rows x d] slice of a row-major
+ * float32 matrix with row stride ld >= d, d % 4 == 0, 4 <= d <= 256; d_sqnorm[r * ld_sq] = the squared norm of row r. d_centroids
+ * float32 [C x d] contiguous with their squared norms d_centroid_sqnorm [C], 1 <= C <= elimrec_kmeans_max_clusters() = 256. Anything
+ * else: ELIMREC_E_BADARG, no launch; n_rows == 0 launches nothing and writes nothing.
+ * elimrec_kmeans_assign: d_assign[r] = the centroid with the largest
+ *     cos = (dot * (1 / max(sqrt(sq_row), 1e-12))) * (1 / max(sqrt(sq_centroid), 1e-12))
+ * (the dot product on the fp32 matrix cores, its summation order fixed by d alone), the lowest id among equal cosines, d_cos[r]
+ * (nullable) that cosine. A row whose squared norm is 0 or not finite gets -1 / -inf; a centroid whose squared norm is 0 or not
+ * finite is never chosen. *d_changed (one int32 on the device, zeroed on the stream by this call) <- the number of rows with
+ * d_assign[r] != d_prev[r]; d_prev nullable: every row counts. A row's outputs depend bit for bit on that row, the centroids, d and
+ * C only. One launch on `stream`.
+ * elimrec_kmeans_update: per cluster c the float64 sum of the unit rows x * (1 / max(sqrt(sq), 1e-12)) (formed in fp32, widened)
+ * of the rows with d_assign[r] == c: partial sums over elimrec_kmeans_segment() = 512 consecutive table rows, members in ascending
+ * row order, partials added in ascending segment order; no floating-point atomics. An assignment outside [0, C) and a row whose
+ * squared norm is 0 or not finite are skipped and never dereferenced. d_sums float64 [C x d] (nullable) <- the sums, d_counts int32
+ * [C] (nullable) <- the members; d_centroids[c] <- float(sum / |sum|) (float64 until the one rounding) and d_centroid_sqnorm[c]
+ * <- its squared norm, IN PLACE; a cluster without a member or whose sum has norm 0 keeps both. d_workspace: at least
+ * elimrec_kmeans_workspace(n_rows, d, C) bytes, 16-byte aligned (0 for arguments out of range). Two launches on `stream`. */
+int elimrec_kmeans_assign(const float *d_T, int64_t ld, int64_t n_rows, int d, const float *d_sqnorm, int64_t ld_sq,
+                          const float *d_centroids, const float *d_centroid_sqnorm, int C, const int32_t *d_prev, int32_t *d_assign,
+                          float *d_cos, int32_t *d_changed, void *stream);
+int elimrec_kmeans_update(const float *d_T, int64_t ld, int64_t n_rows, int d, const float *d_sqnorm, int64_t ld_sq,
+                          const int32_t *d_assign, int C, float *d_centroids, float *d_centroid_sqnorm, double *d_sums,
+                          int32_t *d_counts, void *d_workspace, size_t workspace_bytes, void *stream);
+int elimrec_kmeans_max_clusters(void);
+int elimrec_kmeans_segment(void);
+size_t elimrec_kmeans_workspace(int64_t n_rows, int d, int C);
+
 /* Hard-negative pick (csrc/hardneg.hip): per triplet the best of M candidate items under the current tables. No counterpart in
  * the reference. d_U / d_T point at row 0, column 0 of an [n_users x blocks * d] / [n_items x blocks * d] slice of a row-major
  * float32 matrix with row stride ld_u / ld_i >= blocks * d, block b = columns [b * d, (b + 1) * d); d_sq_u[r * ldsq_u + b] /

@@ -127,6 +127,12 @@ class Net(object):
         self.calibrate_report = int(cfg["calibrate_report"]) if "calibrate_report" in cfg else 0
         if self.calibrate_report and self.world > 1:
             raise ValueError("--calibrate_report needs the whole cached item table on one rank: it is single-GPU")
+        # --cluster_report=K (default 0: off): under each [TEST] line the top-K lists read per content cluster (--cluster_count
+        # spherical k-means clusters of the item rows in --cluster_space), and after both effects the TE -> TIE shift of the clusters'
+        # exposure: does TIE move exposure between kinds of content
+        self.cluster_report = int(cfg["cluster_report"]) if "cluster_report" in cfg else 0
+        if self.cluster_report and self.world > 1:
+            raise ValueError("--cluster_report needs the whole cached item table on one rank: it is single-GPU")
         # --neg_sampling=hard (default uniform): every epoch trains on the best of --neg_candidates=M (8) uniform candidates per
         # triplet under the tables of the last training forward, scored in --neg_space=fused|loss|<head> (fused); the first epoch
         # of a run -- no tables yet -- is the uniform one
@@ -268,7 +274,7 @@ class Net(object):
 
     def test_all_effects(self):
         """TE and TIE metrics on the test split, formatted as the reference prints them."""
-        rec, lines, ranks, shown, backed, sure, reached = self.recommender, {}, {}, {}, {}, {}, {}
+        rec, lines, ranks, shown, backed, sure, reached, grouped = self.recommender, {}, {}, {}, {}, {}, {}, {}
         if self.grouped:
             Logger.info(rec.test_evaluator.metrics_info())
         for effect in EFFECTS:
@@ -300,6 +306,11 @@ class Net(object):
                 reporter = rec.calibrate_reporter
                 Logger.info("  [{}] top-{} of the top-{} pools calibrated to the users' popularity mix, per lambda:\n{}".format(
                     effect, reporter.top_k, reporter.pool, reporter.evaluate(rec)[1]))
+            if self.cluster_report:        # the lists under this effect read per content cluster of the items
+                reporter = rec.cluster_reporter
+                grouped[effect] = reporter.evaluate(rec)
+                Logger.info("  [{}] top-{} lists over the {} content clusters ({} space):\n{}".format(
+                    effect, reporter.top_k, reporter.num_classes, reporter.space, grouped[effect][1]))
             if self.history_report:        # how close the users' training histories sit to the lists under this effect, per space
                 backed[effect] = rec.history_reporter.history_rows(rec)
                 Logger.info("  [{}] support of the top-{} lists in the users' histories:\n{}".format(
@@ -316,6 +327,9 @@ class Net(object):
             Logger.info("  [TE->TIE] list shift:\n{}".format(rec.list_reporter.shift(a[0], a[2], b[0], b[2])[1]))
         if self.audience_report:           # overlap: the share of an item's TE audience that TIE keeps; d_<column>: TIE - TE
             Logger.info("  [TE->TIE] audience shift:\n{}".format(rec.audience_reporter.shift(reached["TE"], reached["TIE"])[1]))
+        if self.cluster_report:            # d_slot_share: the share of the list slots a cluster gains under TIE; d_<column>: TIE - TE
+            Logger.info("  [TE->TIE] content clusters, exposure shift:\n{}".format(
+                rec.cluster_reporter.shift(grouped["TE"][0], grouped["TIE"][0])[1]))
         if self.history_report:            # d_<column>: TIE - TE; a positive d_unexpected_<space>: TIE strays further from the history
             Logger.info("  [TE->TIE] history support shift:\n{}".format(rec.history_reporter.shift(backed["TE"], backed["TIE"])[1]))
         if self.significance_report:       # TIE - TE per user, the users resampled as pairs; p: two-sided, "no difference"
