@@ -236,6 +236,14 @@ SIGNATURES = {
     "elimrec_kmeans_max_clusters": (c_i32, []),
     "elimrec_kmeans_segment": (c_i32, []),
     "elimrec_kmeans_workspace": (c_size, [c_i64, c_i32, c_i32]),
+    "elimrec_uniformity_sum": (c_i32, [c_ptr, c_i64, c_i64, c_i32, c_ptr, c_i64, c_ptr, c_i64, ctypes.c_double, c_ptr, c_ptr, c_ptr, c_size,
+                                       c_ptr]),
+    "elimrec_gram_f64": (c_i32, [c_ptr, c_i64, c_i64, c_i32, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
+    "elimrec_uniformity_workspace": (c_size, [c_i64, c_i32]),
+    "elimrec_gram_workspace": (c_size, [c_i64, c_i32]),
+    "elimrec_geometry_tile": (c_i32, []),
+    "elimrec_geometry_chunk": (c_i32, []),
+    "elimrec_geometry_segment": (c_i32, []),
     "elimrec_pick_hard_negatives": (c_i32, [c_ptr, c_i64, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_i64, c_ptr, c_i64, c_i32, c_i32,
                                             ctypes.POINTER(c_f32), c_ptr, c_ptr, c_i64, c_i32, c_ptr, c_ptr, c_ptr, c_ptr]),
     "elimrec_history_support": (c_i32, [c_ptr, c_i64, c_i64, c_i32, c_i32, c_ptr, c_i64, ctypes.POINTER(c_f32), c_ptr, c_ptr, c_i64,
@@ -384,6 +392,7 @@ class _Recording(object):
                              "elimrec_audience_topk_chunk", "elimrec_audience_topk_tile",
                              "elimrec_list_max_k", "elimrec_list_pair_cosine_small_k", "elimrec_list_pair_cosine_chunk_cols",
                              "elimrec_mmr_max_pool", "elimrec_mmr_rows_in_lds", "elimrec_calibrate_max_classes", "elimrec_kmeans_max_clusters", "elimrec_kmeans_segment",
+                             "elimrec_geometry_tile", "elimrec_geometry_chunk", "elimrec_geometry_segment",
                              "elimrec_segment_plan_form",
                              "elimrec_comm_create", "elimrec_comm_destroy", "elimrec_comm_nranks") or name.startswith("elimrec_program_")
             setattr(self, name, self._wrap(fn, name) if res is c_i32 and not plain else fn)

@@ -8,7 +8,7 @@ from torch import nn
 
 from . import ops
 from .evaluator import ProxyEvaluator, UniEvaluator
-from .reports import AudienceReport, CalibrationReport, ClusterReport, DiversifyReport, EffectReport, HistoryReport, ListReport, NeighbourReport, RankReport, SignificanceReport
+from .reports import AudienceReport, CalibrationReport, ClusterReport, DiversifyReport, EffectReport, GeometryReport, HistoryReport, ListReport, NeighbourReport, RankReport, SignificanceReport
 
 
 class BasicModel(nn.Module):
@@ -136,6 +136,16 @@ class BasicModel(nn.Module):
                 dataset, train, dataset.get_user_test_dict(), config["topks"], metric=config["metric"], group_view=config["group_view"],
                 replicates=n_rep, level=config["significance_level"] if "significance_level" in config else 0.95,
                 seed=config["significance_seed"] if "significance_seed" in config else 2022, evaluator=ev)
+        # --geometry_report=1 (CLI-only, default 0 = off): what the learned cosine spaces look like -- uniformity at --geometry_t
+        # (default 2.0), effective rank, top1, rank99 and centre of the user and the item rows of the fused space and of each head's,
+        # per user group (--group_view) and item popularity group (--item_group_view), and the alignment of the training and the test
+        # pairs -- once per table version (reports.GeometryReport)
+        if "geometry_report" in config and int(config["geometry_report"]) not in (0, 1):
+            raise ValueError("geometry_report must be 0 (off) or 1")
+        self.geometry_reporter = None
+        if "geometry_report" in config and int(config["geometry_report"]):
+            self.geometry_reporter = GeometryReport(dataset, train, dataset.get_user_test_dict(), group_view=config["group_view"],
+                                                    item_group_view=item_view, t=config["geometry_t"] if "geometry_t" in config else 2.0)
         self.infonce_criterion = nn.CrossEntropyLoss()          # BasicModel.py:32
 
     def getFileName(self):

@@ -32,6 +32,9 @@
 //       changed i32[1]): per row the centroid with the largest cosine, the lowest id among equals; -1 / -inf for a row without a norm
 //   kmeans_update(table, sqnorm, assign i32[n], centroids, centroid_sqnorm) -> (centroids f32[C x d], centroid_sqnorm f32[C], sums f64[C x d],
 //       counts i32[C]): the normalised float64 sums of the members' unit rows; an empty cluster keeps its centroid (csrc/kmeans.hip)
+//   uniformity_sum(table f32[n x d], sqnorm f32[n], rows i32[m], t) -> (sum f64[1], counts i64[2] = (pairs, n_valid)): the sum over the
+//       list's positions p < q, both valid, of expf(2 t (cos - 1)); row_gram(table, sqnorm, rows) -> (gram f64[d x d], sum f64[d], count
+//       i64[1]): the float64 Gram matrix and sum of the list's unit rows (csrc/geometry.hip)
 //   pick_hard_negatives(user_table f32[U x blocks*d], user_sqnorm f32[U x blocks], item_table f32[I x blocks*d], item_sqnorm, weights
 //     float[blocks], users i64[n], cands i32[n x M]) -> (neg i64, pos i32, score f32) [n]: per triplet the listed candidate with the largest
 //     sum_b w_b cos_b(u, i), the lowest column among equals; -1 / -1 / -inf without one (csrc/hardneg.hip)
@@ -633,6 +636,46 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> kmeans_update(const a
     return {cen, csq, sums, counts};
 }
 
+// ---- embedding geometry of one block of a table over a list of row ids: the uniformity sum, the float64 Gram (csrc/geometry.hip)
+static void geometry_table(const char *who, const at::Tensor &t, const at::Tensor &sqnorm, const at::Tensor &rows) {
+    need(sqnorm, "sqnorm", at::kFloat, 1); need(rows, "rows", at::kInt, 1);
+    const int64_t n = t.size(0), d = t.size(1);
+    TORCH_CHECK(d % 4 == 0 && d >= 4 && d <= 256, "elimrec::", who, ": the table needs d % 4 == 0 and 4 <= d <= 256 columns, got ", d);
+    TORCH_CHECK(sqnorm.numel() == n, "elimrec::", who, ": sqnorm needs one entry per table row (", n, "), got ", sqnorm.numel());
+}
+
+std::tuple<at::Tensor, at::Tensor> uniformity_sum(const at::Tensor &table, const at::Tensor &sqnorm, const at::Tensor &rows, double t) {
+    const at::Tensor T = rowmajor(table, "table");
+    geometry_table("uniformity_sum", T, sqnorm, rows);
+    TORCH_CHECK(t > 0.0 && t <= 8.0, "elimrec::uniformity_sum: 0 < t <= 8, got ", t);
+    const at::Tensor r = rows.contiguous();
+    const int64_t n_rows = T.size(0), d = T.size(1), n = r.numel();
+    at::Tensor sum = at::zeros({1}, T.options().dtype(at::kDouble)), counts = at::zeros({2}, T.options().dtype(at::kLong));
+    const size_t need_ws = elimrec_uniformity_workspace(n, (int)d);
+    at::Tensor ws = at::empty({(int64_t)need_ws}, T.options().dtype(at::kByte));
+    check(elimrec_uniformity_sum(T.data_ptr<float>(), T.stride(0), n_rows, (int)d, sqnorm.data_ptr<float>(), n_rows > 1 ? sqnorm.stride(0) : 1,
+                                 r.data_ptr<int32_t>(), n, t, sum.data_ptr<double>(), counts.data_ptr<int64_t>(), ws.data_ptr(),
+                                 (size_t)ws.numel(), cur_stream()),
+          "uniformity_sum");
+    return {sum, counts};
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor> row_gram(const at::Tensor &table, const at::Tensor &sqnorm, const at::Tensor &rows) {
+    const at::Tensor T = rowmajor(table, "table");
+    geometry_table("row_gram", T, sqnorm, rows);
+    const at::Tensor r = rows.contiguous();
+    const int64_t n_rows = T.size(0), d = T.size(1), n = r.numel();
+    at::Tensor gram = at::zeros({d, d}, T.options().dtype(at::kDouble)), sum = at::zeros({d}, gram.options());
+    at::Tensor count = at::zeros({1}, T.options().dtype(at::kLong));
+    const size_t need_ws = elimrec_gram_workspace(n, (int)d);
+    at::Tensor ws = at::empty({(int64_t)need_ws}, T.options().dtype(at::kByte));
+    check(elimrec_gram_f64(T.data_ptr<float>(), T.stride(0), n_rows, (int)d, sqnorm.data_ptr<float>(), n_rows > 1 ? sqnorm.stride(0) : 1,
+                           r.data_ptr<int32_t>(), n, gram.data_ptr<double>(), sum.data_ptr<double>(), count.data_ptr<int64_t>(), ws.data_ptr(),
+                           (size_t)ws.numel(), cur_stream()),
+          "row_gram");
+    return {gram, sum, count};
+}
+
 // ---- hard-negative pick: per triplet the best of M candidates over the tables' column blocks
 std::tuple<at::Tensor, at::Tensor, at::Tensor> pick_hard_negatives(const at::Tensor &user_table, const at::Tensor &user_sqnorm,
                                                                    const at::Tensor &item_table, const at::Tensor &item_sqnorm,
@@ -862,6 +905,8 @@ TORCH_LIBRARY(elimrec, m) {
     m.def("list_calibration(Tensor lists, Tensor class_of, int C, Tensor target, float smooth) -> (Tensor, Tensor)");
     m.def("kmeans_assign(Tensor table, Tensor sqnorm, Tensor centroids, Tensor centroid_sqnorm, Tensor? prev) -> (Tensor, Tensor, Tensor)");
     m.def("kmeans_update(Tensor table, Tensor sqnorm, Tensor assign, Tensor centroids, Tensor centroid_sqnorm) -> (Tensor, Tensor, Tensor, Tensor)");
+    m.def("uniformity_sum(Tensor table, Tensor sqnorm, Tensor rows, float t) -> (Tensor, Tensor)");
+    m.def("row_gram(Tensor table, Tensor sqnorm, Tensor rows) -> (Tensor, Tensor, Tensor)");
     m.def("pick_hard_negatives(Tensor user_table, Tensor user_sqnorm, Tensor item_table, Tensor item_sqnorm, float[] weights, Tensor users, "
           "Tensor cands) -> (Tensor, Tensor, Tensor)");
     m.def("history_support(Tensor table, Tensor sqnorm, float[] weights, Tensor users, Tensor lists, Tensor hist_ptr, Tensor hist_items, int top, "
@@ -902,6 +947,8 @@ TORCH_LIBRARY_IMPL(elimrec, CUDA, m) {
     m.impl("list_calibration", &list_calibration);
     m.impl("kmeans_assign", &kmeans_assign);
     m.impl("kmeans_update", &kmeans_update);
+    m.impl("uniformity_sum", &uniformity_sum);
+    m.impl("row_gram", &row_gram);
     m.impl("pick_hard_negatives", &pick_hard_negatives);
     m.impl("history_support", &history_support);
     m.impl("bootstrap_means", &bootstrap_means);

@@ -42,6 +42,7 @@ Effects = collections.namedtuple("Effects", ("columns", "items", "values"))
 Neighbours = collections.namedtuple("Neighbours", ("ids", "scores"))
 Audience = collections.namedtuple("Audience", ("users", "scores"))
 Clusters = collections.namedtuple("Clusters", ("assign", "cos", "centroids", "counts", "n_iter", "converged"))
+Geometry = collections.namedtuple("Geometry", ("columns", "labels", "values"))
 
 
 def classes_from_clusters(assign, n_clusters):
@@ -1452,6 +1453,103 @@ class EliMRec(BasicModel):
     def cluster_users(self, n_clusters, space="fused", iters=25, seed=2022):
         """cluster_items over the user rows."""
         return self._clusters("user", n_clusters, space, iters, seed)
+
+    def _geometry_spaces(self, space):
+        """The spaces a geometry call covers: every one (space None: "fused", then the heads) or the one named."""
+        if space is None:
+            return ("fused",) + tuple(self._mods)
+        self._neighbour_space(space)
+        return (space,)
+
+    @torch.no_grad()
+    def geometry_device(self, side, space="fused", rows=None, t=2.0):
+        """The raw geometry of one cosine space over the item rows (side "item") or the user rows ("user") of the cached tables:
+        (S float64 [1], pairs int64 [1], n_valid int64 [1], G float64 [d x d], m float64 [d]) on the device, nothing read back --
+        the all-pairs uniformity sum at temperature t (ops.uniformity_sum: uniformity = log(S / pairs)) and the float64 Gram matrix
+        and sum of the unit rows (ops.row_gram; reports.spectrum_summary reads the spectrum), two launches each (csrc/geometry.hip).
+        space: "fused" (block 0, the rows predict() scores with) or a head letter of self._mods. rows: the ids within the side --
+        None: all of them; a host array or list, checked on the host (IndexError); or an int32 tensor on the device, which the
+        kernels check entry by entry (an id outside the side is skipped). A repeated id is an entry of its own; a row without a
+        norm takes part in nothing. 0 < t <= 8. Tables as predict_device: those of the last training forward."""
+        lo, n = self._side_rows(side)
+        h = self._neighbour_space(space)
+        t = ops._geometry_t("geometry_device", t)
+        if rows is not None and not (isinstance(rows, torch.Tensor) and rows.is_cuda):
+            rows = np.ascontiguousarray(self._id_lists([rows], side, n)[1], dtype=np.int32)
+        self._require_gpu()
+        dev = self._cached_tables("embedding_geometry() needs", "the embedding geometry needs the whole cached tables on this rank; "
+                                  "the tables are item-sharded (lean / multi-rank evaluation)")
+        d = self.latent_dim
+        sqn = self._block_sqnorms(dev)
+        if rows is None:
+            rows = self._ws.get("geo_all_" + side)
+            if rows is None:
+                rows = self._ws["geo_all_" + side] = torch.arange(n, dtype=torch.int32, device=dev)
+        elif not isinstance(rows, torch.Tensor):
+            rows = torch.from_numpy(rows).to(dev)
+        need = max(ops.uniformity_workspace(rows.numel(), d), ops.row_gram_workspace(rows.numel(), d))
+        if self._ws.get("geo_ws") is None or self._ws["geo_ws"].numel() < need:
+            self._ws["geo_ws"] = torch.empty(need, dtype=torch.uint8, device=dev)
+        table, sq = self._ws["Y"][lo:lo + n, h * d:(h + 1) * d], sqn[lo:lo + n, h]
+        S, counts = ops.uniformity_sum_device(table, sq, rows, t, workspace=self._ws["geo_ws"])
+        G, m, _ = ops.row_gram_device(table, sq, rows, workspace=self._ws["geo_ws"])
+        return S, counts[0:1], counts[1:2], G, m
+
+    def embedding_geometry(self, side="item", space=None, rows=None, t=2.0):
+        """What a learned space looks like: Geometry(columns, labels, values CPU float64 [spaces x 6]), one row per space --
+        space None: "fused" and every single-modal head of self._mods; or the one space named -- over the item rows (side "item")
+        or the user rows ("user"), all of them or the ids `rows`. Columns (reports.GEOMETRY_COLUMNS):
+          n           the rows that took part (a row without a norm does not);
+          uniformity  log of the mean of exp(-t |x^ - y^|^2) = exp(2 t (cos - 1)) over all pairs of them (Wang & Isola, ICML'20):
+                      0 for fully collapsed rows, more negative for rows spread over the sphere; NaN with fewer than two rows;
+          erank       exp of the entropy of the covariance spectrum of the unit rows (Roy & Vetterli), between 1 and d;
+          top1        the share of the variance along the first principal direction;
+          rank99      the number of leading directions that hold 99 % of the variance (dimensional collapse, Jing et al., ICLR'22);
+          centre      the norm of the mean unit row: 0 for rows spread evenly round the sphere, 1 for fully collapsed rows.
+        The all-pairs sum and the Gram matrix are formed on the device (geometry_device), the d x d spectrum on the host in
+        float64. Tables as predict(): those of the last training forward."""
+        from . import reports
+        spaces = self._geometry_spaces(space)
+        self._side_rows(side)
+        ops._geometry_t("embedding_geometry", t)
+        raw = [self.geometry_device(side, s, rows, t) for s in spaces]
+        values = np.stack([reports.geometry_row(*[x.cpu().numpy() for x in r]) for r in raw])
+        return Geometry(reports.GEOMETRY_COLUMNS, tuple(spaces), torch.from_numpy(values))
+
+    @torch.no_grad()
+    def alignment_device(self, users, items, out=None):
+        """2 - 2 cos(user row, item row) of every pair in every space: out float32 [n x (1 + S)] on the device, column 0 the fused
+        space, column 1 + h head h. users int64 [n] / items int32 [n] on the device. One hard_negatives_device launch per space with
+        the item as the pair's only candidate: the cosine is its score, bit for bit. A pair with a row that has no norm has cosine
+        0 there and so the value 2; a user or an item outside its range gives +inf."""
+        n = users.numel()
+        dev = self._require_gpu()
+        spaces = ("fused",) + tuple(self._mods)
+        if out is None:
+            out = torch.empty(n, len(spaces), dtype=torch.float32, device=dev)
+        neg = torch.empty(n, dtype=torch.int64, device=dev)
+        pos = torch.empty(n, dtype=torch.int32, device=dev)
+        score = torch.empty(n, dtype=torch.float32, device=dev)
+        cands = items.reshape(n, 1)
+        for h, s in enumerate(spaces):
+            self.hard_negatives_device(users, cands, s, neg, pos, score)
+            out[:, h] = 2.0 - 2.0 * score
+        return out
+
+    def alignment(self, user_ids, item_ids, space=None):
+        """The alignment term of Wang & Isola / DirectAU per (user, item) pair: |u^ - i^|^2 = 2 - 2 cos(u, i) between the user's
+        and the item's unit rows -- CPU fp32 [n x (1 + S)], column 0 the fused space and column 1 + h head h (space None), or [n]
+        for the one space named. user_ids / item_ids: one id each per pair, checked on the host (IndexError). A pair with a row
+        that has no norm has cosine 0 in that space, so its value is 2; such pairs are not special-cased."""
+        if space is not None:
+            self._neighbour_space(space)
+        users = self._id_lists([user_ids], "user", self.num_users)[1]
+        items = self._id_lists([item_ids], "item", self.num_items)[1]
+        if users.size != items.size:
+            raise ValueError("one item per user: %d users for %d items" % (users.size, items.size))
+        dev = self._require_gpu()
+        out = self.alignment_device(torch.from_numpy(users.astype(np.int64)).to(dev), torch.from_numpy(items.astype(np.int32)).to(dev)).cpu()
+        return out if space is None else out[:, self._neighbour_space(space)].contiguous()
 
     def _audience_row_sum(self, dev, sqn):
         """TIE's sum_i sigmoid(u . i) of EVERY user: the scorer's pass 1 in user blocks of at most 8192, computed once per table

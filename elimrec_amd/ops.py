@@ -1024,6 +1024,12 @@ def __getattr__(name):
         return int(_lib.load().elimrec_kmeans_max_clusters())
     if name == "KMEANS_SEGMENT":         # consecutive table rows per partial sum of kmeans_update
         return int(_lib.load().elimrec_kmeans_segment())
+    if name == "GEOMETRY_TILE":          # list positions one workgroup of uniformity_sum holds as queries
+        return int(_lib.load().elimrec_geometry_tile())
+    if name == "GEOMETRY_CHUNK":         # list positions one workgroup of uniformity_sum streams as candidates
+        return int(_lib.load().elimrec_geometry_chunk())
+    if name == "GEOMETRY_SEGMENT":       # consecutive list positions per partial sum of row_gram
+        return int(_lib.load().elimrec_geometry_segment())
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 
@@ -1904,6 +1910,124 @@ def spherical_kmeans(table, sqnorm, C, iters=25, seed=2022, init=None):
     listed = a_host >= 0
     cohesion = float(c_host[listed].astype(np.float64).sum() / listed.sum()) if listed.any() else float("nan")
     return KMeans(assign[cur], cos, centroids, counts, n_iter, converged, cohesion)
+
+
+GEOMETRY_MAX_T = 8.0                     # the largest temperature uniformity_sum takes (csrc/geometry.hip), known without the library
+
+
+def uniformity_workspace(n, d):
+    """Bytes of workspace uniformity_sum needs for a list of n entries (host arithmetic only; 0 for arguments out of range)."""
+    return int(_lib.load().elimrec_uniformity_workspace(int(n), int(d)))
+
+
+def row_gram_workspace(n, d):
+    """Bytes of workspace row_gram needs for a list of n entries (host arithmetic only; 0 for arguments out of range)."""
+    return int(_lib.load().elimrec_gram_workspace(int(n), int(d)))
+
+
+def _geometry_t(who, t):
+    """The temperature as a float in (0, GEOMETRY_MAX_T]; checked before anything touches the device."""
+    if isinstance(t, bool) or not isinstance(t, (int, float, np.integer, np.floating)) or not 0.0 < float(t) <= GEOMETRY_MAX_T:
+        raise ValueError("elimrec_amd.ops.%s: 0 < t <= %g, got %r" % (who, GEOMETRY_MAX_T, t))
+    return float(t)
+
+
+def _geometry_table(who, table, sqnorm, rows):
+    """The checks uniformity_sum / row_gram share, cosine_topk's -> (table pointer, ld, n_rows, d, norm pointer, norm ld, rows
+    pointer, n). rows: an int32 device tensor, 1-D and contiguous; its ids are checked by the kernel, entry by entry."""
+    for t, name in ((table, "table"), (sqnorm, "sqnorm"), (rows, "rows")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            _dev(t if isinstance(t, torch.Tensor) else 0, name)
+    tp, ld = _rowmajor(table, "table")
+    n_rows, d = table.shape
+    if d % 4 != 0 or not 4 <= d <= KNN_MAX_D:
+        raise ValueError("elimrec_amd.ops.%s: the table needs d %% 4 == 0 and 4 <= d <= %d columns, got %d" % (who, KNN_MAX_D, d))
+    sp = _dev(sqnorm, "sqnorm")
+    if sqnorm.dim() != 1 or sqnorm.numel() != n_rows or sqnorm.device != table.device:
+        raise ValueError("elimrec_amd.ops.%s: sqnorm must be 1-D with one entry per table row (%d) on the table's device" % (who, n_rows))
+    rp = _dev(rows, "rows", torch.int32)
+    if rows.dim() != 1 or not rows.is_contiguous() or rows.device != table.device:
+        raise ValueError("elimrec_amd.ops.%s: rows must be a contiguous 1-D int32 tensor on the table's device" % who)
+    return tp, ld, n_rows, d, sp, max(1, int(sqnorm.stride(0))), rp, rows.numel()
+
+
+def _geometry_workspace(who, workspace, need, dev):
+    if workspace is None:
+        workspace = torch.empty(max(16, need), dtype=torch.uint8, device=dev)
+    wp = _dev(workspace, "workspace", torch.uint8)
+    if workspace.numel() < need or not workspace.is_contiguous() or wp % 16:
+        raise ValueError("elimrec_amd.ops.%s: the workspace needs %d contiguous bytes, 16-byte aligned (got %d)" % (who, need, workspace.numel()))
+    return workspace, wp
+
+
+def uniformity_sum_device(table, sqnorm, rows, t=2.0, workspace=None):
+    """uniformity_sum without the read back: (S float64 [1], counts int64 [2] = (pairs, n_valid)) on the device."""
+    who = "uniformity_sum"
+    t = _geometry_t(who, t)
+    tp, ld, n_rows, d, sp, ld_sq, rp, n = _geometry_table(who, table, sqnorm, rows)
+    dev = table.device
+    workspace, wp = _geometry_workspace(who, workspace, uniformity_workspace(n, d), dev)
+    S = torch.empty(1, dtype=torch.float64, device=dev)
+    counts = torch.empty(2, dtype=torch.int64, device=dev)
+    _lib.check(_lib.load().elimrec_uniformity_sum(tp, ld, n_rows, d, sp, ld_sq, rp, n, t, S.data_ptr(), counts.data_ptr(), wp,
+                                                  workspace.numel(), _stream()), who)
+    return S, counts
+
+
+def uniformity_sum(table, sqnorm, rows, t=2.0, workspace=None):
+    """elimrec_uniformity_sum: the all-pairs sum of the uniformity term of Wang & Isola (ICML'20) over a LIST of rows of `table`:
+    -> (S, pairs, n_valid), S = the float64 sum over the list's positions p < q, both valid, of expf(2 t (cos(p, q) - 1)),
+    pairs = n_valid (n_valid - 1) / 2; the uniformity is log(S / pairs) (uniformity_value). table [n_rows x d] float32 with unit column
+    stride (a column block of a wider matrix is fine), d % 4 == 0, 4 <= d <= 256; sqnorm: 1-D float32, n_rows entries, any stride.
+    rows: int32 device tensor [n], contiguous: an entry is valid when its id lies in [0, n_rows) and its row's squared norm is
+    > 0 and finite -- any other entry (-1, an id past the table, a row without a norm) is skipped by the kernel and missing from
+    n_valid; a repeated id is an entry of its own. 0 < t <= 8. The cosine is cosine_topk's, (dot * inv_lo) * inv_hi on the fp32
+    matrix cores with the two reciprocal norms in ascending order, so a pair's term does not depend on which row comes first and
+    the reversed list differs by the order of the float64 additions alone; every term is widened to float64 before it is added, in an order fixed by n, GEOMETRY_TILE and GEOMETRY_CHUNK
+    alone, without floating-point atomics: two calls give the same bits. workspace: uint8 device tensor of at least
+    uniformity_workspace(n, d) bytes, 16-byte aligned (default: allocated here). The three numbers are read back (a
+    synchronisation); uniformity_sum_device leaves them on the device (csrc/geometry.hip)."""
+    S, counts = uniformity_sum_device(table, sqnorm, rows, t, workspace)
+    counts = counts.cpu()
+    return float(S.cpu().item()), int(counts[0]), int(counts[1])
+
+
+def uniformity_value(S, pairs):
+    """log(S / pairs) in float64; NaN with fewer than two valid rows."""
+    return float(np.log(np.float64(S) / np.float64(pairs))) if pairs > 0 and S > 0 else float("nan")
+
+
+def row_gram_device(table, sqnorm, rows, out_gram=None, out_sum=None, workspace=None):
+    """row_gram without the read back: (G, m, n_valid int64 [1]) on the device."""
+    who = "row_gram"
+    tp, ld, n_rows, d, sp, ld_sq, rp, n = _geometry_table(who, table, sqnorm, rows)
+    dev = table.device
+    for out, name, shape in ((out_gram, "out_gram", (d, d)), (out_sum, "out_sum", (d,))):
+        if out is not None:
+            _dev(out, name, torch.float64)
+            if tuple(out.shape) != shape or not out.is_contiguous() or out.device != dev:
+                raise ValueError("elimrec_amd.ops.row_gram: %s must be a contiguous float64 %s tensor on the table's device"
+                                 % (name, " x ".join(str(x) for x in shape).join("[]")))
+    workspace, wp = _geometry_workspace(who, workspace, row_gram_workspace(n, d), dev)
+    G = out_gram if out_gram is not None else torch.empty(d, d, dtype=torch.float64, device=dev)
+    m = out_sum if out_sum is not None else torch.empty(d, dtype=torch.float64, device=dev)
+    count = torch.empty(1, dtype=torch.int64, device=dev)
+    _lib.check(_lib.load().elimrec_gram_f64(tp, ld, n_rows, d, sp, ld_sq, rp, n, G.data_ptr(), m.data_ptr(), count.data_ptr(), wp,
+                                            workspace.numel(), _stream()), who)
+    return G, m, count
+
+
+def row_gram(table, sqnorm, rows, out_gram=None, out_sum=None, workspace=None):
+    """elimrec_gram_f64: -> (G float64 [d x d], m float64 [d] -- device tensors --, n_valid): G = the sum of x^ x^T and m = the sum
+    of x^ over the valid entries of the list `rows`, x^ = x / max(|x|, 1e-12) formed in fp32 (as uniformity_sum and cosine_topk see
+    the rows) and widened: every product is exact in float64. They are added over segments of GEOMETRY_SEGMENT consecutive list
+    positions in list order and the partials in segment order, no floating-point atomics; the upper triangle is computed and
+    mirrored, so G is exactly symmetric. table / sqnorm / rows as uniformity_sum takes them. out_gram / out_sum: contiguous
+    float64 outputs (default: allocated here); workspace: uint8 device tensor of at least row_gram_workspace(n, d) bytes, 16-byte
+    aligned (default: allocated here). n_valid is read back (a synchronisation); row_gram_device leaves it on the device. The
+    covariance's spectrum is reports.spectrum_summary(G, m, n_valid) (csrc/geometry.hip)."""
+    G, m, count = row_gram_device(table, sqnorm, rows, out_gram, out_sum, workspace)
+    return G, m, int(count.cpu().item())
 
 
 def _block_table(table, sqnorm, blocks, name, who):

@@ -2,7 +2,7 @@
 whose neighbourhood the fused space copies (NeighbourReport), the lists themselves (ListReport), what diversifying them costs and
 buys (DiversifyReport), whether they match each user's own popularity mix (CalibrationReport), which items of a user's history back
 them (HistoryReport), how sure the evaluation metrics are
-(SignificanceReport) -- and what they share: the user /
+(SignificanceReport), what the learned cosine spaces themselves look like (GeometryReport) -- and what they share: the user /
 item groups, the groups as a checked index on the device, the group means, the table format, the model preflight and the block-wise
 top-K lists. The rows come from the model's *_device readers (model.py), the means from ops.group_metric_means."""
 import collections
@@ -1334,3 +1334,168 @@ class SignificanceReport(_Report):
         point = group_table(b - a, res["groups"], len(self.group_labels))
         s = bootstrap_summary(reps, point, self.level)
         return self._tables(s._replace(mean=point), True)
+
+
+GEOMETRY_COLUMNS = ("n", "uniformity", "erank", "top1", "rank99", "centre")
+GeometryTables = collections.namedtuple("GeometryTables", ("columns", "labels", "values", "align_columns", "align_labels", "align"))
+
+
+def spectrum_summary(G, m, n):
+    """The spectrum of a space read from its Gram matrix: (erank, top1, rank99, centre) in float64. G [d x d] = the sum of x^ x^T and
+    m [d] = the sum of x^ over n unit rows (ops.row_gram). The eigenvalues l are those of the covariance G / n - mu mu^T, mu = m / n,
+    clipped at 0 (numpy's eigvalsh of the symmetrised matrix):
+      erank  = exp(-sum p log p), p = l / sum l, the terms with p = 0 left out -- the effective rank of Roy & Vetterli, in [1, d];
+      top1   = max p, the share of the variance along the first principal direction;
+      rank99 = the number of leading directions that hold 99 % of sum l (Jing et al., ICLR'22: dimensional collapse);
+      centre = |mu|: 0 for rows spread evenly round the sphere, 1 for fully collapsed rows (NaN when n < 1).
+    n < 2 or sum l == 0 (all rows equal) gives NaN for erank, top1 and rank99."""
+    G = np.asarray(G, dtype=np.float64)
+    m = np.asarray(m, dtype=np.float64).reshape(-1)
+    n = int(n)
+    nan = float("nan")
+    if G.ndim != 2 or G.shape[0] != G.shape[1] or m.size != G.shape[0]:
+        raise ValueError("spectrum_summary: G must be [d x d] and m [d], got %s and %s" % (G.shape, m.shape))
+    if n < 1:
+        return nan, nan, nan, nan
+    mu = m / n
+    centre = float(np.sqrt(np.dot(mu, mu)))
+    if n < 2:
+        return nan, nan, nan, centre
+    cov = G / n - np.outer(mu, mu)
+    lam = np.clip(np.linalg.eigvalsh((cov + cov.T) * 0.5), 0.0, None)[::-1]
+    # what rounding leaves of a zero covariance is not a spectrum: eigenvalues below d eps times the unit rows' total power (1)
+    lam[lam <= lam.size * np.finfo(np.float64).eps] = 0.0
+    total = lam.sum()
+    if not total > 0.0:
+        return nan, nan, nan, centre
+    p = lam / total
+    nz = p[p > 0]
+    erank = float(np.exp(-(nz * np.log(nz)).sum()))
+    rank99 = float(1 + np.searchsorted(np.cumsum(p), 0.99 - 1e-12))
+    return erank, float(p[0]), min(rank99, float(p.size)), centre
+
+
+def geometry_row(S, pairs, n_valid, G, m):
+    """One row of GEOMETRY_COLUMNS (float64 [6]) from geometry_device's raw results copied to the host."""
+    S, pairs, n = float(np.asarray(S).reshape(-1)[0]), int(np.asarray(pairs).reshape(-1)[0]), int(np.asarray(n_valid).reshape(-1)[0])
+    return np.asarray((float(n), ops.uniformity_value(S, pairs)) + spectrum_summary(G, m, n), dtype=np.float64)
+
+
+def format_geometry(tables):
+    """A GeometryTables as text: the geometry rows under their header, then the alignment rows under theirs."""
+    return (format_table(tables.columns, tables.labels, tables.values) + "\n"
+            + format_table([c.strip() for c in tables.align_columns], tables.align_labels, tables.align))
+
+
+class GeometryReport(_Report):
+    """What the learned spaces look like (--geometry_report=1): per cosine space -- "fused", then every single-modal head -- the
+    columns GEOMETRY_COLUMNS (n, uniformity at temperature t, erank, top1, rank99, centre; EliMRec.embedding_geometry explains them)
+    of the rows `user` (all user rows) and `item` (all item rows), with group_view one row per user group (assign_user_groups over
+    ALL users by their number of training items) and with item_group_view one row per item popularity group (assign_item_groups),
+    uniformity and spectrum taken WITHIN the group's rows; a group with a single row has NaN there, an empty group is omitted.
+    Then per space the rows align_train / align_test: the mean of 2 - 2 cos(u, i) (EliMRec.alignment_device) over the training
+    pairs / the test users' test pairs -- column "all:" -- and over the pairs of each user group and each item group
+    (ops.group_metric_means; NaN for a group without a pair). A pair with a row that has no norm has cosine 0 and counts as 2; they
+    are not special-cased but counted: num_no_norm[(which, space)] after evaluate(). The all-pairs sums and Gram matrices come
+    from EliMRec.geometry_device (csrc/geometry.hip), the d x d spectra are the host's. The spaces do not depend on the predict
+    type; the tables are computed once per table version of a model and kept."""
+
+    name, needs = "geometry", "geometry_device"
+
+    def __init__(self, dataset, user_train_dict, user_test_dict, group_view=None, item_group_view=None, t=2.0):
+        if not isinstance(user_train_dict, dict) or not isinstance(user_test_dict, dict):
+            raise TypeError("user_train_dict and user_test_dict must be dicts")
+        self.t = ops._geometry_t("GeometryReport", t)
+        self.dataset = dataset
+        self.num_users, self.num_items = U, I = int(dataset.num_users), int(dataset.num_items)
+        item_counts = item_train_counts(user_train_dict, I) if item_group_view is not None else None
+        # the row sets: (label, side, ids within the side; None = every row)
+        self.row_sets = [("user", "user", None), ("item", "item", None)]
+        user_names, item_names = [], []
+        if group_view is not None:
+            labels, positions, self.num_discarded = assign_user_groups(list(range(U)), user_train_dict, group_view)
+            self.row_sets += [("user " + x.strip(), "user", p.astype(np.int32)) for x, p in zip(labels, positions)]
+            user_names = [("(%d,%d]:" % b).ljust(12) for b in zip([0] + list(group_view[:-1]), group_view)]
+        if item_group_view is not None:
+            labels, positions = assign_item_groups(np.arange(I, dtype=np.int64), item_counts, item_group_view)
+            self.row_sets += [("item " + x.strip(), "item", p.astype(np.int32)) for x, p in zip(labels, positions)]
+            bounds = [int(b) for b in item_group_view]
+            item_names = ["cold:"] + ["(%d,%d]:" % b for b in zip([0] + bounds[:-1], bounds)] + ["(%d,inf):" % bounds[-1]]
+            item_names = [x.ljust(12) for x in item_names]
+        self.align_columns = [ALL] + user_names + [("item " + x.strip()).ljust(12) for x in item_names]
+        # the pairs and their groups as columns of align_columns (a group without a pair keeps NaN)
+        self._pairs = {}
+        for which, table in (("align_train", user_train_dict), ("align_test", user_test_dict)):
+            users = [u for u, items in table.items() if len(items)]
+            ptr, items, lens = ops.ragged([table[u] for u in users], dtype=np.int32, check=(I, "item ids must lie in [0, %d)" % I), cast=int)
+            pair_user = np.repeat(np.asarray(users, dtype=np.int64), lens)
+            if pair_user.size and (pair_user.min() < 0 or pair_user.max() >= U):
+                raise IndexError("user ids must lie in [0, %d)" % U)
+            cols, positions = [0], [np.arange(items.size, dtype=np.int64)]
+            if group_view is not None and items.size:
+                try:
+                    labels, at, _ = assign_user_groups(users, user_train_dict, group_view)
+                except ValueError:                               # no user of this pair list falls into a group
+                    labels, at = [], []
+                rep = np.repeat(np.arange(len(users), dtype=np.int64), lens)
+                for x, p in zip(labels, at):
+                    cols.append(self.align_columns.index(x))
+                    positions.append(np.flatnonzero(np.isin(rep, p)))
+            if item_group_view is not None and items.size:
+                labels, at = assign_item_groups(items, item_counts, item_group_view)
+                for x, p in zip(labels, at):
+                    cols.append(self.align_columns.index(("item " + x.strip()).ljust(12)))
+                    positions.append(p)
+            self._pairs[which] = (pair_user, items, cols, positions)
+        self.num_no_norm = {}
+        self._done = {}
+
+    def _make_resident(self, device):
+        """The groups' row ids, the pairs and their group indices resident on the device."""
+        rows = [None if ids is None else torch.from_numpy(np.ascontiguousarray(ids)).to(device) for _, _, ids in self.row_sets]
+        pairs = {}
+        for which, (users, items, cols, positions) in self._pairs.items():
+            pairs[which] = (torch.from_numpy(users).to(device), torch.from_numpy(np.ascontiguousarray(items)).to(device),
+                            group_index(positions, items.size, device) if items.size else None)
+        return dict(rows=rows, pairs=pairs)
+
+    def evaluate(self, model):
+        """(final, buf). final = GeometryTables: values float64 [spaces x row sets, 6] with labels "<space> <row set>:" under
+        `columns` = GEOMETRY_COLUMNS; align float32 [spaces x 2, 1 + groups] with labels "<space> align_train:" / "<space>
+        align_test:" under align_columns ("all:", the user groups, the item groups). buf: the two tables in the effect report's
+        format. A second call on the same table version of the same model returns the kept result and launches nothing."""
+        device = self._preflight(model)
+        if model.num_users != self.num_users:
+            raise ValueError("the report was built for %d users, the model has %d" % (self.num_users, model.num_users))
+        key = (id(model), str(device))
+        if hasattr(model, "_cached_tables"):                     # a pending step made real first: it publishes a new table version
+            model._cached_tables("the geometry report needs")
+        version = getattr(model, "_table_version", None)
+        hit = self._done.get(key)
+        if hit is not None and version is not None and hit[0] == version:
+            return hit[1], hit[2]
+        res = self._resident(device)
+        spaces = ("fused",) + tuple(model._mods)
+        labels, raw = [], []
+        for s in spaces:
+            for (label, side, _), rows in zip(self.row_sets, res["rows"]):
+                labels.append(("%s %s:" % (s, label.rstrip(":"))).ljust(20))
+                raw.append(model.geometry_device(side, s, rows, self.t))
+        values = np.stack([geometry_row(*[x.cpu().numpy() for x in r]) for r in raw])
+        align = np.full((2 * len(spaces), len(self.align_columns)), np.nan, dtype=np.float32)
+        sqn = model._block_sqnorms(device)
+        for w, which in enumerate(("align_train", "align_test")):
+            users, items, index = res["pairs"][which]
+            cols = self._pairs[which][2]
+            if index is None:
+                continue
+            rows = model.alignment_device(users, items)
+            align[w::2][:, cols] = group_table(rows, index, len(cols)).T
+            bare = (sqn[users] == 0) | (sqn[self.num_users + items.long()] == 0)
+            for h, n in enumerate(bare.sum(dim=0).cpu().tolist()):
+                self.num_no_norm[(which, spaces[h])] = int(n)
+        align_labels = [("%s %s:" % (s, which)).ljust(20) for s in spaces for which in ("align_train", "align_test")]
+        final = GeometryTables(GEOMETRY_COLUMNS, labels, values, tuple(self.align_columns), align_labels, align)
+        buf = format_geometry(final)
+        self._done[key] = (version, final, buf)
+        return final, buf

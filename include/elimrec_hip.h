@@ -761,6 +761,42 @@ int elimrec_kmeans_max_clusters(void);
 int elimrec_kmeans_segment(void);
 size_t elimrec_kmeans_workspace(int64_t n_rows, int d, int C);
 
+/* Embedding geometry of one block of a table over a LIST of row ids (csrc/geometry.hip): the uniformity sum of Wang & Isola
+ * (ICML'20) and the float64 Gram matrix of the unit rows, whose spectrum gives the effective rank. No counterpart in the reference.
+ * The table as elimrec_cosine_topk takes it: d_T points at row 0, column 0 of an [n_rows x d] slice of a row-major float32 matrix
+ * with row stride ld >= d, d % 4 == 0, 4 <= d <= 256; d_sqnorm[r * ld_sq] = the squared norm of row r. d_rows int32 [n]: the list.
+ * The unit row is x * (1 / max(sqrt(sq), 1e-12)), IEEE, formed in fp32. An entry is VALID when its id lies in [0, n_rows) and its
+ * row's squared norm is > 0 and finite; any other entry (-1, an id past the table, a row without a norm) takes part in nothing,
+ * is missing from n_valid, and is never dereferenced. A repeated id is an entry of its own. Anything else out of range:
+ * ELIMREC_E_BADARG, no launch; n == 0 zeroes the outputs on the stream.
+ * elimrec_uniformity_sum: d_sum[0] <- S = the sum over the positions p < q of the list, both valid, of
+ *     e(p, q) = expf(float(2 t) * (cos(p, q) - 1)),   cos = (dot * inv_lo) * inv_hi
+ * as elimrec_cosine_topk forms the cosine, the two rows' reciprocal norms taken in ascending order so that e(p, q) == e(q, p) bit
+ * for bit (the dot product on the fp32 matrix cores over k = 0, 4, 8, ...: a pair's bits depend on the two rows, d and t only, not
+ * on which of them comes first), expf the accurate device function, every e widened to float64 before it is added; d_counts int64
+ * [2] <- (pairs = n_valid (n_valid - 1) / 2, n_valid). 0 < t <= 8. The caller forms uniformity = log(S / pairs). The positions
+ * are cut into tiles of elimrec_geometry_tile() = 64 and chunks of elimrec_geometry_chunk() = 2048; one workgroup per (tile, chunk)
+ * cell that holds a pair p < q leaves ONE float64 in the workspace (per-lane sums in candidate order, a fixed tree over the lanes),
+ * a second launch adds the cells (256 strided sums in ascending cell order, the same tree). No floating-point atomics: the
+ * order of every addition is fixed by n and these constants -- two calls give the same bits. Two launches on `stream`.
+ * elimrec_gram_f64: d_gram float64 [d x d] <- G = the sum of x^ x^T, d_sum float64 [d] <- m = the sum of x^, d_count int64 [1] <-
+ * n_valid, over the valid entries. The products are of the fp32 unit rows widened to float64 (exact); they are added over segments
+ * of elimrec_geometry_segment() = 512 consecutive list positions in list order and the partials in ascending segment order; the
+ * upper triangle is computed and mirrored, so G is exactly symmetric. Two launches on `stream`.
+ * d_workspace: at least elimrec_uniformity_workspace(n, d) / elimrec_gram_workspace(n, d) bytes, 16-byte aligned (host
+ * arithmetic; 0 for arguments out of range). */
+int elimrec_uniformity_sum(const float *d_T, int64_t ld, int64_t n_rows, int d, const float *d_sqnorm, int64_t ld_sq,
+                           const int32_t *d_rows, int64_t n, double t, double *d_sum, int64_t *d_counts, void *d_workspace,
+                           size_t workspace_bytes, void *stream);
+int elimrec_gram_f64(const float *d_T, int64_t ld, int64_t n_rows, int d, const float *d_sqnorm, int64_t ld_sq,
+                     const int32_t *d_rows, int64_t n, double *d_gram, double *d_sum, int64_t *d_count, void *d_workspace,
+                     size_t workspace_bytes, void *stream);
+size_t elimrec_uniformity_workspace(int64_t n, int d);
+size_t elimrec_gram_workspace(int64_t n, int d);
+int elimrec_geometry_tile(void);
+int elimrec_geometry_chunk(void);
+int elimrec_geometry_segment(void);
+
 /* Hard-negative pick (csrc/hardneg.hip): per triplet the best of M candidate items under the current tables. No counterpart in
  * the reference. d_U / d_T point at row 0, column 0 of an [n_users x blocks * d] / [n_items x blocks * d] slice of a row-major
  * float32 matrix with row stride ld_u / ld_i >= blocks * d, block b = columns [b * d, (b + 1) * d); d_sq_u[r * ldsq_u + b] /

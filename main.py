@@ -106,6 +106,12 @@ class Net(object):
         self.neighbour_report = int(cfg["neighbour_report"]) if "neighbour_report" in cfg else 0
         if self.neighbour_report and self.world > 1:
             raise ValueError("--neighbour_report needs the whole cached item table on one rank: it is single-GPU")
+        # --geometry_report=1 (default 0: off): once per [TEST], after both effects' lines, what the cosine spaces look like --
+        # uniformity (--geometry_t), effective rank and centre of the user and item rows, alignment of the training and test pairs,
+        # in the fused space and in each head's (the spaces do not depend on the predict type)
+        self.geometry_report = int(cfg["geometry_report"]) if "geometry_report" in cfg else 0
+        if self.geometry_report and self.world > 1:
+            raise ValueError("--geometry_report needs the whole cached tables on one rank: it is single-GPU")
         # --list_report=K (default 0: off): under each [TEST] line the top-K lists' intra-list similarity, popularity and catalogue
         # exposure, after both effects how the lists change from TE to TIE
         self.list_report = int(cfg["list_report"]) if "list_report" in cfg else 0
@@ -338,6 +344,9 @@ class Net(object):
         if self.neighbour_report:
             Logger.info("  [neighbours] top-{} cosine neighbours of every item, fused space against the heads:\n{}".format(
                 self.neighbour_report, rec.neighbour_reporter.evaluate(rec)[1]))
+        if self.geometry_report:
+            Logger.info("  [geometry] uniformity (t = {:g}), spectrum and alignment of the cosine spaces:\n{}".format(
+                rec.geometry_reporter.t, rec.geometry_reporter.evaluate(rec)[1]))
         return lines
 
     # ------------------------------------------------------------------ the run
