@@ -244,6 +244,14 @@ SIGNATURES = {
     "elimrec_geometry_tile": (c_i32, []),
     "elimrec_geometry_chunk": (c_i32, []),
     "elimrec_geometry_segment": (c_i32, []),
+    "elimrec_cooccur_topk": (c_i32, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_i32, c_i32, c_i32, c_i64, c_ptr, c_ptr, c_ptr,
+                                     c_ptr, c_ptr, c_size, c_ptr]),
+    "elimrec_cooccur_walk": (c_i32, [c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr]),
+    "elimrec_cooccur_workspace": (c_size, [c_i64, c_i64]),
+    "elimrec_cooccur_slots": (c_i32, []),
+    "elimrec_cooccur_max_k": (c_i32, []),
+    "elimrec_cooccur_groups": (c_i32, []),
+    "elimrec_cooccur_rows_in_lds": (c_i32, [c_i64]),
     "elimrec_pick_hard_negatives": (c_i32, [c_ptr, c_i64, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_i64, c_ptr, c_i64, c_i32, c_i32,
                                             ctypes.POINTER(c_f32), c_ptr, c_ptr, c_i64, c_i32, c_ptr, c_ptr, c_ptr, c_ptr]),
     "elimrec_history_support": (c_i32, [c_ptr, c_i64, c_i64, c_i32, c_i32, c_ptr, c_i64, ctypes.POINTER(c_f32), c_ptr, c_ptr, c_i64,
@@ -393,6 +401,7 @@ class _Recording(object):
                              "elimrec_list_max_k", "elimrec_list_pair_cosine_small_k", "elimrec_list_pair_cosine_chunk_cols",
                              "elimrec_mmr_max_pool", "elimrec_mmr_rows_in_lds", "elimrec_calibrate_max_classes", "elimrec_kmeans_max_clusters", "elimrec_kmeans_segment",
                              "elimrec_geometry_tile", "elimrec_geometry_chunk", "elimrec_geometry_segment",
+                             "elimrec_cooccur_slots", "elimrec_cooccur_max_k", "elimrec_cooccur_groups", "elimrec_cooccur_rows_in_lds",
                              "elimrec_segment_plan_form",
                              "elimrec_comm_create", "elimrec_comm_destroy", "elimrec_comm_nranks") or name.startswith("elimrec_program_")
             setattr(self, name, self._wrap(fn, name) if res is c_i32 and not plain else fn)

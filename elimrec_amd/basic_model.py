@@ -8,7 +8,7 @@ from torch import nn
 
 from . import ops
 from .evaluator import ProxyEvaluator, UniEvaluator
-from .reports import AudienceReport, CalibrationReport, ClusterReport, DiversifyReport, EffectReport, GeometryReport, HistoryReport, ListReport, NeighbourReport, RankReport, SignificanceReport
+from .reports import AudienceReport, CalibrationReport, ClusterReport, CoNeighbourReport, DiversifyReport, EffectReport, GeometryReport, HistoryReport, ListReport, NeighbourReport, RankReport, SignificanceReport
 
 
 class BasicModel(nn.Module):
@@ -146,6 +146,17 @@ class BasicModel(nn.Module):
         if "geometry_report" in config and int(config["geometry_report"]):
             self.geometry_reporter = GeometryReport(dataset, train, dataset.get_user_test_dict(), group_view=config["group_view"],
                                                     item_group_view=item_view, t=config["geometry_t"] if "geometry_t" in config else 2.0)
+        # --co_report=K (CLI-only, default 0 = off): every item's top-K co-interaction neighbours ("users who took this also took
+        # ...", --co_measure=count|cosine|jaccard, default cosine) beside its top-K cosine neighbours in the fused space and in each
+        # head's: how much of the behavioural list the learned lists hold, overall and per --item_group_view popularity group
+        # (reports.CoNeighbourReport)
+        k_co = int(config["co_report"]) if "co_report" in config else 0
+        if k_co < 0:
+            raise ValueError("co_report must be 0 (off) or the K of the co-interaction lists")
+        co_measure = str(config["co_measure"]) if "co_measure" in config else "cosine"
+        if co_measure not in ops.COOCCUR_MEASURES:
+            raise ValueError("co_measure is one of %s, got %r" % (", ".join(sorted(ops.COOCCUR_MEASURES)), co_measure))
+        self.co_reporter = CoNeighbourReport(dataset, train, k_co, measure=co_measure, item_group_view=item_view) if k_co else None
         self.infonce_criterion = nn.CrossEntropyLoss()          # BasicModel.py:32
 
     def getFileName(self):

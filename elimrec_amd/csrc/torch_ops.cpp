@@ -35,6 +35,10 @@
 //   uniformity_sum(table f32[n x d], sqnorm f32[n], rows i32[m], t) -> (sum f64[1], counts i64[2] = (pairs, n_valid)): the sum over the
 //       list's positions p < q, both valid, of expf(2 t (cos - 1)); row_gram(table, sqnorm, rows) -> (gram f64[d x d], sum f64[d], count
 //       i64[1]): the float64 Gram matrix and sum of the list's unit rows (csrc/geometry.hip)
+//   cooccur_topk(q_ptr i64[n + 1], q_nbr i32[E], o_ptr i64[m + 1], o_nbr i32[E], rows i32[Q], K, measure) -> (idx i32, val f32, cnt i32)
+//       [Q x K]: per query row the K rows of its side with the largest co-occurrence score ("count", "cosine", "jaccard") over the
+//       bipartite graph the two CSRs give, (score descending, id ascending), -1 / -inf / 0 fillers; both CSRs and the rows are checked
+//       on the host (csrc/cooccur.hip)
 //   pick_hard_negatives(user_table f32[U x blocks*d], user_sqnorm f32[U x blocks], item_table f32[I x blocks*d], item_sqnorm, weights
 //     float[blocks], users i64[n], cands i32[n x M]) -> (neg i64, pos i32, score f32) [n]: per triplet the listed candidate with the largest
 //     sum_b w_b cos_b(u, i), the lowest column among equals; -1 / -1 / -inf without one (csrc/hardneg.hip)
@@ -58,6 +62,8 @@
 #include <ATen/hip/HIPContext.h>
 #include <torch/library.h>
 
+#include <algorithm>
+#include <string>
 #include <vector>
 
 #include "../../include/elimrec_hip.h"
@@ -676,6 +682,35 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> row_gram(const at::Tensor &table,
     return {gram, sum, count};
 }
 
+// ---- co-interaction neighbours: the top-K of rows of A^T A over a bipartite graph given as two CSRs (csrc/cooccur.hip)
+std::tuple<at::Tensor, at::Tensor, at::Tensor> cooccur_topk(const at::Tensor &q_ptr, const at::Tensor &q_nbr, const at::Tensor &o_ptr,
+                                                            const at::Tensor &o_nbr, const at::Tensor &rows, int64_t K, std::string measure) {
+    need(q_ptr, "q_ptr", at::kLong, 1); need(q_nbr, "q_nbr", at::kInt, 1); need(o_ptr, "o_ptr", at::kLong, 1);
+    need(o_nbr, "o_nbr", at::kInt, 1); need(rows, "rows", at::kInt, 1);
+    TORCH_CHECK(K >= 1 && K <= elimrec_cooccur_max_k(), "elimrec::cooccur_topk: 1 <= K <= ", elimrec_cooccur_max_k(), ", got ", K);
+    const int m = measure == "count" ? 0 : measure == "cosine" ? 1 : measure == "jaccard" ? 2 : -1;
+    TORCH_CHECK(m >= 0, "elimrec::cooccur_topk: measure is one of count, cosine, jaccard, got '", measure, "'");
+    const at::Tensor qp = q_ptr.contiguous(), qn = q_nbr.contiguous(), op = o_ptr.contiguous(), on = o_nbr.contiguous(), r = rows.contiguous();
+    const int64_t n_query = qp.numel() - 1, n_other = op.numel() - 1, Q = r.numel();
+    TORCH_CHECK(n_query >= 0 && n_other >= 0, "elimrec::cooccur_topk: q_ptr and o_ptr need at least one entry");
+    TORCH_CHECK(qn.numel() == on.numel(), "elimrec::cooccur_topk: the two CSRs hold the same edges, got ", qn.numel(), " and ", on.numel());
+    checked_csr(qp, qn, n_query, n_other, true, "cooccur_topk", "q_ptr", "q_nbr", "q_nbr", "the other side has", "rows");
+    checked_csr(op, on, n_other, n_query, true, "cooccur_topk", "o_ptr", "o_nbr", "o_nbr", "the query side has", "rows");
+    checked_ids(r, n_query, true, "cooccur_topk", "query rows", "the side has", "rows");
+    at::Tensor idx = at::empty({Q, K}, r.options()), val = at::empty({Q, K}, r.options().dtype(at::kFloat)), cnt = at::empty({Q, K}, r.options());
+    if (Q == 0) return {idx, val, cnt};
+    at::Tensor walk = at::empty({Q}, qp.options());
+    check(elimrec_cooccur_walk(qp.data_ptr<int64_t>(), qn.data_ptr<int32_t>(), n_query, op.data_ptr<int64_t>(), n_other, r.data_ptr<int32_t>(), Q,
+                               walk.data_ptr<int64_t>(), cur_stream()), "cooccur_topk (walk)");
+    const int64_t n_dense = walk.gt(elimrec_cooccur_slots() / 2).sum().item<int64_t>();
+    at::Tensor ws = at::zeros({(int64_t)std::max<size_t>(16, elimrec_cooccur_workspace(n_dense, n_query))}, r.options().dtype(at::kByte));
+    check(elimrec_cooccur_topk(qp.data_ptr<int64_t>(), qn.data_ptr<int32_t>(), n_query, op.data_ptr<int64_t>(), on.data_ptr<int32_t>(), n_other,
+                               r.data_ptr<int32_t>(), Q, (int)K, m, 1, n_dense, walk.data_ptr<int64_t>(), idx.data_ptr<int32_t>(),
+                               val.data_ptr<float>(), cnt.data_ptr<int32_t>(), ws.data_ptr(), (size_t)ws.numel(), cur_stream()),
+          "cooccur_topk");
+    return {idx, val, cnt};
+}
+
 // ---- hard-negative pick: per triplet the best of M candidates over the tables' column blocks
 std::tuple<at::Tensor, at::Tensor, at::Tensor> pick_hard_negatives(const at::Tensor &user_table, const at::Tensor &user_sqnorm,
                                                                    const at::Tensor &item_table, const at::Tensor &item_sqnorm,
@@ -907,6 +942,7 @@ TORCH_LIBRARY(elimrec, m) {
     m.def("kmeans_update(Tensor table, Tensor sqnorm, Tensor assign, Tensor centroids, Tensor centroid_sqnorm) -> (Tensor, Tensor, Tensor, Tensor)");
     m.def("uniformity_sum(Tensor table, Tensor sqnorm, Tensor rows, float t) -> (Tensor, Tensor)");
     m.def("row_gram(Tensor table, Tensor sqnorm, Tensor rows) -> (Tensor, Tensor, Tensor)");
+    m.def("cooccur_topk(Tensor q_ptr, Tensor q_nbr, Tensor o_ptr, Tensor o_nbr, Tensor rows, int K, str measure) -> (Tensor, Tensor, Tensor)");
     m.def("pick_hard_negatives(Tensor user_table, Tensor user_sqnorm, Tensor item_table, Tensor item_sqnorm, float[] weights, Tensor users, "
           "Tensor cands) -> (Tensor, Tensor, Tensor)");
     m.def("history_support(Tensor table, Tensor sqnorm, float[] weights, Tensor users, Tensor lists, Tensor hist_ptr, Tensor hist_items, int top, "
@@ -949,6 +985,7 @@ TORCH_LIBRARY_IMPL(elimrec, CUDA, m) {
     m.impl("kmeans_update", &kmeans_update);
     m.impl("uniformity_sum", &uniformity_sum);
     m.impl("row_gram", &row_gram);
+    m.impl("cooccur_topk", &cooccur_topk);
     m.impl("pick_hard_negatives", &pick_hard_negatives);
     m.impl("history_support", &history_support);
     m.impl("bootstrap_means", &bootstrap_means);

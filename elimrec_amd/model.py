@@ -1418,6 +1418,64 @@ class EliMRec(BasicModel):
         """similar_items over the user rows: the k users closest to each given user."""
         return self._similar("user", user_ids, k, space, exclude)
 
+    def cooccur_index(self, side):
+        """The training graph as the ops.CooccurIndex of one side ("item": item -> its training users and back; "user": the
+        transpose), built from the data set's train dict at the first call, checked on the host and kept on the model's device."""
+        self._side_rows(side)
+        dev = self._require_gpu()
+        kept = self.__dict__.setdefault("_co_index", {})
+        hit = kept.get(side)
+        if hit is None or hit.device != dev:
+            hit = kept[side] = ops.CooccurIndex.from_train(self.dataset.get_user_train_dict(), self.num_users, self.num_items, side, dev)
+        return hit
+
+    @torch.no_grad()
+    def co_neighbours_device(self, side, rows, k, measure, out_idx, out_val, out_cnt=None):
+        """The k co-interaction neighbours of each given row of the TRAINING GRAPH -- side "item": the items the same users took
+        ("users who took this also took ..."), side "user": the users who took the same items -- as ops.cooccur_topk lists them:
+        out_idx int32 / out_val float32 (optional) / out_cnt int32 (optional, the raw co-count) [B x k] on the device, by (score
+        descending, id ascending), -1 / -inf / 0 where fewer than k rows share a neighbour; the row itself is never listed
+        (csrc/cooccur.hip). measure: "count", "cosine" or "jaccard". rows: the query ids (host array or tensor, checked on the
+        host). Nothing of the learned tables is read: this works on an untrained model, before the first step. Single-GPU."""
+        k, _ = ops._cooccur_k("co_neighbours_device", k), ops._cooccur_measure("co_neighbours_device", measure)
+        index = self.cooccur_index(side)
+        q = ops._cooccur_rows("co_neighbours_device", index, rows)
+        n_dense = int((index.walk[q] > ops.COOCCUR_SLOTS // 2).sum())
+        need = ops.cooccur_workspace(n_dense, index.n_query)
+        kept = self.__dict__.setdefault("_co_ws", {})
+        if need and (kept.get(side) is None or kept[side].numel() < need):
+            if need > ops.COOCCUR_WORKSPACE_BUDGET:
+                raise ValueError("co_neighbours_device: the dense form's counter rows need %d bytes, the budget is %d"
+                                 % (need, ops.COOCCUR_WORKSPACE_BUDGET))
+            kept[side] = torch.zeros(need, dtype=torch.uint8, device=index.device)     # zero once: every call leaves it zero
+        ops.cooccur_topk(index, q, k, out_idx, out_val, out_cnt, measure=measure, workspace=kept.get(side) if need else None)
+        return out_idx, out_val
+
+    def _co(self, side, ids, k, measure):
+        n_rows = self.num_items if side == "item" else self.num_users
+        k, _ = ops._cooccur_k("co_%ss" % side, k), ops._cooccur_measure("co_%ss" % side, measure)
+        ids = self._id_lists([ids], side, n_rows)[1]
+        dev = self._require_gpu()
+        idx = torch.empty(ids.size, k, dtype=torch.int32, device=dev)
+        val = torch.empty(ids.size, k, dtype=torch.float32, device=dev)
+        self.co_neighbours_device(side, ids, k, measure, idx, val)
+        return Neighbours(idx.cpu(), val.cpu())
+
+    def co_items(self, item_ids, k, measure="cosine"):
+        """The k items most often taken by the same training users as each given item -- "users who took this also took ...",
+        ItemKNN's neighbour lists: Neighbours(ids CPU int32 [B x k] (-1 padded), scores CPU fp32 [B x k] (-inf padded)), the tuple
+        similar_items returns, by (score descending, id ascending). With c = the users who took both, a and b the two items'
+        training interactions: measure "count" scores c, "cosine" c / sqrt(a b), "jaccard" c / (a + b - c). The item itself is
+        never listed, nor an item without a common user. 1 <= k <= 256 and a known measure, else ValueError; an id outside the
+        catalogue is an IndexError -- both before anything touches the device. The lists are read off the training graph alone: no
+        cached tables are needed, so this works on an untrained model."""
+        return self._co("item", item_ids, k, measure)
+
+    def co_users(self, user_ids, k, measure="cosine"):
+        """co_items over the users: the k users who took the most items in common with each given user. Needs no cached tables: it
+        works on an untrained model."""
+        return self._co("user", user_ids, k, measure)
+
     @torch.no_grad()
     def clusters_device(self, side, n_clusters, space="fused", iters=25, seed=2022, init=None):
         """Spherical k-means of the item rows (side "item") or the user rows ("user") of one block of the cached tables -- space

@@ -1030,6 +1030,10 @@ def __getattr__(name):
         return int(_lib.load().elimrec_geometry_chunk())
     if name == "GEOMETRY_SEGMENT":       # consecutive list positions per partial sum of row_gram
         return int(_lib.load().elimrec_geometry_segment())
+    if name == "COOCCUR_SLOTS":          # (key, count) pairs of the LDS form's table of cooccur_topk
+        return int(_lib.load().elimrec_cooccur_slots())
+    if name == "COOCCUR_GROUPS":         # workgroups (and counter rows) of cooccur_topk's dense form at most
+        return int(_lib.load().elimrec_cooccur_groups())
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 
@@ -2188,4 +2192,160 @@ def history_support(table, sqnorm, weights, users, lists, hist, top, out_idx, ou
                                                    _dev(hist.ptr, "hist_ptr", torch.int64), _dev(hist.items, "hist_items", torch.int32),
                                                    hist.n_rows, top, 1 if exclude_self else 0, ip, vp, cp, mp, _stream()),
                "history_support")
+    return out_idx
+
+
+COOCCUR_MAX_K = 256                      # the longest list cooccur_topk keeps (csrc/cooccur.hip), known without the library
+COOCCUR_MEASURES = {"count": 0, "cosine": 1, "jaccard": 2}
+COOCCUR_WORKSPACE_BUDGET = 1 << 30       # bytes cooccur_topk allocates for the dense form's counter rows at most (workspace=None)
+
+
+def cooccur_rows_in_lds(W):
+    """Which form cooccur_topk takes for a query row whose walk is W = the sum of deg(u) over the row's segment (host arithmetic
+    only): True = the LDS form (W <= COOCCUR_SLOTS / 2: the hash table's load factor is at most 0.5 whatever the ids are), False =
+    the dense form. Both forms give the same bits. ValueError for W < 0."""
+    form = int(_lib.load().elimrec_cooccur_rows_in_lds(int(W)))
+    if form < 0:
+        raise ValueError("elimrec_amd.ops.cooccur_rows_in_lds: W >= 0, got %d" % W)
+    return bool(form)
+
+
+def cooccur_workspace(n_dense_rows, n):
+    """Bytes of the dense form's counter rows for a call with n_dense_rows rows on that form over a query side of n rows (host
+    arithmetic only): min(n_dense_rows, COOCCUR_GROUPS) int32 rows of n entries."""
+    if n_dense_rows < 0 or not 0 <= n < 2 ** 31 - 1:
+        raise ValueError("elimrec_amd.ops.cooccur_workspace: n_dense_rows >= 0 and 0 <= n < 2^31 - 1, got %d and %d" % (n_dense_rows, n))
+    return int(_lib.load().elimrec_cooccur_workspace(int(n_dense_rows), int(n)))
+
+
+def _cooccur_k(who, K):
+    if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or not 1 <= K <= COOCCUR_MAX_K:
+        raise ValueError("elimrec_amd.ops.%s: K must be an integer, 1 <= K <= %d, got %r" % (who, COOCCUR_MAX_K, K))
+    return int(K)
+
+
+def _cooccur_measure(who, measure):
+    if not isinstance(measure, str) or measure not in COOCCUR_MEASURES:
+        raise ValueError("elimrec_amd.ops.%s: measure is one of %s, got %r" % (who, ", ".join(sorted(COOCCUR_MEASURES)), measure))
+    return COOCCUR_MEASURES[measure]
+
+
+class CooccurIndex(object):
+    """One bipartite graph as two CSRs of the same edges, CHECKED ON THE HOST and then resident on `device`: q_ptr [n_query + 1] /
+    q_nbr maps a row of the query side to its neighbours on the other side (for item queries: item -> its training users), o_ptr
+    [n_other + 1] / o_nbr maps a row of the other side back (user -> items). Checked: the entry counts of the pointers, both
+    ascending from 0 to the edge count, the two edge counts equal (ValueError); integer ids, q_nbr in [0, n_other) and o_nbr in
+    [0, n_query) (IndexError). That o is q transposed is the caller's word -- the kernel needs only what is checked to stay within
+    its arrays. A repeated edge is an edge of its own. cooccur_topk takes the index as is, call after call. Kept on the host:
+    deg (the query side's degrees), walk (int64 [n_query]: W(q) = the sum of deg(u) over q's segment, which picks a row's form)
+    and has_neighbour (bool [n_query]: one of the row's neighbours has degree >= 2, so some other row shares it)."""
+
+    def __init__(self, q_ptr, q_nbr, o_ptr, o_nbr, n_query, n_other, device):
+        who = "CooccurIndex"
+        n_query, n_other = int(n_query), int(n_other)
+        if not (0 <= n_query < 2 ** 31 - 1 and 0 <= n_other < 2 ** 31 - 1):
+            raise ValueError("elimrec_amd.ops.%s: both sides need 0 <= rows < 2^31 - 1, got %d and %d" % (who, n_query, n_other))
+        qp, qn = _checked_csr(q_ptr, q_nbr, n_query, n_other, who, ("q_ptr", "q_nbr", "n_query", "q_nbr spans [%d, %d], the other side has %d rows"))
+        op, on = _checked_csr(o_ptr, o_nbr, n_other, n_query, who, ("o_ptr", "o_nbr", "n_other", "o_nbr spans [%d, %d], the query side has %d rows"))
+        if qn.size != on.size:
+            raise ValueError("elimrec_amd.ops.%s: the two CSRs hold the same edges, got %d and %d" % (who, qn.size, on.size))
+        self.n_query, self.n_other, self.n_edges = n_query, n_other, int(qn.size)
+        self.deg = np.diff(qp)
+        deg_o = np.diff(op)
+        along = np.zeros(qn.size + 1, dtype=np.int64)
+        np.cumsum(deg_o[qn], out=along[1:])
+        self.walk = along[qp[1:]] - along[qp[:-1]]
+        np.cumsum(deg_o[qn] >= 2, out=along[1:])
+        self.has_neighbour = (along[qp[1:]] - along[qp[:-1]]) > 0
+        self.device = torch.device(device)
+        self.q_ptr, self.o_ptr = torch.from_numpy(qp).to(device), torch.from_numpy(op).to(device)
+        self.q_nbr, self.o_nbr = _resident_ids(qn, device), _resident_ids(on, device)
+
+    @classmethod
+    def from_train(cls, user_train_dict, num_users, num_items, side, device):
+        """The training graph: side "item" -- the rows are items, their neighbours the users who took them -- or "user" (the rows
+        are users, co-counted over shared items). user_train_dict: user id -> that user's items."""
+        if side not in ("item", "user"):
+            raise ValueError("elimrec_amd.ops.CooccurIndex.from_train: side is 'item' or 'user', got %r" % (side,))
+        U, I = int(num_users), int(num_items)
+        if not isinstance(user_train_dict, dict):
+            raise TypeError("user_train_dict must be a dict")
+        if any(not 0 <= int(u) < U for u in user_train_dict):
+            raise IndexError("user ids must lie in [0, %d)" % U)
+        none = np.zeros(0, dtype=np.int64)
+        up, ui, lens = ragged([user_train_dict.get(u, none) for u in range(U)], dtype=np.int64,
+                              check=(I, "item ids must lie in [0, %d)" % I), cast=int)
+        order = np.argsort(ui, kind="stable")
+        ip = np.zeros(I + 1, dtype=np.int64)
+        np.cumsum(np.bincount(ui, minlength=I), out=ip[1:])
+        iu = np.repeat(np.arange(U, dtype=np.int64), lens)[order]
+        if side == "item":
+            return cls(ip, iu, up, ui, I, U, device)
+        return cls(up, ui, ip, iu, U, I, device)
+
+
+def _cooccur_rows(who, index, rows):
+    """The query ids of a cooccur call: an ops.CooccurIndex, and rows as a flat host array checked against its side."""
+    if not isinstance(index, CooccurIndex):
+        raise TypeError("elimrec_amd.ops.%s: index must be an ops.CooccurIndex, got %s" % (who, type(index).__name__))
+    return _checked_ids(rows, index.n_query, who, "rows", "query rows span [%d, %d], the side has %d rows")
+
+
+def cooccur_walk(index, rows):
+    """elimrec_cooccur_walk: int64 device tensor [Q] <- W(q) of every query row, the sum of deg(u) over the row's segment -- the
+    number of 2-hop entries cooccur_topk walks for it, which alone picks its form (cooccur_rows_in_lds). rows: host array or tensor
+    of ids, checked on the host (IndexError). index.walk holds the same numbers for every row, from the host's CSR."""
+    q = _cooccur_rows("cooccur_walk", index, rows)
+    out = torch.zeros(max(1, q.size), dtype=torch.int64, device=index.device)[:q.size]
+    if q.size:
+        _lib.check(_lib.load().elimrec_cooccur_walk(_dev(index.q_ptr, "q_ptr", torch.int64), _dev(index.q_nbr, "q_nbr", torch.int32),
+                                                    index.n_query, _dev(index.o_ptr, "o_ptr", torch.int64), index.n_other,
+                                                    _dev(_resident_ids(q, index.device), "rows", torch.int32), q.size, out.data_ptr(),
+                                                    _stream()), "cooccur_walk")
+    return out
+
+
+def cooccur_topk(index, rows, K, out_idx, out_val=None, out_cnt=None, measure="cosine", lds=True, workspace=None):
+    """elimrec_cooccur_topk: per query row q the K rows j != q of the same side that share the most neighbours with it -- "users who
+    took this also took ...", the top-K of a row of A^T A (csrc/cooccur.hip). index: an ops.CooccurIndex. rows: host array or
+    tensor of ids, checked on the host (IndexError; a synchronisation for a device tensor); a repeated id is a row of its own.
+    c(q, j) = the number of two-step walks q -> u -> j (a repeated edge is an edge of its own: the product count), a = deg(q),
+    b = deg(j). measure "count": float(c); "cosine": c / sqrt(a b); "jaccard": c / (a + b - c) -- the last two in float64 with IEEE
+    sqrt and division, rounded once to fp32. Only c >= 1 is listed, never q itself. out_idx int32 / out_val float32 (optional) /
+    out_cnt int32 (optional: the raw c) [Q x K] on the index's device <- the K best by (score descending, id ascending), -1 /
+    -inf / 0 behind them; entries of the outputs beyond [Q x K] are left alone. 1 <= K <= COOCCUR_MAX_K = 256. A row with
+    cooccur_rows_in_lds(index.walk[q]) takes the LDS form (a hash table of COOCCUR_SLOTS pairs), every other row -- with lds=False
+    every row -- the dense form, whose counter rows live in `workspace`: a uint8 device tensor of at least cooccur_workspace(
+    n_dense_rows, index.n_query) bytes, 16-byte aligned, ZERO before its first use (every call leaves it zero); default: allocated
+    and zeroed here, at most COOCCUR_WORKSPACE_BUDGET bytes. A workspace that is too small, or a default past the budget, is a
+    ValueError before any launch. Both forms give the same bits: a row's outputs depend on the graph, the row, K and the measure
+    alone. Every argument error is raised before the device is touched. An empty `rows` returns without a launch."""
+    who = "cooccur_topk"
+    K = _cooccur_k(who, K)
+    m = _cooccur_measure(who, measure)
+    q = _cooccur_rows(who, index, rows)
+    Q, dev = int(q.size), index.device
+    ip = _rows_out(out_idx, "out_idx", torch.int32, Q, K, who, dev)
+    vp = _rows_out(out_val, "out_val", torch.float32, Q, K, who, dev) if out_val is not None else None
+    cp = _rows_out(out_cnt, "out_cnt", torch.int32, Q, K, who, dev) if out_cnt is not None else None
+    if Q == 0:
+        return out_idx
+    half = int(_lib.load().elimrec_cooccur_slots()) // 2
+    n_dense = int((index.walk[q] > half).sum()) if lds else Q
+    need = cooccur_workspace(n_dense, index.n_query)
+    if workspace is None:
+        if need > COOCCUR_WORKSPACE_BUDGET:
+            raise ValueError("elimrec_amd.ops.%s: the dense form's counter rows need %d bytes (%d rows of %d entries), the budget is %d: "
+                             "pass a workspace" % (who, need, min(n_dense, _lib.load().elimrec_cooccur_groups()), index.n_query,
+                                                   COOCCUR_WORKSPACE_BUDGET))
+        workspace = torch.zeros(max(16, need), dtype=torch.uint8, device=dev)
+    wp = _dev(workspace, "workspace", torch.uint8)
+    if workspace.numel() < need or not workspace.is_contiguous() or wp % 16 or workspace.device != dev:
+        raise ValueError("elimrec_amd.ops.%s: the workspace needs %d contiguous bytes on the index's device, 16-byte aligned (got %d)"
+                         % (who, need, workspace.numel()))
+    walk = torch.empty(Q, dtype=torch.int64, device=dev)
+    _lib.check(_lib.load().elimrec_cooccur_topk(_dev(index.q_ptr, "q_ptr", torch.int64), _dev(index.q_nbr, "q_nbr", torch.int32), index.n_query,
+                                                _dev(index.o_ptr, "o_ptr", torch.int64), _dev(index.o_nbr, "o_nbr", torch.int32), index.n_other,
+                                                _dev(_resident_ids(q, dev), "rows", torch.int32), Q, K, m, 1 if lds else 0, n_dense,
+                                                walk.data_ptr(), ip, vp, cp, wp, workspace.numel(), _stream()), who)
     return out_idx

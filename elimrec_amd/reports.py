@@ -2,7 +2,8 @@
 whose neighbourhood the fused space copies (NeighbourReport), the lists themselves (ListReport), what diversifying them costs and
 buys (DiversifyReport), whether they match each user's own popularity mix (CalibrationReport), which items of a user's history back
 them (HistoryReport), how sure the evaluation metrics are
-(SignificanceReport), what the learned cosine spaces themselves look like (GeometryReport) -- and what they share: the user /
+(SignificanceReport), what the learned cosine spaces themselves look like (GeometryReport), whether their neighbourhoods are the
+training graph's co-interaction neighbourhoods (CoNeighbourReport) -- and what they share: the user /
 item groups, the groups as a checked index on the device, the group means, the table format, the model preflight and the block-wise
 top-K lists. The rows come from the model's *_device readers (model.py), the means from ops.group_metric_means."""
 import collections
@@ -1497,5 +1498,115 @@ class GeometryReport(_Report):
         align_labels = [("%s %s:" % (s, which)).ljust(20) for s in spaces for which in ("align_train", "align_test")]
         final = GeometryTables(GEOMETRY_COLUMNS, labels, values, tuple(self.align_columns), align_labels, align)
         buf = format_geometry(final)
+        self._done[key] = (version, final, buf)
+        return final, buf
+
+
+def co_neighbour_columns(mods):
+    """Column names of the co-neighbour report: n (the items counted), co_n, co_score, co_pop, then co_overlap_<space> per space
+    (fused, then the heads' modality letters in head order)."""
+    return ("n", "co_n", "co_score", "co_pop") + tuple("co_overlap_" + s for s in ("fused",) + tuple(str(m) for m in mods))
+
+
+class CoNeighbourReport(_Report):
+    """Are the learned neighbourhoods collaborative or content (--co_report=K)? For EVERY item its co-interaction top-k list -- the
+    items the same training users took, under `measure` ("count", "cosine", "jaccard"; EliMRec.co_neighbours_device,
+    csrc/cooccur.hip) -- beside its cosine top-k list in each space, the fused space and then every single-modal head
+    (EliMRec.neighbours_device), items in blocks of block_items. Per item:
+      co_n = the listed co-neighbours (fewer than k where fewer items share a user); co_score = their mean score;
+      co_pop = their mean training interactions; co_overlap_<space> = the share of the listed co-neighbours that the space's
+      cosine list also holds (ops.list_overlap / co_n).
+    The table holds their means (ops.group_metric_means: float64 sums, rounded once) over all items that HAVE a co-neighbour and
+    -- item_group_view -- per item popularity group (assign_item_groups over the items' training interactions); an item without
+    one is in no group, decided on the host from the CSR: an item has a co-neighbour iff one of its users has degree >= 2. Column
+    0 of every table row is n, the items counted; a group without such an item has n = 0 and NaN. Only the table reaches the host.
+    The lists do not depend on the predict type; the table is computed once per table version of a model and kept."""
+
+    name, needs = "co", "co_neighbours_device"
+
+    def __init__(self, dataset, user_train_dict, k, measure="cosine", item_group_view=None):
+        if not isinstance(user_train_dict, dict):
+            raise TypeError("user_train_dict must be a dict")
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1 or k > min(ops.COOCCUR_MAX_K, ops.KNN_MAX_K):
+            raise ValueError("k must be an integer in [1, %d], got %r" % (min(ops.COOCCUR_MAX_K, ops.KNN_MAX_K), k))
+        ops._cooccur_measure("CoNeighbourReport", measure)
+        self.dataset = dataset
+        self.num_items = I = int(dataset.num_items)
+        self.k, self.measure = int(k), measure
+        self.block_items = 8192
+        self.item_counts = item_train_counts(user_train_dict, I)
+        # an item has a co-neighbour iff one of its users has degree >= 2 (the host's reading of the CSR, as CooccurIndex keeps it)
+        has = np.zeros(I, dtype=bool)
+        for items in user_train_dict.values():
+            if len(items) >= 2:
+                ids = np.asarray(list(items), dtype=np.int64)
+                if ids.size and (ids.min() < 0 or ids.max() >= I):
+                    raise IndexError("item ids must lie in [0, %d)" % I)
+                if np.unique(ids).size >= 2:
+                    has[ids] = True
+        self.has_neighbour = has
+        labels, positions = self._item_groups(np.arange(I, dtype=np.int64), self.item_counts, item_group_view)
+        self.group_labels = labels
+        self._positions = [p[has[p]] for p in positions]
+        self._done = {}
+
+    def _make_resident(self, device):
+        """The group index, the items' training counts and the blocks' checked queries resident on the device."""
+        return dict(groups=group_index(self._positions, self.num_items, device),
+                    counts=torch.from_numpy(self.item_counts.astype(np.float64)).to(device), queries={})
+
+    def co_rows(self, model):
+        """Every item's row of the report on the device: ([items x C] float32, column names without n); a row of an item without
+        a co-neighbour is NaN (it is in no group)."""
+        device = self._preflight(model)
+        res = self._resident(device)
+        mods = tuple(model._mods)
+        columns = co_neighbour_columns(mods)[1:]
+        S, k, I = len(mods), self.k, self.num_items
+        rows = torch.empty(I, len(columns), dtype=torch.float32, device=device)
+        step = max(1, int(self.block_items))
+        B = min(step, I)
+        co_idx = torch.empty(B, k, dtype=torch.int32, device=device)
+        co_val = torch.empty(B, k, dtype=torch.float32, device=device)
+        idx = torch.empty(B, k, dtype=torch.int32, device=device)
+        cnt = torch.empty(B, dtype=torch.int32, device=device)
+        for a in range(0, I, step):
+            b = min(a + step, I)
+            ids = np.arange(a, b, dtype=np.int32)
+            query = res["queries"].get((a, b))
+            if query is None:
+                query = res["queries"][(a, b)] = ops.NeighbourQuery(ids, I, device)
+            model.co_neighbours_device("item", ids, k, self.measure, co_idx[:b - a], co_val[:b - a])
+            listed = co_idx[:b - a] >= 0
+            n = listed.sum(dim=1).double()                                         # 0 gives NaN below
+            out = rows[a:b]
+            out[:, 0] = n.float()
+            out[:, 1] = (torch.where(listed, co_val[:b - a].double(), 0.0).sum(dim=1) / n).float()
+            pop = res["counts"][co_idx[:b - a].clamp(min=0).long()]
+            out[:, 2] = (torch.where(listed, pop, 0.0).sum(dim=1) / n).float()
+            for h, space in enumerate(("fused",) + mods):
+                model.neighbours_device("item", None, k, space, idx[:b - a], None, query=query)
+                ops.list_overlap(co_idx[:b - a], idx[:b - a], cnt)
+                out[:, 3 + h] = (cnt[:b - a].double() / n).float()
+        return rows, columns
+
+    def evaluate(self, model):
+        """(final float64 [1 + item groups x (1 + C)]: row 0 = all items with a co-neighbour, then one row per item popularity
+        group; column 0 = n, the items counted, then the float32 means; buf: a header of column names and one "%.8f" line per row,
+        in the effect report's format). A second call on the same table version of the same model returns the kept result."""
+        device = self._preflight(model)
+        key = (id(model), str(device))
+        if hasattr(model, "_cached_tables"):                     # a pending step made real first: it publishes a new table version
+            model._cached_tables("the co-neighbour report needs")
+        version = getattr(model, "_table_version", None)
+        hit = self._done.get(key)
+        if hit is not None and version is not None and hit[0] == version:
+            return hit[1], hit[2]
+        rows, columns = self.co_rows(model)
+        index = self._resident(device)["groups"]
+        means = group_table(rows, index, len(self.group_labels)).astype(np.float64)
+        means[index.sizes == 0] = np.nan
+        final = np.concatenate([index.sizes.astype(np.float64)[:, None], means], axis=1)
+        buf = format_table(("n",) + tuple(columns), self.group_labels, final)
         self._done[key] = (version, final, buf)
         return final, buf

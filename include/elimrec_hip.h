@@ -797,6 +797,42 @@ int elimrec_geometry_tile(void);
 int elimrec_geometry_chunk(void);
 int elimrec_geometry_segment(void);
 
+/* Co-interaction neighbours (csrc/cooccur.hip): per query row of one side of a bipartite graph the K rows of the same side with the
+ * largest co-occurrence score -- the top-K of a row of A^T A (ItemKNN's neighbour lists). No counterpart in the reference. The
+ * graph comes as two CSRs of the same edges: d_q_ptr int64 [n_query + 1] / d_q_nbr int32 maps a row of the query side to its
+ * neighbours on the other side (item -> its training users), d_o_ptr int64 [n_other + 1] / d_o_nbr int32 maps a row of the other
+ * side back (user -> items). Both pointer arrays ascend from 0 to the edge count: the CALLER checks that (the kernels trust them);
+ * the ids are checked by the kernels, entry by entry -- a neighbour id outside its side is skipped and never dereferenced, a query
+ * id outside [0, n_query) gives a row of fillers. d_rows int32 [Q]: the query ids; a repeated id is a row of its own.
+ * c(q, j), j != q, = the number of two-step walks q -> u -> j; a repeated edge is an edge of its own, so c is the product count.
+ * a = deg(q), b = deg(j) (d_q_ptr differences). measure 0 count: float(c); 1 cosine: c / sqrt(a b); 2 jaccard: c / (a + b - c) --
+ * the last two in float64 with IEEE sqrt and division, rounded once to fp32 (with repeated edges a + b - c may be <= 0: the
+ * quotient, +inf or negative, is ranked as the number it is). Only c >= 1 is listed, never q itself. d_idx int32 / d_val fp32
+ * (optional) / d_cnt int32 (optional, the raw c) [Q x K] <- the K best by (score descending, id ascending), -1 / -inf / 0 behind
+ * them. 1 <= K <= elimrec_cooccur_max_k() = 256.
+ * d_walk int64 [Q] <- W(q) = the sum of deg(u) over q's segment (0 for a query outside the side): the work of the row, which
+ * alone picks its form. use_lds = 1: a row with elimrec_cooccur_rows_in_lds(W) -- W <= elimrec_cooccur_slots() / 2, slots = 4096
+ * (key, count) pairs of an open-addressing table in 32 KiB of LDS, load factor at most 0.5 whatever the ids are -- takes the LDS
+ * form, one workgroup per row; every other row, and with use_lds = 0 every row, the dense form: min(n_dense_rows,
+ * elimrec_cooccur_groups() = 512) workgroups loop over those rows, each with an int32 counter row of n_query entries in
+ * d_workspace (elimrec_cooccur_workspace(n_dense_rows, n_query) bytes, 16-byte aligned), which must be ZERO when the call starts
+ * and is zero again when it ends. n_dense_rows: the caller's count of the dense form's rows (from elimrec_cooccur_walk; Q with
+ * use_lds = 0); it sizes the grid and the workspace only -- with 0 declared, a row that needed the dense form gets fillers.
+ * Both forms give the same bits: a row's outputs depend on the graph, the row, K and the measure alone -- not on the arrival order
+ * of the candidates, the form, Q, the row's place in d_rows or the grid. Integer atomics only. Two or three launches on `stream`.
+ * elimrec_cooccur_walk: d_walk alone, one launch. elimrec_cooccur_rows_in_lds: 1 / 0, -1 for W < 0. */
+int elimrec_cooccur_topk(const int64_t *d_q_ptr, const int32_t *d_q_nbr, int64_t n_query, const int64_t *d_o_ptr,
+                         const int32_t *d_o_nbr, int64_t n_other, const int32_t *d_rows, int64_t Q, int K, int measure, int use_lds,
+                         int64_t n_dense_rows, int64_t *d_walk, int32_t *d_idx, float *d_val, int32_t *d_cnt, void *d_workspace,
+                         size_t workspace_bytes, void *stream);
+int elimrec_cooccur_walk(const int64_t *d_q_ptr, const int32_t *d_q_nbr, int64_t n_query, const int64_t *d_o_ptr, int64_t n_other,
+                         const int32_t *d_rows, int64_t Q, int64_t *d_walk, void *stream);
+size_t elimrec_cooccur_workspace(int64_t n_dense_rows, int64_t n);
+int elimrec_cooccur_slots(void);
+int elimrec_cooccur_max_k(void);
+int elimrec_cooccur_groups(void);
+int elimrec_cooccur_rows_in_lds(int64_t W);
+
 /* Hard-negative pick (csrc/hardneg.hip): per triplet the best of M candidate items under the current tables. No counterpart in
  * the reference. d_U / d_T point at row 0, column 0 of an [n_users x blocks * d] / [n_items x blocks * d] slice of a row-major
  * float32 matrix with row stride ld_u / ld_i >= blocks * d, block b = columns [b * d, (b + 1) * d); d_sq_u[r * ldsq_u + b] /

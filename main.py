@@ -112,6 +112,12 @@ class Net(object):
         self.geometry_report = int(cfg["geometry_report"]) if "geometry_report" in cfg else 0
         if self.geometry_report and self.world > 1:
             raise ValueError("--geometry_report needs the whole cached tables on one rank: it is single-GPU")
+        # --co_report=K (default 0: off), --co_measure=count|cosine|jaccard: once per [TEST], after both effects' lines, how much of
+        # every item's top-K co-interaction list ("users who took this also took ...") its top-K cosine lists hold, in the fused space
+        # and in each head's (the lists do not depend on the predict type)
+        self.co_report = int(cfg["co_report"]) if "co_report" in cfg else 0
+        if self.co_report and self.world > 1:
+            raise ValueError("--co_report needs the whole cached item table on one rank: it is single-GPU")
         # --list_report=K (default 0: off): under each [TEST] line the top-K lists' intra-list similarity, popularity and catalogue
         # exposure, after both effects how the lists change from TE to TIE
         self.list_report = int(cfg["list_report"]) if "list_report" in cfg else 0
@@ -347,6 +353,9 @@ class Net(object):
         if self.geometry_report:
             Logger.info("  [geometry] uniformity (t = {:g}), spectrum and alignment of the cosine spaces:\n{}".format(
                 rec.geometry_reporter.t, rec.geometry_reporter.evaluate(rec)[1]))
+        if self.co_report:
+            Logger.info("  [co-neighbours] top-{} co-interaction neighbours ({}) of every item against its cosine neighbours:\n{}".format(
+                self.co_report, rec.co_reporter.measure, rec.co_reporter.evaluate(rec)[1]))
         return lines
 
     # ------------------------------------------------------------------ the run
