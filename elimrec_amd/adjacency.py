@@ -42,6 +42,8 @@ def build_adj_device(train_users, train_items, num_users, num_items, adj_type, d
     max_deg = 0
     if E:
         max_deg = int(max(torch.bincount(u, minlength=U).max(), torch.bincount(i, minlength=I).max()))
+    else:                # no interactions (the diagonal alone, or no entry): the entry point takes no null pointer, and reads none of these
+        u = i = torch.zeros(1, dtype=torch.int64, device=dev)
     table = torch.from_numpy(_pow_table(adj_type if adj_type in ADJ_TYPES else "mean", max_deg)).to(dev)
     nnz = 2 * E + (N if with_diag else 0)
     rowptr = torch.empty(N + 1, dtype=torch.int32, device=dev)

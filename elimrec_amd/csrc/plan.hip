@@ -204,9 +204,13 @@ extern "C" size_t elimrec_plan_workspace(int64_t n_rows, int64_t n_seg, int64_t 
     size_t tmp = s1 > s2 ? s1 : s2;
     const size_t sc = plan_scan_bytes(n);
     tmp = tmp > sc ? tmp : sc;
-    // keys in / out, rows in, two flag arrays, two scans (rows stage); segment keys in / out + ids in (tiles stage)
-    return align_up(tmp, 256) + 2 * align_up((size_t)n_rows * 8, 256) + 5 * align_up((size_t)n_rows * 4, 256) +
-           3 * align_up((size_t)(n_seg > 0 ? n_seg : 1) * 4, 256) + 1024;
+    // rows stage: keys in / out, rows in, two flag arrays, two scans. Tiles stage (the rows stage's arrays are dead by then, it takes
+    // the same space): the segments' first positions, their lengths, ranks, ids in / out and keys in / out, the tiles' entry counts.
+    // The larger of the two: a graph of few, long rows has more segments and tiles than rows.
+    const size_t ns = (size_t)(n_seg > 0 ? n_seg : 1), nt = (size_t)(n_tiles > 0 ? n_tiles : 1);
+    const size_t rows_stage = 2 * align_up((size_t)n_rows * 8, 256) + 5 * align_up((size_t)n_rows * 4, 256);
+    const size_t tiles_stage = align_up(ns * 8, 256) + 6 * align_up(ns * 4, 256) + align_up(nt * 8, 256);
+    return align_up(tmp, 256) + (rows_stage > tiles_stage ? rows_stage : tiles_stage) + 1024;
 }
 
 // Stage 1: the rows. d_order int32 [n_rows]: rows by (class, side, descending length) -- workgroup rows, wave rows, split rows (by

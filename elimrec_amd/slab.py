@@ -51,6 +51,13 @@ def _is_pow2(x):
     return x >= 1 and (x & (x - 1)) == 0
 
 
+def _check_rows_from(rows_from, n_rows):
+    """A plan of the rows [rows_from, n) holds at least one row: SweepPlan's n_sweep is the user count of a bipartite graph, below
+    n by the item count. A plan of no rows has no tile arrays to hand to a hop (docs/REJECTED.md)."""
+    if rows_from and not 0 < int(rows_from) < int(n_rows):
+        raise ValueError("rows_from must be in [0, n_rows): got %d for %d rows" % (int(rows_from), int(n_rows)))
+
+
 class SellPlan(object):
     """SELL-64 work items of a CSR matrix on a device (struct elimrec_sell)."""
 
@@ -75,6 +82,7 @@ class SellPlan(object):
         col = m.indices.astype(np.int32)
         val = m.data.astype(np.float32)
         deg = np.diff(rowptr)
+        _check_rows_from(rows_from, n_rows)
         T = int(threshold)
         # a wave per row up to 64 neighbours per lane group at 8 groups (measured: 0.319 against 0.322 ms per step with 32),
         # 32 with more, narrower groups (column shards; not re-measured)
@@ -152,11 +160,15 @@ class SellPlan(object):
     def on_device(cls, rowptr, col, val, n_src, threshold=64, side_split=None, ipw=8, rows_from=0, share=None):
         """The tiered plan of a CSR that is ALREADY on the device (rowptr int64 [n + 1], col int32, val fp32: csrc/adj.hip's output, or
         a rank's part of an edge list too large to plan on a host), built there by csrc/plan.hip: the arrays of SellPlan(m,
-        tiered=True, ...) bit for bit (tests/test_shard_gpu.py::test_device_plan_build_equals_the_host_plan), with two read-backs of a
-        handful of counts. T1 / T2 / segment length follow the same rules and environment switches as the host form."""
+        tiered=True, ...) bit for bit (tests/test_shard_gpu.py::test_device_plan_build_equals_the_host_plan;
+        tests/test_plan_build_gpu.py: every lane-group count on the tier ladders, rows_from, degenerate graphs), with two read-backs
+        of a handful of counts. T1 / T2 / segment length follow the same rules and environment switches as the host form."""
         lib = _lib.load()
         dev = rowptr.device
         n_rows = int(rowptr.numel()) - 1
+        _check_rows_from(rows_from, n_rows)
+        if col.numel() == 0:         # no non-zeros: one zero entry, as the host form keeps (the entry points take no null pointer)
+            col, val = torch.zeros(1, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.float32, device=dev)
         T = int(threshold)
         T1 = (64 if ipw <= 8 else 32) * ipw
         T2 = 256 * ipw
@@ -306,9 +318,12 @@ class SellPlan(object):
         tile_long = np.zeros(max(n_tseg * G, 1), np.int32)
         tile_long[:len(seg_long)] = seg_long
         seg_end = len(A[0]) + len(B[0]) + n_tseg
+        # kmax >= 1 also where every tile is empty (a graph of empty rows): it is the ballot launch's grid.y and the bit words' row
+        # stride, and elimrec_slab_hop / elimrec_slab_source_bits refuse a tiered plan whose tile_kmax is not > 0
+        kmax = max(int(((steps * G + 63) // 64).max()), 1) if len(steps) else 1
         return dict(tile_off=tile_off, tile_len=GL.reshape(-1), tile_dst=GD.reshape(-1), tile_long=tile_long, tile_col=tcol,
                     tile_val=tval, n_t4=len(A[0]), n_t1=len(B[0]), n_tseg=n_tseg, n_tfin=len(D[0]), entries=total,
-                    seg_entries=int(tile_off[seg_end]), kmax=int(((steps * G + 63) // 64).max()) if len(steps) else 1)
+                    seg_entries=int(tile_off[seg_end]), kmax=kmax)
 
     def ref(self):
         return ctypes.byref(self.desc)

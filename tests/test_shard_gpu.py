@@ -9,6 +9,7 @@ import pytest
 import scipy.sparse as sp
 import torch
 
+from graph_build_cases import plans_equal as _plans_equal
 from helpers import assert_grad_close, build_model_from_fixture, load_golden, make_config, rel_err, sub
 
 pytestmark = pytest.mark.gpu
@@ -163,19 +164,6 @@ def test_window_sweep_hop_equals_the_tile_hop(d, w, U, I, window, monkeypatch):
     if want is not None:
         assert (y1.dense().double() - want).abs().max().item() < 1e-4
     assert torch.equal(y1.dense()[:U], ((b[:U] + S[:U] * act[:U, None]) * 0.25))
-
-
-def _plans_equal(host, devp):
-    assert (host.n_rows, host.n_src, host.nnz, host.n_seg, host.n_long, host.n_w1, host.n_w4, host.n_tiles, host.tile_groups,
-            host.sell_entries, host.sell_seg_entries) == (devp.n_rows, devp.n_src, devp.nnz, devp.n_seg, devp.n_long, devp.n_w1, devp.n_w4,
-                                                          devp.n_tiles, devp.tile_groups, devp.sell_entries, devp.sell_seg_entries)
-    for k in ("long_rows", "long_seg_ptr", "long_index", "tile_off", "tile_len", "tile_dst", "tile_long", "tile_col", "tile_val", "rowptr",
-              "csr_col", "csr_val"):
-        a, b = host.t[k], devp.t[k]
-        assert a.dtype == b.dtype and a.shape == b.shape and torch.equal(a, b), k
-    for f, _ in host.desc._fields_:
-        if not f.startswith("d_"):
-            assert getattr(host.desc, f) == getattr(devp.desc, f), f
 
 
 @pytest.mark.parametrize("kind,n,U,ipw,T,split,rows_from", [("random", 2500, 900, 8, 64, 900, 0), ("random", 2500, 900, 8, 32, None, 0),
