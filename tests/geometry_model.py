@@ -32,21 +32,54 @@ def unit_rows(T, sq, ids):
     return (T[ids] * inv_norm(np.asarray(sq, dtype=np.float32)[ids])[:, None]).astype(np.float32)
 
 
-def uniformity_model(T, sq, rows, t):
-    """(S, pairs, n_valid, uniformity) in float64 over the valid entries of `rows`."""
+def live_cells(n, tile, chunk):
+    """The (tile, chunk) cells uniformity_sum launches for a list of n positions, in launch order. By the definition, not by the
+    kernel's closed form: the positions are cut into tiles of `tile` and chunks of `chunk`, the cells run tile-major, and tile i
+    meets the chunks c >= i * tile // chunk -- its own chunk and every later one."""
+    n_chunks = (n + chunk - 1) // chunk
+    return [(i, c) for i in range((n + tile - 1) // tile) for c in range(i * tile // chunk, n_chunks)]
+
+
+def cells_with_a_pair(n, tile, chunk):
+    """The set of (tile of p, chunk of q) over all positions p < q < n, by brute force over the positions."""
+    found = set()
+    for p in range(n - 1):
+        found.update((p // tile, int(c)) for c in np.unique(np.arange(p + 1, n) // chunk))
+    return found
+
+
+def uniformity_model(T, sq, rows, t, cells=None):
+    """(S, pairs, n_valid, uniformity) in float64 over the valid entries of `rows`. With cells = (tile, chunk) and a list whose
+    entries are all valid (position = rank among the valid ones), a fifth value: the float64 sum of every cell of
+    live_cells(n, tile, chunk), in that order; a pair outside those cells is an error."""
     ids = valid_entries(rows, sq, np.asarray(T).shape[0])
     n = int(ids.size)
     pairs = n * (n - 1) // 2
+    if cells is not None:
+        tile, chunk = cells
+        assert n == np.asarray(rows).size and 1024 % tile == 0
+        per_cell = np.zeros(((n + tile - 1) // tile, (n + chunk - 1) // chunk))
     if n < 2:
-        return 0.0, pairs, n, float("nan")
+        return (0.0, pairs, n, float("nan")) + (() if cells is None else ([0.0] * len(live_cells(n, tile, chunk)),))
     X = unit_rows(T, sq, ids).astype(np.float64)
     S = 0.0
     for a in range(0, n, 1024):                                      # row blocks: the strict upper triangle
         cos = X[a:a + 1024] @ X.T
         e = np.exp(2.0 * float(t) * (cos - 1.0))
         p = np.arange(a, min(a + 1024, n))[:, None]
-        S += float(np.where(p < np.arange(n)[None, :], e, 0.0).sum())
-    return S, pairs, n, float(np.log(S / pairs))
+        e = np.where(p < np.arange(n)[None, :], e, 0.0)
+        S += float(e.sum())
+        if cells is not None:
+            by_chunk = np.add.reduceat(e, np.arange(0, n, chunk), axis=1)
+            for i in range(a // tile, (min(a + 1024, n) + tile - 1) // tile):
+                per_cell[i] = by_chunk[i * tile - a:(i + 1) * tile - a].sum(0)
+    if cells is None:
+        return S, pairs, n, float(np.log(S / pairs))
+    live = live_cells(n, tile, chunk)
+    mask = np.zeros(per_cell.shape, dtype=bool)
+    mask[tuple(np.asarray(live).T)] = True
+    assert not per_cell[~mask].any()
+    return S, pairs, n, float(np.log(S / pairs)), [float(per_cell[i, c]) for i, c in live]
 
 
 def gram_model(T, sq, rows):

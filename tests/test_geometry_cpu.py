@@ -78,7 +78,65 @@ def test_the_model_by_hand():
     assert np.allclose(al, [0.0, 4.0, 2.0, 2.0], atol=1e-12)                 # a row without a norm: cosine 0
 
 
+# --------------------------------------------------------------------------- the cell grid of uniformity_sum
+def _grid_sizes():
+    from elimrec_amd import ops
+    TILE, CHUNK = ops.GEOMETRY_TILE, ops.GEOMETRY_CHUNK
+    return TILE, CHUNK, [0, 1, TILE, CHUNK, CHUNK + 1, 2 * CHUNK + 1, 3 * CHUNK + TILE + 1]
+
+
+def test_live_cells_are_the_cells_that_hold_a_pair():
+    """gm.live_cells against brute force over the positions: every (tile, chunk) that holds a pair p < q appears exactly once, in
+    tile-major order. The definition (tile i meets the chunks c >= i * TILE // CHUNK) lists ONE cell brute force does not find, and
+    only when n % TILE == 1: the diagonal cell of a last tile of a single position, which has no q behind its p. It is launched
+    (and sized in the workspace) all the same and must add 0; no other cell without a pair may appear."""
+    TILE, CHUNK, sizes = _grid_sizes()
+    for n in sizes:
+        cells = gm.live_cells(n, TILE, CHUNK)
+        assert cells == sorted(set(cells))                                   # each once, tile-major
+        idle = {((n - 1) // TILE, (n - 1) // CHUNK)} if n % TILE == 1 else set()
+        assert set(cells) - gm.cells_with_a_pair(n, TILE, CHUNK) == idle and gm.cells_with_a_pair(n, TILE, CHUNK) <= set(cells)
+    n = sizes[-1]                                                            # the size the device tests use
+    cells = gm.live_cells(n, TILE, CHUNK)
+    assert len(cells) == 290 and n == 6209 and cells[-2:] == [(96, 3), (97, 3)] and cells[256] == (80, 2)
+    small = gm.live_cells(7, 2, 4)                                           # by hand: tiles of 2, chunks of 4
+    assert small == [(0, 0), (0, 1), (1, 0), (1, 1), (2, 1), (3, 1)] and gm.cells_with_a_pair(7, 2, 4) == set(small) - {(3, 1)}
+
+
+def test_uniformity_workspace_is_one_float64_per_live_cell():
+    """8 bytes per cell of gm.live_cells, rounded up to 16; an empty list keeps room for one cell (16 bytes)."""
+    from elimrec_amd import ops
+    TILE, CHUNK, sizes = _grid_sizes()
+    for n in sizes:
+        cells = max(1, len(gm.live_cells(n, TILE, CHUNK)))
+        for d in (4, 64, 128):
+            assert ops.uniformity_workspace(n, d) == (8 * cells + 15) // 16 * 16, (n, d)
+
+
+def test_the_cell_sums_of_the_model_add_up():
+    T = np.random.default_rng(0).standard_normal((150, 8)).astype(np.float32)
+    sq = gm.sqnorms(T)
+    rows = np.random.default_rng(1).permutation(150)[:139]
+    S, pairs, n, uni = gm.uniformity_model(T, sq, rows, 2.0)
+    S2, pairs2, n2, uni2, cells = gm.uniformity_model(T, sq, rows, 2.0, cells=(16, 64))
+    assert (S2, pairs2, n2, uni2) == (S, pairs, n, uni) and len(cells) == len(gm.live_cells(139, 16, 64)) == 4 * 3 + 4 * 2 + 1
+    assert abs(sum(cells) - S) <= 1e-12 * S and cells[-1] > 0
+    X = gm.unit_rows(T, sq, rows).astype(np.float64)                         # cell (tile 5, chunk 2) by its definition
+    want = sum(np.exp(4.0 * (X[p] @ X[q] - 1.0)) for p in range(80, 96) for q in range(128, 139))
+    assert abs(cells[gm.live_cells(139, 16, 64).index((5, 2))] - want) <= 1e-12 * want
+
+
 # --------------------------------------------------------------------------- argument errors before the device is needed
+def test_the_temperature_just_past_the_limit_is_refused():
+    from elimrec_amd import ops
+    T, sq, rows = torch.zeros(8, 4), torch.zeros(8), torch.zeros(3, dtype=torch.int32)
+    for bad in (8.0000001, float(np.nextafter(8.0, 9.0)), np.float64(8.0000001), float("inf")):
+        with pytest.raises(ValueError, match="0 < t <= 8"):
+            ops.uniformity_sum(T, sq, rows, t=bad)
+    with pytest.raises(RuntimeError, match="HIP device tensor"):             # t = 8 passes the check; the tensors are refused next
+        ops.uniformity_sum(T, sq, rows, t=8.0)
+
+
 def test_ops_argument_errors_fire_without_a_gpu():
     from elimrec_amd import ops
     T, sq, rows = torch.zeros(8, 4), torch.zeros(8), torch.zeros(3, dtype=torch.int32)

@@ -8,7 +8,28 @@ the slope 2 t of the exponent, plus 2 ulp each for expf and for the fp32 roundin
 within that, so the mean's is; the float64 sum adds nothing visible.
 Gram: the products of the fp32 unit rows are exact in float64, so only the order of n additions differs from the model's:
 |dG_ab| <= n 2^-52 sum |x^_a x^_b|, likewise for m.
-Alignment: twice the cosine's error, (d + 4) 2^-22."""
+Alignment: twice the cosine's error, (d + 4) 2^-22.
+
+The cell grid of uniformity_sum (tiles of TILE = 64 query positions x chunks of CHUNK = 2048 candidate positions, only the live
+cells launched, decoded from blockIdx.x through 32 (g nc - g (g - 1) / 2)) is trivial up to two chunks. The smallest list at which
+its arithmetic shows, with today's constants:
+  g (g - 1) / 2 is not 0              n = 2 CHUNK + 1 = 4097   (a tile in chunk-row g = 2)
+  more than one live chunk at g >= 1  n = 2 CHUNK + 1 = 4097   (nc = 3: chunk-row 1 meets the chunks 1 and 2)
+  a reduce thread adds a second cell  n = 3 CHUNK + 1 = 6145   (289 cells; 192 at n = 3 CHUNK)
+All three hold from n = 6145 on, but there chunk-row g = 3 is a single tile of a single position, which holds no pair, so nothing
+it computes can be seen. The multi-chunk tests use n = 3 CHUNK + TILE + 1 = 6209: nc = 4, 98 tiles, 290 live cells, and chunk-row 3
+holds a full tile (a pair to see) and a second tile (within / live is not 0 there). At that n the per-cell probes run the general
+form (d = 4) and the register forms d = 64 (SR = 64) and d = 128 (SR = 32); the dense lists run d = 32 (SR = 64), d = 68 (general,
+SR = 16) and d = 128. d = 256 stays at one chunk.
+Not reachable: the last cell (tile 97, chunk 3) is launched and has its float64 in the workspace, but its tile is the one position
+n - 1 with nothing behind it -- it can only be required to add 0 (gm.live_cells lists it, brute force over the pairs does not:
+tests/test_geometry_cpu.py). pairs is n_valid (n_valid - 1) / 2 and not a count of the terms added, so a term taken with q <= p
+cannot show in the counts; it shows as 2 S with one pair in the list.
+Gram: the (bi <= bj) decode of blockIdx.y runs nb = 1, 2, 4 in test_gram_sizes and nb = 3 (d = 132: a last block of 4 columns;
+d = 192: full blocks) over 2 and 3 segments in test_gram_three_column_blocks."""
+import functools
+import time
+
 import numpy as np
 import pytest
 import torch
@@ -144,6 +165,159 @@ def test_uniformity_invariance(d):
     assert np.float64(c[0]).tobytes() == np.float64(e[0]).tobytes() and c[1:3] == e[1:3]
 
 
+# --------------------------------------------------------------------------- uniformity: the cell grid beyond two chunks
+@functools.lru_cache(maxsize=None)
+def _cell_probes(n, TILE, CHUNK):
+    """[(tile, chunk, [(p, q), ...])] over gm.live_cells(n): position pairs p < q with p in the tile and q in the chunk, at the first
+    and last position of each (all the corners that have p < q); in the diagonal cell also q = p + 1 inside the tile, q = the
+    first position of the next tile against the tile's first and its last position, while that tile lies in the same chunk."""
+    out = []
+    for i, c in gm.live_cells(n, TILE, CHUNK):
+        p_lo, p_hi = i * TILE, min((i + 1) * TILE, n) - 1
+        q_lo, q_hi = c * CHUNK, min((c + 1) * CHUNK, n) - 1
+        probes = [(p, q) for p in (p_lo, p_hi) for q in (q_lo, q_hi) if p < q]
+        if c == i * TILE // CHUNK:
+            probes += [(p, q) for p, q in ((p_lo, p_lo + 1), (p_lo, p_hi + 1), (p_hi, p_hi + 1)) if p < q <= q_hi]
+        assert all(p // TILE == i and q // CHUNK == c and p < q < n for p, q in probes)
+        out.append((i, c, sorted(set(probes))))
+    return out
+
+
+def _one_pair_list(n, d):
+    """A resident list of n entries, all -1, its NaN-filled workspace and the call that puts two ids in and takes them out."""
+    from elimrec_amd import ops
+    rows = torch.full((n,), -1, dtype=torch.int32, device=DEV)
+    ws = torch.empty(ops.uniformity_workspace(n, d), dtype=torch.uint8, device=DEV)
+
+    def run(table, norms, entries, t):
+        for p, r in entries:
+            rows[p] = r
+        ws.fill_(255)                                                        # NaN in every cell: one left unwritten reaches S
+        got = ops.uniformity_sum(table, norms, rows, t, workspace=ws)
+        for p, _ in entries:
+            rows[p] = -1
+        return got
+    return run
+
+
+@pytest.mark.parametrize("d", [4, 64, 128])
+def test_uniformity_one_pair_in_every_cell(d):
+    """n = 3 CHUNK + TILE + 1 (6209: nc = 4, 290 live cells), the list all -1 but two entries p < q placed in one live cell, for every
+    live cell and every probe of _cell_probes: S is that one term. n is the smallest list at which g (g - 1) / 2 is not 0, a
+    chunk-row g >= 1 has more than one live chunk, a reduce thread adds a second cell AND chunk-row g = 3 holds a pair and a second
+    tile (the first three hold from 3 CHUNK + 1 = 6145 on: the module's docstring). A cell that is dropped gives S = 0 (NaN where it
+    was never written), one run twice 2 S, a term taken with q <= p 2 S as well. The last cell (tile 97, chunk 3) holds no pair."""
+    TILE, CHUNK, _ = _consts()
+    n, t = 3 * CHUNK + TILE + 1, 2.0
+    T = _rows(64, d, 1200 + d)
+    sq = gm.sqnorms(T)
+    X = gm.unit_rows(T, sq, np.arange(64)).astype(np.float64)
+    table, norms, run = _t(T), _t(sq), _one_pair_list(n, d)
+    probes = _cell_probes(n, TILE, CHUNK)
+    assert len(probes) == 290 and [(i, c) for i, c, pq in probes if not pq] == [((n - 1) // TILE, (n - 1) // CHUNK)]
+    corners = {(p - i * TILE, q - c * CHUNK) for i, c, pq in probes for p, q in pq}
+    assert corners >= {(0, 0), (0, CHUNK - 1), (TILE - 1, 0), (TILE - 1, CHUNK - 1)}
+    k, worst, start = 0, 0.0, time.perf_counter()
+    for i, c, pq in probes:
+        for p, q in pq:
+            a, b = k % 64, (7 * k + 3) % 64                                  # two different rows of the table (6 k + 3 is odd)
+            k += 1
+            S, pairs, n_valid = run(table, norms, ((p, a), (q, b)), t)
+            want = 2.0 * t * (float(X[a] @ X[b]) - 1.0)
+            assert (pairs, n_valid) == (1, 2), (i, c, p, q, pairs, n_valid)
+            assert S > 0 and abs(np.log(S) - want) <= _tol(t, d), (i, c, p, q, S, np.exp(want))
+            worst = max(worst, abs(np.log(S) - want))
+    print("one pair per cell d=%d: %d launches over %d cells in %.2f s, worst |log S - want| %.3g, tol %.3g"
+          % (d, k, len(probes), time.perf_counter() - start, worst, _tol(t, d)))
+
+
+def test_uniformity_entries_that_are_no_pair_and_equal_ids_that_are():
+    """The same n at d = 4. One valid entry (p == q) belongs to no cell's strict triangle: pairs = 0, S = 0 exactly -- every one of
+    the 290 cells, the pairless last one too, writes its 0 over the NaN -- and a NaN value. Two entries with the SAME id at different
+    positions are a pair: S = 1 within the tolerance, in every cell."""
+    from elimrec_amd import ops
+    TILE, CHUNK, _ = _consts()
+    n, t, d = 3 * CHUNK + TILE + 1, 2.0, 4
+    T = _rows(64, d, 1300)
+    sq = gm.sqnorms(T)
+    table, norms, run = _t(T), _t(sq), _one_pair_list(n, d)
+    for p in sorted({i * TILE for i in range((n + TILE - 1) // TILE)} | {c * CHUNK - 1 for c in range(1, 4)} | {n - 2, n - 1}):
+        S, pairs, n_valid = run(table, norms, ((p, p % 64),), t)
+        assert (S, pairs, n_valid) == (0.0, 0, 1) and np.isnan(ops.uniformity_value(S, pairs)), (p, S, pairs, n_valid)
+    for k, (i, c, pq) in enumerate(_cell_probes(n, TILE, CHUNK)):
+        if pq:
+            p, q = pq[k % len(pq)]
+            S, pairs, n_valid = run(table, norms, ((p, k % 64), (q, k % 64)), t)
+            assert (pairs, n_valid) == (1, 2) and S > 0 and abs(np.log(S)) <= _tol(t, d), (i, c, p, q, S)
+
+
+def _dense_list(n, d, TILE, seed):
+    """(T, rows): every entry valid, the row at POSITION p one of 7 fixed random unit directions, u[p // TILE % 7], plus 0.05-scaled
+    Gaussian noise, times a scale in [0.5, 3]; the positions' rows lie in the table in a random order, so rows is a permutation."""
+    rng = np.random.default_rng(seed)
+    u = rng.standard_normal((7, d))
+    u /= np.linalg.norm(u, axis=1, keepdims=True)
+    x = (u[np.arange(n) // TILE % 7] + 0.05 * rng.standard_normal((n, d))) * rng.uniform(0.5, 3.0, (n, 1))
+    rows = rng.permutation(n)
+    T = np.empty((n, d), dtype=np.float32)
+    T[rows] = x.astype(np.float32)
+    return T, rows
+
+
+@pytest.mark.parametrize("d,t", [(32, 2.0), (32, 8.0), (32, 0.5), (68, 2.0), (128, 2.0)])
+def test_uniformity_dense_list_whose_cells_differ(d, t):
+    """n = 3 CHUNK + TILE + 1, every entry valid, against the float64 model (an n^2 product). With i.i.d. rows every cell has
+    nearly the same sum and a cell computed twice in place of another would move S by less than the tolerance; here a tile's rows
+    share one of 7 directions, so the cells differ. That is asserted on the model's cell sums, over all pairs of cells A, B:
+      |A - B| > 100 tol max(A, B) for at least 90 %: the two are far outside each other's rounding error;
+      |A - B| > 2 tol S for at least 80 %: B in place of A moves log S by more than 2 tol, which the kernel's own error (<= tol)
+      cannot bring back inside tol. (A mean cell is S / 290 = 3.4e-3 S and tol is 5e-6 .. 7e-5, so a few per cent between two cells
+      are enough; cells of the same direction and chunk differ by their noise alone and make up the rest.)"""
+    TILE, CHUNK, _ = _consts()
+    n = 3 * CHUNK + TILE + 1
+    T, rows = _dense_list(n, d, TILE, 500 + d)
+    sq = gm.sqnorms(T)
+    wS, wpairs, wn, wuni, cells = gm.uniformity_model(T, sq, rows, t, cells=(TILE, CHUNK))
+    cells, tol = np.asarray(cells), _tol(t, d)
+    assert cells.size == 290 and wn == n
+    upper = np.triu_indices(cells.size, 1)
+    diff = np.abs(cells[:, None] - cells[None, :])[upper]
+    apart, seen = (diff > 100 * tol * np.maximum(cells[:, None], cells[None, :])[upper]).mean(), (diff > 2 * tol * wS).mean()
+    print("dense d=%d t=%g: cell pairs apart by > 100 tol of the larger: %.3f, by > 2 tol S: %.3f" % (d, t, apart, seen))
+    assert apart >= 0.9 and seen >= 0.8
+    table, norms = _t(T), _t(sq)
+    a, b = _uni(T, sq, rows, t, table=table, norms=norms), _uni(T, sq, rows, t, table=table, norms=norms)
+    print("dense d=%d t=%g: got %.12g want %.12g diff %.3g tol %.3g" % (d, t, a[3], wuni, abs(a[3] - wuni), tol))
+    assert a[1:3] == (wpairs, wn) and abs(a[3] - wuni) <= tol
+    assert np.float64(a[0]).tobytes() == np.float64(b[0]).tobytes() and a[1:3] == b[1:3]      # two calls: the same bits
+    r = _uni(T, sq, rows[::-1].copy(), t, table=table, norms=norms)
+    assert r[1:3] == a[1:3] and abs(r[0] - a[0]) <= a[1] * 2.0 ** -52 * a[0]
+
+
+def test_temperature_limits_on_the_device():
+    """t = 8 (GEOMETRY_MAX_T) is taken; the library itself refuses a t past it, 0 and NaN before it writes anything."""
+    from elimrec_amd import _lib, ops
+    TILE, _, _ = _consts()
+    n = TILE + 1
+    T = _rows(n, 4, 8)
+    sq = gm.sqnorms(T)
+    assert ops.GEOMETRY_MAX_T == 8.0
+    _check_uni(T, sq, np.arange(n), 8.0)
+    table, norms, rows = _t(T), _t(sq), _t(np.arange(n, dtype=np.int32))
+    S = torch.full((1,), -7.0, dtype=torch.float64, device=DEV)
+    counts = torch.full((2,), -7, dtype=torch.int64, device=DEV)
+    ws = torch.empty(ops.uniformity_workspace(n, 4), dtype=torch.uint8, device=DEV)
+    lib = _lib.load()
+    for bad in (8.0000001, float(np.nextafter(8.0, 9.0)), 0.0, -2.0, float("nan"), float("inf")):
+        rc = lib.elimrec_uniformity_sum(table.data_ptr(), table.stride(0), n, 4, norms.data_ptr(), 1, rows.data_ptr(), n, bad,
+                                        S.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws.numel(), ops._stream())
+        assert rc != 0 and b"0 < t <= 8" in lib.elimrec_last_error(), (bad, rc)
+        with pytest.raises(ValueError, match="0 < t <= 8"):
+            ops.uniformity_sum(table, norms, rows, bad)
+        torch.cuda.synchronize()
+        assert S.item() == -7.0 and counts.tolist() == [-7, -7]
+
+
 # --------------------------------------------------------------------------- Gram
 def _check_gram(T, sq, rows, table=None, norms=None):
     from elimrec_amd import ops
@@ -191,6 +365,34 @@ def test_gram_lists_and_forms(d):
     norms[:, 1] = sq
     G2, m2, _ = _check_gram(T, sq, rows, table=_t(wide)[1:1 + n_rows, 8:8 + d], norms=_t(norms)[:, 1])
     assert G2.tobytes() == G.tobytes() and m2.tobytes() == m.tobytes()       # the bits do not depend on the table's form
+
+
+@pytest.mark.parametrize("d", [132, 192])
+def test_gram_three_column_blocks(d):
+    """nb = 3 column blocks (d = 132: the last one 4 columns wide; d = 192: all full), 2 and 3 segments, a list with invalid
+    entries and rows without a norm: the six tiles (bi <= bj) of blockIdx.y. An element whose row and column lie in different blocks
+    is named on its own: only a tile decoded to the right (bi, bj), and mirrored, puts the model's value there."""
+    _, _, SEG = _consts()
+    n_rows = 90
+    T = _rows(n_rows, d, 400 + d, zero=(0, 17))
+    sq = gm.sqnorms(T)
+    rng = np.random.default_rng(11)
+    block = np.arange(d) // 64
+    assert block.max() == 2
+    for n in (SEG + 1, 2 * SEG + 3):
+        rows = rng.integers(0, n_rows, size=n)
+        rows[[3, 64, 500]] = -1
+        rows[[0, 65, SEG]] = [n_rows, n_rows + 1000, 2 ** 31 - 1]
+        G, m, n_valid = _check_gram(T, sq, rows)
+        assert 0 < n_valid < n - 6
+        wG, _, _, A, _ = gm.gram_model(T, sq, rows)
+        for bi in range(3):
+            for bj in range(3):
+                if bi != bj:
+                    sel = np.ix_(block == bi, block == bj)
+                    assert (np.abs(G[sel] - wG[sel]) <= n * 2.0 ** -52 * A[sel]).all(), "column blocks (%d, %d) at n = %d" % (bi, bj, n)
+                    # and the model's block is far from 0: a tile that was never written, or written elsewhere, would not pass
+                    assert np.abs(wG[sel]).max() > 1e6 * n * 2.0 ** -52 * A[sel].max()
 
 
 def test_torch_ops_return_what_the_ops_return():
