@@ -3,6 +3,8 @@
 The graph is the CSR q_ptr / q_nbr of the query side (row -> its neighbours on the other side). scipy.sparse forms A^T A from it with
 repeated edges kept (duplicates are summed, so an edge listed twice has weight 2 and c is the product count); the three scores are
 computed in float64 and rounded once to fp32; the order is a stable sort by (score descending, id ascending)."""
+import collections
+
 import numpy as np
 import scipy.sparse as sp
 
@@ -80,6 +82,68 @@ def topk(q_ptr, q_nbr, n_other, rows, K, measure):
         n = order.size
         idx[r, :n], val[r, :n], cnt[r, :n] = j[order], s[order], c[order]
     return idx, val, cnt
+
+
+def dense_groups(walk_of_rows, lds, cap, max_groups, threads=256):
+    """Which query positions each workgroup of the dense form serves (cooccur_dense_kernel): position p is a dense row when lds is
+    off or its walk is past `cap` = COOCCUR_SLOTS / 2; G = min(dense rows, max_groups) workgroups run, workgroup b takes the dense
+    positions p = b (mod G) in ascending order, `threads` of its residue's positions per pass of its outer loop. Returns a list of G
+    lists of (pass, position)."""
+    walk_of_rows = np.asarray(walk_of_rows, dtype=np.int64)
+    dense = ~((walk_of_rows <= cap) & bool(lds))
+    G = min(int(dense.sum()), int(max_groups))
+    return [[(int(p // G) // threads, int(p)) for p in range(b, dense.size, G) if dense[p]] for b in range(G)]
+
+
+Schedule = collections.namedtuple("Schedule", "cuts appended dropped longest ids")
+
+
+def dense_schedule(graph, q, K, measure, cap, users=16, entries=64):
+    """The bookkeeping of the dense form's pass 2 for query row q. graph: (q_ptr, q_nbr, o_ptr, o_nbr). The row's segment is walked
+    `users` neighbours at a time, `entries` entries of each neighbour's list per step; a candidate is claimed (with its whole count
+    c) at the first step that meets it, and appended to the running list if and only if its key (score, then the lower id) exceeds
+    the threshold read at the top of that step; after a step that leaves the list longer than cap - users * entries the list is
+    sorted and, holding at least K, cut to its K best, whose last key becomes the threshold. Returns Schedule(cuts, appended,
+    dropped by the threshold, the longest list met, the final list's K best ids).
+    Deterministic although the kernel is not: which lane wins a claim inside a step changes neither the candidate's count (pass 1
+    is complete), nor its key, nor the threshold it meets (read once per step), so it changes none of these numbers."""
+    q_ptr, q_nbr, o_ptr, o_nbr = (np.asarray(x, dtype=np.int64) for x in graph)
+    deg = np.diff(q_ptr)
+    seg = q_nbr[q_ptr[q]:q_ptr[q + 1]]
+    lists = [o_nbr[o_ptr[u]:o_ptr[u + 1]] for u in seg]
+    c = np.zeros(deg.size, dtype=np.int64)
+    for held in lists:
+        np.add.at(c, held, 1)
+    score = scores(c, np.full(deg.size, deg[q]), deg, measure)
+    limit = cap - users * entries
+    claimed, kept, thr = {int(q)}, [], None
+    cuts = appended = dropped = longest = 0
+    for e0 in range(0, len(lists), users):
+        f, batch = 0, lists[e0:e0 + users]
+        while True:
+            top = thr
+            for held in batch:
+                for j in held[f:f + entries].tolist():
+                    if j in claimed:
+                        continue
+                    claimed.add(j)
+                    key = (float(score[j]), -j)
+                    if top is None or key > top:
+                        kept.append(key)
+                        appended += 1
+                    else:
+                        dropped += 1
+            f += entries
+            longest = max(longest, len(kept))
+            if len(kept) > limit:
+                cuts += 1
+                kept.sort(reverse=True)
+                if len(kept) >= K:
+                    kept, thr = kept[:K], kept[K - 1]
+            if not any(f < held.size for held in batch):
+                break
+    kept.sort(reverse=True)
+    return Schedule(cuts, appended, dropped, longest, [-k[1] for k in kept[:K]])
 
 
 def report_rows(co_idx, co_val, item_counts, space_lists):

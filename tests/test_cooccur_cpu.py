@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import cooccur_cases as cc
 import cooccur_model as cm
 from helpers import build_model_from_fixture, load_golden
 
@@ -192,6 +193,129 @@ def test_report_arguments_and_the_switch():
     src = inspect.getsource(main.Net.__init__)
     assert "--co_report needs the whole cached item table on one rank: it is single-GPU" in src
     assert "[co-neighbours]" in inspect.getsource(main.Net)
+
+
+# --------------------------------------------------------------------------- the inputs of tests/test_cooccur_dense_gpu.py
+# Conditions on the graphs of tests/cooccur_cases.py, not on the kernel: each case reaches the mechanism it is named for.
+def _schedule(name, K, measure):
+    case = cc.case(name)
+    return cm.dense_schedule(cc.csrs(case), case.rows[0], K, measure, cc.cap(), cc.USERS_PER_PASS, cc.ENTRIES_PER_STEP)
+
+
+def _n_candidates(case):
+    q_ptr, q_nbr, _, _ = cc.csrs(case)
+    B = cm.incidence(q_ptr, q_nbr, len(case.users))
+    C = (B[case.rows] @ B.T).toarray()
+    C[np.arange(len(case.rows)), case.rows] = 0
+    return (C > 0).sum(1)
+
+
+def test_the_schedule_model_on_a_small_list():
+    """Item 0 held by three users, walked 2 users at a time and 2 entries a step with a list of 7 (cut once longer than 3), K = 2,
+    "count"; c = 2 for items 1, 3, 4 and 1 for items 2, 5, 6. Users 0 and 1: step (1, 2 | 0, 5) appends 1, 2, 5; step (3, 4 | 1)
+    appends 3, 4 (1 is claimed): 5 kept, cut to ids 1 and 3, the threshold is (2, id 3); step (0 | -). User 2 alone: step (6, 3)
+    drops 6 (c = 1), 3 is claimed; step (0, 4): 4 is claimed."""
+    o_ptr, o_nbr = cm.csr_of([[1, 2, 3, 4, 0], [0, 5, 1], [6, 3, 0, 4]])
+    graph = cm.transpose_csr(o_ptr, o_nbr, 7) + (o_ptr, o_nbr)
+    s = cm.dense_schedule(graph, 0, 2, "count", 7, users=2, entries=2)
+    assert (s.cuts, s.appended, s.dropped, s.longest, s.ids) == (1, 5, 1, 5, [1, 3])
+    assert cm.topk(graph[0], graph[1], 3, [0], 2, "count")[0].tolist() == [s.ids]
+
+
+def test_dense_cases_put_several_rows_on_one_workgroup():
+    G, H = cc.groups(), cc.cap()
+    case = cc.case("many_rows")
+    walk = cc.walk_of_rows(case)
+    assert len(case.rows) > 2 * G and (walk > H).all() and len(set(case.rows)) == case.n_query < len(case.rows)
+    for lds in (True, False):
+        served = cm.dense_groups(walk, lds, H, G)
+        assert len(served) == G and max(len(s) for s in served) >= 3 and sum(len(s) for s in served) == len(case.rows)
+    print("many_rows: Q %d, n %d, edges %d, rows per workgroup %d..%d" % (len(case.rows), case.n_query, sum(map(len, case.users)),
+                                                                         min(map(len, served)), max(map(len, served))))
+    s = cm.dense_schedule(cc.csrs(case), case.rows[0], 65, "cosine", H, cc.USERS_PER_PASS, cc.ENTRIES_PER_STEP)
+    assert s.cuts >= 1 and s.longest <= H                                    # every row leaves a raised threshold behind
+
+    case = cc.case("interleaved")
+    walk = cc.walk_of_rows(case)
+    assert (walk > H).tolist() == [True, False, False, True, False, False, True, False] and (walk > 1).all()
+    served = cm.dense_groups(walk, True, H, G)
+    assert [[p for _, p in s] for s in served] == [[0, 3, 6], [], []]
+    assert [len(s) for s in cm.dense_groups(walk, False, H, G)] == [1] * 8
+    q_ptr, q_nbr, _, _ = cc.csrs(case)
+    lists = cm.topk(q_ptr, q_nbr, len(case.users), [0, 1, 2], H + 200, "count")[0]
+    shared = [np.intersect1d(lists[a][lists[a] >= 0], lists[b][lists[b] >= 0]).size for a, b in ((0, 1), (1, 2))]
+    assert min(shared) > 100                                                 # a counter left dirty by one row is met by the next
+    for q in range(3):
+        s = cm.dense_schedule(cc.csrs(case), q, 5, "jaccard", H, cc.USERS_PER_PASS, cc.ENTRIES_PER_STEP)
+        assert s.cuts >= 1 and s.longest <= H
+    print("interleaved: walks %s, shared candidates %s" % (walk.tolist(), shared))
+
+    case = cc.case("second_pass")
+    walk = cc.walk_of_rows(case)
+    at = np.flatnonzero(walk > H).tolist()
+    served = cm.dense_groups(walk, True, H, G)
+    assert len(case.rows) > cc.CO_THREADS and len(at) == 1 and at[0] >= cc.CO_THREADS and served == [[(1, at[0])]]
+    assert (walk == 0).sum() == 12 and len(cm.dense_groups(walk, False, H, G)) == len(case.rows)
+    print("second_pass: Q %d, the dense row at %d, walks up to %d elsewhere" % (len(case.rows), at[0], walk[walk <= H].max()))
+
+
+@pytest.mark.parametrize("K", [1, 64, 256])
+def test_dense_cases_cut_their_list_as_named(K):
+    H, per = cc.cap(), cc.USERS_PER_PASS * cc.ENTRIES_PER_STEP
+    for name in ("rising", "falling", "flat_desc", "flat_asc"):
+        case = cc.case(name)
+        assert cc.walk_of_rows(case).tolist() == [5 * cc.USERS_PER_PASS * (cc.ENTRIES_PER_STEP + 1)] and _n_candidates(case).tolist() == [5 * per]
+    # scores strictly rising / falling from block to block in arrival order, c = 1 everywhere
+    for name, sign in (("rising", 1), ("falling", -1)):
+        case = cc.case(name)
+        q_ptr = cc.csrs(case)[0]
+        where, deg = cc.block_of(case), np.diff(q_ptr)
+        for measure in ("cosine", "jaccard"):
+            per_block = [np.unique(cm.scores(1, deg[0], deg[where == t], measure)) for t in range(5)]
+            assert all(b.size == 1 for b in per_block) and (sign * np.diff(np.concatenate(per_block)) > 0).all()
+    for measure in ("cosine", "jaccard"):
+        s = _schedule("rising", K, measure)
+        print("rising K=%d %s: %s" % (K, measure, s[:4]))
+        assert s.cuts >= 3 and s.dropped == 0 and s.appended == 5 * per and s.longest <= H
+        s = _schedule("falling", K, measure)
+        print("falling K=%d %s: %s" % (K, measure, s[:4]))
+        assert s.cuts == 1 and s.appended == 2 * per and s.dropped == 3 * per and s.longest <= H
+    s = _schedule("flat_desc", K, "count")
+    print("flat_desc K=%d: %s" % (K, s[:4]))
+    assert s.cuts >= 3 and s.dropped == 0 and s.longest <= H and s.ids == sorted(s.ids) and s.ids[0] == 1
+    s = _schedule("flat_asc", K, "count")
+    print("flat_asc K=%d: %s" % (K, s[:4]))
+    assert s.cuts == 1 and s.appended == 2 * per and s.dropped == 3 * per and s.longest <= H and s.ids == list(range(1, K + 1))
+
+
+def test_lds_cases_reach_the_table_and_list_edges():
+    S, H = cc.slots(), cc.cap()
+    case = cc.case("wrap")
+    q_ptr, q_nbr, _, _ = cc.csrs(case)
+    idx, _, cnt = cm.topk(q_ptr, q_nbr, 2, case.rows, H, "count")
+    keys = idx[0][idx[0] >= 0]
+    assert cc.walk_of_rows(case)[0] <= H and keys.size == 48 and set(cnt[0][:48].tolist()) == {1, 2} and case.rows[0] not in keys
+    # a host table under the kernel's rule (home slot id mod SLOTS, the next slot mod SLOTS when taken), in three insertion orders
+    for order in (keys, keys[::-1], np.sort(keys)):
+        table = {}
+        for j in order.tolist():
+            s = j % S
+            while s in table:
+                s = (s + 1) % S
+            table[s] = j
+        wrapped = [j for s, j in table.items() if s < j % S]
+        assert len(wrapped) >= 28 and set(table) == set(range(S - 4, S)) | set(range(44))
+    for name, n in (("full_list", [H - 1]), ("sort_sizes", [cc.SORT_SIZES[r] for r in cc.case("sort_sizes").rows])):
+        case = cc.case(name)
+        assert _n_candidates(case).tolist() == n and (cc.walk_of_rows(case) <= H).all()
+        print("%s: candidates %s, walks %s" % (name, n, cc.walk_of_rows(case).tolist()))
+    assert cc.walk_of_rows(cc.case("full_list")).tolist() == [H] and sorted(cc.SORT_SIZES) == [63, 64, 65, 128, 129, 1024, 1025]
+    # the same rows through the dense form (lds=False) stay within the list
+    for name in ("full_list", "sort_sizes", "wrap"):
+        case = cc.case(name)
+        for q in case.rows:
+            assert cm.dense_schedule(cc.csrs(case), q, 5, "count", H, cc.USERS_PER_PASS, cc.ENTRIES_PER_STEP).longest <= H
+    assert all(sum(map(len, cc.case(name).users)) < 40000 for name in cc.BUILDERS)
 
 
 def test_cooccur_entries_are_declared_bound_and_registered():
