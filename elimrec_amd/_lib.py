@@ -252,6 +252,14 @@ SIGNATURES = {
     "elimrec_cooccur_max_k": (c_i32, []),
     "elimrec_cooccur_groups": (c_i32, []),
     "elimrec_cooccur_rows_in_lds": (c_i32, [c_i64]),
+    "elimrec_neighbour_vote_topk": (c_i32, [c_ptr, c_ptr, c_i64, c_i32, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_i32, c_i32,
+                                            c_i32, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
+    "elimrec_vote_workspace": (c_size, [c_i64, c_i64]),
+    "elimrec_vote_slots": (c_i32, []),
+    "elimrec_vote_groups": (c_i32, []),
+    "elimrec_vote_max_k": (c_i32, []),
+    "elimrec_vote_frac_bits": (c_i32, []),
+    "elimrec_vote_rows_in_lds": (c_i32, [c_i64]),
     "elimrec_pick_hard_negatives": (c_i32, [c_ptr, c_i64, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_i64, c_ptr, c_i64, c_i32, c_i32,
                                             ctypes.POINTER(c_f32), c_ptr, c_ptr, c_i64, c_i32, c_ptr, c_ptr, c_ptr, c_ptr]),
     "elimrec_history_support": (c_i32, [c_ptr, c_i64, c_i64, c_i32, c_i32, c_ptr, c_i64, ctypes.POINTER(c_f32), c_ptr, c_ptr, c_i64,
@@ -402,6 +410,7 @@ class _Recording(object):
                              "elimrec_mmr_max_pool", "elimrec_mmr_rows_in_lds", "elimrec_calibrate_max_classes", "elimrec_kmeans_max_clusters", "elimrec_kmeans_segment",
                              "elimrec_geometry_tile", "elimrec_geometry_chunk", "elimrec_geometry_segment",
                              "elimrec_cooccur_slots", "elimrec_cooccur_max_k", "elimrec_cooccur_groups", "elimrec_cooccur_rows_in_lds",
+                             "elimrec_vote_slots", "elimrec_vote_groups", "elimrec_vote_max_k", "elimrec_vote_frac_bits", "elimrec_vote_rows_in_lds",
                              "elimrec_segment_plan_form",
                              "elimrec_comm_create", "elimrec_comm_destroy", "elimrec_comm_nranks") or name.startswith("elimrec_program_")
             setattr(self, name, self._wrap(fn, name) if res is c_i32 and not plain else fn)

@@ -8,7 +8,20 @@ from torch import nn
 
 from . import ops
 from .evaluator import ProxyEvaluator, UniEvaluator
-from .reports import AudienceReport, CalibrationReport, ClusterReport, CoNeighbourReport, DiversifyReport, EffectReport, GeometryReport, HistoryReport, ListReport, NeighbourReport, RankReport, SignificanceReport
+from .reports import AudienceReport, BaselineReport, CalibrationReport, ClusterReport, CoNeighbourReport, DiversifyReport, EffectReport, GeometryReport, HistoryReport, ListReport, NeighbourReport, RankReport, SignificanceReport
+
+
+
+def baseline_sources(value):
+    """--baseline_sources as a tuple of names: a list / tuple of strings, or the switch's text "[co,fused,v]" (names unquoted)."""
+    if isinstance(value, str):
+        text = value.strip()
+        if not (text.startswith("[") and text.endswith("]")):
+            raise ValueError("baseline_sources is a list like [co,fused,v], got %r" % (value,))
+        value = [x.strip().strip("'\"") for x in text[1:-1].split(",")]
+    if not isinstance(value, (list, tuple)) or not value or any(not isinstance(x, str) or not x for x in value) or len(set(value)) != len(value):
+        raise ValueError("baseline_sources is a list of distinct names like [co,fused,v], got %r" % (value,))
+    return tuple(value)
 
 
 class BasicModel(nn.Module):
@@ -157,6 +170,29 @@ class BasicModel(nn.Module):
         if co_measure not in ops.COOCCUR_MEASURES:
             raise ValueError("co_measure is one of %s, got %r" % (", ".join(sorted(ops.COOCCUR_MEASURES)), co_measure))
         self.co_reporter = CoNeighbourReport(dataset, train, k_co, measure=co_measure, item_group_view=item_view) if k_co else None
+        # --baseline_report=K (CLI-only, default 0 = off): neighbour-vote baselines beside the model -- per --baseline_sources entry
+        # (default [co]: ItemKNN over the training graph under --baseline_measure=count|cosine|jaccard, default cosine; fused / a head
+        # letter: content-KNN in that space) the test users' top-K lists voted for by the --baseline_neighbours (default 50) nearest
+        # items of every train item: the evaluator's metrics, how full and how popular the lists are, how much of the model's own
+        # list they hold and their catalogue exposure, overall and per user group (reports.BaselineReport)
+        k_base = config["baseline_report"] if "baseline_report" in config else 0
+        if isinstance(k_base, bool) or not isinstance(k_base, int) or k_base < 0:
+            raise ValueError("baseline_report must be 0 (off) or the K of the baseline lists, got %r" % (k_base,))
+        sources = baseline_sources(config["baseline_sources"]) if "baseline_sources" in config else ("co",)
+        n_near = config["baseline_neighbours"] if "baseline_neighbours" in config else 50
+        if isinstance(n_near, bool) or not isinstance(n_near, int) or not 1 <= n_near <= ops.VOTE_MAX_K:
+            raise ValueError("baseline_neighbours must be an integer in [1, %d], got %r" % (ops.VOTE_MAX_K, n_near))
+        base_measure = str(config["baseline_measure"]) if "baseline_measure" in config else "cosine"
+        if base_measure not in ops.COOCCUR_MEASURES:
+            raise ValueError("baseline_measure is one of %s, got %r" % (", ".join(sorted(ops.COOCCUR_MEASURES)), base_measure))
+        self.baseline_reporter = None
+        if k_base:
+            for x in sources:        # (the model checks a head letter against its own heads at the first list)
+                if x not in ("co", "fused", "v", "a", "t"):
+                    raise ValueError("baseline_sources names 'co', 'fused' or a head letter (v, a, t), got %r" % (x,))
+            self.baseline_reporter = BaselineReport(dataset, train, dataset.get_user_test_dict(), config["topks"], metric=config["metric"],
+                                                    sources=sources, neighbours=n_near, measure=base_measure,
+                                                    group_view=config["group_view"], list_k=k_base)
         self.infonce_criterion = nn.CrossEntropyLoss()          # BasicModel.py:32
 
     def getFileName(self):

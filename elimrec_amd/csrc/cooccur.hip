@@ -22,18 +22,19 @@
 // 64-bit key: the order-preserving image of the fp32 score in the high word, ~id in the low word -- a larger key ranks earlier under
 // (score descending, id ascending), and keys are distinct because ids are. The keys (with c beside them) are gathered into a list
 // of COOCCUR_CAP = 2048 slots in LDS -- the LDS form's table holds at most that many -- and sorted by a bitonic network over the
-// next power of two, the empty key 0 behind every candidate. The dense form compares the FULL key against the K-th kept key: a key
+// next power of two, the empty key 0 behind every candidate (co_select.h, shared with vote.hip). The dense form compares the FULL key against the K-th kept key: a key
 // at or below it can never be listed; when the list could overflow it is sorted and cut to the K best, which raises that key. A row's
 // outputs therefore depend bit for bit on the graph, the row, K and the measure -- not on the arrival order, the form, Q, the row's
 // place in `rows` or the grid. No floating-point atomics.
 // A query id outside the side gives fillers; a neighbour id outside its side is skipped and never dereferenced.
 #include <cmath>
 #include "common.h"
+#include "co_select.h"
 
 namespace elimrec {
 
 constexpr int COOCCUR_SLOTS = 4096, COOCCUR_MAX_K = 256, COOCCUR_CAP = COOCCUR_SLOTS / 2, COOCCUR_GROUPS = 512;
-constexpr int CO_THREADS = 256, CO_STEP = 4;                 // CO_STEP: 2-hop entries a lane claims between two capacity checks
+constexpr int CO_STEP = 4;                                   // CO_STEP: 2-hop entries a lane claims between two capacity checks
 static_assert(COOCCUR_CAP >= 2 * CO_THREADS * CO_STEP && COOCCUR_CAP - CO_THREADS * CO_STEP >= COOCCUR_MAX_K, "the dense form's list");
 
 struct CoArgs {
@@ -54,47 +55,12 @@ __device__ __forceinline__ float co_score(int measure, int c, int64_t a, int64_t
     return (float)((double)c / (double)(a + b - (int64_t)c));
 }
 
-// (score, id) as one key: a larger key ranks earlier; 0 is no candidate (the image of a NaN no score takes)
-__device__ __forceinline__ uint64_t co_key(float score, int id) {
-    const uint32_t bits = __float_as_uint(score);
-    const uint32_t hi = (bits & 0x80000000u) ? ~bits : (bits | 0x80000000u);
-    return ((uint64_t)hi << 32) | (uint32_t)~(uint32_t)id;
-}
-__device__ __forceinline__ float co_key_score(uint64_t key) {
-    const uint32_t hi = (uint32_t)(key >> 32);
-    return __uint_as_float((hi & 0x80000000u) ? (hi ^ 0x80000000u) : ~hi);
-}
-__device__ __forceinline__ int co_key_id(uint64_t key) { return (int)~(uint32_t)key; }
-
 __device__ __forceinline__ void co_fillers(const CoArgs &a, int64_t qi, int from, int tid) {
     for (int k = from + tid; k < a.K; k += CO_THREADS) {
         a.idx[qi * a.K + k] = -1;
         if (a.val) a.val[qi * a.K + k] = -__builtin_huge_valf();
         if (a.cnt) a.cnt[qi * a.K + k] = 0;
     }
-}
-
-// the whole workgroup sorts key[0, n) (c beside it) descending: empty keys over [n, m), m the next power of two, a bitonic network
-// over m. Ends with a barrier. n <= COOCCUR_CAP.
-__device__ __forceinline__ void co_sort(uint64_t *key, int *c, int n, int tid) {
-    int m = 64;
-    while (m < n) m <<= 1;
-    for (int i = n + tid; i < m; i += CO_THREADS) { key[i] = 0; c[i] = 0; }
-    __syncthreads();
-    for (int k = 2; k <= m; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < m; i += CO_THREADS) {
-                const int l = i ^ j;
-                if (l > i) {
-                    const uint64_t x = key[i], y = key[l];
-                    if (((i & k) == 0) ? x < y : x > y) {
-                        key[i] = y; key[l] = x;
-                        const int cx = c[i]; c[i] = c[l]; c[l] = cx;
-                    }
-                }
-            }
-            __syncthreads();
-        }
 }
 
 // the sorted list's K best to row qi of the outputs, fillers behind them

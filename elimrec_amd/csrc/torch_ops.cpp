@@ -39,6 +39,9 @@
 //       [Q x K]: per query row the K rows of its side with the largest co-occurrence score ("count", "cosine", "jaccard") over the
 //       bipartite graph the two CSRs give, (score descending, id ascending), -1 / -inf / 0 fillers; both CSRs and the rows are checked
 //       on the host (csrc/cooccur.hip)
+//   neighbour_vote_topk(nbr_idx i32[n x Kn], nbr_val f32[n x Kn], hist_ptr i64[R + 1], hist_items i32, excl_ptr i64[R + 1]?, excl_items i32?,
+//       users i64[B], K) -> (idx i32, val f32, cnt i32) [B x K]: the K items the neighbour lists of each user's history vote for, the
+//       history's own ids and excl's left out; fixed-point int64 sums, the overflow bound and the form rule on the host (csrc/vote.hip)
 //   pick_hard_negatives(user_table f32[U x blocks*d], user_sqnorm f32[U x blocks], item_table f32[I x blocks*d], item_sqnorm, weights
 //     float[blocks], users i64[n], cands i32[n x M]) -> (neg i64, pos i32, score f32) [n]: per triplet the listed candidate with the largest
 //     sum_b w_b cos_b(u, i), the lowest column among equals; -1 / -1 / -inf without one (csrc/hardneg.hip)
@@ -63,6 +66,7 @@
 #include <torch/library.h>
 
 #include <algorithm>
+#include <cmath>
 #include <string>
 #include <vector>
 
@@ -711,6 +715,52 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> cooccur_topk(const at::Tensor &q_
     return {idx, val, cnt};
 }
 
+// ---- neighbour votes: per user the K items the neighbour lists of the user's history vote for (csrc/vote.hip)
+std::tuple<at::Tensor, at::Tensor, at::Tensor> neighbour_vote_topk(const at::Tensor &nbr_idx, const at::Tensor &nbr_val, const at::Tensor &hist_ptr,
+                                                                   const at::Tensor &hist_items, const c10::optional<at::Tensor> &excl_ptr,
+                                                                   const c10::optional<at::Tensor> &excl_items, const at::Tensor &users, int64_t K) {
+    need(nbr_idx, "nbr_idx", at::kInt, 2); need(nbr_val, "nbr_val", at::kFloat, 2); need(hist_ptr, "hist_ptr", at::kLong, 1);
+    need(hist_items, "hist_items", at::kInt, 1); need(users, "users", at::kLong, 1);
+    TORCH_CHECK(K >= 1 && K <= elimrec_vote_max_k(), "elimrec::neighbour_vote_topk: 1 <= K <= ", elimrec_vote_max_k(), ", got ", K);
+    TORCH_CHECK(nbr_idx.sizes() == nbr_val.sizes() && nbr_idx.size(1) >= 1, "elimrec::neighbour_vote_topk: nbr_idx and nbr_val are both [n x Kn], Kn >= 1");
+    TORCH_CHECK(excl_ptr.has_value() == excl_items.has_value(), "elimrec::neighbour_vote_topk: excl_ptr and excl_items come together");
+    const at::Tensor li = nbr_idx.contiguous(), lv = nbr_val.contiguous(), hp = hist_ptr.contiguous(), hi = hist_items.contiguous(), u = users.contiguous();
+    const int64_t n = li.size(0), Kn = li.size(1), n_hist = hp.numel() - 1, B = u.numel();
+    TORCH_CHECK(n_hist >= 0, "elimrec::neighbour_vote_topk: hist_ptr needs at least one entry");
+    checked_csr(hp, hi, n_hist, "neighbour_vote_topk", "hist_ptr", "hist_items");
+    checked_ids(u, n_hist, true, "neighbour_vote_topk", "users", "the histories have", "segments");
+    at::Tensor ep, ei;
+    if (excl_ptr.has_value()) {
+        need(*excl_ptr, "excl_ptr", at::kLong, 1); need(*excl_items, "excl_items", at::kInt, 1);
+        ep = excl_ptr->contiguous(); ei = excl_items->contiguous();
+        TORCH_CHECK(ep.numel() == n_hist + 1, "elimrec::neighbour_vote_topk: hist_ptr and excl_ptr name the same users: ", n_hist + 1, " and ",
+                    ep.numel(), " entries");
+        checked_csr(ep, ei, n_hist, "neighbour_vote_topk", "excl_ptr", "excl_items");
+    }
+    at::Tensor idx = at::empty({B, K}, li.options()), val = at::empty({B, K}, lv.options()), cnt = at::empty({B, K}, li.options());
+    if (B == 0) return {idx, val, cnt};
+    // the host's bounds: the int64 sums cannot overflow, a user's votes stay below the count's mark bit
+    const at::Tensor len = hp.slice(0, 1) - hp.slice(0, 0, n_hist);
+    const int64_t longest = n_hist ? len.max().item<int64_t>() : 0;
+    const double max_abs = li.numel() ? at::where(at::isfinite(lv), lv.abs(), at::zeros_like(lv)).max().item<double>() : 0.0;
+    const double q = std::ceil(max_abs * (double)(1 << elimrec_vote_frac_bits()));
+    TORCH_CHECK_VALUE(q < 4.0e18 && (unsigned __int128)(uint64_t)q * (unsigned __int128)longest * (unsigned __int128)Kn < ((unsigned __int128)1 << 62),
+                      "elimrec::neighbour_vote_topk: the int64 sums could overflow: ceil(", max_abs, " * 2^24) x ", longest,
+                      " (the longest history) x ", Kn, " (Kn) >= 2^62");
+    TORCH_CHECK_VALUE((unsigned __int128)longest * (unsigned __int128)Kn < ((unsigned __int128)1 << 30),
+                      "elimrec::neighbour_vote_topk: ", longest, " (the longest history) x ", Kn, " (Kn) votes of one user, fewer than 2^30 are taken");
+    at::Tensor V = len * (Kn + 1);
+    if (excl_ptr.has_value()) V = V + (ep.slice(0, 1) - ep.slice(0, 0, n_hist));
+    const int64_t n_dense = V.index_select(0, u).gt(elimrec_vote_slots() / 2).sum().item<int64_t>();
+    at::Tensor ws = at::zeros({(int64_t)std::max<size_t>(16, elimrec_vote_workspace(n_dense, n))}, li.options().dtype(at::kByte));
+    check(elimrec_neighbour_vote_topk(li.data_ptr<int32_t>(), lv.data_ptr<float>(), n, (int)Kn, hp.data_ptr<int64_t>(), hi.data_ptr<int32_t>(), n_hist,
+                                      excl_ptr.has_value() ? ep.data_ptr<int64_t>() : nullptr, excl_ptr.has_value() ? ei.data_ptr<int32_t>() : nullptr,
+                                      excl_ptr.has_value() ? n_hist : 0, u.data_ptr<int64_t>(), B, (int)K, 1, 1, n_dense, idx.data_ptr<int32_t>(),
+                                      val.data_ptr<float>(), cnt.data_ptr<int32_t>(), ws.data_ptr(), (size_t)ws.numel(), cur_stream()),
+          "neighbour_vote_topk");
+    return {idx, val, cnt};
+}
+
 // ---- hard-negative pick: per triplet the best of M candidates over the tables' column blocks
 std::tuple<at::Tensor, at::Tensor, at::Tensor> pick_hard_negatives(const at::Tensor &user_table, const at::Tensor &user_sqnorm,
                                                                    const at::Tensor &item_table, const at::Tensor &item_sqnorm,
@@ -943,6 +993,7 @@ TORCH_LIBRARY(elimrec, m) {
     m.def("uniformity_sum(Tensor table, Tensor sqnorm, Tensor rows, float t) -> (Tensor, Tensor)");
     m.def("row_gram(Tensor table, Tensor sqnorm, Tensor rows) -> (Tensor, Tensor, Tensor)");
     m.def("cooccur_topk(Tensor q_ptr, Tensor q_nbr, Tensor o_ptr, Tensor o_nbr, Tensor rows, int K, str measure) -> (Tensor, Tensor, Tensor)");
+    m.def("neighbour_vote_topk(Tensor nbr_idx, Tensor nbr_val, Tensor hist_ptr, Tensor hist_items, Tensor? excl_ptr, Tensor? excl_items, Tensor users, int K) -> (Tensor, Tensor, Tensor)");
     m.def("pick_hard_negatives(Tensor user_table, Tensor user_sqnorm, Tensor item_table, Tensor item_sqnorm, float[] weights, Tensor users, "
           "Tensor cands) -> (Tensor, Tensor, Tensor)");
     m.def("history_support(Tensor table, Tensor sqnorm, float[] weights, Tensor users, Tensor lists, Tensor hist_ptr, Tensor hist_items, int top, "
@@ -986,6 +1037,7 @@ TORCH_LIBRARY_IMPL(elimrec, CUDA, m) {
     m.impl("uniformity_sum", &uniformity_sum);
     m.impl("row_gram", &row_gram);
     m.impl("cooccur_topk", &cooccur_topk);
+    m.impl("neighbour_vote_topk", &neighbour_vote_topk);
     m.impl("pick_hard_negatives", &pick_hard_negatives);
     m.impl("history_support", &history_support);
     m.impl("bootstrap_means", &bootstrap_means);

@@ -53,6 +53,8 @@ def classes_from_clusters(assign, n_clusters):
     return np.where(a < 0, np.int32(n_clusters), a).astype(np.int32)
 
 
+KNN_LIST_BLOCK = 4096                    # items per launch when neighbour_lists builds the lists of the whole catalogue
+KnnLists = collections.namedtuple("KnnLists", ("ids", "scores", "votes"))
 HistorySupport = collections.namedtuple("HistorySupport", ("items", "history", "scores", "count", "mean"))
 
 
@@ -1475,6 +1477,104 @@ class EliMRec(BasicModel):
         """co_items over the users: the k users who took the most items in common with each given user. Needs no cached tables: it
         works on an untrained model."""
         return self._co("user", user_ids, k, measure)
+
+    def _knn_source(self, source, neighbours, measure):
+        """The checks neighbour_lists / recommend_knn / BaselineReport share, before anything touches the device: -> neighbours."""
+        if isinstance(neighbours, bool) or not isinstance(neighbours, (int, np.integer)) or not 1 <= neighbours <= ops.VOTE_MAX_K:
+            raise ValueError("neighbours must be an integer in [1, %d], got %r" % (ops.VOTE_MAX_K, neighbours))
+        ops._cooccur_measure("neighbour_lists", measure)
+        if source != "co":
+            if not (source == "fused" or (isinstance(source, str) and source in self._mods)):
+                raise ValueError("source must be 'co', 'fused' or one of this model's heads %s, got %r"
+                                 % ("/".join(self._mods) or "(none)", source))
+        return int(neighbours)
+
+    @torch.no_grad()
+    def neighbour_lists(self, source="co", neighbours=50, measure="cosine"):
+        """The `neighbours` nearest items of EVERY item as the ops.NeighbourLists [num_items x neighbours] neighbour_vote_topk
+        takes, built in blocks of KNN_LIST_BLOCK items and kept on the device. source "co": the co-interaction neighbours of the
+        training graph under `measure` (co_neighbours_device; no cached tables are needed, so this works on an untrained model),
+        kept per (neighbours, measure); "fused" or a head letter of self._mods: the cosine neighbours in that space of the cached
+        tables (neighbours_device; `measure` is not used), kept per table version. Errors as similar_items / co_items."""
+        neighbours = self._knn_source(source, neighbours, measure)
+        dev = self._require_gpu()
+        kept = self.__dict__.setdefault("_knn_lists", {})
+        if source == "co":
+            key, version = ("co", neighbours, measure), 0
+        else:
+            self._cached_tables("similar_items() / similar_users() need", "neighbour lists need the whole cached tables on this rank; "
+                                "the tables are item-sharded (lean / multi-rank evaluation)")
+            key, version = (source, neighbours), getattr(self, "_table_version", 0)
+        hit = kept.get(key)
+        if hit is not None and hit[0] == version and hit[1].device == dev:
+            return hit[1]
+        I = self.num_items
+        idx = torch.empty(I, neighbours, dtype=torch.int32, device=dev)
+        val = torch.empty(I, neighbours, dtype=torch.float32, device=dev)
+        for lo in range(0, I, KNN_LIST_BLOCK):
+            rows = np.arange(lo, min(I, lo + KNN_LIST_BLOCK), dtype=np.int64)
+            if source == "co":
+                self.co_neighbours_device("item", rows, neighbours, measure, idx[lo:lo + rows.size], val[lo:lo + rows.size])
+            else:
+                self.neighbours_device("item", rows, neighbours, source, idx[lo:lo + rows.size], val[lo:lo + rows.size])
+        lists = ops.NeighbourLists(idx, val, dev)
+        kept[key] = (version, lists)
+        return lists
+
+    @torch.no_grad()
+    def knn_recommend_device(self, users, lists, hist, k, excl=None, out_idx=None, out_val=None, out_cnt=None):
+        """The k items the neighbour lists of each user's history vote for (ops.neighbour_vote_topk, csrc/vote.hip): out_idx int32,
+        out_val float32, out_cnt int32 [B x k] on the device (allocated here when None), by (score descending, id ascending), -1 /
+        -inf / 0 where fewer are voted for. users: segment ids of hist (host array or tensor, checked on the host); lists: an
+        ops.NeighbourLists (neighbour_lists); hist: an ops.HistoryIndex whose own ids are left out; excl: a second HistoryIndex of
+        the same segments to leave out as well. The dense form's workspace is kept (every call leaves it zero). Single-GPU."""
+        dev = self._require_gpu()
+        k = ops._vote_k("knn_recommend_device", k)
+        ops._vote_indexes("knn_recommend_device", lists, hist, excl)
+        u = ops._checked_ids(users, hist.n_rows, "knn_recommend_device", "users", "users span [%d, %d], the histories have %d segments")
+        B = int(u.size)
+        out_idx = torch.empty(B, k, dtype=torch.int32, device=dev) if out_idx is None else out_idx
+        out_val = torch.empty(B, k, dtype=torch.float32, device=dev) if out_val is None else out_val
+        out_cnt = torch.empty(B, k, dtype=torch.int32, device=dev) if out_cnt is None else out_cnt
+        n_dense = int((ops.vote_votes(lists, hist, excl)[u] > ops.VOTE_SLOTS // 2).sum())
+        need = ops.vote_workspace(n_dense, lists.n)
+        ws = self.__dict__.get("_vote_ws")
+        if need and (ws is None or ws.numel() < need or ws.device != dev):
+            if need > ops.COOCCUR_WORKSPACE_BUDGET:
+                raise ValueError("knn_recommend_device: the dense form's rows need %d bytes, the budget is %d"
+                                 % (need, ops.COOCCUR_WORKSPACE_BUDGET))
+            ws = self.__dict__["_vote_ws"] = torch.zeros(need, dtype=torch.uint8, device=dev)      # zero once: every call leaves it zero
+        ops.neighbour_vote_topk(lists, hist, u, k, out_idx, out_val, out_cnt, excl=excl, workspace=ws if need else None)
+        return out_idx, out_val, out_cnt
+
+    def recommend_knn(self, user_ids, k, neighbours=50, source="co", measure="cosine", history=None, exclude=None):
+        """A neighbourhood recommender beside the model's own lists: per user the k items the `neighbours` nearest items of every
+        item of the user's history vote for -- KnnLists(ids CPU int32 [B x k] (-1 padded), scores CPU fp32 [B x k] (-inf padded: the
+        sum of the neighbour scores behind the item, in 2^-24 fixed point), votes CPU int32 [B x k] (their number)), by (score
+        descending, id ascending). source "co" is ItemKNN over the training graph under `measure` ("count", "cosine", "jaccard");
+        "fused" or a head letter of self._mods is content-KNN in that space ("v": recommend what looks like what you took).
+        history: dict user -> item ids (default: the data set's train dict, as explain_history takes it); the history's own items
+        are never listed; `exclude` = dict user -> item ids left out on top, as explain() takes it. k or neighbours outside
+        [1, 256], an unknown source or measure: ValueError; an id outside its side: IndexError -- both before anything touches the
+        device. An empty user_ids returns [0 x k] without a launch."""
+        k = ops._vote_k("recommend_knn", k)
+        neighbours = self._knn_source(source, neighbours, measure)
+        users = self._id_lists([user_ids], "user", self.num_users)[1]
+        if history is None:
+            history = self.dataset.get_user_train_dict()
+        elif not isinstance(history, dict):
+            raise TypeError("history must be a dict user -> item ids")
+        hptr, hflat, _ = self._id_lists([history.get(int(u), []) for u in users], "history item")
+        tptr, tflat = self._excluded(exclude, users, "item")
+        n = int(users.size)
+        if not n:
+            return KnnLists(torch.empty(0, k, dtype=torch.int32), torch.empty(0, k, dtype=torch.float32), torch.empty(0, k, dtype=torch.int32))
+        dev = self._require_gpu()
+        lists = self.neighbour_lists(source, neighbours, measure)
+        hist = ops.HistoryIndex(hptr, hflat, dev, n_items=self.num_items)
+        excl = ops.HistoryIndex(tptr, tflat, dev, n_items=self.num_items) if tflat.size else None
+        idx, val, cnt = self.knn_recommend_device(np.arange(n, dtype=np.int64), lists, hist, k, excl)     # row b's history is segment b
+        return KnnLists(idx.cpu(), val.cpu(), cnt.cpu())
 
     @torch.no_grad()
     def clusters_device(self, side, n_clusters, space="fused", iters=25, seed=2022, init=None):

@@ -6,6 +6,7 @@ else raises (no CPU path).
 """
 import collections
 import ctypes
+import math
 
 import numpy as np
 
@@ -1034,6 +1035,10 @@ def __getattr__(name):
         return int(_lib.load().elimrec_cooccur_slots())
     if name == "COOCCUR_GROUPS":         # workgroups (and counter rows) of cooccur_topk's dense form at most
         return int(_lib.load().elimrec_cooccur_groups())
+    if name == "VOTE_SLOTS":             # (key, sum, count) entries of the LDS form's table of neighbour_vote_topk
+        return int(_lib.load().elimrec_vote_slots())
+    if name == "VOTE_GROUPS":            # workgroups (and workspace rows) of neighbour_vote_topk's dense form at most
+        return int(_lib.load().elimrec_vote_groups())
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 
@@ -2348,4 +2353,142 @@ def cooccur_topk(index, rows, K, out_idx, out_val=None, out_cnt=None, measure="c
                                                 _dev(index.o_ptr, "o_ptr", torch.int64), _dev(index.o_nbr, "o_nbr", torch.int32), index.n_other,
                                                 _dev(_resident_ids(q, dev), "rows", torch.int32), Q, K, m, 1 if lds else 0, n_dense,
                                                 walk.data_ptr(), ip, vp, cp, wp, workspace.numel(), _stream()), who)
+    return out_idx
+
+
+VOTE_MAX_K = 256                         # the longest list neighbour_vote_topk keeps (csrc/vote.hip), known without the library
+VOTE_FRAC_BITS = 24                      # fraction bits of a vote's fixed-point value: q = rint(double(val) * 2^24)
+VOTE_MAX_VOTES = 1 << 30                 # (history length) x Kn of one user stays below this: the count's mark bit of a left-out id
+
+
+class NeighbourLists(object):
+    """Neighbour lists idx int32 / val float32 [n x Kn] as cooccur_topk or cosine_topk write them (-1 / -inf fillers), CHECKED ONCE ON
+    THE HOST -- two dimensions, equal shapes, Kn >= 1, n < 2^31 - 1, the dtypes, contiguous (ValueError / TypeError) -- and then
+    resident on `device`: neighbour_vote_topk takes them as is, call after call. idx and val: host arrays or tensors (device tensors
+    stay where they are when they already live on `device`). max_abs = the largest |val| over the FINITE values (0.0 without one),
+    taken here once -- for device tensors that read is a synchronisation; neighbour_vote_topk's overflow bound uses it. The ids'
+    range is left to the kernel, which checks every entry and never dereferences one outside [0, n)."""
+
+    def __init__(self, idx, val, device):
+        who = "NeighbourLists"
+        it = idx if isinstance(idx, torch.Tensor) else torch.from_numpy(np.asarray(idx))
+        vt = val if isinstance(val, torch.Tensor) else torch.from_numpy(np.asarray(val))
+        if it.dim() != 2 or vt.dim() != 2 or it.shape != vt.shape or it.shape[1] < 1:
+            raise ValueError("elimrec_amd.ops.%s: idx and val are both [n x Kn] with Kn >= 1, got %s and %s"
+                             % (who, tuple(it.shape), tuple(vt.shape)))
+        if it.dtype != torch.int32 or vt.dtype != torch.float32:
+            raise TypeError("elimrec_amd.ops.%s: idx must be int32 and val float32, got %s and %s" % (who, it.dtype, vt.dtype))
+        if not (it.is_contiguous() and vt.is_contiguous()):
+            raise ValueError("elimrec_amd.ops.%s: idx and val must be contiguous" % who)
+        if it.shape[0] >= 2 ** 31 - 1:
+            raise ValueError("elimrec_amd.ops.%s: n < 2^31 - 1, got %d" % (who, it.shape[0]))
+        self.n, self.Kn = int(it.shape[0]), int(it.shape[1])
+        self.device = torch.device(device)
+        self.idx, self.val = it.to(self.device), vt.to(self.device)
+        finite = torch.isfinite(self.val)
+        self.max_abs = float(torch.where(finite, self.val.abs(), torch.zeros_like(self.val)).max().item()) if self.n else 0.0
+
+
+def vote_rows_in_lds(V):
+    """Which form neighbour_vote_topk takes for a user with V = (history length) x Kn + (entries left out) (host arithmetic only):
+    True = the LDS form (V <= VOTE_SLOTS / 2: the hash table's load factor is at most 0.5 whatever the ids are), False = the dense
+    form. Both forms give the same bits. ValueError for V < 0."""
+    form = int(_lib.load().elimrec_vote_rows_in_lds(int(V)))
+    if form < 0:
+        raise ValueError("elimrec_amd.ops.vote_rows_in_lds: V >= 0, got %d" % V)
+    return bool(form)
+
+
+def vote_workspace(n_dense_rows, n):
+    """Bytes of the dense form's rows for a call with n_dense_rows users on that form over lists of n items (host arithmetic only):
+    min(n_dense_rows, VOTE_GROUPS) rows of n int64 sums and n int32 counts."""
+    if n_dense_rows < 0 or not 0 <= n < 2 ** 31 - 1:
+        raise ValueError("elimrec_amd.ops.vote_workspace: n_dense_rows >= 0 and 0 <= n < 2^31 - 1, got %d and %d" % (n_dense_rows, n))
+    return int(_lib.load().elimrec_vote_workspace(int(n_dense_rows), int(n)))
+
+
+def _vote_k(who, K):
+    if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or not 1 <= K <= VOTE_MAX_K:
+        raise ValueError("elimrec_amd.ops.%s: K must be an integer, 1 <= K <= %d, got %r" % (who, VOTE_MAX_K, K))
+    return int(K)
+
+
+def _vote_indexes(who, lists, hist, excl):
+    if not isinstance(lists, NeighbourLists):
+        raise TypeError("elimrec_amd.ops.%s: lists must be an ops.NeighbourLists, got %s" % (who, type(lists).__name__))
+    if not isinstance(hist, HistoryIndex):
+        raise TypeError("elimrec_amd.ops.%s: hist must be an ops.HistoryIndex, got %s" % (who, type(hist).__name__))
+    if excl is not None:
+        if not isinstance(excl, HistoryIndex):
+            raise TypeError("elimrec_amd.ops.%s: excl must be an ops.HistoryIndex or None, got %s" % (who, type(excl).__name__))
+        if excl.n_rows != hist.n_rows:
+            raise ValueError("elimrec_amd.ops.%s: hist and excl name the same users: %d and %d segments" % (who, hist.n_rows, excl.n_rows))
+
+
+def vote_votes(lists, hist, excl=None, exclude_history=True):
+    """Host int64 [hist.n_rows]: V of every segment = (history length) x Kn + (entries left out: the history's own with
+    exclude_history, plus excl's) -- the number that alone picks a user's form in neighbour_vote_topk (vote_rows_in_lds)."""
+    _vote_indexes("vote_votes", lists, hist, excl)
+    V = hist.sizes.astype(np.int64) * (lists.Kn + (1 if exclude_history else 0))
+    return V if excl is None else V + excl.sizes
+
+
+def neighbour_vote_topk(lists, hist, users, K, out_idx, out_val=None, out_cnt=None, excl=None, exclude_history=True, lds=True,
+                        workspace=None):
+    """elimrec_neighbour_vote_topk: per user the K items the neighbour lists of the user's history vote for -- ItemKNN (lists from
+    cooccur_topk) or content-KNN (lists from cosine_topk) recommendations (csrc/vote.hip). lists: an ops.NeighbourLists [n x Kn];
+    hist: an ops.HistoryIndex, the histories; excl: a second HistoryIndex of the same segments, ids to leave out on top (optional);
+    users: host array or tensor of segment ids, checked on the host (IndexError; a synchronisation for a device tensor), a repeated
+    id is a row of its own. A vote is a pair (history position p, slot s) with j = hist[p] in [0, n), i = idx[j, s] in [0, n) and
+    val[j, s] finite -- anything else is skipped; a repeated history id votes again, a repeated id within a list votes again. It
+    adds q = rint(double(val) * 2^24) (round half even) to an int64 sum S and 1 to an int32 count c. Listed: c >= 1 and not left
+    out (the history's own ids with exclude_history, excl's segment). score = float(double(S) * 2^-24). out_idx int32 / out_val
+    float32 (optional) / out_cnt int32 (optional: c) [B x K] on the lists' device <- the K best by (score descending, id
+    ascending), -1 / -inf / 0 behind them. 1 <= K <= VOTE_MAX_K = 256.
+    Refused before any launch (ValueError): sums that could overflow -- ceil(lists.max_abs * 2^24) x (hist's longest segment) x Kn
+    >= 2^62 --, (longest segment) x Kn >= 2^30, a workspace that is too small, a default workspace past COOCCUR_WORKSPACE_BUDGET.
+    A user with vote_rows_in_lds(V) (vote_votes) takes the LDS form, every other user -- with lds=False every user -- the dense
+    form, whose rows live in `workspace`: a uint8 device tensor of at least vote_workspace(n_dense_rows, n) bytes, 16-byte aligned,
+    ZERO before its first use (every call leaves it zero); default: allocated and zeroed here. Both forms give the same bits: a
+    user's outputs depend on the history as a multiset, the lists, the exclusions and K alone. Every argument error is raised before
+    the device is touched. An empty `users` returns without a launch."""
+    who = "neighbour_vote_topk"
+    K = _vote_k(who, K)
+    _vote_indexes(who, lists, hist, excl)
+    u = _checked_ids(users, hist.n_rows, who, "users", "users span [%d, %d], the histories have %d segments")
+    B, dev = int(u.size), lists.device
+    longest = int(hist.sizes.max()) if hist.sizes.size else 0
+    if math.ceil(lists.max_abs * 2.0 ** VOTE_FRAC_BITS) * longest * lists.Kn >= 2 ** 62:
+        raise ValueError("elimrec_amd.ops.%s: the int64 sums could overflow: ceil(%r * 2^%d) x %d (the longest history) x %d (Kn) >= 2^62"
+                         % (who, lists.max_abs, VOTE_FRAC_BITS, longest, lists.Kn))
+    if longest * lists.Kn >= VOTE_MAX_VOTES:
+        raise ValueError("elimrec_amd.ops.%s: %d (the longest history) x %d (Kn) votes of one user, fewer than 2^30 are taken"
+                         % (who, longest, lists.Kn))
+    if hist.ptr.device != dev or (excl is not None and excl.ptr.device != dev):
+        raise ValueError("elimrec_amd.ops.%s: the lists live on %s, the histories on %s" % (who, dev, hist.ptr.device))
+    ip = _rows_out(out_idx, "out_idx", torch.int32, B, K, who, dev)
+    vp = _rows_out(out_val, "out_val", torch.float32, B, K, who, dev) if out_val is not None else None
+    cp = _rows_out(out_cnt, "out_cnt", torch.int32, B, K, who, dev) if out_cnt is not None else None
+    if B == 0:
+        return out_idx
+    half = int(_lib.load().elimrec_vote_slots()) // 2
+    n_dense = int((vote_votes(lists, hist, excl, exclude_history)[u] > half).sum()) if lds else B
+    need = vote_workspace(n_dense, lists.n)
+    if workspace is None:
+        if need > COOCCUR_WORKSPACE_BUDGET:
+            raise ValueError("elimrec_amd.ops.%s: the dense form's rows need %d bytes (%d rows of %d entries), the budget is %d: pass a "
+                             "workspace" % (who, need, min(n_dense, _lib.load().elimrec_vote_groups()), lists.n, COOCCUR_WORKSPACE_BUDGET))
+        workspace = torch.zeros(max(16, need), dtype=torch.uint8, device=dev)
+    wp = _dev(workspace, "workspace", torch.uint8)
+    if workspace.numel() < need or not workspace.is_contiguous() or wp % 16 or workspace.device != dev:
+        raise ValueError("elimrec_amd.ops.%s: the workspace needs %d contiguous bytes on the lists' device, 16-byte aligned (got %d)"
+                         % (who, need, workspace.numel()))
+    up = torch.from_numpy(np.ascontiguousarray(u, dtype=np.int64)).to(dev)
+    ep, ei, en = (None, None, 0) if excl is None else (_dev(excl.ptr, "excl_ptr", torch.int64), _dev(excl.items, "excl_items", torch.int32),
+                                                       excl.n_rows)
+    _lib.check(_lib.load().elimrec_neighbour_vote_topk(_dev(lists.idx, "nbr_idx", torch.int32), _dev(lists.val, "nbr_val", torch.float32),
+                                                       lists.n, lists.Kn, _dev(hist.ptr, "hist_ptr", torch.int64),
+                                                       _dev(hist.items, "hist_items", torch.int32), hist.n_rows, ep, ei, en,
+                                                       _dev(up, "users", torch.int64), B, K, 1 if exclude_history else 0, 1 if lds else 0,
+                                                       n_dense, ip, vp, cp, wp, workspace.numel(), _stream()), who)
     return out_idx

@@ -1610,3 +1610,131 @@ class CoNeighbourReport(_Report):
         buf = format_table(("n",) + tuple(columns), self.group_labels, final)
         self._done[key] = (version, final, buf)
         return final, buf
+
+
+BASELINE_LIST_COLUMNS = ("filled", "pop", "overlap", "coverage", "gini", "entropy")
+BaselineTables = collections.namedtuple("BaselineTables", ("columns", "labels", "table"))
+
+
+class BaselineReport(_Report):
+    """Does the model beat a neighbourhood baseline on this split, and do its lists differ from the baseline's at all
+    (--baseline_report=K)? Per source a neighbour-vote recommender (EliMRec.knn_recommend_device, csrc/vote.hip) over the test users
+    in the evaluator's default order, their train items as the history and left out: "co" = ItemKNN over the training graph under
+    `measure`, "fused" / a head letter = content-KNN in that space of the cached tables ("v": recommend what looks like what you
+    took -- the single-modal shortcut as a recommender of its own), each item's `neighbours` nearest items voting.
+    metric_rows() is ops.rank_metrics over those lists with the truth CSR, metric ids and shown-column layout of
+    SignificanceReport.metric_rows, so the two row blocks pair user by user (SignificanceReport.shift); a -1 filler is a miss (the
+    metric kernel compares ids against a truth list of ids >= 0). evaluate() gives one row per source -- with group_view one block of
+    group rows per source, through ops.group_metric_means -- over the evaluator's shown metric columns and BASELINE_LIST_COLUMNS:
+      filled = the mean share of the list's slots that hold an item; pop = the mean training interactions of a user's listed items
+      (0 for an empty list); overlap = the share of the model's own top-K list under the current predict type that the baseline list
+      also holds (ops.list_overlap / K); coverage, gini, entropy = exposure_summary of the rows' lists (ops.list_exposure).
+    top_k / metric: the evaluator's; list_k: the lists' length (default and at least the largest cutoff, at most 256). The baseline
+    lists do not depend on the predict type -- only `overlap` does -- and are kept as EliMRec.neighbour_lists keeps its own."""
+
+    name, needs = "baseline", "knn_recommend_device"
+
+    def __init__(self, dataset, user_train_dict, user_test_dict, top_k, metric=None, sources=("co",), neighbours=50, measure="cosine",
+                 group_view=None, list_k=None):
+        from .evaluator import UniEvaluator, re_metric_dict
+        if not isinstance(user_train_dict, dict) or not isinstance(user_test_dict, dict):
+            raise TypeError("user_train_dict and user_test_dict must be dicts")
+        if isinstance(sources, str) or not len(sources) or any(not isinstance(x, str) or not x for x in sources) or len(set(sources)) != len(sources):
+            raise ValueError("sources is a sequence of distinct names: 'co', 'fused' or a head letter, got %r" % (sources,))
+        if isinstance(neighbours, bool) or not isinstance(neighbours, (int, np.integer)) or not 1 <= neighbours <= ops.VOTE_MAX_K:
+            raise ValueError("neighbours must be an integer in [1, %d], got %r" % (ops.VOTE_MAX_K, neighbours))
+        ops._cooccur_measure("BaselineReport", measure)
+        self.evaluator = ev = UniEvaluator(dataset, user_train_dict, user_test_dict, metric=metric, top_k=top_k)
+        list_k = ev.max_top if list_k is None else list_k
+        if isinstance(list_k, bool) or not isinstance(list_k, (int, np.integer)) or not ev.max_top <= list_k <= ops.VOTE_MAX_K:
+            raise ValueError("the lists hold the largest cutoff shown (%d) to %d items, got %r" % (ev.max_top, ops.VOTE_MAX_K, list_k))
+        self.dataset = dataset
+        self.num_items = I = int(dataset.num_items)
+        self.user_pos_train = user_train_dict
+        self.user_pos_test = user_test_dict
+        self.top_k = self.k = int(list_k)
+        self.sources, self.neighbours, self.measure = tuple(sources), int(neighbours), measure
+        self.users = ev.default_users()
+        self.metric_columns = tuple("%s@%d" % (re_metric_dict[m], k) for m in ev.metrics for k in ev.top_show)
+        self.columns = self.metric_columns + BASELINE_LIST_COLUMNS
+        self._shown = (np.arange(ev.metrics_num, dtype=np.int64)[:, None] * ev.max_top + (np.asarray(ev.top_show, dtype=np.int64) - 1)[None, :]).reshape(-1)
+        self.item_counts = item_train_counts(user_train_dict, I)
+        self.group_labels, self._positions = self._user_groups(self.users, user_train_dict, group_view)
+        self.labels = [("%s %s" % (x, g.strip())).ljust(16) for x in self.sources for g in self.group_labels]
+        self._lists = {}
+
+    def _make_resident(self, device):
+        """The user group index and positions, the shown columns, the items' training counts, the test users' histories (segment b =
+        user b of self.users) and the truth CSR resident on the device."""
+        hptr, hflat, _ = ops.ragged([self.user_pos_train.get(u, []) for u in self.users], check=(
+            self.num_items, "item ids must lie in [0, %d)" % self.num_items), cast=int)
+        return dict(groups=group_index(self._positions, len(self.users), device), shown=torch.from_numpy(self._shown).to(device),
+                    positions=[torch.from_numpy(np.asarray(p, dtype=np.int64)).to(device) for p in self._positions],
+                    counts=torch.from_numpy(self.item_counts.astype(np.float64)).to(device),
+                    hist=ops.HistoryIndex(hptr if len(self.users) else np.zeros(2, dtype=np.int64), hflat, device, n_items=self.num_items),
+                    truth=lists_csr(self.users, self.user_pos_test, device, unique=True))
+
+    def knn_lists(self, model, source):
+        """The baseline's lists of one source on the device: int32 [test users x K], users in the evaluator's default order, train
+        items masked, -1 where fewer than K items are voted for. Kept for as long as the model keeps the source's neighbour lists."""
+        if source not in self.sources:
+            raise ValueError("source is one of this report's %s, got %r" % ("/".join(self.sources), source))
+        device = self._preflight(model)
+        res = self._resident(device)
+        lists = model.neighbour_lists(source, self.neighbours, self.measure)
+        hit = self._lists.get((source, str(device)))
+        if hit is not None and hit[0] is lists:
+            return hit[1]
+        n, K = len(self.users), self.k
+        idx = torch.empty(n, K, dtype=torch.int32, device=device)
+        val = torch.empty(min(n, self.block_users), K, dtype=torch.float32, device=device)
+        cnt = torch.empty(min(n, self.block_users), K, dtype=torch.int32, device=device)
+        for a in range(0, n, self.block_users):
+            b = min(n, a + self.block_users)
+            model.knn_recommend_device(np.arange(a, b, dtype=np.int64), lists, res["hist"], K, None, idx[a:b], val[:b - a], cnt[:b - a])
+        self._lists[(source, str(device))] = (lists, idx)
+        return idx
+
+    def metric_rows(self, model, source):
+        """The test users' metric rows of one source's lists, compacted to the shown columns on the device: ([users x Cs] float32
+        contiguous, column names like "Recall@10") -- SignificanceReport.metric_rows' layout and user order."""
+        ev = self.evaluator
+        lists = self.knn_lists(model, source)
+        res = self._resident(lists.device)
+        first = lists if self.k == ev.max_top else lists[:, :ev.max_top].contiguous()
+        out = torch.empty(len(self.users), ev.metrics_num * ev.max_top, dtype=torch.float32, device=lists.device)
+        if len(self.users):
+            ops.rank_metrics(first, res["truth"][0], res["truth"][1], ev.metrics, out)
+        return out.index_select(1, res["shown"]), self.metric_columns
+
+    def evaluate(self, model):
+        """(BaselineTables(columns, labels, table float64 [sources x (1 + groups) x C]), buf): per source row "all:" and then the
+        group_view groups, over self.columns. buf: a header of column names and one "%.8f" line per row."""
+        device = self._preflight(model)
+        res = self._resident(device)
+        n, K, G, Cs = len(self.users), self.k, len(self.group_labels), len(self.metric_columns)
+        own = torch.empty(n, K, dtype=torch.int32, device=device)
+        for a, b, _, idx in self.top_lists(model, self.users, K, self.block_users, self.tie_order):
+            own[a:b] = idx
+        table = np.zeros((len(self.sources) * G, len(self.columns)), dtype=np.float64)
+        shared = torch.empty(n, dtype=torch.int32, device=device)
+        for s, source in enumerate(self.sources):
+            lists = self.knn_lists(model, source)
+            rows = torch.empty(n, Cs + 3, dtype=torch.float32, device=device)
+            rows[:, :Cs] = self.metric_rows(model, source)[0]
+            listed = lists >= 0
+            filled = listed.sum(dim=1).double()
+            rows[:, Cs] = (filled / K).float()
+            pop = torch.where(listed, res["counts"][lists.clamp(min=0).long()], 0.0).sum(dim=1) / filled.clamp(min=1.0)
+            rows[:, Cs + 1] = pop.float()
+            if n:
+                ops.list_overlap(own, lists, shared)
+            rows[:, Cs + 2] = (shared.double() / K).float()
+            table[s * G:(s + 1) * G, :Cs + 3] = group_table(rows, res["groups"], G)
+            for g, at in enumerate(res["positions"]):
+                counts = torch.zeros(self.num_items, dtype=torch.int32, device=device)
+                if at.numel():
+                    ops.list_exposure(lists.index_select(0, at).contiguous(), counts)
+                table[s * G + g, Cs + 3:] = exposure_summary(counts.cpu().numpy(), [np.arange(self.num_items)])[0, 1:4]
+        final = BaselineTables(self.columns, list(self.labels), table)
+        return final, format_table(final.columns, final.labels, final.table)

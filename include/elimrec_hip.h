@@ -833,6 +833,41 @@ int elimrec_cooccur_max_k(void);
 int elimrec_cooccur_groups(void);
 int elimrec_cooccur_rows_in_lds(int64_t W);
 
+/* Neighbour votes (csrc/vote.hip): per user the K items the neighbour lists of the user's history vote for -- ItemKNN / content-KNN
+ * recommendations. No counterpart in the reference. d_nbr_idx int32 / d_nbr_val fp32 [n x Kn]: the neighbour lists as
+ * elimrec_cooccur_topk or elimrec_cosine_topk write them (-1 / -inf fillers). d_hist_ptr int64 [n_hist_rows + 1] / d_hist_items
+ * int32: the histories as CSR; d_excl_ptr / d_excl_items (both or neither, n_excl_rows rows): ids to leave out on top. d_users
+ * int64 [B] names the segment of both CSRs; a user outside the histories gets fillers, one outside the second CSR leaves nothing
+ * more out.
+ * A vote is a pair (history position p, slot s) with j = hist[p] in [0, n), i = nbr_idx[j, s] in [0, n) and nbr_val[j, s] finite;
+ * anything else is skipped and never dereferenced. A repeated history id votes again, a repeated id within a list votes again. The
+ * vote adds q = rint(double(val) * 2^24) (round half even) to an int64 sum S(u, i) and 1 to an int32 count c(u, i). Listed: c >= 1
+ * and not left out -- left out are the ids of the history segment itself (exclude_history = 1) and the second CSR's segment.
+ * score = float(double(S) * 2^-24). d_idx int32 / d_val fp32 (optional) / d_cnt int32 (optional, c) [B x K] <- the K best by (score
+ * descending, id ascending), -1 / -inf / 0 behind them. 1 <= K <= elimrec_vote_max_k() = 256. THE CALLER keeps the sums within
+ * int64 (|q| x longest history x Kn < 2^62) and the votes of one user below 2^30.
+ * V(u) = (history length) x Kn + (entries left out) alone picks the form. use_lds = 1: a row with elimrec_vote_rows_in_lds(V) --
+ * V <= elimrec_vote_slots() / 2, slots = 2048 (key, int64 sum, int32 count) entries of an open-addressing table in 32 KiB of LDS,
+ * load factor at most 0.5 whatever the ids are, a selection list of slots / 2 keys beside it -- takes the LDS form, one workgroup
+ * per row; every other row, and with use_lds = 0 every row, the dense form: min(n_dense_rows, elimrec_vote_groups() = 512)
+ * workgroups loop over those rows, each with n int64 sums and n int32 counts in d_workspace (elimrec_vote_workspace(n_dense_rows,
+ * n) bytes, 16-byte aligned), which must be ZERO when the call starts and is zero again when it ends. n_dense_rows: the caller's
+ * count of the dense form's rows; it sizes the grid and the workspace only -- any count from 1 to B serves every such row (fewer
+ * workgroups then share the rows), with 0 declared a row that needed the dense form gets fillers; use_lds = 0 needs at least 1. Both forms give the same bits: a user's outputs depend on the history as a multiset, the
+ * lists, the exclusions and K alone. Integer atomics only. One or two launches on `stream`.
+ * elimrec_vote_rows_in_lds: 1 / 0, -1 for V < 0. elimrec_vote_frac_bits: 24. */
+int elimrec_neighbour_vote_topk(const int32_t *d_nbr_idx, const float *d_nbr_val, int64_t n, int Kn, const int64_t *d_hist_ptr,
+                                const int32_t *d_hist_items, int64_t n_hist_rows, const int64_t *d_excl_ptr,
+                                const int32_t *d_excl_items, int64_t n_excl_rows, const int64_t *d_users, int64_t B, int K,
+                                int exclude_history, int use_lds, int64_t n_dense_rows, int32_t *d_idx, float *d_val, int32_t *d_cnt,
+                                void *d_workspace, size_t workspace_bytes, void *stream);
+size_t elimrec_vote_workspace(int64_t n_dense_rows, int64_t n);
+int elimrec_vote_slots(void);
+int elimrec_vote_groups(void);
+int elimrec_vote_max_k(void);
+int elimrec_vote_frac_bits(void);
+int elimrec_vote_rows_in_lds(int64_t V);
+
 /* Hard-negative pick (csrc/hardneg.hip): per triplet the best of M candidate items under the current tables. No counterpart in
  * the reference. d_U / d_T point at row 0, column 0 of an [n_users x blocks * d] / [n_items x blocks * d] slice of a row-major
  * float32 matrix with row stride ld_u / ld_i >= blocks * d, block b = columns [b * d, (b + 1) * d); d_sq_u[r * ldsq_u + b] /

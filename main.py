@@ -162,6 +162,13 @@ class Net(object):
         # (--significance_level) of every shown metric over R resamples of the test users, overall and per user group; after both
         # effects the paired TE -> TIE difference with its two-sided p-value. It needs metric rows only (run on one GPU only so far)
         self.significance_report = int(cfg["significance_report"]) if "significance_report" in cfg else 0
+        # --baseline_report=K (default 0: off), --baseline_sources=[co,fused,v,...], --baseline_neighbours=50, --baseline_measure: under
+        # each [TEST] line a [baselines] table -- neighbour-vote recommenders (ItemKNN over the training graph, content-KNN in a space
+        # of the tables) on the same split; only `overlap` (with the model's own lists) differs between the effects. With
+        # --significance_report also the paired model - baseline metric difference per source
+        self.baseline_report = int(cfg["baseline_report"]) if "baseline_report" in cfg else 0
+        if self.baseline_report and self.world > 1:
+            raise ValueError("--baseline_report needs the whole cached item table on one rank: it is single-GPU")
         Logger.info(count_parameters(self.recommender))
         self.opt = FusedAdam(self.recommender.parameters(), lr=cfg.lr, weight_decay=cfg.weight_decay)
         self.loss_name = str(cfg.loss)
@@ -332,6 +339,14 @@ class Net(object):
                 sure[effect] = reporter.metric_rows(rec)
                 Logger.info("  [{}] metric intervals ({} replicates, {:g} %):\n{}".format(
                     effect, reporter.replicates, 100.0 * reporter.level, reporter.evaluate(rec, sure[effect])[1]))
+            if self.baseline_report:       # neighbourhood baselines on the same split; only `overlap` depends on the effect
+                reporter = rec.baseline_reporter
+                Logger.info("  [{}] [baselines] top-{} neighbour-vote lists ({} neighbours, {}):\n{}".format(
+                    effect, reporter.k, reporter.neighbours, reporter.measure, reporter.evaluate(rec)[1]))
+                if self.significance_report:   # model - baseline per user, the users resampled as pairs
+                    for source in reporter.sources:
+                        Logger.info("  [{} - {}] metric difference, paired bootstrap:\n{}".format(
+                            effect, source, rec.significance_reporter.shift(reporter.metric_rows(rec, source), sure[effect])[1]))
         if self.rank_report:               # positive delta: TIE ranks the test item higher than TE does
             Logger.info("  [TE->TIE] rank shift of the test items:\n{}".format(rec.rank_reporter.shift(ranks["TE"], ranks["TIE"])[1]))
         if self.list_report:               # overlap: the share of the TE list that TIE keeps; d_<column>: TIE - TE
