@@ -8,34 +8,40 @@ namespace elimrec {
 
 constexpr int kMaxBatch = 8;
 typedef float v16f __attribute__((ext_vector_type(16)));
-#ifndef ELIMREC_BWDW_TN2
-#define ELIMREC_BWDW_TN2 64
-#endif
-constexpr int TN1 = 64, TN2 = ELIMREC_BWDW_TN2, TRB = 32;      // TN2 = 64 (one MFMA tile per wave; measured 3 us faster
-                                                                  // per step than 128 = two tiles per wave: more, smaller workgroups)
-constexpr int BNJ = TN2 / 64, BC4 = TN2 / 4, BRP = 256 / BC4, BPS = TRB / BRP;   // tiles per wave; B loader geometry
+constexpr int TN1 = 64, TN2 = 64, TRB = 32;                    // output tile (one 32 x 32 MFMA tile per wave); rows per LDS stage
+constexpr int ZT = 2;                                             // output tiles of one row chunk that ONE workgroup owns (below)
+constexpr int BC4 = TN2 / 4, BRP = 256 / BC4, BPS = TRB / BRP;    // B loader geometry: float4 per row, rows per pass, passes
 
 struct BwdProblem {
     elimrec_linear_bwd_desc d;
     int chunk_rows, chunks, t1, t2;       // decomposition
-    int first_block;                      // prefix of (chunks * t1 * t2) over the problems before this one
+    int first_block;                      // prefix of (chunks * t1 * ceil(t2 / ZT)) over the problems before this one
     float *slabs, *cslabs;
 };
 struct BwdBatch { BwdProblem p[kMaxBatch]; int n; };
 
-// One workgroup of the partial launch: a chunk of rows x one 64 x TN2 output tile (see gemm.hip, "weight grad").
-// As / Bs: the caller's LDS stages ([2][TRB * TN1], [2][TRB * TN2] floats = 32 KB: five workgroups per CU). The per-row
-// weights of the weighted column sum stay in registers: lane k of wave 0 holds row k's, the sum reads it with v_readlane.
+// One workgroup of the partial launch: a chunk of rows x a PAIR of adjacent 64 x TN2 output tiles (see gemm.hip, "weight grad").
+// The chunk's A rows are fetched and staged once for both tiles of the pair (a 64 x 128 problem is one workgroup per chunk, a
+// 64 x 256 one two; four tiles would need 64 accumulators + 40 staging registers: more than five workgroups per CU leave).
+// As / Bs: the caller's LDS stages ([2][TRB * TN1], [2][TRB * TN2] floats = 32 KB: five workgroups per CU): As[s & 1] holds the A rows
+// of stage s, Bs[z] the B rows of tile z of the stage being multiplied (one stage of each: two barriers per stage, around the
+// store). The global loads of stage s + 1 are in flight during the MFMAs of stage s; a second register set (two stages ahead)
+// does not fit the 96 registers of five workgroups per CU beside two accumulator tiles. The per-row weights of the weighted
+// column sum stay in registers: lane k of wave 0 holds row k's, the sum reads it with v_readlane.
+// The rows enter every output element's sum as before -- the same MFMA sequence over the same operands per element --, and
+// the slab layout is the reduce's: same bits.
+struct BwdStage { float4 a[2], b[ZT][BPS]; float w; };
 __device__ __forceinline__ void bwd_w_partial_body(const BwdBatch &batch, int block, float (*As)[TRB * TN1], float (*Bs)[TRB * TN2]) {
+    static_assert(ZT == 2 && TN2 == 64, "two B tiles share the two Bs stages");
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int pi = 0;
     while (pi + 1 < batch.n && block >= batch.p[pi + 1].first_block) ++pi;
     const BwdProblem &pb = batch.p[pi];
     const int local = block - pb.first_block;
-    const int n1_tiles = pb.t1, n2_tiles = pb.t2;
-    const int chunk = local / (n1_tiles * n2_tiles);
-    const int tile = local - chunk * (n1_tiles * n2_tiles);
-    const int tile_y = tile / n2_tiles, tile_z = tile - tile_y * n2_tiles;
+    const int n1_tiles = pb.t1, n2_tiles = pb.t2, n2_pairs = (n2_tiles + ZT - 1) / ZT;
+    const int chunk = local / (n1_tiles * n2_pairs);
+    const int tile = local - chunk * (n1_tiles * n2_pairs);
+    const int tile_y = tile / n2_pairs, pair_z = tile - tile_y * n2_pairs;
     const float *__restrict__ A = pb.d.d_A;
     const float *__restrict__ B = pb.d.d_B;
     const int32_t *__restrict__ row_index = pb.d.d_row_index;
@@ -43,81 +49,87 @@ __device__ __forceinline__ void bwd_w_partial_body(const BwdBatch &batch, int bl
     const int64_t lda = pb.d.lda, ldb = pb.d.ldb, R = pb.d.R;
     const int n1 = pb.d.n1, n2 = pb.d.n2, chunk_rows = pb.chunk_rows;
     float *__restrict__ slabs = pb.slabs;
-    float *__restrict__ colsum_slabs = pb.d.d_colsum ? pb.cslabs : nullptr;
-    const float *__restrict__ cw = pb.d.d_colsum ? pb.d.d_colsum_weight : nullptr;
+    // the column sum is a function of the A rows alone: the workgroup of the first pair forms it
+    float *__restrict__ colsum_slabs = (pb.d.d_colsum && pair_z == 0) ? pb.cslabs : nullptr;
+    const float *__restrict__ cw = colsum_slabs ? pb.d.d_colsum_weight : nullptr;
     int64_t rb = 0, re = R;
     if (range) { rb = range[0]; re = range[1]; }
     const int64_t r0 = rb + (int64_t)chunk * chunk_rows;
     const int64_t r1 = (r0 + chunk_rows < re) ? r0 + chunk_rows : re;
-    const int i_base = tile_y * TN1, j_base = tile_z * TN2;
+    const int i_base = tile_y * TN1, j_base = pair_z * ZT * TN2;
+    const bool tile1 = pair_z * ZT + 1 < n2_tiles;        // the pair's second tile exists
 
-    // loader geometry: A block = 32 rows x 16 float4 (2 per thread); B block = 32 rows x 32 float4 (4 per thread)
+    // loader geometry: A block = 32 rows x 16 float4 (2 per thread); a B tile likewise (BPS per thread and tile)
     const int a_row = tid >> 4, a_c4 = tid & 15;          // + 16 rows on the second pass
     const int b_row = tid / BC4, b_c4 = tid % BC4;        // + BRP rows per pass, BPS passes
     const bool a_col_ok = (i_base + a_c4 * 4) < n1;       // n1, n2 are multiples of 4
-    const bool b_col_ok = (j_base + b_c4 * 4) < n2;
-    float4 ra[2], rbv[BPS];
-    float rw = 1.f, rw_cur = 1.f;                          // the block in flight / the block in LDS
-    auto load_block = [&](int64_t row0) {
+    const bool b_col_ok0 = (j_base + b_c4 * 4) < n2;
+    const bool b_col_ok1 = tile1 && (j_base + TN2 + b_c4 * 4) < n2;
+    BwdStage P;                                            // the stage in flight
+    P.w = 1.f;
+    float rw_cur = 1.f;                                    // the weights of the stage in LDS
+    auto load_block = [&](BwdStage &g, int64_t row0) {
         if (cw && tid < TRB) {
             const int64_t r = row0 + tid;
-            rw = r < r1 ? cw[row_index ? (int64_t)row_index[r] : r] : 0.f;
+            g.w = r < r1 ? cw[row_index ? (int64_t)row_index[r] : r] : 0.f;
         }
 #pragma unroll
         for (int p = 0; p < 2; ++p) {
             const int64_t r = row0 + a_row + 16 * p;
-            ra[p] = (a_col_ok && r < r1) ? *reinterpret_cast<const float4 *>(A + r * lda + i_base + a_c4 * 4)
-                                         : make_float4(0.f, 0.f, 0.f, 0.f);
+            g.a[p] = (a_col_ok && r < r1) ? *reinterpret_cast<const float4 *>(A + r * lda + i_base + a_c4 * 4)
+                                          : make_float4(0.f, 0.f, 0.f, 0.f);
         }
 #pragma unroll
         for (int p = 0; p < BPS; ++p) {
             const int64_t r = row0 + b_row + BRP * p;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (b_col_ok && r < r1) {
+            float4 v0 = make_float4(0.f, 0.f, 0.f, 0.f), v1 = v0;
+            if ((b_col_ok0 || b_col_ok1) && r < r1) {
                 const int64_t br = row_index ? (int64_t)row_index[r] : r;
-                v = *reinterpret_cast<const float4 *>(B + br * ldb + j_base + b_c4 * 4);
+                const float *src = B + br * ldb + j_base + b_c4 * 4;
+                if (b_col_ok0) v0 = *reinterpret_cast<const float4 *>(src);
+                if (b_col_ok1) v1 = *reinterpret_cast<const float4 *>(src + TN2);
             }
-            rbv[p] = v;
+            g.b[0][p] = v0;
+            g.b[1][p] = v1;
         }
     };
-    auto store_block = [&](int buf) {
-        rw_cur = rw;
+    auto store_block = [&](const BwdStage &g, int abuf) {
+        rw_cur = g.w;
 #pragma unroll
         for (int p = 0; p < 2; ++p)
-            *reinterpret_cast<float4 *>(&As[buf][(a_row + 16 * p) * TN1 + a_c4 * 4]) = ra[p];
+            *reinterpret_cast<float4 *>(&As[abuf][(a_row + 16 * p) * TN1 + a_c4 * 4]) = g.a[p];
 #pragma unroll
-        for (int p = 0; p < BPS; ++p)
-            *reinterpret_cast<float4 *>(&Bs[buf][(b_row + BRP * p) * TN2 + b_c4 * 4]) = rbv[p];
+        for (int p = 0; p < BPS; ++p) {
+            *reinterpret_cast<float4 *>(&Bs[0][(b_row + BRP * p) * TN2 + b_c4 * 4]) = g.b[0][p];
+            if (tile1) *reinterpret_cast<float4 *>(&Bs[1][(b_row + BRP * p) * TN2 + b_c4 * 4]) = g.b[1][p];
+        }
     };
 
     const int wi = (wave & 1) * 32, wj = (wave >> 1) * (TN2 / 2);
     const int li = lane & 31, lk = lane >> 5;
-    // 64-column problems (the single-modal heads) fill half of the 128-column tile: the waves of the empty half do not
-    // multiply zeros or write them (the reduce never reads the padding columns)
-    const bool wave_on = (j_base + wj) < n2;
-    const bool half1_on = BNJ > 1 && (j_base + wj + 32) < n2;
+    // a problem narrower than its tiles: the waves of an empty half do not multiply zeros or write them (the reduce never reads
+    // the padding columns)
+    const bool wave_on0 = (j_base + wj) < n2;
+    const bool wave_on1 = tile1 && (j_base + TN2 + wj) < n2;
     v16f acc0 = {0}, acc1 = {0};
     float csum = 0.f;                                      // threads 0..63: column sum of A[:, i_base + tid]
-    int buf = 0;
-    if (r0 < r1) {
-        load_block(r0);
-        store_block(0);
-    }
-    __syncthreads();
-    for (int64_t row0 = r0; row0 < r1; row0 += TRB) {
-        const bool more = (row0 + TRB) < r1;
-        if (more) load_block(row0 + TRB);                  // in flight during the MFMAs below
-        const float *as = As[buf], *bs = Bs[buf];
-        if (wave_on) {
+    auto multiply = [&](int abuf) {
+        const float *as = As[abuf], *bs0 = Bs[0], *bs1 = Bs[1];
+        if (wave_on1) {                                    // (wave_on1 implies wave_on0)
 #pragma unroll
             for (int kk = 0; kk < TRB; kk += 2) {
                 const float a = as[(kk + lk) * TN1 + wi + li];
-                const float b0 = bs[(kk + lk) * TN2 + wj + li];
+                const float b0 = bs0[(kk + lk) * TN2 + wj + li];
+                const float b1 = bs1[(kk + lk) * TN2 + wj + li];
                 acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b0, acc0, 0, 0, 0);
-                if (BNJ > 1) {
-                    const float b1 = bs[(kk + lk) * TN2 + wj + (BNJ > 1 ? 32 : 0) + li];
-                    acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b1, acc1, 0, 0, 0);
-                }
+                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b1, acc1, 0, 0, 0);
+            }
+        } else if (wave_on0) {
+#pragma unroll
+            for (int kk = 0; kk < TRB; kk += 2) {
+                const float a = as[(kk + lk) * TN1 + wi + li];
+                const float b0 = bs0[(kk + lk) * TN2 + wj + li];
+                acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b0, acc0, 0, 0, 0);
             }
         }
         if (colsum_slabs && tid < TN1) {
@@ -130,21 +142,34 @@ __device__ __forceinline__ void bwd_w_partial_body(const BwdBatch &batch, int bl
                 for (int k = 0; k < TRB; ++k) csum += as[k * TN1 + tid];
             }
         }
-        if (more) store_block(buf ^ 1);
+    };
+    if (r0 < r1) {
+        load_block(P, r0);
+        store_block(P, 0);
+    }
+    __syncthreads();
+    int buf = 0;
+    for (int64_t row0 = r0; row0 < r1; row0 += TRB) {
+        const bool more = (row0 + TRB) < r1;
+        if (more) load_block(P, row0 + TRB);               // in flight during the MFMAs below
+        multiply(buf);
+        if (!more) break;
+        __syncthreads();                                   // every wave is done with Bs
+        store_block(P, buf ^ 1);
         __syncthreads();
         buf ^= 1;
     }
     const int n1_pad = n1_tiles * TN1, n2_pad = n2_tiles * TN2;
     float *slab = slabs + (size_t)chunk * n1_pad * n2_pad;
-    if (wave_on) {
+    if (wave_on0) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int row = i_base + wi + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
             slab[(size_t)row * n2_pad + j_base + wj + li] = acc0[r];
-            if (half1_on) slab[(size_t)row * n2_pad + j_base + wj + 32 + li] = acc1[r];
+            if (wave_on1) slab[(size_t)row * n2_pad + j_base + TN2 + wj + li] = acc1[r];
         }
     }
-    if (colsum_slabs && tile_z == 0 && tid < TN1) colsum_slabs[(size_t)chunk * n1_pad + i_base + tid] = csum;
+    if (colsum_slabs && tid < TN1) colsum_slabs[(size_t)chunk * n1_pad + i_base + tid] = csum;
 }
 
 // lane q of an output element's four: chunks q, q+4, q+8, ... in that order, four loads in flight
@@ -303,7 +328,7 @@ static inline int bwd_w_build_batch(const elimrec_linear_bwd_desc *descs, int n,
         pb.d = d;
         bwd_w_dims(d.R, d.n1, d.n2, pb.chunk_rows, pb.chunks, pb.t1, pb.t2);
         pb.first_block = blocks;
-        blocks += pb.chunks * pb.t1 * pb.t2;
+        blocks += pb.chunks * pb.t1 * ((pb.t2 + ZT - 1) / ZT);
         pb.slabs = (float *)ws;
         pb.cslabs = pb.slabs + (size_t)pb.chunks * pb.t1 * TN1 * pb.t2 * TN2;
         ws += bwd_w_bytes(d.R, d.n1, d.n2);

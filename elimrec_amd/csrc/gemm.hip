@@ -166,14 +166,15 @@ __global__ __launch_bounds__(256) void linear_fwd_kernel(FwdBatch batch) {
 
 // --------------------------------------------------------------------------------- weight grad
 // out[i, j] = sum_r A[r, i] * B[idx(r), j]   (A^T . B; the reduction runs over ROWS).
-// A workgroup owns one chunk of rows and one 64 x TN2 output tile (4 waves x TN2/64 MFMA tiles).
-// Rows are staged 32 at a time through LDS with 16-byte loads (a row of A or B is contiguous),
-// double-buffered: the global loads of block t+1 are in flight while block t feeds the MFMAs.
+// A workgroup owns one chunk of rows and a pair of adjacent 64 x TN2 output tiles (4 waves x one MFMA tile of each):
+// the chunk's A rows are fetched and staged once for both (bwd_w.h).
+// Rows are staged 32 at a time through LDS with 16-byte loads (a row of A or B is contiguous);
+// the global loads of block t+1 are in flight while block t feeds the MFMAs.
 // MFMA operands come straight from the row-major LDS image: lane (i, k) of the A operand is
 // As[k][i0 + i] -- consecutive lanes, consecutive addresses, no transpose anywhere.
 // Each workgroup writes its partial tile to slab[chunk]; slabs are summed in chunk order
 // (reduce_slabs_kernel), so the result is bitwise reproducible.
-__global__ __launch_bounds__(256) void linear_bwd_w_partial_kernel(BwdBatch batch) {
+__global__ __launch_bounds__(256, 5) void linear_bwd_w_partial_kernel(BwdBatch batch) {      // 32 KB of LDS: five per CU
     __shared__ float As[2][TRB * TN1];
     __shared__ float Bs[2][TRB * TN2];
     bwd_w_partial_body(batch, (int)blockIdx.x, As, Bs);
