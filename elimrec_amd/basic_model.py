@@ -8,7 +8,7 @@ from torch import nn
 
 from . import ops
 from .evaluator import ProxyEvaluator, UniEvaluator
-from .reports import AudienceReport, BaselineReport, CalibrationReport, ClusterReport, CoNeighbourReport, DiversifyReport, EffectReport, GeometryReport, HistoryReport, ListReport, NeighbourReport, RankReport, SignificanceReport
+from .reports import AudienceReport, BaselineReport, CalibrationReport, ClusterReport, ColdStartReport, CoNeighbourReport, DiversifyReport, EffectReport, GeometryReport, HistoryReport, ListReport, NeighbourReport, RankReport, SignificanceReport
 
 
 
@@ -193,6 +193,17 @@ class BasicModel(nn.Module):
             self.baseline_reporter = BaselineReport(dataset, train, dataset.get_user_test_dict(), config["topks"], metric=config["metric"],
                                                     sources=sources, neighbours=n_near, measure=base_measure,
                                                     group_view=config["group_view"], list_k=k_base)
+        # --coldstart_report=K (CLI-only, default 0 = off): the cold test items (no training interaction, a test interaction) as
+        # trained, folded in from their content and folded in with the mean id row -- pair means of rank, pct, rr and hit@K for the
+        # topks and K, overall and per user group (reports.ColdStartReport)
+        k_cold = int(config["coldstart_report"]) if "coldstart_report" in config else 0
+        if k_cold < 0:
+            raise ValueError("coldstart_report must be 0 (off) or a K for hit@K")
+        self.coldstart_reporter = None
+        if k_cold:
+            ks = [int(k) for k in config["topks"]]
+            self.coldstart_reporter = ColdStartReport(dataset, train, dataset.get_user_test_dict(), ks + [k_cold] * (k_cold not in ks),
+                                                      group_view=config["group_view"])
         self.infonce_criterion = nn.CrossEntropyLoss()          # BasicModel.py:32
 
     def getFileName(self):

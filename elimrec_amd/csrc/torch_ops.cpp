@@ -18,6 +18,8 @@
 //       column means, float64 sums in listed order (the indices are checked on the host first: a synchronisation)
 //   rank_targets(scores f32[B x I], tgt_ptr i64[B+1], tgt_items i32) -> i32[n_targets]: the 0-based position of every listed item in
 //       its row's full ranking by (score desc, id asc), -1 at -inf (the lists are checked on the host first: a synchronisation)
+//   rank_values(scores f32[B x I], val_ptr i64[B+1], vals f32, skip i32?) -> i32[n_vals]: #{j != skip: scores[b, j] >= v}, where a new
+//       item of that score would land in the row's full ranking; -1 for a value that is not finite (csrc/coldstart.hip)
 //   list_pair_cosine(table f32[n x blocks*d], sqnorm f32[n x blocks], lists i32[B x K], blocks) -> f32[B x blocks]: per list and
 //       column block the mean pairwise cosine of the listed rows (entries outside [0, n) are not listed; NaN below two)
 //   list_exposure(lists i32[B x K], n_rows) -> i32[n_rows]: how often every row is listed
@@ -408,6 +410,34 @@ at::Tensor rank_targets(const at::Tensor &scores, const at::Tensor &tgt_ptr, con
     check(elimrec_rank_targets(sc.data_ptr<float>(), B, I, sc.stride(0), tp.data_ptr<int64_t>(), ti.data_ptr<int32_t>(), n,
                                out.data_ptr<int32_t>(), cur_stream()),
           "rank_targets");
+    return out;
+}
+
+// ---- insertion ranks by value: where an item outside the block would land in each row's full ranking
+at::Tensor rank_values(const at::Tensor &scores, const at::Tensor &val_ptr, const at::Tensor &vals, const c10::optional<at::Tensor> &skip) {
+    need(scores, "scores", at::kFloat, 2);
+    const at::Tensor sc = scores.stride(1) == 1 ? scores : scores.contiguous();
+    need(val_ptr, "val_ptr", at::kLong, 1); need(vals, "vals", at::kFloat, 1);
+    const at::Tensor vp = val_ptr.contiguous(), v = vals.contiguous();
+    const int64_t B = sc.size(0), I = sc.size(1), n = v.numel();
+    TORCH_CHECK(vp.numel() == B + 1, "elimrec::rank_values: val_ptr needs B + 1 = ", B + 1, " entries, got ", vp.numel());
+    checked_csr(vp, v, B, "rank_values", "val_ptr", "vals");
+    at::Tensor sk;
+    if (skip.has_value() && skip->defined()) {
+        need(*skip, "skip", at::kInt, 1);
+        sk = skip->contiguous();
+        TORCH_CHECK(sk.numel() == n, "elimrec::rank_values: skip needs one entry per value (", n, "), got ", sk.numel());
+        if (n) {
+            const int64_t lo = sk.min().item<int64_t>(), hi = sk.max().item<int64_t>();
+            TORCH_CHECK_INDEX(lo >= -1 && hi < I, "elimrec::rank_values: skipped columns span [", lo, ", ", hi, "], the block has ", I,
+                              " columns (-1: none)");
+        }
+    }
+    at::Tensor out = at::empty({n}, v.options().dtype(at::kInt));
+    if (n == 0 || B == 0) return out;
+    check(elimrec_rank_values(sc.data_ptr<float>(), B, I, sc.stride(0), vp.data_ptr<int64_t>(), v.data_ptr<float>(),
+                              sk.defined() ? sk.data_ptr<int32_t>() : nullptr, n, out.data_ptr<int32_t>(), cur_stream()),
+          "rank_values");
     return out;
 }
 
@@ -979,6 +1009,7 @@ TORCH_LIBRARY(elimrec, m) {
     m.def("score_candidates(Tensor Y, int U, int I, Tensor users, int d, int S, int head_mask, int fusion_mode, int predict_type, Tensor cand_ptr, Tensor cand_items, int width) -> Tensor");
     m.def("score_effects(Tensor Y, int U, int I, Tensor users, int d, int S, int head_mask, int fusion_mode, Tensor cand_ptr, Tensor cand_items, int width) -> Tensor");
     m.def("rank_targets(Tensor scores, Tensor tgt_ptr, Tensor tgt_items) -> Tensor");
+    m.def("rank_values(Tensor scores, Tensor val_ptr, Tensor vals, Tensor? skip) -> Tensor");
     m.def("cosine_topk(Tensor table, Tensor sqnorm, Tensor query_rows, int K, bool exclude_self) -> (Tensor, Tensor)");
     m.def("audience_topk(Tensor Y, int U, int I, Tensor items, Tensor? excl_ptr, Tensor? excl_users, int d, int S, int head_mask, int fusion_mode, "
           "int predict_type, int K, Tensor? sqnorm, Tensor? row_sum, int I_total) -> (Tensor, Tensor)");
@@ -1024,6 +1055,7 @@ TORCH_LIBRARY_IMPL(elimrec, CUDA, m) {
     m.impl("score_candidates", &score_candidates);
     m.impl("score_effects", &score_effects);
     m.impl("rank_targets", &rank_targets);
+    m.impl("rank_values", &rank_values);
     m.impl("cosine_topk", &cosine_topk);
     m.impl("audience_topk", &audience_topk);
     m.impl("list_overlap", &list_overlap);

@@ -53,6 +53,20 @@ def classes_from_clusters(assign, n_clusters):
     return np.where(a < 0, np.int32(n_clusters), a).astype(np.int32)
 
 
+class NewItems(object):
+    """Items folded in from content (EliMRec.fold_in_items), on the device: rows [Q x Cy] -- the rows the cached item table would
+    hold for them --, table [U + Q x Cy] = the cached user rows, then the new rows (a catalogue of Q items to the scorers), sqn its
+    block norms [U + Q x 1 + S], and version = the model's table version the rows were computed against: a handle used after the
+    cached tables changed raises. New item q carries id num_items + q wherever ids are merged with the catalogue's."""
+
+    def __init__(self, rows, table, sqn, version, num_users):
+        self.rows, self.table, self.sqn, self.version, self.num_users = rows, table, sqn, int(version), int(num_users)
+        self.n_items = int(rows.shape[0])
+
+    def __len__(self):
+        return self.n_items
+
+
 KNN_LIST_BLOCK = 4096                    # items per launch when neighbour_lists builds the lists of the whole catalogue
 KnnLists = collections.namedtuple("KnnLists", ("ids", "scores", "votes"))
 HistorySupport = collections.namedtuple("HistorySupport", ("items", "history", "scores", "count", "mean"))
@@ -740,6 +754,7 @@ class EliMRec(BasicModel):
             blk = slice((h + 1) * d, (h + 2) * d)
             head.append((Out[:, blk], W["s_dense_%s.weight" % m], W["s_dense_%s.bias" % m], Y[:, blk]))
         ops.linear_fwd_batched(head)
+        self._table_W = W                         # the weights these tables were built with (fold_in_items reads the same ones)
         self._publish_cache(Y, dirty=self._tables_dirty)
 
     def _propagate(self, csr, X0, t0, t1, out):
@@ -877,6 +892,11 @@ class EliMRec(BasicModel):
         ops.segment_plan(all_keys, self.num_users, self.num_users + self.num_items, ws["active_rows"][:n], ws["seg_info"],
                          ws["slot_seg"][:n], ws["plan_ws"])
         self._compute_tables(ws)
+        # the tables were built with the live weights, which the optimizer step that follows replaces: keep a copy of the projection
+        # weights for fold_in_items, as the column-shard engine's update does (one device copy of the non-embedding parameters)
+        if "snap" in ws:
+            ws["snap"].copy_(ws["flat_param"][ws["tail_off"]:])
+            self._table_W = ws["snap_views"]
         ops.bpr_head(ws["Y"], self.num_users, self.num_items, users, pos, neg, self.latent_dim,
                      self._last_block_weights, ws["loss_rows"], grad_rows, ws["keys_scratch"] if need_grad else None)
         loss = torch.empty((), dtype=torch.float32, device=self._device())
@@ -2065,6 +2085,272 @@ class EliMRec(BasicModel):
         ops.list_calibration(out_idx, class_of, C, torch.empty(n, C, dtype=torch.float32, device=dev), target=targets_t, smooth=smooth,
                              out_kl=kl)
         return out_idx.cpu(), scores.cpu(), kl.cpu()
+
+    # ------------------------------------------------------------------ cold start: items folded in from content
+    def _new_item_inputs(self, features, id_rows, normalized):
+        """The host checks of fold_in_items, all before anything touches the device: ({letter: float32 [Q x D_m] host tensor,
+        normalised as the model's own buffer is}, id rows float32 [Q x d], Q)."""
+        if not isinstance(features, dict) or set(features) != set(self._mods):
+            raise ValueError("features must be a dict with exactly the heads %s, got %s"
+                             % ("/".join(self._mods), sorted(features) if isinstance(features, dict) else type(features).__name__))
+
+        def host(x, what, width):
+            t = x.detach().cpu() if isinstance(x, torch.Tensor) else torch.from_numpy(np.asarray(x))
+            if not t.is_floating_point() or t.dim() != 2 or t.shape[1] != width:
+                raise ValueError("%s must be a float array [Q x %d], got %s %s" % (what, width, t.dtype, tuple(t.shape)))
+            t = t.float().contiguous()
+            if not bool(torch.isfinite(t).all()):
+                raise ValueError("%s holds an entry that is not finite" % what)
+            return t
+
+        feats, Q = {}, None
+        for m in self._mods:
+            t = host(features[m], "features[%r]" % m, getattr(self, m + "_dense").weight.shape[1])
+            if Q is not None and t.shape[0] != Q:
+                raise ValueError("features[%r] has %d rows, the other heads have %d" % (m, t.shape[0], Q))
+            Q = t.shape[0]
+            word_bag = m == "t" and self.dataset_name == "tiktok" and "feature_modalities" not in self.config
+            feats[m] = t if normalized or word_bag else F.normalize(t, dim=1).contiguous()     # (:377-378: the word bag stays as it is)
+        ids = torch.zeros(Q, self.latent_dim) if id_rows is None else host(id_rows, "id_rows", self.latent_dim)
+        if ids.shape[0] != Q:
+            raise ValueError("id_rows has %d rows, the features have %d" % (ids.shape[0], Q))
+        return feats, ids, Q
+
+    def _whole_tables(self, what):
+        """_cached_tables for the cold-start readers: single GPU, whole tables -- lean and item-sharded tables are refused."""
+        msg = "%s needs the whole cached tables on this rank; the tables are item-sharded or lean" % what
+        if self.__dict__.get("_lean") or self.__dict__.get("_wide"):
+            raise CandidateScoringError(msg)
+        return self._cached_tables(what + " needs", msg)
+
+    def _check_new(self, new):
+        if not isinstance(new, NewItems) or new.num_users != self.num_users:
+            raise TypeError("`new` must be the NewItems handle of this model's fold_in_items()")
+        if new.n_items and new.version != getattr(self, "_table_version", 0):
+            raise RuntimeError("the cached tables changed since these items were folded in (table version %d, now %d): "
+                               "call fold_in_items() again" % (new.version, getattr(self, "_table_version", 0)))
+
+    @torch.no_grad()
+    def fold_in_items(self, features, id_rows=None, normalized=False):
+        """Items that arrived after the graph was built, from their content alone -> NewItems (rows the cached item table would
+        hold for them, on the device). features: dict head letter -> float [Q x D_m], exactly the letters of self._mods;
+        normalized=False row-normalises them as the model normalises its own buffers (F.normalize, eps 1e-12; tiktok's word-bag
+        t_feat is left alone), True takes every row as given. id_rows [Q x d] or None = zeros: a new item has no trained id row.
+        A node without edges has the closed-form layer mean kappa x0 (reports.isolated_row_scale), so Out_m = (kappa F_m) W_m^T +
+        kappa b_m and the id block = kappa id_rows; Y_new = the item fusion Linear on Out, plus the s_dense heads on its blocks --
+        two ops.linear_fwd_batched calls with the weights the cached tables were built with (after a training step: the copy
+        taken before the update). A row depends on its own inputs only. The checks and the normalisation run on the host, as the
+        model's own buffers are normalised there: device inputs come down for them and go up again (one round trip of Q rows). ValueError for a missing / extra head, a wrong width or a non-finite entry, before anything touches the device;
+        Q = 0 gives an empty handle without a launch."""
+        from .reports import isolated_row_scale
+        feats, ids, Q = self._new_item_inputs(features, id_rows, normalized)
+        U, d, Cy = self.num_users, self.latent_dim, self.Cy
+        if Q == 0:
+            dev = self._require_gpu()
+            return NewItems(torch.empty(0, Cy, dtype=torch.float32, device=dev), None, None, getattr(self, "_table_version", 0), U)
+        dev = self._whole_tables("fold_in_items()")
+        W = self.__dict__.get("_table_W")
+        if W is None:                 # (tables put there by hand, not by a forward of this model)
+            raise RuntimeError("fold_in_items() needs the weights the cached tables were built with: call bpr_loss or compute() first")
+        kappa = isolated_row_scale(str(self.config["adj_type"]), self.n_layers)
+        f32 = dict(dtype=torch.float32, device=dev)
+        out = torch.empty(Q, self.C, **f32)
+        out[:, :d] = ids.to(dev) * kappa
+        scale = torch.full((Q,), kappa, **f32)
+        zero = torch.zeros(Q, d, **f32)
+        ops.linear_fwd_batched([((feats[m].to(dev) * kappa).contiguous(), W[m + "_dense.weight"], W[m + "_dense.bias"],
+                                 out[:, (k + 1) * d:(k + 2) * d], scale, zero) for k, m in enumerate(self._mods)])
+        Y = self._ws["Y"]
+        table = torch.empty(U + Q, Cy, **f32)
+        table[:U] = Y[:U]
+        rows = table[U:]
+        wi = self._fusion_weights(W)[1]
+        head = [(out, wi, W["embedding_item_after_GCN.bias"], rows[:, :d])]
+        for h, m in enumerate(self._mods):
+            blk = slice((h + 1) * d, (h + 2) * d)
+            head.append((out[:, blk], W["s_dense_%s.weight" % m], W["s_dense_%s.bias" % m], rows[:, blk]))
+        ops.linear_fwd_batched(head)
+        sqn = ops.row_sqnorms(table, d, 1 + self.S, torch.empty(U + Q, 1 + self.S, **f32))
+        return NewItems(rows, table, sqn, self._table_version, U)
+
+    @torch.no_grad()
+    def predict_new_items_device(self, users, new, out):
+        """out [B x Q] (float32, unit column stride, on the device) <- every user's score of every new item under the current
+        predict type and fusion mode. The scorer predict_device runs, over the handle's table ([the users' rows ; the new rows]) as
+        ONE item shard of Q items (ops.score_topk_shard, phase 2): a folded copy of a catalogue item scores bit for bit what
+        predict() holds in the item's column. TIE's catalogue mean comes from the scorer's pass 1 over the TRAINED catalogue of
+        num_items items: the new items are not in it."""
+        self._check_new(new)
+        dev = self._whole_tables("predict_new_items()")
+        users = torch.as_tensor(users, device=dev).long().contiguous()
+        B, Q = users.numel(), new.n_items
+        if not B or not Q:
+            return out
+        if tuple(out.shape) != (B, Q):
+            raise ValueError("out must be [%d x %d]" % (B, Q))
+        if ops.PREDICT_TYPES.get(self.predict_type, 0) == 2:
+            row_sum = self._catalogue_row_sum(dev, users, self.predict_type, self._block_sqnorms(dev))
+        else:
+            row_sum = torch.zeros(B, dtype=torch.float32, device=dev)
+        need = ops.score_workspace(B, self.num_users, Q, self.S, 1, topk_only=False, d=self.latent_dim)
+        if self._ws.get("new_score_ws") is None or self._ws["new_score_ws"].numel() < need:
+            self._ws["new_score_ws"] = torch.empty(need, dtype=torch.uint8, device=dev)
+        ops.score_topk_shard(new.table, self.num_users, Q, users, self.latent_dim, self.S, self._head_mask(), self.fusion_mode,
+                             self.predict_type, self._ws["new_score_ws"], 2, row_sum, self.num_items, 0, scores=out, sqnorm=new.sqn)
+        return out
+
+    def predict_new_items(self, user_ids, new):
+        """Scores of the new items: CPU fp32 [len(user_ids) x Q] -- what predict() would hold in the items' columns had they been
+        in the catalogue without an edge."""
+        dev = self._require_gpu()
+        ids = self._id_lists([user_ids], "user", self.num_users)[1]
+        out = torch.empty(ids.size, len(new), dtype=torch.float32, device=dev)
+        return self.predict_new_items_device(torch.from_numpy(ids).to(dev), new, out).cpu()
+
+    def audience_new_items(self, new, k, exclude=None):
+        """audience() of the new items: Audience(users CPU int32 [Q x k], scores CPU fp32 [Q x k]) by (score descending, user id
+        ascending) under the current predict type; `exclude` = dict new item q -> user ids to leave out. 1 <= k <= 256."""
+        k = int(k)
+        if not 1 <= k <= ops.AUDIENCE_MAX_K:
+            raise ValueError("k must lie in [1, %d]" % ops.AUDIENCE_MAX_K)
+        self._check_new(new)
+        Q, U = new.n_items, self.num_users
+        ptr, flat = self._excluded(exclude, range(Q), "user", U)
+        if not Q:
+            return Audience(torch.empty(0, k, dtype=torch.int32), torch.empty(0, k, dtype=torch.float32))
+        dev = self._whole_tables("audience_new_items()")
+        query = ops.AudienceQuery(np.arange(Q, dtype=np.int64), Q, U, dev, ptr if flat.size else None, flat if flat.size else None)
+        idx = torch.empty(Q, k, dtype=torch.int32, device=dev)
+        val = torch.empty(Q, k, dtype=torch.float32, device=dev)
+        tie = ops.PREDICT_TYPES.get(self.predict_type, 0) == 2
+        row_sum = self._audience_row_sum(dev, self._block_sqnorms(dev)) if tie else None
+        ops.audience_topk(new.table, U, Q, query, self.latent_dim, self.S, self._head_mask(), self.fusion_mode, self.predict_type, k,
+                          idx, val, sqnorm=new.sqn, row_sum=row_sum, I_total=self.num_items)
+        return Audience(idx.cpu(), val.cpu())
+
+    NEW_ITEM_QUERY_BLOCK = 64                # new rows per cosine_topk call of similar_to_new_items
+
+    def similar_to_new_items(self, new, k, space="fused"):
+        """The k CATALOGUE items closest to each new item by cosine: Neighbours(ids CPU int32 [Q x k], scores CPU fp32 [Q x k]) by
+        (score descending, id ascending); space as similar_items. ops.cosine_topk over [the catalogue's block ; a block of new rows]
+        with the new rows as the queries, each leaving out every new row of its block."""
+        k = int(k)
+        if not 1 <= k <= ops.KNN_MAX_K:
+            raise ValueError("k must lie in [1, %d]" % ops.KNN_MAX_K)
+        h = self._neighbour_space(space)
+        self._check_new(new)
+        Q, U, I, d = new.n_items, self.num_users, self.num_items, self.latent_dim
+        if not Q:
+            return Neighbours(torch.empty(0, k, dtype=torch.int32), torch.empty(0, k, dtype=torch.float32))
+        dev = self._whole_tables("similar_to_new_items()")
+        sqn = self._block_sqnorms(dev)
+        nb = self.NEW_ITEM_QUERY_BLOCK
+        table = torch.empty(I + nb, d, dtype=torch.float32, device=dev)
+        norms = torch.empty(I + nb, dtype=torch.float32, device=dev)
+        table[:I] = self._ws["Y"][U:, h * d:(h + 1) * d]
+        norms[:I] = sqn[U:, h]
+        idx = torch.empty(Q, k, dtype=torch.int32, device=dev)
+        val = torch.empty(Q, k, dtype=torch.float32, device=dev)
+        for a in range(0, Q, nb):
+            n = min(nb, Q - a)
+            table[I:I + n] = new.rows[a:a + n, h * d:(h + 1) * d]
+            norms[I:I + n] = new.sqn[U + a:U + a + n, h]
+            block = np.arange(I, I + n, dtype=np.int64)
+            query = ops.NeighbourQuery(block, I + n, dev, np.arange(n + 1, dtype=np.int64) * n, np.tile(block, n))
+            ops.cosine_topk(table[:I + n], norms[:I + n], query, k, idx[a:a + n], val[a:a + n], exclude_self=True)
+        return Neighbours(idx.cpu(), val.cpu())
+
+    def _train_mask(self, exclude, user_ids, dev):
+        tptr, tflat = self._excluded(exclude, user_ids, "item")
+        return (torch.from_numpy(tptr).to(dev), torch.from_numpy(tflat.astype(np.int32)).to(dev)) if tflat.size else (None, None)
+
+    RECOMMEND_MAX_K = 256                    # the longest list recommend_with_new merges (2 k candidates per row in topk_merge's LDS)
+
+    def recommend_with_new(self, user_ids, new, k, exclude=None):
+        """Each user's top-k over the catalogue AND the new items: CPU (ids int32 [B x k], scores fp32 [B x k]) by (score
+        descending, id ascending), new item q under id num_items + q; `exclude` = dict user -> catalogue item ids left out, as
+        explain() takes it. The user's catalogue top-k (predict_device) merged with its best min(k, Q) new items (a stable sort
+        of predict_new_items_device's block) by ops.topk_merge. 1 <= k <= min(RECOMMEND_MAX_K = 256, num_items). A user whose
+        unmasked catalogue is shorter than k gets masked items at -inf from predict_device: they are no candidates of the merge,
+        so new items take those places, and -1 / -inf remain only where catalogue and new items together are fewer than k."""
+        k = int(k)
+        if not 1 <= k <= min(self.RECOMMEND_MAX_K, self.num_items):
+            raise ValueError("k must lie in [1, %d]" % min(self.RECOMMEND_MAX_K, self.num_items))
+        self._check_new(new)
+        ids = self._id_lists([user_ids], "user", self.num_users)[1]
+        dev = self._require_gpu()
+        masked = self._train_mask(exclude, ids, dev)
+        B, Q = ids.size, new.n_items
+        if not B:
+            return torch.empty(0, k, dtype=torch.int32), torch.empty(0, k, dtype=torch.float32)
+        self._whole_tables("recommend_with_new()")
+        users = torch.from_numpy(ids).to(dev)
+        idx, val = self.predict_device(users, top_k=k, train_ptr=masked[0], train_items=masked[1])
+        idx = idx.masked_fill(val == float("-inf"), -1)          # a masked item behind a short catalogue is no candidate
+        if not Q:
+            return idx.cpu(), val.cpu()
+        block = self.predict_new_items_device(users, new, torch.empty(B, Q, dtype=torch.float32, device=dev))
+        kq = min(k, Q)
+        nval, nidx = torch.sort(block, dim=1, descending=True, stable=True)     # equal scores keep q ascending
+        cand_val = torch.cat((val, nval[:, :kq]), dim=1).contiguous()
+        cand_idx = torch.cat((idx, (nidx[:, :kq] + self.num_items).int()), dim=1).contiguous()
+        out_idx = torch.empty(B, k, dtype=torch.int32, device=dev)
+        out_val = torch.empty(B, k, dtype=torch.float32, device=dev)
+        ops.topk_merge(cand_val, cand_idx, k, out_idx, out_val)
+        return out_idx.cpu(), out_val.cpu()
+
+    RANK_BLOCK_BYTES = 2 << 30               # the [users x items] score block of rank_new_items stays within it (RankReport.block_bytes)
+
+    @torch.no_grad()
+    def rank_new_items_device(self, users, new, train_ptr=None, train_items=None, skip=None, among=False):
+        """Where every new item would land in each user's FULL ranking: int32 [B x Q] on the device, rank[b, q] = the number of
+        catalogue items user b scores at least as high as new item q (the new item goes behind equal scores: its id is the larger
+        one), the train items (CSR on the device) masked. One predict_device call into a [B x I] block, predict_new_items_device,
+        then ops.rank_values (csrc/coldstart.hip). skip: int [Q] (host), per new item a catalogue column that is not counted (its
+        own entry when a catalogue item was folded in again; -1: none). among: add the number of OTHER new items that beat q by
+        (score descending, q ascending)."""
+        self._check_new(new)
+        dev = self._whole_tables("rank_new_items()")
+        users = torch.as_tensor(users, device=dev).long().contiguous()
+        B, Q, I = users.numel(), new.n_items, self.num_items
+        rank = torch.empty(B, Q, dtype=torch.int32, device=dev)
+        if skip is not None:
+            skip = np.asarray(skip).reshape(-1)
+            if skip.size != Q or skip.dtype.kind not in "iu" or (skip.size and (skip.min() < -1 or skip.max() >= I)):
+                raise IndexError("skip needs one catalogue column in [0, %d) or -1 per new item (%d)" % (I, Q))
+        if not B or not Q:
+            return rank
+        lds = (I + 3) // 4 * 4                    # rows 16-byte aligned: the count takes its 16-byte loads
+        block = torch.empty(B, lds, dtype=torch.float32, device=dev)[:, :I]
+        self.predict_device(users, scores=block, train_ptr=train_ptr, train_items=train_items)
+        vals = self.predict_new_items_device(users, new, torch.empty(B, Q, dtype=torch.float32, device=dev))
+        val_ptr = np.arange(B + 1, dtype=np.int64) * Q
+        ops.rank_values(block, val_ptr, vals.view(-1), rank.view(-1), skip=None if skip is None else np.tile(skip.astype(np.int32), B))
+        if among:
+            order = torch.sort(vals, dim=1, descending=True, stable=True)[1]
+            place = torch.empty_like(order)
+            place.scatter_(1, order, torch.arange(Q, device=dev).expand(B, Q).contiguous())
+            rank += torch.where(rank >= 0, place.int(), torch.zeros_like(rank))
+        return rank
+
+    def rank_new_items(self, user_ids, new, exclude=None, among=False):
+        """The catalogue rank every new item would take: CPU int32 [len(user_ids) x Q], 0-based, under the current predict type;
+        `exclude` = dict user -> item ids masked out of the ranking (the train items, as rank_items takes it). Users go in blocks
+        whose score block stays within RANK_BLOCK_BYTES. among=True counts the other new items ranked above it as well."""
+        self._check_new(new)
+        ids = self._id_lists([user_ids], "user", self.num_users)[1]
+        tptr, tflat = self._excluded(exclude, ids, "item")
+        dev = self._require_gpu()
+        out = torch.empty(ids.size, len(new), dtype=torch.int32)
+        step = max(1, int(self.RANK_BLOCK_BYTES) // ((self.num_items + 3) // 4 * 16))
+        for a in range(0, ids.size, step):
+            b = min(a + step, ids.size)
+            masked = (None, None)
+            if tptr[b] > tptr[a]:
+                masked = (torch.from_numpy(tptr[a:b + 1] - tptr[a]).to(dev),
+                          torch.from_numpy(tflat[tptr[a]:tptr[b]].astype(np.int32)).to(dev))
+            out[a:b] = self.rank_new_items_device(torch.from_numpy(ids[a:b]).to(dev), new, masked[0], masked[1], among=among).cpu()
+        return out
 
     def predict(self, user_ids, candidate_items=None):
         """:96-113. CPU fp32 tensor [len(user_ids) x I]; `candidate_items` is ignored as in the reference."""

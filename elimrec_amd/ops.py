@@ -952,6 +952,45 @@ def rank_targets(scores, tgt_ptr, tgt_items, out):
     return out
 
 
+def rank_values(scores, val_ptr, vals, out, skip=None):
+    """elimrec_rank_values: out int32 [>= n_vals] <- where each listed value would land in its row's full ranking,
+    #{j != skip: scores[b, j] >= v}: a new item goes behind every catalogue item of equal score (its id is the larger one); -1 for
+    a value that is not finite. scores [B x I] float32, unit column stride, masked entries -inf (rank_targets' block; columns
+    beyond I of a padded block are not read). val_ptr int64 [B + 1] / vals float32: the values as CSR -- val_ptr a host array or a
+    tensor, checked on the host at every call (a synchronisation for a device tensor), vals a contiguous device tensor. skip
+    (optional): one column per value that is not counted -- the item's own catalogue entry -- or -1; a host array or a tensor,
+    checked on the host: a column outside [0, I) is an IndexError. Entries of out beyond n_vals are left alone. O(I log Q) per row
+    (csrc/coldstart.hip): RANK_VALUES_PER_PASS values are sorted per pass, RANK_VALUES_SEGMENT columns go to one workgroup."""
+    sp, lds = _rowmajor(scores, "scores")
+    B, I = scores.shape
+    vp = _dev(vals, "vals")
+    if vals.dim() != 1 or not vals.is_contiguous() or vals.device != scores.device:
+        raise ValueError("elimrec_amd.ops.rank_values: vals must be a contiguous 1-D tensor on the block's device")
+    n = int(vals.numel())
+    p = np.ascontiguousarray(_host(val_ptr), dtype=np.int64).reshape(-1)
+    if p.size != B + 1:
+        raise ValueError("elimrec_amd.ops.rank_values: val_ptr needs B + 1 = %d entries, got %d" % (B + 1, p.size))
+    if p[0] != 0 or p[-1] != n or (np.diff(p) < 0).any():
+        raise ValueError("elimrec_amd.ops.rank_values: val_ptr must ascend from 0 to len(vals) = %d" % n)
+    sk = None
+    if skip is not None:
+        s = _host(skip).reshape(-1)
+        _integer_ids(s, "rank_values", "skip")
+        if s.size != n:
+            raise ValueError("elimrec_amd.ops.rank_values: skip needs one entry per value (%d), got %d" % (n, s.size))
+        if s.size and (int(s.min()) < -1 or int(s.max()) >= I):
+            raise IndexError("elimrec_amd.ops.rank_values: skipped columns span [%d, %d], the block has %d columns (-1: none)"
+                             % (int(s.min()), int(s.max()), I))
+        sk = skip.contiguous() if isinstance(skip, torch.Tensor) and skip.is_cuda and skip.dtype == torch.int32 else _resident_ids(s, scores.device)
+    if not (isinstance(out, torch.Tensor) and out.dim() == 1 and out.is_contiguous() and out.numel() >= n):
+        raise ValueError("elimrec_amd.ops.rank_values: out must be a contiguous 1-D tensor of at least %d entries" % n)
+    ptr = val_ptr.contiguous() if isinstance(val_ptr, torch.Tensor) and val_ptr.is_cuda and val_ptr.dtype == torch.int64 \
+        else torch.from_numpy(p).to(scores.device)
+    _lib.check(_lib.load().elimrec_rank_values(sp, B, I, lds, _dev(ptr, "val_ptr", torch.int64), vp, _dev(sk, "skip", torch.int32), n,
+                                               _dev(out, "out", torch.int32), _stream()), "rank_values")
+    return out
+
+
 RANK_PAIR_COLUMNS = ("rank", "rr", "pct")
 RANK_USER_COLUMNS = ("auc", "mrr_full", "first_rank")
 
@@ -1001,6 +1040,10 @@ def __getattr__(name):
         return int(_lib.load().elimrec_rank_segment())
     if name == "RANK_TARGETS_PER_PASS":  # targets rank_targets stages per pass over a segment
         return int(_lib.load().elimrec_rank_targets_per_pass())
+    if name == "RANK_VALUES_SEGMENT":    # columns of a score row one workgroup of rank_values streams
+        return int(_lib.load().elimrec_rank_values_segment())
+    if name == "RANK_VALUES_PER_PASS":   # values rank_values sorts in LDS per pass over a segment
+        return int(_lib.load().elimrec_rank_values_per_pass())
     if name == "KNN_CHUNK":              # candidate rows one workgroup of cosine_topk streams
         return int(_lib.load().elimrec_cosine_topk_chunk())
     if name == "KNN_TILE":               # query rows one workgroup of cosine_topk holds (16 when K > 64)

@@ -114,6 +114,23 @@ def format_table(columns, labels, table):
     return "columns:\t%s" % "\t".join(str(c).ljust(12) for c in columns) + format_rows(labels, table)
 
 
+def isolated_row_scale(adj_type, L):
+    """kappa: the layer mean of a node WITHOUT edges is kappa x0, as the propagation kernels evaluate it in float32 (pure host
+    arithmetic). Adjacencies without a diagonal ('plain', 'gcmc', 'pre'): every hop gives the node a zero row, the mean is
+    (x0 + 0) * inv with inv = 1.0f / (L + 1). 'norm' and 'mean' (anything else, as create_adj_mat reads it) give an isolated node
+    the identity row, so the mean is the sum of L + 1 copies of x0 in hop order times inv. -> a Python float holding the float32."""
+    L = int(L)
+    if L < 0:
+        raise ValueError("L must not be negative, got %d" % L)
+    inv = np.float32(1.0) / np.float32(L + 1)
+    if adj_type in ("plain", "gcmc", "pre"):
+        return float(inv)
+    acc = np.float32(1.0)
+    for _ in range(L):
+        acc = np.float32(acc + np.float32(1.0))
+    return float(np.float32(acc * inv))
+
+
 class _Report(object):
     """What the reports share. A subclass names itself (`name`: its word in the messages and its --<name>_report switch), the model
     method it needs (`needs`), sets num_items / top_k where the model has to match them, and builds what it keeps on a device in
@@ -1738,3 +1755,170 @@ class BaselineReport(_Report):
                 table[s * G + g, Cs + 3:] = exposure_summary(counts.cpu().numpy(), [np.arange(self.num_items)])[0, 1:4]
         final = BaselineTables(self.columns, list(self.labels), table)
         return final, format_table(final.columns, final.labels, final.table)
+
+
+COLDSTART_VARIANTS = ("catalogue", "content", "mean_id")
+
+
+def cold_test_items(user_train_dict, user_test_dict, num_items):
+    """The cold test items of a split: catalogue items without a training interaction and with at least one test interaction ->
+    (their ids int64 ascending, the (user, item) test pairs on them in user_test_dict order)."""
+    counts = item_train_counts(user_train_dict, num_items)
+    pairs = [(u, int(i)) for u, items in user_test_dict.items() for i in items if 0 <= int(i) < num_items and counts[int(i)] == 0]
+    return np.unique(np.asarray([i for _, i in pairs], dtype=np.int64)), pairs
+
+
+def coldstart_columns(ks):
+    return ("items", "pairs", "rank", "pct", "rr") + tuple("hit@%d" % int(k) for k in ks)
+
+
+def coldstart_row(rank, n_cand, ks, n_items):
+    """One row of the cold-start table from the pairs' ranks and candidate counts (host, float64): the number of items and pairs,
+    then the pair means of rank, pct = rank / (n_cand - 1) (0 when n_cand <= 1), rr = 1 / (rank + 1) and hit@K = (rank < K)."""
+    rank, n_cand = np.asarray(rank, dtype=np.float64), np.asarray(n_cand, dtype=np.float64)
+    pct = np.where(n_cand > 1, rank / np.maximum(n_cand - 1.0, 1.0), 0.0)
+    cols = [rank, pct, 1.0 / (rank + 1.0)] + [(rank < k).astype(np.float64) for k in ks]
+    return np.asarray([float(n_items), float(rank.size)] + [float(c.mean()) if c.size else np.nan for c in cols])
+
+
+def format_coldstart(columns, labels, table):
+    """format_table, or the one line of a split without cold test items (columns = None)."""
+    if columns is None:
+        return "no cold test item in this split (every test item has a training interaction): nothing to report"
+    return format_table(columns, labels, table)
+
+
+class ColdStartReport(_Report):
+    """How the model serves items it has no interaction for (--coldstart_report=K): over the cold test items of the split (catalogue
+    items without a training interaction and with a test interaction) and the (test user, cold test item) pairs on them, the pair
+    means of the rank report's columns for three variants of the item's row:
+      catalogue  the item as trained -- its row of the cached table, with its never-updated id row (ops.rank_targets);
+      content    its row folded in from its features with a zero id row (EliMRec.fold_in_items, ops.rank_values, its own catalogue
+                 column not counted);
+      mean_id    the same with the mean embedding row of the items that have training interactions as its id row.
+    Ranks are exact, over the whole catalogue with the user's train items masked, under the model's current predict type. Tables:
+    [1 + user groups] blocks of one row per variant; the pair rows and their means come from ops.rank_pair_rows /
+    ops.group_metric_means. Users go in blocks whose score block stays within block_bytes."""
+
+    name, needs = "coldstart", "predict_new_items_device"
+
+    def __init__(self, dataset, user_train_dict, user_test_dict, top_k, group_view=None):
+        if not isinstance(user_train_dict, dict) or not isinstance(user_test_dict, dict):
+            raise TypeError("user_train_dict and user_test_dict must be dicts")
+        ks = [top_k] if isinstance(top_k, (int, np.integer)) and not isinstance(top_k, bool) else list(top_k)
+        if not ks or any(isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1 for k in ks):
+            raise ValueError("top_k must be a positive integer or a list of them, got %r" % (top_k,))
+        self.dataset = dataset
+        self.num_items = I = int(dataset.num_items)
+        self.user_pos_train = user_train_dict
+        self.user_pos_test = user_test_dict
+        self.ks = [int(k) for k in ks]
+        self.columns = coldstart_columns(self.ks)
+        self.block_bytes = 2 << 30
+        self.items, pairs = cold_test_items(user_train_dict, user_test_dict, I)
+        self.train_items = np.flatnonzero(item_train_counts(user_train_dict, I) > 0)
+        self.users, per_user = [], []
+        for u, i in pairs:
+            if not self.users or self.users[-1] != u:
+                self.users.append(u)
+                per_user.append([])
+            per_user[-1].append(i)
+        self.pair_ptr, self.pair_items, lens = ops.ragged(per_user, dtype=np.int32)
+        self.pair_user = np.repeat(np.arange(len(self.users), dtype=np.int64), lens)
+        self.pair_q = np.searchsorted(self.items, self.pair_items).astype(np.int64)         # position among the cold items
+        self.pair_n_cand = np.asarray([I - len(set(int(i) for i in user_train_dict.get(self.users[p], []))) for p in self.pair_user],
+                                      dtype=np.int32)
+        self.num_pairs = int(self.pair_items.size)
+        self.group_labels, self._user_pos = ([ALL], []) if not self.num_pairs else self._user_groups(self.users, user_train_dict, group_view)
+        self._pair_pos = [np.flatnonzero(np.isin(self.pair_user, p)) for p in self._user_pos]
+        self.group_items = [int(np.unique(self.pair_items[p]).size) for p in self._pair_pos]
+
+    @property
+    def block_users(self):
+        return max(1, int(self.block_bytes) // ((self.num_items + 3) // 4 * 16))
+
+    def _make_resident(self, device):
+        return dict(pair_n_cand=torch.from_numpy(self.pair_n_cand).to(device), groups=group_index(self._pair_pos, self.num_pairs, device))
+
+    def new_items(self, model, variant):
+        """The cold test items folded in from the model's own feature rows: variant 'content' (zero id rows) or 'mean_id'."""
+        feats = {m: getattr(model, m + "_feat")[torch.from_numpy(self.items).to(getattr(model, m + "_feat").device)] for m in model._mods}
+        ids = None
+        if variant == "mean_id":
+            model.plugin.sync_params()
+            w = model.embedding_item.weight.detach()
+            mean = w[torch.from_numpy(self.train_items).to(w.device)].double().mean(0).float() if self.train_items.size else w.new_zeros(w.shape[1])
+            ids = mean.expand(self.items.size, -1).contiguous()
+        return model.fold_in_items(feats, id_rows=ids, normalized=True)
+
+    def pair_ranks(self, model):
+        """The exact rank of every pair per variant under the model's current predict type: int32 [3 x num_pairs] on the device.
+        Per user block ONE predict_device call into a score block serves all three variants: ops.rank_targets over the pairs' own
+        columns, then one ops.rank_values call whose CSR lists, per user, the content values of its pairs and then the mean_id
+        values (gathered from predict_new_items_device's [users x cold items] blocks), each with its own column skipped."""
+        device = self._preflight(model)
+        V = len(COLDSTART_VARIANTS)
+        ranks = torch.empty(V, self.num_pairs, dtype=torch.int32, device=device)
+        new = [self.new_items(model, v) for v in COLDSTART_VARIANTS[1:]]
+        I, step = self.num_items, self.block_users
+        lds = (I + 3) // 4 * 4                    # rows 16-byte aligned: the counts take their 16-byte loads
+        for a in range(0, len(self.users), step):
+            b = min(a + step, len(self.users))
+            lo, hi = int(self.pair_ptr[a]), int(self.pair_ptr[b])
+            n = hi - lo
+            users = torch.as_tensor(np.asarray(self.users[a:b], dtype=np.int64)).to(device)
+            train = lists_csr(self.users[a:b], self.user_pos_train, device, cast=int)
+            train = train if train[1].numel() else (None, None)
+            block = torch.empty(b - a, lds, dtype=torch.float32, device=device)[:, :I]
+            model.predict_device(users, scores=block, train_ptr=train[0], train_items=train[1])
+            ptr = self.pair_ptr[a:b + 1] - lo
+            ops.rank_targets(block, ptr, self.pair_items[lo:hi], ranks[0, lo:hi])
+            # per user its pairs once per folded variant: list position = (V - 1) * ptr[u] + v * len(u) + (position among the user's pairs)
+            lens = np.diff(ptr)
+            first = np.repeat(ptr[:-1], lens)
+            within = np.arange(n, dtype=np.int64) - first
+            at = [torch.from_numpy((V - 1) * first + v * np.repeat(lens, lens) + within).to(device) for v in range(V - 1)]
+            rows = torch.from_numpy(self.pair_user[lo:hi] - a).to(device)
+            cols = torch.from_numpy(self.pair_q[lo:hi]).to(device)
+            vals = torch.empty((V - 1) * n, dtype=torch.float32, device=device)
+            skip = np.empty((V - 1) * n, dtype=np.int32)
+            for v, handle in enumerate(new):
+                scores = model.predict_new_items_device(users, handle, torch.empty(b - a, handle.n_items, dtype=torch.float32, device=device))
+                vals[at[v]] = scores[rows, cols]
+                skip[at[v].cpu().numpy()] = self.pair_items[lo:hi]
+            out = ops.rank_values(block, (V - 1) * ptr, vals, torch.empty((V - 1) * n, dtype=torch.int32, device=device), skip=skip)
+            for v in range(V - 1):
+                ranks[1 + v, lo:hi] = out[at[v]]
+        return ranks
+
+    def evaluate(self, model, ranks=None):
+        """(final, buf). final float32 [1 + user groups x 3 variants x columns] (columns: items, pairs, then the pair means of rank,
+        pct, rr, hit@K) -- or None for a split without cold test items, with the one line that says so as buf."""
+        if not self.num_pairs:
+            self._preflight(model)
+            return None, format_coldstart(None, None, None)
+        if ranks is None:
+            ranks = self.pair_ranks(model)
+        res = self._resident(ranks.device)
+        G, V, C = len(self.group_labels), len(COLDSTART_VARIANTS), len(self.columns)
+        final = np.zeros((G, V, C), dtype=np.float32)
+        order = [0, 2, 1] + list(range(3, 3 + len(self.ks)))           # rank_pair_rows gives rank, rr, pct, hit@K
+        for v in range(V):
+            rows = torch.empty(self.num_pairs, 3 + len(self.ks), dtype=torch.float32, device=ranks.device)
+            ops.rank_pair_rows(ranks[v].contiguous(), res["pair_n_cand"], self.ks, rows)
+            final[:, v, 2:] = group_table(rows, res["groups"], G)[:, order]
+        final[:, :, 0] = np.asarray(self.group_items, dtype=np.float32)[:, None]
+        final[:, :, 1] = np.asarray([p.size for p in self._pair_pos], dtype=np.float32)[:, None]
+        return final, self._format(self.columns, final)
+
+    def _format(self, columns, final):
+        labels = [(v + ":").ljust(12) for v in COLDSTART_VARIANTS]
+        return "\n".join(("%s\n" % g.strip() if len(self.group_labels) > 1 else "") + format_coldstart(columns, labels, final[k])
+                         for k, g in enumerate(self.group_labels))
+
+    def shift(self, final_a, final_b):
+        """TE -> TIE: (final_b - final_a over the mean columns, buf) with columns d_<column>."""
+        if final_a is None or final_b is None:
+            return None, format_coldstart(None, None, None)
+        delta = (final_b - final_a)[:, :, 2:]
+        return delta, self._format(tuple("d_" + c for c in self.columns[2:]), delta)

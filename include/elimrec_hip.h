@@ -586,6 +586,22 @@ int elimrec_rank_targets(const float *d_scores, int64_t B, int64_t I, int64_t ld
                          const int32_t *d_tgt_items, int64_t n_targets, int32_t *d_rank, void *stream);
 int elimrec_rank_segment(void);
 int elimrec_rank_targets_per_pass(void);
+/* Insertion ranks by value (csrc/coldstart.hip): where an item that is NOT a column of the block would land in each row's full
+ * ranking. d_scores as elimrec_rank_targets takes it; the values as CSR, d_val_ptr int64 [B + 1] / d_vals float32 [n_vals];
+ * d_skip (or NULL): int32 [n_vals], per value one column of its row that is not counted (-1: none) -- the item's own catalogue
+ * entry when a catalogue item is folded in again; the Python wrappers reject columns outside [0, I) on the host, the kernel
+ * ignores them. d_rank int32 [n_vals]:
+ *     rank = #{ j in [0, I), j != skip : scores[b, j] >= v }
+ * the new item goes behind every catalogue item of equal score (its id is larger than every catalogue id); -1 where v is not
+ * finite. A -inf score never counts, -0.0 == 0.0, NaN scores are outside the contract. O(I log Q) per row: the row's values
+ * are sorted in LDS (elimrec_rank_values_per_pass() per pass, longer lists take further passes), every score of a segment of
+ * elimrec_rank_values_segment() columns binary-searches them and adds 1 to an LDS integer bin, a suffix sum gives the counts.
+ * One memset + one launch on `stream`, integer atomic adds into the zeroed d_rank: the counts do not depend on the grid or on
+ * arrival order. A row without values is not read. Exactly n_vals entries of d_rank are written. */
+int elimrec_rank_values(const float *d_scores, int64_t B, int64_t I, int64_t lds, const int64_t *d_val_ptr, const float *d_vals,
+                        const int32_t *d_skip, int64_t n_vals, int32_t *d_rank, void *stream);
+int elimrec_rank_values_segment(void);
+int elimrec_rank_values_per_pass(void);
 /* Rows of the rank report from those ranks. Per pair (no counterpart in the reference, whose metrics stop at K:
  * metric.h:17-106): d_out [P x (3 + n_k)] float32 contiguous = rank, rr = 1 / (rank + 1), pct = rank / (n_cand - 1) (0 when
  * n_cand <= 1), then hit@ks[c] = (rank < ks[c]); ks host int[n_k], n_k <= 16; computed in double, rounded once (the rank column

@@ -169,6 +169,11 @@ class Net(object):
         self.baseline_report = int(cfg["baseline_report"]) if "baseline_report" in cfg else 0
         if self.baseline_report and self.world > 1:
             raise ValueError("--baseline_report needs the whole cached item table on one rank: it is single-GPU")
+        # --coldstart_report=K (default 0: off): under each [TEST] line how the cold test items rank as trained, folded in from their
+        # content and folded in with the mean id row; after both effects the TE -> TIE difference of the means
+        self.coldstart_report = int(cfg["coldstart_report"]) if "coldstart_report" in cfg else 0
+        if self.coldstart_report and self.world > 1:
+            raise ValueError("--coldstart_report needs the whole cached item table on one rank: it is single-GPU")
         Logger.info(count_parameters(self.recommender))
         self.opt = FusedAdam(self.recommender.parameters(), lr=cfg.lr, weight_decay=cfg.weight_decay)
         self.loss_name = str(cfg.loss)
@@ -293,7 +298,7 @@ class Net(object):
 
     def test_all_effects(self):
         """TE and TIE metrics on the test split, formatted as the reference prints them."""
-        rec, lines, ranks, shown, backed, sure, reached, grouped = self.recommender, {}, {}, {}, {}, {}, {}, {}
+        rec, lines, ranks, shown, backed, sure, reached, grouped, cold = self.recommender, {}, {}, {}, {}, {}, {}, {}, {}
         if self.grouped:
             Logger.info(rec.test_evaluator.metrics_info())
         for effect in EFFECTS:
@@ -309,6 +314,9 @@ class Net(object):
             if self.rank_report:           # where the test items stand in the full ranking under this effect
                 ranks[effect] = rec.rank_reporter.pair_ranks(rec)
                 Logger.info("  [{}] catalogue rank of the test items:\n{}".format(effect, rec.rank_reporter.evaluate(rec, ranks[effect])[1]))
+            if self.coldstart_report:      # the cold test items as trained / from content / with the mean id row under this effect
+                cold[effect], buf = rec.coldstart_reporter.evaluate(rec)
+                Logger.info("  [{}] cold test items (no training interaction):\n{}".format(effect, buf))
             if self.list_report:           # the lists themselves under this effect: how alike, how popular, how much of the catalogue
                 shown[effect] = rec.list_reporter.list_rows(rec)
                 Logger.info("  [{}] top-{} lists: similarity, popularity, exposure:\n{}".format(
@@ -347,6 +355,8 @@ class Net(object):
                     for source in reporter.sources:
                         Logger.info("  [{} - {}] metric difference, paired bootstrap:\n{}".format(
                             effect, source, rec.significance_reporter.shift(reporter.metric_rows(rec, source), sure[effect])[1]))
+        if self.coldstart_report:          # d_<column>: TIE - TE
+            Logger.info("  [TE->TIE] cold test items:\n{}".format(rec.coldstart_reporter.shift(cold["TE"], cold["TIE"])[1]))
         if self.rank_report:               # positive delta: TIE ranks the test item higher than TE does
             Logger.info("  [TE->TIE] rank shift of the test items:\n{}".format(rec.rank_reporter.shift(ranks["TE"], ranks["TIE"])[1]))
         if self.list_report:               # overlap: the share of the TE list that TIE keeps; d_<column>: TIE - TE
