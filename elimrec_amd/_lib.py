@@ -206,6 +206,8 @@ SIGNATURES = {
     "elimrec_rank_values": (c_i32, [c_ptr, c_i64, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr]),
     "elimrec_rank_values_segment": (c_i32, []),
     "elimrec_rank_values_per_pass": (c_i32, []),
+    "elimrec_segment_row_sum": (c_i32, [c_ptr, c_i64, c_i64, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_i64, c_ptr]),
+    "elimrec_segment_row_sum_chunk": (c_i32, []),
     "elimrec_rank_pair_rows": (c_i32, [c_ptr, c_ptr, c_i64, ctypes.POINTER(ctypes.c_int), c_i32, c_ptr, c_ptr]),
     "elimrec_rank_user_rows": (c_i32, [c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr]),
     "elimrec_cosine_topk": (c_i32, [c_ptr, c_i64, c_i64, c_i32, c_ptr, c_i64, c_ptr, c_i64, c_i32, c_ptr, c_ptr, c_i32, c_ptr, c_ptr,
@@ -407,7 +409,7 @@ class _Recording(object):
             plain = name in ("elimrec_abi_version", "elimrec_program_fn_count", "elimrec_program_fn_args", "elimrec_comm_unique_id",
                              "elimrec_score_get_math", "elimrec_score_get_bf16x3", "elimrec_group_metric_means_chunk",
                              "elimrec_rank_segment", "elimrec_rank_targets_per_pass", "elimrec_slab_hop_adam_wgrad_jobs",
-                             "elimrec_rank_values_segment", "elimrec_rank_values_per_pass",
+                             "elimrec_rank_values_segment", "elimrec_rank_values_per_pass", "elimrec_segment_row_sum_chunk",
                              "elimrec_cosine_topk_chunk", "elimrec_cosine_topk_tile",
                              "elimrec_audience_topk_chunk", "elimrec_audience_topk_tile",
                              "elimrec_list_max_k", "elimrec_list_pair_cosine_small_k", "elimrec_list_pair_cosine_chunk_cols",

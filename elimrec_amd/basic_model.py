@@ -8,7 +8,7 @@ from torch import nn
 
 from . import ops
 from .evaluator import ProxyEvaluator, UniEvaluator
-from .reports import AudienceReport, BaselineReport, CalibrationReport, ClusterReport, ColdStartReport, CoNeighbourReport, DiversifyReport, EffectReport, GeometryReport, HistoryReport, ListReport, NeighbourReport, RankReport, SignificanceReport
+from .reports import AudienceReport, BaselineReport, CalibrationReport, ClusterReport, ColdStartReport, CoNeighbourReport, DiversifyReport, EffectReport, GeometryReport, HistoryReport, ListReport, NeighbourReport, NewUserReport, RankReport, SignificanceReport
 
 
 
@@ -204,6 +204,18 @@ class BasicModel(nn.Module):
             ks = [int(k) for k in config["topks"]]
             self.coldstart_reporter = ColdStartReport(dataset, train, dataset.get_user_test_dict(), ks + [k_cold] * (k_cold not in ks),
                                                       group_view=config["group_view"])
+        # --newuser_report=K (CLI-only, default 0 = off): the test users with a training history as trained, folded in from their
+        # training items and folded in with the mean id row -- the evaluator's metrics at the topks and K, the share of the trained
+        # top-K list each variant keeps and the cosine to the trained row, overall and per user group (reports.NewUserReport)
+        k_new = config["newuser_report"] if "newuser_report" in config else 0
+        if isinstance(k_new, bool) or not isinstance(k_new, int) or not 0 <= k_new <= 256:
+            raise ValueError("newuser_report must be 0 (off) or the K of the lists, 1 <= K <= 256, got %r" % (k_new,))
+        self.newuser_reporter = None
+        if k_new:
+            ks = [int(k) for k in config["topks"]]
+            self.newuser_reporter = NewUserReport(dataset, train, dataset.get_user_test_dict(), ks + [k_new] * (k_new not in ks),
+                                                  group_view=config["group_view"], metric=config["metric"], k=k_new)
+            self.newuser_reporter.tie_order = self.test_evaluator.evaluator.tie_order
         self.infonce_criterion = nn.CrossEntropyLoss()          # BasicModel.py:32
 
     def getFileName(self):

@@ -20,6 +20,9 @@
 //       its row's full ranking by (score desc, id asc), -1 at -inf (the lists are checked on the host first: a synchronisation)
 //   rank_values(scores f32[B x I], val_ptr i64[B+1], vals f32, skip i32?) -> i32[n_vals]: #{j != skip: scores[b, j] >= v}, where a new
 //       item of that score would land in the row's full ranking; -1 for a value that is not finite (csrc/coldstart.hip)
+//   segment_row_sum(table f32[n x C], ptr i64[Q+1], rows i32, weights f32, row_offset) -> f32[Q x C]: per list the weighted sum of
+//       the rows table[row_offset + rows[j]], float64 products and sums rounded once (csrc/foldin.hip; ids and weights are
+//       checked on the host first: a synchronisation)
 //   list_pair_cosine(table f32[n x blocks*d], sqnorm f32[n x blocks], lists i32[B x K], blocks) -> f32[B x blocks]: per list and
 //       column block the mean pairwise cosine of the listed rows (entries outside [0, n) are not listed; NaN below two)
 //   list_exposure(lists i32[B x K], n_rows) -> i32[n_rows]: how often every row is listed
@@ -438,6 +441,27 @@ at::Tensor rank_values(const at::Tensor &scores, const at::Tensor &val_ptr, cons
     check(elimrec_rank_values(sc.data_ptr<float>(), B, I, sc.stride(0), vp.data_ptr<int64_t>(), v.data_ptr<float>(),
                               sk.defined() ? sk.data_ptr<int32_t>() : nullptr, n, out.data_ptr<int32_t>(), cur_stream()),
           "rank_values");
+    return out;
+}
+
+// ---- weighted sums of table rows over ragged lists: the fold-in of new users
+at::Tensor segment_row_sum(const at::Tensor &table, const at::Tensor &ptr, const at::Tensor &rows, const at::Tensor &weights, int64_t row_offset) {
+    need(table, "table", at::kFloat, 2);
+    const at::Tensor tb = table.stride(1) == 1 && table.stride(0) % 4 == 0 && ((uintptr_t)table.data_ptr<float>() & 15) == 0 ? table : table.contiguous();
+    need(ptr, "ptr", at::kLong, 1); need(rows, "rows", at::kInt, 1); need(weights, "weights", at::kFloat, 1);
+    const at::Tensor p = ptr.contiguous(), r = rows.contiguous(), w = weights.contiguous();
+    const int64_t n = tb.size(0), C = tb.size(1), Q = p.numel() - 1, E = r.numel();
+    TORCH_CHECK(Q >= 0, "elimrec::segment_row_sum: ptr needs Q + 1 >= 1 entries");
+    TORCH_CHECK(C >= 4 && C <= 1280 && C % 4 == 0, "elimrec::segment_row_sum: C must be a multiple of 4 in [4, 1280], got ", C);
+    TORCH_CHECK(w.numel() == E, "elimrec::segment_row_sum: weights needs one entry per row id (", E, "), got ", w.numel());
+    TORCH_CHECK_INDEX(row_offset >= 0 && row_offset <= n, "elimrec::segment_row_sum: row_offset ", row_offset, " outside [0, ", n, "]");
+    checked_csr(p, r, Q, n - row_offset, true, "segment_row_sum", "ptr", "rows", "row ids", "the table holds", "rows behind row_offset");
+    TORCH_CHECK(E == 0 || at::isfinite(w).all().item<bool>(), "elimrec::segment_row_sum: weights holds an entry that is not finite");
+    at::Tensor out = at::empty({Q, C}, tb.options());
+    if (Q == 0) return out;
+    check(elimrec_segment_row_sum(tb.data_ptr<float>(), n, C, tb.stride(0), row_offset, p.data_ptr<int64_t>(), E ? r.data_ptr<int32_t>() : nullptr,
+                                  E ? w.data_ptr<float>() : nullptr, Q, E, out.data_ptr<float>(), C, cur_stream()),
+          "segment_row_sum");
     return out;
 }
 
@@ -1010,6 +1034,7 @@ TORCH_LIBRARY(elimrec, m) {
     m.def("score_effects(Tensor Y, int U, int I, Tensor users, int d, int S, int head_mask, int fusion_mode, Tensor cand_ptr, Tensor cand_items, int width) -> Tensor");
     m.def("rank_targets(Tensor scores, Tensor tgt_ptr, Tensor tgt_items) -> Tensor");
     m.def("rank_values(Tensor scores, Tensor val_ptr, Tensor vals, Tensor? skip) -> Tensor");
+    m.def("segment_row_sum(Tensor table, Tensor ptr, Tensor rows, Tensor weights, int row_offset) -> Tensor");
     m.def("cosine_topk(Tensor table, Tensor sqnorm, Tensor query_rows, int K, bool exclude_self) -> (Tensor, Tensor)");
     m.def("audience_topk(Tensor Y, int U, int I, Tensor items, Tensor? excl_ptr, Tensor? excl_users, int d, int S, int head_mask, int fusion_mode, "
           "int predict_type, int K, Tensor? sqnorm, Tensor? row_sum, int I_total) -> (Tensor, Tensor)");
@@ -1056,6 +1081,7 @@ TORCH_LIBRARY_IMPL(elimrec, CUDA, m) {
     m.impl("score_effects", &score_effects);
     m.impl("rank_targets", &rank_targets);
     m.impl("rank_values", &rank_values);
+    m.impl("segment_row_sum", &segment_row_sum);
     m.impl("cosine_topk", &cosine_topk);
     m.impl("audience_topk", &audience_topk);
     m.impl("list_overlap", &list_overlap);

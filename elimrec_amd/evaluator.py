@@ -25,6 +25,7 @@ from .reports import CalibrationReport, CalibrationTables, calibration_columns, 
 from .reports import CLUSTER_COLUMNS, CLUSTER_USER_COLUMNS, ClusterReport, ClusterShift, ClusterTables, cluster_rows, cluster_user_rows   # noqa: F401
 from .reports import CoNeighbourReport, co_neighbour_columns   # noqa: F401
 from .reports import COLDSTART_VARIANTS, ColdStartReport, cold_test_items, coldstart_columns, coldstart_row, isolated_row_scale   # noqa: F401
+from .reports import NEWUSER_VARIANTS, NewUserReport, fold_in_weights, format_newuser, newuser_columns, newuser_overall_metrics   # noqa: F401
 from .reports import BASELINE_LIST_COLUMNS, BaselineReport, BaselineTables   # noqa: F401
 from .reports import GEOMETRY_COLUMNS, GeometryReport, GeometryTables, spectrum_summary   # noqa: F401
 from .reports import (AUDIENCE_COLUMNS, AUDIENCE_EXPOSURE_COLUMNS, AudienceReport, AudienceTables, DIVERSIFY_COLUMNS, EXPOSURE_COLUMNS, DiversifyReport, DiversifyTables, EffectReport, HistoryReport, ListReport,   # noqa: F401

@@ -67,6 +67,24 @@ class NewItems(object):
         return self.n_items
 
 
+class NewUsers(object):
+    """Users folded in from their histories (EliMRec.fold_in_users), on the device: rows [Q x Cy] -- the rows the cached user table
+    would hold for them --, table [Q + I x Cy] = the new rows, then the cached item rows (Q users and the catalogue to the
+    scorers: new user q is user q), sqn its block norms [Q + I x 1 + S], layer_mean [Q x C] the rows of the layer-mean table the
+    projections read, hist_ptr int64 [Q + 1] / hist_items int32 the histories resident on the device (the scorer's mask), with
+    their host copies hist_ptr_host / hist_flat, and version = the model's table version the rows were computed against: a handle
+    used after the cached tables changed raises."""
+
+    def __init__(self, rows, table, sqn, version, num_users, num_items, hist_ptr_host, hist_flat, hist_ptr, hist_items, layer_mean=None):
+        self.rows, self.table, self.sqn, self.version = rows, table, sqn, int(version)
+        self.num_users, self.num_items = int(num_users), int(num_items)
+        self.hist_ptr_host, self.hist_flat, self.hist_ptr, self.hist_items, self.layer_mean = hist_ptr_host, hist_flat, hist_ptr, hist_items, layer_mean
+        self.n_users = int(rows.shape[0])
+
+    def __len__(self):
+        return self.n_users
+
+
 KNN_LIST_BLOCK = 4096                    # items per launch when neighbour_lists builds the lists of the whole catalogue
 KnnLists = collections.namedtuple("KnnLists", ("ids", "scores", "votes"))
 HistorySupport = collections.namedtuple("HistorySupport", ("items", "history", "scores", "count", "mean"))
@@ -2118,10 +2136,15 @@ class EliMRec(BasicModel):
 
     def _whole_tables(self, what):
         """_cached_tables for the cold-start readers: single GPU, whole tables -- lean and item-sharded tables are refused."""
-        msg = "%s needs the whole cached tables on this rank; the tables are item-sharded or lean" % what
-        if self.__dict__.get("_lean") or self.__dict__.get("_wide"):
-            raise CandidateScoringError(msg)
+        msg = self._refuse_partial_tables(what)
         return self._cached_tables(what + " needs", msg)
+
+    def _refuse_partial_tables(self, what):
+        """The refusal of lean / wide / item-sharded tables alone (no table is built or read) -> the refusal's words."""
+        msg = "%s needs the whole cached tables on this rank; the tables are item-sharded or lean" % what
+        if self.__dict__.get("_lean") or self.__dict__.get("_wide") or self.__dict__.get("_eval_shard") is not None:
+            raise CandidateScoringError(msg)
+        return msg
 
     def _check_new(self, new):
         if not isinstance(new, NewItems) or new.num_users != self.num_users:
@@ -2351,6 +2374,228 @@ class EliMRec(BasicModel):
                           torch.from_numpy(tflat[tptr[a]:tptr[b]].astype(np.int32)).to(dev))
             out[a:b] = self.rank_new_items_device(torch.from_numpy(ids[a:b]).to(dev), new, masked[0], masked[1], among=among).cpu()
         return out
+
+    # ------------------------------------------------------------------ cold start: users folded in from their histories
+    def _item_degree(self):
+        """Training interactions per item (int64 [num_items], host): the degree the frozen adjacency gives an item."""
+        deg = self.__dict__.get("_item_train_degree")
+        if deg is None:
+            from .reports import item_train_counts
+            deg = self._item_train_degree = item_train_counts(self.dataset.get_user_train_dict(), self.num_items)
+        return deg
+
+    def _new_user_inputs(self, histories, id_rows):
+        """The host checks of fold_in_users, all before anything touches the device: (hist_ptr int64, hist_items int64, the id rows
+        as a float32 [Q x d] host tensor, None (no id term) or "mean")."""
+        if isinstance(histories, (str, bytes, dict)) or not hasattr(histories, "__len__"):
+            raise TypeError("histories must be a list of item id lists, got %s" % type(histories).__name__)
+        ptr, flat, _ = self._id_lists(list(histories), "history item")
+        Q = len(histories)
+        if id_rows is None or (isinstance(id_rows, str) and id_rows == "mean"):
+            return ptr, flat, id_rows
+        if isinstance(id_rows, str):
+            raise ValueError("id_rows must be None, 'mean' or a float array [Q x %d], got %r" % (self.latent_dim, id_rows))
+        t = id_rows.detach().cpu() if isinstance(id_rows, torch.Tensor) else torch.from_numpy(np.asarray(id_rows))
+        if not t.is_floating_point() or t.dim() != 2 or tuple(t.shape) != (Q, self.latent_dim):
+            raise ValueError("id_rows must be a float array [%d x %d], got %s %s" % (Q, self.latent_dim, t.dtype, tuple(t.shape)))
+        t = t.float().contiguous()
+        if not bool(torch.isfinite(t).all()):
+            raise ValueError("id_rows holds an entry that is not finite")
+        return ptr, flat, t
+
+    def _check_new_users(self, new):
+        if not isinstance(new, NewUsers) or new.num_items != self.num_items or new.num_users != self.num_users:
+            raise TypeError("`new` must be the NewUsers handle of this model's fold_in_users()")
+        if new.n_users and new.version != getattr(self, "_table_version", 0):
+            raise RuntimeError("the cached tables changed since these users were folded in (table version %d, now %d): "
+                               "call fold_in_users() again" % (new.version, getattr(self, "_table_version", 0)))
+
+    def mean_user_id_row(self):
+        """The mean embedding_user row of the users that have a training interaction (float64 mean, rounded once): float32 [d] on
+        the parameters' device -- what fold_in_users(id_rows="mean") gives every new user as its id row."""
+        self.plugin.sync_params()
+        w = self.embedding_user.weight.detach()
+        train = self.dataset.get_user_train_dict()
+        active = np.asarray(sorted(int(u) for u, items in train.items() if len(items) and 0 <= int(u) < self.num_users), dtype=np.int64)
+        if not active.size:
+            return w.new_zeros(w.shape[1])
+        return w[torch.from_numpy(active).to(w.device)].double().mean(0).float()
+
+    @torch.no_grad()
+    def fold_in_users(self, histories, id_rows=None):
+        """Users that arrived after the graph was built, from the items they took -> NewUsers (the rows the cached user table would
+        hold for them, on the device). histories: one list of catalogue item ids per user; repeats count as given. The graph stays
+        frozen -- no other node's row changes -- and with Out the cached layer-mean table
+            OutNew[q] = kappa x0_q + sum_{i in H_q} w_qi Out[U + i]          (ops.segment_row_sum, csrc/foldin.hip: float64 sums)
+        with w_qi the off-diagonal entry the adjacency would give the edge (reports.fold_in_weights: the item's TRAINING degree, the
+        user's degree = len(H_q)), kappa = reports.isolated_row_scale and x0_q = id_rows[q] in every block. id_rows: None (no id
+        term), a float [Q x d], or "mean" = mean_user_id_row(). With id_rows=None this is the mean of the user's layers 1 .. L + 1 in
+        the graph extended by that one row -- the neighbourhood aggregate of the history's layer means -- NOT the row training would
+        give: layer 0 is unknown for a new user and layer L + 1 takes its place. Y_new = the USER fusion Linear on OutNew plus the
+        s_dense heads on its blocks: one ops.linear_fwd_batched call with the weights the cached tables were built with. An empty
+        history is allowed: its OutNew row is kappa x0, and with no id_rows its fused block and its heads come from the biases
+        alone (every such user gets the same scores, those of the biases' row against each item row: one ranking for all of them,
+        not a constant score). A row depends
+        on its own history only: one user or a batch of 8192, the same bits. IndexError for an id outside the catalogue,
+        ValueError for id_rows of a wrong shape or with a non-finite entry, both before anything touches the device; Q = 0 gives an
+        empty handle without a launch."""
+        from .reports import fold_in_weights, isolated_row_scale
+        ptr, flat, ids = self._new_user_inputs(histories, id_rows)
+        U, I, d, Cy = self.num_users, self.num_items, self.latent_dim, self.Cy
+        Q = int(ptr.size - 1)
+        if Q == 0:
+            dev = self._require_gpu()
+            self._refuse_partial_tables("fold_in_users()")          # (an empty request is refused like any other; nothing is launched)
+            return NewUsers(torch.empty(0, Cy, dtype=torch.float32, device=dev), None, None, getattr(self, "_table_version", 0), U, I,
+                            ptr, flat, None, None)
+        adj_type = str(self.config["adj_type"])
+        weights = fold_in_weights(adj_type, ptr, flat, self._item_degree())
+        dev = self._whole_tables("fold_in_users()")
+        W = self.__dict__.get("_table_W")
+        if W is None:                 # (tables put there by hand, not by a forward of this model)
+            raise RuntimeError("fold_in_users() needs the weights the cached tables were built with: call bpr_loss or compute() first")
+        f32 = dict(dtype=torch.float32, device=dev)
+        hist_ptr = torch.from_numpy(ptr).to(dev)
+        hist_items = ops._resident_ids(flat, dev)
+        out = torch.empty(Q, self.C, **f32)
+        ops.segment_row_sum(self._ws["Out"], ptr, flat.astype(np.int32), weights, out, row_offset=U)
+        if ids is not None:
+            x0 = self.mean_user_id_row().to(dev).expand(Q, -1) if isinstance(ids, str) else ids.to(dev)
+            out += (x0 * isolated_row_scale(adj_type, self.n_layers)).repeat(1, self.C // d)
+        table = torch.empty(Q + I, Cy, **f32)
+        table[Q:] = self._ws["Y"][U:]
+        rows = table[:Q]
+        wu = self._fusion_weights(W)[0]
+        head = [(out, wu, W["embedding_user_after_GCN.bias"], rows[:, :d])]
+        for h, m in enumerate(self._mods):
+            blk = slice((h + 1) * d, (h + 2) * d)
+            head.append((out[:, blk], W["s_dense_%s.weight" % m], W["s_dense_%s.bias" % m], rows[:, blk]))
+        ops.linear_fwd_batched(head)
+        sqn = ops.row_sqnorms(table, d, 1 + self.S, torch.empty(Q + I, 1 + self.S, **f32))
+        return NewUsers(rows, table, sqn, self._table_version, U, I, ptr, flat, hist_ptr, hist_items, layer_mean=out)
+
+    def _new_user_scores(self, new, scores=None, top_k=0, train_ptr=None, train_items=None, tie_order="id"):
+        """The evaluator's scorer (ops.score_topk, what predict_device runs) over the handle's table with U := Q and the users
+        0 .. Q - 1 -> (idx, val) [Q x top_k] or (None, None). Under TIE the catalogue mean is the scorer's own pass 1 over the
+        trained catalogue, the item rows of the table."""
+        self._check_new_users(new)
+        dev = self._whole_tables("the readers of fold_in_users()")
+        Q, I = new.n_users, self.num_items
+        users = torch.arange(Q, dtype=torch.int64, device=dev)
+        need = ops.score_workspace(Q, Q, I, self.S, max(top_k, 1), topk_only=scores is None and top_k > 0, d=self.latent_dim)
+        if self._ws.get("new_user_score_ws") is None or self._ws["new_user_score_ws"].numel() < need:
+            self._ws["new_user_score_ws"] = torch.empty(need, dtype=torch.uint8, device=dev)
+        idx = val = None
+        if top_k:
+            idx = torch.empty(Q, top_k, dtype=torch.int32, device=dev)
+            val = torch.empty(Q, top_k, dtype=torch.float32, device=dev)
+        ops.score_topk(new.table, Q, I, users, self.latent_dim, self.S, self._head_mask(), self.fusion_mode, self.predict_type,
+                       self._ws["new_user_score_ws"], scores=scores, K=top_k, topk_idx=idx, topk_val=val, train_ptr=train_ptr,
+                       train_items=train_items, sqnorm=new.sqn, tie_order=tie_order)
+        return idx, val
+
+    @torch.no_grad()
+    def predict_new_users_device(self, new, out):
+        """out [Q x I] (float32, unit column stride, on the device) <- every new user's score of every catalogue item under the
+        current predict type and fusion mode: bit for bit what predict() would give a trained user whose cached row is the
+        handle's row."""
+        self._check_new_users(new)
+        if not new.n_users:
+            return out
+        if tuple(out.shape) != (new.n_users, self.num_items):
+            raise ValueError("out must be [%d x %d]" % (new.n_users, self.num_items))
+        self._new_user_scores(new, scores=out)
+        return out
+
+    def predict_new_users(self, new):
+        """Scores of the new users: CPU fp32 [Q x I]."""
+        dev = self._require_gpu()
+        out = torch.empty(len(new), self.num_items, dtype=torch.float32, device=dev)
+        return self.predict_new_users_device(new, out).cpu()
+
+    def _new_user_mask(self, new, exclude_history, exclude, dev):
+        """The items left out of each new user's ranking as CSR on the device, (None, None) when there are none: the history (the
+        handle's resident lists when nothing else is excluded) and `exclude` = dict q -> item ids."""
+        Q = new.n_users
+        more = self._excluded(exclude, range(Q), "item") if exclude else None
+        if more is None or not more[1].size:
+            if not exclude_history or not new.hist_flat.size:
+                return None, None
+            return new.hist_ptr, new.hist_items
+        lists = [np.concatenate((new.hist_flat[new.hist_ptr_host[q]:new.hist_ptr_host[q + 1]] if exclude_history else more[1][:0],
+                                 more[1][more[0][q]:more[0][q + 1]])) for q in range(Q)]
+        ptr, flat, _ = ops.ragged(lists, dtype=np.int32)
+        return torch.from_numpy(ptr).to(dev), torch.from_numpy(flat).to(dev)
+
+    @torch.no_grad()
+    def recommend_new_users(self, new, k, exclude_history=True, exclude=None, tie_order="id"):
+        """Each new user's top-k catalogue items: CPU (ids int32 [Q x k], scores fp32 [Q x k]) by (score descending, id ascending) --
+        tie_order="reference": the evaluator's order among equal scores. exclude_history masks the user's history exactly as the
+        evaluator masks train items (the scorer's train_ptr / train_items; an id listed twice is masked once); `exclude` = dict
+        q -> further item ids. 1 <= k <= min(256, num_items)."""
+        k = int(k)
+        if not 1 <= k <= min(self.RECOMMEND_MAX_K, self.num_items):
+            raise ValueError("k must lie in [1, %d]" % min(self.RECOMMEND_MAX_K, self.num_items))
+        if tie_order not in ops.TIE_ORDERS:
+            raise ValueError("tie_order must be id or reference")
+        self._check_new_users(new)
+        if not new.n_users:
+            return torch.empty(0, k, dtype=torch.int32), torch.empty(0, k, dtype=torch.float32)
+        dev = self._require_gpu()
+        masked = self._new_user_mask(new, exclude_history, exclude, dev)
+        idx, val = self._new_user_scores(new, top_k=k, train_ptr=masked[0], train_items=masked[1], tie_order=tie_order)
+        return idx.cpu(), val.cpu()
+
+    @torch.no_grad()
+    def rank_items_for_new_users(self, new, items, exclude_history=True):
+        """The exact catalogue rank of given items for each new user: CPU int32 [Q x longest list], row q = the 0-based positions of
+        items[q] in user q's full ranking under the current predict type, padded with -1 -- rank_items over the handle: the scorer's
+        block with the history masked (exclude_history), then ops.rank_targets; an item that is itself masked gets -1."""
+        self._check_new_users(new)
+        Q, I = new.n_users, self.num_items
+        if len(items) != Q:
+            raise ValueError("one item list per user: %d lists for %d users" % (len(items), Q))
+        ptr, flat, lens = self._id_lists(items, "item")
+        rank = np.zeros(0, dtype=np.int32)
+        if flat.size:
+            dev = self._require_gpu()
+            index = ops.TargetIndex(ptr, flat.astype(np.int32), Q, I, dev)
+            masked = self._new_user_mask(new, exclude_history, None, dev)
+            lds = (I + 3) // 4 * 4                # rows 16-byte aligned: the count takes its 16-byte loads
+            block = torch.empty(Q, lds, dtype=torch.float32, device=dev)[:, :I]
+            self._new_user_scores(new, scores=block, train_ptr=masked[0], train_items=masked[1])
+            rank = ops.rank_targets(block, index, None, torch.empty(index.n_targets, dtype=torch.int32, device=dev)).cpu().numpy()
+        return torch.from_numpy(ops.ragged_padded(rank, lens))
+
+    def similar_users_to_new(self, new, k, space="fused"):
+        """The k TRAINED users closest to each new user by cosine: Neighbours(ids CPU int32 [Q x k], scores CPU fp32 [Q x k]) by
+        (score descending, id ascending); space as similar_users. ops.cosine_topk over [the cached user rows' block ; a block of new
+        rows] with the new rows as the queries, each leaving out every new row of its block."""
+        k = int(k)
+        if not 1 <= k <= ops.KNN_MAX_K:
+            raise ValueError("k must lie in [1, %d]" % ops.KNN_MAX_K)
+        h = self._neighbour_space(space)
+        self._check_new_users(new)
+        Q, U, d = new.n_users, self.num_users, self.latent_dim
+        if not Q:
+            return Neighbours(torch.empty(0, k, dtype=torch.int32), torch.empty(0, k, dtype=torch.float32))
+        dev = self._whole_tables("similar_users_to_new()")
+        sqn = self._block_sqnorms(dev)
+        nb = self.NEW_ITEM_QUERY_BLOCK
+        table = torch.empty(U + nb, d, dtype=torch.float32, device=dev)
+        norms = torch.empty(U + nb, dtype=torch.float32, device=dev)
+        table[:U] = self._ws["Y"][:U, h * d:(h + 1) * d]
+        norms[:U] = sqn[:U, h]
+        idx = torch.empty(Q, k, dtype=torch.int32, device=dev)
+        val = torch.empty(Q, k, dtype=torch.float32, device=dev)
+        for a in range(0, Q, nb):
+            n = min(nb, Q - a)
+            table[U:U + n] = new.rows[a:a + n, h * d:(h + 1) * d]
+            norms[U:U + n] = new.sqn[a:a + n, h]
+            block = np.arange(U, U + n, dtype=np.int64)
+            query = ops.NeighbourQuery(block, U + n, dev, np.arange(n + 1, dtype=np.int64) * n, np.tile(block, n))
+            ops.cosine_topk(table[:U + n], norms[:U + n], query, k, idx[a:a + n], val[a:a + n], exclude_self=True)
+        return Neighbours(idx.cpu(), val.cpu())
 
     def predict(self, user_ids, candidate_items=None):
         """:96-113. CPU fp32 tensor [len(user_ids) x I]; `candidate_items` is ignored as in the reference."""

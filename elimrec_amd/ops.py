@@ -991,6 +991,56 @@ def rank_values(scores, val_ptr, vals, out, skip=None):
     return out
 
 
+FOLDIN_MAX_COLUMNS = 1280               # the widest table segment_row_sum takes (csrc/foldin.hip), known without the library
+
+
+def segment_row_sum(table, ptr, rows, weights, out, row_offset=0):
+    """elimrec_segment_row_sum: out float32 [Q x C] <- per list the weighted sum of table rows,
+    out[q] = sum_j weights[j] * table[row_offset + rows[j]] over j in [ptr[q], ptr[q + 1]) -- the fold-in of a new user from its
+    history. Every product and every sum in float64, rounded to float32 once; an empty list gives zeros. table float32 [n x C],
+    unit column stride, a row stride that is a multiple of 4 floats, 16-byte aligned, C % 4 == 0, 4 <= C <= FOLDIN_MAX_COLUMNS.
+    ptr int64 [Q + 1] / rows int32 / weights float32 (as long as rows): host arrays or tensors, checked on the host at every call
+    (a synchronisation for device tensors) -- ptr ascends from 0 to len(rows) (ValueError), every id in [0, n - row_offset)
+    (IndexError), every weight finite (ValueError) -- before anything is launched; Q = 0 launches nothing. One workgroup per list,
+    chunks of FOLDIN_CHUNK entries dealt to its four waves in turn, no atomics and no workspace: a list's bits depend on its own
+    entries, C and the table alone, not on Q or on the other lists of the call (csrc/foldin.hip)."""
+    who = "segment_row_sum"
+    tp, ld = _rowmajor(table, "table")
+    n, C = table.shape
+    if C % 4 or not 4 <= C <= FOLDIN_MAX_COLUMNS:
+        raise ValueError("elimrec_amd.ops.%s: C must be a multiple of 4 in [4, %d], got %d" % (who, FOLDIN_MAX_COLUMNS, C))
+    if ld % 4 or tp % 16:
+        raise ValueError("elimrec_amd.ops.%s: table needs a row stride that is a multiple of 4 floats and a 16-byte aligned base" % who)
+    row_offset = int(row_offset)
+    if not 0 <= row_offset <= n:
+        raise IndexError("elimrec_amd.ops.%s: row_offset %d outside [0, %d]" % (who, row_offset, n))
+    if not (isinstance(out, torch.Tensor) and out.dim() == 2 and out.shape[1] == C and (out.shape[0] == 0 or out.stride(1) == 1)
+            and out.device == table.device):
+        raise ValueError("elimrec_amd.ops.%s: out must be a [Q x %d] tensor with unit column stride on the table's device" % (who, C))
+    Q = int(out.shape[0])
+    p, ids = _checked_csr(ptr, rows, Q, n - row_offset, who,
+                          ("ptr", "rows", "Q", "row ids span [%d, %d], the table holds %d rows behind row_offset"))
+    E = int(ids.size)
+    w = _host(weights).reshape(-1)
+    if w.size != E:
+        raise ValueError("elimrec_amd.ops.%s: weights needs one entry per row id (%d), got %d" % (who, E, w.size))
+    if E and (w.dtype.kind != "f" or not np.isfinite(w).all()):
+        raise ValueError("elimrec_amd.ops.%s: weights must be finite floats" % who)
+    if Q == 0:
+        return out
+    op, ldo = _rowmajor(out, "out")
+    if (Q > 1 and ldo % 4) or op % 16:
+        raise ValueError("elimrec_amd.ops.%s: out needs a row stride that is a multiple of 4 floats and a 16-byte aligned base" % who)
+    dev = table.device
+    keep = lambda x, dt: isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == dt and x.device == dev and x.dim() == 1 and x.is_contiguous()
+    ptr_t = ptr if keep(ptr, torch.int64) else torch.from_numpy(p).to(dev)
+    rows_t = rows if keep(rows, torch.int32) and E else _resident_ids(ids, dev)
+    w_t = weights if keep(weights, torch.float32) and E else torch.from_numpy(np.ascontiguousarray(w if E else np.zeros(1), dtype=np.float32)).to(dev)
+    _lib.check(_lib.load().elimrec_segment_row_sum(tp, n, C, ld, row_offset, _dev(ptr_t, "ptr", torch.int64), _dev(rows_t, "rows", torch.int32),
+                                                   _dev(w_t, "weights"), Q, E, op, max(ldo, C) if Q > 1 else C, _stream()), who)
+    return out
+
+
 RANK_PAIR_COLUMNS = ("rank", "rr", "pct")
 RANK_USER_COLUMNS = ("auc", "mrr_full", "first_rank")
 
@@ -1044,6 +1094,8 @@ def __getattr__(name):
         return int(_lib.load().elimrec_rank_values_segment())
     if name == "RANK_VALUES_PER_PASS":   # values rank_values sorts in LDS per pass over a segment
         return int(_lib.load().elimrec_rank_values_per_pass())
+    if name == "FOLDIN_CHUNK":           # entries of a list one wave of segment_row_sum takes at a time
+        return int(_lib.load().elimrec_segment_row_sum_chunk())
     if name == "KNN_CHUNK":              # candidate rows one workgroup of cosine_topk streams
         return int(_lib.load().elimrec_cosine_topk_chunk())
     if name == "KNN_TILE":               # query rows one workgroup of cosine_topk holds (16 when K > 64)

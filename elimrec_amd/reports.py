@@ -1922,3 +1922,169 @@ class ColdStartReport(_Report):
             return None, format_coldstart(None, None, None)
         delta = (final_b - final_a)[:, :, 2:]
         return delta, self._format(tuple("d_" + c for c in self.columns[2:]), delta)
+
+
+NEWUSER_VARIANTS = ("trained", "history", "history+mean_id")
+
+
+def fold_in_weights(adj_type, hist_ptr, hist_items, item_degree):
+    """The weights of EliMRec.fold_in_users: per history entry the off-diagonal value the frozen adjacency (create_adj_mat) would
+    give the edge (new user q, item i), with n = len(H_q) the new user's degree -- repeats count as given -- and deg_i the item's
+    TRAINING degree: 'plain' 1; 'gcmc' and 'mean' (anything else, as create_adj_mat reads it) 1 / n; 'norm' 1 / (n + 1) (the row
+    is normalised with its diagonal, which itself carries nothing: a new user has no trained row); 'pre' 1 / sqrt(n max(deg_i, 1))
+    (a cold item takes degree 1: the new edge is its first). Pure host arithmetic in float64, rounded once -> float32
+    [len(hist_items)]. hist_ptr int64 [Q + 1] ascending from 0 to len(hist_items) (ValueError), every id in [0, len(item_degree))
+    (IndexError)."""
+    ptr = np.ascontiguousarray(np.asarray(hist_ptr), dtype=np.int64).reshape(-1)
+    items = np.asarray(hist_items).reshape(-1)
+    deg = np.asarray(item_degree).reshape(-1)
+    if items.size and not np.issubdtype(items.dtype, np.integer):
+        raise TypeError("hist_items must hold integers, got %s" % items.dtype)
+    if ptr.size < 1 or ptr[0] != 0 or ptr[-1] != items.size or (np.diff(ptr) < 0).any():
+        raise ValueError("hist_ptr must ascend from 0 to len(hist_items) = %d" % items.size)
+    items = items.astype(np.int64)
+    if items.size and (int(items.min()) < 0 or int(items.max()) >= deg.size):
+        raise IndexError("history item ids span [%d, %d], the catalogue has %d items" % (int(items.min()), int(items.max()), deg.size))
+    n = np.repeat(np.diff(ptr), np.diff(ptr)).astype(np.float64)
+    if adj_type == "plain":
+        w = np.ones(items.size, dtype=np.float64)
+    elif adj_type == "norm":
+        w = 1.0 / (n + 1.0)
+    elif adj_type == "pre":
+        w = 1.0 / np.sqrt(n * np.maximum(deg[items].astype(np.float64), 1.0))
+    else:
+        w = 1.0 / n
+    return w.astype(np.float32)
+
+
+def newuser_columns(metric_columns):
+    return ("users",) + tuple(metric_columns) + ("overlap", "cos")
+
+
+def newuser_overall_metrics(metric_rows):
+    """The `all:` row's metric columns from per-user metric rows [n x Cs] (host, float32): UniEvaluator._summary's own expression,
+    numpy's float32 mean over the users -- a column's mean does not depend on which other columns stand beside it, so the `trained`
+    variant repeats the test pass's numbers bit for bit."""
+    rows = np.ascontiguousarray(metric_rows, dtype=np.float32)
+    return np.mean(rows, axis=0) if rows.shape[0] else np.full(rows.shape[1], np.nan, dtype=np.float32)
+
+
+def format_newuser(columns, labels, table):
+    """format_table, or the one line of a split without a test user that has a training history (columns = None)."""
+    if columns is None:
+        return "no test user with a training history in this split: nothing to report"
+    return format_table(columns, labels, table)
+
+
+class NewUserReport(_Report):
+    """What serving a user WITHOUT retraining costs (--newuser_report=K): over the test users with a non-empty training history, one
+    row per variant of the user's row of the cached table:
+      trained          the cached row: the evaluator's own lists;
+      history          the row folded in from the user's training items with a zero id row (EliMRec.fold_in_users);
+      history+mean_id  the same with id_rows="mean".
+    Columns: users, the evaluator's shown metrics at top_k (ops.rank_metrics over each variant's top-K lists with the train items
+    masked, the evaluator's tie order: the `trained` row of the `all:` block repeats the test pass's numbers bit for bit when every
+    test user has a training history and K does not exceed the largest of the topks), overlap = the share of the trained top-k
+    list the variant keeps (ops.list_overlap; k = the switch's K) and cos = the mean cosine between the variant's fused row and the
+    trained fused row. Overall and, with group_view, per user group (ops.group_metric_means). Users go in blocks of block_users;
+    the tables reach the host, and -- for the `all:` block, as in the evaluator's own summary -- the users' shown metric rows."""
+
+    name, needs = "newuser", "fold_in_users"
+    tie_order = "reference"               # the evaluator's default; BasicModel hands the test evaluator's over
+
+    def __init__(self, dataset, user_train_dict, user_test_dict, top_k, group_view=None, metric=None, k=None):
+        from .evaluator import UniEvaluator, re_metric_dict
+        if not isinstance(user_train_dict, dict) or not isinstance(user_test_dict, dict):
+            raise TypeError("user_train_dict and user_test_dict must be dicts")
+        ks = list(top_k) if isinstance(top_k, (list, tuple, np.ndarray)) else [top_k]
+        if not ks or any(isinstance(x, bool) or not isinstance(x, (int, np.integer)) or x < 1 for x in ks):
+            raise ValueError("top_k must be a positive integer or a list of them, got %r" % (top_k,))
+        ks = sorted(set(int(x) for x in ks))
+        k = ks[-1] if k is None else k
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= ks[-1]:
+            raise ValueError("k, the overlap's list length, must lie in [1, the largest cutoff %d], got %r" % (ks[-1], k))
+        if ks[-1] > 256:
+            raise ValueError("the lists hold at most 256 items, got a cutoff of %d" % ks[-1])
+        self.evaluator = ev = UniEvaluator(dataset, user_train_dict, user_test_dict, metric=metric, top_k=ks)
+        self.dataset = dataset
+        self.num_items = int(dataset.num_items)
+        self.user_pos_train = user_train_dict
+        self.user_pos_test = user_test_dict
+        self.top_k, self.k = int(ev.max_top), int(k)
+        self.users = [u for u in ev.default_users() if len(user_train_dict.get(u, []))]
+        self.metric_columns = tuple("%s@%d" % (re_metric_dict[m], c) for m in ev.metrics for c in ev.top_show)
+        self.columns = newuser_columns(self.metric_columns)
+        self._shown = (np.arange(ev.metrics_num, dtype=np.int64)[:, None] * ev.max_top + (np.asarray(ev.top_show, dtype=np.int64) - 1)[None, :]).reshape(-1)
+        self.group_labels, self._positions = ([ALL], []) if not self.users else self._user_groups(self.users, user_train_dict, group_view)
+
+    def _make_resident(self, device):
+        return dict(groups=group_index(self._positions, len(self.users), device), shown=torch.from_numpy(self._shown).to(device))
+
+    def user_rows(self, model):
+        """The per-user rows of every variant on the device: float32 [3 x users x (Cs + 2)] -- the shown metrics, overlap, cos --
+        and the variants' top-K lists int32 [3 x users x K] (what the tests replay on the host)."""
+        device = self._preflight(model)
+        res = self._resident(device)
+        ev, K, k, d = self.evaluator, self.top_k, self.k, model.latent_dim
+        n, Cs, V = len(self.users), len(self.metric_columns), len(NEWUSER_VARIANTS)
+        rows = torch.empty(V, n, Cs + 2, dtype=torch.float32, device=device)
+        lists = torch.empty(V, n, K, dtype=torch.int32, device=device)
+        for a in range(0, n, self.block_users):
+            b = min(n, a + self.block_users)
+            users = self.users[a:b]
+            train_ptr, train_items = lists_csr(users, self.user_pos_train, device, cast=int)
+            truth_ptr, truth_items = lists_csr(users, self.user_pos_test, device, unique=True)
+            users_t = torch.as_tensor(np.asarray(users, dtype=np.int64)).to(device)
+            lists[0, a:b] = model.predict_device(users_t, top_k=K, train_ptr=train_ptr, train_items=train_items, tie_order=self.tie_order)[0]
+            own = model._ws["Y"][users_t, :d].double()
+            sq_own = (own * own).sum(1)
+            metrics = torch.empty(b - a, ev.metrics_num * ev.max_top, dtype=torch.float32, device=device)
+            shared = torch.empty(b - a, dtype=torch.int32, device=device)
+            first = lists[0, a:b, :k].contiguous()
+            for v in range(V):
+                fused = own
+                if v:
+                    new = model.fold_in_users([self.user_pos_train[u] for u in users], id_rows=None if v == 1 else "mean")
+                    lists[v, a:b] = model._new_user_scores(new, top_k=K, train_ptr=new.hist_ptr, train_items=new.hist_items,
+                                                           tie_order=self.tie_order)[0]
+                    fused = new.rows[:, :d].double()
+                ops.rank_metrics(lists[v, a:b].contiguous(), truth_ptr, truth_items, ev.metrics, metrics)
+                rows[v, a:b, :Cs] = metrics.index_select(1, res["shown"])
+                ops.list_overlap(first, lists[v, a:b, :k].contiguous(), shared)
+                rows[v, a:b, Cs] = (shared.double() / k).float()
+                den = torch.sqrt(sq_own * (fused * fused).sum(1))
+                rows[v, a:b, Cs + 1] = torch.where(den > 0, (own * fused).sum(1) / torch.where(den > 0, den, torch.ones_like(den)),
+                                                   torch.zeros_like(den)).float()
+        return rows, lists
+
+    def evaluate(self, model, rows=None):
+        """(final float32 [1 + user groups x 3 variants x columns], buf) -- or (None, the one line that says so) for a split without
+        a test user that has a training history. The `all:` block's metric columns are the evaluator's own overall expression over
+        the users' metric rows (newuser_overall_metrics: the bits UniEvaluator.evaluate returns when every test user has a
+        training history); the group blocks, and overlap / cos everywhere, are ops.group_metric_means' float64 means."""
+        if not self.users:
+            self._preflight(model)
+            return None, format_newuser(None, None, None)
+        if rows is None:
+            rows = self.user_rows(model)[0]
+        res = self._resident(rows.device)
+        G, V = len(self.group_labels), len(NEWUSER_VARIANTS)
+        final = np.zeros((G, V, len(self.columns)), dtype=np.float32)
+        Cs = len(self.metric_columns)
+        for v in range(V):
+            final[:, v, 1:] = group_table(rows[v], res["groups"], G)
+            final[0, v, 1:1 + Cs] = newuser_overall_metrics(rows[v][:, :Cs].contiguous().cpu().numpy())
+        final[:, :, 0] = np.asarray([p.size for p in self._positions], dtype=np.float32)[:, None]
+        return final, self._format(self.columns, final)
+
+    def _format(self, columns, final):
+        labels = [(v + ":").ljust(16) for v in NEWUSER_VARIANTS]
+        return "\n".join(("%s\n" % g.strip() if len(self.group_labels) > 1 else "") + format_newuser(columns, labels, final[i])
+                         for i, g in enumerate(self.group_labels))
+
+    def shift(self, final_a, final_b):
+        """TE -> TIE: (final_b - final_a over the mean columns, buf) with columns d_<column>."""
+        if final_a is None or final_b is None:
+            return None, format_newuser(None, None, None)
+        delta = (final_b - final_a)[:, :, 1:]
+        return delta, self._format(tuple("d_" + c for c in self.columns[1:]), delta)

@@ -602,6 +602,21 @@ int elimrec_rank_values(const float *d_scores, int64_t B, int64_t I, int64_t lds
                         const int32_t *d_skip, int64_t n_vals, int32_t *d_rank, void *stream);
 int elimrec_rank_values_segment(void);
 int elimrec_rank_values_per_pass(void);
+/* Weighted sums of table rows over ragged lists (csrc/foldin.hip): the fold-in of new users from their histories. d_table
+ * float32 [n_rows x C], row stride ld (a multiple of 4 floats, the base 16-byte aligned), C a multiple of 4 in [4, 1280]; the
+ * lists as CSR, d_ptr int64 [Q + 1] / d_rows int32 [n_entries] with d_weights float32 [n_entries] beside them; d_out float32
+ * [Q x C], row stride ldo:
+ *     out[q, :] = sum_{j in [ptr[q], ptr[q + 1])} weights[j] * table[row_offset + rows[j], :]
+ * every product formed and every sum kept in float64, rounded to float32 once; an empty list writes zeros. One workgroup of four
+ * waves per list, chunks of elimrec_segment_row_sum_chunk() entries dealt to the waves in turn, entries added in order within
+ * a wave and the waves' partial sums in wave order: no atomics, no workspace, and a list's bits depend on its own entries, C
+ * and the table alone -- not on Q or on the other lists of the call. The Python wrappers reject ids outside
+ * [0, n_rows - row_offset) and weights that are not finite on the host; the kernel gives an id outside the window weight zero.
+ * One launch on `stream`; Q = 0 launches nothing. */
+int elimrec_segment_row_sum(const float *d_table, int64_t n_rows, int64_t C, int64_t ld, int64_t row_offset, const int64_t *d_ptr,
+                            const int32_t *d_rows, const float *d_weights, int64_t Q, int64_t n_entries, float *d_out, int64_t ldo,
+                            void *stream);
+int elimrec_segment_row_sum_chunk(void);
 /* Rows of the rank report from those ranks. Per pair (no counterpart in the reference, whose metrics stop at K:
  * metric.h:17-106): d_out [P x (3 + n_k)] float32 contiguous = rank, rr = 1 / (rank + 1), pct = rank / (n_cand - 1) (0 when
  * n_cand <= 1), then hit@ks[c] = (rank < ks[c]); ks host int[n_k], n_k <= 16; computed in double, rounded once (the rank column

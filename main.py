@@ -174,6 +174,11 @@ class Net(object):
         self.coldstart_report = int(cfg["coldstart_report"]) if "coldstart_report" in cfg else 0
         if self.coldstart_report and self.world > 1:
             raise ValueError("--coldstart_report needs the whole cached item table on one rank: it is single-GPU")
+        # --newuser_report=K (default 0: off): under each [TEST] line the test users as trained, folded in from their training items and
+        # folded in with the mean id row; after both effects the TE -> TIE difference of the means
+        self.newuser_report = int(cfg["newuser_report"]) if "newuser_report" in cfg else 0
+        if self.newuser_report and self.world > 1:
+            raise ValueError("--newuser_report needs the whole cached tables on one rank: it is single-GPU")
         Logger.info(count_parameters(self.recommender))
         self.opt = FusedAdam(self.recommender.parameters(), lr=cfg.lr, weight_decay=cfg.weight_decay)
         self.loss_name = str(cfg.loss)
@@ -298,7 +303,7 @@ class Net(object):
 
     def test_all_effects(self):
         """TE and TIE metrics on the test split, formatted as the reference prints them."""
-        rec, lines, ranks, shown, backed, sure, reached, grouped, cold = self.recommender, {}, {}, {}, {}, {}, {}, {}, {}
+        rec, lines, ranks, shown, backed, sure, reached, grouped, cold, fresh = self.recommender, {}, {}, {}, {}, {}, {}, {}, {}, {}
         if self.grouped:
             Logger.info(rec.test_evaluator.metrics_info())
         for effect in EFFECTS:
@@ -317,6 +322,9 @@ class Net(object):
             if self.coldstart_report:      # the cold test items as trained / from content / with the mean id row under this effect
                 cold[effect], buf = rec.coldstart_reporter.evaluate(rec)
                 Logger.info("  [{}] cold test items (no training interaction):\n{}".format(effect, buf))
+            if self.newuser_report:        # the test users as trained / folded in from their histories / with the mean id row
+                fresh[effect], buf = rec.newuser_reporter.evaluate(rec)
+                Logger.info("  [{}] [new users] test users folded in from their training histories:\n{}".format(effect, buf))
             if self.list_report:           # the lists themselves under this effect: how alike, how popular, how much of the catalogue
                 shown[effect] = rec.list_reporter.list_rows(rec)
                 Logger.info("  [{}] top-{} lists: similarity, popularity, exposure:\n{}".format(
@@ -357,6 +365,8 @@ class Net(object):
                             effect, source, rec.significance_reporter.shift(reporter.metric_rows(rec, source), sure[effect])[1]))
         if self.coldstart_report:          # d_<column>: TIE - TE
             Logger.info("  [TE->TIE] cold test items:\n{}".format(rec.coldstart_reporter.shift(cold["TE"], cold["TIE"])[1]))
+        if self.newuser_report:            # d_<column>: TIE - TE
+            Logger.info("  [TE->TIE] [new users]:\n{}".format(rec.newuser_reporter.shift(fresh["TE"], fresh["TIE"])[1]))
         if self.rank_report:               # positive delta: TIE ranks the test item higher than TE does
             Logger.info("  [TE->TIE] rank shift of the test items:\n{}".format(rec.rank_reporter.shift(ranks["TE"], ranks["TIE"])[1]))
         if self.list_report:               # overlap: the share of the TE list that TIE keeps; d_<column>: TIE - TE
