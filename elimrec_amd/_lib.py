@@ -265,6 +265,14 @@ SIGNATURES = {
     "elimrec_vote_max_k": (c_i32, []),
     "elimrec_vote_frac_bits": (c_i32, []),
     "elimrec_vote_rows_in_lds": (c_i32, [c_i64]),
+    "elimrec_walk_topk": (c_i32, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_i32, c_ptr, c_ptr, c_ptr, c_i32, c_i64, c_ptr,
+                                  c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
+    "elimrec_walk_workspace": (c_size, [c_i64, c_i64]),
+    "elimrec_walk_slots": (c_i32, []),
+    "elimrec_walk_max_k": (c_i32, []),
+    "elimrec_walk_groups": (c_i32, []),
+    "elimrec_walk_frac_bits": (c_i32, []),
+    "elimrec_walk_rows_in_lds": (c_i32, [c_i64]),
     "elimrec_pick_hard_negatives": (c_i32, [c_ptr, c_i64, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_i64, c_ptr, c_i64, c_i32, c_i32,
                                             ctypes.POINTER(c_f32), c_ptr, c_ptr, c_i64, c_i32, c_ptr, c_ptr, c_ptr, c_ptr]),
     "elimrec_history_support": (c_i32, [c_ptr, c_i64, c_i64, c_i32, c_i32, c_ptr, c_i64, ctypes.POINTER(c_f32), c_ptr, c_ptr, c_i64,
@@ -417,6 +425,7 @@ class _Recording(object):
                              "elimrec_geometry_tile", "elimrec_geometry_chunk", "elimrec_geometry_segment",
                              "elimrec_cooccur_slots", "elimrec_cooccur_max_k", "elimrec_cooccur_groups", "elimrec_cooccur_rows_in_lds",
                              "elimrec_vote_slots", "elimrec_vote_groups", "elimrec_vote_max_k", "elimrec_vote_frac_bits", "elimrec_vote_rows_in_lds",
+                             "elimrec_walk_slots", "elimrec_walk_max_k", "elimrec_walk_groups", "elimrec_walk_frac_bits", "elimrec_walk_rows_in_lds",
                              "elimrec_segment_plan_form",
                              "elimrec_comm_create", "elimrec_comm_destroy", "elimrec_comm_nranks") or name.startswith("elimrec_program_")
             setattr(self, name, self._wrap(fn, name) if res is c_i32 and not plain else fn)

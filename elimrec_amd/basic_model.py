@@ -172,7 +172,7 @@ class BasicModel(nn.Module):
         self.co_reporter = CoNeighbourReport(dataset, train, k_co, measure=co_measure, item_group_view=item_view) if k_co else None
         # --baseline_report=K (CLI-only, default 0 = off): neighbour-vote baselines beside the model -- per --baseline_sources entry
         # (default [co]: ItemKNN over the training graph under --baseline_measure=count|cosine|jaccard, default cosine; fused / a head
-        # letter: content-KNN in that space) the test users' top-K lists voted for by the --baseline_neighbours (default 50) nearest
+        # letter: content-KNN in that space; rp3: RP3beta over the training graph under --baseline_alpha / --baseline_beta) the test users' top-K lists voted for by the --baseline_neighbours (default 50) nearest
         # items of every train item: the evaluator's metrics, how full and how popular the lists are, how much of the model's own
         # list they hold and their catalogue exposure, overall and per user group (reports.BaselineReport)
         k_base = config["baseline_report"] if "baseline_report" in config else 0
@@ -185,14 +185,18 @@ class BasicModel(nn.Module):
         base_measure = str(config["baseline_measure"]) if "baseline_measure" in config else "cosine"
         if base_measure not in ops.COOCCUR_MEASURES:
             raise ValueError("baseline_measure is one of %s, got %r" % (", ".join(sorted(ops.COOCCUR_MEASURES)), base_measure))
+        # --baseline_alpha=1.0 / --baseline_beta=0.6 (CLI-only): RP3beta's exponents for the source rp3 -- the transition
+        # probabilities' power and the popularity penalty on the target item; finite numbers in [0, 4], the commonly used defaults
+        base_alpha, base_beta = ops._rp3_params("baseline_alpha / baseline_beta", config["baseline_alpha"] if "baseline_alpha" in config else 1.0,
+                                                config["baseline_beta"] if "baseline_beta" in config else 0.6)
         self.baseline_reporter = None
         if k_base:
             for x in sources:        # (the model checks a head letter against its own heads at the first list)
-                if x not in ("co", "fused", "v", "a", "t"):
-                    raise ValueError("baseline_sources names 'co', 'fused' or a head letter (v, a, t), got %r" % (x,))
+                if x not in ("co", "rp3", "fused", "v", "a", "t"):
+                    raise ValueError("baseline_sources names 'co', 'rp3', 'fused' or a head letter (v, a, t), got %r" % (x,))
             self.baseline_reporter = BaselineReport(dataset, train, dataset.get_user_test_dict(), config["topks"], metric=config["metric"],
                                                     sources=sources, neighbours=n_near, measure=base_measure,
-                                                    group_view=config["group_view"], list_k=k_base)
+                                                    group_view=config["group_view"], list_k=k_base, alpha=base_alpha, beta=base_beta)
         # --coldstart_report=K (CLI-only, default 0 = off): the cold test items (no training interaction, a test interaction) as
         # trained, folded in from their content and folded in with the mean id row -- pair means of rank, pct, rr and hit@K for the
         # topks and K, overall and per user group (reports.ColdStartReport)

@@ -44,6 +44,10 @@
 //       [Q x K]: per query row the K rows of its side with the largest co-occurrence score ("count", "cosine", "jaccard") over the
 //       bipartite graph the two CSRs give, (score descending, id ascending), -1 / -inf / 0 fillers; both CSRs and the rows are checked
 //       on the host (csrc/cooccur.hip)
+//   walk_topk(q_ptr, q_nbr, o_ptr, o_nbr, rows i32[Q], K, mid_weight i64[m], row_scale f64[n], col_scale f64[n]) -> (idx i32, val f32) [Q x K]:
+//       cooccur_topk's lists with every two-step walk q -> u -> j weighing mid_weight[u] (2^-40 fixed point), the int64 sum scaled by
+//       row_scale[q] col_scale[j] in float64 and rounded once -- P3alpha / RP3beta; the weights, the scales and the overflow bound are
+//       checked on the host (ValueError) (csrc/walk.hip)
 //   neighbour_vote_topk(nbr_idx i32[n x Kn], nbr_val f32[n x Kn], hist_ptr i64[R + 1], hist_items i32, excl_ptr i64[R + 1]?, excl_items i32?,
 //       users i64[B], K) -> (idx i32, val f32, cnt i32) [B x K]: the K items the neighbour lists of each user's history vote for, the
 //       history's own ids and excl's left out; fixed-point int64 sums, the overflow bound and the form rule on the host (csrc/vote.hip)
@@ -769,6 +773,49 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> cooccur_topk(const at::Tensor &q_
     return {idx, val, cnt};
 }
 
+// ---- weighted two-step walks: cooccur_topk's lists with every walk q -> u -> j weighing mid_weight[u] (csrc/walk.hip)
+std::tuple<at::Tensor, at::Tensor> walk_topk(const at::Tensor &q_ptr, const at::Tensor &q_nbr, const at::Tensor &o_ptr, const at::Tensor &o_nbr,
+                                             const at::Tensor &rows, int64_t K, const at::Tensor &mid_weight, const at::Tensor &row_scale,
+                                             const at::Tensor &col_scale) {
+    need(q_ptr, "q_ptr", at::kLong, 1); need(q_nbr, "q_nbr", at::kInt, 1); need(o_ptr, "o_ptr", at::kLong, 1);
+    need(o_nbr, "o_nbr", at::kInt, 1); need(rows, "rows", at::kInt, 1);
+    need(mid_weight, "mid_weight", at::kLong, 1); need(row_scale, "row_scale", at::kDouble, 1); need(col_scale, "col_scale", at::kDouble, 1);
+    TORCH_CHECK_VALUE(K >= 1 && K <= elimrec_walk_max_k(), "elimrec::walk_topk: 1 <= K <= ", elimrec_walk_max_k(), ", got ", K);
+    const at::Tensor qp = q_ptr.contiguous(), qn = q_nbr.contiguous(), op = o_ptr.contiguous(), on = o_nbr.contiguous(), r = rows.contiguous();
+    const at::Tensor mw = mid_weight.contiguous(), rs = row_scale.contiguous(), cs = col_scale.contiguous();
+    const int64_t n_query = qp.numel() - 1, n_other = op.numel() - 1, Q = r.numel();
+    TORCH_CHECK(n_query >= 0 && n_other >= 0, "elimrec::walk_topk: q_ptr and o_ptr need at least one entry");
+    TORCH_CHECK(qn.numel() == on.numel(), "elimrec::walk_topk: the two CSRs hold the same edges, got ", qn.numel(), " and ", on.numel());
+    TORCH_CHECK_VALUE(mw.numel() == n_other && rs.numel() == n_query && cs.numel() == n_query, "elimrec::walk_topk: mid_weight has one entry per row "
+                      "of the other side (", n_other, "), row_scale and col_scale one per query-side row (", n_query, "), got ", mw.numel(), ", ",
+                      rs.numel(), " and ", cs.numel());
+    checked_csr(qp, qn, n_query, n_other, true, "walk_topk", "q_ptr", "q_nbr", "q_nbr", "the other side has", "rows");
+    checked_csr(op, on, n_other, n_query, true, "walk_topk", "o_ptr", "o_nbr", "o_nbr", "the query side has", "rows");
+    checked_ids(r, n_query, true, "walk_topk", "query rows", "the side has", "rows");
+    const int64_t max_w = n_other ? mw.max().item<int64_t>() : 0;
+    TORCH_CHECK_VALUE(n_other == 0 || mw.min().item<int64_t>() >= 0, "elimrec::walk_topk: mid_weight holds a negative entry");
+    TORCH_CHECK_VALUE(n_query == 0 || (at::isfinite(rs).all().item<bool>() && at::isfinite(cs).all().item<bool>() && rs.min().item<double>() >= 0.0 &&
+                                       cs.min().item<double>() >= 0.0),
+                      "elimrec::walk_topk: row_scale and col_scale are finite and >= 0");
+    at::Tensor idx = at::empty({Q, K}, r.options()), val = at::empty({Q, K}, r.options().dtype(at::kFloat));
+    if (Q == 0) return {idx, val};
+    at::Tensor walk = at::empty({Q}, qp.options());
+    check(elimrec_cooccur_walk(qp.data_ptr<int64_t>(), qn.data_ptr<int32_t>(), n_query, op.data_ptr<int64_t>(), n_other, r.data_ptr<int32_t>(), Q,
+                               walk.data_ptr<int64_t>(), cur_stream()), "walk_topk (walk)");
+    const int64_t max_walk = walk.max().item<int64_t>();
+    TORCH_CHECK_VALUE((unsigned __int128)max_walk * (unsigned __int128)max_w < ((unsigned __int128)1 << 62),
+                      "elimrec::walk_topk: the int64 sums could overflow: ", max_walk, " (the longest walk) x ", max_w, " (the largest weight) >= 2^62");
+    const double top = (((double)max_walk * (double)max_w * std::ldexp(1.0, -elimrec_walk_frac_bits())) * rs.max().item<double>()) * cs.max().item<double>();
+    TORCH_CHECK_VALUE(std::isfinite(top), "elimrec::walk_topk: the scores leave float64: (the longest walk) x (the largest weight) x the largest scales");
+    const int64_t n_dense = walk.gt(elimrec_walk_slots() / 2).sum().item<int64_t>();
+    at::Tensor ws = at::zeros({(int64_t)std::max<size_t>(16, elimrec_walk_workspace(n_dense, n_query))}, r.options().dtype(at::kByte));
+    check(elimrec_walk_topk(qp.data_ptr<int64_t>(), qn.data_ptr<int32_t>(), n_query, op.data_ptr<int64_t>(), on.data_ptr<int32_t>(), n_other,
+                            r.data_ptr<int32_t>(), Q, (int)K, mw.data_ptr<int64_t>(), rs.data_ptr<double>(), cs.data_ptr<double>(), 1, n_dense,
+                            walk.data_ptr<int64_t>(), idx.data_ptr<int32_t>(), val.data_ptr<float>(), ws.data_ptr(), (size_t)ws.numel(), cur_stream()),
+          "walk_topk");
+    return {idx, val};
+}
+
 // ---- neighbour votes: per user the K items the neighbour lists of the user's history vote for (csrc/vote.hip)
 std::tuple<at::Tensor, at::Tensor, at::Tensor> neighbour_vote_topk(const at::Tensor &nbr_idx, const at::Tensor &nbr_val, const at::Tensor &hist_ptr,
                                                                    const at::Tensor &hist_items, const c10::optional<at::Tensor> &excl_ptr,
@@ -1049,6 +1096,7 @@ TORCH_LIBRARY(elimrec, m) {
     m.def("uniformity_sum(Tensor table, Tensor sqnorm, Tensor rows, float t) -> (Tensor, Tensor)");
     m.def("row_gram(Tensor table, Tensor sqnorm, Tensor rows) -> (Tensor, Tensor, Tensor)");
     m.def("cooccur_topk(Tensor q_ptr, Tensor q_nbr, Tensor o_ptr, Tensor o_nbr, Tensor rows, int K, str measure) -> (Tensor, Tensor, Tensor)");
+    m.def("walk_topk(Tensor q_ptr, Tensor q_nbr, Tensor o_ptr, Tensor o_nbr, Tensor rows, int K, Tensor mid_weight, Tensor row_scale, Tensor col_scale) -> (Tensor, Tensor)");
     m.def("neighbour_vote_topk(Tensor nbr_idx, Tensor nbr_val, Tensor hist_ptr, Tensor hist_items, Tensor? excl_ptr, Tensor? excl_items, Tensor users, int K) -> (Tensor, Tensor, Tensor)");
     m.def("pick_hard_negatives(Tensor user_table, Tensor user_sqnorm, Tensor item_table, Tensor item_sqnorm, float[] weights, Tensor users, "
           "Tensor cands) -> (Tensor, Tensor, Tensor)");
@@ -1095,6 +1143,7 @@ TORCH_LIBRARY_IMPL(elimrec, CUDA, m) {
     m.impl("uniformity_sum", &uniformity_sum);
     m.impl("row_gram", &row_gram);
     m.impl("cooccur_topk", &cooccur_topk);
+    m.impl("walk_topk", &walk_topk);
     m.impl("neighbour_vote_topk", &neighbour_vote_topk);
     m.impl("pick_hard_negatives", &pick_hard_negatives);
     m.impl("history_support", &history_support);

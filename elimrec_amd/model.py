@@ -22,6 +22,7 @@ What the reference does with 12+12 torch.sparse.mm calls, 8 addmm and autograd p
 Propagation is linear, so nothing of the forward pass is kept for backward except Out (or its active rows) and Y.
 """
 import collections
+import math
 import os
 
 import numpy as np
@@ -1516,29 +1517,115 @@ class EliMRec(BasicModel):
         works on an untrained model."""
         return self._co("user", user_ids, k, measure)
 
-    def _knn_source(self, source, neighbours, measure):
+    def walk_weights(self, side, alpha, beta):
+        """The ops.WalkWeights of RP3beta over one side of the training graph (ops.rp3_weights over cooccur_index(side)), kept per
+        (side, alpha, beta) on the model's device."""
+        index = self.cooccur_index(side)
+        kept = self.__dict__.setdefault("_walk_weights", {})
+        key = (side, float(alpha), float(beta))
+        hit = kept.get(key)
+        if hit is None or hit.device != index.device:
+            hit = kept[key] = ops.rp3_weights(index, alpha, beta)
+        return hit
+
+    @torch.no_grad()
+    def walk_neighbours_device(self, side, rows, k, alpha, beta, out_idx, out_val):
+        """The k RP3beta neighbours of each given row of the TRAINING GRAPH -- side "item": the items a two-step random walk item
+        -> user -> item reaches, each transition probability raised to `alpha`, the target's score divided by its popularity
+        deg^beta; side "user": the same over users -- as ops.walk_topk lists them: out_idx int32 / out_val float32 [B x k] on the
+        device, by (score descending, id ascending), -1 / -inf where fewer than k rows are reached; the row itself is never listed
+        (csrc/walk.hip). rows: the query ids (host array or tensor, checked on the host). The dense form's workspace is kept (every
+        call leaves it zero). Nothing of the learned tables is read: this works on an untrained model. Single-GPU."""
+        k = ops._walk_k("walk_neighbours_device", k)
+        index = self.cooccur_index(side)
+        weights = self.walk_weights(side, alpha, beta)
+        q = ops._cooccur_rows("walk_neighbours_device", index, rows)
+        n_dense = int((index.walk[q] > ops.WALK_SLOTS // 2).sum())
+        need = ops.walk_workspace(n_dense, index.n_query)
+        kept = self.__dict__.setdefault("_walk_ws", {})
+        if need and (kept.get(side) is None or kept[side].numel() < need or kept[side].device != index.device):
+            if need > ops.COOCCUR_WORKSPACE_BUDGET:
+                raise ValueError("walk_neighbours_device: the dense form's rows need %d bytes, the budget is %d"
+                                 % (need, ops.COOCCUR_WORKSPACE_BUDGET))
+            kept[side] = torch.zeros(need, dtype=torch.uint8, device=index.device)     # zero once: every call leaves it zero
+        ops.walk_topk(index, q, k, weights, out_idx, out_val, workspace=kept.get(side) if need else None)
+        return out_idx, out_val
+
+    def _rp3(self, side, ids, k, alpha, beta):
+        n_rows = self.num_items if side == "item" else self.num_users
+        k = ops._walk_k("rp3_%ss" % side, k)
+        alpha, beta = ops._rp3_params("rp3_%ss" % side, alpha, beta)
+        ids = self._id_lists([ids], side, n_rows)[1]
+        dev = self._require_gpu()
+        idx = torch.empty(ids.size, k, dtype=torch.int32, device=dev)
+        val = torch.empty(ids.size, k, dtype=torch.float32, device=dev)
+        self.walk_neighbours_device(side, ids, k, alpha, beta, idx, val)
+        return Neighbours(idx.cpu(), val.cpu())
+
+    def rp3_items(self, item_ids, k, alpha=1.0, beta=0.6):
+        """The k items a two-step random walk over the training graph reaches from each given item, RP3beta's neighbour lists
+        (Paudel et al. 2016; beta = 0 is P3alpha, Cooper et al. 2014): Neighbours(ids CPU int32 [B x k] (-1 padded), scores CPU
+        fp32 [B x k] (-inf padded)), by (score descending, id ascending). score(q, j) = sum over the users u who took both of
+        (1 / deg(q))^alpha (1 / deg(u))^alpha, divided by deg(j)^beta -- beta is the popularity penalty on the target item. The
+        defaults alpha = 1.0, beta = 0.6 are those of the commonly used implementation and are NOT TUNED here. The item itself is
+        never listed, nor an item without a common user. 1 <= k <= 256, alpha and beta finite in [0, 4], else ValueError; an id
+        outside the catalogue is an IndexError -- both before anything touches the device. The lists are read off the training
+        graph alone: no cached tables are needed, so this works on an untrained model."""
+        return self._rp3("item", item_ids, k, alpha, beta)
+
+    def rp3_users(self, user_ids, k, alpha=1.0, beta=0.6):
+        """rp3_items over the users: the k users a walk user -> item -> user reaches from each given user. The defaults are those of
+        the commonly used implementation and are not tuned here. Needs no cached tables: it works on an untrained model."""
+        return self._rp3("user", user_ids, k, alpha, beta)
+
+    def _knn_source(self, source, neighbours, measure, alpha=1.0, beta=0.6):
         """The checks neighbour_lists / recommend_knn / BaselineReport share, before anything touches the device: -> neighbours."""
         if isinstance(neighbours, bool) or not isinstance(neighbours, (int, np.integer)) or not 1 <= neighbours <= ops.VOTE_MAX_K:
             raise ValueError("neighbours must be an integer in [1, %d], got %r" % (ops.VOTE_MAX_K, neighbours))
         ops._cooccur_measure("neighbour_lists", measure)
-        if source != "co":
+        if source == "rp3":
+            ops._rp3_params("neighbour_lists", alpha, beta)
+        elif source != "co":
             if not (source == "fused" or (isinstance(source, str) and source in self._mods)):
-                raise ValueError("source must be 'co', 'fused' or one of this model's heads %s, got %r"
+                raise ValueError("source must be 'co', 'rp3', 'fused' or one of this model's heads %s, got %r"
                                  % ("/".join(self._mods) or "(none)", source))
         return int(neighbours)
 
+    @staticmethod
+    def _vote_scale(val):
+        """(e, zero_votes) of a block of list values [n x Kn] (-inf fillers) whose magnitudes the vote's 2^-24 fixed point would lose:
+        the power of two 2^e that puts the largest finite value into [0.5, 1) (0 without a positive one; at most 126), applied IN
+        PLACE with torch.ldexp -- exact, and the order is kept --, and the share of the listed entries whose vote rint(double(val)
+        * 2^24) is 0 all the same (0.0 without a listed entry)."""
+        finite = torch.isfinite(val)
+        top = float(torch.where(finite, val, torch.zeros_like(val)).max().item()) if val.numel() else 0.0
+        e = min(126, -math.frexp(top)[1]) if top > 0.0 else 0
+        if e:
+            val.copy_(torch.ldexp(val, torch.tensor(e, dtype=torch.int32, device=val.device)))
+        listed = int(finite.sum().item())
+        lost = int((finite & (torch.round(val.double() * 2.0 ** ops.VOTE_FRAC_BITS) == 0)).sum().item())
+        return e, (lost / listed if listed else 0.0)
+
     @torch.no_grad()
-    def neighbour_lists(self, source="co", neighbours=50, measure="cosine"):
+    def neighbour_lists(self, source="co", neighbours=50, measure="cosine", alpha=1.0, beta=0.6):
         """The `neighbours` nearest items of EVERY item as the ops.NeighbourLists [num_items x neighbours] neighbour_vote_topk
         takes, built in blocks of KNN_LIST_BLOCK items and kept on the device. source "co": the co-interaction neighbours of the
         training graph under `measure` (co_neighbours_device; no cached tables are needed, so this works on an untrained model),
-        kept per (neighbours, measure); "fused" or a head letter of self._mods: the cosine neighbours in that space of the cached
-        tables (neighbours_device; `measure` is not used), kept per table version. Errors as similar_items / co_items."""
-        neighbours = self._knn_source(source, neighbours, measure)
+        kept per (neighbours, measure); "rp3": the RP3beta neighbours of the training graph under `alpha` and `beta`
+        (walk_neighbours_device; `measure` is not used; untrained models as well), kept per (neighbours, alpha, beta) -- their
+        values, deg^-alpha deg^-alpha deg^-beta, are far below the 2^-24 a vote is quantised to, so the whole block is multiplied by
+        ONE power of two 2^e that puts its largest value into [0.5, 1): the returned lists carry scale_exp = e and zero_votes = the
+        share of the listed entries whose fixed-point vote is 0 all the same (that loss is the vote's, and it is reported, not
+        hidden); "fused" or a head letter of self._mods: the cosine neighbours in that space of the cached tables
+        (neighbours_device; `measure` is not used), kept per table version. alpha and beta are read by "rp3" alone. Errors as
+        similar_items / co_items / rp3_items."""
+        neighbours = self._knn_source(source, neighbours, measure, alpha, beta)
         dev = self._require_gpu()
         kept = self.__dict__.setdefault("_knn_lists", {})
         if source == "co":
             key, version = ("co", neighbours, measure), 0
+        elif source == "rp3":
+            key, version = ("rp3", neighbours, float(alpha), float(beta)), 0
         else:
             self._cached_tables("similar_items() / similar_users() need", "neighbour lists need the whole cached tables on this rank; "
                                 "the tables are item-sharded (lean / multi-rank evaluation)")
@@ -1553,9 +1640,14 @@ class EliMRec(BasicModel):
             rows = np.arange(lo, min(I, lo + KNN_LIST_BLOCK), dtype=np.int64)
             if source == "co":
                 self.co_neighbours_device("item", rows, neighbours, measure, idx[lo:lo + rows.size], val[lo:lo + rows.size])
+            elif source == "rp3":
+                self.walk_neighbours_device("item", rows, neighbours, alpha, beta, idx[lo:lo + rows.size], val[lo:lo + rows.size])
             else:
                 self.neighbours_device("item", rows, neighbours, source, idx[lo:lo + rows.size], val[lo:lo + rows.size])
+        scale = self._vote_scale(val) if source == "rp3" else None
         lists = ops.NeighbourLists(idx, val, dev)
+        if scale is not None:
+            lists.scale_exp, lists.zero_votes = scale
         kept[key] = (version, lists)
         return lists
 
@@ -1585,18 +1677,20 @@ class EliMRec(BasicModel):
         ops.neighbour_vote_topk(lists, hist, u, k, out_idx, out_val, out_cnt, excl=excl, workspace=ws if need else None)
         return out_idx, out_val, out_cnt
 
-    def recommend_knn(self, user_ids, k, neighbours=50, source="co", measure="cosine", history=None, exclude=None):
+    def recommend_knn(self, user_ids, k, neighbours=50, source="co", measure="cosine", history=None, exclude=None, alpha=1.0, beta=0.6):
         """A neighbourhood recommender beside the model's own lists: per user the k items the `neighbours` nearest items of every
         item of the user's history vote for -- KnnLists(ids CPU int32 [B x k] (-1 padded), scores CPU fp32 [B x k] (-inf padded: the
         sum of the neighbour scores behind the item, in 2^-24 fixed point), votes CPU int32 [B x k] (their number)), by (score
         descending, id ascending). source "co" is ItemKNN over the training graph under `measure` ("count", "cosine", "jaccard");
-        "fused" or a head letter of self._mods is content-KNN in that space ("v": recommend what looks like what you took).
+        "fused" or a head letter of self._mods is content-KNN in that space ("v": recommend what looks like what you took);
+        "rp3" is RP3beta over the training graph under `alpha` and `beta` (rp3_items; the two are ignored by the other sources; the
+        defaults are the commonly used ones, not tuned here), its scores in units of 2^-e, e = neighbour_lists(...).scale_exp.
         history: dict user -> item ids (default: the data set's train dict, as explain_history takes it); the history's own items
         are never listed; `exclude` = dict user -> item ids left out on top, as explain() takes it. k or neighbours outside
         [1, 256], an unknown source or measure: ValueError; an id outside its side: IndexError -- both before anything touches the
         device. An empty user_ids returns [0 x k] without a launch."""
         k = ops._vote_k("recommend_knn", k)
-        neighbours = self._knn_source(source, neighbours, measure)
+        neighbours = self._knn_source(source, neighbours, measure, alpha, beta)
         users = self._id_lists([user_ids], "user", self.num_users)[1]
         if history is None:
             history = self.dataset.get_user_train_dict()
@@ -1608,7 +1702,7 @@ class EliMRec(BasicModel):
         if not n:
             return KnnLists(torch.empty(0, k, dtype=torch.int32), torch.empty(0, k, dtype=torch.float32), torch.empty(0, k, dtype=torch.int32))
         dev = self._require_gpu()
-        lists = self.neighbour_lists(source, neighbours, measure)
+        lists = self.neighbour_lists(source, neighbours, measure, alpha, beta)
         hist = ops.HistoryIndex(hptr, hflat, dev, n_items=self.num_items)
         excl = ops.HistoryIndex(tptr, tflat, dev, n_items=self.num_items) if tflat.size else None
         idx, val, cnt = self.knn_recommend_device(np.arange(n, dtype=np.int64), lists, hist, k, excl)     # row b's history is segment b

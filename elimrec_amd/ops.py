@@ -2337,7 +2337,7 @@ class CooccurIndex(object):
     ascending from 0 to the edge count, the two edge counts equal (ValueError); integer ids, q_nbr in [0, n_other) and o_nbr in
     [0, n_query) (IndexError). That o is q transposed is the caller's word -- the kernel needs only what is checked to stay within
     its arrays. A repeated edge is an edge of its own. cooccur_topk takes the index as is, call after call. Kept on the host:
-    deg (the query side's degrees), walk (int64 [n_query]: W(q) = the sum of deg(u) over q's segment, which picks a row's form)
+    deg (the query side's degrees), deg_other (the other side's), walk (int64 [n_query]: W(q) = the sum of deg(u) over q's segment, which picks a row's form)
     and has_neighbour (bool [n_query]: one of the row's neighbours has degree >= 2, so some other row shares it)."""
 
     def __init__(self, q_ptr, q_nbr, o_ptr, o_nbr, n_query, n_other, device):
@@ -2351,7 +2351,7 @@ class CooccurIndex(object):
             raise ValueError("elimrec_amd.ops.%s: the two CSRs hold the same edges, got %d and %d" % (who, qn.size, on.size))
         self.n_query, self.n_other, self.n_edges = n_query, n_other, int(qn.size)
         self.deg = np.diff(qp)
-        deg_o = np.diff(op)
+        self.deg_other = deg_o = np.diff(op)
         along = np.zeros(qn.size + 1, dtype=np.int64)
         np.cumsum(deg_o[qn], out=along[1:])
         self.walk = along[qp[1:]] - along[qp[:-1]]
@@ -2451,6 +2451,154 @@ def cooccur_topk(index, rows, K, out_idx, out_val=None, out_cnt=None, measure="c
     return out_idx
 
 
+WALK_MAX_K = 256                         # the longest list walk_topk keeps (csrc/walk.hip), known without the library
+WALK_FRAC_BITS = 40                      # fraction bits of a walk's fixed-point weight: mid_weight = rint(weight * 2^40)
+WALK_SLOTS = 4096                        # (key, sum) entries of the LDS form's table of walk_topk: W <= WALK_SLOTS / 2 takes that form
+
+
+def walk_rows_in_lds(W):
+    """Which form walk_topk takes for a query row whose walk is W = the sum of deg(u) over the row's segment (index.walk,
+    cooccur_walk; host arithmetic only): True = the LDS form (W <= WALK_SLOTS / 2), False = the dense form. Both forms give the
+    same bits. ValueError for W < 0."""
+    form = int(_lib.load().elimrec_walk_rows_in_lds(int(W)))
+    if form < 0:
+        raise ValueError("elimrec_amd.ops.walk_rows_in_lds: W >= 0, got %d" % W)
+    return bool(form)
+
+
+def walk_workspace(n_dense_rows, n):
+    """Bytes of the dense form's rows for a call with n_dense_rows rows on that form over a query side of n rows (host arithmetic
+    only): min(n_dense_rows, 512) rows of n int64 sums."""
+    if n_dense_rows < 0 or not 0 <= n < 2 ** 31 - 1:
+        raise ValueError("elimrec_amd.ops.walk_workspace: n_dense_rows >= 0 and 0 <= n < 2^31 - 1, got %d and %d" % (n_dense_rows, n))
+    return int(_lib.load().elimrec_walk_workspace(int(n_dense_rows), int(n)))
+
+
+def _walk_k(who, K):
+    if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or not 1 <= K <= WALK_MAX_K:
+        raise ValueError("elimrec_amd.ops.%s: K must be an integer, 1 <= K <= %d, got %r" % (who, WALK_MAX_K, K))
+    return int(K)
+
+
+class WalkWeights(object):
+    """The three arrays of a weighted two-step walk (walk_topk), CHECKED ONCE ON THE HOST and then resident on `device`:
+    mid_weight int64 [n_other], every entry >= 0 -- the weight of a walk through u in WALK_FRAC_BITS = 40 bit fixed point --,
+    row_scale and col_scale float64 [n_query], finite and >= 0. An integer dtype for mid_weight and float64 for the scales, one
+    dimension each, the scales of one length, else ValueError. Kept on the host: n_other, n_query, max_weight (a Python int) and
+    max_scale = max(row_scale) * max(col_scale), which walk_topk's bounds use."""
+
+    def __init__(self, mid_weight, row_scale, col_scale, device):
+        who = "WalkWeights"
+        w, r, c = _host(mid_weight), _host(row_scale), _host(col_scale)
+        if w.ndim != 1 or not np.issubdtype(w.dtype, np.integer) or w.dtype == np.uint64:
+            raise ValueError("elimrec_amd.ops.%s: mid_weight is a flat array of a signed integer dtype, got %s %s" % (who, w.dtype, w.shape))
+        if r.ndim != 1 or c.ndim != 1 or r.dtype != np.float64 or c.dtype != np.float64 or r.shape != c.shape:
+            raise ValueError("elimrec_amd.ops.%s: row_scale and col_scale are flat float64 arrays of one length, got %s %s and %s %s"
+                             % (who, r.dtype, r.shape, c.dtype, c.shape))
+        w = np.ascontiguousarray(w, dtype=np.int64)
+        if w.size and int(w.min()) < 0:
+            raise ValueError("elimrec_amd.ops.%s: mid_weight holds a negative weight (%d)" % (who, int(w.min())))
+        for name, x in (("row_scale", r), ("col_scale", c)):
+            if x.size and not (np.isfinite(x).all() and float(x.min()) >= 0.0):
+                raise ValueError("elimrec_amd.ops.%s: %s is finite and >= 0 everywhere" % (who, name))
+        self.n_other, self.n_query = int(w.size), int(r.size)
+        self.max_weight = int(w.max()) if w.size else 0
+        self.max_scale = (float(r.max()) * float(c.max())) if r.size else 0.0
+        self.device = torch.device(device)
+        pad = lambda x, dt: torch.from_numpy(np.ascontiguousarray(x if x.size else np.zeros(1), dtype=dt)).to(self.device)
+        self.mid_weight, self.row_scale, self.col_scale = pad(w, np.int64), pad(r, np.float64), pad(c, np.float64)
+
+
+def _rp3_params(who, alpha, beta):
+    """RP3beta's two exponents as floats: finite numbers in [0, 4], anything else is a ValueError."""
+    for name, x in (("alpha", alpha), ("beta", beta)):
+        if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or not (math.isfinite(x) and 0.0 <= x <= 4.0):
+            raise ValueError("%s: %s is a finite number in [0, 4], got %r" % (who, name, x))
+    return float(alpha), float(beta)
+
+
+def rp3_weights(index, alpha, beta):
+    """The ops.WalkWeights of P3alpha / RP3beta (Cooper et al. 2014, Paudel et al. 2016) over an ops.CooccurIndex, in numpy float64
+    from the index's degrees: the walk q -> u -> j has probability (1 / deg(q))^alpha (1 / deg(u))^alpha, and the target pays
+    deg(j)^-beta for its popularity. mid_weight[u] = rint(deg(u)^-alpha * 2^40), row_scale[q] = deg(q)^-alpha, col_scale[j] =
+    deg(j)^-beta; a row of degree 0 gets 0 in all three. alpha and beta are finite numbers in [0, 4] (ValueError). alpha = beta =
+    0 counts the walks: every weight is 2^40 and every scale 1."""
+    if not isinstance(index, CooccurIndex):
+        raise TypeError("elimrec_amd.ops.rp3_weights: index must be an ops.CooccurIndex, got %s" % type(index).__name__)
+    alpha, beta = _rp3_params("elimrec_amd.ops.rp3_weights", alpha, beta)
+
+    def power(deg, p):
+        d = deg.astype(np.float64)
+        return np.where(deg > 0, np.power(np.maximum(d, 1.0), -p), 0.0)
+
+    mid = np.rint(power(index.deg_other, alpha) * 2.0 ** WALK_FRAC_BITS).astype(np.int64)
+    return WalkWeights(mid, power(index.deg, alpha), power(index.deg, beta), index.device)
+
+
+def _walk_bounds(who, index, q, weights):
+    """The host's bounds of a walk call: the weights fit the index; the int64 sums cannot overflow; the scores stay in float64."""
+    if not isinstance(weights, WalkWeights):
+        raise TypeError("elimrec_amd.ops.%s: weights must be an ops.WalkWeights, got %s" % (who, type(weights).__name__))
+    if weights.n_other != index.n_other or weights.n_query != index.n_query:
+        raise ValueError("elimrec_amd.ops.%s: the index has %d query rows and %d rows on the other side, the weights %d scales and %d weights"
+                         % (who, index.n_query, index.n_other, weights.n_query, weights.n_other))
+    if weights.device != index.device:
+        raise ValueError("elimrec_amd.ops.%s: the index lives on %s, the weights on %s" % (who, index.device, weights.device))
+    longest = int(index.walk[q].max()) if q.size else 0
+    if longest * weights.max_weight >= 2 ** 62:
+        raise ValueError("elimrec_amd.ops.%s: the int64 sums could overflow: %d (the longest walk) x %d (the largest weight) >= 2^62"
+                         % (who, longest, weights.max_weight))
+    if not math.isfinite(float(longest * weights.max_weight) * 2.0 ** -WALK_FRAC_BITS * weights.max_scale):
+        raise ValueError("elimrec_amd.ops.%s: the scores leave float64: %d (the longest walk) x %d (the largest weight) x 2^-%d x %r"
+                         % (who, longest, weights.max_weight, WALK_FRAC_BITS, weights.max_scale))
+
+
+def walk_topk(index, rows, K, weights, out_idx, out_val=None, lds=True, workspace=None):
+    """elimrec_walk_topk: cooccur_topk's lists with every two-step walk weighted by the node it passes through (csrc/walk.hip) --
+    P3alpha / RP3beta with rp3_weights, Adamic-Adar or resource allocation with other weights. index: an ops.CooccurIndex;
+    weights: an ops.WalkWeights of its two sides; rows: host array or tensor of ids, checked on the host (IndexError).
+    S(q, j) = the sum over the walks q -> u -> j, j != q, of mid_weight[u] (int64; a repeated edge is a walk of its own);
+    val = float32((float64(S) * 2^-40) * row_scale[q] * col_scale[j]), float64 left to right, rounded once. Listed: the rows
+    with at least one walk, never q itself. out_idx int32 / out_val float32 (optional) [Q x K] on the index's device <- the K best
+    by (fp32 score descending, id ascending), -1 / -inf behind them. 1 <= K <= WALK_MAX_K = 256. A row with
+    walk_rows_in_lds(index.walk[q]) takes the LDS form, every other row -- with lds=False every row -- the dense form, whose int64
+    rows live in `workspace`: a uint8 device tensor of at least walk_workspace(n_dense_rows, index.n_query) bytes, 16-byte aligned,
+    ZERO before its first use (every call leaves it zero); default: allocated and zeroed here, at most COOCCUR_WORKSPACE_BUDGET
+    bytes. Refused before any launch (ValueError): (the longest walk of the rows) x (the largest weight) >= 2^62, scores that would
+    leave float64, weights that do not fit the index, K, a workspace that is too small, a default workspace past the budget.
+    Both forms give the same bits: a row's outputs depend on the graph, the three arrays, the row and K alone. An empty `rows`
+    returns without a launch."""
+    who = "walk_topk"
+    K = _walk_k(who, K)
+    q = _cooccur_rows(who, index, rows)
+    _walk_bounds(who, index, q, weights)
+    Q, dev = int(q.size), index.device
+    ip = _rows_out(out_idx, "out_idx", torch.int32, Q, K, who, dev)
+    vp = _rows_out(out_val, "out_val", torch.float32, Q, K, who, dev) if out_val is not None else None
+    if Q == 0:
+        return out_idx
+    n_dense = int((index.walk[q] > WALK_SLOTS // 2).sum()) if lds else Q
+    need = walk_workspace(n_dense, index.n_query)
+    if workspace is None:
+        if need > COOCCUR_WORKSPACE_BUDGET:
+            raise ValueError("elimrec_amd.ops.%s: the dense form's rows need %d bytes (%d rows of %d sums), the budget is %d: pass a "
+                             "workspace" % (who, need, min(n_dense, _lib.load().elimrec_walk_groups()), index.n_query,
+                                            COOCCUR_WORKSPACE_BUDGET))
+        workspace = torch.zeros(max(16, need), dtype=torch.uint8, device=dev)
+    wp = _dev(workspace, "workspace", torch.uint8)
+    if workspace.numel() < need or not workspace.is_contiguous() or wp % 16 or workspace.device != dev:
+        raise ValueError("elimrec_amd.ops.%s: the workspace needs %d contiguous bytes on the index's device, 16-byte aligned (got %d)"
+                         % (who, need, workspace.numel()))
+    walk = torch.empty(Q, dtype=torch.int64, device=dev)
+    _lib.check(_lib.load().elimrec_walk_topk(_dev(index.q_ptr, "q_ptr", torch.int64), _dev(index.q_nbr, "q_nbr", torch.int32), index.n_query,
+                                             _dev(index.o_ptr, "o_ptr", torch.int64), _dev(index.o_nbr, "o_nbr", torch.int32), index.n_other,
+                                             _dev(_resident_ids(q, dev), "rows", torch.int32), Q, K,
+                                             _dev(weights.mid_weight, "mid_weight", torch.int64), _dev(weights.row_scale, "row_scale", torch.float64),
+                                             _dev(weights.col_scale, "col_scale", torch.float64), 1 if lds else 0, n_dense, walk.data_ptr(),
+                                             ip, vp, wp, workspace.numel(), _stream()), who)
+    return out_idx
+
+
 VOTE_MAX_K = 256                         # the longest list neighbour_vote_topk keeps (csrc/vote.hip), known without the library
 VOTE_FRAC_BITS = 24                      # fraction bits of a vote's fixed-point value: q = rint(double(val) * 2^24)
 VOTE_MAX_VOTES = 1 << 30                 # (history length) x Kn of one user stays below this: the count's mark bit of a left-out id
@@ -2462,7 +2610,11 @@ class NeighbourLists(object):
     resident on `device`: neighbour_vote_topk takes them as is, call after call. idx and val: host arrays or tensors (device tensors
     stay where they are when they already live on `device`). max_abs = the largest |val| over the FINITE values (0.0 without one),
     taken here once -- for device tensors that read is a synchronisation; neighbour_vote_topk's overflow bound uses it. The ids'
-    range is left to the kernel, which checks every entry and never dereferences one outside [0, n)."""
+    range is left to the kernel, which checks every entry and never dereferences one outside [0, n). scale_exp / zero_votes: the
+    power of two EliMRec.neighbour_lists multiplied the values by before they came here, and the share of listed entries whose
+    fixed-point vote is 0 (source "rp3"; 0 / None otherwise)."""
+
+    scale_exp, zero_votes = 0, None
 
     def __init__(self, idx, val, device):
         who = "NeighbourLists"

@@ -1638,7 +1638,10 @@ class BaselineReport(_Report):
     (--baseline_report=K)? Per source a neighbour-vote recommender (EliMRec.knn_recommend_device, csrc/vote.hip) over the test users
     in the evaluator's default order, their train items as the history and left out: "co" = ItemKNN over the training graph under
     `measure`, "fused" / a head letter = content-KNN in that space of the cached tables ("v": recommend what looks like what you
-    took -- the single-modal shortcut as a recommender of its own), each item's `neighbours` nearest items voting.
+    took -- the single-modal shortcut as a recommender of its own), "rp3" = RP3beta over the training graph under `alpha` and
+    `beta` (EliMRec.rp3_items: the graph random walk with a popularity penalty on the target; the defaults are the commonly used
+    ones, not tuned here; its list values are scaled by one power of two before they vote, and rp3_info = (scale exponent e,
+    zero_votes) says what the vote's fixed point still loses), each item's `neighbours` nearest items voting.
     metric_rows() is ops.rank_metrics over those lists with the truth CSR, metric ids and shown-column layout of
     SignificanceReport.metric_rows, so the two row blocks pair user by user (SignificanceReport.shift); a -1 filler is a miss (the
     metric kernel compares ids against a truth list of ids >= 0). evaluate() gives one row per source -- with group_view one block of
@@ -1652,15 +1655,17 @@ class BaselineReport(_Report):
     name, needs = "baseline", "knn_recommend_device"
 
     def __init__(self, dataset, user_train_dict, user_test_dict, top_k, metric=None, sources=("co",), neighbours=50, measure="cosine",
-                 group_view=None, list_k=None):
+                 group_view=None, list_k=None, alpha=1.0, beta=0.6):
         from .evaluator import UniEvaluator, re_metric_dict
         if not isinstance(user_train_dict, dict) or not isinstance(user_test_dict, dict):
             raise TypeError("user_train_dict and user_test_dict must be dicts")
         if isinstance(sources, str) or not len(sources) or any(not isinstance(x, str) or not x for x in sources) or len(set(sources)) != len(sources):
-            raise ValueError("sources is a sequence of distinct names: 'co', 'fused' or a head letter, got %r" % (sources,))
+            raise ValueError("sources is a sequence of distinct names: 'co', 'rp3', 'fused' or a head letter, got %r" % (sources,))
         if isinstance(neighbours, bool) or not isinstance(neighbours, (int, np.integer)) or not 1 <= neighbours <= ops.VOTE_MAX_K:
             raise ValueError("neighbours must be an integer in [1, %d], got %r" % (ops.VOTE_MAX_K, neighbours))
         ops._cooccur_measure("BaselineReport", measure)
+        self.alpha, self.beta = ops._rp3_params("BaselineReport", alpha, beta)
+        self.rp3_info = None
         self.evaluator = ev = UniEvaluator(dataset, user_train_dict, user_test_dict, metric=metric, top_k=top_k)
         list_k = ev.max_top if list_k is None else list_k
         if isinstance(list_k, bool) or not isinstance(list_k, (int, np.integer)) or not ev.max_top <= list_k <= ops.VOTE_MAX_K:
@@ -1698,7 +1703,9 @@ class BaselineReport(_Report):
             raise ValueError("source is one of this report's %s, got %r" % ("/".join(self.sources), source))
         device = self._preflight(model)
         res = self._resident(device)
-        lists = model.neighbour_lists(source, self.neighbours, self.measure)
+        lists = model.neighbour_lists(source, self.neighbours, self.measure, self.alpha, self.beta)
+        if source == "rp3":
+            self.rp3_info = (lists.scale_exp, lists.zero_votes)
         hit = self._lists.get((source, str(device)))
         if hit is not None and hit[0] is lists:
             return hit[1]
@@ -1726,7 +1733,9 @@ class BaselineReport(_Report):
 
     def evaluate(self, model):
         """(BaselineTables(columns, labels, table float64 [sources x (1 + groups) x C]), buf): per source row "all:" and then the
-        group_view groups, over self.columns. buf: a header of column names and one "%.8f" line per row."""
+        group_view groups, over self.columns. buf: a header of column names and one "%.8f" line per row; with "rp3" among the
+        sources one more line: rp3: alpha=... beta=... scale=2^e zero_votes=... (the share of its listed neighbour entries whose
+        fixed-point vote is 0)."""
         device = self._preflight(model)
         res = self._resident(device)
         n, K, G, Cs = len(self.users), self.k, len(self.group_labels), len(self.metric_columns)
@@ -1754,7 +1763,10 @@ class BaselineReport(_Report):
                     ops.list_exposure(lists.index_select(0, at).contiguous(), counts)
                 table[s * G + g, Cs + 3:] = exposure_summary(counts.cpu().numpy(), [np.arange(self.num_items)])[0, 1:4]
         final = BaselineTables(self.columns, list(self.labels), table)
-        return final, format_table(final.columns, final.labels, final.table)
+        buf = format_table(final.columns, final.labels, final.table)
+        if "rp3" in self.sources:
+            buf += "\nrp3: alpha=%g beta=%g scale=2^%d zero_votes=%.6f" % ((self.alpha, self.beta) + self.rp3_info)
+        return final, buf
 
 
 COLDSTART_VARIANTS = ("catalogue", "content", "mean_id")

@@ -899,6 +899,33 @@ int elimrec_vote_max_k(void);
 int elimrec_vote_frac_bits(void);
 int elimrec_vote_rows_in_lds(int64_t V);
 
+/* Weighted two-step walks (csrc/walk.hip): elimrec_cooccur_topk's lists with every walk q -> u -> j, j != q, weighing
+ * d_mid_weight[u] -- P3alpha / RP3beta neighbour lists, Adamic-Adar and resource allocation by other weights. No counterpart in
+ * the reference. The graph, d_rows, d_walk, use_lds, n_dense_rows and the form rule are elimrec_cooccur_topk's (walk_slots = 4096
+ * (int32 key, int64 sum) entries in 48 KiB of LDS, the selection list written over them; W <= slots / 2 takes the LDS form).
+ * d_mid_weight int64 [n_other], every entry >= 0, in elimrec_walk_frac_bits() = 40 bit fixed point; d_row_scale / d_col_scale
+ * float64 [n_query], finite and >= 0. S(q, j) = the int64 sum of the walks' weights (a repeated edge is a walk of its own);
+ * val = (float)((((double)S * 2^-40) * row_scale[q]) * col_scale[j]): float64, left to right, rounded once to fp32. THE CALLER
+ * keeps S within int64: (the largest W) x (the largest weight) < 2^62. Listed: the rows with at least one walk through a valid u
+ * (a sum of 0 is listed with score 0), never q itself. d_idx int32 / d_val fp32 (optional) [Q x K] <- the K best by (fp32 score
+ * descending, id ascending), -1 / -inf behind them. 1 <= K <= elimrec_walk_max_k() = 256. A query id outside the side gives
+ * fillers; a neighbour id outside its side is skipped and never dereferenced.
+ * The dense form: min(n_dense_rows, elimrec_walk_groups() = 512) workgroups, each with a row of n_query int64 sums in d_workspace
+ * (elimrec_walk_workspace(n_dense_rows, n_query) bytes, 16-byte aligned), which must be ZERO when the call starts and is zero
+ * again when it ends. Both forms give the same bits: a row's outputs depend on the graph, the three arrays, the row and K alone.
+ * Integer atomics only, no floating-point sums. Two or three launches on `stream` (the first is elimrec_cooccur_walk's). */
+int elimrec_walk_topk(const int64_t *d_q_ptr, const int32_t *d_q_nbr, int64_t n_query, const int64_t *d_o_ptr,
+                      const int32_t *d_o_nbr, int64_t n_other, const int32_t *d_rows, int64_t Q, int K,
+                      const int64_t *d_mid_weight, const double *d_row_scale, const double *d_col_scale, int use_lds,
+                      int64_t n_dense_rows, int64_t *d_walk, int32_t *d_idx, float *d_val, void *d_workspace,
+                      size_t workspace_bytes, void *stream);
+size_t elimrec_walk_workspace(int64_t n_dense_rows, int64_t n);
+int elimrec_walk_slots(void);
+int elimrec_walk_max_k(void);
+int elimrec_walk_groups(void);
+int elimrec_walk_frac_bits(void);
+int elimrec_walk_rows_in_lds(int64_t W);
+
 /* Hard-negative pick (csrc/hardneg.hip): per triplet the best of M candidate items under the current tables. No counterpart in
  * the reference. d_U / d_T point at row 0, column 0 of an [n_users x blocks * d] / [n_items x blocks * d] slice of a row-major
  * float32 matrix with row stride ld_u / ld_i >= blocks * d, block b = columns [b * d, (b + 1) * d); d_sq_u[r * ldsq_u + b] /
