@@ -170,11 +170,12 @@ class BasicModel(nn.Module):
         if co_measure not in ops.COOCCUR_MEASURES:
             raise ValueError("co_measure is one of %s, got %r" % (", ".join(sorted(ops.COOCCUR_MEASURES)), co_measure))
         self.co_reporter = CoNeighbourReport(dataset, train, k_co, measure=co_measure, item_group_view=item_view) if k_co else None
-        # --baseline_report=K (CLI-only, default 0 = off): neighbour-vote baselines beside the model -- per --baseline_sources entry
-        # (default [co]: ItemKNN over the training graph under --baseline_measure=count|cosine|jaccard, default cosine; fused / a head
-        # letter: content-KNN in that space; rp3: RP3beta over the training graph under --baseline_alpha / --baseline_beta) the test users' top-K lists voted for by the --baseline_neighbours (default 50) nearest
-        # items of every train item: the evaluator's metrics, how full and how popular the lists are, how much of the model's own
-        # list they hold and their catalogue exposure, overall and per user group (reports.BaselineReport)
+        # --baseline_report=K (CLI-only, default 0 = off): baselines beside the model -- per --baseline_sources entry (default [co]:
+        # ItemKNN over the training graph under --baseline_measure=count|cosine|jaccard, default cosine; fused / a head letter:
+        # content-KNN in that space; rp3: RP3beta over the training graph under --baseline_alpha / --baseline_beta; ials: the iALS
+        # factor model, no vote) the test users' top-K lists, voted for by the --baseline_neighbours (default 50) nearest items of
+        # every train item: the evaluator's metrics, how full and how popular the lists are, how much of the model's own list they
+        # hold and their catalogue exposure, overall and per user group (reports.BaselineReport)
         k_base = config["baseline_report"] if "baseline_report" in config else 0
         if isinstance(k_base, bool) or not isinstance(k_base, int) or k_base < 0:
             raise ValueError("baseline_report must be 0 (off) or the K of the baseline lists, got %r" % (k_base,))
@@ -189,14 +190,21 @@ class BasicModel(nn.Module):
         # probabilities' power and the popularity penalty on the target item; finite numbers in [0, 4], the commonly used defaults
         base_alpha, base_beta = ops._rp3_params("baseline_alpha / baseline_beta", config["baseline_alpha"] if "baseline_alpha" in config else 1.0,
                                                 config["baseline_beta"] if "baseline_beta" in config else 0.6)
+        # --baseline_factors=64 / --baseline_iters=15 / --baseline_conf=1.0 / --baseline_reg=0.01 / --baseline_reg_scale=0.0 (CLI-only):
+        # the source ials -- implicit-feedback ALS over the training graph (EliMRec.fit_ials): factors in {16, 32, 48, 64}, 1 <= iters
+        # <= 100, conf >= 0, reg > 0, 0 <= reg_scale <= 1 (0: the constant ridge; > 0: scaled by (degree + 1) ** reg_scale); not tuned
+        ials = ops._ials_params("baseline_factors / _iters / _conf / _reg / _reg_scale",
+                                *[config["baseline_" + k] if ("baseline_" + k) in config else v for k, v in (
+                                    ("factors", 64), ("iters", 15), ("conf", 1.0), ("reg", 0.01), ("reg_scale", 0.0))])
         self.baseline_reporter = None
         if k_base:
             for x in sources:        # (the model checks a head letter against its own heads at the first list)
-                if x not in ("co", "rp3", "fused", "v", "a", "t"):
-                    raise ValueError("baseline_sources names 'co', 'rp3', 'fused' or a head letter (v, a, t), got %r" % (x,))
+                if x not in ("co", "rp3", "ials", "fused", "v", "a", "t"):
+                    raise ValueError("baseline_sources names 'co', 'rp3', 'ials', 'fused' or a head letter (v, a, t), got %r" % (x,))
             self.baseline_reporter = BaselineReport(dataset, train, dataset.get_user_test_dict(), config["topks"], metric=config["metric"],
                                                     sources=sources, neighbours=n_near, measure=base_measure,
-                                                    group_view=config["group_view"], list_k=k_base, alpha=base_alpha, beta=base_beta)
+                                                    group_view=config["group_view"], list_k=k_base, alpha=base_alpha, beta=base_beta,
+                                                    factors=ials[0], iters=ials[1], conf=ials[2], reg=ials[3], reg_scale=ials[4])
         # --coldstart_report=K (CLI-only, default 0 = off): the cold test items (no training interaction, a test interaction) as
         # trained, folded in from their content and folded in with the mean id row -- pair means of rank, pct, rr and hit@K for the
         # topks and K, overall and per user group (reports.ColdStartReport)

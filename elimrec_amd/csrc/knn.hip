@@ -1,4 +1,6 @@
-// Cosine top-K of table rows against the rows of the same table (similar items / similar users), and the overlap of two id lists.
+// Cosine top-K of table rows against the rows of the same table (similar items / similar users) or of a second table
+// (cross_topk: the query rows come from a table of their own -- with unit squared norms on both sides the score is the plain dot
+// product, inv_norm(1.0) being exactly 1: serving a factor model), and the overlap of two id lists.
 //
 // knn_chunk_kernel: the grid is (query tiles x candidate chunks). A workgroup of W waves holds 16 W query rows -- a wave owns 16
 // of them as the A operands of v_mfma_f32_16x16x4_f32 (registers for d = 32 / 64 / 128, a lane-private LDS column otherwise) --
@@ -31,6 +33,8 @@ typedef float knn_v4f __attribute__((ext_vector_type(4)));
 struct KnnArgs {
     const float *T; int64_t ld, n_rows; int d;
     const float *sq; int64_t ld_sq;
+    const float *Tq; int64_t ldq, nq_rows;   // the query table (cosine_topk: the table itself): rows, stride, row count,
+    const float *sqq; int64_t ld_sqq;        // squared norms and their stride
     const int32_t *qrows; int64_t Q; int exclude_self;
     const int64_t *excl_ptr; const int32_t *excl_rows;
     int K, n_chunks, vec;              // vec: T is 16-byte aligned and ld % 4 == 0 -> a row's float4s are single loads
@@ -64,13 +68,13 @@ __global__ __launch_bounds__(64 * W) void knn_chunk_kernel(KnnArgs a) {
     const int64_t c_begin = (int64_t)chunk * KNN_CHUNK;
     const int64_t c_end = c_begin + KNN_CHUNK < a.n_rows ? c_begin + KNN_CHUNK : a.n_rows;
 
-    // A operands: query (q0 + li), element k = 4 ks + kq; a query outside [0, Q) or with an id outside the table is all zeros
+    // A operands: query (q0 + li), element k = 4 ks + kq; a query outside [0, Q) or with an id outside the query table is all zeros
     float qa[D ? D / 4 : 1];
     {
         const int64_t q = q0 + li;
         int64_t qr = q < a.Q ? (int64_t)a.qrows[q] : -1;
-        if (qr >= a.n_rows) qr = -1;
-        const float *row = qr >= 0 ? a.T + qr * a.ld + kq : nullptr;
+        if (qr >= a.nq_rows) qr = -1;
+        const float *row = qr >= 0 ? a.Tq + qr * a.ldq + kq : nullptr;
         if (D) {
 #pragma unroll
             for (int ks = 0; ks < (D ? D / 4 : 1); ++ks) qa[ks] = row ? row[4 * ks] : 0.f;
@@ -85,15 +89,15 @@ __global__ __launch_bounds__(64 * W) void knn_chunk_kernel(KnnArgs a) {
     for (int r = 0; r < 4; ++r) {
         const int64_t q = q0 + 4 * kq + r;
         int64_t qr = q < a.Q ? (int64_t)a.qrows[q] : -1;
-        if (qr >= a.n_rows) qr = -1;
+        if (qr >= a.nq_rows) qr = -1;
         qid[r] = (int)qr;
-        invq[r] = qr >= 0 ? inv_norm(a.sq[qr * a.ld_sq]) : 0.f;
+        invq[r] = qr >= 0 ? inv_norm(a.sqq[qr * a.ld_sqq]) : 0.f;
         thr[r] = knn_thr0(qr >= 0);
     }
     if (lane < 16) {
         const int64_t q = q0 + lane;
         int64_t qr = q < a.Q ? (int64_t)a.qrows[q] : -1;
-        if (qr >= a.n_rows) qr = -1;
+        if (qr >= a.nq_rows) qr = -1;
         knn_list_reset(my, lane, qr >= 0);
     }
 
@@ -191,17 +195,17 @@ __global__ __launch_bounds__(256) void list_overlap_kernel(const int32_t *__rest
 }
 
 template <int D, int W>
-static int knn_launch(const KnnArgs &a, int64_t n_tiles, hipStream_t s) {
-    return knn_launch_chunks("cosine_topk", knn_chunk_kernel<D, W>, a, n_tiles, a.n_chunks, 64 * W, knn_lds_bytes(D, W, a.d, a.K), s);
+static int knn_launch(const char *who, const KnnArgs &a, int64_t n_tiles, hipStream_t s) {
+    return knn_launch_chunks(who, knn_chunk_kernel<D, W>, a, n_tiles, a.n_chunks, 64 * W, knn_lds_bytes(D, W, a.d, a.K), s);
 }
 
 template <int W>
-static int knn_dispatch(const KnnArgs &a, int64_t n_tiles, hipStream_t s) {
+static int knn_dispatch(const char *who, const KnnArgs &a, int64_t n_tiles, hipStream_t s) {
     switch (a.d) {
-    case 32: return knn_launch<32, W>(a, n_tiles, s);
-    case 64: return knn_launch<64, W>(a, n_tiles, s);
-    case 128: return knn_launch<128, W>(a, n_tiles, s);
-    default: return knn_launch<0, W>(a, n_tiles, s);
+    case 32: return knn_launch<32, W>(who, a, n_tiles, s);
+    case 64: return knn_launch<64, W>(who, a, n_tiles, s);
+    case 128: return knn_launch<128, W>(who, a, n_tiles, s);
+    default: return knn_launch<0, W>(who, a, n_tiles, s);
     }
 }
 
@@ -216,26 +220,31 @@ extern "C" size_t elimrec_cosine_topk_workspace(int64_t Q, int64_t n_rows, int K
     return knn_workspace_bytes(Q, n_rows, K);
 }
 
-extern "C" int elimrec_cosine_topk(const float *d_T, int64_t ld, int64_t n_rows, int d, const float *d_sqnorm, int64_t ld_sq,
-                                   const int32_t *d_query_rows, int64_t Q, int exclude_self, const int64_t *d_excl_ptr,
-                                   const int32_t *d_excl_rows, int K, int32_t *d_idx, float *d_val, void *d_workspace,
-                                   size_t workspace_bytes, void *stream) {
-    if (int rc = knn_check_k("cosine_topk", K)) return rc;
-    if (int rc = table_dims("cosine_topk", d, 1)) return rc;
-    ELIMREC_REQUIRE(Q >= 0 && n_rows >= 0 && n_rows < (int64_t)INT32_MAX - KNN_CHUNK, "cosine_topk: need Q >= 0 and 0 <= n_rows < 2^31 - %d",
+// what the two entry points share; `who` names the caller in every message
+static int knn_run(const char *who, const float *d_Tq, int64_t ldq, int64_t nq_rows, const float *d_sqq, int64_t ld_sqq, const float *d_T,
+                   int64_t ld, int64_t n_rows, int d, const float *d_sqnorm, int64_t ld_sq, const int32_t *d_query_rows, int64_t Q,
+                   int exclude_self, const int64_t *d_excl_ptr, const int32_t *d_excl_rows, int K, int32_t *d_idx, float *d_val,
+                   void *d_workspace, size_t workspace_bytes, void *stream) {
+    if (int rc = knn_check_k(who, K)) return rc;
+    if (int rc = table_dims(who, d, 1)) return rc;
+    ELIMREC_REQUIRE(Q >= 0 && n_rows >= 0 && n_rows < (int64_t)INT32_MAX - KNN_CHUNK, "%s: need Q >= 0 and 0 <= n_rows < 2^31 - %d", who,
                     KNN_CHUNK + 1);
-    ELIMREC_REQUIRE(ld >= d && ld_sq >= 1, "cosine_topk: ld < d or ld_sq < 1");
+    ELIMREC_REQUIRE(ld >= d && ld_sq >= 1, "%s: ld < d or ld_sq < 1", who);
+    ELIMREC_REQUIRE(nq_rows >= 0 && ldq >= d && ld_sqq >= 1, "%s: the query table needs rows >= 0, ld >= d and ld_sq >= 1", who);
     if (Q == 0) return 0;
-    ELIMREC_REQUIRE(d_query_rows && d_idx && d_workspace, "cosine_topk: null pointer");
-    ELIMREC_REQUIRE(n_rows == 0 || (d_T && d_sqnorm), "cosine_topk: null pointer");
-    if (int rc = knn_check_buffers("cosine_topk", d_excl_ptr, d_excl_rows, d_workspace, workspace_bytes, Q, n_rows, K)) return rc;
+    ELIMREC_REQUIRE(d_query_rows && d_idx && d_workspace, "%s: null pointer", who);
+    ELIMREC_REQUIRE(n_rows == 0 || (d_T && d_sqnorm), "%s: null pointer", who);
+    ELIMREC_REQUIRE(nq_rows == 0 || (d_Tq && d_sqq), "%s: null pointer", who);
+    if (int rc = knn_check_buffers(who, d_excl_ptr, d_excl_rows, d_workspace, workspace_bytes, Q, n_rows, K)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if (n_rows == 0) return knn_fill_empty("cosine_topk", d_idx, d_val, Q, K, s);       // an empty table
+    if (n_rows == 0) return knn_fill_empty(who, d_idx, d_val, Q, K, s);       // an empty table
     KnnWorkspace ws;
-    if (int rc = knn_carve("cosine_topk", "queries", Q, n_rows, K, d_workspace, &ws)) return rc;
+    if (int rc = knn_carve(who, "queries", Q, n_rows, K, d_workspace, &ws)) return rc;
     KnnArgs a;
     a.T = d_T; a.ld = ld; a.n_rows = n_rows; a.d = d;
     a.sq = d_sqnorm; a.ld_sq = ld_sq;
+    a.Tq = d_Tq; a.ldq = ldq; a.nq_rows = nq_rows;
+    a.sqq = d_sqq; a.ld_sqq = ld_sqq;
     a.qrows = d_query_rows; a.Q = Q; a.exclude_self = exclude_self ? 1 : 0;
     a.excl_ptr = d_excl_ptr; a.excl_rows = d_excl_rows;
     a.K = K; a.n_chunks = (int)ws.n_chunks;
@@ -243,10 +252,30 @@ extern "C" int elimrec_cosine_topk(const float *d_T, int64_t ld, int64_t n_rows,
     a.ws_val = ws.val; a.ws_idx = ws.idx;
     const int rows = K <= KNN_SMALLK ? KNN_TILE : 16;
     const int64_t n_tiles = (Q + rows - 1) / rows;
-    ELIMREC_REQUIRE(n_tiles < (int64_t)INT32_MAX, "cosine_topk: too many query tiles for one launch");
-    int rc = K <= KNN_SMALLK ? knn_dispatch<4>(a, n_tiles, s) : knn_dispatch<1>(a, n_tiles, s);
+    ELIMREC_REQUIRE(n_tiles < (int64_t)INT32_MAX, "%s: too many query tiles for one launch", who);
+    int rc = K <= KNN_SMALLK ? knn_dispatch<4>(who, a, n_tiles, s) : knn_dispatch<1>(who, a, n_tiles, s);
     if (rc) return rc;
     return knn_merge(ws, Q, K, d_idx, d_val, stream);
+}
+
+extern "C" int elimrec_cosine_topk(const float *d_T, int64_t ld, int64_t n_rows, int d, const float *d_sqnorm, int64_t ld_sq,
+                                   const int32_t *d_query_rows, int64_t Q, int exclude_self, const int64_t *d_excl_ptr,
+                                   const int32_t *d_excl_rows, int K, int32_t *d_idx, float *d_val, void *d_workspace,
+                                   size_t workspace_bytes, void *stream) {
+    return knn_run("cosine_topk", d_T, ld, n_rows, d_sqnorm, ld_sq, d_T, ld, n_rows, d, d_sqnorm, ld_sq, d_query_rows, Q, exclude_self,
+                   d_excl_ptr, d_excl_rows, K, d_idx, d_val, d_workspace, workspace_bytes, stream);
+}
+
+extern "C" size_t elimrec_cross_topk_workspace(int64_t Q, int64_t n_rows, int K) {
+    return knn_workspace_bytes(Q, n_rows, K);
+}
+
+extern "C" int elimrec_cross_topk(const float *d_Tq, int64_t ldq, int64_t nq_rows, const float *d_sqq, int64_t ld_sqq, const float *d_T,
+                                  int64_t ld, int64_t n_rows, int d, const float *d_sqnorm, int64_t ld_sq, const int32_t *d_query_rows,
+                                  int64_t Q, const int64_t *d_excl_ptr, const int32_t *d_excl_rows, int K, int32_t *d_idx, float *d_val,
+                                  void *d_workspace, size_t workspace_bytes, void *stream) {
+    return knn_run("cross_topk", d_Tq, ldq, nq_rows, d_sqq, ld_sqq, d_T, ld, n_rows, d, d_sqnorm, ld_sq, d_query_rows, Q, 0, d_excl_ptr,
+                   d_excl_rows, K, d_idx, d_val, d_workspace, workspace_bytes, stream);
 }
 
 extern "C" int elimrec_list_overlap(const int32_t *d_a, const int32_t *d_b, int64_t n_rows, int K, int32_t *d_count, void *stream) {

@@ -48,6 +48,13 @@
 //       cooccur_topk's lists with every two-step walk q -> u -> j weighing mid_weight[u] (2^-40 fixed point), the int64 sum scaled by
 //       row_scale[q] col_scale[j] in float64 and rounded once -- P3alpha / RP3beta; the weights, the scales and the overflow bound are
 //       checked on the host (ValueError) (csrc/walk.hip)
+//   cross_topk(query_table f32[nq x d], query_sqnorm f32[nq]?, table f32[n x d], sqnorm f32[n]?, query_rows i32[Q], excl_ptr i64[Q + 1]?,
+//       excl_rows i32?, K) -> (idx i32, val f32) [Q x K]: cosine_topk with a query table of its own; a missing sqnorm is a vector of ones,
+//       without both the score is the plain dot product (csrc/knn.hip)
+//   als_solve(ptr i64[n + 1], nbr i32, F f32[n_fixed x d], A0 f64[d x d], reg f64[n], conf, rows i32[Q]?) -> f32[n x d]: one half-sweep of
+//       implicit-feedback ALS, out[r] = (A0 + reg[r] I + conf sum f f^T)^-1 (1 + conf) sum f over row r's list, float64 Cholesky per row;
+//       rows not listed are zero; the CSR (strictly ascending lists), reg and conf are checked on the host (csrc/als.hip). A row that
+//       is not positive definite raises through TORCH_CHECK, a RuntimeError here (ops.als_solve raises ArithmeticError with the same words)
 //   neighbour_vote_topk(nbr_idx i32[n x Kn], nbr_val f32[n x Kn], hist_ptr i64[R + 1], hist_items i32, excl_ptr i64[R + 1]?, excl_items i32?,
 //       users i64[B], K) -> (idx i32, val f32, cnt i32) [B x K]: the K items the neighbour lists of each user's history vote for, the
 //       history's own ids and excl's left out; fixed-point int64 sums, the overflow bound and the form rule on the host (csrc/vote.hip)
@@ -489,6 +496,85 @@ std::tuple<at::Tensor, at::Tensor> cosine_topk(const at::Tensor &table, const at
                               val.data_ptr<float>(), ws.data_ptr(), (size_t)ws.numel(), cur_stream()),
           "cosine_topk");
     return {idx, val};
+}
+
+// ---- cosine_topk with a query table of its own; without norms the plain dot product (serving a factor model)
+std::tuple<at::Tensor, at::Tensor> cross_topk(const at::Tensor &query_table, const c10::optional<at::Tensor> &query_sqnorm, const at::Tensor &table,
+                                              const c10::optional<at::Tensor> &sqnorm, const at::Tensor &query_rows,
+                                              const c10::optional<at::Tensor> &excl_ptr, const c10::optional<at::Tensor> &excl_rows, int64_t K) {
+    const at::Tensor tq = rowmajor(query_table, "query_table"), t = rowmajor(table, "table");
+    need(query_rows, "query_rows", at::kInt, 1);
+    const at::Tensor q = query_rows.contiguous();
+    const int64_t nq = tq.size(0), n = t.size(0), d = t.size(1), Q = q.numel();
+    TORCH_CHECK_VALUE(K >= 1 && K <= 256, "elimrec::cross_topk: 1 <= K <= 256, got ", K);
+    TORCH_CHECK_VALUE(d % 4 == 0 && d >= 4 && d <= 256, "elimrec::cross_topk: the table needs d % 4 == 0 and 4 <= d <= 256 columns, got ", d);
+    TORCH_CHECK_VALUE(tq.size(1) == d, "elimrec::cross_topk: the two tables share d, got ", tq.size(1), " and ", d);
+    TORCH_CHECK_VALUE(excl_ptr.has_value() == excl_rows.has_value(), "elimrec::cross_topk: excl_ptr and excl_rows come together");
+    const at::Tensor sqq = query_sqnorm.has_value() ? *query_sqnorm : at::ones({std::max<int64_t>(nq, 1)}, tq.options());
+    const at::Tensor sq = sqnorm.has_value() ? *sqnorm : at::ones({std::max<int64_t>(n, 1)}, t.options());
+    need(sqq, "query_sqnorm", at::kFloat, 1); need(sq, "sqnorm", at::kFloat, 1);
+    TORCH_CHECK_VALUE((!query_sqnorm.has_value() || sqq.numel() == nq) && (!sqnorm.has_value() || sq.numel() == n),
+                      "elimrec::cross_topk: the squared norms need one entry per row of their table");
+    checked_ids(q, nq, true, "cross_topk", "query rows", "the query table has", "rows");
+    at::Tensor ep, er;
+    if (excl_ptr.has_value()) {
+        need(*excl_ptr, "excl_ptr", at::kLong, 1); need(*excl_rows, "excl_rows", at::kInt, 1);
+        ep = excl_ptr->contiguous(); er = excl_rows->contiguous();
+        TORCH_CHECK_VALUE(ep.numel() == Q + 1, "elimrec::cross_topk: excl_ptr needs Q + 1 = ", Q + 1, " entries, got ", ep.numel());
+        checked_csr(ep, er, Q, n, true, "cross_topk", "excl_ptr", "excl_rows", "excluded rows", "the table has", "rows");
+    }
+    at::Tensor idx = at::empty({Q, K}, q.options()), val = at::empty({Q, K}, t.options());
+    if (Q == 0) return {idx, val};
+    const size_t need_ws = elimrec_cross_topk_workspace(Q, n, (int)K);
+    at::Tensor ws = at::empty({(int64_t)need_ws}, t.options().dtype(at::kByte));
+    check(elimrec_cross_topk(tq.data_ptr<float>(), tq.stride(0), nq, sqq.data_ptr<float>(), sqq.numel() > 1 ? sqq.stride(0) : 1, t.data_ptr<float>(),
+                             t.stride(0), n, (int)d, sq.data_ptr<float>(), sq.numel() > 1 ? sq.stride(0) : 1, q.data_ptr<int32_t>(), Q,
+                             ep.defined() ? ep.data_ptr<int64_t>() : nullptr, ep.defined() && er.numel() ? er.data_ptr<int32_t>() : (ep.defined() ? q.data_ptr<int32_t>() : nullptr),
+                             (int)K, idx.data_ptr<int32_t>(), val.data_ptr<float>(), ws.data_ptr(), (size_t)ws.numel(), cur_stream()),
+          "cross_topk");
+    return {idx, val};
+}
+
+// ---- one half-sweep of implicit-feedback ALS (csrc/als.hip)
+at::Tensor als_solve(const at::Tensor &ptr, const at::Tensor &nbr, const at::Tensor &F, const at::Tensor &A0, const at::Tensor &reg, double conf,
+                     const c10::optional<at::Tensor> &rows) {
+    need(ptr, "ptr", at::kLong, 1); need(nbr, "nbr", at::kInt, 1); need(A0, "A0", at::kDouble, 2); need(reg, "reg", at::kDouble, 1);
+    const at::Tensor f = rowmajor(F, "F"), p = ptr.contiguous(), nb = nbr.contiguous(), a0 = A0.contiguous(), rg = reg.contiguous();
+    const int64_t n = p.numel() - 1, n_fixed = f.size(0), d = f.size(1);
+    TORCH_CHECK_VALUE(n >= 0, "elimrec::als_solve: ptr needs n + 1 >= 1 entries");
+    TORCH_CHECK_VALUE(d % 16 == 0 && d >= 16 && d <= 64, "elimrec::als_solve: the factors need d % 16 == 0 and 16 <= d <= 64 columns, got ", d);
+    TORCH_CHECK_VALUE(a0.size(0) == d && a0.size(1) == d, "elimrec::als_solve: A0 must be [", d, " x ", d, "]");
+    TORCH_CHECK_VALUE(rg.numel() == n, "elimrec::als_solve: reg needs one entry per row (", n, "), got ", rg.numel());
+    TORCH_CHECK_VALUE(std::isfinite(conf) && conf >= 0.0, "elimrec::als_solve: conf is finite and >= 0, got ", conf);
+    TORCH_CHECK_VALUE(n == 0 || (at::isfinite(rg).all().item<bool>() && rg.min().item<double>() >= 0.0), "elimrec::als_solve: every reg is finite and >= 0");
+    checked_csr(p, nb, n, n_fixed, true, "als_solve", "ptr", "nbr", "nbr", "the fixed side has", "rows");
+    const at::Tensor hp = p.cpu(), hn = nb.cpu();
+    const int64_t *pp = hp.data_ptr<int64_t>();
+    const int32_t *nn = hn.data_ptr<int32_t>();
+    for (int64_t r = 0; r < n; ++r)
+        for (int64_t e = pp[r] + 1; e < pp[r + 1]; ++e)
+            TORCH_CHECK_VALUE(nn[e] > nn[e - 1], "elimrec::als_solve: every list is strictly ascending (no repeated edge): row ", r, " lists ", nn[e - 1],
+                              ", then ", nn[e]);
+    at::Tensor q;
+    if (rows.has_value()) {
+        need(*rows, "rows", at::kInt, 1);
+        q = rows->contiguous();
+        checked_ids(q, n, true, "als_solve", "rows", "the side has", "rows");
+    } else {
+        q = at::argsort(p.slice(0, 0, n) - p.slice(0, 1), /*stable=*/true, 0, false).to(at::kInt);   // degree descending
+    }
+    at::Tensor out = at::zeros({n, d}, f.options());
+    if (q.numel() == 0) return out;
+    at::Tensor status = at::zeros({2}, nb.options());
+    status.select(0, 1).fill_((int64_t)INT32_MAX);
+    check(elimrec_als_solve(f.data_ptr<float>(), f.stride(0), n_fixed, (int)d, a0.data_ptr<double>(), p.data_ptr<int64_t>(),
+                            nb.numel() ? nb.data_ptr<int32_t>() : nullptr, n, q.data_ptr<int32_t>(), q.numel(), rg.data_ptr<double>(), conf,
+                            out.data_ptr<float>(), out.stride(0), status.data_ptr<int32_t>(), cur_stream()),
+          "als_solve");
+    const at::Tensor hs = status.cpu();
+    TORCH_CHECK(hs.data_ptr<int32_t>()[0] == 0, "elimrec::als_solve: A_r is not positive definite for ", hs.data_ptr<int32_t>()[0],
+                " row(s), the first is row ", hs.data_ptr<int32_t>()[1], " (written as zeros)");
+    return out;
 }
 
 // ---- audience lists: per query item the K users with the largest predict() score (csrc/audience.hip)
@@ -1095,6 +1181,8 @@ TORCH_LIBRARY(elimrec, m) {
     m.def("kmeans_update(Tensor table, Tensor sqnorm, Tensor assign, Tensor centroids, Tensor centroid_sqnorm) -> (Tensor, Tensor, Tensor, Tensor)");
     m.def("uniformity_sum(Tensor table, Tensor sqnorm, Tensor rows, float t) -> (Tensor, Tensor)");
     m.def("row_gram(Tensor table, Tensor sqnorm, Tensor rows) -> (Tensor, Tensor, Tensor)");
+    m.def("cross_topk(Tensor query_table, Tensor? query_sqnorm, Tensor table, Tensor? sqnorm, Tensor query_rows, Tensor? excl_ptr, Tensor? excl_rows, int K) -> (Tensor, Tensor)");
+    m.def("als_solve(Tensor ptr, Tensor nbr, Tensor F, Tensor A0, Tensor reg, float conf, Tensor? rows) -> Tensor");
     m.def("cooccur_topk(Tensor q_ptr, Tensor q_nbr, Tensor o_ptr, Tensor o_nbr, Tensor rows, int K, str measure) -> (Tensor, Tensor, Tensor)");
     m.def("walk_topk(Tensor q_ptr, Tensor q_nbr, Tensor o_ptr, Tensor o_nbr, Tensor rows, int K, Tensor mid_weight, Tensor row_scale, Tensor col_scale) -> (Tensor, Tensor)");
     m.def("neighbour_vote_topk(Tensor nbr_idx, Tensor nbr_val, Tensor hist_ptr, Tensor hist_items, Tensor? excl_ptr, Tensor? excl_items, Tensor users, int K) -> (Tensor, Tensor, Tensor)");
@@ -1142,6 +1230,8 @@ TORCH_LIBRARY_IMPL(elimrec, CUDA, m) {
     m.impl("kmeans_update", &kmeans_update);
     m.impl("uniformity_sum", &uniformity_sum);
     m.impl("row_gram", &row_gram);
+    m.impl("cross_topk", &cross_topk);
+    m.impl("als_solve", &als_solve);
     m.impl("cooccur_topk", &cooccur_topk);
     m.impl("walk_topk", &walk_topk);
     m.impl("neighbour_vote_topk", &neighbour_vote_topk);

@@ -88,6 +88,7 @@ class NewUsers(object):
 
 KNN_LIST_BLOCK = 4096                    # items per launch when neighbour_lists builds the lists of the whole catalogue
 KnnLists = collections.namedtuple("KnnLists", ("ids", "scores", "votes"))
+IalsFactors = collections.namedtuple("IalsFactors", ("users", "items", "params", "objective"))
 HistorySupport = collections.namedtuple("HistorySupport", ("items", "history", "scores", "count", "mean"))
 
 
@@ -1707,6 +1708,119 @@ class EliMRec(BasicModel):
         excl = ops.HistoryIndex(tptr, tflat, dev, n_items=self.num_items) if tflat.size else None
         idx, val, cnt = self.knn_recommend_device(np.arange(n, dtype=np.int64), lists, hist, k, excl)     # row b's history is segment b
         return KnnLists(idx.cpu(), val.cpu(), cnt.cpu())
+
+    @staticmethod
+    def _ials_params(factors=64, iters=15, conf=1.0, reg=0.01, reg_scale=0.0, seed=2022):
+        """The checks fit_ials / recommend_ials / BaselineReport share (ops._ials_params), before anything touches the device: -> the
+        parameter tuple the fit is kept under."""
+        return ops._ials_params("fit_ials", factors, iters, conf, reg, reg_scale, seed)
+
+    def _ials_graph(self, dev):
+        """The training graph as the two ops.AlsIndex of the fit -- every user's list de-duplicated and sorted, the transpose
+        likewise --, checked once and kept on the device: (users' index, items' index)."""
+        hit = self.__dict__.get("_ials_index")
+        if hit is None or hit[0].device != dev:
+            U, I = self.num_users, self.num_items
+            train = self.dataset.get_user_train_dict()
+            none = np.zeros(0, dtype=np.int64)
+            up, ui, _ = self._id_lists([np.unique(np.asarray(train.get(u, none), dtype=np.int64)) for u in range(U)], "train item")
+            order = np.argsort(ui, kind="stable")
+            ip = np.zeros(I + 1, dtype=np.int64)
+            np.cumsum(np.bincount(ui, minlength=I), out=ip[1:])
+            iu = np.repeat(np.arange(U, dtype=np.int64), np.diff(up))[order]
+            hit = self.__dict__["_ials_index"] = (ops.AlsIndex(up, ui, U, I, dev), ops.AlsIndex(ip, iu, I, U, dev))
+        return hit
+
+    @torch.no_grad()
+    def fit_ials(self, factors=64, iters=15, conf=1.0, reg=0.01, reg_scale=0.0, seed=2022):
+        """The implicit-feedback ALS baseline (Hu, Koren, Volinsky, ICDM 2008) over the TRAINING GRAPH alone: IalsFactors(users
+        float32 [U x factors], items float32 [I x factors] -- device tensors --, params, objective), kept per parameter tuple (a
+        second call returns the kept handle). A pure-ID factor model of the model's own dimension: what the content and the graph
+        convolution buy is the difference to it. Nothing of the learned tables is read, so this works on an untrained model.
+        Items start at float32(0.01 * default_rng(seed).standard_normal((I, factors))), users at zero; every iteration solves the
+        users from the items, then the items from the users, each half-sweep one ops.als_solve (csrc/als.hip) over the float64
+        Gram of the fixed side (ops.row_gram). reg[r] = reg * (deg(r) + 1) ** reg_scale: reg_scale = 0 is the classical constant
+        ridge, reg_scale > 0 the frequency-scaled ridge of Rendle et al. (RecSys 2022) without its second constant. objective:
+        float64 [2 iters], the iALS loss after every half-sweep,
+            <G_X, G_Y>_F + sum_obs [(1 + conf)(1 - s)^2 - s^2] + sum_r reg[r] |x_r|^2,
+        the Grams from ops.row_gram, the observed term a float64 torch composition (a log line, not the hot path). The defaults
+        are not tuned here. factors in {16, 32, 48, 64}, 1 <= iters <= 100, conf >= 0, reg > 0, 0 <= reg_scale <= 1, all finite:
+        else ValueError before anything touches the device. Single-GPU."""
+        params = self._ials_params(factors, iters, conf, reg, reg_scale, seed)
+        factors, iters, conf, reg, reg_scale, seed = params
+        dev = self._require_gpu()
+        kept = self.__dict__.setdefault("_ials", {})
+        hit = kept.get(params)
+        if hit is not None and hit.users.device == dev:
+            return hit
+        U, I = self.num_users, self.num_items
+        by_user, by_item = self._ials_graph(dev)
+        # the ridges stay host arrays for als_solve: checked there without a read back (a device tensor would be read back per half-sweep)
+        host_u = reg * (by_user.deg.astype(np.float64) + 1.0) ** reg_scale
+        host_i = reg * (by_item.deg.astype(np.float64) + 1.0) ** reg_scale
+        reg_u, reg_i = torch.from_numpy(host_u).to(dev), torch.from_numpy(host_i).to(dev)
+        Y = torch.from_numpy((0.01 * np.random.default_rng(seed).standard_normal((I, factors))).astype(np.float32)).to(dev)
+        X = torch.zeros(U, factors, dtype=torch.float32, device=dev)
+        ones = torch.ones(max(U, I), dtype=torch.float32, device=dev)
+        every = torch.arange(max(U, I), dtype=torch.int32, device=dev)
+        G = {s: torch.empty(factors, factors, dtype=torch.float64, device=dev) for s in "XY"}
+        ws = torch.empty(max(16, ops.row_gram_workspace(max(U, I), factors)), dtype=torch.uint8, device=dev)
+        edge_u = torch.repeat_interleave(torch.arange(U, device=dev), torch.from_numpy(by_user.deg).to(dev))
+        edge_i = by_user.nbr[:by_user.n_edges].long()
+        objective = torch.empty(2 * iters, dtype=torch.float64, device=dev)
+
+        def gram(T, side, n):
+            return ops.row_gram_device(T, ones[:n], every[:n], out_gram=G[side], workspace=ws)[0]
+
+        def loss(at):
+            s = (X[edge_u].double() * Y[edge_i].double()).sum(1)
+            objective[at] = ((gram(X, "X", U) * gram(Y, "Y", I)).sum() + ((1.0 + conf) * (1.0 - s) ** 2 - s * s).sum()
+                             + (reg_u * X.double().pow(2).sum(1)).sum() + (reg_i * Y.double().pow(2).sum(1)).sum())
+
+        for it in range(iters):
+            ops.als_solve(by_user, Y, gram(Y, "Y", I), host_u, conf, X)
+            loss(2 * it)
+            ops.als_solve(by_item, X, gram(X, "X", U), host_i, conf, Y)
+            loss(2 * it + 1)
+        hit = kept[params] = IalsFactors(X, Y, params, objective.cpu().numpy())
+        return hit
+
+    @torch.no_grad()
+    def ials_recommend_device(self, users, factors, k, excl=None, out_idx=None, out_val=None):
+        """The k items with the largest x_u . y_i of an IalsFactors (fit_ials), over ops.cross_topk: out_idx int32 / out_val
+        float32 [B x k] on the device (allocated here when None), by (score descending, id ascending), -1 / -inf where fewer than
+        k items are left. users: user ids (host array or tensor, checked on the host) or an ops.CrossQuery that carries its
+        exclusions; excl: (ptr, item ids) to leave out per user, as CSR on the host. 1 <= k <= 256. Single-GPU."""
+        dev = self._require_gpu()
+        if not isinstance(factors, IalsFactors):
+            raise TypeError("factors must be the IalsFactors fit_ials returns")
+        k = ops._cooccur_k("ials_recommend_device", k)
+        if isinstance(users, ops.CrossQuery):
+            query = users
+        else:
+            query = ops.CrossQuery(users, self.num_users, self.num_items, dev, *(excl if excl is not None else (None, None)))
+        B = query.n_queries
+        out_idx = torch.empty(B, k, dtype=torch.int32, device=dev) if out_idx is None else out_idx
+        out_val = torch.empty(B, k, dtype=torch.float32, device=dev) if out_val is None else out_val
+        ops.cross_topk(factors.users, None, factors.items, None, query, k, out_idx, out_val)
+        return out_idx, out_val
+
+    def recommend_ials(self, user_ids, k, exclude=None, **fit):
+        """The iALS baseline's lists: per user the k items with the largest x_u . y_i under fit_ials(**fit) -- Neighbours(ids CPU
+        int32 [B x k] (-1 padded), scores CPU fp32 [B x k] (-inf padded)), by (score descending, id ascending). exclude: dict user
+        -> item ids left out, as recommend_knn takes it; default: the data set's train dict. A user without history has the zero
+        vector: every item scores 0 and the lowest ids are listed. k outside [1, 256] or a fit parameter out of range: ValueError;
+        an id outside its side: IndexError -- both before anything touches the device. An empty user_ids returns [0 x k] without
+        a launch or a fit."""
+        k = ops._cooccur_k("recommend_ials", k)
+        params = self._ials_params(**fit)
+        users = self._id_lists([user_ids], "user", self.num_users)[1]
+        tptr, tflat = self._excluded(self.dataset.get_user_train_dict() if exclude is None else exclude, users, "item")
+        if not users.size:
+            return Neighbours(torch.empty(0, k, dtype=torch.int32), torch.empty(0, k, dtype=torch.float32))
+        self._require_gpu()
+        idx, val = self.ials_recommend_device(users, self.fit_ials(*params), k, (tptr, tflat))
+        return Neighbours(idx.cpu(), val.cpu())
 
     @torch.no_grad()
     def clusters_device(self, side, n_clusters, space="fused", iters=25, seed=2022, init=None):

@@ -1134,6 +1134,8 @@ def __getattr__(name):
         return int(_lib.load().elimrec_vote_slots())
     if name == "VOTE_GROUPS":            # workgroups (and workspace rows) of neighbour_vote_topk's dense form at most
         return int(_lib.load().elimrec_vote_groups())
+    if name == "ALS_CHUNK":              # neighbour rows one workgroup of als_solve stages in LDS at a time
+        return int(_lib.load().elimrec_als_chunk())
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 
@@ -1454,6 +1456,71 @@ def cosine_topk(table, sqnorm, query_rows, K, out_idx, out_val=None, exclude_sel
         query = NeighbourQuery(query_rows, n, table.device, excl_ptr, excl_rows)
     return _topk_call("cosine_topk", n, query, K, out_idx, out_val, workspace, table.device, None, lambda: (
         tp, ld, n, d, sp, ld_sq, _dev(query.rows, "query_rows", torch.int32), query.n_queries, 1 if exclude_self else 0,
+        _dev(query.excl_ptr, "excl_ptr", torch.int64), _dev(query.excl_rows, "excl_rows", torch.int32)))
+
+
+class CrossQuery(_ListQuery):
+    """Query rows of an n_query_rows-row query table and, optionally, per query a list of CANDIDATE rows (of the n_rows-row
+    candidate table) to leave out as CSR (excl_ptr [Q + 1], excl_rows), CHECKED ON THE HOST -- every query id in
+    [0, n_query_rows), every exclusion id in [0, n_rows), ptr[0] = 0, ascending, ptr[Q] = len(excl_rows) -- and then resident on
+    `device`: cross_topk takes it as is, call after call. Exclusion lists may repeat ids, in any order, and may be empty."""
+
+    def __init__(self, rows, n_query_rows, n_rows, device, excl_ptr=None, excl_rows=None):
+        _ListQuery.__init__(self, rows, n_query_rows, device, excl_ptr, excl_rows, n_rows, ("rows", "excl_rows"),
+                            ("query rows span [%d, %d], the query table has %d rows", "excluded rows span [%d, %d], the table has %d rows"))
+        self.n_query_rows, self.n_rows = int(n_query_rows), int(n_rows)
+        self.rows, self.excl_rows = self.ids, self.excl_ids
+
+
+def _cross_side(t, sq, name, sq_name):
+    """One side of cross_topk before the device is required: (rows, d) of a 2-D tensor with unit column stride and its squared
+    norms' entry count (None: ones)."""
+    if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.stride(1) != 1:
+        raise ValueError("elimrec_amd.ops.cross_topk: %s must be a 2-D tensor with unit column stride" % name)
+    if sq is not None and (not isinstance(sq, torch.Tensor) or sq.dim() != 1 or sq.numel() != t.shape[0] or sq.device != t.device):
+        raise ValueError("elimrec_amd.ops.cross_topk: %s must be 1-D with one entry per row of %s (%d) on its device" % (sq_name, name, t.shape[0]))
+    return int(t.shape[0]), int(t.shape[1])
+
+
+def cross_topk(query_table, query_sqnorm, table, sqnorm, query_rows, K, out_idx, out_val=None, excl_ptr=None, excl_rows=None,
+               workspace=None):
+    """elimrec_cross_topk: cosine_topk with a query table of its own -- per query row (a row of `query_table` [nq x d]) the K rows
+    of `table` [n x d] with the largest score, by (score descending, row id ascending); out_idx int32 / out_val float32 (optional)
+    [Q x K], -1 / -inf where fewer than K candidates exist. Both tables float32 with unit column stride on one device, the same d,
+    d % 4 == 0, 4 <= d <= 256. score = (dot * inv(query_sqnorm[q])) * inv(sqnorm[c]) as cosine_topk forms it; query_sqnorm / sqnorm =
+    None means a vector of ones on that side, and with both None the score is the plain fp32 dot product (1 / max(sqrt(1), 1e-12)
+    is exactly 1): top-K_i x_u . y_i of a factor model. Left out: the query's list of the CSR excl_ptr [Q + 1] / excl_rows, ids of
+    CANDIDATE rows; there is no exclude_self. query_rows and the CSR: host arrays or tensors, checked on the host at every call, or
+    query_rows = a CrossQuery (excl_ptr = excl_rows = None), checked once. The same kernel, chunks (KNN_CHUNK), workspace
+    (cosine_topk_workspace bytes), selection and merge as cosine_topk. Every argument error is raised before the device is
+    required. 1 <= K <= 256."""
+    who = "cross_topk"
+    nq, dq = _cross_side(query_table, query_sqnorm, "query_table", "query_sqnorm")
+    n, d = _cross_side(table, sqnorm, "table", "sqnorm")
+    if dq != d or query_table.device != table.device:
+        raise ValueError("elimrec_amd.ops.cross_topk: the two tables share d and the device, got d = %d on %s and %d on %s"
+                         % (dq, query_table.device, d, table.device))
+    K = int(K)
+    _topk_dims(who, K, KNN_MAX_K, d, "the table")
+    if isinstance(query_rows, CrossQuery):
+        query = query_rows
+        if excl_ptr is not None or excl_rows is not None:
+            raise ValueError("elimrec_amd.ops.cross_topk: a CrossQuery carries its own exclusions (pass excl_ptr=excl_rows=None)")
+        if query.n_query_rows > nq or query.n_rows > n or query.rows.device != table.device:
+            raise IndexError("elimrec_amd.ops.cross_topk: the CrossQuery was checked for %d query rows and %d rows on %s, the tables have "
+                             "%d and %d on %s" % (query.n_query_rows, query.n_rows, query.rows.device, nq, n, table.device))
+    else:
+        query = CrossQuery(query_rows, nq, n, table.device, excl_ptr, excl_rows)
+    qp, ldq = _rowmajor(query_table, "query_table")
+    tp, ld = _rowmajor(table, "table")
+    if query_sqnorm is None:
+        query_sqnorm = torch.ones(max(1, nq), dtype=torch.float32, device=table.device)
+    if sqnorm is None:
+        sqnorm = torch.ones(max(1, n), dtype=torch.float32, device=table.device)
+    sqp, sp = _dev(query_sqnorm, "query_sqnorm"), _dev(sqnorm, "sqnorm")
+    ld_sqq, ld_sq = max(1, int(query_sqnorm.stride(0))), max(1, int(sqnorm.stride(0)))
+    return _topk_call(who, n, query, K, out_idx, out_val, workspace, table.device, None, lambda: (
+        qp, ldq, nq, sqp, ld_sqq, tp, ld, n, d, sp, ld_sq, _dev(query.rows, "query_rows", torch.int32), query.n_queries,
         _dev(query.excl_ptr, "excl_ptr", torch.int64), _dev(query.excl_rows, "excl_rows", torch.int32)))
 
 
@@ -2739,3 +2806,131 @@ def neighbour_vote_topk(lists, hist, users, K, out_idx, out_val=None, out_cnt=No
                                                        _dev(up, "users", torch.int64), B, K, 1 if exclude_history else 0, 1 if lds else 0,
                                                        n_dense, ip, vp, cp, wp, workspace.numel(), _stream()), who)
     return out_idx
+
+
+ALS_FACTORS = (16, 32, 48, 64)           # the factor dimensions als_solve takes (csrc/als.hip), known without the library
+
+
+class AlsIndex(object):
+    """The CSR of the side an ALS half-sweep solves (ptr [n + 1] / nbr: a row's neighbours on the fixed side of n_fixed rows),
+    CHECKED ON THE HOST and then resident on `device`: ptr[0] = 0, ascending, ptr[n] = len(nbr) and EVERY LIST STRICTLY ASCENDING
+    -- no repeated edge, so als_solve's formula is the whole definition -- (ValueError); integer ids in [0, n_fixed) (IndexError).
+    als_solve takes it as is, call after call, so a fit checks each side once. Kept on the host: deg (int64 [n]) and by_degree
+    (int32 [n]: all rows, degree descending, equal degrees by ascending id -- the order als_solve launches them in)."""
+
+    def __init__(self, ptr, nbr, n, n_fixed, device):
+        who = "AlsIndex"
+        n, n_fixed = int(n), int(n_fixed)
+        if not (0 <= n < 2 ** 31 - 1 and 0 <= n_fixed < 2 ** 31 - 1):
+            raise ValueError("elimrec_amd.ops.%s: both sides need 0 <= rows < 2^31 - 1, got %d and %d" % (who, n, n_fixed))
+        p, ids = _checked_csr(ptr, nbr, n, n_fixed, who, ("ptr", "nbr", "n", "nbr spans [%d, %d], the fixed side has %d rows"))
+        if ids.size > 1:
+            bad = np.diff(ids.astype(np.int64)) <= 0
+            starts = p[1:-1]
+            bad[starts[(starts > 0) & (starts < ids.size)] - 1] = False      # the step from one list into the next
+            if bad.any():
+                at = int(np.flatnonzero(bad)[0])
+                raise ValueError("elimrec_amd.ops.%s: every list is strictly ascending (no repeated edge): row %d lists %d, then %d"
+                                 % (who, int(np.searchsorted(p, at, side="right") - 1), int(ids[at]), int(ids[at + 1])))
+        self.n, self.n_fixed, self.n_edges = n, n_fixed, int(ids.size)
+        self.deg = np.diff(p)
+        self.by_degree = np.argsort(-self.deg, kind="stable").astype(np.int32)
+        self.device = torch.device(device)
+        self.ptr = torch.from_numpy(p).to(device)
+        self.nbr = _resident_ids(ids, device)
+
+
+def _als_params(who, d, conf):
+    if d not in ALS_FACTORS:
+        raise ValueError("elimrec_amd.ops.%s: the factors need d %% 16 == 0 and 16 <= d <= 64 columns, got %d" % (who, d))
+    if isinstance(conf, bool) or not isinstance(conf, (int, float, np.integer, np.floating)) or not (math.isfinite(conf) and conf >= 0):
+        raise ValueError("elimrec_amd.ops.%s: conf is finite and >= 0, got %r" % (who, conf))
+    return float(conf)
+
+
+def _ials_params(who, factors=64, iters=15, conf=1.0, reg=0.01, reg_scale=0.0, seed=2022):
+    """The parameters of an iALS fit (EliMRec.fit_ials, BaselineReport, the --baseline_* switches), checked before anything touches
+    the device (ValueError): -> (factors, iters, conf, reg, reg_scale, seed)."""
+    def number(x):
+        return not isinstance(x, bool) and isinstance(x, (int, float, np.integer, np.floating)) and math.isfinite(x)
+    if isinstance(factors, bool) or not isinstance(factors, (int, np.integer)) or factors not in ALS_FACTORS:
+        raise ValueError("%s: factors must be one of %s, got %r" % (who, ALS_FACTORS, factors))
+    if isinstance(iters, bool) or not isinstance(iters, (int, np.integer)) or not 1 <= iters <= 100:
+        raise ValueError("%s: iters must be an integer in [1, 100], got %r" % (who, iters))
+    if not (number(conf) and conf >= 0):
+        raise ValueError("%s: conf must be finite and >= 0, got %r" % (who, conf))
+    if not (number(reg) and reg > 0):
+        raise ValueError("%s: reg must be finite and > 0, got %r" % (who, reg))
+    if not (number(reg_scale) and 0 <= reg_scale <= 1):
+        raise ValueError("%s: reg_scale must lie in [0, 1], got %r" % (who, reg_scale))
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or seed < 0:
+        raise ValueError("%s: seed must be an integer >= 0, got %r" % (who, seed))
+    return int(factors), int(iters), float(conf), float(reg), float(reg_scale), int(seed)
+
+
+def _als_reg(who, reg, n, device):
+    """The per-row ridge as a float64 device tensor [n]: a number (every row's), a host array or a tensor; finite and >= 0
+    (ValueError) -- a host value is checked before anything touches the device, a device tensor by a read back."""
+    if isinstance(reg, torch.Tensor) and reg.is_cuda:
+        if reg.dtype != torch.float64 or reg.dim() != 1 or reg.numel() != n or not reg.is_contiguous():
+            raise ValueError("elimrec_amd.ops.%s: reg must be a contiguous float64 tensor with one entry per row (%d)" % (who, n))
+        if n and not bool((torch.isfinite(reg) & (reg >= 0)).all().item()):
+            raise ValueError("elimrec_amd.ops.%s: every reg is finite and >= 0" % who)
+        return None, reg
+    host = np.asarray(_host(reg), dtype=np.float64)
+    host = np.full(n, float(host), dtype=np.float64) if host.ndim == 0 else np.ascontiguousarray(host.reshape(-1))
+    if host.size != n:
+        raise ValueError("elimrec_amd.ops.%s: reg needs one entry per row (%d), got %d" % (who, n, host.size))
+    if n and not (np.isfinite(host) & (host >= 0)).all():
+        raise ValueError("elimrec_amd.ops.%s: every reg is finite and >= 0" % who)
+    return host, None
+
+
+def als_solve(index, F, A0, reg, conf, out, rows=None):
+    """elimrec_als_solve: one half-sweep of implicit-feedback ALS (Hu, Koren, Volinsky, ICDM 2008; csrc/als.hip). For every listed
+    row r of the side `index` (an ops.AlsIndex) describes, N(r) its neighbours and f_j row j of F:
+        A_r = A0 + reg[r] I + conf sum_{j in N(r)} f_j f_j^T,   b_r = (1 + conf) sum_{j in N(r)} f_j,   out[r] = A_r^-1 b_r
+    F float32 [n_fixed x d] with unit column stride (a column block of a wider matrix is fine), d in ALS_FACTORS = {16, 32, 48, 64};
+    A0 float64 [d x d] contiguous: F^T F, from row_gram(F, ones, arange(n_fixed))[0] -- with unit norms the exact-product float64
+    Gram in a fixed order; only its upper triangle is read. reg: the per-row ridge, a number, a host array or a float64 device
+    tensor [n], finite and >= 0; conf: a number, finite and >= 0. out float32 [n x d] with unit column stride: row r is written for
+    every listed r, other rows are left alone. rows: host array or tensor of ids (IndexError), default every row; they are
+    launched by degree descending, and a row's bits do not depend on that: everything is float64 with exact products, summed in
+    the CSR order of the row's list (ALS_CHUNK rows per LDS stage), rounded to float32 once. A row with an empty list is zeros.
+    A row whose A_r is not positive definite (a Cholesky pivot <= 0 or not finite) is written as zeros and the call raises
+    ArithmeticError naming the lowest such row, after every other row has been solved. The status word is read back (a
+    synchronisation). Every argument error is raised before the device is required. -> out."""
+    who = "als_solve"
+    if not isinstance(index, AlsIndex):
+        raise TypeError("elimrec_amd.ops.%s: index must be an ops.AlsIndex, got %s" % (who, type(index).__name__))
+    if not isinstance(F, torch.Tensor) or F.dim() != 2 or F.stride(1) != 1 or F.shape[0] != index.n_fixed:
+        raise ValueError("elimrec_amd.ops.%s: F must be [%d x d] with unit column stride" % (who, index.n_fixed))
+    d = int(F.shape[1])
+    conf = _als_params(who, d, conf)
+    reg_host, reg_dev = _als_reg(who, reg, index.n, index.device)
+    if rows is None:
+        q = index.by_degree
+    else:
+        q = _checked_ids(rows, index.n, who, "rows", "rows span [%d, %d], the side has %d rows")
+        q = q[np.argsort(-index.deg[q], kind="stable")]
+    dev = index.device
+    fp, ld = _rowmajor(F, "F")
+    ap = _dev(A0, "A0", torch.float64)
+    if tuple(A0.shape) != (d, d) or not A0.is_contiguous() or A0.device != dev or F.device != dev:
+        raise ValueError("elimrec_amd.ops.%s: A0 must be a contiguous float64 [%d x %d] tensor, with F on the index's device" % (who, d, d))
+    op, ld_out = _rowmajor(out, "out")
+    if tuple(out.shape) != (index.n, d) or out.device != dev:
+        raise ValueError("elimrec_amd.ops.%s: out must be [%d x %d] on the index's device" % (who, index.n, d))
+    if q.size == 0:
+        return out
+    if reg_dev is None:
+        reg_dev = torch.from_numpy(reg_host).to(dev)
+    status = torch.tensor([0, 2 ** 31 - 1], dtype=torch.int32, device=dev)
+    _lib.check(_lib.load().elimrec_als_solve(fp, ld, index.n_fixed, d, ap, _dev(index.ptr, "ptr", torch.int64),
+                                             _dev(index.nbr, "nbr", torch.int32), index.n, _dev(_resident_ids(q, dev), "rows", torch.int32),
+                                             int(q.size), reg_dev.data_ptr(), conf, op, ld_out, status.data_ptr(), _stream()), who)
+    bad, first = (int(x) for x in status.cpu())
+    if bad:
+        raise ArithmeticError("elimrec_amd.ops.%s: A_r is not positive definite for %d row(s), the first is row %d (written as zeros)"
+                              % (who, bad, first))
+    return out

@@ -1641,7 +1641,11 @@ class BaselineReport(_Report):
     took -- the single-modal shortcut as a recommender of its own), "rp3" = RP3beta over the training graph under `alpha` and
     `beta` (EliMRec.rp3_items: the graph random walk with a popularity penalty on the target; the defaults are the commonly used
     ones, not tuned here; its list values are scaled by one power of two before they vote, and rp3_info = (scale exponent e,
-    zero_votes) says what the vote's fixed point still loses), each item's `neighbours` nearest items voting.
+    zero_votes) says what the vote's fixed point still loses), each item's `neighbours` nearest items voting;
+    "ials" = the implicit-feedback ALS factor model of EliMRec.fit_ials under factors / iters / conf / reg / reg_scale (no
+    neighbour vote: its lists are the top-K of x_u . y_i, EliMRec.ials_recommend_device; `neighbours` and `measure` do not apply to it;
+    the defaults are not tuned here; under the table one line gives the settings and the loss after the first and the last
+    half-sweep).
     metric_rows() is ops.rank_metrics over those lists with the truth CSR, metric ids and shown-column layout of
     SignificanceReport.metric_rows, so the two row blocks pair user by user (SignificanceReport.shift); a -1 filler is a miss (the
     metric kernel compares ids against a truth list of ids >= 0). evaluate() gives one row per source -- with group_view one block of
@@ -1655,17 +1659,18 @@ class BaselineReport(_Report):
     name, needs = "baseline", "knn_recommend_device"
 
     def __init__(self, dataset, user_train_dict, user_test_dict, top_k, metric=None, sources=("co",), neighbours=50, measure="cosine",
-                 group_view=None, list_k=None, alpha=1.0, beta=0.6):
+                 group_view=None, list_k=None, alpha=1.0, beta=0.6, factors=64, iters=15, conf=1.0, reg=0.01, reg_scale=0.0):
         from .evaluator import UniEvaluator, re_metric_dict
         if not isinstance(user_train_dict, dict) or not isinstance(user_test_dict, dict):
             raise TypeError("user_train_dict and user_test_dict must be dicts")
         if isinstance(sources, str) or not len(sources) or any(not isinstance(x, str) or not x for x in sources) or len(set(sources)) != len(sources):
-            raise ValueError("sources is a sequence of distinct names: 'co', 'rp3', 'fused' or a head letter, got %r" % (sources,))
+            raise ValueError("sources is a sequence of distinct names: 'co', 'rp3', 'ials', 'fused' or a head letter, got %r" % (sources,))
         if isinstance(neighbours, bool) or not isinstance(neighbours, (int, np.integer)) or not 1 <= neighbours <= ops.VOTE_MAX_K:
             raise ValueError("neighbours must be an integer in [1, %d], got %r" % (ops.VOTE_MAX_K, neighbours))
         ops._cooccur_measure("BaselineReport", measure)
         self.alpha, self.beta = ops._rp3_params("BaselineReport", alpha, beta)
         self.rp3_info = None
+        self.ials_params, self.ials_objective = ops._ials_params("BaselineReport", factors, iters, conf, reg, reg_scale), None
         self.evaluator = ev = UniEvaluator(dataset, user_train_dict, user_test_dict, metric=metric, top_k=top_k)
         list_k = ev.max_top if list_k is None else list_k
         if isinstance(list_k, bool) or not isinstance(list_k, (int, np.integer)) or not ev.max_top <= list_k <= ops.VOTE_MAX_K:
@@ -1703,6 +1708,8 @@ class BaselineReport(_Report):
             raise ValueError("source is one of this report's %s, got %r" % ("/".join(self.sources), source))
         device = self._preflight(model)
         res = self._resident(device)
+        if source == "ials":
+            return self._ials_lists(model, device)
         lists = model.neighbour_lists(source, self.neighbours, self.measure, self.alpha, self.beta)
         if source == "rp3":
             self.rp3_info = (lists.scale_exp, lists.zero_votes)
@@ -1717,6 +1724,26 @@ class BaselineReport(_Report):
             b = min(n, a + self.block_users)
             model.knn_recommend_device(np.arange(a, b, dtype=np.int64), lists, res["hist"], K, None, idx[a:b], val[:b - a], cnt[:b - a])
         self._lists[(source, str(device))] = (lists, idx)
+        return idx
+
+    def _ials_lists(self, model, device):
+        """knn_lists of the source "ials": the top-K of x_u . y_i under EliMRec.fit_ials(*self.ials_params) through
+        EliMRec.ials_recommend_device, in blocks of block_users with the train items masked. Kept for as long as the model keeps
+        the fit; the neighbour-vote settings (neighbours, measure) do not apply."""
+        fit = model.fit_ials(*self.ials_params)
+        self.ials_objective = (float(fit.objective[0]), float(fit.objective[-1]))
+        hit = self._lists.get(("ials", str(device)))
+        if hit is not None and hit[0] is fit:
+            return hit[1]
+        n, K = len(self.users), self.k
+        idx = torch.empty(n, K, dtype=torch.int32, device=device)
+        val = torch.empty(min(n, self.block_users), K, dtype=torch.float32, device=device)
+        for a in range(0, n, self.block_users):
+            b = min(n, a + self.block_users)
+            ptr, flat, _ = ops.ragged([self.user_pos_train.get(u, []) for u in self.users[a:b]], check=(
+                self.num_items, "item ids must lie in [0, %d)" % self.num_items), cast=int)
+            model.ials_recommend_device(np.asarray(self.users[a:b], dtype=np.int64), fit, K, (ptr, flat), idx[a:b], val[:b - a])
+        self._lists[("ials", str(device))] = (fit, idx)
         return idx
 
     def metric_rows(self, model, source):
@@ -1766,6 +1793,8 @@ class BaselineReport(_Report):
         buf = format_table(final.columns, final.labels, final.table)
         if "rp3" in self.sources:
             buf += "\nrp3: alpha=%g beta=%g scale=2^%d zero_votes=%.6f" % ((self.alpha, self.beta) + self.rp3_info)
+        if "ials" in self.sources:
+            buf += "\nials: factors=%d iters=%d conf=%g reg=%g reg_scale=%g objective=%.8g -> %.8g" % (self.ials_params[:5] + self.ials_objective)
         return final, buf
 
 

@@ -33,4 +33,5 @@ OPS = ("propagate", "linear_fwd", "linear_bwd_w", "bpr_head_fwd", "adam_step_", 
        "score_candidates", "sample_negatives", "score_effects", "rank_targets", "cosine_topk", "audience_topk", "list_overlap",
        "list_pair_cosine", "list_exposure", "mmr_rerank", "pick_hard_negatives", "history_support", "bootstrap_means",
        "bootstrap_diff_means", "calibrate_rerank", "list_calibration", "kmeans_assign", "kmeans_update", "uniformity_sum",
-       "row_gram", "cooccur_topk", "neighbour_vote_topk", "rank_values", "segment_row_sum")
+       "row_gram", "cooccur_topk", "neighbour_vote_topk", "rank_values", "segment_row_sum", "cross_topk",
+       "als_solve")

@@ -664,6 +664,16 @@ int elimrec_cosine_topk(const float *d_T, int64_t ld, int64_t n_rows, int d, con
 size_t elimrec_cosine_topk_workspace(int64_t Q, int64_t n_rows, int K);
 int elimrec_cosine_topk_chunk(void);
 int elimrec_cosine_topk_tile(void);
+/* elimrec_cosine_topk with a query table of its own: query q is row d_query_rows[q] of d_Tq (an [nq_rows x d] slice with row
+ * stride ldq, squared norms d_sqq[r * ld_sqq]), the candidates are the n_rows rows of d_T as above. Same kernel, chunks,
+ * workspace (elimrec_cross_topk_workspace = elimrec_cosine_topk_workspace), selection and merge; the exclusion ids are candidate
+ * rows and there is no exclude_self. With squared norms of exactly 1.0 on both sides the score is the plain fp32 dot product
+ * (1 / max(sqrt(1), 1e-12) is exactly 1): top-K_i x_u . y_i of a factor model. A query id outside [0, nq_rows) gives fillers. */
+int elimrec_cross_topk(const float *d_Tq, int64_t ldq, int64_t nq_rows, const float *d_sqq, int64_t ld_sqq, const float *d_T,
+                       int64_t ld, int64_t n_rows, int d, const float *d_sqnorm, int64_t ld_sq, const int32_t *d_query_rows,
+                       int64_t Q, const int64_t *d_excl_ptr, const int32_t *d_excl_rows, int K, int32_t *d_idx, float *d_val,
+                       void *d_workspace, size_t workspace_bytes, void *stream);
+size_t elimrec_cross_topk_workspace(int64_t Q, int64_t n_rows, int K);
 /* d_count[r] = the number of ids >= 0 of d_a[r, :] that also occur in d_b[r, :]; d_a / d_b int32 [n_rows x K] contiguous, lists of
  * distinct ids and -1 fillers, 1 <= K <= 1024. One wave per row, the integers are exact. */
 int elimrec_list_overlap(const int32_t *d_a, const int32_t *d_b, int64_t n_rows, int K, int32_t *d_count, void *stream);
@@ -925,6 +935,24 @@ int elimrec_walk_max_k(void);
 int elimrec_walk_groups(void);
 int elimrec_walk_frac_bits(void);
 int elimrec_walk_rows_in_lds(int64_t W);
+
+/* One half-sweep of implicit-feedback ALS (csrc/als.hip; Hu, Koren, Volinsky, ICDM 2008). No counterpart in the reference.
+ * For every listed row r = d_rows[q] of the side being solved, N(r) = d_nbr[d_ptr[r] .. d_ptr[r + 1]) its neighbours on the
+ * fixed side and f_j row j of d_F (an [n_fixed x d] slice of a row-major float32 matrix, row stride ld):
+ *     A_r = A0 + reg[r] I + conf sum_{j in N(r)} f_j f_j^T,   b_r = (1 + conf) sum_{j in N(r)} f_j,   out[r] = A_r^-1 b_r
+ * d_A0 float64 [d x d] contiguous (the caller's F^T F; only the upper triangle is read), d_reg float64 [n], conf finite and
+ * >= 0, d % 16 == 0 and 16 <= d <= 64. d_ptr int64 [n + 1] / d_nbr int32: the CSR of the side being solved -- THE CALLER
+ * guarantees ptr ascending from 0, ids in [0, n_fixed) and every list strictly ascending (no repeated edge; the Python wrappers
+ * check all of it on the host). One workgroup per listed row; everything in float64 (the widened products are exact), the sums
+ * in the CSR order of the row's list, rounded to float32 once at the store: a row's bits depend on A0, reg[r], conf and the
+ * listed rows of F in list order alone. Cholesky in LDS; a pivot <= 0 or not finite adds 1 to d_status[0], lowers d_status[1]
+ * to min(d_status[1], r) and writes the row as zeros -- THE CALLER sets d_status int32 [2] to {0, INT32_MAX} before the call and
+ * reads it afterwards. A row with an empty list is zeros. Rows of d_out (row stride ld_out) that are not listed are left alone.
+ * elimrec_als_chunk(): neighbour rows per LDS stage. One launch on `stream`, no host synchronisation. */
+int elimrec_als_solve(const float *d_F, int64_t ld, int64_t n_fixed, int d, const double *d_A0, const int64_t *d_ptr,
+                      const int32_t *d_nbr, int64_t n, const int32_t *d_rows, int64_t Q, const double *d_reg, double conf,
+                      float *d_out, int64_t ld_out, int32_t *d_status, void *stream);
+int elimrec_als_chunk(void);
 
 /* Hard-negative pick (csrc/hardneg.hip): per triplet the best of M candidate items under the current tables. No counterpart in
  * the reference. d_U / d_T point at row 0, column 0 of an [n_users x blocks * d] / [n_items x blocks * d] slice of a row-major
