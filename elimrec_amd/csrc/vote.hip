@@ -21,8 +21,10 @@
 //              pass 2 walks the votes again and claims each touched entry through its COUNT (a sum may legitimately be 0) with an
 //              exchange to 0, then takes the sum the same way; pass 3 claims the left-out ids no vote met. The row is clean again.
 // The 16 lanes of a quarter wave share one history position and stride its list, so 16 positions are in flight per workgroup.
-// Selection is cooccur.hip's (co_select.h); the dense form compares the full key against the K-th kept key and, when the list could
-// overflow, sorts it and cuts it to the K best.
+// The two forms' skeleton -- the table's insert, the dense form's row scheduler and its list with the cut rule, the outputs -- and the
+// selection are co_select.h's, shared with cooccur.hip and walk.hip; the dense form compares the full key against the K-th kept key
+// and, when the list could overflow, sorts it and cuts it to the K best. The traversal (history x list slots), the marks of the
+// left-out ids and the (sum, count) pair are this file's own.
 #include <cmath>
 #include "common.h"
 #include "co_select.h"
@@ -32,7 +34,6 @@ namespace elimrec {
 constexpr int VOTE_SLOTS = 2048, VOTE_MAX_K = 256, VOTE_CAP = VOTE_SLOTS / 2, VOTE_GROUPS = 512, VOTE_FRAC_BITS = 24;
 constexpr int VOTE_STEP = 2;                                 // votes a lane claims between two capacity checks of the dense form
 constexpr int VOTE_MARK = 1 << 30;                           // the count's bit of a left-out id; a row has fewer votes than that
-static_assert(VOTE_CAP >= 2 * CO_THREADS * VOTE_STEP && VOTE_CAP - CO_THREADS * VOTE_STEP >= VOTE_MAX_K, "the dense form's list");
 static_assert(VOTE_SLOTS * 16 + VOTE_CAP * 12 + 64 <= 64 * 1024, "the LDS form's table and list stay within 64 KiB");
 
 struct VoteArgs {
@@ -40,10 +41,13 @@ struct VoteArgs {
     const int64_t *hist_ptr; const int32_t *hist_items; int64_t n_hist;
     const int64_t *excl_ptr; const int32_t *excl_items; int64_t n_excl;       // excl_ptr may be null
     const int64_t *users; int64_t B;
+    // the four integers lie together and arrive in one scalar load; with K apart in a CoOut, vote_lds_kernel measured 3 to 7 % slower
     int K, exclude_history, use_lds, groups;
     int32_t *idx; float *val; int32_t *cnt;                  // [B x K]; val and cnt may be null
     unsigned long long *sum; int32_t *ctr;                   // [groups][n] each: the dense form's rows
 };
+
+__device__ __forceinline__ CoOut vote_out(const VoteArgs &a) { return {a.K, a.idx, a.val, a.cnt}; }
 
 __host__ __device__ inline bool vote_in_lds(int64_t V) { return V >= 0 && V <= VOTE_CAP; }
 
@@ -63,25 +67,6 @@ __device__ __forceinline__ VoteRow vote_row(const VoteArgs &a, int64_t b) {
 __device__ __forceinline__ long long vote_fixed(float v) { return (long long)rint((double)v * (double)(1 << VOTE_FRAC_BITS)); }
 __device__ __forceinline__ float vote_score(long long S) { return (float)((double)S * (1.0 / (double)(1 << VOTE_FRAC_BITS))); }
 
-__device__ __forceinline__ void vote_fillers(const VoteArgs &a, int64_t b, int from, int tid) {
-    for (int k = from + tid; k < a.K; k += CO_THREADS) {
-        a.idx[b * a.K + k] = -1;
-        if (a.val) a.val[b * a.K + k] = -__builtin_huge_valf();
-        if (a.cnt) a.cnt[b * a.K + k] = 0;
-    }
-}
-
-// the sorted list's K best to row b of the outputs, fillers behind them
-__device__ __forceinline__ void vote_emit(const VoteArgs &a, int64_t b, const uint64_t *key, const int *c, int n, int tid) {
-    const int kept = n < a.K ? n : a.K;
-    for (int k = tid; k < kept; k += CO_THREADS) {
-        a.idx[b * a.K + k] = co_key_id(key[k]);
-        if (a.val) a.val[b * a.K + k] = co_key_score(key[k]);
-        if (a.cnt) a.cnt[b * a.K + k] = c[k];
-    }
-    vote_fillers(a, b, kept, tid);
-}
-
 // the e-th left-out id of a row: the history segment first (with exclude_history), then the second CSR's segment
 __device__ __forceinline__ int64_t vote_left_out_count(const VoteArgs &a, const VoteRow &r) {
     return (a.exclude_history ? r.h1 - r.h0 : 0) + (r.x1 - r.x0);
@@ -89,16 +74,6 @@ __device__ __forceinline__ int64_t vote_left_out_count(const VoteArgs &a, const 
 __device__ __forceinline__ int vote_left_out(const VoteArgs &a, const VoteRow &r, int64_t e) {
     const int64_t nh = a.exclude_history ? r.h1 - r.h0 : 0;
     return e < nh ? a.hist_items[r.h0 + e] : a.excl_items[r.x0 + (e - nh)];
-}
-
-// the slot of id j in the table, entered when new: at most V <= SLOTS / 2 distinct keys, so a free slot always exists
-__device__ __forceinline__ int vote_slot(int *hk, int j) {
-    int s = j & (VOTE_SLOTS - 1);
-    for (;;) {
-        const int prev = atomicCAS(&hk[s], -1, j);
-        if (prev == -1 || prev == j) return s;
-        s = (s + 1) & (VOTE_SLOTS - 1);
-    }
 }
 
 __global__ __launch_bounds__(CO_THREADS) void vote_lds_kernel(VoteArgs a) {
@@ -110,12 +85,13 @@ __global__ __launch_bounds__(CO_THREADS) void vote_lds_kernel(VoteArgs a) {
     __shared__ int s_n;
     const int tid = threadIdx.x;
     const int64_t b = blockIdx.x;
+    const CoOut out = vote_out(a);
     const VoteRow r = vote_row(a, b);
     if (!(a.use_lds && vote_in_lds(r.V))) {                  // (uniform) the dense form's row; without a row there it gets fillers
-        if (a.groups == 0) vote_fillers(a, b, 0, tid);
+        if (a.groups == 0) co_fillers(out, b, 0, tid);
         return;
     }
-    if (!r.known || r.h1 == r.h0) { vote_fillers(a, b, 0, tid); return; }
+    if (!r.known || r.h1 == r.h0) { co_fillers(out, b, 0, tid); return; }
     for (int s = tid; s < VOTE_SLOTS; s += CO_THREADS) { s_hk[s] = -1; s_hs[s] = 0; s_hc[s] = 0; }
     if (tid == 0) s_n = 0;
     __syncthreads();
@@ -123,7 +99,7 @@ __global__ __launch_bounds__(CO_THREADS) void vote_lds_kernel(VoteArgs a) {
     for (int64_t e = tid; e < n_out; e += CO_THREADS) {
         const int j = vote_left_out(a, r, e);
         if (j < 0 || j >= a.n) continue;
-        atomicOr(&s_hc[vote_slot(s_hk, j)], VOTE_MARK);
+        atomicOr(&s_hc[co_slot<VOTE_SLOTS>(s_hk, j)], VOTE_MARK);
     }
     __syncthreads();
     const int g = tid >> 4, l = tid & 15;
@@ -136,7 +112,7 @@ __global__ __launch_bounds__(CO_THREADS) void vote_lds_kernel(VoteArgs a) {
             const int i = li[s];
             const float v = lv[s];
             if (i < 0 || i >= a.n || !isfinite(v)) continue;
-            const int at = vote_slot(s_hk, i);
+            const int at = co_slot<VOTE_SLOTS>(s_hk, i);
             atomicAdd(&s_hs[at], (unsigned long long)vote_fixed(v));
             atomicAdd(&s_hc[at], 1);
         }
@@ -153,7 +129,7 @@ __global__ __launch_bounds__(CO_THREADS) void vote_lds_kernel(VoteArgs a) {
     __syncthreads();
     const int n = s_n;
     co_sort(s_key, s_c, n, tid);
-    vote_emit(a, b, s_key, s_c, n, tid);
+    co_emit(out, b, s_key, s_c, n, tid);
 }
 
 // claim entry i of the row: its count (and with it the sum) is this lane's when c != 0, and both are zero afterwards
@@ -164,25 +140,16 @@ __device__ __forceinline__ int vote_claim(int32_t *ctr, unsigned long long *sum,
 }
 
 __global__ __launch_bounds__(CO_THREADS) void vote_dense_kernel(VoteArgs a) {
-    __shared__ uint64_t s_key[VOTE_CAP];
-    __shared__ int s_c[VOTE_CAP];
-    __shared__ uint64_t s_thr;                               // the K-th kept key once K are kept, else 0
-    __shared__ int s_n;
-    __shared__ int s_flag[CO_THREADS];
     const int tid = threadIdx.x, g = tid >> 4, l = tid & 15;
-    const int64_t G = gridDim.x, w = blockIdx.x;
-    int32_t *ctr = a.ctr + w * a.n;
-    unsigned long long *sum = a.sum + w * a.n;
-    for (int64_t base = 0; base * G < a.B; base += CO_THREADS) {         // this workgroup's rows: positions b = w (mod G)
-        const int64_t mine = (base + tid) * G + w;
-        s_flag[tid] = mine < a.B && !(a.use_lds && vote_in_lds(vote_row(a, mine).V));
-        __syncthreads();
-        for (int t = 0; t < CO_THREADS; ++t) {
-            if (!s_flag[t]) continue;                        // (uniform)
-            const int64_t b = (base + t) * G + w;
+    const CoOut out = vote_out(a);
+    int32_t *ctr = a.ctr + (int64_t)blockIdx.x * a.n;
+    unsigned long long *sum = a.sum + (int64_t)blockIdx.x * a.n;
+    co_dense_rows<VOTE_CAP, VOTE_STEP, VOTE_MAX_K>(
+        a.B, [&](int64_t b) { return !(a.use_lds && vote_in_lds(vote_row(a, b).V)); },
+        [&](int64_t b, const CoList<VOTE_CAP, VOTE_STEP, VOTE_MAX_K> &list) {
             const VoteRow r = vote_row(a, b);
-            if (!r.known || r.h1 == r.h0) { vote_fillers(a, b, 0, tid); continue; }
-            if (tid == 0) { s_n = 0; s_thr = 0; }
+            if (!r.known || r.h1 == r.h0) { co_fillers(out, b, 0, tid); return; }
+            list.reset(tid);
             // pass 0: mark the left-out ids
             const int64_t n_out = vote_left_out_count(a, r);
             for (int64_t e = tid; e < n_out; e += CO_THREADS) {
@@ -216,7 +183,7 @@ __global__ __launch_bounds__(CO_THREADS) void vote_dense_kernel(VoteArgs a) {
                 }
                 int s0 = 0;
                 for (;;) {
-                    const uint64_t thr = s_thr;
+                    const uint64_t thr = list.threshold();
 #pragma unroll
                     for (int q = 0; q < VOTE_STEP; ++q) {
                         const int s = s0 + l + 16 * q;
@@ -226,21 +193,11 @@ __global__ __launch_bounds__(CO_THREADS) void vote_dense_kernel(VoteArgs a) {
                         long long S = 0;
                         const int c = vote_claim(ctr, sum, i, &S);
                         if (c <= 0 || (c & VOTE_MARK)) continue;       // another lane claimed it, no finite vote met it, or left out
-                        const uint64_t key = co_key(vote_score(S), i);
-                        if (key > thr) {
-                            const int pos = atomicAdd(&s_n, 1);          // <= CAP - 512 before the step, at most 512 adds in it
-                            s_key[pos] = key;
-                            s_c[pos] = c;
-                        }
+                        list.offer(co_key(vote_score(S), i), c, thr);
                     }
                     s0 += 16 * VOTE_STEP;
                     const int more = __syncthreads_or(s0 < s1);
-                    if (__syncthreads_or(s_n > VOTE_CAP - CO_THREADS * VOTE_STEP)) {
-                        const int n = s_n;
-                        co_sort(s_key, s_c, n, tid);
-                        if (tid == 0 && n >= a.K) { s_n = a.K; s_thr = s_key[a.K - 1]; }
-                        __syncthreads();
-                    }
+                    list.cut(out.K, tid);
                     if (!more) break;
                 }
             }
@@ -251,19 +208,12 @@ __global__ __launch_bounds__(CO_THREADS) void vote_dense_kernel(VoteArgs a) {
                 if (j >= 0 && j < a.n) vote_claim(ctr, sum, j, &S);
             }
             __threadfence();
-            __syncthreads();
-            const int n = s_n;
-            co_sort(s_key, s_c, n, tid);
-            vote_emit(a, b, s_key, s_c, n, tid);
-            __syncthreads();
-        }
-        __syncthreads();
-    }
+            list.finish(out, b, tid);
+        });
 }
 
-static inline int64_t vote_groups(int64_t n_dense_rows) { return n_dense_rows < VOTE_GROUPS ? (n_dense_rows < 0 ? 0 : n_dense_rows) : VOTE_GROUPS; }
 static inline size_t vote_workspace(int64_t n_dense_rows, int64_t n) {
-    return align_up((size_t)vote_groups(n_dense_rows) * (size_t)n * (sizeof(int64_t) + sizeof(int32_t)), 16);
+    return co_workspace(n_dense_rows, VOTE_GROUPS, n, sizeof(int64_t) + sizeof(int32_t));
 }
 
 }  // namespace elimrec
@@ -286,38 +236,27 @@ extern "C" int elimrec_neighbour_vote_topk(const int32_t *d_nbr_idx, const float
                                            int exclude_history, int use_lds, int64_t n_dense_rows, int32_t *d_idx, float *d_val,
                                            int32_t *d_cnt, void *d_workspace, size_t workspace_bytes, void *stream) {
     const char *who = "neighbour_vote_topk";
-    ELIMREC_REQUIRE(K >= 1 && K <= VOTE_MAX_K, "%s: 1 <= K <= %d, got %d", who, VOTE_MAX_K, K);
+    if (int rc = co_check_forms(who, K, VOTE_MAX_K, use_lds)) return rc;
     ELIMREC_REQUIRE(n >= 0 && n < (int64_t)INT32_MAX && Kn >= 1, "%s: 0 <= n < 2^31 - 1 and Kn >= 1, got %lld and %d", who, (long long)n, Kn);
     ELIMREC_REQUIRE(n_hist_rows >= 0 && n_excl_rows >= 0, "%s: the CSRs need 0 or more rows, got %lld and %lld", who, (long long)n_hist_rows,
                     (long long)n_excl_rows);
     ELIMREC_REQUIRE(exclude_history == 0 || exclude_history == 1, "%s: exclude_history is 0 or 1, got %d", who, exclude_history);
-    ELIMREC_REQUIRE(use_lds == 0 || use_lds == 1, "%s: use_lds is 0 or 1, got %d", who, use_lds);
     ELIMREC_REQUIRE(B >= 0 && B < (int64_t)INT32_MAX, "%s: 0 <= B < 2^31 - 1, got %lld", who, (long long)B);
-    ELIMREC_REQUIRE(n_dense_rows >= 0 && n_dense_rows <= B, "%s: 0 <= n_dense_rows <= B, got %lld", who, (long long)n_dense_rows);
+    if (int rc = co_check_dense_rows(who, n_dense_rows, B, "B")) return rc;
     ELIMREC_REQUIRE(use_lds || n_dense_rows >= 1 || B == 0, "%s: without the LDS form every row is a dense row (n_dense_rows >= 1)", who);
     ELIMREC_REQUIRE((d_excl_ptr == nullptr) == (d_excl_items == nullptr), "%s: the second CSR comes whole or not at all", who);
     if (B == 0) return 0;
     ELIMREC_REQUIRE(d_hist_ptr && d_hist_items && d_users && d_idx && (n == 0 || (d_nbr_idx && d_nbr_val)), "%s: null pointer", who);
-    const size_t need = vote_workspace(n_dense_rows, n);
-    ELIMREC_REQUIRE(n_dense_rows == 0 || n == 0 || (d_workspace && workspace_bytes >= need && reinterpret_cast<uintptr_t>(d_workspace) % 16 == 0),
-                    "%s: the workspace needs %zu bytes, 16-byte aligned (got %zu)", who, need, workspace_bytes);
+    if (int rc = co_check_workspace(who, n_dense_rows, n, vote_workspace(n_dense_rows, n), d_workspace, workspace_bytes)) return rc;
     VoteArgs a = {};
     a.nbr_idx = d_nbr_idx; a.nbr_val = d_nbr_val; a.n = n; a.Kn = Kn;
     a.hist_ptr = d_hist_ptr; a.hist_items = d_hist_items; a.n_hist = n_hist_rows;
     a.excl_ptr = d_excl_ptr; a.excl_items = d_excl_items; a.n_excl = n_excl_rows;
     a.users = d_users; a.B = B;
-    a.K = K; a.exclude_history = exclude_history; a.use_lds = use_lds; a.groups = (int)vote_groups(n_dense_rows);
-    a.idx = d_idx; a.val = d_val; a.cnt = d_cnt;
+    a.exclude_history = exclude_history; a.use_lds = use_lds; a.groups = (int)co_groups(n_dense_rows, VOTE_GROUPS);
+    a.K = K; a.idx = d_idx; a.val = d_val; a.cnt = d_cnt;
     a.sum = static_cast<unsigned long long *>(d_workspace);                   // the sums first (8-byte entries), the counts behind them
     a.ctr = reinterpret_cast<int32_t *>(a.sum + (size_t)a.groups * (size_t)n);
-    hipStream_t s = (hipStream_t)stream;
-    if (use_lds) {
-        hipLaunchKernelGGL(vote_lds_kernel, dim3((unsigned)B), dim3(CO_THREADS), 0, s, a);
-        ELIMREC_LAUNCH_CHECK("neighbour_vote_topk (LDS form)");
-    }
-    if (a.groups > 0) {
-        hipLaunchKernelGGL(vote_dense_kernel, dim3((unsigned)a.groups), dim3(CO_THREADS), 0, s, a);
-        ELIMREC_LAUNCH_CHECK("neighbour_vote_topk (dense form)");
-    }
-    return 0;
+    return co_launch_forms(vote_lds_kernel, "neighbour_vote_topk (LDS form)", vote_dense_kernel, "neighbour_vote_topk (dense form)", B, use_lds,
+                           a.groups, a, (hipStream_t)stream);
 }

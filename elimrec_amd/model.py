@@ -1479,29 +1479,41 @@ class EliMRec(BasicModel):
         descending, id ascending), -1 / -inf / 0 where fewer than k rows share a neighbour; the row itself is never listed
         (csrc/cooccur.hip). measure: "count", "cosine" or "jaccard". rows: the query ids (host array or tensor, checked on the
         host). Nothing of the learned tables is read: this works on an untrained model, before the first step. Single-GPU."""
-        k, _ = ops._cooccur_k("co_neighbours_device", k), ops._cooccur_measure("co_neighbours_device", measure)
+        who = "co_neighbours_device"
+        k, _ = ops._form_k(who, k, ops.COOCCUR_MAX_K), ops._cooccur_measure(who, measure)
         index = self.cooccur_index(side)
-        q = ops._cooccur_rows("co_neighbours_device", index, rows)
-        n_dense = int((index.walk[q] > ops.COOCCUR_SLOTS // 2).sum())
-        need = ops.cooccur_workspace(n_dense, index.n_query)
-        kept = self.__dict__.setdefault("_co_ws", {})
-        if need and (kept.get(side) is None or kept[side].numel() < need):
-            if need > ops.COOCCUR_WORKSPACE_BUDGET:
-                raise ValueError("co_neighbours_device: the dense form's counter rows need %d bytes, the budget is %d"
-                                 % (need, ops.COOCCUR_WORKSPACE_BUDGET))
-            kept[side] = torch.zeros(need, dtype=torch.uint8, device=index.device)     # zero once: every call leaves it zero
-        ops.cooccur_topk(index, q, k, out_idx, out_val, out_cnt, measure=measure, workspace=kept.get(side) if need else None)
+        q = ops._cooccur_rows(who, index, rows)
+        need = ops.cooccur_workspace(int((index.walk[q] > ops.COOCCUR_SLOTS // 2).sum()), index.n_query)
+        ops.cooccur_topk(index, q, k, out_idx, out_val, out_cnt, measure=measure, workspace=self._kept_workspace(who, need, index.device))
         return out_idx, out_val
 
-    def _co(self, side, ids, k, measure):
-        n_rows = self.num_items if side == "item" else self.num_users
-        k, _ = ops._cooccur_k("co_%ss" % side, k), ops._cooccur_measure("co_%ss" % side, measure)
-        ids = self._id_lists([ids], side, n_rows)[1]
+    def _kept_workspace(self, who, need, dev):
+        """The model's ONE zeroed workspace for the dense form of the two-form calls (ops.cooccur_topk, walk_topk,
+        neighbour_vote_topk): a uint8 tensor of at least `need` bytes on `dev`, None for need = 0. Re-made (and zeroed) when it is
+        missing, too small or on another device; past ops.COOCCUR_WORKSPACE_BUDGET a ValueError that names the caller, before
+        anything is allocated."""
+        # One buffer is enough for the three families: each runs on the current stream, and every call leaves its workspace zero
+        # (csrc/co_select.h), so the next call -- of whichever family -- finds it as the first one did.
+        ws = self.__dict__.get("_form_ws")
+        if need and (ws is None or ws.numel() < need or ws.device != torch.device(dev)):
+            if need > ops.COOCCUR_WORKSPACE_BUDGET:
+                raise ValueError("%s: the dense form's rows need %d bytes, the budget is %d" % (who, need, ops.COOCCUR_WORKSPACE_BUDGET))
+            ws = self.__dict__["_form_ws"] = torch.zeros(need, dtype=torch.uint8, device=dev)
+        return ws if need else None
+
+    def _graph_neighbours(self, side, ids, k, lists_into):
+        """The host half of co_items / rp3_items and their user twins: the ids checked against their side, lists_into(ids, idx, val)
+        fills the two device tensors [B x k] -> Neighbours on the CPU."""
+        ids = self._id_lists([ids], side, self.num_items if side == "item" else self.num_users)[1]
         dev = self._require_gpu()
         idx = torch.empty(ids.size, k, dtype=torch.int32, device=dev)
         val = torch.empty(ids.size, k, dtype=torch.float32, device=dev)
-        self.co_neighbours_device(side, ids, k, measure, idx, val)
+        lists_into(ids, idx, val)
         return Neighbours(idx.cpu(), val.cpu())
+
+    def _co(self, side, ids, k, measure):
+        k, _ = ops._form_k("co_%ss" % side, k, ops.COOCCUR_MAX_K), ops._cooccur_measure("co_%ss" % side, measure)
+        return self._graph_neighbours(side, ids, k, lambda ids, idx, val: self.co_neighbours_device(side, ids, k, measure, idx, val))
 
     def co_items(self, item_ids, k, measure="cosine"):
         """The k items most often taken by the same training users as each given item -- "users who took this also took ...",
@@ -1537,31 +1549,19 @@ class EliMRec(BasicModel):
         device, by (score descending, id ascending), -1 / -inf where fewer than k rows are reached; the row itself is never listed
         (csrc/walk.hip). rows: the query ids (host array or tensor, checked on the host). The dense form's workspace is kept (every
         call leaves it zero). Nothing of the learned tables is read: this works on an untrained model. Single-GPU."""
-        k = ops._walk_k("walk_neighbours_device", k)
+        who = "walk_neighbours_device"
+        k = ops._form_k(who, k, ops.WALK_MAX_K)
         index = self.cooccur_index(side)
         weights = self.walk_weights(side, alpha, beta)
-        q = ops._cooccur_rows("walk_neighbours_device", index, rows)
-        n_dense = int((index.walk[q] > ops.WALK_SLOTS // 2).sum())
-        need = ops.walk_workspace(n_dense, index.n_query)
-        kept = self.__dict__.setdefault("_walk_ws", {})
-        if need and (kept.get(side) is None or kept[side].numel() < need or kept[side].device != index.device):
-            if need > ops.COOCCUR_WORKSPACE_BUDGET:
-                raise ValueError("walk_neighbours_device: the dense form's rows need %d bytes, the budget is %d"
-                                 % (need, ops.COOCCUR_WORKSPACE_BUDGET))
-            kept[side] = torch.zeros(need, dtype=torch.uint8, device=index.device)     # zero once: every call leaves it zero
-        ops.walk_topk(index, q, k, weights, out_idx, out_val, workspace=kept.get(side) if need else None)
+        q = ops._cooccur_rows(who, index, rows)
+        need = ops.walk_workspace(int((index.walk[q] > ops.WALK_SLOTS // 2).sum()), index.n_query)
+        ops.walk_topk(index, q, k, weights, out_idx, out_val, workspace=self._kept_workspace(who, need, index.device))
         return out_idx, out_val
 
     def _rp3(self, side, ids, k, alpha, beta):
-        n_rows = self.num_items if side == "item" else self.num_users
-        k = ops._walk_k("rp3_%ss" % side, k)
+        k = ops._form_k("rp3_%ss" % side, k, ops.WALK_MAX_K)
         alpha, beta = ops._rp3_params("rp3_%ss" % side, alpha, beta)
-        ids = self._id_lists([ids], side, n_rows)[1]
-        dev = self._require_gpu()
-        idx = torch.empty(ids.size, k, dtype=torch.int32, device=dev)
-        val = torch.empty(ids.size, k, dtype=torch.float32, device=dev)
-        self.walk_neighbours_device(side, ids, k, alpha, beta, idx, val)
-        return Neighbours(idx.cpu(), val.cpu())
+        return self._graph_neighbours(side, ids, k, lambda ids, idx, val: self.walk_neighbours_device(side, ids, k, alpha, beta, idx, val))
 
     def rp3_items(self, item_ids, k, alpha=1.0, beta=0.6):
         """The k items a two-step random walk over the training graph reaches from each given item, RP3beta's neighbour lists
@@ -1660,22 +1660,16 @@ class EliMRec(BasicModel):
         ops.NeighbourLists (neighbour_lists); hist: an ops.HistoryIndex whose own ids are left out; excl: a second HistoryIndex of
         the same segments to leave out as well. The dense form's workspace is kept (every call leaves it zero). Single-GPU."""
         dev = self._require_gpu()
-        k = ops._vote_k("knn_recommend_device", k)
-        ops._vote_indexes("knn_recommend_device", lists, hist, excl)
-        u = ops._checked_ids(users, hist.n_rows, "knn_recommend_device", "users", "users span [%d, %d], the histories have %d segments")
+        who = "knn_recommend_device"
+        k = ops._form_k(who, k, ops.VOTE_MAX_K)
+        ops._vote_indexes(who, lists, hist, excl)
+        u = ops._checked_ids(users, hist.n_rows, who, "users", "users span [%d, %d], the histories have %d segments")
         B = int(u.size)
         out_idx = torch.empty(B, k, dtype=torch.int32, device=dev) if out_idx is None else out_idx
         out_val = torch.empty(B, k, dtype=torch.float32, device=dev) if out_val is None else out_val
         out_cnt = torch.empty(B, k, dtype=torch.int32, device=dev) if out_cnt is None else out_cnt
-        n_dense = int((ops.vote_votes(lists, hist, excl)[u] > ops.VOTE_SLOTS // 2).sum())
-        need = ops.vote_workspace(n_dense, lists.n)
-        ws = self.__dict__.get("_vote_ws")
-        if need and (ws is None or ws.numel() < need or ws.device != dev):
-            if need > ops.COOCCUR_WORKSPACE_BUDGET:
-                raise ValueError("knn_recommend_device: the dense form's rows need %d bytes, the budget is %d"
-                                 % (need, ops.COOCCUR_WORKSPACE_BUDGET))
-            ws = self.__dict__["_vote_ws"] = torch.zeros(need, dtype=torch.uint8, device=dev)      # zero once: every call leaves it zero
-        ops.neighbour_vote_topk(lists, hist, u, k, out_idx, out_val, out_cnt, excl=excl, workspace=ws if need else None)
+        need = ops.vote_workspace(int((ops.vote_votes(lists, hist, excl)[u] > ops.VOTE_SLOTS // 2).sum()), lists.n)
+        ops.neighbour_vote_topk(lists, hist, u, k, out_idx, out_val, out_cnt, excl=excl, workspace=self._kept_workspace(who, need, dev))
         return out_idx, out_val, out_cnt
 
     def recommend_knn(self, user_ids, k, neighbours=50, source="co", measure="cosine", history=None, exclude=None, alpha=1.0, beta=0.6):
@@ -1690,7 +1684,7 @@ class EliMRec(BasicModel):
         are never listed; `exclude` = dict user -> item ids left out on top, as explain() takes it. k or neighbours outside
         [1, 256], an unknown source or measure: ValueError; an id outside its side: IndexError -- both before anything touches the
         device. An empty user_ids returns [0 x k] without a launch."""
-        k = ops._vote_k("recommend_knn", k)
+        k = ops._form_k("recommend_knn", k, ops.VOTE_MAX_K)
         neighbours = self._knn_source(source, neighbours, measure, alpha, beta)
         users = self._id_lists([user_ids], "user", self.num_users)[1]
         if history is None:
@@ -1794,7 +1788,7 @@ class EliMRec(BasicModel):
         dev = self._require_gpu()
         if not isinstance(factors, IalsFactors):
             raise TypeError("factors must be the IalsFactors fit_ials returns")
-        k = ops._cooccur_k("ials_recommend_device", k)
+        k = ops._form_k("ials_recommend_device", k, ops.COOCCUR_MAX_K)
         if isinstance(users, ops.CrossQuery):
             query = users
         else:
@@ -1812,7 +1806,7 @@ class EliMRec(BasicModel):
         vector: every item scores 0 and the lowest ids are listed. k outside [1, 256] or a fit parameter out of range: ValueError;
         an id outside its side: IndexError -- both before anything touches the device. An empty user_ids returns [0 x k] without
         a launch or a fit."""
-        k = ops._cooccur_k("recommend_ials", k)
+        k = ops._form_k("recommend_ials", k, ops.COOCCUR_MAX_K)
         params = self._ials_params(**fit)
         users = self._id_lists([user_ids], "user", self.num_users)[1]
         tptr, tflat = self._excluded(self.dataset.get_user_train_dict() if exclude is None else exclude, users, "item")

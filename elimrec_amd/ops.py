@@ -2367,28 +2367,66 @@ COOCCUR_MEASURES = {"count": 0, "cosine": 1, "jaccard": 2}
 COOCCUR_WORKSPACE_BUDGET = 1 << 30       # bytes cooccur_topk allocates for the dense form's counter rows at most (workspace=None)
 
 
+# The two-form calls (cooccur_topk, walk_topk, neighbour_vote_topk; csrc/co_select.h) share one host front end. `family` is the
+# middle of the library's symbols: elimrec_<family>_slots / _groups / _rows_in_lds / _workspace.
+
+def _form_rows_in_lds(family, name, size):
+    form = int(getattr(_lib.load(), "elimrec_%s_rows_in_lds" % family)(int(size)))
+    if form < 0:
+        raise ValueError("elimrec_amd.ops.%s_rows_in_lds: %s >= 0, got %d" % (family, name, size))
+    return bool(form)
+
+
+def _form_workspace(family, n_dense_rows, n):
+    if n_dense_rows < 0 or not 0 <= n < 2 ** 31 - 1:
+        raise ValueError("elimrec_amd.ops.%s_workspace: n_dense_rows >= 0 and 0 <= n < 2^31 - 1, got %d and %d" % (family, n_dense_rows, n))
+    return int(getattr(_lib.load(), "elimrec_%s_workspace" % family)(int(n_dense_rows), int(n)))
+
+
+def _form_k(who, K, max_k):
+    if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or not 1 <= K <= max_k:
+        raise ValueError("elimrec_amd.ops.%s: K must be an integer, 1 <= K <= %d, got %r" % (who, max_k, K))
+    return int(K)
+
+
+def _form_call(who, family, sizes, at, lds, n, K, outs, workspace, dev, where):
+    """The back half of a two-form call, before anything is launched. sizes()[at]: the host's size of every row of the call (W of a
+    walk, V of a vote), which picks its form -- a callable, asked only when rows take the LDS form; where: whose device `dev` is; n: the entries of a dense row; outs: (out_idx, out_val, out_cnt), the last two optional. -> None for a
+    call without rows, else ((idx, val, cnt) device pointers, n_dense, the workspace tensor -- the caller holds it until its launch
+    is queued): a default workspace is allocated and zeroed here under COOCCUR_WORKSPACE_BUDGET, a caller's is checked (ValueError)."""
+    R = int(at.size)
+    out_idx, out_val, out_cnt = outs
+    ip = _rows_out(out_idx, "out_idx", torch.int32, R, K, who, dev)
+    vp = _rows_out(out_val, "out_val", torch.float32, R, K, who, dev) if out_val is not None else None
+    cp = _rows_out(out_cnt, "out_cnt", torch.int32, R, K, who, dev) if out_cnt is not None else None
+    if R == 0:
+        return None
+    lib = _lib.load()
+    n_dense = int((sizes()[at] > getattr(lib, "elimrec_%s_slots" % family)() // 2).sum()) if lds else R
+    need = _form_workspace(family, n_dense, n)
+    if workspace is None:
+        if need > COOCCUR_WORKSPACE_BUDGET:
+            raise ValueError("elimrec_amd.ops.%s: the dense form's rows need %d bytes (%d rows of %d entries), the budget is %d: pass a "
+                             "workspace" % (who, need, min(n_dense, getattr(lib, "elimrec_%s_groups" % family)()), n, COOCCUR_WORKSPACE_BUDGET))
+        workspace = torch.zeros(max(16, need), dtype=torch.uint8, device=dev)
+    wp = _dev(workspace, "workspace", torch.uint8)
+    if workspace.numel() < need or not workspace.is_contiguous() or wp % 16 or workspace.device != dev:
+        raise ValueError("elimrec_amd.ops.%s: the workspace needs %d contiguous bytes on the %s device, 16-byte aligned (got %d)"
+                         % (who, need, where, workspace.numel()))
+    return (ip, vp, cp), n_dense, workspace
+
+
 def cooccur_rows_in_lds(W):
     """Which form cooccur_topk takes for a query row whose walk is W = the sum of deg(u) over the row's segment (host arithmetic
     only): True = the LDS form (W <= COOCCUR_SLOTS / 2: the hash table's load factor is at most 0.5 whatever the ids are), False =
     the dense form. Both forms give the same bits. ValueError for W < 0."""
-    form = int(_lib.load().elimrec_cooccur_rows_in_lds(int(W)))
-    if form < 0:
-        raise ValueError("elimrec_amd.ops.cooccur_rows_in_lds: W >= 0, got %d" % W)
-    return bool(form)
+    return _form_rows_in_lds("cooccur", "W", W)
 
 
 def cooccur_workspace(n_dense_rows, n):
     """Bytes of the dense form's counter rows for a call with n_dense_rows rows on that form over a query side of n rows (host
     arithmetic only): min(n_dense_rows, COOCCUR_GROUPS) int32 rows of n entries."""
-    if n_dense_rows < 0 or not 0 <= n < 2 ** 31 - 1:
-        raise ValueError("elimrec_amd.ops.cooccur_workspace: n_dense_rows >= 0 and 0 <= n < 2^31 - 1, got %d and %d" % (n_dense_rows, n))
-    return int(_lib.load().elimrec_cooccur_workspace(int(n_dense_rows), int(n)))
-
-
-def _cooccur_k(who, K):
-    if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or not 1 <= K <= COOCCUR_MAX_K:
-        raise ValueError("elimrec_amd.ops.%s: K must be an integer, 1 <= K <= %d, got %r" % (who, COOCCUR_MAX_K, K))
-    return int(K)
+    return _form_workspace("cooccur", n_dense_rows, n)
 
 
 def _cooccur_measure(who, measure):
@@ -2488,33 +2526,19 @@ def cooccur_topk(index, rows, K, out_idx, out_val=None, out_cnt=None, measure="c
     ValueError before any launch. Both forms give the same bits: a row's outputs depend on the graph, the row, K and the measure
     alone. Every argument error is raised before the device is touched. An empty `rows` returns without a launch."""
     who = "cooccur_topk"
-    K = _cooccur_k(who, K)
+    K = _form_k(who, K, COOCCUR_MAX_K)
     m = _cooccur_measure(who, measure)
     q = _cooccur_rows(who, index, rows)
     Q, dev = int(q.size), index.device
-    ip = _rows_out(out_idx, "out_idx", torch.int32, Q, K, who, dev)
-    vp = _rows_out(out_val, "out_val", torch.float32, Q, K, who, dev) if out_val is not None else None
-    cp = _rows_out(out_cnt, "out_cnt", torch.int32, Q, K, who, dev) if out_cnt is not None else None
-    if Q == 0:
+    call = _form_call(who, "cooccur", lambda: index.walk, q, lds, index.n_query, K, (out_idx, out_val, out_cnt), workspace, dev, "index's")
+    if call is None:
         return out_idx
-    half = int(_lib.load().elimrec_cooccur_slots()) // 2
-    n_dense = int((index.walk[q] > half).sum()) if lds else Q
-    need = cooccur_workspace(n_dense, index.n_query)
-    if workspace is None:
-        if need > COOCCUR_WORKSPACE_BUDGET:
-            raise ValueError("elimrec_amd.ops.%s: the dense form's counter rows need %d bytes (%d rows of %d entries), the budget is %d: "
-                             "pass a workspace" % (who, need, min(n_dense, _lib.load().elimrec_cooccur_groups()), index.n_query,
-                                                   COOCCUR_WORKSPACE_BUDGET))
-        workspace = torch.zeros(max(16, need), dtype=torch.uint8, device=dev)
-    wp = _dev(workspace, "workspace", torch.uint8)
-    if workspace.numel() < need or not workspace.is_contiguous() or wp % 16 or workspace.device != dev:
-        raise ValueError("elimrec_amd.ops.%s: the workspace needs %d contiguous bytes on the index's device, 16-byte aligned (got %d)"
-                         % (who, need, workspace.numel()))
+    (ip, vp, cp), n_dense, ws = call
     walk = torch.empty(Q, dtype=torch.int64, device=dev)
     _lib.check(_lib.load().elimrec_cooccur_topk(_dev(index.q_ptr, "q_ptr", torch.int64), _dev(index.q_nbr, "q_nbr", torch.int32), index.n_query,
                                                 _dev(index.o_ptr, "o_ptr", torch.int64), _dev(index.o_nbr, "o_nbr", torch.int32), index.n_other,
                                                 _dev(_resident_ids(q, dev), "rows", torch.int32), Q, K, m, 1 if lds else 0, n_dense,
-                                                walk.data_ptr(), ip, vp, cp, wp, workspace.numel(), _stream()), who)
+                                                walk.data_ptr(), ip, vp, cp, ws.data_ptr(), ws.numel(), _stream()), who)
     return out_idx
 
 
@@ -2527,24 +2551,13 @@ def walk_rows_in_lds(W):
     """Which form walk_topk takes for a query row whose walk is W = the sum of deg(u) over the row's segment (index.walk,
     cooccur_walk; host arithmetic only): True = the LDS form (W <= WALK_SLOTS / 2), False = the dense form. Both forms give the
     same bits. ValueError for W < 0."""
-    form = int(_lib.load().elimrec_walk_rows_in_lds(int(W)))
-    if form < 0:
-        raise ValueError("elimrec_amd.ops.walk_rows_in_lds: W >= 0, got %d" % W)
-    return bool(form)
+    return _form_rows_in_lds("walk", "W", W)
 
 
 def walk_workspace(n_dense_rows, n):
     """Bytes of the dense form's rows for a call with n_dense_rows rows on that form over a query side of n rows (host arithmetic
     only): min(n_dense_rows, 512) rows of n int64 sums."""
-    if n_dense_rows < 0 or not 0 <= n < 2 ** 31 - 1:
-        raise ValueError("elimrec_amd.ops.walk_workspace: n_dense_rows >= 0 and 0 <= n < 2^31 - 1, got %d and %d" % (n_dense_rows, n))
-    return int(_lib.load().elimrec_walk_workspace(int(n_dense_rows), int(n)))
-
-
-def _walk_k(who, K):
-    if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or not 1 <= K <= WALK_MAX_K:
-        raise ValueError("elimrec_amd.ops.%s: K must be an integer, 1 <= K <= %d, got %r" % (who, WALK_MAX_K, K))
-    return int(K)
+    return _form_workspace("walk", n_dense_rows, n)
 
 
 class WalkWeights(object):
@@ -2636,33 +2649,21 @@ def walk_topk(index, rows, K, weights, out_idx, out_val=None, lds=True, workspac
     Both forms give the same bits: a row's outputs depend on the graph, the three arrays, the row and K alone. An empty `rows`
     returns without a launch."""
     who = "walk_topk"
-    K = _walk_k(who, K)
+    K = _form_k(who, K, WALK_MAX_K)
     q = _cooccur_rows(who, index, rows)
     _walk_bounds(who, index, q, weights)
     Q, dev = int(q.size), index.device
-    ip = _rows_out(out_idx, "out_idx", torch.int32, Q, K, who, dev)
-    vp = _rows_out(out_val, "out_val", torch.float32, Q, K, who, dev) if out_val is not None else None
-    if Q == 0:
+    call = _form_call(who, "walk", lambda: index.walk, q, lds, index.n_query, K, (out_idx, out_val, None), workspace, dev, "index's")
+    if call is None:
         return out_idx
-    n_dense = int((index.walk[q] > WALK_SLOTS // 2).sum()) if lds else Q
-    need = walk_workspace(n_dense, index.n_query)
-    if workspace is None:
-        if need > COOCCUR_WORKSPACE_BUDGET:
-            raise ValueError("elimrec_amd.ops.%s: the dense form's rows need %d bytes (%d rows of %d sums), the budget is %d: pass a "
-                             "workspace" % (who, need, min(n_dense, _lib.load().elimrec_walk_groups()), index.n_query,
-                                            COOCCUR_WORKSPACE_BUDGET))
-        workspace = torch.zeros(max(16, need), dtype=torch.uint8, device=dev)
-    wp = _dev(workspace, "workspace", torch.uint8)
-    if workspace.numel() < need or not workspace.is_contiguous() or wp % 16 or workspace.device != dev:
-        raise ValueError("elimrec_amd.ops.%s: the workspace needs %d contiguous bytes on the index's device, 16-byte aligned (got %d)"
-                         % (who, need, workspace.numel()))
+    (ip, vp, _), n_dense, ws = call
     walk = torch.empty(Q, dtype=torch.int64, device=dev)
     _lib.check(_lib.load().elimrec_walk_topk(_dev(index.q_ptr, "q_ptr", torch.int64), _dev(index.q_nbr, "q_nbr", torch.int32), index.n_query,
                                              _dev(index.o_ptr, "o_ptr", torch.int64), _dev(index.o_nbr, "o_nbr", torch.int32), index.n_other,
                                              _dev(_resident_ids(q, dev), "rows", torch.int32), Q, K,
                                              _dev(weights.mid_weight, "mid_weight", torch.int64), _dev(weights.row_scale, "row_scale", torch.float64),
                                              _dev(weights.col_scale, "col_scale", torch.float64), 1 if lds else 0, n_dense, walk.data_ptr(),
-                                             ip, vp, wp, workspace.numel(), _stream()), who)
+                                             ip, vp, ws.data_ptr(), ws.numel(), _stream()), who)
     return out_idx
 
 
@@ -2707,24 +2708,13 @@ def vote_rows_in_lds(V):
     """Which form neighbour_vote_topk takes for a user with V = (history length) x Kn + (entries left out) (host arithmetic only):
     True = the LDS form (V <= VOTE_SLOTS / 2: the hash table's load factor is at most 0.5 whatever the ids are), False = the dense
     form. Both forms give the same bits. ValueError for V < 0."""
-    form = int(_lib.load().elimrec_vote_rows_in_lds(int(V)))
-    if form < 0:
-        raise ValueError("elimrec_amd.ops.vote_rows_in_lds: V >= 0, got %d" % V)
-    return bool(form)
+    return _form_rows_in_lds("vote", "V", V)
 
 
 def vote_workspace(n_dense_rows, n):
     """Bytes of the dense form's rows for a call with n_dense_rows users on that form over lists of n items (host arithmetic only):
     min(n_dense_rows, VOTE_GROUPS) rows of n int64 sums and n int32 counts."""
-    if n_dense_rows < 0 or not 0 <= n < 2 ** 31 - 1:
-        raise ValueError("elimrec_amd.ops.vote_workspace: n_dense_rows >= 0 and 0 <= n < 2^31 - 1, got %d and %d" % (n_dense_rows, n))
-    return int(_lib.load().elimrec_vote_workspace(int(n_dense_rows), int(n)))
-
-
-def _vote_k(who, K):
-    if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or not 1 <= K <= VOTE_MAX_K:
-        raise ValueError("elimrec_amd.ops.%s: K must be an integer, 1 <= K <= %d, got %r" % (who, VOTE_MAX_K, K))
-    return int(K)
+    return _form_workspace("vote", n_dense_rows, n)
 
 
 def _vote_indexes(who, lists, hist, excl):
@@ -2767,7 +2757,7 @@ def neighbour_vote_topk(lists, hist, users, K, out_idx, out_val=None, out_cnt=No
     user's outputs depend on the history as a multiset, the lists, the exclusions and K alone. Every argument error is raised before
     the device is touched. An empty `users` returns without a launch."""
     who = "neighbour_vote_topk"
-    K = _vote_k(who, K)
+    K = _form_k(who, K, VOTE_MAX_K)
     _vote_indexes(who, lists, hist, excl)
     u = _checked_ids(users, hist.n_rows, who, "users", "users span [%d, %d], the histories have %d segments")
     B, dev = int(u.size), lists.device
@@ -2780,23 +2770,11 @@ def neighbour_vote_topk(lists, hist, users, K, out_idx, out_val=None, out_cnt=No
                          % (who, longest, lists.Kn))
     if hist.ptr.device != dev or (excl is not None and excl.ptr.device != dev):
         raise ValueError("elimrec_amd.ops.%s: the lists live on %s, the histories on %s" % (who, dev, hist.ptr.device))
-    ip = _rows_out(out_idx, "out_idx", torch.int32, B, K, who, dev)
-    vp = _rows_out(out_val, "out_val", torch.float32, B, K, who, dev) if out_val is not None else None
-    cp = _rows_out(out_cnt, "out_cnt", torch.int32, B, K, who, dev) if out_cnt is not None else None
-    if B == 0:
+    call = _form_call(who, "vote", lambda: vote_votes(lists, hist, excl, exclude_history), u, lds, lists.n, K,
+                      (out_idx, out_val, out_cnt), workspace, dev, "lists'")
+    if call is None:
         return out_idx
-    half = int(_lib.load().elimrec_vote_slots()) // 2
-    n_dense = int((vote_votes(lists, hist, excl, exclude_history)[u] > half).sum()) if lds else B
-    need = vote_workspace(n_dense, lists.n)
-    if workspace is None:
-        if need > COOCCUR_WORKSPACE_BUDGET:
-            raise ValueError("elimrec_amd.ops.%s: the dense form's rows need %d bytes (%d rows of %d entries), the budget is %d: pass a "
-                             "workspace" % (who, need, min(n_dense, _lib.load().elimrec_vote_groups()), lists.n, COOCCUR_WORKSPACE_BUDGET))
-        workspace = torch.zeros(max(16, need), dtype=torch.uint8, device=dev)
-    wp = _dev(workspace, "workspace", torch.uint8)
-    if workspace.numel() < need or not workspace.is_contiguous() or wp % 16 or workspace.device != dev:
-        raise ValueError("elimrec_amd.ops.%s: the workspace needs %d contiguous bytes on the lists' device, 16-byte aligned (got %d)"
-                         % (who, need, workspace.numel()))
+    (ip, vp, cp), n_dense, ws = call
     up = torch.from_numpy(np.ascontiguousarray(u, dtype=np.int64)).to(dev)
     ep, ei, en = (None, None, 0) if excl is None else (_dev(excl.ptr, "excl_ptr", torch.int64), _dev(excl.items, "excl_items", torch.int32),
                                                        excl.n_rows)
@@ -2804,7 +2782,7 @@ def neighbour_vote_topk(lists, hist, users, K, out_idx, out_val=None, out_cnt=No
                                                        lists.n, lists.Kn, _dev(hist.ptr, "hist_ptr", torch.int64),
                                                        _dev(hist.items, "hist_items", torch.int32), hist.n_rows, ep, ei, en,
                                                        _dev(up, "users", torch.int64), B, K, 1 if exclude_history else 0, 1 if lds else 0,
-                                                       n_dense, ip, vp, cp, wp, workspace.numel(), _stream()), who)
+                                                       n_dense, ip, vp, cp, ws.data_ptr(), ws.numel(), _stream()), who)
     return out_idx
 
 

@@ -152,6 +152,31 @@ def test_model_argument_errors_fire_without_a_gpu():
     assert "untrained" in model.co_neighbours_device.__doc__
 
 
+def test_the_model_keeps_one_workspace_for_the_two_form_calls():
+    """EliMRec._kept_workspace, which co_neighbours_device, walk_neighbours_device and knn_recommend_device share (host logic only:
+    CPU and meta tensors): the same zeroed buffer while the need fits, a new one when the need grows or the device asked for is
+    another one, nothing for a need of 0, and past the budget a ValueError that names the caller before anything is allocated."""
+    from elimrec_amd import ops
+    model, _ = build_model_from_fixture(load_golden("ml3"), "cpu")
+    cpu, meta = torch.device("cpu"), torch.device("meta")
+    assert model._kept_workspace("co_neighbours_device", 0, cpu) is None
+    a = model._kept_workspace("co_neighbours_device", 4096, cpu)
+    assert a.dtype == torch.uint8 and a.numel() >= 4096 and a.device == cpu and not a.any()
+    assert model._kept_workspace("walk_neighbours_device", 4096, cpu) is a and model._kept_workspace("knn_recommend_device", 64, cpu) is a
+    assert model._kept_workspace("knn_recommend_device", 0, cpu) is None and model._kept_workspace("co_neighbours_device", 16, cpu) is a
+    b = model._kept_workspace("walk_neighbours_device", 4097, cpu)              # the need grows
+    assert b is not a and b.numel() >= 4097 and not b.any() and model._kept_workspace("co_neighbours_device", 4096, cpu) is b
+    c = model._kept_workspace("co_neighbours_device", 64, meta)                 # the model moved: every family asks for the new device
+    assert c is not b and c.device == meta and model._kept_workspace("knn_recommend_device", 64, meta) is c
+    assert model._kept_workspace("co_neighbours_device", 64, cpu).device == cpu
+    kept = model._kept_workspace("co_neighbours_device", 64, cpu)
+    for who in ("co_neighbours_device", "walk_neighbours_device", "knn_recommend_device"):
+        with pytest.raises(ValueError, match=who):
+            model._kept_workspace(who, ops.COOCCUR_WORKSPACE_BUDGET + 1, meta)
+    assert model._kept_workspace("co_neighbours_device", 64, cpu) is kept      # the refusal allocated and replaced nothing
+    assert model._kept_workspace("walk_neighbours_device", ops.COOCCUR_WORKSPACE_BUDGET, meta).numel() == ops.COOCCUR_WORKSPACE_BUDGET
+
+
 def test_report_arguments_and_the_switch():
     from elimrec_amd.evaluator import CoNeighbourReport, co_neighbour_columns
     assert co_neighbour_columns("va") == ("n", "co_n", "co_score", "co_pop", "co_overlap_fused", "co_overlap_v", "co_overlap_a")
