@@ -1493,7 +1493,8 @@ def cross_topk(query_table, query_sqnorm, table, sqnorm, query_rows, K, out_idx,
     CANDIDATE rows; there is no exclude_self. query_rows and the CSR: host arrays or tensors, checked on the host at every call, or
     query_rows = a CrossQuery (excl_ptr = excl_rows = None), checked once. The same kernel, chunks (KNN_CHUNK), workspace
     (cosine_topk_workspace bytes), selection and merge as cosine_topk. Every argument error is raised before the device is
-    required. 1 <= K <= 256."""
+    required. 1 <= K <= 256. Dot products are unbounded: a score of +inf is listed first (ties by row id), a score of -inf or
+    NaN is no candidate and is never listed."""
     who = "cross_topk"
     nq, dq = _cross_side(query_table, query_sqnorm, "query_table", "query_sqnorm")
     n, d = _cross_side(table, sqnorm, "table", "sqnorm")

@@ -106,3 +106,54 @@ def report_rows(ids, vals, counts, k):
 def report_means(rows, positions):
     """Float64 means of the float32 rows per group of row positions."""
     return np.stack([rows[p].astype(np.float64).mean(0) for p in positions])
+
+
+# ---- cross_topk (csrc/knn.hip with a query table of its own): the kernel's own expression in np.float32
+def inv_norm32(sq, n):
+    """cosine.h::inv_norm per row in np.float32: 1 / max(sqrt(sq), 1e-12f), both correctly rounded; sq = None: a vector of ones."""
+    if sq is None:
+        return np.ones(n, dtype=np.float32)
+    with np.errstate(all="ignore"):
+        return np.float32(1.0) / np.maximum(np.sqrt(np.asarray(sq, dtype=np.float32)), np.float32(1e-12))
+
+
+def fma_chain_dot32(A, B):
+    """[len(A) x len(B)] float32 dot products as the k-ordered fmaf chain the matrix instruction runs: acc <- fl32(a_k b_k + acc), the
+    product unrounded (exact in float64). The float64 sum is exact for the operands this is used with (small integers, powers of two
+    of one magnitude), so there is no double rounding. A product beyond float32 overflows only when the SUM is rounded: +inf plus a
+    finite product of the other sign stays +inf, where separate float32 multiplies and adds would give inf - inf = NaN."""
+    A, B = np.asarray(A, dtype=np.float64), np.asarray(B, dtype=np.float64)
+    acc = np.zeros((A.shape[0], B.shape[0]), dtype=np.float32)
+    with np.errstate(all="ignore"):
+        for k in range(A.shape[1]):
+            acc = (A[:, k, None] * B[None, :, k] + acc.astype(np.float64)).astype(np.float32)
+    return acc
+
+
+def cross_scores32(Tq, sqq, T, sq, rows, chain=False):
+    """float32 [len(rows) x n] scores (dot * invq) * invc in the kernel's order; rows: valid query ids. The dot product: a float64
+    matrix product rounded once (exact when every partial sum is a float32, as for integer tables with |entry| <= 8 and d <= 256) or
+    fma_chain_dot32 (chain=True)."""
+    Tq, T = np.asarray(Tq, dtype=np.float32), np.asarray(T, dtype=np.float32)
+    rows = np.asarray(rows, dtype=np.int64)
+    dot = fma_chain_dot32(Tq[rows], T) if chain else (Tq[rows].astype(np.float64) @ T.astype(np.float64).T).astype(np.float32)
+    with np.errstate(all="ignore"):
+        return (dot * inv_norm32(sqq, Tq.shape[0])[rows][:, None]) * inv_norm32(sq, T.shape[0])[None, :]
+
+
+def cross_lists32(Tq, sqq, T, sq, rows, K, excl=None, chain=False):
+    """(ids int64, values float32) [Q x K] of cross_topk: a query id outside the query table gives a row of fillers, an exclusion id
+    outside [0, n) excludes nothing, a score of -inf or NaN is no candidate (the kernel keeps what is > its threshold, -inf at
+    first), +inf ranks first, ties by id."""
+    rows = np.asarray(rows, dtype=np.int64)
+    nq, n = np.asarray(Tq).shape[0], np.asarray(T).shape[0]
+    ok = (rows >= 0) & (rows < nq)
+    s = cross_scores32(Tq, sqq, T, sq, np.where(ok, rows, 0), chain).astype(np.float64) if nq else np.zeros((rows.size, n))
+    s[np.isnan(s)] = -np.inf
+    s[~ok] = -np.inf
+    if excl is not None:
+        for b, lst in enumerate(excl):
+            hit = [int(e) for e in lst if 0 <= int(e) < n]
+            s[b, hit] = -np.inf
+    ids, vals = topk64(s, K)
+    return ids, vals.astype(np.float32)
