@@ -221,6 +221,14 @@ SIGNATURES = {
     "elimrec_als_solve": (c_i32, [c_ptr, c_i64, c_i64, c_i32, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_ptr, ctypes.c_double, c_ptr, c_i64,
                                   c_ptr, c_ptr]),
     "elimrec_als_chunk": (c_i32, []),
+    "elimrec_gram_counts": (c_i32, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, ctypes.c_double, c_ptr, c_i64, c_ptr]),
+    "elimrec_spd_inverse": (c_i32, [c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
+    "elimrec_spd_inverse_workspace": (c_size, [c_i64]),
+    "elimrec_ease_block": (c_i32, []),
+    "elimrec_ease_topk": (c_i32, [c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_i32, c_ptr, c_ptr, c_ptr, c_size,
+                                  c_ptr]),
+    "elimrec_ease_topk_workspace": (c_size, [c_i64, c_i64, c_i32]),
+    "elimrec_ease_hist_stage": (c_i32, []),
     "elimrec_list_overlap": (c_i32, [c_ptr, c_ptr, c_i64, c_i32, c_ptr, c_ptr]),
     "elimrec_audience_topk": (c_i32, [c_ptr, c_i64, c_i64, c_i64, c_i32, c_i32, c_u32, c_i32, c_i32, c_ptr, c_ptr, c_i64, c_ptr, c_i64,
                                       c_ptr, c_ptr, c_i32, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
@@ -432,7 +440,7 @@ class _Recording(object):
                              "elimrec_cooccur_slots", "elimrec_cooccur_max_k", "elimrec_cooccur_groups", "elimrec_cooccur_rows_in_lds",
                              "elimrec_vote_slots", "elimrec_vote_groups", "elimrec_vote_max_k", "elimrec_vote_frac_bits", "elimrec_vote_rows_in_lds",
                              "elimrec_walk_slots", "elimrec_walk_max_k", "elimrec_walk_groups", "elimrec_walk_frac_bits", "elimrec_walk_rows_in_lds",
-                             "elimrec_segment_plan_form", "elimrec_als_chunk",
+                             "elimrec_segment_plan_form", "elimrec_als_chunk", "elimrec_ease_block", "elimrec_ease_hist_stage",
                              "elimrec_comm_create", "elimrec_comm_destroy", "elimrec_comm_nranks") or name.startswith("elimrec_program_")
             setattr(self, name, self._wrap(fn, name) if res is c_i32 and not plain else fn)
 

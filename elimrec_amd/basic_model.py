@@ -173,9 +173,10 @@ class BasicModel(nn.Module):
         # --baseline_report=K (CLI-only, default 0 = off): baselines beside the model -- per --baseline_sources entry (default [co]:
         # ItemKNN over the training graph under --baseline_measure=count|cosine|jaccard, default cosine; fused / a head letter:
         # content-KNN in that space; rp3: RP3beta over the training graph under --baseline_alpha / --baseline_beta; ials: the iALS
-        # factor model, no vote) the test users' top-K lists, voted for by the --baseline_neighbours (default 50) nearest items of
-        # every train item: the evaluator's metrics, how full and how popular the lists are, how much of the model's own list they
-        # hold and their catalogue exposure, overall and per user group (reports.BaselineReport)
+        # factor model, no vote; ease: the closed-form EASE^R item-item model under --baseline_l2, no vote) the test users' top-K
+        # lists, voted for by the --baseline_neighbours (default 50) nearest items of every train item: the evaluator's metrics,
+        # how full and how popular the lists are, how much of the model's own list they hold and their catalogue exposure, overall
+        # and per user group (reports.BaselineReport)
         k_base = config["baseline_report"] if "baseline_report" in config else 0
         if isinstance(k_base, bool) or not isinstance(k_base, int) or k_base < 0:
             raise ValueError("baseline_report must be 0 (off) or the K of the baseline lists, got %r" % (k_base,))
@@ -196,15 +197,18 @@ class BasicModel(nn.Module):
         ials = ops._ials_params("baseline_factors / _iters / _conf / _reg / _reg_scale",
                                 *[config["baseline_" + k] if ("baseline_" + k) in config else v for k, v in (
                                     ("factors", 64), ("iters", 15), ("conf", 1.0), ("reg", 0.01), ("reg_scale", 0.0))])
+        # --baseline_l2=500.0 (CLI-only): the source ease -- EASE^R over the training graph (EliMRec.fit_ease), its one
+        # hyper-parameter, finite and > 0; 500 is the commonly quoted value, not tuned
+        base_l2 = ops._ease_params("baseline_l2", config["baseline_l2"] if "baseline_l2" in config else 500.0)
         self.baseline_reporter = None
         if k_base:
             for x in sources:        # (the model checks a head letter against its own heads at the first list)
-                if x not in ("co", "rp3", "ials", "fused", "v", "a", "t"):
-                    raise ValueError("baseline_sources names 'co', 'rp3', 'ials', 'fused' or a head letter (v, a, t), got %r" % (x,))
+                if x not in ("co", "rp3", "ials", "ease", "fused", "v", "a", "t"):
+                    raise ValueError("baseline_sources names 'co', 'rp3', 'ials', 'ease', 'fused' or a head letter (v, a, t), got %r" % (x,))
             self.baseline_reporter = BaselineReport(dataset, train, dataset.get_user_test_dict(), config["topks"], metric=config["metric"],
                                                     sources=sources, neighbours=n_near, measure=base_measure,
                                                     group_view=config["group_view"], list_k=k_base, alpha=base_alpha, beta=base_beta,
-                                                    factors=ials[0], iters=ials[1], conf=ials[2], reg=ials[3], reg_scale=ials[4])
+                                                    factors=ials[0], iters=ials[1], conf=ials[2], reg=ials[3], reg_scale=ials[4], l2=base_l2)
         # --coldstart_report=K (CLI-only, default 0 = off): the cold test items (no training interaction, a test interaction) as
         # trained, folded in from their content and folded in with the mean id row -- pair means of rank, pct, rr and hit@K for the
         # topks and K, overall and per user group (reports.ColdStartReport)

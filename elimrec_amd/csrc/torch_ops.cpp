@@ -55,6 +55,12 @@
 //       implicit-feedback ALS, out[r] = (A0 + reg[r] I + conf sum f f^T)^-1 (1 + conf) sum f over row r's list, float64 Cholesky per row;
 //       rows not listed are zero; the CSR (strictly ascending lists), reg and conf are checked on the host (csrc/als.hip). A row that
 //       is not positive definite raises through TORCH_CHECK, a RuntimeError here (ops.als_solve raises ArithmeticError with the same words)
+//   gram_counts(q_ptr i64[n + 1], q_nbr i32, o_ptr i64[n_other + 1], o_nbr i32, l2) -> f64[n x n]: the walks i -> u -> j of a bipartite
+//       graph + l2 on the diagonal, X^T X + l2 I of a binary X; integer counts, exact (csrc/ease.hip)
+//   spd_inverse(A f64[n x n]) -> (inverse f64[n x n], pivot_min f64[1]): the symmetric block sweep in float64 on a copy of A; a matrix
+//       that is not positive definite raises through TORCH_CHECK (ops.spd_inverse works in place and raises ArithmeticError)
+//   ease_topk(P f64[I x I], hist_ptr i64[R + 1], hist_items i32, excl_ptr i64[R + 1]?, excl_items i32?, users i64[B], K) -> (idx i32,
+//       val f32) [B x K]: the K items with the largest -(sum_{i in H, i != j} P_ij) / P_jj, excl's ids (default: the history's) left out
 //   neighbour_vote_topk(nbr_idx i32[n x Kn], nbr_val f32[n x Kn], hist_ptr i64[R + 1], hist_items i32, excl_ptr i64[R + 1]?, excl_items i32?,
 //       users i64[B], K) -> (idx i32, val f32, cnt i32) [B x K]: the K items the neighbour lists of each user's history vote for, the
 //       history's own ids and excl's left out; fixed-point int64 sums, the overflow bound and the form rule on the host (csrc/vote.hip)
@@ -575,6 +581,76 @@ at::Tensor als_solve(const at::Tensor &ptr, const at::Tensor &nbr, const at::Ten
     TORCH_CHECK(hs.data_ptr<int32_t>()[0] == 0, "elimrec::als_solve: A_r is not positive definite for ", hs.data_ptr<int32_t>()[0],
                 " row(s), the first is row ", hs.data_ptr<int32_t>()[1], " (written as zeros)");
     return out;
+}
+
+// ---- EASE (csrc/ease.hip): the Gram matrix of a bipartite graph, a dense SPD inverse, the top-K of the history's rows of P
+static at::Tensor nonempty_ids(const at::Tensor &ids) { return ids.numel() ? ids.contiguous() : at::zeros({1}, ids.options()); }
+
+at::Tensor gram_counts(const at::Tensor &q_ptr, const at::Tensor &q_nbr, const at::Tensor &o_ptr, const at::Tensor &o_nbr, double l2) {
+    need(q_ptr, "q_ptr", at::kLong, 1); need(q_nbr, "q_nbr", at::kInt, 1); need(o_ptr, "o_ptr", at::kLong, 1); need(o_nbr, "o_nbr", at::kInt, 1);
+    const at::Tensor qp = q_ptr.contiguous(), op = o_ptr.contiguous();
+    const int64_t n = qp.numel() - 1, n_other = op.numel() - 1;
+    TORCH_CHECK_VALUE(n >= 0 && n_other >= 0, "elimrec::gram_counts: both pointers need at least one entry");
+    TORCH_CHECK_VALUE(std::isfinite(l2) && l2 >= 0.0, "elimrec::gram_counts: l2 is finite and >= 0, got ", l2);
+    TORCH_CHECK_VALUE(q_nbr.numel() == o_nbr.numel(), "elimrec::gram_counts: the two CSRs hold the same edges, got ", q_nbr.numel(), " and ", o_nbr.numel());
+    checked_csr(qp, q_nbr, n, n_other, true, "gram_counts", "q_ptr", "q_nbr", "q_nbr", "the other side has", "rows");
+    checked_csr(op, o_nbr, n_other, n, true, "gram_counts", "o_ptr", "o_nbr", "o_nbr", "the query side has", "rows");
+    at::Tensor out = at::empty({n, n}, qp.options().dtype(at::kDouble));
+    if (n == 0) return out;
+    const at::Tensor qn = nonempty_ids(q_nbr), on = nonempty_ids(o_nbr);
+    check(elimrec_gram_counts(qp.data_ptr<int64_t>(), qn.data_ptr<int32_t>(), op.data_ptr<int64_t>(), on.data_ptr<int32_t>(), n, n_other, l2,
+                              out.data_ptr<double>(), n, cur_stream()),
+          "gram_counts");
+    return out;
+}
+
+std::tuple<at::Tensor, at::Tensor> spd_inverse(const at::Tensor &A) {
+    need(A, "A", at::kDouble, 2);
+    TORCH_CHECK_VALUE(A.size(0) == A.size(1) && A.size(0) >= 1, "elimrec::spd_inverse: A must be square with n >= 1 rows");
+    const int64_t n = A.size(0);
+    at::Tensor out = A.clone(at::MemoryFormat::Contiguous);
+    at::Tensor pivot = at::empty({1}, out.options()), status = at::empty({2}, out.options().dtype(at::kInt));
+    at::Tensor ws = at::empty({(int64_t)elimrec_spd_inverse_workspace(n)}, out.options().dtype(at::kByte));
+    check(elimrec_spd_inverse(out.data_ptr<double>(), n, n, pivot.data_ptr<double>(), status.data_ptr<int32_t>(), ws.data_ptr(), (size_t)ws.numel(),
+                              cur_stream()),
+          "spd_inverse");
+    const at::Tensor hs = status.cpu();
+    TORCH_CHECK(hs.data_ptr<int32_t>()[0] == 0, "elimrec::spd_inverse: the matrix is not positive definite: the pivot at index ",
+                hs.data_ptr<int32_t>()[1], " is <= 0 or not finite");
+    return {out, pivot};
+}
+
+std::tuple<at::Tensor, at::Tensor> ease_topk(const at::Tensor &P, const at::Tensor &hist_ptr, const at::Tensor &hist_items,
+                                             const c10::optional<at::Tensor> &excl_ptr, const c10::optional<at::Tensor> &excl_items,
+                                             const at::Tensor &users, int64_t K) {
+    need(P, "P", at::kDouble, 2); need(hist_ptr, "hist_ptr", at::kLong, 1); need(hist_items, "hist_items", at::kInt, 1);
+    need(users, "users", at::kLong, 1);
+    TORCH_CHECK_VALUE(P.size(0) == P.size(1), "elimrec::ease_topk: P must be square");
+    TORCH_CHECK_VALUE(K >= 1 && K <= 256, "elimrec::ease_topk: 1 <= K <= 256, got ", K);
+    TORCH_CHECK_VALUE(excl_ptr.has_value() == excl_items.has_value(), "elimrec::ease_topk: excl_ptr and excl_items come together");
+    const at::Tensor p = P.stride(1) == 1 ? P : P.contiguous(), hp = hist_ptr.contiguous(), u = users.contiguous();
+    const int64_t n = p.size(0), n_seg = hp.numel() - 1, Q = u.numel();
+    TORCH_CHECK_VALUE(n_seg >= 1, "elimrec::ease_topk: hist_ptr needs n_rows + 1 >= 2 entries");
+    checked_csr(hp, hist_items, n_seg, n, true, "ease_topk", "hist_ptr", "hist_items", "history items", "the catalogue has", "items");
+    checked_ids(u, n_seg, true, "ease_topk", "users", "the histories have", "segments");
+    at::Tensor ep, ei;
+    if (excl_ptr.has_value()) {
+        need(*excl_ptr, "excl_ptr", at::kLong, 1); need(*excl_items, "excl_items", at::kInt, 1);
+        ep = excl_ptr->contiguous();
+        TORCH_CHECK_VALUE(ep.numel() == n_seg + 1, "elimrec::ease_topk: excl_ptr needs n_rows + 1 = ", n_seg + 1, " entries, got ", ep.numel());
+        checked_csr(ep, *excl_items, n_seg, n, true, "ease_topk", "excl_ptr", "excl_items", "excluded items", "the catalogue has", "items");
+        ei = nonempty_ids(*excl_items);
+    }
+    at::Tensor idx = at::empty({Q, K}, hist_items.options()), val = at::empty({Q, K}, p.options().dtype(at::kFloat));
+    if (Q == 0) return {idx, val};
+    const at::Tensor hi = nonempty_ids(hist_items);
+    at::Tensor ws = at::empty({(int64_t)elimrec_ease_topk_workspace(Q, n, (int)K)}, p.options().dtype(at::kByte));
+    check(elimrec_ease_topk(p.data_ptr<double>(), n > 1 ? p.stride(0) : n, n, hp.data_ptr<int64_t>(), hi.data_ptr<int32_t>(),
+                            ep.defined() ? ep.data_ptr<int64_t>() : nullptr, ep.defined() ? ei.data_ptr<int32_t>() : nullptr, n_seg,
+                            u.data_ptr<int64_t>(), Q, (int)K, idx.data_ptr<int32_t>(), val.data_ptr<float>(), ws.data_ptr(), (size_t)ws.numel(),
+                            cur_stream()),
+          "ease_topk");
+    return {idx, val};
 }
 
 // ---- audience lists: per query item the K users with the largest predict() score (csrc/audience.hip)
@@ -1183,6 +1259,9 @@ TORCH_LIBRARY(elimrec, m) {
     m.def("row_gram(Tensor table, Tensor sqnorm, Tensor rows) -> (Tensor, Tensor, Tensor)");
     m.def("cross_topk(Tensor query_table, Tensor? query_sqnorm, Tensor table, Tensor? sqnorm, Tensor query_rows, Tensor? excl_ptr, Tensor? excl_rows, int K) -> (Tensor, Tensor)");
     m.def("als_solve(Tensor ptr, Tensor nbr, Tensor F, Tensor A0, Tensor reg, float conf, Tensor? rows) -> Tensor");
+    m.def("gram_counts(Tensor q_ptr, Tensor q_nbr, Tensor o_ptr, Tensor o_nbr, float l2) -> Tensor");
+    m.def("spd_inverse(Tensor A) -> (Tensor, Tensor)");
+    m.def("ease_topk(Tensor P, Tensor hist_ptr, Tensor hist_items, Tensor? excl_ptr, Tensor? excl_items, Tensor users, int K) -> (Tensor, Tensor)");
     m.def("cooccur_topk(Tensor q_ptr, Tensor q_nbr, Tensor o_ptr, Tensor o_nbr, Tensor rows, int K, str measure) -> (Tensor, Tensor, Tensor)");
     m.def("walk_topk(Tensor q_ptr, Tensor q_nbr, Tensor o_ptr, Tensor o_nbr, Tensor rows, int K, Tensor mid_weight, Tensor row_scale, Tensor col_scale) -> (Tensor, Tensor)");
     m.def("neighbour_vote_topk(Tensor nbr_idx, Tensor nbr_val, Tensor hist_ptr, Tensor hist_items, Tensor? excl_ptr, Tensor? excl_items, Tensor users, int K) -> (Tensor, Tensor, Tensor)");
@@ -1232,6 +1311,9 @@ TORCH_LIBRARY_IMPL(elimrec, CUDA, m) {
     m.impl("row_gram", &row_gram);
     m.impl("cross_topk", &cross_topk);
     m.impl("als_solve", &als_solve);
+    m.impl("gram_counts", &gram_counts);
+    m.impl("spd_inverse", &spd_inverse);
+    m.impl("ease_topk", &ease_topk);
     m.impl("cooccur_topk", &cooccur_topk);
     m.impl("walk_topk", &walk_topk);
     m.impl("neighbour_vote_topk", &neighbour_vote_topk);

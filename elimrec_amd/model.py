@@ -89,6 +89,7 @@ class NewUsers(object):
 KNN_LIST_BLOCK = 4096                    # items per launch when neighbour_lists builds the lists of the whole catalogue
 KnnLists = collections.namedtuple("KnnLists", ("ids", "scores", "votes"))
 IalsFactors = collections.namedtuple("IalsFactors", ("users", "items", "params", "objective"))
+EaseModel = collections.namedtuple("EaseModel", ("P", "l2", "pivot_min", "bytes"))
 HistorySupport = collections.namedtuple("HistorySupport", ("items", "history", "scores", "count", "mean"))
 
 
@@ -1814,6 +1815,90 @@ class EliMRec(BasicModel):
             return Neighbours(torch.empty(0, k, dtype=torch.int32), torch.empty(0, k, dtype=torch.float32))
         self._require_gpu()
         idx, val = self.ials_recommend_device(users, self.fit_ials(*params), k, (tptr, tflat))
+        return Neighbours(idx.cpu(), val.cpu())
+
+    @torch.no_grad()
+    def fit_ease(self, l2=500.0):
+        """The EASE^R baseline (Steck, WWW 2019) over the TRAINING GRAPH alone: with X the binary user x item matrix (every
+        user's list de-duplicated, as _ials_graph builds it), G = X^T X + l2 I and P = G^-1 -- EaseModel(P float64 [I x I] on the
+        device, l2, pivot_min, bytes), kept per l2 (a second call returns the kept handle). The item-item weights are B_ij =
+        -P_ij / P_jj off the diagonal; they are never formed: ease_recommend_device ranks from P. ops.gram_counts builds G (exact
+        integer counts), ops.spd_inverse inverts it in place in float64 (csrc/ease.hip); pivot_min is the smallest pivot of the
+        sweep (>= l2 up to rounding: how far G is from singular), bytes what P and the sweep's workspace took. Nothing of the
+        learned tables is read, so this works on an untrained model. l2 is the model's one hyper-parameter, an explicit
+        popularity damping; the default 500 is the commonly quoted value, not tuned here. l2 finite and > 0 and num_items <=
+        ops.EASE_MAX_ITEMS: else ValueError before anything touches the device. Single-GPU; lean tables are refused.
+        Every kept fit holds 8 I^2 bytes of device memory (46 GB at the Tiktok shape) until drop_ease releases it."""
+        l2 = ops._ease_params("fit_ease", l2, self.num_items)
+        self._no_lean("fit_ease()")
+        dev = self._require_gpu()
+        kept = self.__dict__.setdefault("_ease", {})
+        hit = kept.get(l2)
+        if hit is not None and hit.P.device == dev:
+            return hit
+        U, I = self.num_users, self.num_items
+        train = self.dataset.get_user_train_dict()
+        index = ops.CooccurIndex.from_train({u: np.unique(np.asarray(v, dtype=np.int64)) for u, v in train.items()}, U, I, "item", dev)
+        P = torch.empty(I, I, dtype=torch.float64, device=dev)
+        ops.gram_counts(index, l2, P)
+        ws = torch.empty(ops.spd_inverse_workspace(I), dtype=torch.uint8, device=dev)
+        pivot_min = ops.spd_inverse(P, ws)
+        hit = kept[l2] = EaseModel(P, l2, pivot_min, P.numel() * 8 + ws.numel())
+        return hit
+
+    def drop_ease(self, l2=None):
+        """Release the kept EASE fit of `l2` (None: every kept fit) -- 8 I^2 bytes of device memory each; a handle the caller
+        still holds keeps its tensor alive. -> the number of fits dropped."""
+        kept = self.__dict__.get("_ease", {})
+        gone = list(kept) if l2 is None else [k for k in kept if k == float(l2)]
+        for k in gone:
+            del kept[k]
+        return len(gone)
+
+    @torch.no_grad()
+    def ease_recommend_device(self, users, ease, k, hist, excl=None, out_idx=None, out_val=None):
+        """The k items with the largest EASE score -(sum_{i in H, i != j} P_ij) / P_jj of an EaseModel (fit_ease), over
+        ops.ease_topk: out_idx int32 / out_val float32 [B x k] on the device (allocated here when None), by (score descending, id
+        ascending), -1 / -inf where fewer than k items are left. users: segment ids of hist (host array or tensor, checked on the
+        host); hist: an ops.HistoryIndex with n_items = num_items, the histories; excl: a second HistoryIndex over the same
+        segments, the ids left out instead of the history (default: the history itself). 1 <= k <= 256. Single-GPU."""
+        dev = self._require_gpu()
+        if not isinstance(ease, EaseModel):
+            raise TypeError("ease must be the EaseModel fit_ease returns")
+        k = ops._form_k("ease_recommend_device", k, ops.EASE_MAX_K)
+        B = int(np.asarray(ops._host(users)).size)
+        out_idx = torch.empty(B, k, dtype=torch.int32, device=dev) if out_idx is None else out_idx
+        out_val = torch.empty(B, k, dtype=torch.float32, device=dev) if out_val is None else out_val
+        ops.ease_topk(ease.P, hist, users, k, out_idx, out_val, excl=excl)
+        return out_idx, out_val
+
+    def recommend_ease(self, user_ids, k, exclude=None, history=None, l2=500.0):
+        """The EASE baseline's lists: per user the k items with the largest score under fit_ease(l2) -- Neighbours(ids CPU int32
+        [B x k] (-1 padded), scores CPU fp32 [B x k] (-inf padded)), by (score descending, id ascending). history: dict user ->
+        item ids (default: the data set's train dict, as recommend_knn takes it); the history's own items are never listed;
+        exclude: dict user -> item ids left out on top. A user without history scores 0 everywhere: the lowest ids are listed.
+        k outside [1, 256], l2 not finite and positive or a catalogue beyond ops.EASE_MAX_ITEMS: ValueError; an id outside its
+        side: IndexError -- both before anything touches the device. An empty user_ids returns [0 x k] without a launch or a fit."""
+        k = ops._form_k("recommend_ease", k, ops.EASE_MAX_K)
+        l2 = ops._ease_params("recommend_ease", l2, self.num_items)
+        users = self._id_lists([user_ids], "user", self.num_users)[1]
+        if history is None:
+            history = self.dataset.get_user_train_dict()
+        elif not isinstance(history, dict):
+            raise TypeError("history must be a dict user -> item ids")
+        lists = [list(history.get(int(u), [])) for u in users]
+        hptr, hflat, _ = self._id_lists(lists, "history item")
+        tptr, tflat = self._excluded(exclude, users, "item")
+        n = int(users.size)
+        if not n:
+            return Neighbours(torch.empty(0, k, dtype=torch.int32), torch.empty(0, k, dtype=torch.float32))
+        dev = self._require_gpu()
+        hist = ops.HistoryIndex(hptr, hflat, dev, n_items=self.num_items)
+        excl = None
+        if tflat.size:                   # what is left out replaces the history in ease_topk: the history and the extra ids
+            eptr, eflat, _ = self._id_lists([h + list((exclude or {}).get(int(u), [])) for h, u in zip(lists, users)], "excluded item")
+            excl = ops.HistoryIndex(eptr, eflat, dev, n_items=self.num_items)
+        idx, val = self.ease_recommend_device(np.arange(n, dtype=np.int64), self.fit_ease(l2), k, hist, excl)    # row b is segment b
         return Neighbours(idx.cpu(), val.cpu())
 
     @torch.no_grad()

@@ -1136,6 +1136,10 @@ def __getattr__(name):
         return int(_lib.load().elimrec_vote_groups())
     if name == "ALS_CHUNK":              # neighbour rows one workgroup of als_solve stages in LDS at a time
         return int(_lib.load().elimrec_als_chunk())
+    if name == "EASE_BLOCK":             # block width of spd_inverse's sweep
+        return int(_lib.load().elimrec_ease_block())
+    if name == "EASE_HIST_STAGE":        # history ids one wave of ease_topk stages in LDS at a time
+        return int(_lib.load().elimrec_ease_hist_stage())
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 
@@ -2913,3 +2917,138 @@ def als_solve(index, F, A0, reg, conf, out, rows=None):
         raise ArithmeticError("elimrec_amd.ops.%s: A_r is not positive definite for %d row(s), the first is row %d (written as zeros)"
                               % (who, bad, first))
     return out
+
+
+EASE_MAX_K = 256                         # the longest list ease_topk keeps (csrc/ease.hip), known without the library
+# the largest catalogue EliMRec.fit_ease takes: 8 I^2 = 214.7 GB at I = 163 840 (2560 sweep blocks of 64), + 2 * 64 * I * 8 B = 0.17 GB
+# of sweep workspace, leaves 73 GB of a 288 GB card: the evaluator's tables ([U + I] x 256 floats: below 1 GB at such a catalogue), the
+# graph and the top-K workspace (users x ceil(I / 4096) x K x 8 B: 2.6 GB for 31 504 users at K = 256) fit many times over
+EASE_MAX_ITEMS = 163840
+
+
+def _ease_params(who, l2=500.0, num_items=None):
+    """The parameter of an EASE fit (EliMRec.fit_ease, BaselineReport, --baseline_l2), checked before anything touches the device
+    (ValueError): l2 finite and > 0; num_items (when given) at most EASE_MAX_ITEMS. -> l2 as a float."""
+    if isinstance(l2, bool) or not isinstance(l2, (int, float, np.integer, np.floating)) or not (math.isfinite(l2) and l2 > 0):
+        raise ValueError("%s: l2 must be finite and > 0, got %r" % (who, l2))
+    if num_items is not None and int(num_items) > EASE_MAX_ITEMS:
+        raise ValueError("%s: the dense item-item matrix takes 8 I^2 bytes; I <= EASE_MAX_ITEMS = %d, got %d" % (who, EASE_MAX_ITEMS, num_items))
+    return float(l2)
+
+
+def _square_f64(who, t, name, n=None):
+    """A float64 device matrix [n x >= n] with unit column stride: (pointer, ld, n)."""
+    if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.stride(1) != 1 or t.shape[1] != t.shape[0] or (n is not None and t.shape[0] != n):
+        raise ValueError("elimrec_amd.ops.%s: %s must be a 2-D square tensor%s with unit column stride"
+                         % (who, name, "" if n is None else " [%d x %d]" % (n, n)))
+    p = _dev(t, name, torch.float64)
+    n = int(t.shape[0])
+    ld = int(t.stride(0)) if n > 1 else max(n, int(t.stride(0)))
+    if ld < n:
+        raise ValueError("elimrec_amd.ops.%s: %s needs a row stride >= %d" % (who, name, n))
+    return p, ld, n
+
+
+def gram_counts(index, l2, out):
+    """elimrec_gram_counts (csrc/ease.hip): out float64 [n x n] (unit column stride, row stride >= n) <- X^T X + l2 I of the
+    bipartite graph `index` describes -- an ops.CooccurIndex whose query side are the n rows of the result (for EASE: side "item":
+    item -> its training users, user -> items). Entry (i, j) counts the walks i -> u -> j, so with lists that hold no repeated edge
+    it is the Gram matrix of the binary X; the counts are integers, the result is exact and does not depend on the launch
+    geometry. l2: a number, finite and >= 0. Every argument error is raised before the device is required. -> out."""
+    who = "gram_counts"
+    if not isinstance(index, CooccurIndex):
+        raise TypeError("elimrec_amd.ops.%s: index must be an ops.CooccurIndex, got %s" % (who, type(index).__name__))
+    if isinstance(l2, bool) or not isinstance(l2, (int, float, np.integer, np.floating)) or not (math.isfinite(l2) and l2 >= 0):
+        raise ValueError("elimrec_amd.ops.%s: l2 is finite and >= 0, got %r" % (who, l2))
+    op, ld, n = _square_f64(who, out, "out", index.n_query)
+    if out.device != index.device:
+        raise ValueError("elimrec_amd.ops.%s: out lives on %s, the index on %s" % (who, out.device, index.device))
+    if n == 0:
+        return out
+    _lib.check(_lib.load().elimrec_gram_counts(_dev(index.q_ptr, "q_ptr", torch.int64), _dev(index.q_nbr, "q_nbr", torch.int32),
+                                               _dev(index.o_ptr, "o_ptr", torch.int64), _dev(index.o_nbr, "o_nbr", torch.int32), n,
+                                               index.n_other, float(l2), op, ld, _stream()), who)
+    return out
+
+
+def spd_inverse_workspace(n):
+    """Bytes of workspace spd_inverse needs for an [n x n] matrix (host arithmetic only)."""
+    return int(_lib.load().elimrec_spd_inverse_workspace(int(n)))
+
+
+def spd_inverse(A, workspace=None):
+    """elimrec_spd_inverse (csrc/ease.hip): A float64 [n x n], n >= 1, symmetric positive definite with both triangles stored (unit
+    column stride) <- its inverse, in place, all float64: the symmetric block sweep of width 64 on v_mfma_f64_16x16x4_f64. The
+    result is exactly symmetric and its bits depend on A alone (two calls on copies agree bit for bit). workspace: a uint8 device
+    tensor of at least spd_inverse_workspace(n) bytes, 16-byte aligned; default: allocated here. -> the smallest pivot of the
+    blocks' square-root-free Cholesky factorisations (a float; read back: a synchronisation). A pivot that is <= 0 or not finite
+    raises ArithmeticError naming its index; A is then left half swept. Every argument error is raised before the device is
+    required."""
+    who = "spd_inverse"
+    if isinstance(A, torch.Tensor) and A.dim() == 2 and A.shape[0] == A.shape[1] == 0:
+        raise ValueError("elimrec_amd.ops.%s: A needs n >= 1 rows" % who)
+    ap, ld, n = _square_f64(who, A, "A")
+    lib = _lib.load()
+    need = int(lib.elimrec_spd_inverse_workspace(n))
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=A.device)
+    wp = _dev(workspace, "workspace", torch.uint8)
+    if workspace.numel() < need or not workspace.is_contiguous() or wp % 16 or workspace.device != A.device:
+        raise ValueError("elimrec_amd.ops.%s: the workspace needs %d contiguous bytes on A's device, 16-byte aligned (got %d)"
+                         % (who, need, workspace.numel()))
+    pivot = torch.empty(1, dtype=torch.float64, device=A.device)
+    status = torch.empty(2, dtype=torch.int32, device=A.device)
+    _lib.check(lib.elimrec_spd_inverse(ap, n, ld, pivot.data_ptr(), status.data_ptr(), wp, workspace.numel(), _stream()), who)
+    bad, first = (int(x) for x in status.cpu())
+    if bad:
+        raise ArithmeticError("elimrec_amd.ops.%s: the matrix is not positive definite: the pivot at index %d is <= 0 or not finite "
+                              "(A is left half swept)" % (who, first))
+    return float(pivot.item())
+
+
+_EaseQuery = collections.namedtuple("_EaseQuery", ("n_queries",))
+
+
+def ease_topk_workspace(Q, n, K):
+    """Bytes of workspace ease_topk needs (host arithmetic only)."""
+    return int(_lib.load().elimrec_ease_topk_workspace(int(Q), int(n), int(K)))
+
+
+def ease_topk(P, hist, users, K, out_idx, out_val=None, excl=None, workspace=None):
+    """elimrec_ease_topk (csrc/ease.hip): per user the K items j with the largest EASE score
+        s_j = float32(-(sum_{i in H, i != j} P[i, j]) / P[j, j]),
+    the sum in float64 in the order of the user's history H, by (score descending, id ascending). P float64 [I x I] with unit
+    column stride: G^-1 of an EASE fit, or any table with a non-zero diagonal. hist: an ops.HistoryIndex built with n_items = I;
+    users: host array or tensor of its segment ids, checked on the host (IndexError), a repeated id is a row of its own. excl: a
+    second HistoryIndex over the same segments, the ids left out INSTEAD of the history (so an item of the history can be listed:
+    the sum then skips it); default: the history itself is left out. out_idx int32 / out_val float32 (optional) [B x K] on P's
+    device, -1 / -inf where fewer than K items are left. An empty history scores 0 everywhere: the lowest ids that are not left
+    out. No [B x I] block is written; grid, K-lists, workspace (ease_topk_workspace bytes) and merge as cosine_topk. Every argument
+    error is raised before the device is required. 1 <= K <= 256. An empty `users` returns without a launch."""
+    who = "ease_topk"
+    K = int(K)
+    if not 1 <= K <= EASE_MAX_K:
+        raise ValueError("elimrec_amd.ops.%s: 1 <= K <= %d, got %d" % (who, EASE_MAX_K, K))
+    if not isinstance(P, torch.Tensor) or P.dim() != 2 or P.stride(1) != 1 or P.shape[0] != P.shape[1]:
+        raise ValueError("elimrec_amd.ops.%s: P must be a 2-D square tensor with unit column stride" % who)
+    n = int(P.shape[0])
+    for h, name in ((hist, "hist"), (excl, "excl")):
+        if h is None and name == "excl":
+            continue
+        if not isinstance(h, HistoryIndex):
+            raise TypeError("elimrec_amd.ops.%s: %s must be an ops.HistoryIndex%s, got %s"
+                            % (who, name, " or None" if name == "excl" else "", type(h).__name__))
+        if h.n_items is None or h.n_items > n:
+            raise IndexError("elimrec_amd.ops.%s: %s must be checked against the catalogue (n_items <= %d), got %r" % (who, name, n, h.n_items))
+    if excl is not None and excl.n_rows != hist.n_rows:
+        raise ValueError("elimrec_amd.ops.%s: hist and excl name the same users: %d and %d segments" % (who, hist.n_rows, excl.n_rows))
+    u = _checked_ids(users, hist.n_rows, who, "users", "users span [%d, %d], the histories have %d segments")
+    pp, ld, n = _square_f64(who, P, "P")
+    dev = P.device
+    if hist.ptr.device != dev or (excl is not None and excl.ptr.device != dev):
+        raise ValueError("elimrec_amd.ops.%s: P lives on %s, the histories on %s" % (who, dev, hist.ptr.device))
+    up = torch.from_numpy(np.ascontiguousarray(u if u.size else np.zeros(1), dtype=np.int64)).to(dev)
+    ep, ei = (None, None) if excl is None else (_dev(excl.ptr, "excl_ptr", torch.int64), _dev(excl.items, "excl_items", torch.int32))
+    return _topk_call(who, n, _EaseQuery(int(u.size)), K, out_idx, out_val, workspace, dev, dev, lambda: (
+        pp, ld, n, _dev(hist.ptr, "hist_ptr", torch.int64), _dev(hist.items, "hist_items", torch.int32), ep, ei, hist.n_rows,
+        _dev(up, "users", torch.int64), int(u.size)))

@@ -1645,7 +1645,9 @@ class BaselineReport(_Report):
     "ials" = the implicit-feedback ALS factor model of EliMRec.fit_ials under factors / iters / conf / reg / reg_scale (no
     neighbour vote: its lists are the top-K of x_u . y_i, EliMRec.ials_recommend_device; `neighbours` and `measure` do not apply to it;
     the defaults are not tuned here; under the table one line gives the settings and the loss after the first and the last
-    half-sweep).
+    half-sweep); "ease" = the closed-form EASE^R item-item model of EliMRec.fit_ease under `l2` (no neighbour vote either: its lists
+    are EliMRec.ease_recommend_device's; neighbours, measure, alpha and beta do not apply to it; the default l2 = 500 is the commonly
+    quoted value, not tuned here; under the table one line gives l2, the catalogue, the bytes of P and the sweep's smallest pivot).
     metric_rows() is ops.rank_metrics over those lists with the truth CSR, metric ids and shown-column layout of
     SignificanceReport.metric_rows, so the two row blocks pair user by user (SignificanceReport.shift); a -1 filler is a miss (the
     metric kernel compares ids against a truth list of ids >= 0). evaluate() gives one row per source -- with group_view one block of
@@ -1659,18 +1661,20 @@ class BaselineReport(_Report):
     name, needs = "baseline", "knn_recommend_device"
 
     def __init__(self, dataset, user_train_dict, user_test_dict, top_k, metric=None, sources=("co",), neighbours=50, measure="cosine",
-                 group_view=None, list_k=None, alpha=1.0, beta=0.6, factors=64, iters=15, conf=1.0, reg=0.01, reg_scale=0.0):
+                 group_view=None, list_k=None, alpha=1.0, beta=0.6, factors=64, iters=15, conf=1.0, reg=0.01, reg_scale=0.0,
+                 l2=500.0):
         from .evaluator import UniEvaluator, re_metric_dict
         if not isinstance(user_train_dict, dict) or not isinstance(user_test_dict, dict):
             raise TypeError("user_train_dict and user_test_dict must be dicts")
         if isinstance(sources, str) or not len(sources) or any(not isinstance(x, str) or not x for x in sources) or len(set(sources)) != len(sources):
-            raise ValueError("sources is a sequence of distinct names: 'co', 'rp3', 'ials', 'fused' or a head letter, got %r" % (sources,))
+            raise ValueError("sources is a sequence of distinct names: 'co', 'rp3', 'ials', 'ease', 'fused' or a head letter, got %r" % (sources,))
         if isinstance(neighbours, bool) or not isinstance(neighbours, (int, np.integer)) or not 1 <= neighbours <= ops.VOTE_MAX_K:
             raise ValueError("neighbours must be an integer in [1, %d], got %r" % (ops.VOTE_MAX_K, neighbours))
         ops._cooccur_measure("BaselineReport", measure)
         self.alpha, self.beta = ops._rp3_params("BaselineReport", alpha, beta)
         self.rp3_info = None
         self.ials_params, self.ials_objective = ops._ials_params("BaselineReport", factors, iters, conf, reg, reg_scale), None
+        self.l2, self.ease_info = ops._ease_params("BaselineReport", l2, dataset.num_items if "ease" in sources else None), None
         self.evaluator = ev = UniEvaluator(dataset, user_train_dict, user_test_dict, metric=metric, top_k=top_k)
         list_k = ev.max_top if list_k is None else list_k
         if isinstance(list_k, bool) or not isinstance(list_k, (int, np.integer)) or not ev.max_top <= list_k <= ops.VOTE_MAX_K:
@@ -1710,6 +1714,8 @@ class BaselineReport(_Report):
         res = self._resident(device)
         if source == "ials":
             return self._ials_lists(model, device)
+        if source == "ease":
+            return self._ease_lists(model, device, res)
         lists = model.neighbour_lists(source, self.neighbours, self.measure, self.alpha, self.beta)
         if source == "rp3":
             self.rp3_info = (lists.scale_exp, lists.zero_votes)
@@ -1744,6 +1750,24 @@ class BaselineReport(_Report):
                 self.num_items, "item ids must lie in [0, %d)" % self.num_items), cast=int)
             model.ials_recommend_device(np.asarray(self.users[a:b], dtype=np.int64), fit, K, (ptr, flat), idx[a:b], val[:b - a])
         self._lists[("ials", str(device))] = (fit, idx)
+        return idx
+
+    def _ease_lists(self, model, device, res):
+        """knn_lists of the source "ease": the top-K of the EASE scores under EliMRec.fit_ease(self.l2) through
+        EliMRec.ease_recommend_device, in blocks of block_users, the train items as the history and left out. Kept for as long as
+        the model keeps the fit; the neighbour-vote settings do not apply."""
+        fit = model.fit_ease(self.l2)
+        self.ease_info = (fit.l2, int(fit.P.shape[0]), fit.bytes, fit.pivot_min)
+        hit = self._lists.get(("ease", str(device)))
+        if hit is not None and hit[0] is fit:
+            return hit[1]
+        n, K = len(self.users), self.k
+        idx = torch.empty(n, K, dtype=torch.int32, device=device)
+        val = torch.empty(min(n, self.block_users), K, dtype=torch.float32, device=device)
+        for a in range(0, n, self.block_users):
+            b = min(n, a + self.block_users)
+            model.ease_recommend_device(np.arange(a, b, dtype=np.int64), fit, K, res["hist"], None, idx[a:b], val[:b - a])
+        self._lists[("ease", str(device))] = (fit, idx)
         return idx
 
     def metric_rows(self, model, source):
@@ -1795,6 +1819,8 @@ class BaselineReport(_Report):
             buf += "\nrp3: alpha=%g beta=%g scale=2^%d zero_votes=%.6f" % ((self.alpha, self.beta) + self.rp3_info)
         if "ials" in self.sources:
             buf += "\nials: factors=%d iters=%d conf=%g reg=%g reg_scale=%g objective=%.8g -> %.8g" % (self.ials_params[:5] + self.ials_objective)
+        if "ease" in self.sources:
+            buf += "\nease: l2=%g items=%d bytes=%d pivot_min=%.8g" % self.ease_info
         return final, buf
 
 

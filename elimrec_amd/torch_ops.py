@@ -34,4 +34,4 @@ OPS = ("propagate", "linear_fwd", "linear_bwd_w", "bpr_head_fwd", "adam_step_", 
        "list_pair_cosine", "list_exposure", "mmr_rerank", "pick_hard_negatives", "history_support", "bootstrap_means",
        "bootstrap_diff_means", "calibrate_rerank", "list_calibration", "kmeans_assign", "kmeans_update", "uniformity_sum",
        "row_gram", "cooccur_topk", "neighbour_vote_topk", "rank_values", "segment_row_sum", "cross_topk",
-       "als_solve")
+       "als_solve", "gram_counts", "spd_inverse", "ease_topk")

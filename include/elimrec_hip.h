@@ -954,6 +954,41 @@ int elimrec_als_solve(const float *d_F, int64_t ld, int64_t n_fixed, int d, cons
                       float *d_out, int64_t ld_out, int32_t *d_status, void *stream);
 int elimrec_als_chunk(void);
 
+/* EASE^R (csrc/ease.hip; Steck, WWW 2019): G = X^T X + l2 I, P = G^-1, score_j(H) = -(sum_{i in H, i != j} P_ij) / P_jj. No
+ * counterpart in the reference.
+ * elimrec_gram_counts: d_out float64 [n x ld], ld >= n, row i <- the number of walks i -> u -> j over the two CSRs of one
+ * bipartite graph (d_q_ptr int64 [n + 1] / d_q_nbr: row -> its neighbours on the other side of n_other rows; d_o_ptr int64
+ * [n_other + 1] / d_o_nbr: back), + l2 on the diagonal: with lists that hold no repeated edge X^T X + l2 I of the binary X. THE
+ * CALLER guarantees both pointers ascending from 0 and ids inside their sides (the Python wrappers check); an id outside is
+ * skipped. One workgroup per row, 64-bit integer atomics into the row itself, converted in place: exact, the same bits for any
+ * geometry. l2 finite and >= 0. */
+int elimrec_gram_counts(const int64_t *d_q_ptr, const int32_t *d_q_nbr, const int64_t *d_o_ptr, const int32_t *d_o_nbr, int64_t n,
+                        int64_t n_other, double l2, double *d_out, int64_t ld, void *stream);
+/* elimrec_spd_inverse: d_A float64 [n x ld] symmetric positive definite (both triangles stored; the upper one is read) <- its
+ * inverse, in place, exactly symmetric, all float64: the symmetric block sweep of width elimrec_ease_block() = 64, 3 launches per
+ * pivot block on `stream`, no host synchronisation. An element's bits depend on A and the block width alone. *d_pivot_min <- the
+ * smallest pivot of the blocks' square-root-free Cholesky factorisations; a pivot <= 0 or not finite adds 1 to d_status[0], lowers
+ * d_status[1] to its index and ends the sweep (A is left half swept) -- both words are initialised here ({0, INT32_MAX}, +inf)
+ * and read by THE CALLER afterwards. d_workspace: elimrec_spd_inverse_workspace(n) bytes, 16-byte aligned. Nothing outside A and
+ * the workspace is read or written for any n >= 1; n = 0 only initialises the two words. */
+int elimrec_spd_inverse(double *d_A, int64_t n, int64_t ld, double *d_pivot_min, int32_t *d_status, void *d_workspace,
+                        size_t workspace_bytes, void *stream);
+size_t elimrec_spd_inverse_workspace(int64_t n);
+int elimrec_ease_block(void);
+/* elimrec_ease_topk: per query b (segment d_users[b] of the history CSR d_hist_ptr int64 [n_seg + 1] / d_hist_items) the K
+ * columns j of d_P (float64 [n x ld]; any table with a non-zero diagonal) with the largest
+ *     score_j = float(-(sum_{i in H, i != j} P_ij) / P_jj),
+ * the sum in float64 in the history's order, by (score descending, id ascending); d_idx int32 / d_val float32 (may be NULL)
+ * [Q x K], -1 / -inf behind them. Left out: the segment of d_excl_ptr / d_excl_items (a CSR over the same n_seg segments), or,
+ * with both NULL, the history itself. A history id outside [0, n) adds nothing, a segment id outside [0, n_seg) gives fillers.
+ * Grid, K-lists, workspace (elimrec_ease_topk_workspace bytes, 16-byte aligned) and merge as elimrec_cosine_topk; history ids
+ * pass through an LDS stage of elimrec_ease_hist_stage() ids. 1 <= K <= 256. No [Q x n] block is written. */
+int elimrec_ease_topk(const double *d_P, int64_t ld, int64_t n, const int64_t *d_hist_ptr, const int32_t *d_hist_items,
+                      const int64_t *d_excl_ptr, const int32_t *d_excl_items, int64_t n_seg, const int64_t *d_users, int64_t Q,
+                      int K, int32_t *d_idx, float *d_val, void *d_workspace, size_t workspace_bytes, void *stream);
+size_t elimrec_ease_topk_workspace(int64_t Q, int64_t n, int K);
+int elimrec_ease_hist_stage(void);
+
 /* Hard-negative pick (csrc/hardneg.hip): per triplet the best of M candidate items under the current tables. No counterpart in
  * the reference. d_U / d_T point at row 0, column 0 of an [n_users x blocks * d] / [n_items x blocks * d] slice of a row-major
  * float32 matrix with row stride ld_u / ld_i >= blocks * d, block b = columns [b * d, (b + 1) * d); d_sq_u[r * ldsq_u + b] /

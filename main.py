@@ -162,7 +162,8 @@ class Net(object):
         # (--significance_level) of every shown metric over R resamples of the test users, overall and per user group; after both
         # effects the paired TE -> TIE difference with its two-sided p-value. It needs metric rows only (run on one GPU only so far)
         self.significance_report = int(cfg["significance_report"]) if "significance_report" in cfg else 0
-        # --baseline_report=K (default 0: off), --baseline_sources=[co,rp3,ials,fused,v,...], --baseline_neighbours=50, --baseline_measure,
+        # --baseline_report=K (default 0: off), --baseline_sources=[co,rp3,ials,ease,fused,v,...], --baseline_l2=500.0 (EASE's one
+        # hyper-parameter, source ease), --baseline_neighbours=50, --baseline_measure,
         # --baseline_alpha=1.0, --baseline_beta=0.6 (RP3beta's exponents, source rp3): under each [TEST] line a [baselines] table --
         # neighbour-vote recommenders (ItemKNN and RP3beta over the training graph, content-KNN in a space of the tables; under the
         # table one "rp3:" line with the exponents, the lists' power-of-two scale and the share of votes the fixed point loses) on the same split; only `overlap` (with the model's own lists) differs between the effects. With
